@@ -1,7 +1,11 @@
 """bench.py -- one "step" = one pass of the X-MAP hot path (item-item similarity -> cross-domain
 extension -> AlterEgo generation) over synthetic Amazon-format ratings already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints its line.  --full adds what takes runs of its own: the CPU
+baselines (the oracle timed on this host) and, in the default c2 line, three steps each of the recsim and dense workloads
+(`other_workloads`).  --dump-outputs DIR writes what the last timed step returned as float64 .npy files (dump_outputs).
 
 N > 1: one rank per GPU over RCCL.  Under a launcher (torch.distributed.run sets RANK / WORLD_SIZE / LOCAL_RANK) every
 process is a rank; WITHOUT one, `python bench.py --gpus N` starts the N ranks itself -- the parent touches no GPU, runs
@@ -214,7 +218,7 @@ def bench_dense(args, rank, world, local, dist, sink=None):
                "roofline": {"bound": "mfma", "kernel": "k_dense_topk", "achieved": ach, "peak": MFMA_F32_PEAK_TF,
                             "unit": "TFLOP/s", "frac": ach / MFMA_F32_PEAK_TF, "traffic": pmc_traffic("k_dense_topk"),
                             "algorithmic_flop_per_launch": flop, "launch_ms": ms}}
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             from oracle import xmap_oracle as xo
             rows, threads = 64, 4
             a, b = xo.dense_normalize(Ft[:rows].cpu().numpy()), xo.dense_normalize(Fs.cpu().numpy())
@@ -344,7 +348,7 @@ def bench_recsim(args, rank, world, local, dist, sink=None):
            "kernel_ms": {n: float(np.mean(v)) for n, v in sorted(tm.items())},
            "roofline": {"bound": "hbm", "kernel": "k_pair_tri<LS>", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": ach / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes_per_launch": bytes_tri, "launch_ms": tri_ms}}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle import xmap_oracle as xo
         users = min(len(uu), 500000)           # bounded sample: the first users' rows (a closed sub-problem)
         t0 = time.time()
@@ -463,6 +467,53 @@ def bench_api(args, rank, world, local, dist):
           "setup_s": setup})
 
 
+DUMP_SEED = 20240611
+DUMP_LIMIT = 64 << 20       # bytes of .npy payload at most
+
+
+def dump_outputs(out_dir, res, n_items):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 .npy files (~45 MB at configs[1]) -- the
+    item-item similarity lists (stage A), the candidate counts and best XMAP_TOPC candidates per start (stage B), the
+    replacement choice and map (stage C), the AlterEgo rows and the step's counts.  The order the kernels leave open (the
+    columns within a similarity row, the ends within a start's best list) is made canonical; the large outputs are cut to
+    a fixed, seeded sample (whole similarity rows, starts, AlterEgo rows), so that two builds are compared position for
+    position."""
+    I = int(n_items)
+    S, E, G = res["S"], res["E"], res["G"]
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {}
+    # stage A: the rows of a random order of the items, while there are at most 2^20 entries and 4096 rows
+    row_ptr = S.row_ptr[:I + 1].cpu().numpy().astype(np.int64)
+    cnt = np.diff(row_ptr)
+    order = rng.permutation(I)
+    rows = np.sort(order[:np.searchsorted(np.cumsum(cnt[order]), 1 << 20, side="right")][:4096])
+    idx = np.concatenate([np.arange(row_ptr[i], row_ptr[i + 1]) for i in rows] + [np.zeros(0, np.int64)])
+    it = torch.from_numpy(idx).to(S.col.device)
+    col, sim = S.col[it].cpu().numpy(), S.sim[it].cpu().numpy()
+    o = np.lexsort((col, np.repeat(np.arange(len(rows)), cnt[rows])))
+    out.update(sim_rows=rows, sim_row_len=cnt[rows], sim_col=col[o], sim_val=sim[o])
+    # stage B: candidate counts of every start; the best candidates of 16384 starts, ends ascending (-1: empty slot)
+    starts = np.sort(rng.choice(I, min(I, 16384), replace=False))
+    st = torch.from_numpy(starts).to(E.top_end.device)
+    te, tv = E.top_end[st].cpu().numpy(), E.top_val[st].cpu().numpy()
+    o = np.argsort(te, axis=1, kind="stable")
+    out.update(ext_n_cand=E.n_cand[:I].cpu().numpy(), ext_starts=starts,
+               ext_top_end=np.take_along_axis(te, o, 1), ext_top_val=np.take_along_axis(tv, o, 1))
+    # stage C: the replacement of every item, and 2^20 of the AlterEgo rows (in the engine's own row order)
+    out.update(choice=res["choice"][:I].cpu().numpy(), map=res["map"][:I].cpu().numpy())
+    pos = np.sort(rng.choice(G.n_rows, min(G.n_rows, 1 << 20), replace=False))
+    p = torch.from_numpy(pos).to(G.user.device)
+    out.update(alterego_user=G.user[p].cpu().numpy(), alterego_item=G.item[p].cpu().numpy(), alterego_rating=G.rating[p].cpu().numpy())
+    out["counts"] = np.array([res[n] for n in ("n_eval", "n_kept", "n_paths", "n_out", "n_rows", "n_profiles")])
+    out = {n: np.ascontiguousarray(a, np.float64) for n, a in out.items()}      # indices < 2^53: exact
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in out.items():
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+    log("dump: %d arrays, %.1f MB -> %s" % (len(out), total / 1e6, out_dir))
+
+
 def launcher_argv(n_ranks, port, argv):
     """the command `bench.py --gpus N` runs when no launcher started it: N ranks of this script on this node"""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n_ranks),
@@ -529,10 +580,18 @@ def main():
     ap.add_argument("--api", action="store_true")        # configs[1] through the pipeline API of the drop-in package (one GPU)
     ap.add_argument("--feed", action="store_true")       # --api: the train set through the native feeder (text -> CSR in C++)
     ap.add_argument("--no-extra", action="store_true")   # default c2 run at N = 1: skip the short recsim / dense lines
+    ap.add_argument("--full", action="store_true")       # + the CPU baselines and (c2, N = 1) the recsim / dense side lines
+    ap.add_argument("--dump-outputs", metavar="DIR")     # what the last timed step returned, as float64 .npy (dump_outputs)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.api or args.workload in ("recsim", "c4", "dense")):
+        ap.error("--dump-outputs: the default path only (workloads c2, c1, s1)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and max(args.gpus, world) > 1:      # (a rank of N holds its share of the lists only)
+        ap.error("--dump-outputs: one GPU only")
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("XMAP_DIST_BACKEND", "nccl") != "nccl":
         local = local % max(torch.cuda.device_count(), 1)
@@ -624,6 +683,8 @@ def main():
     wall = time.time() - t_start
     tm = eng.timer_ms()
     eng.timers = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, r.n_items)
     if os.environ.get("XMAP_BENCH_DUMP") == "1" and rank == 0:      # per-step values of every bracket (diagnosis)
         for n_, v_ in sorted(tm.items()):
             log("timer %-14s %s" % (n_, " ".join("%.3f" % x for x in v_)))
@@ -737,11 +798,11 @@ def main():
                                                    "achieved": bytes_a / t_a / 1e9 if t_a > 0 else 0.0,
                                                    "frac": bytes_a / t_a / 1e9 / HBM_PEAK_GBS if t_a > 0 else 0.0}},
         }
-        if not args.no_cpu and world == 1:      # the CPU baseline is timed at N = 1 only
+        if args.full and not args.no_cpu and world == 1:      # the CPU baseline is timed at N = 1 only
             out["cpu_baseline"] = cpu_baseline(r, attrs, args.method, k=k)
-        if world == 1 and args.workload == "c2" and not args.no_extra:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_extra:
             # the two other full-size workloads (`--workload recsim`, `--workload dense`), three steps each, so that every
-            # run of the default command records them; their full lines (with cpu_baseline) come from their own flags
+            # --full run of the default command records them; their full lines (with cpu_baseline) come from their own flags
             res = None
             eng._scratch.clear()            # 26 GB of accumulator rows
             torch.cuda.empty_cache()
