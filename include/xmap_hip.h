@@ -34,6 +34,11 @@ extern "C" {
 
 #define XMAP_COSINE 0         /* BaselinerSim.method == "cosine"        (core/baselinerSim.py:213) */
 #define XMAP_ADJUST_COSINE 1  /* BaselinerSim.method == "adjust_cosine" (core/baselinerSim.py:215) */
+/* "cosine" for ratings whose plain fp64 sums may round (fractional ratings): the pair entry points
+ * (xmap_sim2_pairs, xmap_sim2_merge_partials, xmap_sim_count / xmap_sim_fill) sum the dot product as a double-double,
+ * like XMAP_ADJUST_COSINE with a zero user average and the plain norms, so the result is the exact sum rounded once
+ * whatever the order of the raters.  For ratings where the predicate holds both codes give the same bits. */
+#define XMAP_COSINE_EXACT 2
 
 #define XMAP_TOPC 10          /* candidates kept per start item: generator.py:85 keeps 10, :109 keeps 4 */
 
@@ -246,9 +251,9 @@ int xmap_sim3_mirror(void *stream, int32_t n_items, int64_t coo_cap, const int32
 
 /* User-sharded input (BASELINE configs[2]: "reduce-scatter of cross-shard partial similarities"): a rank
  * holds the complete profiles of a share of the USERS.  Per item its share of get_universal_item_info's sums
- * (core/baselinerSim.py:56-82) is xmap_item_partials -> [I][5] = (sum r, sum r^2, sum (r - avg_u)^2 as an exact (value, error)
- * pair, raters); the shares of all ranks, gathered as [n_parts][I][5], are added up and finished by xmap_item_merge
- * (rank order; exact for the adjusted norm and for integer-valued ratings).  xmap_sim2_pairs with phases bit 32 ("raw": no
+ * (core/baselinerSim.py:56-82) is xmap_item_partials -> [I][7] = (sum r, sum r^2, sum (r - avg_u)^2, each as an exact (value,
+ * error) pair, raters); the shares of all ranks, gathered as [n_parts][I][7], are added up exactly and finished by
+ * xmap_item_merge.  xmap_sim2_pairs with phases bit 32 ("raw": no
  * heavy set, coo_ls != NULL) then emits, for every pair two of the rank's users co-rated, the partial sums of
  * calculate_cosine_sim / calculate_adjusted_cosine_sim (:115-174) and retrieve_path_info (:97-113) unfinished and unfiltered:
  * coo_sim / coo_ls = the dot product as an exact (value, error) pair, coo_nij, coo_mutu.  xmap_sim2_pack_partials turns
@@ -266,8 +271,8 @@ int xmap_sim2_pack_pairs(void *stream, int64_t n_coo, const int32_t *coo_i, cons
                          const int32_t *coo_mutu, const int32_t *coo_nij, int64_t *rec /*[n_coo][3]*/, int64_t *h_count);
 int xmap_sim2_unpack_pairs(void *stream, int64_t n, const int64_t *rec /*[n][3]*/, int32_t *coo_i, int32_t *coo_j, double *coo_sim,
                            int32_t *coo_mutu, int32_t *coo_nij);
-int xmap_item_partials(void *stream, const xmap_ratings *R, const double *u_avg, double *partial /*[I][5]*/);
-int xmap_item_merge(void *stream, int32_t n_items, int32_t n_parts, const double *parts /*[n_parts][I][5]*/, double *info /*[I][4]*/,
+int xmap_item_partials(void *stream, const xmap_ratings *R, const double *u_avg, double *partial /*[I][7]*/);
+int xmap_item_merge(void *stream, int32_t n_items, int32_t n_parts, const double *parts /*[n_parts][I][7]*/, double *info /*[I][4]*/,
                     double *norms /*[2][I]*/);
 int xmap_sim2_pack_partials(void *stream, int64_t n_coo, const int32_t *coo_i, const int32_t *coo_j, const double *coo_hi,
                             const double *coo_lo, const int32_t *coo_mutu, const int32_t *coo_nij, int64_t *rec /*[n_coo][4]*/,

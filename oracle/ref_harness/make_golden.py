@@ -101,6 +101,13 @@ def case_multilabel():
     return [(u, [((i[:-2] + "S:1:") if i.endswith("S:") else i, r, t) for (i, r, t) in prof]) for (u, prof) in recs]
 
 
+def case_fractional():
+    """The structure of `small` with non-integer ratings (each a float32 value, what the engine stores): fp64 sums of
+    these round, so only an order-independent (exact) sum reproduces the same bits in every order of the raters."""
+    r = synth.fractional(synth.make_two_domain(4, 400, 150, 150, overlap=0.3), seed=5)
+    return r.train_records()
+
+
 CASES = {
     "kat7": (case_kat7, dict(ks=[2], seeds=[7])),
     "tiny": (lambda: case_synth(3, 60, 30, 30, overlap=0.5), dict(ks=[2, 5], seeds=[5])),
@@ -108,6 +115,7 @@ CASES = {
     "medium": (lambda: case_synth(5, 1500, 400, 400, overlap=0.25), dict(ks=[2, 5], seeds=[5])),
     "mixed": (case_mixed_prefix, dict(ks=[3], seeds=[5])),
     "multilabel": (case_multilabel, dict(ks=[4], seeds=[5])),
+    "fractional": (case_fractional, dict(ks=[2, 5], seeds=[5])),
 }
 
 

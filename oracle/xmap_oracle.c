@@ -85,22 +85,22 @@ void xo_user_info(int64_t U, const int64_t *ptr, const float *rating, double *av
 
 /* A3: core/baselinerSim.py:40-82  get_universal_item_info
  *   combineByKey in trainRDD order (one partition): (sum r, sum r**2, sum (r-avg_u)**2, n)
- *   -> (1.0*sum/n, sqrt(sum r**2), sqrt(sum (r-avg_u)**2), 1.0*n).  `**2` is C pow(); the third sum
- *   is accumulated error-free (order-independent canonical value). */
+ *   -> (1.0*sum/n, sqrt(sum r**2), sqrt(sum (r-avg_u)**2), 1.0*n).  `**2` is C pow().  Canonical value: each
+ *   of the three sums is accumulated error-free (dd_add) and rounded once, so it does not depend on the order of
+ *   the raters.  The reference's left-to-right sums give the same bits for integer ratings (every partial sum is
+ *   exact) and differ by a few ulp at most for fractional ones. */
 void xo_item_info(int64_t U, int32_t I, const int64_t *ptr, const int32_t *item, const float *rating,
                   const double *uavg, double *info /* [I][4] */) {
     double *acc = (double *)calloc((size_t)I * 4, sizeof(double));
-    double *lo = (double *)calloc((size_t)I, sizeof(double));
+    double *lo = (double *)calloc((size_t)I * 3, sizeof(double));   /* error terms of the three sums */
     for (int64_t u = 0; u < U; u++)
         for (int64_t e = ptr[u]; e < ptr[u + 1]; e++) {
             double r = (double)rating[e];
-            double *x = acc + (size_t)item[e] * 4;
+            double *x = acc + (size_t)item[e] * 4, *l = lo + (size_t)item[e] * 3;
             double d = r - uavg[u];
-            x[0] += r;
-            x[1] += pow(r, 2.0);
-            /* canonical value: exact sum of the fp64 squares (see dd_add); the reference's
-             * left-to-right sum of pow(d, 2) differs from it by a few ulp at most */
-            dd_add(&x[2], &lo[item[e]], d * d);
+            dd_add(&x[0], &l[0], r);
+            dd_add(&x[1], &l[1], pow(r, 2.0));
+            dd_add(&x[2], &l[2], d * d);
             x[3] += 1.0;
         }
     free(lo);
@@ -152,7 +152,7 @@ static int cmp_i32(const void *a, const void *b) {
  * Row-wise restatement: for item i, walk its raters in trainRDD order (that is the
  * order reduceByKey concatenates the co-rater triples in, one partition), collect the
  * per-pair term lists, then apply exactly the reference's reductions:
- *   cosine : python sum() left to right of 1.0*r_i*r_j                        (:126-131)
+ *   cosine : python sum() of 1.0*r_i*r_j  -> exact sum of the same fp64 terms, rounded once   (:126-131)
  *   adjust : np.sum((rx-avg)*(ry-avg))  -> exact sum of the same fp64 terms, rounded once (:156-164)
  *   sim    = (cos * min(n,cap)) / cap, cos = dot/(norm_i*norm_j) if (norm_i*norm_j) else 0.0   (:84-95)
  *   mutu   = #{(r_i>=avg_i & r_j>=avg_j) | (r_i<avg_i & r_j<avg_j)}            (:97-113)
@@ -250,20 +250,16 @@ XoSim *xo_item_sim(int method, int cap, int64_t U, int32_t I, const int64_t *ptr
                 int32_t n = cnt[j];
                 const double *terms = grouped + off;
                 off += n;
-                double dot;
-                if (method == XO_COSINE) {
-                    dot = 0.0;
-                    for (int32_t k = 0; k < n; k++) dot += terms[k];
-                } else {
-                    /* canonical value: the correctly rounded EXACT sum of the fp64 terms (error-free
-                     * double-double accumulation).  The reference's np.sum rounds in pairwise order of a
-                     * co-rater list whose order depends on Spark partitioning; the exact sum is the
-                     * order-independent value both oracle and HIP path adopt (differs from np.sum by
-                     * <= 1e-13 relative on the golden vectors, every discrete output identical). */
-                    double hi = 0.0, lo = 0.0;
-                    for (int32_t k = 0; k < n; k++) dd_add(&hi, &lo, terms[k]);
-                    dot = hi;
-                }
+                /* canonical value, both methods: the EXACT sum of the fp64 terms (error-free double-double
+                 * accumulation), rounded once.  The reference's sums (python sum() left to right for cosine,
+                 * np.sum's pairwise order for adjusted cosine) run over a co-rater list whose order depends on
+                 * Spark partitioning; the exact sum is the order-independent value both oracle and HIP path adopt.
+                 * For integer ratings the cosine terms are integers and every order gives these bits; otherwise
+                 * it differs from the reference by a few ulp (<= 1e-13 relative on the golden vectors, every
+                 * discrete output identical). */
+                double hi = 0.0, lo = 0.0;
+                for (int32_t k = 0; k < n; k++) dd_add(&hi, &lo, terms[k]);
+                double dot = hi;
                 int c1 = (method == XO_COSINE) ? 1 : 2;
                 double np_ = info[(size_t)i * 4 + c1] * info[(size_t)j * 4 + c1];
                 double cs = np_ ? 1.0 * dot / np_ : 0.0;

@@ -7,7 +7,11 @@ import numpy as np
 from xmap.engine import ids as xids
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = ["kat7", "tiny", "mixed", "multilabel", "small", "medium"]
+CASES = ["kat7", "tiny", "mixed", "multilabel", "small", "medium", "fractional"]
+# cases with non-integer ratings: the reference's left-to-right fp64 sums (item sums, cosine dot) round there, the
+# canonical value is the exact sum rounded once -- sums to FRACTIONAL_RTOL, every discrete output still exact
+FRACTIONAL = {"fractional"}
+FRACTIONAL_RTOL = 1e-13
 METHODS = ["cosine", "adjust_cosine"]
 CAP = 50
 

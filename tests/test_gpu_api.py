@@ -25,7 +25,7 @@ def records(gold):
 
 
 @pytest.mark.parametrize("method", METHODS)
-@pytest.mark.parametrize("case", ["kat7", "small", "mixed", "multilabel"])
+@pytest.mark.parametrize("case", ["kat7", "small", "mixed", "multilabel", "fractional"])
 def test_three_pipelines(case, method):
     import torch
     assert torch.cuda.is_available()

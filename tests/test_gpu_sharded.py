@@ -51,9 +51,17 @@ def _summary(res):
                 ae_user=G.user.cpu().numpy(), ae_item=G.item.cpu().numpy(), ae_rating=G.rating.cpu().numpy())
 
 
-def _engine(dev="cuda:0"):
-    from xmap.engine import synth, device
+def _ratings(frac=False):
+    """the input of these tests; frac: the same structure with non-integer ratings (synth.fractional, seeded: every
+    spawned worker rebuilds the same input)"""
+    from xmap.engine import synth
     r = synth.make_two_domain(21, 4000, 700, 700)
+    return synth.fractional(r, seed=21) if frac else r
+
+
+def _engine(dev="cuda:0", frac=False):
+    from xmap.engine import device
+    r = _ratings(frac)
     return device.Engine(device.DeviceRatings(r.user_ptr, r.item, r.rating, r.time, r.n_items, r.item_attrs(), dev))
 
 
@@ -81,10 +89,10 @@ def _rccl_world():
     return n
 
 
-def _worker(rank, world, port, q, backend="gloo"):
+def _worker(rank, world, port, q, backend="gloo", method="adjust_cosine", frac=False):
     dist, dev = _init(rank, world, port, backend)
     from xmap.engine import sharded
-    res = sharded.run_step(_engine(dev), "adjust_cosine", 50, 5, True, dist, rank, world)
+    res = sharded.run_step(_engine(dev, frac), method, 50, 5, True, dist, rank, world)
     q.put((rank, _summary(res)))
     dist.barrier()
     dist.destroy_process_group()
@@ -131,16 +139,16 @@ def test_world2_equals_world1(world):
     _check_world_equals_world1(world, "gloo")
 
 
-def _check_world_equals_world1(world, backend):
+def _check_world_equals_world1(world, backend, method="adjust_cosine", frac=False):
     import torch
     import torch.multiprocessing as mp
     assert torch.cuda.is_available()
     from xmap.engine import sharded
-    ref = _summary(sharded.run_step(_engine(), "adjust_cosine", 50, 5, True))
+    ref = _summary(sharded.run_step(_engine(frac=frac), method, 50, 5, True))
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q, backend)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, backend, method, frac)) for r in range(world)]
     for p in procs:
         p.start()
     got = _collect(q, procs, world)
@@ -228,10 +236,10 @@ def _check_multidomain(world, backend):
             assert np.array_equal(out[key], v), (rank, key)
 
 
-def _user_share(rank, world, dev="cuda:0"):
+def _user_share(rank, world, dev="cuda:0", frac=False):
     """the complete profiles of a contiguous share of the users (items indexed globally)"""
-    from xmap.engine import synth, device
-    r = synth.make_two_domain(21, 4000, 700, 700)
+    from xmap.engine import device
+    r = _ratings(frac)
     lo, hi = r.n_users * rank // world, r.n_users * (rank + 1) // world
     e0, e1 = int(r.user_ptr[lo]), int(r.user_ptr[hi])
     ptr = (r.user_ptr[lo:hi + 1] - r.user_ptr[lo]).astype(np.int64)
@@ -239,10 +247,10 @@ def _user_share(rank, world, dev="cuda:0"):
     return device.Engine(R), lo
 
 
-def _users_worker(rank, world, port, method, q, backend="gloo"):
+def _users_worker(rank, world, port, method, q, backend="gloo", frac=False):
     dist, dev = _init(rank, world, port, backend)
     from xmap.engine import sharded
-    eng, lo = _user_share(rank, world, dev)
+    eng, lo = _user_share(rank, world, dev, frac)
     res = sharded.run_step_users(eng, lo, method, 50, 5, True, dist)
     out = _summary(res)
     out["info"] = res["info"].cpu().numpy()
@@ -265,18 +273,18 @@ def test_user_sharded_equals_world1(world, method):
     _check_user_sharded(world, method, "gloo")
 
 
-def _check_user_sharded(world, method, backend):
+def _check_user_sharded(world, method, backend, frac=False):
     import torch
     import torch.multiprocessing as mp
     assert torch.cuda.is_available()
     from xmap.engine import sharded
-    one = sharded.run_step(_engine(), method, 50, 5, True)
+    one = sharded.run_step(_engine(frac=frac), method, 50, 5, True)
     ref = _summary(one)
     ref["info"] = one["S"].info.cpu().numpy()
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_users_worker, args=(r, world, port, method, q, backend)) for r in range(world)]
+    procs = [ctx.Process(target=_users_worker, args=(r, world, port, method, q, backend, frac)) for r in range(world)]
     for p in procs:
         p.start()
     got = _collect(q, procs, world)

@@ -8,6 +8,7 @@
 //
 // Everything below is orchestration of the kernels' own entry points (include/xmap_hip.h): buffer sizes, prefix sums,
 // overflow retries and unit planning that xmap/engine/device.py does for the Python host.  No torch, no other library.
+#include <math.h>
 #include <stdlib.h>
 #include <vector>
 
@@ -34,6 +35,7 @@ struct xmap_ctx {
     // ratings
     xmap_ratings R;
     bool have_ratings = false;
+    bool plain_exact = true;        // cosine may use the plain fp64 sums (plain_sums_exact)
     // stage A
     bool have_sim = false;
     xmap_sim S;
@@ -190,6 +192,29 @@ void xmap_ctx_destroy(xmap_ctx *c) {
     delete c;
 }
 
+// The plain fp64 sums of cosine mode (an item's sums of r and r^2, a pair's dot product) are exact in any order when every
+// rating is a multiple of 2^-e and U M^2 2^2e <= 2^53 (M = max |r|, U = users: no sum has more terms).  Otherwise cosine
+// runs as XMAP_COSINE_EXACT; XMAP_EXACT_COSINE=1 in the environment forces that route.  (xmap/engine/exactness.py is the
+// same rule for the Python host.)
+static bool plain_sums_exact(int64_t U, int64_t nnz, const float *rating) {
+    const char *force = getenv("XMAP_EXACT_COSINE");
+    if (force && force[0] == '1') return false;
+    double M = 0.0;
+    int e = 0;
+    for (int64_t k = 0; k < nnz; k++) {
+        const double r = fabs((double)rating[k]);
+        if (!(r <= 1e300)) return false;                   // inf, nan
+        if (r > M) M = r;
+        while (e <= 26 && ldexp(r, e) != floor(ldexp(r, e))) e++;
+        if (e > 26) return false;
+    }
+    if (M == 0.0) return true;
+    const double Mi = ldexp(M, e);                         // an integer
+    if (Mi > 134217728.0) return false;                    // Mi^2 > 2^54
+    const uint64_t m2 = (uint64_t)Mi * (uint64_t)Mi;
+    return (uint64_t)U <= (1ull << 53) / m2;
+}
+
 int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const int64_t *user_ptr, const int32_t *item,
                             const float *rating, const int64_t *time, const int32_t *prefix_cls, const int32_t *suffix_cls,
                             const uint32_t *contains_mask, const uint8_t *flags) {
@@ -224,6 +249,7 @@ int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const
     R.user_ptr = d_ptr; R.user_item = d_item; R.user_rating = d_rating; R.user_time = d_time;
     R.item_ptr = d_iptr; R.item_user = d_iuser; R.item_rating = d_irating;
     R.prefix_cls = d_pre; R.suffix_cls = d_suf; R.contains_mask = d_mask; R.flags = d_flags;
+    c->plain_exact = plain_sums_exact(n_users, nnz, rating);
     XM_HIP(hipStreamSynchronize(c->st));
     c->have_ratings = true;
     return XMAP_OK;
@@ -237,6 +263,7 @@ int xmap_ctx_item_sim(xmap_ctx *c, int method, int cap, int64_t *n_kept, int64_t
     xmap_ratings &R = c->R;
     const int I = R.n_items;
     const int64_t U = R.n_users, nnz = R.nnz;
+    const int pair_method = (method == XMAP_COSINE && !c->plain_exact) ? XMAP_COSINE_EXACT : method;
     Pool tmp;                       // layout / plan / half COO: released at the end of the stage
     struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
 #define T_ALLOC(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), c->st))
@@ -295,7 +322,7 @@ int xmap_ctx_item_sim(xmap_ctx *c, int method, int cap, int64_t *n_kept, int64_t
         T_ALLOCZ(d_cnt, 6); T_ALLOC(d_shards, 2 * 4096); T_ALLOC(rowcnt_h, 64 * 1024);
         // all phases in one call: the heavy rows run on a side stream next to the class launches of the light rows; own and
         // mirrored row counts apart (mir), kept / evaluated pairs summed on the device (phase 64)
-        XM_TRY(xmap_sim2_pairs(c->st, &R, method, cap, c->u_avg, norms, rcrec, ub, Q, small, uq_item, uq_q, hc + 2, 0, n_light, hid, hlist,
+        XM_TRY(xmap_sim2_pairs(c->st, &R, pair_method, cap, c->u_avg, norms, rcrec, ub, Q, small, uq_item, uq_q, hc + 2, 0, n_light, hid, hlist,
                                ctl, Cc, uc_ptr, uc_item, uc_c, (int32_t)n_hu, n_heavy, 8 | 1 | 2 | 4 | 16 | 64 | 128, hp_hi, hp_lo, hp_cnt,
                                hp_mut, cap_coo, coo_i, coo_j, coo_sim, coo_mutu, coo_nij, nullptr, own, rowcnt_h, d_shards, d_cnt, mir));
         int64_t h_cnt[6];

@@ -96,6 +96,17 @@ __device__ __forceinline__ void dd_add(double &hi, double &lo, double x) {
     hi = h2;
 }
 
+// fixed butterfly of double-double partial sums over groups of G lanes: lane 0 of each group ends with the group's sum
+template <int G>
+__device__ __forceinline__ void dd_reduce(double &hi, double &lo) {
+#pragma unroll
+    for (int m = G / 2; m >= 1; m >>= 1) {
+        double oh = __shfl_down(hi, m, G), ol = __shfl_down(lo, m, G);
+        dd_add(hi, lo, oh);
+        dd_add(hi, lo, ol);
+    }
+}
+
 // murmur3 finaliser: partition hash of an item index
 __device__ __forceinline__ uint32_t mix32(uint32_t h) {
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;

@@ -5,6 +5,10 @@
 
 namespace xmap {
 
+// an item's partial sums (a user share, a chunk of its raters): sum r, sum r^2 and the adjusted norm^2, each as an exact
+// (value, error) pair, then the rater count -- k_item_merge / k_item_big add the partials up exactly
+constexpr int ITEM_PART = 7;
+
 // one wave per item: lane-strided partial sums, fixed butterfly reduction (deterministic)
 // stats of item i on a group of G lanes (G = 16: four items per wave; G = 64: the whole wave); gl = lane in the group.
 // All lanes of the wave call it (the reductions are wave instructions); `on` says whether this group has an item.
@@ -23,23 +27,24 @@ __device__ __forceinline__ void item_stats_group(bool on, int i, int gl, int I, 
                                                  double *info, double *norms, int *ia_user, double *partial = nullptr) {
     long long p0 = 0, p1 = 0;
     if (on) { p0 = iptr[i]; p1 = iptr[i + 1]; }
-    double s = 0.0, q = 0.0, a2 = 0.0, a2lo = 0.0;
+    // every sum is an exact double-double (order-independent whatever the rating values), rounded once at the end
+    double s = 0.0, slo = 0.0, q = 0.0, qlo = 0.0, a2 = 0.0, a2lo = 0.0;
     if (G < 64 || !POP || p1 - p0 <= 64 * 8) {
         for (long long p = p0 + gl; p < p1; p += G) {
             double r; int u;
             src.load(p, r, u);
             double d = r - src.uavg(u);
-            s += r;
-            q += r * r;
-            dd_add(a2, a2lo, d * d);   // exact sum of the fp64 squares (order-independent)
+            dd_add(s, slo, r);
+            dd_add(q, qlo, r * r);
+            dd_add(a2, a2lo, d * d);
         }
     } else {
         // popular items (up to 1e5 raters): 8 independent accumulators keep 8 gathers in flight per lane instead of
         // a chain of 1300 dependent round trips; the partials are merged exactly below
         constexpr int UN = 8;
-        double su[UN], qu[UN], ah[UN], al[UN];
+        double su[UN], sl[UN], qu[UN], ql[UN], ah[UN], al[UN];
 #pragma unroll
-        for (int t = 0; t < UN; t++) { su[t] = 0.0; qu[t] = 0.0; ah[t] = 0.0; al[t] = 0.0; }
+        for (int t = 0; t < UN; t++) { su[t] = 0.0; sl[t] = 0.0; qu[t] = 0.0; ql[t] = 0.0; ah[t] = 0.0; al[t] = 0.0; }
         // software pipeline: the ratings and users of the NEXT round are requested before this round's user averages
         // are gathered, so a round costs one dependent round trip, not two (156 rounds for the most popular item: the
         // kernel's tail).  Same partial sums in the same order.
@@ -66,34 +71,33 @@ __device__ __forceinline__ void item_stats_group(bool on, int i, int gl, int I, 
                 if (uu[t] < 0) continue;
                 const double r = rr[t];
                 const double d = r - av[t];
-                su[t] += r;
-                qu[t] += r * r;
+                dd_add(su[t], sl[t], r);
+                dd_add(qu[t], ql[t], r * r);
                 dd_add(ah[t], al[t], d * d);
             }
         }
 #pragma unroll
         for (int t = 0; t < UN; t++) {
-            s += su[t];
-            q += qu[t];
+            dd_add(s, slo, su[t]);
+            dd_add(s, slo, sl[t]);
+            dd_add(q, qlo, qu[t]);
+            dd_add(q, qlo, ql[t]);
             dd_add(a2, a2lo, ah[t]);
             dd_add(a2, a2lo, al[t]);
         }
     }
-#pragma unroll
-    for (int m = G / 2; m >= 1; m >>= 1) { s += __shfl_xor(s, m, 64); q += __shfl_xor(q, m, 64); }
-#pragma unroll
-    for (int m = G / 2; m >= 1; m >>= 1) {
-        double oh = __shfl_down(a2, m, G), ol = __shfl_down(a2lo, m, G);
-        dd_add(a2, a2lo, oh);
-        dd_add(a2, a2lo, ol);
-    }
+    dd_reduce<G>(s, slo);
+    dd_reduce<G>(q, qlo);
+    dd_reduce<G>(a2, a2lo);
     if (partial) {     // user-sharded input: this rank's share of the item's sums (k_item_merge adds the shares up)
         if (on && gl == 0) {
-            double *o = partial + (size_t)i * 5;
-            o[0] = s; o[1] = q; o[2] = a2; o[3] = a2lo; o[4] = (double)(p1 - p0);
+            double *o = partial + (size_t)i * ITEM_PART;
+            o[0] = s; o[1] = slo; o[2] = q; o[3] = qlo; o[4] = a2; o[5] = a2lo; o[6] = (double)(p1 - p0);
         }
         return;
     }
+    s = __shfl(s, 0, G);
+    q = __shfl(q, 0, G);
     a2 = __shfl(a2, 0, G);
     double n = (double)(p1 - p0);
     double avg = (p1 > p0) ? 1.0 * s / n : 0.0;

@@ -131,18 +131,22 @@ __global__ __launch_bounds__(256) void k_item_stats(int I, int lo, int hi, const
     }
 }
 
-// user-sharded input: the item sums of the ranks' user shares [n_parts][I][5] = (sum r, sum r^2, adjusted
-// norm^2 as an exact (value, error) pair, raters) are added up in rank order -- the adjusted norm exactly -- and finished
-// as k_item_stats finishes them
+// user-sharded input: the item sums of the ranks' user shares [n_parts][I][ITEM_PART] = (sum r, sum r^2,
+// adjusted norm^2, each as an exact (value, error) pair, raters) are added up exactly and finished as k_item_stats
+// finishes them
 __global__ __launch_bounds__(256) void k_item_merge(int I, int n_parts, const double *parts, double *info, double *norms) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= I) return;
-    double s = 0.0, q = 0.0, a2 = 0.0, a2lo = 0.0, n = 0.0;
+    double s = 0.0, slo = 0.0, q = 0.0, qlo = 0.0, a2 = 0.0, a2lo = 0.0, n = 0.0;
     for (int r = 0; r < n_parts; r++) {
-        const double *o = parts + ((size_t)r * I + i) * 5;
-        s += o[0]; q += o[1]; n += o[4];
-        dd_add(a2, a2lo, o[2]);
-        dd_add(a2, a2lo, o[3]);
+        const double *o = parts + ((size_t)r * I + i) * ITEM_PART;
+        dd_add(s, slo, o[0]);
+        dd_add(s, slo, o[1]);
+        dd_add(q, qlo, o[2]);
+        dd_add(q, qlo, o[3]);
+        dd_add(a2, a2lo, o[4]);
+        dd_add(a2, a2lo, o[5]);
+        n += o[6];
     }
     const double avg = (n > 0.0) ? 1.0 * s / n : 0.0;
     info[(size_t)i * 4 + 0] = avg;
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(A_THREADS) void k_pair_sim(PairArgs A) {
     __shared__ uint32_t s_mut[A_WAVES][SLOTS];
     __shared__ double s_dot[A_WAVES][SLOTS];
     // adjusted-cosine terms are summed error-free (double-double): the low words live here
-    __shared__ double s_lo[METHOD == XMAP_ADJUST_COSINE ? A_WAVES : 1][METHOD == XMAP_ADJUST_COSINE ? SLOTS : 1];
+    __shared__ double s_lo[METHOD != XMAP_COSINE ? A_WAVES : 1][METHOD != XMAP_COSINE ? SLOTS : 1];   // (value, error) sums
 
     const int w = threadIdx.x >> 6;
     const int lane = lane_id();
@@ -247,13 +251,13 @@ __global__ __launch_bounds__(A_THREADS) void k_pair_sim(PairArgs A) {
     uint32_t *cnt = s_cnt[w];
     uint32_t *mut = s_mut[w];
     double *dot = s_dot[w];
-    double *dlo = s_lo[METHOD == XMAP_ADJUST_COSINE ? w : 0];
+    double *dlo = s_lo[METHOD != XMAP_COSINE ? w : 0];
     for (int s = lane; s < SLOTS; s += 64) {
         key[s] = EMPTY;
         cnt[s] = 0;
         mut[s] = 0;
         dot[s] = 0.0;
-        if (METHOD == XMAP_ADJUST_COSINE) dlo[s] = 0.0;
+        if (METHOD != XMAP_COSINE) dlo[s] = 0.0;
     }
 
     const int i = uniform(A.unit_item[unit]);
@@ -328,7 +332,7 @@ __global__ __launch_bounds__(A_THREADS) void k_pair_sim(PairArgs A) {
                             mut[h] += (gej == gei) ? 1u : 0u;
                             if (METHOD == XMAP_COSINE) {
                                 dot[h] += (1.0 * ri) * (double)rj;   // exact for integer ratings
-                            } else {
+                            } else {                                 // adjusted, or exact cosine (a = 0)
                                 double hi = dot[h], lo = dlo[h];
                                 dd_add(hi, lo, (ri - a) * ((double)rj - a));
                                 dot[h] = hi;
@@ -344,7 +348,7 @@ __global__ __launch_bounds__(A_THREADS) void k_pair_sim(PairArgs A) {
     }
 
     // finalise from LDS: cosine (:91-95), significance weighting (:84-89), zero filter (:198,:207)
-    const int c1 = (METHOD == XMAP_COSINE) ? 1 : 2;
+    const int c1 = (METHOD == XMAP_ADJUST_COSINE) ? 2 : 1;
     const double norm_i = A.info[(size_t)i * 4 + c1];
     long long out = WRITE ? A.unit_off[unit] : 0;
     int kept = 0, evald = 0;
@@ -392,6 +396,9 @@ static int launch_pair(hipStream_t st, int method, bool write, const PairArgs &A
     if (method == XMAP_COSINE) {
         if (write) k_pair_sim<XMAP_COSINE, true><<<grid, block, 0, st>>>(A);
         else k_pair_sim<XMAP_COSINE, false><<<grid, block, 0, st>>>(A);
+    } else if (method == XMAP_COSINE_EXACT) {
+        if (write) k_pair_sim<XMAP_COSINE_EXACT, true><<<grid, block, 0, st>>>(A);
+        else k_pair_sim<XMAP_COSINE_EXACT, false><<<grid, block, 0, st>>>(A);
     } else {
         if (write) k_pair_sim<XMAP_ADJUST_COSINE, true><<<grid, block, 0, st>>>(A);
         else k_pair_sim<XMAP_ADJUST_COSINE, false><<<grid, block, 0, st>>>(A);
@@ -485,7 +492,7 @@ int xmap_item_stats(void *stream, const xmap_ratings *R, const double *u_avg, do
     return XMAP_OK;
 }
 
-int xmap_item_partials(void *stream, const xmap_ratings *R, const double *u_avg, double *partial /*[I][5]*/) {
+int xmap_item_partials(void *stream, const xmap_ratings *R, const double *u_avg, double *partial /*[I][ITEM_PART]*/) {
     XM_ARG(R && u_avg && partial && R->nnz < 0x7fffffffLL);
     hipStream_t st = (hipStream_t)stream;
     if (R->n_items > 0) {
@@ -554,7 +561,7 @@ int xmap_sim_count(void *stream, const xmap_ratings *R, int method, int cap, con
                    const int32_t *unit_q, int64_t unit_lo, int64_t unit_hi, int32_t *unit_cnt, int64_t *d_counters,
                    int64_t *h_counters) {
     XM_ARG(R && u_avg && info && ua_item && ia_user && Q && unit_item && unit_q && unit_cnt && d_counters);
-    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE);
+    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE || method == XMAP_COSINE_EXACT);
     XM_ARG(cap > 0 && R->nnz < 0x7fffffffLL);
     hipStream_t st = (hipStream_t)stream;
     XM_HIP(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
@@ -580,7 +587,7 @@ int xmap_sim_fill(void *stream, const xmap_ratings *R, int method, int cap, cons
                   double *sim, int32_t *mutu, int32_t *nij) {
     XM_SCOPE(stream);
     XM_ARG(R && u_avg && info && ua_item && ia_user && Q && unit_item && unit_q && unit_off);
-    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE);
+    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE || method == XMAP_COSINE_EXACT);
     XM_ARG(cap > 0 && R->nnz < 0x7fffffffLL);
     PairArgs A = make_args(R, cap, u_avg, info, ua_item, ia_user, Q, unit_item, unit_q, unit_lo, unit_hi);
     A.unit_off = (const long long *)unit_off;

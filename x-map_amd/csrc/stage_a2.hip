@@ -24,7 +24,8 @@
 //   k_pair_heavy    : rows of H, raters in chunks (one rater per lane), DENSE LDS table over H, partial tables to HBM
 //   k_heavy_merge   : double-double merge of the chunk partials (4 waves per row), finalise, append
 //   k_scatter       : mirror the half-COO into the CSR rows (atomic cursors)
-// Sums are exact (double-double, or integer-exact in cosine mode), so neither the order of raters nor the
+// Sums are exact (double-double, or plain fp64 in cosine mode for ratings whose sums are exact in any order -- the host's
+// predicate, xmap/engine/exactness.py; otherwise cosine runs as XMAP_COSINE_EXACT), so neither the order of raters nor the
 // chunking changes a bit of the result.
 #include <type_traits>
 
@@ -423,7 +424,7 @@ __global__ __launch_bounds__(256) void k_shard_sums(const unsigned long long *sh
 
 // Light rows.  The co-ratings of a block of raters are walked as one flat list, one per lane (k_pair_tri: walk).  Lanes
 // of different raters may meet on one partner: the counters use LDS atomics, the fp64 sum is either an LDS atomic add
-// (cosine: integer-exact, order irrelevant) or, for the double-double sum of adjusted cosine, serialised per slot
+// (cosine over ratings the host found exact: order irrelevant) or, for the double-double sum, serialised per slot
 // (conflicts are rare): through a claim word inside one wave, through a lock bit in the slot's key when several waves
 // share the table.
 
@@ -1577,7 +1578,7 @@ struct BigList {
     unsigned *counters;       // [0] chunks listed, [1] big items listed
     int2 *chunks;             // (item, chunk)
     int4 *items;              // (item, first chunk, chunks, -)
-    double *part;             // [chunk][5]
+    double *part;             // [chunk][ITEM_PART]
     long long chunk_cap, item_cap;
 };
 
@@ -1622,7 +1623,7 @@ __global__ __launch_bounds__(256) void k_item_chunks(const long long *iptr, cons
     const long long p0 = iptr[d.x] + (long long)d.y * STAT_CHK;
     const long long p1 = min(iptr[d.x + 1], p0 + STAT_CHK);
     constexpr int UN = 8;
-    double s = 0.0, q = 0.0, a2 = 0.0, a2lo = 0.0;
+    double s = 0.0, slo = 0.0, q = 0.0, qlo = 0.0, a2 = 0.0, a2lo = 0.0;
     for (long long p = p0 + lane; p < p1; p += 64 * UN) {
         double rr[UN], av[UN];
         int uu[UN];
@@ -1637,22 +1638,17 @@ __global__ __launch_bounds__(256) void k_item_chunks(const long long *iptr, cons
         for (int t = 0; t < UN; t++) {
             if (uu[t] < 0) continue;
             const double dlt = rr[t] - av[t];
-            s += rr[t];
-            q += rr[t] * rr[t];
+            dd_add(s, slo, rr[t]);
+            dd_add(q, qlo, rr[t] * rr[t]);
             dd_add(a2, a2lo, dlt * dlt);
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { s += __shfl_xor(s, m, 64); q += __shfl_xor(q, m, 64); }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        double oh = __shfl_down(a2, m, 64), ol = __shfl_down(a2lo, m, 64);
-        dd_add(a2, a2lo, oh);
-        dd_add(a2, a2lo, ol);
-    }
+    dd_reduce<64>(s, slo);
+    dd_reduce<64>(q, qlo);
+    dd_reduce<64>(a2, a2lo);
     if (lane == 0) {
-        double *o = B.part + (size_t)c * 5;
-        o[0] = s; o[1] = q; o[2] = a2; o[3] = a2lo; o[4] = (double)(p1 - p0);
+        double *o = B.part + (size_t)c * ITEM_PART;
+        o[0] = s; o[1] = slo; o[2] = q; o[3] = qlo; o[4] = a2; o[5] = a2lo; o[6] = (double)(p1 - p0);
     }
 }
 
@@ -1660,12 +1656,16 @@ __global__ __launch_bounds__(64) void k_item_big(int I, BigList B, double *info,
     const unsigned b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B.counters[1]) return;
     const int4 d = B.items[b];
-    double s = 0.0, q = 0.0, a2 = 0.0, a2lo = 0.0, n = 0.0;
+    double s = 0.0, slo = 0.0, q = 0.0, qlo = 0.0, a2 = 0.0, a2lo = 0.0, n = 0.0;
     for (int x = 0; x < d.z; x++) {
-        const double *o = B.part + (size_t)(d.y + x) * 5;
-        s += o[0]; q += o[1]; n += o[4];
-        dd_add(a2, a2lo, o[2]);
-        dd_add(a2, a2lo, o[3]);
+        const double *o = B.part + (size_t)(d.y + x) * ITEM_PART;
+        dd_add(s, slo, o[0]);
+        dd_add(s, slo, o[1]);
+        dd_add(q, qlo, o[2]);
+        dd_add(q, qlo, o[3]);
+        dd_add(a2, a2lo, o[4]);
+        dd_add(a2, a2lo, o[5]);
+        n += o[6];
     }
     const int i = d.x;
     info[(size_t)i * 4 + 0] = (n > 0.0) ? 1.0 * s / n : 0.0;
@@ -2189,14 +2189,25 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
     XM_ARG(Q && small && uq_item && uq_q && cls_ptr && hid && hlist && ctl && C && uc_ptr && uc_item && uc_c);
     XM_ARG(coo_i && coo_j && coo_sim && coo_mutu && coo_nij && rowcnt && rowcnt_h && d_shards && d_counters);
     XM_ARG(coo_cap >= COO_SHARDS);
-    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE);
+    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE || method == XMAP_COSINE_EXACT);
     XM_ARG(n_heavy_units == 0 || !(phases & 5) || (hp_hi && hp_lo && hp_cnt && hp_mut));
+    hipStream_t st = (hipStream_t)stream;
+    // exact cosine: the adjusted-cosine kernels (double-double dot product) with a zero user average and the plain norms
+    const bool exact_cos = method == XMAP_COSINE_EXACT;
+    const double *nrm = norms + (method == XMAP_ADJUST_COSINE ? (size_t)R->n_items : 0);
+    if (exact_cos) {
+        double *zero_avg = nullptr;
+        const size_t ub = sizeof(double) * (size_t)(R->n_users > 0 ? R->n_users : 1);
+        XM_HIP(xm_malloc_async((void **)&zero_avg, ub, st));
+        XM_HIP(hipMemsetAsync(zero_avg, 0, ub, st));
+        u_avg = zero_avg;
+        method = XMAP_ADJUST_COSINE;
+    }
     // coo_ls selects the RecommenderSim variant: exact (double-double) sums, no filter, local sensitivity; its layout
     // has no heavy rows
     const bool raw = (phases & 32) != 0;      // partial sums of a user share: coo_ls is then the error column of the dot
     XM_ARG(!coo_ls || ((raw || method == XMAP_ADJUST_COSINE) && n_heavy_units == 0));
     XM_ARG(!raw || (coo_ls && n_heavy_units == 0 && n_heavy == 0));
-    hipStream_t st = (hipStream_t)stream;
     if (phases & 8) {   // reset the COO cursor / counters / row counts
         XM_HIP(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
         XM_HIP(hipMemsetAsync(d_shards, 0, 2 * COO_SHARDS * sizeof(int64_t), st));
@@ -2208,7 +2219,7 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
     TriArgs A;
     memset(&A, 0, sizeof(A));
     A.iptr = (const long long *)R->item_ptr; A.rc = (const RaterRec *)rc; A.ub = (const int2 *)ub;
-    A.u_avg = u_avg; A.nrm = norms + (method == XMAP_COSINE ? 0 : (size_t)R->n_items); A.cap = cap;
+    A.u_avg = u_avg; A.nrm = nrm; A.cap = cap;
     A.Q = Q; A.small = small; A.uq_item = uq_item; A.uq_q = uq_q; A.unit_lo = unit_lo; A.unit_hi = unit_hi;
     A.hid = hid; A.hlist = hlist; A.CH = ctl; A.uc_item = uc_item; A.uc_c = uc_c;
     A.uc_ptr = (const long long *)uc_ptr; A.C = C;
@@ -2387,7 +2398,7 @@ int xmap_sim2_merge_partials(void *stream, int method, int cap, int32_t n_items,
                              int32_t *coo_nij, int32_t *rowcnt, int64_t *h_counts /*[2]: kept, evaluated (unordered pairs)*/) {
     XM_SCOPE(stream);
     XM_ARG(rec_sorted && norms && coo_i && coo_j && coo_sim && coo_mutu && coo_nij && rowcnt && h_counts && n >= 0 && cap > 0);
-    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE);
+    XM_ARG(method == XMAP_COSINE || method == XMAP_ADJUST_COSINE || method == XMAP_COSINE_EXACT);
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *cnt = nullptr;
     XM_HIP(xm_malloc_async((void **)&cnt, 2 * sizeof(unsigned long long), st));
@@ -2395,7 +2406,8 @@ int xmap_sim2_merge_partials(void *stream, int method, int cap, int32_t n_items,
     XM_HIP(hipMemsetAsync(rowcnt, 0, sizeof(int32_t) * (size_t)(n_items > 0 ? n_items : 1), st));
     if (n > 0) {
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        const double *nrm = norms + (method == XMAP_COSINE ? 0 : (size_t)n_items);
+        // exact cosine: the records hold the dot products as (value, error) pairs; added up exactly, over the plain norms
+        const double *nrm = norms + (method == XMAP_ADJUST_COSINE ? (size_t)n_items : 0);
         if (method == XMAP_COSINE)
             k_merge_partials<XMAP_COSINE><<<grid, block, 0, st>>>(n, (const long long *)rec_sorted, nrm, cap, cnt, coo_i, coo_j, coo_sim,
                                                                   coo_mutu, coo_nij, rowcnt);
@@ -2537,7 +2549,7 @@ int xmap_sim3_layout(void *stream, const xmap_ratings *R, int64_t *item_ptr, con
         XM_HIP(xm_malloc_async((void **)&B.counters, 2 * sizeof(unsigned), st));
         XM_HIP(xm_malloc_async((void **)&B.chunks, sizeof(int2) * (size_t)B.chunk_cap, st));
         XM_HIP(xm_malloc_async((void **)&B.items, sizeof(int4) * (size_t)B.item_cap, st));
-        XM_HIP(xm_malloc_async((void **)&B.part, sizeof(double) * 5 * (size_t)B.chunk_cap, st));
+        XM_HIP(xm_malloc_async((void **)&B.part, sizeof(double) * ITEM_PART * (size_t)B.chunk_cap, st));
         XM_HIP(hipMemsetAsync(B.counters, 0, 2 * sizeof(unsigned), st));
         const dim3 grid((unsigned)((stats_hi - stats_lo + 15) / 16)), gridC((unsigned)((B.chunk_cap + 3) / 4)), gridI((unsigned)((B.item_cap + 63) / 64));
         if (wide) {

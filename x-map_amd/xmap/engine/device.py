@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import hipabi as abi
+from .exactness import plain_sums_exact
 
 lib = abi.lib
 vp, i32, i64, check = abi.vp, abi.i32, abi.i64, abi.check
@@ -44,6 +45,8 @@ class DeviceRatings(object):
         self.n_users = len(user_ptr) - 1
         self.n_items = int(n_items)
         self.nnz = int(user_ptr[-1])
+        # cosine may run on the plain fp64 sums (fast kernels) only when they are exact in any order (xmap.engine.exactness)
+        self.plain_exact = plain_sums_exact(rating[:self.nnz], self.n_users)
         # contributions of the "tri" formulation (every unordered pair of a profile once): a property of the profile
         # lengths, so the engine sizes its pair buffers and unit arrays without asking the device
         d = np.diff(user_ptr)
@@ -161,6 +164,12 @@ class Engine(object):
         return torch.zeros(shape, dtype=dtype, device=self.dev)
 
     # ------------------------------------------------------------------ stage A
+    def pair_method(self, method):
+        """the method code the pair kernels run: cosine over ratings whose plain fp64 sums may round (R.plain_exact False)
+        takes the double-double route, XMAP_COSINE_EXACT"""
+        m = abi.METHODS[method] if isinstance(method, str) else int(method)
+        return abi.COSINE_EXACT if (m == abi.COSINE and not self.R.plain_exact) else m
+
     def build_csc(self):
         """item -> raters layout of the ratings (device counting sort; part of every stage-A pass)"""
         R = self.R
@@ -194,19 +203,20 @@ class Engine(object):
 
     def stats_partial(self):
         """user-sharded input: CSC of this rank's users, their user info, and the rank's share of the item sums
-        [I][5] = (sum r, sum r^2, adjusted norm^2 as (value, error), raters) -- xmap.engine.sharded.run_step_users"""
+        [I][7] = (sum r, sum r^2, adjusted norm^2, each as an exact (value, error) pair, raters) --
+        xmap.engine.sharded.run_step_users"""
         R = self.R
         st = _stream(self.dev)
         self.build_csc()
         u_avg = self._empty(max(R.n_users, 1), torch.float64)
         u_norm = self._empty(max(R.n_users, 1), torch.float64)
         check(lib.xmap_user_stats(st, C.byref(R.c), vp(u_avg), vp(u_norm)))
-        partial = self._out((max(R.n_items, 1), 5), torch.float64, R.n_items > 0)
+        partial = self._out((max(R.n_items, 1), 7), torch.float64, R.n_items > 0)
         check(lib.xmap_item_partials(st, C.byref(R.c), vp(u_avg), vp(partial)))
         return u_avg, u_norm, partial
 
     def stats_merge(self, parts):
-        """parts [n_parts][I][5] (the ranks' shares in rank order) -> info [I][4]; sets self.norms"""
+        """parts [n_parts][I][7] (the ranks' shares in rank order) -> info [I][4]; sets self.norms"""
         I = self.R.n_items
         parts = parts.contiguous()
         info = self._out((max(I, 1), 4), torch.float64, I > 0)
@@ -257,6 +267,10 @@ class Engine(object):
         st = _stream(self.dev)
         I = self.R.n_items
         m = abi.METHODS[method] if isinstance(method, str) else int(method)
+        # cosine shares are always added up exactly: a rank's predicate covers its own users only, and its records hold
+        # exact (value, error) pairs either way (integer ratings: error 0, the same bits as the plain sum)
+        if m == abi.COSINE:
+            m = abi.COSINE_EXACT
         n = int(rec_sorted.shape[0])
         coo_i = torch.full((max(n, 1),), -1, dtype=torch.int32, device=self.dev)
         coo_j = self._empty(max(n, 1), torch.int32)
@@ -305,7 +319,7 @@ class Engine(object):
             return self.item_sim_tri(method, cap, slot_target)
         R = self.R
         st = _stream(self.dev)
-        m = abi.METHODS[method] if isinstance(method, str) else int(method)
+        m = self.pair_method(method)
         if stats is None or stats[3] is None:
             with self.timed("stats"):
                 stats = self.stats(packed=True)
@@ -349,7 +363,7 @@ class Engine(object):
                                     vp(Q), vp(unit_item), vp(unit_q), i64(lo), i64(hi), vp(unit_off),
                                     vp(col), vp(sim), vp(mutu), vp(nij)))
         S = SimResult()
-        S.method, S.cap, S.n_items = m, int(cap), I
+        S.method, S.cap, S.n_items = abi.METHODS[method] if isinstance(method, str) else int(method), int(cap), I
         S.u_avg, S.u_norm, S.info = u_avg, u_norm, info
         S.row_ptr, S.col, S.sim, S.mutu, S.nij = row_ptr, col[:kept], sim[:kept], mutu[:kept], nij[:kept]
         S.n_kept, S.n_eval, S.n_contrib, S.n_units = kept, evaluated, int(contrib), hi - lo
@@ -465,7 +479,7 @@ class Engine(object):
         the kept-pair count so that the host's wait falls into their 0.2 ms; tri_mirror is then called with counted=True."""
         R = self.R
         st = _stream(self.dev)
-        m = abi.METHODS[method] if isinstance(method, str) else int(method)
+        m = self.pair_method(method)
         u_avg, u_norm, info, _, _ = stats
         I = R.n_items
         coo_slack = 1.0

@@ -148,6 +148,7 @@ def train_state_from_feed(feed):
     idt.iidx = {s: k for k, s in enumerate(idt.iids)}
     idt.attrs = attrs
     st.idt = idt
+    session.check_float32(ptr, item, rating, idt.uids, idt.iids)     # the rule of TrainState: float32 must hold every rating
     st.times, st.ratings = _LazyTimes(when), _LazyRatings(rating)
     n = len(item)
     st.R = device.DeviceRatings(ptr, item, rating.astype(np.float32), np.arange(n, dtype=np.int64), len(idt.iids), attrs)

@@ -14,6 +14,7 @@ XLIB_PATH = os.environ.get("XMAP_HIP_XLIB") or os.path.normpath(os.path.join(HER
 
 COSINE, ADJUST_COSINE = 0, 1
 METHODS = {"cosine": COSINE, "adjust_cosine": ADJUST_COSINE}
+COSINE_EXACT = 2          # XMAP_COSINE_EXACT: cosine with double-double sums (the pair entry points only)
 TOPC = 10
 MID_ROWS_SPAN = 36864     # XMAP_MID_ROWS_SPAN: columns of a middle-list row per LDS pass
 ERR_HIP, ERR_ARG, ERR_OVERFLOW, ERR_CAPACITY = -1, -2, -3, -4     # XMAP_ERR_* of include/xmap_hip.h

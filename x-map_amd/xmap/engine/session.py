@@ -18,6 +18,25 @@ from .localrdd import LocalRDD, records_of
 _engines = {}   # id(trainRDD) -> (weakref or None, TrainState, fingerprint or None)
 
 
+def float32_rating_error(uid, iid, value):
+    """the ValueError for a caller rating that float32 -- the rating type of the three stages -- cannot hold exactly: the
+    AlterEgo means would be taken over a different value than the one the caller passed"""
+    return ValueError("rating %r of user %r, item %r is not exactly representable as float32 (the engine's rating type); "
+                      "round the ratings to np.float32 first, e.g. float(np.float32(r))" % (value, uid, iid))
+
+
+def check_float32(ptr, item, rating64, uids, iids):
+    """raise float32_rating_error for the first rating of a CSR (trainRDD order) that float32 does not hold exactly
+    (NaN passes: it stays NaN)"""
+    r64 = np.asarray(rating64, np.float64)
+    r32 = r64.astype(np.float32).astype(np.float64)
+    bad = np.nonzero((r32 != r64) & ~np.isnan(r64))[0]
+    if len(bad):
+        e = int(bad[0])
+        u = int(np.searchsorted(ptr, e, side="right") - 1)
+        raise float32_rating_error(uids[u], iids[int(item[e])], float(r64[e]))
+
+
 class TrainState(object):
     def __init__(self, records):
         from . import device
@@ -34,6 +53,8 @@ class TrainState(object):
             for (iid, r, t) in prof:
                 item[e] = iidx[iid]
                 rating[e] = r
+                if float(rating[e]) != float(r) and r == r:          # (NaN stays NaN)
+                    raise float32_rating_error(records[u][0], iid, r)
                 self.times.append(t)
                 self.ratings.append(r)
                 e += 1

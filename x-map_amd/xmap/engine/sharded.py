@@ -316,7 +316,7 @@ def run_step_users(eng, user_lo, method, cap, k, private, dist, group=None, slot
     partial similarities"): eng.R holds the complete profiles of this rank's users -- users [user_lo, user_lo + n_users) of
     the whole data set, items indexed globally -- instead of a replica of all ratings.
 
-    Stage A: every rank sums its users' contributions.  Item statistics: the shares [I][5] are all-gathered (the all-gather
+    Stage A: every rank sums its users' contributions.  Item statistics: the shares [I][7] are all-gathered (the all-gather
     of per-item norms) and added up in rank order, the adjusted norm exactly.  Pairs: the pair kernel runs over the rank's
     users in "raw" mode and emits, per pair two of its users co-rated, the partial dot product (an exact (value, error)
     pair), n_ij and the mutuality; the 32-byte records are sorted by pair key and sent to the rank that owns the pair's

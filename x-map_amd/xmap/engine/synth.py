@@ -21,6 +21,8 @@ import numpy as np
 T0 = 1325376000  # 2012-01-01 00:00:00 UTC
 T1 = 1388534399  # 2013-12-31 23:59:59 UTC
 RATING_P = np.array([.05, .05, .10, .25, .55])
+# non-integer ratings (fractional(): tests of the sums that are inexact in fp64)
+FRACTIONAL = (0.5, 1.3, 1.7, 2.1, 2.6, 3.3, 3.7, 4.2, 4.5, 4.9)
 
 
 class Ratings(object):
@@ -158,6 +160,14 @@ def make_multi_domain(seed, n_users, n_src_items, n_tgt_items, n_sources, overla
         out.append(Ratings(ptr, it[order], np.concatenate([rs, rt])[order], np.concatenate([ts, tt])[order],
                            n_src + len(tgt_numbers), n_src, src_numbers, tgt_numbers))
     return out
+
+
+def fractional(r, seed=0, values=FRACTIONAL):
+    """r with every rating replaced by a float32 value drawn from `values` (seeded: a spawned worker rebuilds the same
+    input).  The default values are not integers: cosine mode's fp64 sums of such ratings round, so their order matters."""
+    rng = np.random.default_rng(seed)
+    rating = np.asarray(values, np.float32)[rng.integers(0, len(values), size=r.nnz)]
+    return Ratings(r.user_ptr, r.item, rating, r.time, r.n_items, r.n_src_items, r.src_numbers, r.tgt_numbers)
 
 
 # named workloads (BASELINE.json configs)
