@@ -595,7 +595,8 @@ typedef struct xmap_ctx xmap_ctx;
  *   xmap_feed_arrays : copies into caller buffers (any but user_ptr may be NULL); when = the timestamps as doubles
  *   xmap_feed_ids    : the id strings back to back + offsets [n + 1] (which = 0 users, 1 items; bytes may be NULL); which | 2:
  *                      a newline behind every id (bytes + n in all; offsets may then be NULL)
- *   xmap_ctx_upload_feed : the coarse ABI's upload straight from a feed (xmap_ctx_upload_ratings on its arrays)
+ *   xmap_ctx_upload_feed : the coarse ABI's upload straight from a feed (xmap_ctx_upload_ratings on its arrays); a rating
+ *                      float32 does not hold exactly (NaN aside) -> XMAP_ERR_ARG naming uid, iid and value, context unchanged
  *   xmap_feed_format : test / bench utility, the inverse for one domain (items [item_lo, item_hi) of a CSR -> text) */
 typedef struct xmap_feed xmap_feed;
 int xmap_feed_text(const char *text, int64_t len, int32_t year_from, int32_t year_to, const char *label, int32_t min_ratings,

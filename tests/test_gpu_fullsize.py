@@ -376,3 +376,44 @@ def test_c4_shape_full_size():
     sel = out["domain"] == d
     assert np.array_equal(G.user.cpu().numpy(), out["user"][sel]) and np.array_equal(G.item.cpu().numpy() - n_src, out["item"][sel])
     assert np.array_equal(G.rating.cpu().numpy(), out["rating"][sel])
+
+
+def test_coarse_abi_full_size(c2):
+    """The coarse C ABI (xmap_ctx_*: its own stage-A retries, its 24 GB row sizing and max_rows cap) at BASELINE configs[1],
+    adjusted cosine, k = 50, private, against the Python engine on the same input: the whole stage-A matrix and the item
+    info, the path and candidate counts, the ten best candidates of every start, the AlterEgo rows.  One side's device
+    memory is released before the other side runs."""
+    import ctypes as C
+    import torch
+    from test_gpu_coarse_oracle import Ctx, stage_a, stage_c, ext_download, upload
+    r, eng = c2
+    I = r.n_items
+    S = eng.item_sim("adjust_cosine", CAP)
+    _, rows, cols, sim, mutu, nij = _csr(S)
+    info = S.info.cpu().numpy()
+    E = eng.extend(S, 50)
+    want_b = (E.n_paths, E.n_out, E.n_cand.cpu().numpy()[:I], E.top_end.cpu().numpy()[:I], E.top_val.cpu().numpy()[:I])
+    _, choice, mp = eng.select(E, True)
+    G = eng.alterego(mp)
+    want_c = (choice.cpu().numpy()[:I], G.user.cpu().numpy(), G.item.cpu().numpy(), G.rating.cpu().numpy(), G.time.cpu().numpy())
+    del S, E, choice, mp, G
+    eng._drop_scratch("qacc", "qhacc", "acc", "hacc")
+    torch.cuda.empty_cache()
+    ctx = Ctx()
+    try:
+        upload(ctx, r)
+        A = stage_a(ctx, "adjust_cosine", I, r.n_users)
+        assert np.array_equal(A["rows"], rows) and np.array_equal(A["cols"], cols)
+        assert np.array_equal(A["sim"], sim) and np.array_equal(A["mutu"], mutu) and np.array_equal(A["nij"], nij)
+        assert np.array_equal(A["info"], info)
+        del A, rows, cols, sim, mutu, nij
+        n_out, n_paths = C.c_int64(0), C.c_int64(0)
+        ctx.call("xmap_ctx_extend", 50, C.byref(n_out), C.byref(n_paths))
+        got_b = (n_paths.value, n_out.value) + ext_download(ctx, I)
+        for x, y in zip(got_b, want_b):
+            assert np.array_equal(x, y)
+        Cc = stage_c(ctx, I, True, None)
+        for x, y in zip((Cc["choice"], Cc["user"], Cc["item"], Cc["rating"], Cc["time"]), want_c):
+            assert np.array_equal(x, y)
+    finally:
+        ctx.close()

@@ -283,16 +283,11 @@ def test_long_profiles_and_popular_items(dev, method):
     xo.sim_free(So)
 
 
-@pytest.mark.parametrize("method", METHODS)
-def test_keys_larger_than_a_tile(dev, method):
-    """The two transpositions of stage A (rater records by item, kept pairs by heavier item: csrc/tilesort.h) with keys
-    far larger than a tile: two items rated by every user (8000 raters; each is the partner of every lighter row, so its
-    mirrored half has thousands of entries too), next to thousands of items with a handful.  Both sequences of the stage
-    (round 3: one transposition, tile-sorted mirror; round 2: CSC + cursor-atomic mirror) against the oracle, bit for bit."""
-    from oracle import xmap_oracle as xo
+# test_keys_larger_than_a_tile's input (also run through the coarse ABI: test_gpu_coarse_oracle.py): 8000 users, and every
+# one of them also rates source item 7 and target item n_src + 11 (appended to the profile if absent).  -> (ratings, hubs)
+def hub_ratings():
     from xmap.engine import synth
     r = synth.make_two_domain(31, 8000, 4000, 4000, overlap=0.4)
-    # every user also rates source item 7 and target item n_src + 11 (appended to the profile if absent)
     hubs = (7, r.n_src_items + 11)
     rng = np.random.default_rng(5)
     ptr, item, rating, time = [0], [], [], []
@@ -304,8 +299,20 @@ def test_keys_larger_than_a_tile(dev, method):
                 it.append(h); ra.append(float(rng.integers(1, 6))); ti.append(int(rng.integers(synth.T0, synth.T1)))
         item += it; rating += ra; time += ti
         ptr.append(len(item))
-    ptr, item = np.asarray(ptr, np.int64), np.asarray(item, np.int32)
-    rating, time = np.asarray(rating, np.float32), np.asarray(time, np.int64)
+    return synth.Ratings(np.asarray(ptr, np.int64), np.asarray(item, np.int32), np.asarray(rating, np.float32),
+                         np.asarray(time, np.int64), r.n_items, r.n_src_items, r.src_numbers, r.tgt_numbers), hubs
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_keys_larger_than_a_tile(dev, method):
+    """The two transpositions of stage A (rater records by item, kept pairs by heavier item: csrc/tilesort.h) with keys
+    far larger than a tile: two items rated by every user (8000 raters; each is the partner of every lighter row, so its
+    mirrored half has thousands of entries too), next to thousands of items with a handful.  Both sequences of the stage
+    (round 3: one transposition, tile-sorted mirror; round 2: CSC + cursor-atomic mirror) against the oracle, bit for bit."""
+    from oracle import xmap_oracle as xo
+    from xmap.engine import synth
+    r, hubs = hub_ratings()
+    ptr, item, rating, time = r.user_ptr, r.item, r.rating, r.time
     assert np.bincount(item, minlength=r.n_items)[list(hubs)].tolist() == [r.n_users, r.n_users]
     attrs = r.item_attrs()
     eng = _engine(dev, ptr, item, rating, time, r.n_items, attrs)
@@ -530,3 +537,40 @@ def test_rows_longer_than_one_knn_chunk(dev):
     ln = np.diff(S.row_ptr.cpu().numpy())
     assert (ln > 2048).sum() > 200 and ln.max() > 4096
     _check_all_stages(dev, r, "cosine", 3)
+
+
+def _ext_bytes(E, I):
+    return [E.n_paths, E.n_out, E.n_cand.cpu().numpy()[:I], E.top_end.cpu().numpy()[:I], E.top_val.cpu().numpy()[:I]] + \
+        list(_xsim_lists(E, I))
+
+
+@pytest.mark.parametrize("case", ["c1", "s9"])
+def test_second_pass_after_a_capacity_refusal(dev, case, monkeypatch):
+    """Candidate lists that do not fit the list buffer (xs_cap): the enumeration refuses with XMAP_ERR_CAPACITY after a
+    complete pass and extend_tables runs it again with the exact size, on the accumulator rows the refused pass left zeroed.
+    xs_cap = 1, n_out - 1 (refused) and n_out (fits exactly: the kernel's test is off + nt <= xs_cap) give the default
+    capacity's bytes in every formulation; the same engine at default capacity afterwards shows the rows it keeps are clean."""
+    from xmap.engine import synth
+    r = synth.config_c1() if case == "c1" else synth.make_two_domain(9, 3000, 600, 600)
+    I = r.n_items
+    eng = _engine(dev, r.user_ptr, r.item, r.rating, r.time, I, r.item_attrs())
+    S = eng.item_sim("adjust_cosine", CAP)
+    confs = [("cols", {}, None), ("enum", dict(algo="enum"), None), ("mid", dict(algo="mid"), None),
+             ("heavy", dict(chunk=64), None), ("slow_div", {}, "1")]
+    for name, kw, slow in confs:
+        if slow:
+            monkeypatch.setenv("XMAP_SLOW_DIV", slow)
+        E0 = eng.extend(S, 5, full=True, **kw)
+        want = _ext_bytes(E0, I)
+        n_out = E0.n_out
+        assert n_out > 2, name
+        if name == "heavy":
+            assert E0.units.n_heavy > 0
+        for cap in (1, n_out - 1, n_out):
+            E = eng.extend(S, 5, full=True, xs_cap=cap, **kw)
+            assert E.xs_end.numel() == n_out, (name, cap)
+            for x, y in zip(_ext_bytes(E, I), want):
+                assert np.array_equal(x, y), (name, cap)
+        for x, y in zip(_ext_bytes(eng.extend(S, 5, full=True, **kw), I), want):
+            assert np.array_equal(x, y), (name, "after")
+        monkeypatch.delenv("XMAP_SLOW_DIV", raising=False)

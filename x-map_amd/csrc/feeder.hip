@@ -576,13 +576,30 @@ int xmap_feed_ids(const xmap_feed *f, int32_t which, char *bytes, int64_t *offse
 void xmap_feed_free(xmap_feed *f) { delete f; }
 
 /* coarse ABI: the ratings of a feed -> the context (xmap_ctx_upload_ratings with the feed's arrays; `time` = the position of
- * the rating in the feed, like the Python engine, which keeps the time objects on the host) */
+ * the rating in the feed, like the Python engine, which keeps the time objects on the host).  The drop-in's rule
+ * (session.check_float32): a rating that float32 does not hold exactly is refused, naming the first such rating in CSR
+ * order; NaN passes.  The context is left as it was. */
 int xmap_ctx_upload_feed(xmap_ctx *ctx, const xmap_feed *f) {
     XM_ARG(ctx && f);
     const Feed &F = f->F;
     std::vector<float> r32(F.rating.size());
     std::vector<int64_t> tpos(F.rating.size());
-    for (size_t e = 0; e < F.rating.size(); e++) { r32[e] = (float)F.rating[e]; tpos[e] = (int64_t)e; }
+    for (size_t e = 0; e < F.rating.size(); e++) {
+        const double r = F.rating[e];
+        r32[e] = (float)r;
+        tpos[e] = (int64_t)e;
+        if ((double)r32[e] != r && !isnan(r)) {
+            const size_t u = (size_t)(std::upper_bound(F.ptr.begin(), F.ptr.end(), (int64_t)e) - F.ptr.begin()) - 1;
+            char val[32];
+            for (int p = 1; p <= 17; p++) {         // the shortest text that reads back as r (Python's repr)
+                snprintf(val, sizeof(val), "%.*g", p, r);
+                if (strtod(val, nullptr) == r) break;
+            }
+            set_error("rating %s of user '%s', item '%s' is not exactly representable as float32 (the engine's rating type); "
+                      "round the ratings to float32 first", val, F.uids[u].c_str(), F.iids[(size_t)F.item[e]].c_str());
+            return XMAP_ERR_ARG;
+        }
+    }
     static const int64_t zero = 0;
     return xmap_ctx_upload_ratings(ctx, (int64_t)F.uids.size(), (int32_t)F.iids.size(), F.ptr.empty() ? &zero : F.ptr.data(),
                                    F.item.data(), r32.data(), tpos.data(), F.prefix_cls.data(), F.suffix_cls.data(),
