@@ -348,11 +348,7 @@ struct TriArgs {
 // cosine (:91-95), significance weighting (:84-89), zero filter (:198,:207) for one accumulated pair
 template <int METHOD>
 __device__ __forceinline__ bool finish_pair(const TriArgs &A, int i, int j, int n, int m, double dot, double &simv) {
-#ifdef EXP_NONRM      // attribution builds (profiles/tools/a_variants.sh), never shipped
-    const double np = A.nrm[i] * A.nrm[i];
-#else
     const double np = A.nrm[i] * A.nrm[j];
-#endif
     const double cs = (np != 0.0) ? 1.0 * dot / np : 0.0;
     const int mn = n < A.cap ? n : A.cap;
     simv = 1.0 * cs * (double)mn / (double)A.cap;
@@ -403,10 +399,8 @@ __device__ __forceinline__ void append_pairs(const TriArgs &A, int i, int s_begi
         if (keep) {
             long long p = (long long)base + __popcll(km & lanemask_lt());
             A.coo_i[p] = i; A.coo_j[p] = j;
-#ifndef EXP_NOCOO     // (indices still written: the mirror reads them)
             A.coo_sim[p] = sv; A.coo_mutu[p] = m; A.coo_nij[p] = n;
             if (A.coo_aux) A.coo_aux[p] = aux(s0 + lane);
-#endif
         }
         base += __popcll(km);
     }
@@ -448,19 +442,10 @@ __device__ __forceinline__ unsigned long long ls_key(double d) {
     return (d != d) ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(d);
 }
 
-// -DA_TRACE: per-unit time stamps (profiles/tools/trace_a.py reads them): a unit of the smallest class lives ~14 us -- 2.0 us
+// Per-unit time stamps (round 3, profiles/r03c_pair_trace.txt): a unit of the smallest class lives ~14 us -- 2.0 us
 // until its item / partition / rater range are read, 3.4 us until the first rater records and prefixes are in, 9.7 us
 // until its (single) step of 8 raters is in the table, 4.3 us of finalisation and appends -- and holds its LDS table
 // all that time; LDS capacity x unit lifetime (79 GB us over 41 MB of LDS = 1.9 ms) is what bounds the class launches.
-#ifdef A_TRACE
-__device__ unsigned long long g_atrace[1 << 21][2];   // per light unit: begin, end (wall_clock64, 100 MHz)
-__device__ unsigned int g_astamp[1 << 21][4];          // offsets from begin: unit read, first rater records in, walk done
-struct ATraceEnd { long long u; long long t0;
-    __device__ ~ATraceEnd() { if (threadIdx.x == 0 && u < (1 << 21)) { g_atrace[u][0] = (unsigned long long)t0; g_atrace[u][1] = wall_clock64(); } } };
-#define A_STAMP(k) do { if (threadIdx.x == 0 && unit < (1 << 21)) g_astamp[unit][k] = (unsigned)(wall_clock64() - (unsigned long long)tr_.t0); } while (0)
-#else
-#define A_STAMP(k) do {} while (0)
-#endif
 // A field of the kernel's argument struct, read from the kernarg segment where it is used (a volatile scalar load: it stays
 // at that place).  The finalisation needs seventeen pointers the walk never touches; as plain uses of A they are all loaded
 // at the kernel's entry and kept -- 101 SGPRs, i.e. 7 waves per SIMD, or ~100 v_writelane / v_readlane spill moves per unit
@@ -468,19 +453,10 @@ struct ATraceEnd { long long u; long long t0;
 // KARG reads at offsetof(TriArgs, field) from the kernarg base: correct only while the struct is the kernel's FIRST and ONLY
 // parameter (k_pair_tri(TriArgs A), k_pair_heavy(TriArgs A)): keep it so.
 static_assert(std::is_standard_layout<TriArgs>::value, "KARG() addresses TriArgs fields by offsetof");
-#ifdef EXP_NOKARG
-#define KARG(field) (A.field)
-#else
 #define KARG(field) (*(decltype(TriArgs::field) const volatile __attribute__((address_space(4))) *)( \
     (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TriArgs, field)))
-#endif
 template <int METHOD, int LOG_SLOTS, int NW, bool LS>
-#ifdef EXP_NOMINW
-#define PAIR_MINW 1
-#else
-#define PAIR_MINW ((LOG_SLOTS == 7 && !LS) ? 8 : 1)
-#endif
-__global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   // (128 slots: 8 waves per SIMD fit, keep the SGPRs below the limit for that)
+__global__ __launch_bounds__(64 * NW, (LOG_SLOTS == 7 && !LS) ? 8 : 1) void k_pair_tri(TriArgs A) {   // (128 slots: 8 waves per SIMD fit, keep the SGPRs below the limit for that)
     constexpr int SLOTS_ = 1 << LOG_SLOTS;
     constexpr bool ADJ = METHOD == XMAP_ADJUST_COSINE;
     using RT = typename std::conditional<LS, double, float>::type;      // rating type of the profile copy and the rater records
@@ -505,9 +481,6 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
     const int lane = lane_id();
     const long long unit = A.unit_lo + blockIdx.x;
     if (unit >= A.unit_hi) return;
-#ifdef A_TRACE
-    ATraceEnd tr_{unit, (long long)wall_clock64()};
-#endif
     // the unit's record in one round trip: item; (partition, first rater, end of raters, partitions of the row)
     const int i = uniform(A.uq_item[unit]);
     const int4 ud = ((const int4 *)A.uq_q)[unit];
@@ -523,7 +496,6 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
     }
     const double nx = A.nrm[i];     // (for the finalisation: in flight during the walk)
     int ovf = 0;
-    A_STAMP(0);
 
     // walk(body): every co-rating of this unit's raters (those of hash partition q); body(act, j, jw, rj, ri, a, gei)
     // runs once per lane and 64 co-ratings.  Wave w takes every NW-th block of RB raters, one rater record per lane
@@ -531,17 +503,11 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
     // raters on average: blocks of 16 deal them out evenly -- a unit lives as long as its busiest wave, and holds its table
     // that long).  The prefixes of a block are walked as ONE flat list (round 2 gave each rater 8 lanes: half of the
     // lanes idle, one dependent load per 8 entries of the longest of eight prefixes, 10-18 us per unit of which the
-    // table work was a fraction -- profiles/tools/trace_a.py): an inclusive scan of the prefix lengths over the lanes, then
+    // table work was a fraction -- profiles/r03c_pair_trace.txt): an inclusive scan of the prefix lengths over the lanes, then
     // lane l of round t takes co-rating 64 t + l, finds its rater by binary search over the scan (log2 RB permutes) and loads
     // its entry; all loads of WU rounds are in flight together and every lane of every round but the last is busy.
-#ifndef EXP_RB       // (tuning builds: profiles/tools/a_variants.sh; shipped values below)
-#define EXP_RB 16
-#endif
-#ifndef EXP_WU
-#define EXP_WU 2
-#endif
-    constexpr int RB = (NW == 1 || NW == 16) ? 64 : EXP_RB;
-    constexpr int WU = EXP_WU;
+    constexpr int RB = (NW == 1 || NW == 16) ? 64 : 16;
+    constexpr int WU = 2;
     // Loads of the walk: every one is unconditional (a clamped index for a lane that has nothing to load) and nothing is
     // done with a loaded value before the loads that can go out with it are out -- a load under `if (act)`, or a select on a
     // freshly prefetched record, is waited for on the spot, which had put a block's record prefetch, the user averages and the
@@ -580,9 +546,6 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
             for (int d = 1; d < RB; d <<= 1) { const int v = __shfl_up(end, d, 64); if (lane >= d) end += v; }
             const int total = rl32(end, RB - 1);
             const int start = end - len;
-#ifdef A_TRACE
-            if (base == p0 + RB * w) A_STAMP(1);
-#endif
             for (int f0 = 0; f0 < total; f0 += 64 * WU) {
                 int jw[WU]; RT rj[WU]; bool act[WU]; double ri[WU], a[WU]; unsigned gei[WU];
                 int tt[WU], ee[WU], uu[WU];
@@ -602,9 +565,7 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
                 for (int u = 0; u < WU; u++) {
                     entry(ee[u], jw[u], rj[u]);
                     a[u] = 0.0;
-#ifndef EXP_NOUAVG
                     if (ADJ && !LS) a[u] = A.u_avg[uu[u]];
-#endif
                 }
 #pragma unroll
                 for (int u = 0; u < WU; u++) {
@@ -678,7 +639,6 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
             }
         }
     });
-    A_STAMP(2);
     if (NW > 1) {
         if (ovf) s_ovf = 1;
         __syncthreads();          // all raters are in the table (and every lock bit is clear again)
@@ -778,12 +738,7 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
         fa[t] = (ADJ && k_raw) ? dlo[sl] : 0.0;
         fy[t] = 0.0;
         if (fo[t]) {
-#ifdef EXP_NONRM
-            fy[t] = nx;
-#else
             if (!k_raw) fy[t] = k_nrm[kj];
-#endif
-
         }
     }
     int kept = 0, occ = 0;
@@ -822,10 +777,8 @@ __global__ __launch_bounds__(64 * NW, PAIR_MINW) void k_pair_tri(TriArgs A) {   
             const long long pp = (long long)cbase + __popcll(km & lanemask_lt());
             const int j = fj[t];
             k_coo_i[pp] = i; k_coo_j[pp] = j;
-#ifndef EXP_NOCOO
             k_coo_sim[pp] = fs[t]; k_coo_mutu[pp] = fm[t]; k_coo_nij[pp] = fn[t];
             if (k_coo_aux) k_coo_aux[pp] = fa[t];
-#endif
         }
         cbase += __popcll(km);
     }
@@ -2016,14 +1969,6 @@ int mirror_counts(hipStream_t st, int n_items, long long range_cap, int n_ranges
 }  // namespace
 
 extern "C" {
-#ifdef A_TRACE
-int xmap_debug_astamp(unsigned int *host, long long n_units) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(xmap::g_astamp), (size_t)n_units * 16);
-}
-int xmap_debug_atrace(unsigned long long *host, long long n_units) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(xmap::g_atrace), (size_t)n_units * 16);
-}
-#endif
 
 int xmap_sim2_layout(void *stream, const xmap_ratings *R, const double *info, int32_t ch_min, int32_t *hist /*[U+2]*/,
                      int64_t *pre /*[U+3]*/, int32_t *ctl /*[4]: CH, n_heavy*/, int32_t *hid, int32_t *hlist /*[1024]*/,

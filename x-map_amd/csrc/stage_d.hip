@@ -92,10 +92,7 @@ void k_dense_topk(int n_t, int n_s, int n_tiles, long long share, int n_pieces, 
     __shared__ __attribute__((aligned(16))) float Bs[2][D_GROUP * D_TILE][K + 4];   // row stride K+4: conflict-free ds_read_b128
 
     const int w = uniform((int)(threadIdx.x >> 6)), lane = lane_id();      // (uniform: the schedule's branches are scalar ones)
-    const bool late = w >= D_WAVES / 2;   // waves w and w + 4 share a SIMD (checked with HW_REG_HW_ID, build -DD_TRACE)
-#ifdef D_TRACE
-    const unsigned long long rt0 = wall_clock64();
-#endif
+    const bool late = w >= D_WAVES / 2;   // waves w and w + 4 share a SIMD (checked once with HW_REG_HW_ID stamps)
     const long long total = (long long)((n_t + D_ROWS - 1) / D_ROWS) * n_tiles;
     const long long w_lo = blockIdx.x * share;
     const long long w_hi = min(total, w_lo + share);
@@ -188,9 +185,6 @@ void k_dense_topk(int n_t, int n_s, int n_tiles, long long share, int n_pieces, 
             m[r] = __builtin_amdgcn_fcmpf(fabsf(acc[r]), thr[r], 3) & jm;
             any |= m[r];
         }
-#ifdef D_NOINSERT
-        if (any == 0x123456789abcull) out_val[1] = 1.f;
-#else
         if (any) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
@@ -201,7 +195,6 @@ void k_dense_topk(int n_t, int n_s, int n_tiles, long long share, int n_pieces, 
                 }
             }
         }
-#endif
     };
 
     const int n_groups = ((s_hi - s_lo + D_TILE - 1) / D_TILE + D_GROUP - 1) / D_GROUP;
@@ -224,15 +217,8 @@ void k_dense_topk(int n_t, int n_s, int n_tiles, long long share, int n_pieces, 
 #pragma nounroll
             for (int sub = 0; sub < 2; sub++) {
                 if ((sub == 0) == late && pend) {
-#ifdef D_NORANK
-                    float sacc = 0.f;
-#pragma unroll
-                    for (int r = 0; r < 16; r++) sacc += acc0[r] + acc1[r];
-                    if (sacc == 123.456f) out_val[0] = sacc;
-#else
                     rank_tile(acc0, pend_c0);
                     rank_tile(acc1, pend_c0 + D_TILE);
-#endif
                     pend = false;
                 }
                 if (sub == 0 && g < n_groups && c0 < s_hi) {
@@ -279,16 +265,6 @@ void k_dense_topk(int n_t, int n_s, int n_tiles, long long share, int n_pieces, 
         }
     }
     }   // segments
-#ifdef D_TRACE
-    if (lane == 0) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        unsigned long long *tr = (unsigned long long *)out_val;
-        const size_t o = ((size_t)blockIdx.x * D_WAVES + w) * 4;
-        tr[o + 0] = rt0; tr[o + 1] = wall_clock64(); tr[o + 2] = hw; tr[o + 3] = xcc;
-    }
-#endif
 }
 
 // fold the n_split sorted partial lists of a row (wave per row): a candidate's final rank is the sum over the lists of

@@ -1042,13 +1042,12 @@ class Engine(object):
         slot_budget = min(int(float(os.environ.get("XMAP_SLOT_BUDGET_GB", "120")) * (1 << 30)), int(0.45 * self.hbm_available("qacc")))
         if "XMAP_N_SLOTS" in os.environ:
             n_slots = int(os.environ["XMAP_N_SLOTS"])
-        else:       # one row per wave the kernel keeps resident (4 per SIMD since round 4)
+        else:       # one row per wave the kernel keeps resident (P_WAVES per SIMD: csrc/paths4.hip)
             ns = C.c_int32(0)
             check(lib.xmap_extend_cols_slots(C.byref(ns)))
             n_slots = min(n_slots, int(ns.value))
         n_slots = int(max(4, min(n_slots, slot_budget // (36 * nU), max(U.n_units, 4))))
-        abl = int(os.environ.get("XMAP_ABL_ROW_ENTRIES", "0"))     # (ablation builds of k_paths4 with longer rows, -DQ_STORE)
-        acc = self._zero_scratch("qacc", n_slots * max(nU, abl) * 4, torch.float64)
+        acc = self._zero_scratch("qacc", n_slots * nU * 4, torch.float64)
         touched = self._empty(n_slots * nU, torch.int32)
         hacc = self._zero_scratch("qhacc", max(U.n_rows, 1) * nU * 4, torch.float64) if U.n_rows else None
         htouched = self._empty(max(U.n_rows, 1) * nU, torch.int32) if U.n_rows else None
