@@ -6,7 +6,10 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail]
+
+--device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
+(xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.
 """
 import argparse
 import os
@@ -68,6 +71,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=31)
     ap.add_argument("--workdir", default="/tmp/xmap_demo")
     ap.add_argument("--private", action="store_true")
+    ap.add_argument("--device-tail", action="store_true")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -101,12 +105,18 @@ def main(argv=None):
     rsim = RecommenderSim(rc["calculate_xmap_sim_method"], rc["calculate_xmap_weighting"])
     rpriv = RecommenderPrivacy(rc["mapping_range"], rc["private_epsilon"], rc["private_rpo"])
     rpred = RecommenderPrediction(rc["decay_alpha"], rc["calculate_xmap_sim_method"])
-    _, _, ubd, ibd, uinfo, iinfo, alterEgo_sim = timed(
-        "recommender_sim", assist.recommender_calculate_sim_pipeline, sc, rsim, alterEgo_profile)
-    kept = timed("recommender_privacy", assist.recommender_privacy_pipeline, rpriv, alterEgo_sim, rc["private_flag"])
-    simpair_bd = sc.broadcast(kept.collectAsMap())
-    mae = timed("recommender_prediction", assist.recommender_prediction_pipeline, rpred, rsim, testRDD, simpair_bd,
-                ubd, ibd, uinfo, iinfo)
+    if args.device_tail and not rc["private_flag"]:
+        from xmap.engine import session
+        predicted = timed("recommender_device_tail", session.recommend, alterEgo_profile, testRDD, rc["calculate_xmap_weighting"],
+                          rc["mapping_range"], rc["decay_alpha"])
+        mae = rpred.calculate_mae(predicted)
+    else:
+        _, _, ubd, ibd, uinfo, iinfo, alterEgo_sim = timed(
+            "recommender_sim", assist.recommender_calculate_sim_pipeline, sc, rsim, alterEgo_profile)
+        kept = timed("recommender_privacy", assist.recommender_privacy_pipeline, rpriv, alterEgo_sim, rc["private_flag"])
+        simpair_bd = sc.broadcast(kept.collectAsMap())
+        mae = timed("recommender_prediction", assist.recommender_prediction_pipeline, rpred, rsim, testRDD, simpair_bd,
+                    ubd, ibd, uinfo, iinfo)
     assist.write_to_disk({"mae": mae}, para, os.path.join(args.workdir, "data", "output"))
     sc.stop()
     print("train users %d, test users %d, sim pairs %d, AlterEgo rows %d" % (

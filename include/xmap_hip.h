@@ -543,6 +543,35 @@ int xmap_predict(void *stream, int64_t n_test, const int32_t *test_user, const i
                  const double *rt_time, const double *item_avg, const double *wtab, int32_t n_w, double *out_plain,
                  double *out_decay, int32_t *status);
 
+/* ---- the device-resident recommender tail (csrc/stage_e_rows.hip): AlterEgo rows -> profiles -> prediction -> MAE, no host
+ * conversion in between.
+ * xmap_rec_profiles: the rows of xmap_alterego_fill (pass-through segment [0, n_target_rows), then the mapped segment, each in
+ *   user order; off_t / off_m [U+1] = the exclusive scans of xmap_alterego_count's counts that the fill pass took) -> user-major
+ *   profiles prof_ptr [U+1], prof_item / prof_rating / prof_time [n_rows]: a user's rows contiguous, in stage-C row order
+ *   (its pass-through rows, then its mapped rows).  Item indices are unchanged (the engine's index space), so the profiles
+ *   are the CSR that xmap_sim3_layout takes with rating64 = prof_rating (RecommenderSim).
+ * xmap_predict_rows: RecommenderPrediction.item_based_prediction (core/recommenderPrediction.py:26-105), one wave per test
+ *   pair.  Neighbour lists in the layout xmap_rec_select writes: nb_cnt [I] (<= 0: the item has no list, status 1),
+ *   nb_col / nb_sim [I][keep], keep <= 64; evidence = for each neighbour in list order the rows of the test user's profile
+ *   that hold it, in profile order (user test = equality of indices; test_user outside [0, n_users): a user without rows);
+ *   item_avg [I]; wtab[d] = exp(-alpha d), d = 0 .. n_w - 1, made by the caller.  Sums left to right in fp64, decayed sums in
+ *   stable time order, equal times share a rank, now = ranks + 1, bound_rating -- the Python statement bit for bit.  No limit
+ *   on the evidence of a pair (more than 128 entries: a second launch stages them in a temporary sized by the first).
+ *   status: 0 predicted, 1 no neighbour list, 2 the Python statement raises here (zero weight sum, non-finite value) or
+ *   now > n_w.  *h_max_now (may be NULL) = the largest `now` met: a table of that many entries serves every pair.  Syncs.
+ * xmap_mae: calculate_mae (:107-139) over the pairs with status 0: mae[0] = their count, mae[1] = sum |real - plain|,
+ *   mae[2] = sum |real - decayed| (device, 3 doubles); exact double-double sums rounded once, independent of the order. */
+int xmap_rec_profiles(void *stream, int64_t n_users, int64_t n_rows, int64_t n_target_rows, const int64_t *off_t, const int64_t *off_m,
+                      const int32_t *user, const int32_t *item, const double *rating, const int64_t *time, int64_t *prof_ptr,
+                      int32_t *prof_item, double *prof_rating, int64_t *prof_time);
+int xmap_predict_rows(void *stream, int64_t n_test, const int32_t *test_user, const int32_t *test_item, int64_t n_users,
+                      int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col, const double *nb_sim,
+                      const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time,
+                      const double *item_avg, const double *wtab, int32_t n_w, double *out_plain, double *out_decay,
+                      int32_t *status, int32_t *h_max_now);
+int xmap_mae(void *stream, int64_t n_test, const int32_t *status, const double *real, const double *out_plain, const double *out_decay,
+             double *mae /*[3], device*/);
+
 /* ---- stage C: generator_pipeline (utils/assist.py:136-150) ---------------------------------- */
 
 /* Generator.cross_private_mapping / cross_nonprivate_mapping (core/generator.py:27-111) + map_to_dict
@@ -582,6 +611,22 @@ int xmap_alterego_fill(void *stream, const xmap_ratings *R, const int32_t *map_s
  *   xmap_ctx_generate       : generator_pipeline (assist.py:136-150): private: arg-max |xsim|; else picks [I];
  *                             choice [I] (or NULL) receives the chosen source item per start (-1: none)
  *   xmap_ctx_gen_download   : AlterEgo rows (user, item, rating fp64, time), pass-through target rows first
+ * The recommender tail over those rows, all on the device (call order: generate -> rec_sim -> rec_select or
+ * rec_set_neighbors -> predict; any of item_sim / extend / generate / upload drops the tail):
+ *   xmap_ctx_rec_sim        : recommender_calculate_sim_pipeline (assist.py:153-177): user-major profiles of the AlterEgo
+ *                             rows, then RecommenderSim (cosine branch, cap) -> n_pairs directed pairs, a self pair once
+ *   xmap_ctx_rec_profiles_download : the profiles (prof_ptr [U+1], item / rating / time [n_rows]); any pointer may be NULL
+ *   xmap_ctx_rec_download   : CSR by first item (row_ptr [I+1]; col / sim / ls / n_ij [n_pairs]; rows not sorted), per-item
+ *                             average of the AlterEgo ratings and norm [I]; any pointer may be NULL
+ *   xmap_ctx_rec_select     : nonprivate_neighbor_selection (recommenderPrivacy.py:22-35), keep <= 64
+ *   xmap_ctx_rec_set_neighbors : neighbour lists made by the host instead (the private selection, perturbed similarities):
+ *                             cnt [I], col / sim [I][keep]
+ *   xmap_ctx_rec_neighbors_download : cnt [I], col / sim / ls [I][keep] (ls = 0 for host-made lists); NULL = skip
+ *   xmap_ctx_predict        : recommender_prediction_pipeline (assist.py:195-207): n_test pairs (user, item); wtab = the
+ *                             caller's exp(-alpha d), d = 0 .. n_w - 1; out_plain / out_decay / status [n_test] as
+ *                             xmap_predict_rows; test_rating may be NULL, else mae [3] (may be NULL) = {predicted pairs,
+ *                             sum |real - plain|, sum |real - decayed|}; *max_now (may be NULL) = table length that serves
+ *                             every pair (status 2 pairs of a shorter table: call again with a longer one)
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -629,6 +674,16 @@ int xmap_ctx_candidates(xmap_ctx *ctx, int32_t *n_top);
 int xmap_ctx_generate(xmap_ctx *ctx, int private_flag, const int32_t *picks, int32_t *choice, int64_t *n_rows,
                       int64_t *n_target_rows);
 int xmap_ctx_gen_download(xmap_ctx *ctx, int32_t *user, int32_t *item, double *rating, int64_t *time);
+int xmap_ctx_rec_sim(xmap_ctx *ctx, int cap, int64_t *n_pairs);
+int xmap_ctx_rec_profiles_download(xmap_ctx *ctx, int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time);
+int xmap_ctx_rec_download(xmap_ctx *ctx, int64_t *row_ptr, int32_t *col, double *sim, double *ls, int32_t *nij, double *item_avg,
+                          double *item_norm);
+int xmap_ctx_rec_select(xmap_ctx *ctx, int keep);
+int xmap_ctx_rec_set_neighbors(xmap_ctx *ctx, int keep, const int32_t *cnt, const int32_t *col, const double *sim);
+int xmap_ctx_rec_neighbors_download(xmap_ctx *ctx, int32_t *cnt, int32_t *col, double *sim, double *ls);
+int xmap_ctx_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                     const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
+                     int32_t *max_now);
 
 #ifdef __cplusplus
 }

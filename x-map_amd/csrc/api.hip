@@ -4,6 +4,8 @@
 //   xmap_ctx_create -> xmap_ctx_upload_ratings -> xmap_ctx_item_sim     (baseliner_calculate_sim_pipeline, assist.py:66-77)
 //                                              -> xmap_ctx_extend       (extender_pipeline, assist.py:80-102; lazy lists)
 //                                              -> xmap_ctx_generate     (generator_pipeline, assist.py:136-150)
+//   the recommender tail over the AlterEgo rows, device-resident:   -> xmap_ctx_rec_sim (assist.py:153-177)
+//                     -> xmap_ctx_rec_select | xmap_ctx_rec_set_neighbors (assist.py:179-192) -> xmap_ctx_predict (assist.py:195-207)
 //   xmap_ctx_*_download copy results into caller-allocated host buffers whose sizes the stage call reported.
 //
 // Everything below is orchestration of the kernels' own entry points (include/xmap_hip.h): buffer sizes, prefix sums,
@@ -62,6 +64,20 @@ struct xmap_ctx {
     double *g_rating = nullptr;
     int64_t *g_time = nullptr;
     int64_t n_rows = 0, n_target_rows = 0;
+    int64_t *g_off_t = nullptr, *g_off_m = nullptr;     // per-user offsets of the two row segments (exclusive scans, [U+1])
+    // the recommender tail: profiles of the AlterEgo rows, RecommenderSim over them, neighbour lists
+    Pool p_rec, p_nb;
+    bool have_rec = false, have_nb = false;
+    int64_t *pf_ptr = nullptr, *pf_time = nullptr;
+    int32_t *pf_item = nullptr;
+    double *pf_rating = nullptr;
+    int64_t *rs_row_ptr = nullptr;
+    int32_t *rs_col = nullptr, *rs_nij = nullptr;
+    double *rs_sim = nullptr, *rs_ls = nullptr, *rs_avg = nullptr, *rs_norm = nullptr;
+    int64_t rec_pairs = 0;
+    int keep = 0;
+    int32_t *nb_cnt = nullptr, *nb_col = nullptr;
+    double *nb_sim = nullptr, *nb_ls = nullptr;
 };
 
 namespace xmap {
@@ -90,6 +106,12 @@ template <typename T>
 static int d2h(T *host, const T *dev, size_t n, hipStream_t st) {
     if (n) XM_HIP(hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, st));
     return XMAP_OK;
+}
+
+// any earlier stage run again invalidates the recommender tail (as the stages invalidate each other)
+static void drop_tail(xmap_ctx *c) {
+    c->p_nb.release(); c->p_rec.release();
+    c->have_rec = c->have_nb = false;
 }
 
 // one reverse adjacency: count -> scan -> fill
@@ -187,6 +209,7 @@ void xmap_ctx_destroy(xmap_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->st);
+    drop_tail(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_rows.release(); c->p_ratings.release();
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
@@ -220,6 +243,7 @@ int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const
                             const uint32_t *contains_mask, const uint8_t *flags) {
     XM_ARG(c && user_ptr && prefix_cls && suffix_cls && contains_mask && flags && n_users >= 0 && n_items >= 0);
     XM_HIP(hipSetDevice(c->device));
+    drop_tail(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_ratings.release();
     c->have_sim = c->have_ext = c->have_gen = false;
     const int64_t nnz = user_ptr[n_users];
@@ -258,6 +282,7 @@ int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const
 int xmap_ctx_item_sim(xmap_ctx *c, int method, int cap, int64_t *n_kept, int64_t *n_evaluated) {
     XM_ARG(c && c->have_ratings && (method == XMAP_COSINE || method == XMAP_ADJUST_COSINE) && cap > 0);
     XM_HIP(hipSetDevice(c->device));
+    drop_tail(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release();
     c->have_sim = c->have_ext = c->have_gen = false;
     xmap_ratings &R = c->R;
@@ -386,6 +411,7 @@ int xmap_ctx_sim_download(xmap_ctx *c, int64_t *row_ptr, int32_t *col, double *s
 int xmap_ctx_extend(xmap_ctx *c, int top_k, int64_t *n_out, int64_t *n_paths) {
     XM_ARG(c && c->have_sim && top_k >= 1);
     XM_HIP(hipSetDevice(c->device));
+    drop_tail(c);
     c->p_gen.release(); c->p_ext.release();
     c->have_ext = c->have_gen = false;
     const int I = c->R.n_items, k = top_k;
@@ -546,6 +572,7 @@ int xmap_ctx_candidates(xmap_ctx *c, int32_t *n_top) {
 int xmap_ctx_generate(xmap_ctx *c, int private_flag, const int32_t *picks, int32_t *choice, int64_t *n_rows, int64_t *n_target_rows) {
     XM_ARG(c && c->have_ext);
     XM_HIP(hipSetDevice(c->device));
+    drop_tail(c);
     c->p_gen.release();
     c->have_gen = false;
     const int I = c->R.n_items;
@@ -566,6 +593,7 @@ int xmap_ctx_generate(xmap_ctx *c, int private_flag, const int32_t *picks, int32
     XM_TRY(xmap_alterego_fill(c->st, &c->R, d_map, off_t, off_m, nt, c->g_user, c->g_item, c->g_rating, c->g_time));
     XM_HIP(hipStreamSynchronize(c->st));
     c->n_rows = n; c->n_target_rows = nt;
+    c->g_off_t = off_t; c->g_off_m = off_m;
     c->have_gen = true;
     if (n_rows) *n_rows = n;
     if (n_target_rows) *n_target_rows = nt;
@@ -580,6 +608,252 @@ int xmap_ctx_gen_download(xmap_ctx *c, int32_t *user, int32_t *item, double *rat
     if (item) XM_TRY(d2h(item, (const int32_t *)c->g_item, n, c->st));
     if (rating) XM_TRY(d2h(rating, (const double *)c->g_rating, n, c->st));
     if (time) XM_TRY(d2h(time, (const int64_t *)c->g_time, n, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+// ---- the recommender tail ---------------------------------------------------------------------------------------------
+
+int xmap_ctx_rec_sim(xmap_ctx *c, int cap, int64_t *n_pairs) {
+    XM_ARG(c && c->have_gen && cap > 0);
+    XM_HIP(hipSetDevice(c->device));
+    drop_tail(c);
+    const int I = c->R.n_items;
+    const int64_t U = c->R.n_users, nnz = c->n_rows;
+    XM_ARG(nnz < 2147483647ll);
+    const size_t n1 = (size_t)(nnz ? nnz : 1), i1 = (size_t)(I ? I : 1);
+    // (a) user-major profiles in stage-C row order
+    XM_ALLOCZ(c->p_rec, c->pf_ptr, U + 1);
+    XM_ALLOC(c->p_rec, c->pf_item, n1); XM_ALLOC(c->p_rec, c->pf_rating, n1); XM_ALLOC(c->p_rec, c->pf_time, n1);
+    XM_TRY(xmap_rec_profiles(c->st, U, nnz, c->n_target_rows, c->g_off_t, c->g_off_m, c->g_user, c->g_item, c->g_rating, c->g_time,
+                             c->pf_ptr, c->pf_item, c->pf_rating, c->pf_time));
+    XM_ALLOCZ(c->p_rec, c->rs_row_ptr, I + 1);
+    XM_ALLOCZ(c->p_rec, c->rs_avg, i1); XM_ALLOCZ(c->p_rec, c->rs_norm, i1);
+    c->rec_pairs = 0;
+    if (I == 0 || nnz == 0) {
+        XM_HIP(hipStreamSynchronize(c->st));
+        c->have_rec = true;
+        if (n_pairs) *n_pairs = 0;
+        return XMAP_OK;
+    }
+    std::vector<int64_t> h_ptr((size_t)U + 1);
+    XM_TRY(d2h(h_ptr.data(), (const int64_t *)c->pf_ptr, (size_t)U + 1, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    int64_t half_contrib = 0;
+    for (int64_t u = 0; u < U; u++) { const int64_t d = h_ptr[u + 1] - h_ptr[u]; half_contrib += d * (d - 1) / 2; }
+    Pool tmp;
+    struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
+#define T_ALLOC(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), c->st))
+#define T_ALLOCZ(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), c->st, true))
+    // the profiles as the ratings of the pair machinery: fp64 ratings (wide records), zero user average, no heavy set
+    xmap_ratings P = c->R;
+    float *f_dummy, *f_irating;
+    int64_t *item_ptr;
+    int32_t *i_user;
+    T_ALLOCZ(f_dummy, n1); T_ALLOCZ(f_irating, n1); T_ALLOCZ(item_ptr, I + 1); T_ALLOCZ(i_user, n1);
+    P.nnz = nnz; P.user_ptr = c->pf_ptr; P.user_item = c->pf_item; P.user_rating = f_dummy; P.user_time = c->pf_time;
+    P.item_ptr = item_ptr; P.item_user = i_user; P.item_rating = f_irating;
+    int32_t *cnt, *hist, *ctl, *hid, *hlist;
+    int64_t *pre;
+    uint64_t *ub_key, *ub, *rcrec, *Wp, *srec, *buf_a, *buf_b;
+    double *u_avg, *info, *norms;
+    T_ALLOC(cnt, i1); T_ALLOCZ(u_avg, U ? U : 1); T_ALLOCZ(info, i1 * 4); T_ALLOCZ(norms, 2 * i1);
+    T_ALLOC(hist, U + 2); T_ALLOC(pre, U + 3); T_ALLOC(ctl, 4); T_ALLOC(hid, i1); T_ALLOCZ(hlist, 1024);
+    T_ALLOC(ub_key, n1); T_ALLOC(ub, 2 * n1); T_ALLOC(rcrec, 2 * n1); T_ALLOC(Wp, i1);
+    T_ALLOC(srec, 3 * n1); T_ALLOC(buf_a, 3 * n1); T_ALLOC(buf_b, 3 * n1);
+    const int ch_min = (int)((U + 2 > 64) ? U + 2 : 64);        // more raters than users: no item is heavy
+    XM_TRY(xmap_sim3_layout(c->st, &P, item_ptr, c->pf_rating, ch_min, 1 | 2 | 4, 0, I, cnt, u_avg, nullptr, hist, pre, ctl, hid, hlist,
+                            ub_key, ub, srec, buf_a, buf_b, rcrec, Wp, info, norms, nullptr));
+    int32_t *Q, *Cc, *Qcat, *uq_item = nullptr, *uq_q = nullptr, *uc_item = nullptr, *uc_c = nullptr;
+    uint8_t *small;
+    int64_t *uq_ptr, *uc_ptr;
+    T_ALLOCZ(Q, i1); T_ALLOCZ(Cc, i1); T_ALLOCZ(small, i1); T_ALLOC(Qcat, 5 * i1); T_ALLOCZ(uq_ptr, (size_t)5 * I + 1);
+    T_ALLOCZ(uc_ptr, I + 1);
+    int slot_target = 768;
+    double coo_slack = 1.0;
+    int64_t hc[10];
+    int64_t n_light = 0;
+    auto plan = [&](int target) -> int {
+        const int64_t cap_light = half_contrib / target + I + 1, cap_heavy = nnz / ch_min + 1025;
+        T_ALLOC(uq_item, cap_light); T_ALLOC(uq_q, 4 * cap_light); T_ALLOC(uc_item, cap_heavy); T_ALLOC(uc_c, cap_heavy);
+        XM_TRY(xmap_sim3_plan(c->st, &P, target, pre, hid, ctl, Q, Cc, small, Wp, Qcat, uq_ptr, uc_ptr, 1, uq_item, uq_q, uc_item, uc_c,
+                              cap_light, cap_heavy, hc));
+        n_light = hc[0];
+        return XMAP_OK;
+    };
+    XM_TRY(plan(slot_target));
+    int32_t *coo_i = nullptr, *coo_j = nullptr, *coo_mutu = nullptr, *coo_nij = nullptr, *own = nullptr, *mir = nullptr;
+    double *coo_sim = nullptr, *coo_ls = nullptr;
+    int64_t *d_shards = nullptr;
+    int64_t cap_coo = 0, n = 0;
+    for (;;) {
+        cap_coo = ((int64_t)((double)(half_contrib > 0 ? half_contrib : 1) * coo_slack) / 4096 + 1100) * 4096;
+        double *hp_hi, *hp_lo;
+        int32_t *hp_cnt, *hp_mut, *rowcnt_h;
+        int64_t *d_cnt;
+        T_ALLOC(coo_i, cap_coo); T_ALLOC(coo_j, cap_coo); T_ALLOC(coo_sim, cap_coo); T_ALLOC(coo_mutu, cap_coo); T_ALLOC(coo_nij, cap_coo);
+        T_ALLOC(coo_ls, cap_coo); T_ALLOC(own, i1); T_ALLOC(mir, i1);
+        T_ALLOC(hp_hi, 1024); T_ALLOC(hp_lo, 1024); T_ALLOC(hp_cnt, 1024); T_ALLOC(hp_mut, 1024);
+        T_ALLOCZ(d_cnt, 6); T_ALLOC(d_shards, 2 * 4096); T_ALLOC(rowcnt_h, 64 * 1024);
+        // the RecommenderSim variant of the pair kernels: exact sums, nothing filtered, self pairs, local sensitivities
+        XM_TRY(xmap_sim2_pairs(c->st, &P, XMAP_ADJUST_COSINE, cap, u_avg, norms, rcrec, ub, Q, small, uq_item, uq_q, hc + 2, 0, n_light, hid,
+                               hlist, ctl, Cc, uc_ptr, uc_item, uc_c, 0, 0, 8 | 2 | 16 | 64 | 128, hp_hi, hp_lo, hp_cnt, hp_mut, cap_coo,
+                               coo_i, coo_j, coo_sim, coo_mutu, coo_nij, coo_ls, own, rowcnt_h, d_shards, d_cnt, mir));
+        int64_t h_cnt[6];
+        XM_TRY(d2h(h_cnt, d_cnt, 6, c->st));
+        XM_HIP(hipStreamSynchronize(c->st));
+        if (h_cnt[2]) {
+            if (slot_target <= 32) { set_error("pair-table overflow"); return XMAP_ERR_OVERFLOW; }
+            slot_target /= 2;
+            XM_TRY(plan(slot_target));
+            continue;
+        }
+        if (h_cnt[3]) {
+            if (coo_slack > 64) { set_error("half-COO overflow"); return XMAP_ERR_CAPACITY; }
+            coo_slack *= 2;
+            continue;
+        }
+        n = h_cnt[4];
+        break;
+    }
+    // mirror: row = [own | mirrored], the local sensitivity travels along; a self pair is one entry
+    int64_t *mptr;
+    T_ALLOCZ(mptr, I + 1);
+    const size_t kept_max = (size_t)(n ? 2 * n : 1), nn = (size_t)(n ? n : 1);
+    int32_t *mutu, *fill, *tot;
+    uint64_t *mir_a, *mir_b;
+    XM_ALLOC(c->p_rec, c->rs_col, kept_max); XM_ALLOC(c->p_rec, c->rs_sim, kept_max); XM_ALLOC(c->p_rec, c->rs_nij, kept_max);
+    XM_ALLOC(c->p_rec, c->rs_ls, kept_max);
+    T_ALLOC(mutu, kept_max); T_ALLOC(fill, i1); T_ALLOC(tot, i1); T_ALLOC(mir_a, 4 * nn); T_ALLOC(mir_b, 4 * nn);
+    XM_TRY(xmap_sim3_mircount(c->st, I, cap_coo, coo_i, coo_j, d_shards, n, 1, mir_a, mir));
+    XM_TRY(xmap_sim3_mirror(c->st, I, cap_coo, coo_i, coo_j, coo_sim, coo_mutu, coo_nij, d_shards, n, own, mir, tot, c->rs_row_ptr, mptr, fill,
+                            mir_a, mir_b, c->rs_col, c->rs_sim, mutu, c->rs_nij, coo_ls, c->rs_ls, 0, I));
+    // the item averages the prediction reads are the layout's (exact sum / n), the norms its adjusted norms (zero user average)
+    XM_HIP(hipMemcpy2DAsync(c->rs_avg, sizeof(double), info, 4 * sizeof(double), sizeof(double), (size_t)I, hipMemcpyDeviceToDevice, c->st));
+    XM_HIP(hipMemcpyAsync(c->rs_norm, norms + I, sizeof(double) * (size_t)I, hipMemcpyDeviceToDevice, c->st));
+    int64_t kept = 0;
+    XM_TRY(d2h(&kept, (const int64_t *)(c->rs_row_ptr + I), 1, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    c->rec_pairs = kept;
+    c->have_rec = true;
+    if (n_pairs) *n_pairs = kept;
+    return XMAP_OK;
+#undef T_ALLOC
+#undef T_ALLOCZ
+}
+
+int xmap_ctx_rec_profiles_download(xmap_ctx *c, int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time) {
+    XM_ARG(c && c->have_rec);
+    XM_HIP(hipSetDevice(c->device));
+    const size_t n = (size_t)c->n_rows;
+    if (prof_ptr) XM_TRY(d2h(prof_ptr, (const int64_t *)c->pf_ptr, (size_t)c->R.n_users + 1, c->st));
+    if (prof_item) XM_TRY(d2h(prof_item, (const int32_t *)c->pf_item, n, c->st));
+    if (prof_rating) XM_TRY(d2h(prof_rating, (const double *)c->pf_rating, n, c->st));
+    if (prof_time) XM_TRY(d2h(prof_time, (const int64_t *)c->pf_time, n, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+int xmap_ctx_rec_download(xmap_ctx *c, int64_t *row_ptr, int32_t *col, double *sim, double *ls, int32_t *nij, double *item_avg,
+                          double *item_norm) {
+    XM_ARG(c && c->have_rec);
+    XM_HIP(hipSetDevice(c->device));
+    const size_t I = (size_t)c->R.n_items, n = (size_t)c->rec_pairs;
+    if (row_ptr) XM_TRY(d2h(row_ptr, (const int64_t *)c->rs_row_ptr, I + 1, c->st));
+    if (col) XM_TRY(d2h(col, (const int32_t *)c->rs_col, n, c->st));
+    if (sim) XM_TRY(d2h(sim, (const double *)c->rs_sim, n, c->st));
+    if (ls) XM_TRY(d2h(ls, (const double *)c->rs_ls, n, c->st));
+    if (nij) XM_TRY(d2h(nij, (const int32_t *)c->rs_nij, n, c->st));
+    if (item_avg) XM_TRY(d2h(item_avg, (const double *)c->rs_avg, I, c->st));
+    if (item_norm) XM_TRY(d2h(item_norm, (const double *)c->rs_norm, I, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+static int alloc_neighbors(xmap_ctx *c, int keep) {
+    c->p_nb.release();
+    c->have_nb = false;
+    const size_t m = (size_t)(c->R.n_items ? c->R.n_items : 1) * keep;
+    XM_ALLOCZ(c->p_nb, c->nb_cnt, c->R.n_items ? c->R.n_items : 1);
+    XM_ALLOCZ(c->p_nb, c->nb_col, m); XM_ALLOCZ(c->p_nb, c->nb_sim, m); XM_ALLOCZ(c->p_nb, c->nb_ls, m);
+    c->keep = keep;
+    return XMAP_OK;
+}
+
+int xmap_ctx_rec_select(xmap_ctx *c, int keep) {
+    XM_ARG(c && c->have_rec && keep >= 1 && keep <= 64);
+    XM_HIP(hipSetDevice(c->device));
+    XM_TRY(alloc_neighbors(c, keep));
+    if (c->rec_pairs > 0)
+        XM_TRY(xmap_rec_select(c->st, c->R.n_items, c->rs_row_ptr, c->rs_col, c->rs_sim, c->rs_ls, keep, c->nb_cnt, c->nb_col, c->nb_sim,
+                               c->nb_ls));
+    XM_HIP(hipStreamSynchronize(c->st));
+    c->have_nb = true;
+    return XMAP_OK;
+}
+
+int xmap_ctx_rec_set_neighbors(xmap_ctx *c, int keep, const int32_t *cnt, const int32_t *col, const double *sim) {
+    XM_ARG(c && c->have_rec && keep >= 1 && keep <= 64 && cnt && col && sim);
+    XM_HIP(hipSetDevice(c->device));
+    const int I = c->R.n_items;
+    for (int i = 0; i < I; i++) {
+        XM_ARG(cnt[i] <= keep);
+        for (int t = 0; t < cnt[i]; t++) XM_ARG(col[(size_t)i * keep + t] >= 0 && col[(size_t)i * keep + t] < I);
+    }
+    XM_TRY(alloc_neighbors(c, keep));
+    const size_t m = (size_t)I * keep;
+    if (I) {
+        XM_HIP(hipMemcpyAsync(c->nb_cnt, cnt, sizeof(int32_t) * (size_t)I, hipMemcpyHostToDevice, c->st));
+        XM_HIP(hipMemcpyAsync(c->nb_col, col, sizeof(int32_t) * m, hipMemcpyHostToDevice, c->st));
+        XM_HIP(hipMemcpyAsync(c->nb_sim, sim, sizeof(double) * m, hipMemcpyHostToDevice, c->st));
+    }
+    XM_HIP(hipStreamSynchronize(c->st));
+    c->have_nb = true;
+    return XMAP_OK;
+}
+
+int xmap_ctx_rec_neighbors_download(xmap_ctx *c, int32_t *cnt, int32_t *col, double *sim, double *ls) {
+    XM_ARG(c && c->have_rec && c->have_nb);
+    XM_HIP(hipSetDevice(c->device));
+    const size_t I = (size_t)c->R.n_items, m = I * (size_t)c->keep;
+    if (cnt) XM_TRY(d2h(cnt, (const int32_t *)c->nb_cnt, I, c->st));
+    if (col) XM_TRY(d2h(col, (const int32_t *)c->nb_col, m, c->st));
+    if (sim) XM_TRY(d2h(sim, (const double *)c->nb_sim, m, c->st));
+    if (ls) XM_TRY(d2h(ls, (const double *)c->nb_ls, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                     const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
+                     int32_t *max_now) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(n_test >= 0 && wtab && n_w >= 1 && (n_test == 0 || (test_user && test_item && out_plain && out_decay && status)));
+    XM_ARG(!mae || test_rating || n_test == 0);
+    XM_HIP(hipSetDevice(c->device));
+    if (max_now) *max_now = 0;
+    if (mae) mae[0] = mae[1] = mae[2] = 0.0;
+    if (n_test == 0) return XMAP_OK;
+    Pool tmp;
+    struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
+    int32_t *d_user, *d_item, *d_status;
+    double *d_real = nullptr, *d_w, *d_plain, *d_decay, *d_mae;
+    const size_t n = (size_t)n_test;
+    XM_TRY(h2d(tmp, &d_user, test_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_item, test_item, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    if (test_rating) XM_TRY(h2d(tmp, &d_real, test_rating, n, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, n, c->st, true)); XM_TRY(dalloc(tmp, &d_decay, n, c->st, true));
+    XM_TRY(dalloc(tmp, &d_status, n, c->st, true)); XM_TRY(dalloc(tmp, &d_mae, 3, c->st, true));
+    XM_TRY(xmap_predict_rows(c->st, n_test, d_user, d_item, c->R.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim, c->pf_ptr,
+                             c->pf_item, c->pf_rating, c->pf_time, c->rs_avg, d_w, n_w, d_plain, d_decay, d_status, max_now));
+    if (mae) {
+        XM_TRY(xmap_mae(c->st, n_test, d_status, d_real, d_plain, d_decay, d_mae));
+        XM_TRY(d2h(mae, (const double *)d_mae, 3, c->st));
+    }
+    XM_TRY(d2h(out_plain, (const double *)d_plain, n, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, n, c->st));
+    XM_TRY(d2h(status, (const int32_t *)d_status, n, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
     return XMAP_OK;
 }

@@ -1435,9 +1435,72 @@ class Engine(object):
                 G.user += u_lo
         G.n_rows, G.n_target_rows = n, nt
         G.cnt_t, G.cnt_m = cnt_t, cnt_m
+        G.off_t, G.off_m = off_t, off_m      # (the device-resident tail groups the rows by user from these: alterego_profiles)
         G.n_profiles = n_prof
         G.user, G.item, G.rating, G.time = G.user[:n], G.item[:n], G.rating[:n], G.time[:n]
         return G
+
+    def alterego_profiles(self, G, time_key=None):
+        """The AlterEgo rows of alterego() as user-major profiles, built on the device (xmap_rec_profiles): a user's rows
+        contiguous and in stage-C row order, item indices unchanged.  Returns a DeviceRatings-compatible view (fp64 ratings,
+        rating64) -- Engine(view).rec_sim(cap) is RecommenderSim over the rows without a host copy.  time_key: an int64
+        tensor to carry instead of G.time (a caller whose G.time holds positions passes the rank of its time objects)."""
+        R = self.R
+        st = _stream(self.dev)
+        U, n = R.n_users, int(G.n_rows)
+        n1 = max(n, 1)
+        tm = G.time if time_key is None else time_key.contiguous()
+        ptr = self._empty(U + 1, torch.int64)
+        item = self._empty(n1, torch.int32)
+        rating = self._empty(n1, torch.float64)
+        time = self._empty(n1, torch.int64)
+        with self.timed("rec_profiles"):
+            check(lib.xmap_rec_profiles(st, i64(U), i64(n), i64(G.n_target_rows), vp(G.off_t), vp(G.off_m), vp(G.user), vp(G.item),
+                                        vp(G.rating), vp(tm), vp(ptr), vp(item), vp(rating), vp(time)))
+        P = object.__new__(DeviceRatings)
+        P.device, P.n_users, P.n_items, P.nnz = R.device, U, R.n_items, n
+        P.plain_exact = False
+        d = ptr[1:] - ptr[:-1]
+        P.half_contrib = int((d * (d - 1) // 2).sum().item()) if U else 0
+        P.user_ptr, P.user_item, P.user_rating64, P.user_time = ptr, item, rating, time
+        P.user_rating = rating.float()
+        P.item_ptr = torch.zeros(R.n_items + 1, dtype=torch.int64, device=self.dev)
+        P.item_user = torch.zeros(n1, dtype=torch.int32, device=self.dev)
+        P.item_rating = torch.zeros(n1, dtype=torch.float32, device=self.dev)
+        P.csc_ready = False
+        P.prefix_cls, P.suffix_cls, P.contains_mask, P.flags = R.prefix_cls, R.suffix_cls, R.contains_mask, R.flags
+        P.c = abi.Ratings(U, R.n_items, n, ptr.data_ptr(), item.data_ptr(), P.user_rating.data_ptr(), time.data_ptr(),
+                          P.item_ptr.data_ptr(), P.item_user.data_ptr(), P.item_rating.data_ptr(), R.prefix_cls.data_ptr(),
+                          R.suffix_cls.data_ptr(), R.contains_mask.data_ptr(), R.flags.data_ptr())
+        return P
+
+    def predict(self, P, neighbors, test_user, test_item, item_avg, wtab):
+        """RecommenderPrediction.item_based_prediction on the device (xmap_predict_rows, one wave per test pair) over the
+        profiles P of alterego_profiles: neighbors = (cnt [I], col [I][keep], sim [I][keep], ...) as rec_select returns
+        them (or made by the host), test_user / test_item int32 tensors, item_avg [I] fp64, wtab = exp(-alpha d) fp64.
+        Returns (plain, decayed, status, max_now); a pair with status 2 and max_now > len(wtab) needs a longer table."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        T = int(test_user.numel())
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        plain = self._empty(max(T, 1), torch.float64)
+        decay = self._empty(max(T, 1), torch.float64)
+        status = self._empty(max(T, 1), torch.int32)
+        h = C.c_int32(0)
+        with self.timed("predict_rows"):
+            check(lib.xmap_predict_rows(st, i64(T), vp(test_user.contiguous()), vp(test_item.contiguous()), i64(P.n_users),
+                                        i32(P.n_items), i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
+                                        vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()),
+                                        vp(plain), vp(decay), vp(status), C.byref(h)))
+        return plain[:T], decay[:T], status[:T], int(h.value)
+
+    def mae(self, status, real, plain, decay):
+        """calculate_mae's sums on the device (xmap_mae): tensor [3] = (predicted pairs, sum |real - plain|, sum |real - decayed|)"""
+        out = self._empty(3, torch.float64)
+        with self.timed("mae"):
+            check(lib.xmap_mae(_stream(self.dev), i64(status.numel()), vp(status.contiguous()), vp(real.contiguous()),
+                               vp(plain.contiguous()), vp(decay.contiguous()), vp(out)))
+        return out
 
     def _pinned3(self):
         h = getattr(self, "_h3", None)

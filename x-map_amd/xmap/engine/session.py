@@ -247,6 +247,104 @@ class AlterEgoRDD(LocalRDD):
         return out
 
 
+def time_rank(state):
+    """int64 device tensor over the positions of the train rows: the dense rank of the caller's time objects (their order
+    and their ties; the device never sees the objects).  Built once per train state."""
+    key = getattr(state, "_time_rank", None)
+    if key is None:
+        import torch
+        when = getattr(state.times, "when", None)
+        if when is not None:                        # native feed: numbers already
+            rank = np.unique(np.asarray(when), return_inverse=True)[1]
+        else:
+            order = {t: k for k, t in enumerate(sorted(set(state.times)))}
+            rank = np.fromiter((order[t] for t in state.times), np.int64, len(state.times))
+        key = state._time_rank = torch.from_numpy(np.ascontiguousarray(rank, np.int64).reshape(-1)).to(state.engine.dev)
+    return key
+
+
+def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
+    """The recommender tail on the device, from an AlterEgoRDD handle to the records of
+    RecommenderPrediction.item_based_recommendation: profiles of the AlterEgo rows (Engine.alterego_profiles), RecommenderSim
+    (rec_sim, cap), neighbour selection (rec_select, keep = mapping_range; or `neighbors`: the lists a host-side selection
+    made, [(iid, [(nid, sim)*])*] or a dict of them -- the private route), prediction with temporal decay alpha and no limit
+    on the evidence of a pair (Engine.predict).  Returns a LocalRDD of (uid, [(iid, real, plain, decayed) | ()]) in testRDD
+    order, usable with calculate_mae; it carries .mae (count, sum |real - plain|, sum |real - decayed| from the device, or
+    None when a real rating is not a number), .item_info {iid: (avg, norm, n)} and .sim_pairs {iid: [(nid, sim)*]}: the
+    dictionaries the Python statement takes.  A user id matches by equality."""
+    import torch
+    from . import device
+    if not isinstance(alterEgoRDD, AlterEgoRDD):
+        raise TypeError("recommend() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device)")
+    st, G = alterEgoRDD.state, alterEgoRDD.G
+    eng, idt = st.engine, st.idt
+    dev = eng.dev
+    I = len(idt.iids)
+    key = time_rank(st)[G.time] if G.n_rows else G.time
+    P = eng.alterego_profiles(G, time_key=key)
+    eng2 = device.Engine(P)
+    eng2.timers = eng.timers
+    S = eng2.rec_sim(int(cap))
+    item_avg = S.info[:I, 0].contiguous()
+    if neighbors is None:
+        nb = eng2.rec_select(S, int(keep))[:3]
+    else:
+        lists = dict(neighbors) if not isinstance(neighbors, dict) else neighbors
+        width = max([len(v) for v in lists.values()] + [1])
+        if width > 64:
+            raise ValueError("a neighbour list holds %d entries; the device prediction takes up to 64" % width)
+        cnt = np.zeros(max(I, 1), np.int32)
+        col = np.full((max(I, 1), width), -1, np.int32)
+        sim = np.zeros((max(I, 1), width), np.float64)
+        for iid, lst in lists.items():
+            i = idt.iidx[iid]
+            cnt[i] = len(lst)
+            for q, (nid, sv) in enumerate(lst):
+                col[i, q] = idt.iidx[nid]
+                sim[i, q] = sv
+        nb = tuple(torch.from_numpy(a).to(dev) for a in (cnt, col, sim))
+    recs = records_of(testRDD)
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    tu = np.fromiter((uidx.get(uid, -1) for uid, pairs in recs for _ in pairs), np.int32)
+    ti = np.fromiter((idt.iidx.get(pair[0], -1) for _, pairs in recs for pair in pairs), np.int32)
+    try:
+        real = np.fromiter((float(pair[1]) for _, pairs in recs for pair in pairs), np.float64)
+    except (TypeError, ValueError):
+        real = None
+    d_tu, d_ti = torch.from_numpy(tu).to(dev), torch.from_numpy(ti).to(dev)
+    n_w = 66
+    while True:
+        wtab = torch.from_numpy(np.asarray([np.exp(- alpha * d) for d in range(n_w)], np.float64)).to(dev)     # scalar np.exp, like the reference
+        plain, decay, status, max_now = eng2.predict(P, nb, d_tu, d_ti, item_avg, wtab)
+        if max_now <= n_w:
+            break
+        n_w = max_now
+    mae = None
+    if real is not None and len(tu):
+        mae = tuple(eng2.mae(status, torch.from_numpy(real).to(dev), plain, decay).tolist())
+    plain, decay, status = plain.cpu().numpy(), decay.cpu().numpy(), status.cpu().numpy()
+    cnt, col, sim = [x.cpu().numpy() for x in nb]
+    info, iids = S.info.cpu().numpy(), idt.iids
+    out, q = [], 0
+    for uid, pairs in recs:
+        line = []
+        for pair in pairs:
+            if status[q] == 0:
+                line.append((pair[0], pair[1], float(plain[q]), float(decay[q])))
+            elif status[q] == 1:
+                line.append(())
+            else:
+                raise ZeroDivisionError("prediction of (%r, %r): zero weight sum or non-finite value (the reference raises here)"
+                                        % (uid, pair[0]))
+            q += 1
+        out.append((uid, line))
+    res = LocalRDD(out, getattr(testRDD, "ctx", None))
+    res.mae = mae
+    res.item_info = {iids[i]: (float(info[i, 0]), float(info[i, 1]), int(info[i, 3])) for i in range(I) if info[i, 3] > 0}
+    res.sim_pairs = {iids[i]: [(iids[col[i, t]], float(sim[i, t])) for t in range(cnt[i])] for i in range(I) if cnt[i] > 0}
+    return res
+
+
 # ---------------------------------------------------------------------------------------------
 def sim_from_records(state, records):
     """Device SimResult from generic ((iid1,iid2),(sim,mutu,frac,label)) records (any order)."""
