@@ -129,7 +129,7 @@ int xmap_sim_row_ptr(void *stream, int32_t n_items, const int64_t *unit_ptr, con
                      int64_t *row_ptr /*[I+1]*/);
 #endif /* XMAP_CROSSCHECK */
 
-/* ---- stage A, second formulation (stage_a2.hip): each unordered pair is computed once, in the row of its lighter
+/* ---- stage A, second formulation (csrc/tri.h; tri_layout.hip, tri_pairs.hip, tri_mirror.hip, tri_records.hip): each unordered pair is computed once, in the row of its lighter
  * item (weight = (rater count, index)), appended to a half COO and mirrored into the CSR.  Same results as
  * xmap_sim_count/fill (sums are exact, hence order-independent); about 40x fewer rater visits on skewed data.
  *   layout : per-user private profile copies sorted heaviest first (ub: item | flag, rating interleaved), one 16-byte
@@ -142,20 +142,32 @@ int xmap_sim_row_ptr(void *stream, int32_t n_items, const int64_t *unit_ptr, con
  *            rows of H.  The light units are listed class-major (largest tables first): Qcat[rank][i] = Q[i] in the
  *            row's class rank, uq_ptr = exclusive scan over Qcat; h_counts = {light units, heavy units, first unit
  *            of class rank 0..4, light units} (cls_ptr of xmap_sim2_pairs = h_counts + 2).
- *   pairs  : phases bit 8 = reset counters/rowcnt, 1 = k_pair_heavy (chunk partials of the rows of H), 2 = k_pair_tri
+ *   pairs  : phases = XMAP_PAIRS_* (below): RESET = reset counters/rowcnt, HEAVY = k_pair_heavy (chunk partials of the rows
+ *            of H), LIGHT = k_pair_tri
  *            (light units [unit_lo, unit_hi), one launch per table class; 16 / 4 / 2 waves share a 1024 / 1024 / 512-slot table),
- *            4 = k_heavy_merge, 16 = (last; mircnt == NULL only) the mirrored row counts rowcnt[j]++ from the COO's partner
- *            column, 128 = with 8: do not mark the unused COO entries (a caller that reads the COO through the shard
- *            cursors only saves a 4 B x coo_cap fill); with 1 | 2 | 4 in one call the
+ *            HEAVY_MERGE = k_heavy_merge, MIRCOUNT = (last; mircnt == NULL only) the mirrored row counts rowcnt[j]++ from the
+ *            COO's partner column, NO_MARKS = with RESET: do not mark the unused COO entries (a caller that reads the COO
+ *            through the shard cursors only saves a 4 B x coo_cap fill); with HEAVY | LIGHT | HEAVY_MERGE in one call the
  *            heavy rows (partials, then merge) run on a side stream next to the class launches of the light rows;
  *            kept pairs (i lighter, j heavier) ->
  *            half COO: coo_cap entries cut into 4096 shards with a cursor each (d_shards[0][s]; unused entries keep
  *            coo_i = -1), rowcnt[i]++ / rowcnt[j]++; d_shards[1][s] sums to the unordered pairs evaluated;
  *            d_counters[2] = table overflow, [3] = COO shard overflow.
- *            bits 16-23 / 8-15 of phases = m / r (m > 1): only the rows of H whose item index % m == r are computed
- *            (item-sharded ranks deal the heavy rows round-robin; partials and merge of a row stay on one rank).
+ *            XMAP_PAIRS_DEAL(m, r) in phases (bits 16-23 / 8-15; m > 1): only the rows of H whose item index % m == r are
+ *            computed (item-sharded ranks deal the heavy rows round-robin; partials and merge of a row stay on one rank).
  *   scatter: after an exclusive scan of rowcnt -> row_ptr, both directions of every valid COO entry (n_coo = coo_cap
  *            entries are scanned) into the CSR. */
+#define XMAP_PAIRS_HEAVY 1         /* chunk partials of the rows of H */
+#define XMAP_PAIRS_LIGHT 2         /* the light rows */
+#define XMAP_PAIRS_HEAVY_MERGE 4   /* merge of the chunk partials */
+#define XMAP_PAIRS_RESET 8         /* clear the COO cursors, the counters and the row counts first */
+#define XMAP_PAIRS_MIRCOUNT 16     /* the round-2 mirrored counts, added to rowcnt (ignored when mircnt is given) */
+#define XMAP_PAIRS_RAW 32          /* user-sharded input: unfinished, unfiltered partial sums (see xmap_sim2_pack_partials) */
+#define XMAP_PAIRS_SHARD_SUMS 64   /* d_counters[4] / [5] = kept / evaluated unordered pairs */
+#define XMAP_PAIRS_NO_MARKS 128    /* with RESET: leave the unused COO entries unmarked */
+#define XMAP_PAIRS_DEAL(m, r) ((((m) & 0xff) << 16) | (((r) & 0xff) << 8))
+#define XMAP_PAIRS_DEAL_MOD(phases) (((phases) >> 16) & 0xff)
+#define XMAP_PAIRS_DEAL_REM(phases) (((phases) >> 8) & 0xff)
 int xmap_sim2_layout(void *stream, const xmap_ratings *R, const double *info, int32_t ch_min, int32_t *hist /*[U+2]*/,
                      int64_t *pre /*[U+3]*/, int32_t *ctl /*[4]*/, int32_t *hid /*[I]*/, int32_t *hlist /*[1024]*/,
                      uint64_t *ub_key /*[nnz] scratch*/, void *ub /*[nnz] x 8 B: item|flag, rating*/,
@@ -180,7 +192,7 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
                     double *hp_hi, double *hp_lo, int32_t *hp_cnt, int32_t *hp_mut, int64_t coo_cap, int32_t *coo_i,
                     int32_t *coo_j, double *coo_sim, int32_t *coo_mutu, int32_t *coo_nij,
                     double *coo_ls /*NULL, or the RecommenderSim variant (below)*/, int32_t *rowcnt,
-                    int32_t *rowcnt_h /*[64][1024] scratch*/, int64_t *d_shards /*[2][4096]*/,
+                    int64_t *d_shards /*[2][4096]*/,
                     int64_t *d_counters /*[4]; [6] with phases bit 64: [4] / [5] = kept / evaluated unordered pairs, the sums
                                           of d_shards[0] / [1]*/,
                     int32_t *mircnt /*[I] or NULL.  NULL: rowcnt[i]++ / rowcnt[j]++ as described above.  Else rowcnt counts
@@ -204,12 +216,18 @@ int xmap_sim2_scatter(void *stream, int32_t n_items, int64_t n_coo, const int32_
  * The CSC arrays (R->item_user / item_rating) are neither read nor written; R->item_ptr (= item_ptr) is written.
  * rating64 != NULL: the ratings are fp64 (RecommenderSim over AlterEgo means, core/recommenderSim.py:64-133; R->user_rating is
  * ignored), the user averages are zero by construction (u_avg must be zero-filled, u_norm may be NULL), there is no
- * mutuality, and ub / rc use the 16-byte wide forms xmap_sim2_pairs reads when coo_ls != NULL without phases bit 32.
- * phases: 1 = everything up to the rater records and W+; 2 = item statistics of the items [stats_lo, stats_hi) (and the flags
- * of THEIR rater records); 4 = flags of the profile copy, 8 = flags of all rater records -- both from the complete info.
- * One GPU: 1 | 2 | 4 with all items.  Item-sharded ranks: 1 | 2 with the rank's share, an all-gather of info / norms (the
- * all-gather of per-item norms), then 4 | 8.
+ * mutuality, and ub / rc use the 16-byte wide forms xmap_sim2_pairs reads when coo_ls != NULL without XMAP_PAIRS_RAW.
+ * phases (XMAP_LAYOUT_*): RECORDS = everything up to the rater records and W+; STATS = item statistics of the items
+ * [stats_lo, stats_hi) (and the flags of THEIR rater records); UB_FLAGS = flags of the profile copy, RC_FLAGS = flags of all
+ * rater records -- both from the complete info.
+ * One GPU: RECORDS | STATS | UB_FLAGS with all items.  Item-sharded ranks: RECORDS | STATS with the rank's share, an all-gather
+ * of info / norms (the all-gather of per-item norms), then UB_FLAGS | RC_FLAGS.
  * h_ctl (host, [2], may be NULL) = {CH, |H|}; synchronises if given. */
+#define XMAP_LAYOUT_RECORDS 1
+#define XMAP_LAYOUT_STATS 2
+#define XMAP_LAYOUT_UB_FLAGS 4
+#define XMAP_LAYOUT_RC_FLAGS 8
+#define XMAP_LAYOUT_ALL 15
 int xmap_sim3_layout(void *stream, const xmap_ratings *R, int64_t *item_ptr /*[I+1] = R->item_ptr*/,
                      const double *rating64 /*[nnz] or NULL*/, int32_t ch_min, int32_t phases, int32_t stats_lo, int32_t stats_hi,
                      int32_t *cnt /*[I] scratch*/,
@@ -253,7 +271,7 @@ int xmap_sim3_mirror(void *stream, int32_t n_items, int64_t coo_cap, const int32
  * holds the complete profiles of a share of the USERS.  Per item its share of get_universal_item_info's sums
  * (core/baselinerSim.py:56-82) is xmap_item_partials -> [I][7] = (sum r, sum r^2, sum (r - avg_u)^2, each as an exact (value,
  * error) pair, raters); the shares of all ranks, gathered as [n_parts][I][7], are added up exactly and finished by
- * xmap_item_merge.  xmap_sim2_pairs with phases bit 32 ("raw": no
+ * xmap_item_merge.  xmap_sim2_pairs with XMAP_PAIRS_RAW ("raw": no
  * heavy set, coo_ls != NULL) then emits, for every pair two of the rank's users co-rated, the partial sums of
  * calculate_cosine_sim / calculate_adjusted_cosine_sim (:115-174) and retrieve_path_info (:97-113) unfinished and unfiltered:
  * coo_sim / coo_ls = the dot product as an exact (value, error) pair, coo_nij, coo_mutu.  xmap_sim2_pack_partials turns

@@ -29,6 +29,11 @@ def test_abi_exports_every_declared_symbol():
     for n in sorted(names):
         assert hasattr(X, n), n
     assert hipabi.lib.xmap_version() >= 100
+    # the phase bits Python passes are the header's (XMAP_PAIRS_*, XMAP_LAYOUT_*), the heavy deal packs as its macro does
+    consts = hipabi.header_constants()
+    assert len(consts) == 13 and {n: getattr(hipabi, n) for n in consts} == consts
+    deal = re.search(r"#define XMAP_PAIRS_DEAL\(m, r\) (.*)", hdr).group(1)
+    assert eval(deal, {"m": 0x1a5, "r": 0x37c}) == hipabi.pairs_deal(0x1a5, 0x37c) == (0xa5 << 16) | (0x7c << 8)
     # struct layouts match the header (field order / count)
     assert [f[0] for f in hipabi.Ratings._fields_] == re.findall(
         r"(?:const\s+)?\w+\s+\*?(\w+);", hdr[hdr.index("typedef struct xmap_ratings {"):hdr.index("} xmap_ratings;")])

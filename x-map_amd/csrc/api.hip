@@ -25,6 +25,7 @@ struct Pool {
         ptrs.clear();
     }
 };
+struct ScratchPool : Pool { ~ScratchPool() { release(); } };       // a stage's temporaries: released when the call returns
 
 }  // namespace xmap
 
@@ -188,6 +189,125 @@ static int run_enumeration(xmap_ctx *c, int64_t xs_cap, int64_t *xs_off, int32_t
     return rc;
 }
 
+// ---- stage A of the coarse ABI.  What differs between xmap_ctx_item_sim (BaselinerSim over the ratings) and xmap_ctx_rec_sim
+// (RecommenderSim over the AlterEgo profiles); scratch, sizing, retries and the order of the fine-grained calls are tri_pass's.
+struct TriPass {
+    const xmap_ratings *R;      // the ratings view (its item_ptr is written by the layout)
+    const double *rating64;     // fp64 ratings (wide profile entries, rater records and sort records), or NULL: R->user_rating
+    int ch_min, dups, method, cap;
+    bool heavy;                 // run the rows of H (false: the layout has none)
+    bool aux, skip_self;        // a sixth COO / CSR column (the pairs' local sensitivities); a row may pair with itself (no mirrored entry)
+    int64_t half_contrib;       // sum over the users of d (d - 1) / 2: sizes the unit lists and the half COO
+    Pool *stats_pool, *csr_pool, *mutu_pool;    // where u_avg / u_norm / info, the CSR columns and the mutu column are kept
+    int64_t *row_ptr;           // [I + 1], zeroed: the CSR's row pointers
+};
+struct TriResult {
+    double *u_avg, *u_norm /*NULL with rating64*/, *info, *norms /*in tmp*/, *sim, *aux;
+    int32_t *col, *mutu, *nij;
+    int64_t n, n_unordered, kept;   // kept / evaluated unordered pairs; room of the CSR columns (2 n: a self pair uses one of its two)
+};
+
+// layout -> plan(slot_target) -> pairs (again with smaller partitions after a table overflow, with more slack after a COO
+// overflow; one host wait per attempt) -> mirrored counts -> mirror.  tmp: the pass's scratch, the caller's to release.
+static int tri_pass(hipStream_t st, const TriPass &J, Pool &tmp, TriResult &O) {
+#define T_ALLOC(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), st))
+#define T_ALLOCZ(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), st, true))
+    const xmap_ratings &R = *J.R;
+    const int I = R.n_items;
+    const int64_t U = R.n_users, nnz = R.nnz;
+    const bool wide = J.rating64 != nullptr;
+    const size_t n1 = (size_t)(nnz ? nnz : 1), i1 = (size_t)(I ? I : 1);
+    const size_t rw = wide ? 3 : 2;         // 64-bit words of a sort record
+    // A2 / A3 + layout of the "tri" formulation: one transposition (xmap_sim3_layout); the CSC arrays stay unbuilt
+    int32_t *cnt, *hist, *ctl, *hid, *hlist;
+    int64_t *pre;
+    uint64_t *ub_key, *ub, *rcrec, *Wp, *srec, *buf_a, *buf_b;
+    O.u_norm = nullptr; O.aux = nullptr;
+    XM_TRY(dalloc(*J.stats_pool, &O.u_avg, (size_t)U, st, wide));       // (fp64 ratings: the user averages are zero by construction)
+    if (!wide) XM_TRY(dalloc(*J.stats_pool, &O.u_norm, (size_t)U, st));
+    XM_TRY(dalloc(*J.stats_pool, &O.info, i1 * 4, st, true));
+    T_ALLOCZ(O.norms, 2 * i1);
+    T_ALLOC(cnt, i1);
+    T_ALLOC(hist, U + 2); T_ALLOC(pre, U + 3); T_ALLOC(ctl, 4); T_ALLOC(hid, i1); T_ALLOCZ(hlist, 1024);
+    T_ALLOC(ub_key, n1); T_ALLOC(ub, (wide ? 2 : 1) * n1); T_ALLOC(rcrec, 2 * n1); T_ALLOC(Wp, i1);
+    T_ALLOC(srec, rw * n1); T_ALLOC(buf_a, rw * n1); T_ALLOC(buf_b, rw * n1);
+    XM_TRY(xmap_sim3_layout(st, &R, (int64_t *)R.item_ptr, J.rating64, J.ch_min, XMAP_LAYOUT_RECORDS | XMAP_LAYOUT_STATS | XMAP_LAYOUT_UB_FLAGS,
+                            0, I, cnt, O.u_avg, O.u_norm, hist, pre, ctl, hid, hlist, ub_key, ub, srec, buf_a, buf_b, rcrec, Wp, O.info,
+                            O.norms, nullptr));
+    int32_t *Q, *Cc, *Qcat, *uq_item = nullptr, *uq_q = nullptr, *uc_item = nullptr, *uc_c = nullptr;
+    uint8_t *small;
+    int64_t *uq_ptr, *uc_ptr;
+    T_ALLOCZ(Q, i1); T_ALLOCZ(Cc, i1); T_ALLOCZ(small, i1); T_ALLOC(Qcat, 5 * i1); T_ALLOCZ(uq_ptr, (size_t)5 * I + 1);
+    T_ALLOCZ(uc_ptr, I + 1);
+    int slot_target = 768;          // (75 % load of the 1024-slot tables; device.py: SLOT_TARGET / CH_MIN)
+    double coo_slack = 1.0;
+    int64_t hc[10];
+    auto plan = [&](int target) -> int {
+        const int64_t cap_light = J.half_contrib / target + I + 1, cap_heavy = nnz / J.ch_min + 1025;
+        T_ALLOC(uq_item, cap_light); T_ALLOC(uq_q, 4 * cap_light); T_ALLOC(uc_item, cap_heavy); T_ALLOC(uc_c, cap_heavy);
+        return xmap_sim3_plan(st, &R, target, pre, hid, ctl, Q, Cc, small, Wp, Qcat, uq_ptr, uc_ptr, J.dups, uq_item, uq_q, uc_item, uc_c,
+                              cap_light, cap_heavy, hc);
+    };
+    XM_TRY(plan(slot_target));
+    // all phases in one call: the heavy rows run on a side stream next to the class launches of the light rows; own and
+    // mirrored row counts apart (mir), kept / evaluated pairs summed on the device
+    const int phases = XMAP_PAIRS_RESET | XMAP_PAIRS_LIGHT | XMAP_PAIRS_MIRCOUNT | XMAP_PAIRS_SHARD_SUMS | XMAP_PAIRS_NO_MARKS |
+                       (J.heavy ? XMAP_PAIRS_HEAVY | XMAP_PAIRS_HEAVY_MERGE : 0);
+    int32_t *coo_i = nullptr, *coo_j = nullptr, *coo_mutu = nullptr, *coo_nij = nullptr, *own = nullptr, *mir = nullptr;
+    double *coo_sim = nullptr, *coo_aux = nullptr;
+    int64_t *d_shards = nullptr;
+    int64_t cap_coo = 0;
+    for (;;) {
+        const int64_t n_light = hc[0], n_hu = J.heavy ? hc[1] : 0, n_heavy = J.heavy ? hc[9] : 0;
+        cap_coo = ((int64_t)((double)(J.half_contrib > 0 ? J.half_contrib : 1) * coo_slack) / 4096 + 1100) * 4096;
+        double *hp_hi, *hp_lo;
+        int32_t *hp_cnt, *hp_mut;
+        int64_t *d_cnt;
+        T_ALLOC(coo_i, cap_coo); T_ALLOC(coo_j, cap_coo); T_ALLOC(coo_sim, cap_coo); T_ALLOC(coo_mutu, cap_coo); T_ALLOC(coo_nij, cap_coo);
+        if (J.aux) T_ALLOC(coo_aux, cap_coo);
+        T_ALLOC(own, i1); T_ALLOC(mir, i1);
+        const size_t hp = (size_t)(n_hu ? n_hu : 1) * 1024;
+        T_ALLOC(hp_hi, hp); T_ALLOC(hp_lo, hp); T_ALLOC(hp_cnt, hp); T_ALLOC(hp_mut, hp);
+        T_ALLOCZ(d_cnt, 6); T_ALLOC(d_shards, 2 * 4096);
+        XM_TRY(xmap_sim2_pairs(st, &R, J.method, J.cap, O.u_avg, O.norms, rcrec, ub, Q, small, uq_item, uq_q, hc + 2, 0, n_light, hid, hlist,
+                               ctl, Cc, uc_ptr, uc_item, uc_c, (int32_t)n_hu, (int32_t)n_heavy, phases, hp_hi, hp_lo, hp_cnt, hp_mut, cap_coo, coo_i,
+                               coo_j, coo_sim, coo_mutu, coo_nij, coo_aux, own, d_shards, d_cnt, mir));
+        int64_t h_cnt[6];
+        XM_TRY(d2h(h_cnt, d_cnt, 6, st));
+        XM_HIP(hipStreamSynchronize(st));
+        if (h_cnt[2]) {                 // an LDS pair table overflowed: smaller partitions
+            if (slot_target <= 32) { set_error("pair-table overflow"); return XMAP_ERR_OVERFLOW; }
+            slot_target /= 2;
+            XM_TRY(plan(slot_target));
+            continue;
+        }
+        if (h_cnt[3]) {                 // a half-COO shard overflowed: more slack
+            if (coo_slack > 64) { set_error("half-COO overflow"); return XMAP_ERR_CAPACITY; }
+            coo_slack *= 2;
+            continue;
+        }
+        O.n = h_cnt[4]; O.n_unordered = h_cnt[5];
+        break;
+    }
+    // mirror the half COO into the CSR (row = [own | mirrored], tile sort by the heavier item); a sixth column travels along
+    const int64_t n = O.n;
+    const size_t nn = (size_t)(n ? n : 1);
+    O.kept = 2 * n;
+    int64_t *mptr;
+    int32_t *fill, *tot;
+    uint64_t *mir_a, *mir_b;
+    T_ALLOCZ(mptr, I + 1);
+    XM_TRY(dalloc(*J.csr_pool, &O.col, (size_t)O.kept, st)); XM_TRY(dalloc(*J.csr_pool, &O.sim, (size_t)O.kept, st));
+    XM_TRY(dalloc(*J.mutu_pool, &O.mutu, (size_t)O.kept, st)); XM_TRY(dalloc(*J.csr_pool, &O.nij, (size_t)O.kept, st));
+    if (J.aux) XM_TRY(dalloc(*J.csr_pool, &O.aux, (size_t)O.kept, st));
+    T_ALLOC(fill, i1); T_ALLOC(tot, i1); T_ALLOC(mir_a, (J.aux ? 4 : 3) * nn); T_ALLOC(mir_b, (J.aux ? 4 : 3) * nn);
+    XM_TRY(xmap_sim3_mircount(st, I, cap_coo, coo_i, coo_j, d_shards, n, J.skip_self ? 1 : 0, mir_a, mir));
+    return xmap_sim3_mirror(st, I, cap_coo, coo_i, coo_j, coo_sim, coo_mutu, coo_nij, d_shards, n, own, mir, tot, J.row_ptr, mptr, fill, mir_a,
+                            mir_b, O.col, O.sim, O.mutu, O.nij, coo_aux, O.aux, 0, I);
+#undef T_ALLOC
+#undef T_ALLOCZ
+}
+
 }  // namespace xmap
 
 extern "C" {
@@ -287,109 +407,25 @@ int xmap_ctx_item_sim(xmap_ctx *c, int method, int cap, int64_t *n_kept, int64_t
     c->have_sim = c->have_ext = c->have_gen = false;
     xmap_ratings &R = c->R;
     const int I = R.n_items;
-    const int64_t U = R.n_users, nnz = R.nnz;
     const int pair_method = (method == XMAP_COSINE && !c->plain_exact) ? XMAP_COSINE_EXACT : method;
-    Pool tmp;                       // layout / plan / half COO: released at the end of the stage
-    struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
-#define T_ALLOC(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), c->st))
-#define T_ALLOCZ(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), c->st, true))
-    // A2 / A3 + layout of the "tri" formulation: one transposition (xmap_sim3_layout); the CSC arrays stay unbuilt
-    int32_t *cnt;
-    T_ALLOC(cnt, I);
-    double *norms;
-    XM_ALLOC(c->p_sim, c->u_avg, U);
-    XM_ALLOC(c->p_sim, c->u_norm, U);
-    XM_ALLOCZ(c->p_sim, c->info, (size_t)I * 4);
-    T_ALLOCZ(norms, (size_t)2 * I);
-    int32_t *hist, *ctl, *hid, *hlist;
-    int64_t *pre;
-    uint64_t *ub_key, *ub, *rcrec, *Wp, *srec, *buf_a, *buf_b;
-    const size_t n1 = (size_t)(nnz ? nnz : 1);
-    T_ALLOC(hist, U + 2); T_ALLOC(pre, U + 3); T_ALLOC(ctl, 4); T_ALLOC(hid, I); T_ALLOCZ(hlist, 1024);
-    T_ALLOC(ub_key, n1); T_ALLOC(ub, n1); T_ALLOC(rcrec, 2 * n1); T_ALLOC(Wp, I);
-    T_ALLOC(srec, 2 * n1); T_ALLOC(buf_a, 2 * n1); T_ALLOC(buf_b, 2 * n1);
-    const int ch_min = 2048;
-    XM_TRY(xmap_sim3_layout(c->st, &R, (int64_t *)R.item_ptr, nullptr, ch_min, 1 | 2 | 4, 0, I, cnt, c->u_avg, c->u_norm, hist, pre, ctl,
-                            hid, hlist, ub_key, ub, srec, buf_a, buf_b, rcrec, Wp, c->info, norms, nullptr));
-    const int64_t half_contrib = c->half_contrib;
-    int32_t *Q, *Cc, *Qcat, *uq_item = nullptr, *uq_q = nullptr, *uc_item = nullptr, *uc_c = nullptr;
-    uint8_t *small;
-    int64_t *uq_ptr, *uc_ptr;
-    T_ALLOCZ(Q, I); T_ALLOCZ(Cc, I); T_ALLOCZ(small, I); T_ALLOC(Qcat, (size_t)5 * (I ? I : 1)); T_ALLOCZ(uq_ptr, (size_t)5 * I + 1);
-    T_ALLOCZ(uc_ptr, I + 1);
-    int slot_target = 768;          // (75 % load of the 1024-slot tables; device.py: SLOT_TARGET / CH_MIN)
-    double coo_slack = 1.0;
-    int64_t hc[10];
-    int64_t n_light = 0, n_hu = 0;
-    int n_heavy = 0;
-    auto plan = [&](int target) -> int {
-        const int64_t cap_light = half_contrib / target + I + 1, cap_heavy = nnz / ch_min + 1025;
-        T_ALLOC(uq_item, cap_light); T_ALLOC(uq_q, 4 * cap_light); T_ALLOC(uc_item, cap_heavy); T_ALLOC(uc_c, cap_heavy);
-        XM_TRY(xmap_sim3_plan(c->st, &R, target, pre, hid, ctl, Q, Cc, small, Wp, Qcat, uq_ptr, uc_ptr, 0, uq_item, uq_q, uc_item, uc_c,
-                              cap_light, cap_heavy, hc));
-        n_light = hc[0]; n_hu = hc[1]; n_heavy = (int)hc[9];
-        return XMAP_OK;
-    };
-    XM_TRY(plan(slot_target));
-    int32_t *coo_i = nullptr, *coo_j = nullptr, *coo_mutu = nullptr, *coo_nij = nullptr, *own = nullptr, *mir = nullptr;
-    double *coo_sim = nullptr;
-    int64_t *d_shards = nullptr;
-    int64_t cap_coo = 0, n = 0, n_unordered = 0;
-    for (;;) {
-        cap_coo = ((int64_t)((double)(half_contrib > 0 ? half_contrib : 1) * coo_slack) / 4096 + 1100) * 4096;
-        double *hp_hi, *hp_lo;
-        int32_t *hp_cnt, *hp_mut, *rowcnt_h;
-        int64_t *d_cnt;
-        T_ALLOC(coo_i, cap_coo); T_ALLOC(coo_j, cap_coo); T_ALLOC(coo_sim, cap_coo); T_ALLOC(coo_mutu, cap_coo); T_ALLOC(coo_nij, cap_coo);
-        T_ALLOC(own, I); T_ALLOC(mir, I);
-        const size_t hp = (size_t)(n_hu ? n_hu : 1) * 1024;
-        T_ALLOC(hp_hi, hp); T_ALLOC(hp_lo, hp); T_ALLOC(hp_cnt, hp); T_ALLOC(hp_mut, hp);
-        T_ALLOCZ(d_cnt, 6); T_ALLOC(d_shards, 2 * 4096); T_ALLOC(rowcnt_h, 64 * 1024);
-        // all phases in one call: the heavy rows run on a side stream next to the class launches of the light rows; own and
-        // mirrored row counts apart (mir), kept / evaluated pairs summed on the device (phase 64)
-        XM_TRY(xmap_sim2_pairs(c->st, &R, pair_method, cap, c->u_avg, norms, rcrec, ub, Q, small, uq_item, uq_q, hc + 2, 0, n_light, hid, hlist,
-                               ctl, Cc, uc_ptr, uc_item, uc_c, (int32_t)n_hu, n_heavy, 8 | 1 | 2 | 4 | 16 | 64 | 128, hp_hi, hp_lo, hp_cnt,
-                               hp_mut, cap_coo, coo_i, coo_j, coo_sim, coo_mutu, coo_nij, nullptr, own, rowcnt_h, d_shards, d_cnt, mir));
-        int64_t h_cnt[6];
-        XM_TRY(d2h(h_cnt, d_cnt, 6, c->st));
-        XM_HIP(hipStreamSynchronize(c->st));
-        if (h_cnt[2]) {                 // an LDS pair table overflowed: smaller partitions
-            if (slot_target <= 32) { set_error("pair-table overflow"); return XMAP_ERR_OVERFLOW; }
-            slot_target /= 2;
-            XM_TRY(plan(slot_target));
-            continue;
-        }
-        if (h_cnt[3]) {                 // a half-COO shard overflowed: more slack
-            if (coo_slack > 64) { set_error("half-COO overflow"); return XMAP_ERR_CAPACITY; }
-            coo_slack *= 2;
-            continue;
-        }
-        n = h_cnt[4]; n_unordered = h_cnt[5];
-        break;
-    }
-    // mirror the half COO into the CSR (row = [own | mirrored], tile sort by the heavier item)
-    int64_t *row_ptr, *mptr;
+    ScratchPool tmp;                       // layout / plan / half COO: released at the end of the stage
+    int64_t *row_ptr;
     XM_ALLOCZ(c->p_sim, row_ptr, I + 1);
-    T_ALLOCZ(mptr, I + 1);
-    const int64_t kept = 2 * n;
-    int32_t *col, *mutu, *nij, *fill, *tot;
-    double *sim;
-    uint64_t *mir_a, *mir_b;
-    XM_ALLOC(c->p_sim, col, kept); XM_ALLOC(c->p_sim, sim, kept); XM_ALLOC(c->p_sim, mutu, kept); XM_ALLOC(c->p_sim, nij, kept);
-    T_ALLOC(fill, I); T_ALLOC(tot, I); T_ALLOC(mir_a, (size_t)3 * (n ? n : 1)); T_ALLOC(mir_b, (size_t)3 * (n ? n : 1));
-    XM_TRY(xmap_sim3_mircount(c->st, I, cap_coo, coo_i, coo_j, d_shards, n, 0, mir_a, mir));
-    XM_TRY(xmap_sim3_mirror(c->st, I, cap_coo, coo_i, coo_j, coo_sim, coo_mutu, coo_nij, d_shards, n, own, mir, tot, row_ptr, mptr, fill,
-                            mir_a, mir_b, col, sim, mutu, nij, nullptr, nullptr, 0, I));
+    TriPass J;
+    J.R = &R; J.rating64 = nullptr; J.ch_min = 2048; J.dups = 0; J.method = pair_method; J.cap = cap;
+    J.heavy = true; J.aux = false; J.skip_self = false; J.half_contrib = c->half_contrib;
+    J.stats_pool = J.csr_pool = J.mutu_pool = &c->p_sim; J.row_ptr = row_ptr;
+    TriResult O;
+    XM_TRY(tri_pass(c->st, J, tmp, O));
     XM_HIP(hipStreamSynchronize(c->st));
-    c->S.n_items = I; c->S.row_ptr = row_ptr; c->S.col = col; c->S.sim = sim; c->S.mutu = mutu; c->S.nij = nij; c->S.info = c->info;
+    c->u_avg = O.u_avg; c->u_norm = O.u_norm; c->info = O.info;
+    c->S.n_items = I; c->S.row_ptr = row_ptr; c->S.col = O.col; c->S.sim = O.sim; c->S.mutu = O.mutu; c->S.nij = O.nij; c->S.info = c->info;
     c->S.frac = nullptr;
-    c->n_kept = kept; c->n_eval = 2 * n_unordered; c->n_contrib = 2 * half_contrib;
+    c->n_kept = O.kept; c->n_eval = 2 * O.n_unordered; c->n_contrib = 2 * c->half_contrib;
     c->have_sim = true;
-    if (n_kept) *n_kept = kept;
+    if (n_kept) *n_kept = c->n_kept;
     if (n_evaluated) *n_evaluated = c->n_eval;
     return XMAP_OK;
-#undef T_ALLOC
-#undef T_ALLOCZ
 }
 
 int xmap_ctx_sim_download(xmap_ctx *c, int64_t *row_ptr, int32_t *col, double *sim, int32_t *mutu, int32_t *nij, double *info,
@@ -536,8 +572,7 @@ int xmap_ctx_ext_lists(xmap_ctx *c, int64_t *xs_off, int32_t *xs_end, double *xs
     const int I = c->R.n_items;
     if (I == 0) return XMAP_OK;
     const int64_t cap = c->n_out > 0 ? c->n_out : 1;      // exact: the candidate counts of the first pass
-    Pool tmp;
-    struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
+    ScratchPool tmp;
     int64_t *d_off;
     int32_t *d_end;
     double *d_val;
@@ -557,8 +592,7 @@ int xmap_ctx_candidates(xmap_ctx *c, int32_t *n_top) {
     XM_HIP(hipSetDevice(c->device));
     const int I = c->R.n_items;
     if (I == 0) return XMAP_OK;
-    Pool tmp;
-    struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
+    ScratchPool tmp;
     int32_t *d_top, *d_choice, *d_map;
     XM_TRY(dalloc(tmp, &d_top, (size_t)I, c->st, true));
     XM_TRY(dalloc(tmp, &d_choice, (size_t)I, c->st, true));
@@ -641,105 +675,34 @@ int xmap_ctx_rec_sim(xmap_ctx *c, int cap, int64_t *n_pairs) {
     XM_HIP(hipStreamSynchronize(c->st));
     int64_t half_contrib = 0;
     for (int64_t u = 0; u < U; u++) { const int64_t d = h_ptr[u + 1] - h_ptr[u]; half_contrib += d * (d - 1) / 2; }
-    Pool tmp;
-    struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
-#define T_ALLOC(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), c->st))
-#define T_ALLOCZ(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), c->st, true))
+    ScratchPool tmp;
     // the profiles as the ratings of the pair machinery: fp64 ratings (wide records), zero user average, no heavy set
     xmap_ratings P = c->R;
     float *f_dummy, *f_irating;
     int64_t *item_ptr;
     int32_t *i_user;
-    T_ALLOCZ(f_dummy, n1); T_ALLOCZ(f_irating, n1); T_ALLOCZ(item_ptr, I + 1); T_ALLOCZ(i_user, n1);
+    XM_ALLOCZ(tmp, f_dummy, n1); XM_ALLOCZ(tmp, f_irating, n1); XM_ALLOCZ(tmp, item_ptr, I + 1); XM_ALLOCZ(tmp, i_user, n1);
     P.nnz = nnz; P.user_ptr = c->pf_ptr; P.user_item = c->pf_item; P.user_rating = f_dummy; P.user_time = c->pf_time;
     P.item_ptr = item_ptr; P.item_user = i_user; P.item_rating = f_irating;
-    int32_t *cnt, *hist, *ctl, *hid, *hlist;
-    int64_t *pre;
-    uint64_t *ub_key, *ub, *rcrec, *Wp, *srec, *buf_a, *buf_b;
-    double *u_avg, *info, *norms;
-    T_ALLOC(cnt, i1); T_ALLOCZ(u_avg, U ? U : 1); T_ALLOCZ(info, i1 * 4); T_ALLOCZ(norms, 2 * i1);
-    T_ALLOC(hist, U + 2); T_ALLOC(pre, U + 3); T_ALLOC(ctl, 4); T_ALLOC(hid, i1); T_ALLOCZ(hlist, 1024);
-    T_ALLOC(ub_key, n1); T_ALLOC(ub, 2 * n1); T_ALLOC(rcrec, 2 * n1); T_ALLOC(Wp, i1);
-    T_ALLOC(srec, 3 * n1); T_ALLOC(buf_a, 3 * n1); T_ALLOC(buf_b, 3 * n1);
-    const int ch_min = (int)((U + 2 > 64) ? U + 2 : 64);        // more raters than users: no item is heavy
-    XM_TRY(xmap_sim3_layout(c->st, &P, item_ptr, c->pf_rating, ch_min, 1 | 2 | 4, 0, I, cnt, u_avg, nullptr, hist, pre, ctl, hid, hlist,
-                            ub_key, ub, srec, buf_a, buf_b, rcrec, Wp, info, norms, nullptr));
-    int32_t *Q, *Cc, *Qcat, *uq_item = nullptr, *uq_q = nullptr, *uc_item = nullptr, *uc_c = nullptr;
-    uint8_t *small;
-    int64_t *uq_ptr, *uc_ptr;
-    T_ALLOCZ(Q, i1); T_ALLOCZ(Cc, i1); T_ALLOCZ(small, i1); T_ALLOC(Qcat, 5 * i1); T_ALLOCZ(uq_ptr, (size_t)5 * I + 1);
-    T_ALLOCZ(uc_ptr, I + 1);
-    int slot_target = 768;
-    double coo_slack = 1.0;
-    int64_t hc[10];
-    int64_t n_light = 0;
-    auto plan = [&](int target) -> int {
-        const int64_t cap_light = half_contrib / target + I + 1, cap_heavy = nnz / ch_min + 1025;
-        T_ALLOC(uq_item, cap_light); T_ALLOC(uq_q, 4 * cap_light); T_ALLOC(uc_item, cap_heavy); T_ALLOC(uc_c, cap_heavy);
-        XM_TRY(xmap_sim3_plan(c->st, &P, target, pre, hid, ctl, Q, Cc, small, Wp, Qcat, uq_ptr, uc_ptr, 1, uq_item, uq_q, uc_item, uc_c,
-                              cap_light, cap_heavy, hc));
-        n_light = hc[0];
-        return XMAP_OK;
-    };
-    XM_TRY(plan(slot_target));
-    int32_t *coo_i = nullptr, *coo_j = nullptr, *coo_mutu = nullptr, *coo_nij = nullptr, *own = nullptr, *mir = nullptr;
-    double *coo_sim = nullptr, *coo_ls = nullptr;
-    int64_t *d_shards = nullptr;
-    int64_t cap_coo = 0, n = 0;
-    for (;;) {
-        cap_coo = ((int64_t)((double)(half_contrib > 0 ? half_contrib : 1) * coo_slack) / 4096 + 1100) * 4096;
-        double *hp_hi, *hp_lo;
-        int32_t *hp_cnt, *hp_mut, *rowcnt_h;
-        int64_t *d_cnt;
-        T_ALLOC(coo_i, cap_coo); T_ALLOC(coo_j, cap_coo); T_ALLOC(coo_sim, cap_coo); T_ALLOC(coo_mutu, cap_coo); T_ALLOC(coo_nij, cap_coo);
-        T_ALLOC(coo_ls, cap_coo); T_ALLOC(own, i1); T_ALLOC(mir, i1);
-        T_ALLOC(hp_hi, 1024); T_ALLOC(hp_lo, 1024); T_ALLOC(hp_cnt, 1024); T_ALLOC(hp_mut, 1024);
-        T_ALLOCZ(d_cnt, 6); T_ALLOC(d_shards, 2 * 4096); T_ALLOC(rowcnt_h, 64 * 1024);
-        // the RecommenderSim variant of the pair kernels: exact sums, nothing filtered, self pairs, local sensitivities
-        XM_TRY(xmap_sim2_pairs(c->st, &P, XMAP_ADJUST_COSINE, cap, u_avg, norms, rcrec, ub, Q, small, uq_item, uq_q, hc + 2, 0, n_light, hid,
-                               hlist, ctl, Cc, uc_ptr, uc_item, uc_c, 0, 0, 8 | 2 | 16 | 64 | 128, hp_hi, hp_lo, hp_cnt, hp_mut, cap_coo,
-                               coo_i, coo_j, coo_sim, coo_mutu, coo_nij, coo_ls, own, rowcnt_h, d_shards, d_cnt, mir));
-        int64_t h_cnt[6];
-        XM_TRY(d2h(h_cnt, d_cnt, 6, c->st));
-        XM_HIP(hipStreamSynchronize(c->st));
-        if (h_cnt[2]) {
-            if (slot_target <= 32) { set_error("pair-table overflow"); return XMAP_ERR_OVERFLOW; }
-            slot_target /= 2;
-            XM_TRY(plan(slot_target));
-            continue;
-        }
-        if (h_cnt[3]) {
-            if (coo_slack > 64) { set_error("half-COO overflow"); return XMAP_ERR_CAPACITY; }
-            coo_slack *= 2;
-            continue;
-        }
-        n = h_cnt[4];
-        break;
-    }
-    // mirror: row = [own | mirrored], the local sensitivity travels along; a self pair is one entry
-    int64_t *mptr;
-    T_ALLOCZ(mptr, I + 1);
-    const size_t kept_max = (size_t)(n ? 2 * n : 1), nn = (size_t)(n ? n : 1);
-    int32_t *mutu, *fill, *tot;
-    uint64_t *mir_a, *mir_b;
-    XM_ALLOC(c->p_rec, c->rs_col, kept_max); XM_ALLOC(c->p_rec, c->rs_sim, kept_max); XM_ALLOC(c->p_rec, c->rs_nij, kept_max);
-    XM_ALLOC(c->p_rec, c->rs_ls, kept_max);
-    T_ALLOC(mutu, kept_max); T_ALLOC(fill, i1); T_ALLOC(tot, i1); T_ALLOC(mir_a, 4 * nn); T_ALLOC(mir_b, 4 * nn);
-    XM_TRY(xmap_sim3_mircount(c->st, I, cap_coo, coo_i, coo_j, d_shards, n, 1, mir_a, mir));
-    XM_TRY(xmap_sim3_mirror(c->st, I, cap_coo, coo_i, coo_j, coo_sim, coo_mutu, coo_nij, d_shards, n, own, mir, tot, c->rs_row_ptr, mptr, fill,
-                            mir_a, mir_b, c->rs_col, c->rs_sim, mutu, c->rs_nij, coo_ls, c->rs_ls, 0, I));
+    // the RecommenderSim variant of the pair kernels: exact sums, nothing filtered, self pairs, local sensitivities
+    TriPass J;
+    J.R = &P; J.rating64 = c->pf_rating; J.dups = 1; J.method = XMAP_ADJUST_COSINE; J.cap = cap;
+    J.ch_min = (int)((U + 2 > 64) ? U + 2 : 64);        // more raters than users: no item is heavy
+    J.heavy = false; J.aux = true; J.skip_self = true; J.half_contrib = half_contrib;
+    J.stats_pool = J.mutu_pool = &tmp; J.csr_pool = &c->p_rec; J.row_ptr = c->rs_row_ptr;
+    TriResult O;
+    XM_TRY(tri_pass(c->st, J, tmp, O));
+    c->rs_col = O.col; c->rs_sim = O.sim; c->rs_nij = O.nij; c->rs_ls = O.aux;
     // the item averages the prediction reads are the layout's (exact sum / n), the norms its adjusted norms (zero user average)
-    XM_HIP(hipMemcpy2DAsync(c->rs_avg, sizeof(double), info, 4 * sizeof(double), sizeof(double), (size_t)I, hipMemcpyDeviceToDevice, c->st));
-    XM_HIP(hipMemcpyAsync(c->rs_norm, norms + I, sizeof(double) * (size_t)I, hipMemcpyDeviceToDevice, c->st));
-    int64_t kept = 0;
+    XM_HIP(hipMemcpy2DAsync(c->rs_avg, sizeof(double), O.info, 4 * sizeof(double), sizeof(double), (size_t)I, hipMemcpyDeviceToDevice, c->st));
+    XM_HIP(hipMemcpyAsync(c->rs_norm, O.norms + I, sizeof(double) * (size_t)I, hipMemcpyDeviceToDevice, c->st));
+    int64_t kept = 0;           // a self pair is one entry: the CSR's length is its last row pointer
     XM_TRY(d2h(&kept, (const int64_t *)(c->rs_row_ptr + I), 1, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
     c->rec_pairs = kept;
     c->have_rec = true;
     if (n_pairs) *n_pairs = kept;
     return XMAP_OK;
-#undef T_ALLOC
-#undef T_ALLOCZ
 }
 
 int xmap_ctx_rec_profiles_download(xmap_ctx *c, int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time) {
@@ -834,8 +797,7 @@ int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, cons
     if (max_now) *max_now = 0;
     if (mae) mae[0] = mae[1] = mae[2] = 0.0;
     if (n_test == 0) return XMAP_OK;
-    Pool tmp;
-    struct Guard { Pool &p; ~Guard() { p.release(); } } guard{tmp};
+    ScratchPool tmp;
     int32_t *d_user, *d_item, *d_status;
     double *d_real = nullptr, *d_w, *d_plain, *d_decay, *d_mae;
     const size_t n = (size_t)n_test;

@@ -1,5 +1,5 @@
 // item_stats.h -- get_universal_item_info (reference core/baselinerSim.py:40-82) for one item on a group of lanes; shared by
-// the CSC-driven kernel of stage_a.hip and the rater-record-driven one of stage_a2.hip (one transposition per pass).
+// the CSC-driven kernel of stage_a.hip and the rater-record-driven one of tri_layout.hip (one transposition per pass).
 #pragma once
 #include "common.h"
 
@@ -13,7 +13,7 @@ constexpr int ITEM_PART = 7;
 // stats of item i on a group of G lanes (G = 16: four items per wave; G = 64: the whole wave); gl = lane in the group.
 // All lanes of the wave call it (the reductions are wave instructions); `on` says whether this group has an item.
 // Src: where an item's raters come from -- src.load(p, rating, user) of rater p (CSC position) and src.uavg(user):
-// the CSC arrays (CscSrc) or the rater records of the pair kernel (stage_a2.hip: RcSrc / RcWideSrc).
+// the CSC arrays (CscSrc) or the rater records of the pair kernel (tri_layout.hip: RcSrc / RcWideSrc).
 struct CscSrc {
     const int *iuser; const float *irating; const double *u_avg;
     static constexpr bool has_flags = false;

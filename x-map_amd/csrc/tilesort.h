@@ -60,40 +60,7 @@ struct Geo {
 
 __device__ __forceinline__ long long measure(const Geo &G, int k, long long p) { return p + (long long)k * G.KW; }
 
-// one thread per key: tile, tile boundaries, large keys and their slices
-__global__ __launch_bounds__(256) void k_ts_plan(Geo G) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= G.K) return;
-    const long long p = G.ptr[k], cnt = G.ptr[k + 1] - p;
-    const int t = (int)(measure(G, k, p) >> G.ts_log);
-    const bool large = cnt >= (1ll << G.ts_log);
-    G.tk[k] = (unsigned)t | (large ? 0x80000000u : 0u);
-    const int tp = k > 0 ? (int)(measure(G, k - 1, G.ptr[k - 1]) >> G.ts_log) : -1;
-    for (int x = tp + 1; x <= t; x++) { G.tile_key0[x] = k; G.tile_pos0[x] = p; }
-    if (k == G.K - 1)
-        for (int x = t + 1; x <= G.T; x++) { G.tile_key0[x] = G.K; G.tile_pos0[x] = G.ptr[G.K]; }
-    if (large) {
-        G.tile_large[t] = k;
-        const int nsl = (int)((cnt + SL - 1) / SL);
-        const unsigned base = atomicAdd(&G.counters[1], (unsigned)nsl);
-        for (int x = 0; x < nsl; x++)
-            if ((long long)base + x < G.slist_cap) G.slist[base + x] = make_int2(k, x);
-    }
-}
-
-// one thread per level-A bucket: its chunks of CH records for level B
-__global__ __launch_bounds__(256) void k_ts_chunks(Geo G) {
-    const int a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= G.NA) return;
-    const int t0 = a << NB_LOG, t1 = min(G.T, (a + 1) << NB_LOG);
-    const long long size = G.tile_pos0[t1] - G.tile_pos0[t0];
-    const int nch = (int)((size + G.ch - 1) / G.ch);
-    if (nch == 0) return;
-    const unsigned base = atomicAdd(&G.counters[0], (unsigned)nch);
-    for (int x = 0; x < nch; x++)
-        if ((long long)base + x < G.clist_cap) G.clist[base + x] = make_int2(a, x);
-}
-
+// (k_ts_plan / k_ts_chunks, which fill these tables: with their only caller, ts_prepare in tri_mirror.hip)
 // exclusive scan of cnt[0 .. n) (n <= 2 * BT) into off[0 .. n], all BT threads call
 __device__ __forceinline__ void block_scan_2(const unsigned *cnt, unsigned *off, int n, unsigned *wsum) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;

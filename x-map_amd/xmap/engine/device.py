@@ -313,7 +313,7 @@ class Engine(object):
 
     def item_sim(self, method, cap, slot_target=SLOT_TARGET, item_range=None, stats=None, plan=None, algo="tri"):
         """baseliner_calculate_sim_pipeline.  algo "tri" (default): each unordered pair once + mirror
-        (stage_a2.hip); algo "rows": complete rows per unit (stage_a.hip), supports item_range -- a TEST formulation: its
+        (tri_pairs.hip and its siblings); algo "rows": complete rows per unit (stage_a.hip), supports item_range -- a TEST formulation: its
         kernels live in libxmap_hip_xcheck.so (abi.xlib()), not in the product library."""
         if algo == "tri" and item_range is None and plan is None:
             return self.item_sim_tri(method, cap, slot_target)
@@ -374,28 +374,15 @@ class Engine(object):
         S._keep = (col, sim, mutu, nij)
         return S
 
-    # ---- stage A, second formulation (stage_a2.hip): each unordered pair once, mirrored into the CSR
+    # ---- stage A, second formulation (csrc/tri.h, tri_*.hip): each unordered pair once, mirrored into the CSR
     def tri_layout(self, stats, slot_target=SLOT_TARGET, ch_min=CH_MIN, dups=False):
         """weight-sorted private profiles, rater records, heavy set, work units (method independent).
         dups: a profile may hold an item more than once (AlterEgo rows)."""
-        R = self.R
-        st = _stream(self.dev)
-        I, U, nnz = R.n_items, R.n_users, R.nnz
-        info = stats[2]
-        L = SimResult()
-        L.hist = self._empty(U + 2, torch.int32)
-        L.pre = self._empty(U + 3, torch.int64)
-        L.ctl = self._empty(4, torch.int32)
-        L.hid = self._empty(max(I, 1), torch.int32)
-        L.hlist = self._zeros(1024, torch.int32)
-        L.ub_key = self._empty(max(nnz, 1), torch.int64)
-        L.ub = self._empty(max(nnz, 1), torch.int64)           # (item | flag, rating bits) pairs
-        L.rc = self._empty(max(nnz, 1) * 2, torch.int64)       # 16-byte rater records
-        L.Wp = self._empty(max(I, 1), torch.int64)
-        L.dups = bool(dups)
+        R, I = self.R, self.R.n_items
+        L = self._layout_buffers(dups)
         h_ctl = (C.c_int32 * 2)()
         with self.timed("tri_layout"):
-            check(lib.xmap_sim2_layout(st, C.byref(R.c), vp(info), i32(ch_min), vp(L.hist), vp(L.pre), vp(L.ctl),
+            check(lib.xmap_sim2_layout(_stream(self.dev), C.byref(R.c), vp(stats[2]), i32(ch_min), vp(L.hist), vp(L.pre), vp(L.ctl),
                                        vp(L.hid), vp(L.hlist), vp(L.ub_key), vp(L.ub), vp(L.rc), vp(L.Wp),
                                        i32(1 if dups else 0), h_ctl))
         L.CH, L.n_heavy = int(h_ctl[0]), int(h_ctl[1])
@@ -405,16 +392,38 @@ class Engine(object):
         L.half_contrib, L.heavy_half = int(both[0]), int(both[1])
         return L
 
-    def _tri_plan(self, L, slot_target):
-        R = self.R
-        st = _stream(self.dev)
-        I = R.n_items
+    def _layout_buffers(self, dups, wide=False):
+        """what both layouts (tri_layout, layout3) fill for the plan and the pair kernels"""
+        I, U, nnz = self.R.n_items, self.R.n_users, self.R.nnz
+        n1, i1 = max(nnz, 1), max(I, 1)
+        L = SimResult()
+        L.hist = self._empty(U + 2, torch.int32)
+        L.pre = self._empty(U + 3, torch.int64)
+        L.ctl = self._empty(4, torch.int32)
+        L.hid = self._empty(i1, torch.int32)
+        L.hlist = self._zeros(1024, torch.int32)
+        L.ub_key = self._empty(n1, torch.int64)
+        L.ub = self._empty(n1 * (2 if wide else 1), torch.int64)    # (item | flag, rating bits) pairs; wide: 16-byte entries
+        L.rc = self._empty(n1 * 2, torch.int64)                      # 16-byte rater records
+        L.Wp = self._empty(i1, torch.int64)
+        L.dups = bool(dups)
+        return L
+
+    def _plan_buffers(self, L):
+        """what both plans (_tri_plan, _tri_plan3) fill per item"""
+        I = self.R.n_items
         L.Q = self._out(max(I, 1), torch.int32, I > 0)
         L.C = self._out(max(I, 1), torch.int32, I > 0)
         L.small = self._out(max(I, 1), torch.uint8, I > 0)
         L.Qcat = self._empty(5 * max(I, 1), torch.int32)
         L.uq_ptr = self._out(5 * I + 1, torch.int64, I > 0)     # light units class-major: [table class rank][item]
         L.uc_ptr = self._out(I + 1, torch.int64, I > 0)
+
+    def _tri_plan(self, L, slot_target):
+        R = self.R
+        st = _stream(self.dev)
+        I = R.n_items
+        self._plan_buffers(L)
         h = (C.c_int64 * 8)()
         with self.timed("tri_plan"):
             check(lib.xmap_sim2_plan(st, C.byref(R.c), i32(slot_target), vp(L.rc), vp(L.pre), vp(L.hid),
@@ -436,12 +445,7 @@ class Engine(object):
         R = self.R
         st = _stream(self.dev)
         I = R.n_items
-        L.Q = self._out(max(I, 1), torch.int32, I > 0)
-        L.C = self._out(max(I, 1), torch.int32, I > 0)
-        L.small = self._out(max(I, 1), torch.uint8, I > 0)
-        L.Qcat = self._empty(5 * max(I, 1), torch.int32)
-        L.uq_ptr = self._out(5 * I + 1, torch.int64, I > 0)
-        L.uc_ptr = self._out(I + 1, torch.int64, I > 0)
+        self._plan_buffers(L)
         cap_light = L.half_contrib // max(int(slot_target), 1) + I + 1
         cap_heavy = R.nnz // max(int(L.ch_min), 1) + 1025
         L.uq_item = self._empty(cap_light, torch.int32)
@@ -500,31 +504,32 @@ class Engine(object):
             hp_lo = self._empty(max(nh, 1) * 1024, torch.float64)
             hp_cnt = self._empty(max(nh, 1) * 1024, torch.int32)
             hp_mut = self._empty(max(nh, 1) * 1024, torch.int32)
-            d_cnt = self._zeros(6, torch.int64)       # [4], [5]: the shard sums (phases bit 64)
+            d_cnt = self._zeros(6, torch.int64)       # [4], [5]: the shard sums (PAIRS_SHARD_SUMS)
             d_shards = self._empty(2 * 4096, torch.int64)
-            rowcnt_h = self._empty(64 * 1024, torch.int32)
 
-            deal = 0 if heavy_deal is None else ((int(heavy_deal[1]) & 0xff) << 16) | ((int(heavy_deal[0]) & 0xff) << 8)
+            deal = 0 if heavy_deal is None else abi.pairs_deal(heavy_deal[1], heavy_deal[0])
+            heavy, merge = (abi.PAIRS_HEAVY, abi.PAIRS_HEAVY_MERGE) if do_heavy else (0, 0)
+            light = abi.PAIRS_LIGHT | (abi.PAIRS_RAW if raw else 0)
 
             def run(phases):
-                phases |= deal | (0 if marks else 128)
+                phases |= deal | (0 if marks else abi.PAIRS_NO_MARKS)
                 check(lib.xmap_sim2_pairs(
                     st, C.byref(R.c), m, int(cap), vp(u_avg), vp(self.norms), vp(L.rc), vp(L.ub), vp(L.Q), vp(L.small),
                     vp(L.uq_item),
                     vp(L.uq_q), L.cls_ptr, i64(lo), i64(hi), vp(L.hid), vp(L.hlist), vp(L.ctl), vp(L.C), vp(L.uc_ptr),
                     vp(L.uc_item), vp(L.uc_c), i32(nh), i32(L.n_heavy), phases,
                     vp(hp_hi), vp(hp_lo), vp(hp_cnt), vp(hp_mut), i64(cap_coo), vp(coo_i), vp(coo_j), vp(coo_sim),
-                    vp(coo_mutu), vp(coo_nij), vp(coo_ls), vp(rowcnt), vp(rowcnt_h), vp(d_shards), vp(d_cnt), vp(mircnt)))
+                    vp(coo_mutu), vp(coo_nij), vp(coo_ls), vp(rowcnt), vp(d_shards), vp(d_cnt), vp(mircnt)))
             if os.environ.get("XMAP_SPLIT_PHASES") == "1":        # one timer per phase (analysis)
                 with self.timed("pair_heavy"):
-                    run(8 | (1 if do_heavy else 0))
+                    run(abi.PAIRS_RESET | heavy)
                 with self.timed("pair_tri"):
-                    run(2 | (32 if raw else 0))
+                    run(light)
                 with self.timed("heavy_merge"):
-                    run((4 if do_heavy else 0) | 16)
+                    run(merge | abi.PAIRS_MIRCOUNT)
             else:       # the heavy rows (chunk partials + merge) on a side stream next to the class launches of the light rows
                 with self.timed("pair_tri"):
-                    run(8 | 2 | 16 | 64 | (5 if do_heavy else 0) | (32 if raw else 0))
+                    run(abi.PAIRS_RESET | heavy | light | merge | abi.PAIRS_MIRCOUNT | abi.PAIRS_SHARD_SUMS)
             if count_mir and split and not raw:
                 with self.timed("mir_count"):
                     scratch = self._empty(cap_coo, torch.int32)
@@ -590,13 +595,7 @@ class Engine(object):
         R = self.R
         with self.timed("rec_stats"):
             stats, L = self.layout3(slot_target, ch_min=max(64, R.n_users + 2), wide=True)      # no heavy set
-        info = stats[2]
-        if os.environ.get("XMAP_A_V2") == "1":        # round-2 mirror (cursor atomics), kept as a cross-check
-            coo, rowcnt, n, n_unordered = self.tri_pairs("adjust_cosine", cap, stats, L, do_heavy=False, rec=True)
-            S = self.tri_scatter(coo, rowcnt, info, n, L)
-        else:
-            coo, own, n, n_unordered, mir, shards = self.tri_pairs("adjust_cosine", cap, stats, L, do_heavy=False, rec=True, split=True, marks=False, count_mir=True)
-            S = self.tri_mirror(coo, own, mir, info, n, shards, counted=True)
+        S, n_unordered = self._pairs_to_csr("adjust_cosine", cap, stats, L, rec=True)
         S.cap, S.n_unordered, S.layout = int(cap), n_unordered, L
         S.norm = self.norms[R.n_items:2 * R.n_items]
         return S
@@ -627,23 +626,13 @@ class Engine(object):
         I, U, nnz = R.n_items, R.n_users, R.nnz
         n1, i1 = max(nnz, 1), max(I, 1)
         rw = 3 if wide else 2                                    # 64-bit words per sort record
-        L = SimResult()
+        L = self._layout_buffers(wide, wide)
         cnt = self._empty(i1, torch.int32)
         u_avg = self._zeros(max(U, 1), torch.float64) if wide else self._empty(max(U, 1), torch.float64)
         u_norm = None if wide else self._empty(max(U, 1), torch.float64)
-        L.hist = self._empty(U + 2, torch.int32)
-        L.pre = self._empty(U + 3, torch.int64)
-        L.ctl = self._empty(4, torch.int32)
-        L.hid = self._empty(i1, torch.int32)
-        L.hlist = self._zeros(1024, torch.int32)
-        L.ub_key = self._empty(n1, torch.int64)
-        L.ub = self._empty(n1 * (2 if wide else 1), torch.int64)
         srec = self._empty(n1 * rw, torch.int64)
         buf_a = self._empty(n1 * rw, torch.int64)
         buf_b = self._empty(n1 * rw, torch.int64)
-        L.rc = self._empty(n1 * 2, torch.int64)
-        L.Wp = self._empty(i1, torch.int64)
-        L.dups = bool(wide)
         L.wide = bool(wide)
         info = self._out((i1, 4), torch.float64, I > 0)
         self.norms = self._out(2 * i1, torch.float64, I > 0)
@@ -660,15 +649,15 @@ class Engine(object):
         L.half_contrib = R.half_contrib          # = sum of W+ over the items (the host knows it from the profile lengths)
         if item_range is None:
             with self.timed("layout3"):
-                call(1 | 2 | 4, 0, I)
+                call(abi.LAYOUT_RECORDS | abi.LAYOUT_STATS | abi.LAYOUT_UB_FLAGS, 0, I)
             self._tri_plan3(L, slot_target)
         else:
             with self.timed("layout3"):
-                call(1 | 2, int(item_range[0]), int(item_range[1]))
+                call(abi.LAYOUT_RECORDS | abi.LAYOUT_STATS, int(item_range[0]), int(item_range[1]))
 
             def finish():
                 with self.timed("layout3_flags"):
-                    call(4 | 8, 0, I)
+                    call(abi.LAYOUT_UB_FLAGS | abi.LAYOUT_RC_FLAGS, 0, I)
                 self._tri_plan3(L, slot_target)
             L.finish = finish
         return (u_avg, u_norm, info, None, None), L
@@ -730,6 +719,17 @@ class Engine(object):
         S.ls = ls[:kept] if ls is not None else None
         return S
 
+    def _pairs_to_csr(self, method, cap, stats, L, rec=False):
+        """pair kernels + mirror over a layout -> (CSR, unordered pairs evaluated).  XMAP_A_V2=1: the round-2 mirror (one
+        combined count per row, cursor atomics) -- kept as a cross-check of the round-3 one (own and mirrored counts apart,
+        tile sort).  rec: the RecommenderSim variant, no heavy rows."""
+        if os.environ.get("XMAP_A_V2") == "1":
+            coo, rowcnt, n, n_unordered = self.tri_pairs(method, cap, stats, L, do_heavy=not rec, rec=rec)
+            return self.tri_scatter(coo, rowcnt, stats[2], n, L), n_unordered
+        coo, own, n, n_unordered, mir, shards = self.tri_pairs(method, cap, stats, L, do_heavy=not rec, rec=rec, split=True,
+                                                               marks=False, count_mir=True)
+        return self.tri_mirror(coo, own, mir, stats[2], n, shards, counted=True), n_unordered
+
     def item_sim_tri(self, method, cap, slot_target=SLOT_TARGET, ch_min=CH_MIN):
         """baseliner_calculate_sim_pipeline, second formulation (all rows, one GPU).  XMAP_A_V2=1: the round-2 sequence
         (CSC build, CSC-driven rater records, cursor-atomic mirror) -- kept as a cross-check of the round-3 one."""
@@ -737,12 +737,9 @@ class Engine(object):
             with self.timed("stats"):
                 stats = self.stats()
             L = self.tri_layout(stats, slot_target, ch_min)
-            coo, rowcnt, n, n_unordered = self.tri_pairs(method, cap, stats, L)
-            S = self.tri_scatter(coo, rowcnt, stats[2], n, L)
         else:
             stats, L = self.layout3(slot_target, ch_min)
-            coo, rowcnt, n, n_unordered, mir, shards = self.tri_pairs(method, cap, stats, L, split=True, marks=False, count_mir=True)
-            S = self.tri_mirror(coo, rowcnt, mir, stats[2], n, shards, counted=True)
+        S, n_unordered = self._pairs_to_csr(method, cap, stats, L)
         S.method = abi.METHODS[method] if isinstance(method, str) else int(method)
         S.cap = int(cap)
         S.u_avg, S.u_norm = stats[0], stats[1]

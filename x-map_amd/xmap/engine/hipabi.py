@@ -18,6 +18,15 @@ COSINE_EXACT = 2          # XMAP_COSINE_EXACT: cosine with double-double sums (t
 TOPC = 10
 MID_ROWS_SPAN = 36864     # XMAP_MID_ROWS_SPAN: columns of a middle-list row per LDS pass
 ERR_HIP, ERR_ARG, ERR_OVERFLOW, ERR_CAPACITY = -1, -2, -3, -4     # XMAP_ERR_* of include/xmap_hip.h
+# phases of xmap_sim2_pairs (XMAP_PAIRS_*) and of xmap_sim3_layout (XMAP_LAYOUT_*); tests/test_cpu_host.py holds them to the header
+PAIRS_HEAVY, PAIRS_LIGHT, PAIRS_HEAVY_MERGE, PAIRS_RESET = 1, 2, 4, 8
+PAIRS_MIRCOUNT, PAIRS_RAW, PAIRS_SHARD_SUMS, PAIRS_NO_MARKS = 16, 32, 64, 128
+LAYOUT_RECORDS, LAYOUT_STATS, LAYOUT_UB_FLAGS, LAYOUT_RC_FLAGS, LAYOUT_ALL = 1, 2, 4, 8, 15
+
+
+def pairs_deal(m, r):
+    """XMAP_PAIRS_DEAL: of the heavy rows only those with item index % m == r"""
+    return ((int(m) & 0xff) << 16) | ((int(r) & 0xff) << 8)
 
 
 class XmapError(RuntimeError):
@@ -121,6 +130,15 @@ def header_prototypes(path=HEADER_PATH):
                 types.append(C.c_int32)
         out[name] = types
     return out
+
+
+def header_constants(prefixes=("XMAP_PAIRS_", "XMAP_LAYOUT_"), path=HEADER_PATH):
+    """{name without XMAP_: value} of the header's plain integer #defines with one of the prefixes"""
+    import re
+    with open(path) as f:
+        text = f.read()
+    return {n[len("XMAP_"):]: int(v) for n, v in re.findall(r"^#define\s+(XMAP_\w+)\s+(-?\d+)\b", text, flags=re.M)
+            if n.startswith(tuple(prefixes))}
 
 
 # argtypes of every export: a mis-ordered or mis-typed argument raises in ctypes instead of corrupting device memory
