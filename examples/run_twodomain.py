@@ -9,7 +9,8 @@ work directory (the reference ships none).
     python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
-(xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.
+(xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the top 5
+target items of three test users (xmap.engine.session.recommend_topn).
 """
 import argparse
 import os
@@ -122,6 +123,13 @@ def main(argv=None):
     print("train users %d, test users %d, sim pairs %d, AlterEgo rows %d" % (
         trainRDD.count(), testRDD.count(), item2item_simRDD.count(), alterEgo_profile.count()))
     print("MAE (no decay; decay):", mae)
+    from xmap.engine import session
+    if isinstance(alterEgo_profile, session.AlterEgoRDD) and not rc["private_flag"]:
+        # what the library is for: target-domain items for users known through their source-domain ratings
+        top = session.recommend_topn(alterEgo_profile, [uid for uid, _ in testRDD.take(3)], rc["calculate_xmap_weighting"],
+                                     rc["mapping_range"], rc["decay_alpha"], 5)
+        for uid, lst in top.collect():
+            print("top 5 for %s:" % uid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "no evidence")
     print("seconds:", {k: round(v, 3) for k, v in t.items()})
     return mae
 

@@ -590,6 +590,33 @@ int xmap_predict_rows(void *stream, int64_t n_test, const int32_t *test_user, co
 int xmap_mae(void *stream, int64_t n_test, const int32_t *status, const double *real, const double *out_plain, const double *out_decay,
              double *mae /*[3], device*/);
 
+/* ---- top-N recommendation (csrc/stage_e_topn.hip): per query user the n_top best items among those the user's own rows give
+ * evidence for, ranked by the UNROUNDED prediction.  Same arrays as xmap_predict_rows (neighbour lists nb_cnt [I], nb_col /
+ * nb_sim [I][keep], keep <= 64; profiles; item_avg [I]; wtab[d] = exp(-alpha d), d = 0 .. n_w - 1).
+ *   candidates of user u: the items i with nb_cnt[i] > 0 of whose first min(nb_cnt[i], keep) neighbours u's profile holds at
+ *     least one (an entry outside [0, I) is ignored), and -- without XMAP_TOPN_KEEP_HELD -- that u does not hold itself.  An
+ *     item without evidence is never a candidate (its prediction is the item average, the same for every user).
+ *   scores: `plain` and `decayed`, the two values xmap_predict_rows holds before bound_rating -- the same kernel body, so the
+ *     same operations in the same order (evidence in list order, within a neighbour in profile order, sums left to right in
+ *     fp64, decayed sums in stable time order, equal times share a rank, now = ranks + 1); no limit on the evidence.  A
+ *     candidate xmap_predict_rows would give status 2 (zero weight sum, non-finite value, now > n_w) is dropped and counted.
+ *   ranking: by rank_by (0 plain, 1 decayed) descending, item index ascending on equal scores (scores compare as numbers).
+ *   outputs per query q (device): out_cnt[q] = min(n_top, candidates kept); out_item [q][n_top] (-1 behind the count),
+ *     out_plain / out_decay [q][n_top] (0.0 behind the count).  1 <= n_top <= 64.  A query user outside [0, n_users) or without
+ *     rows gets count 0; query users may repeat, in any order.  The result is a pure function of the inputs.
+ *   h_stats (host, [4] or NULL): candidates scored, candidates dropped, the largest `now` met (beyond n_w: call again with a
+ *     table of that length, as with xmap_predict_rows), the largest candidate count of one query.
+ * Passes: reverse neighbour lists (count, scan, fill) -> candidates per query through an LDS bitmap of the item space (count,
+ * scan, fill: buffers of exactly the counted size) -> scores -> segmented selection.  Temporaries from the stream's arena.  Syncs. */
+#define XMAP_TOPN_KEEP_HELD 1
+int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                   int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                   const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                   const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
+                   int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
+                   int64_t *h_stats /* host, [4] or NULL: candidates scored, candidates dropped (status 2),
+                                       largest `now`, largest candidate count of one query */);
+
 /* ---- stage C: generator_pipeline (utils/assist.py:136-150) ---------------------------------- */
 
 /* Generator.cross_private_mapping / cross_nonprivate_mapping (core/generator.py:27-111) + map_to_dict
@@ -630,7 +657,7 @@ int xmap_alterego_fill(void *stream, const xmap_ratings *R, const int32_t *map_s
  *                             choice [I] (or NULL) receives the chosen source item per start (-1: none)
  *   xmap_ctx_gen_download   : AlterEgo rows (user, item, rating fp64, time), pass-through target rows first
  * The recommender tail over those rows, all on the device (call order: generate -> rec_sim -> rec_select or
- * rec_set_neighbors -> predict; any of item_sim / extend / generate / upload drops the tail):
+ * rec_set_neighbors -> predict | recommend; any of item_sim / extend / generate / upload drops the tail):
  *   xmap_ctx_rec_sim        : recommender_calculate_sim_pipeline (assist.py:153-177): user-major profiles of the AlterEgo
  *                             rows, then RecommenderSim (cosine branch, cap) -> n_pairs directed pairs, a self pair once
  *   xmap_ctx_rec_profiles_download : the profiles (prof_ptr [U+1], item / rating / time [n_rows]); any pointer may be NULL
@@ -645,6 +672,11 @@ int xmap_alterego_fill(void *stream, const xmap_ratings *R, const int32_t *map_s
  *                             xmap_predict_rows; test_rating may be NULL, else mae [3] (may be NULL) = {predicted pairs,
  *                             sum |real - plain|, sum |real - decayed|}; *max_now (may be NULL) = table length that serves
  *                             every pair (status 2 pairs of a shorter table: call again with a longer one)
+ *   xmap_ctx_recommend      : top-N recommendation (xmap_topn_rows over the resident profiles, lists and averages): host
+ *                             arrays in and out; n_query user indices, 1 <= n_top <= 64, rank_by 0 plain / 1 decayed, flags
+ *                             0 or XMAP_TOPN_KEEP_HELD; out_cnt [n_query], out_item / out_plain / out_decay [n_query][n_top];
+ *                             stats [4] (may be NULL) as h_stats; stats[2] > n_w: call again with a table of that length.
+ *                             Needs the same stages as xmap_ctx_predict and is dropped by the same calls
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -702,6 +734,9 @@ int xmap_ctx_rec_neighbors_download(xmap_ctx *ctx, int32_t *cnt, int32_t *col, d
 int xmap_ctx_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
                      const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
                      int32_t *max_now);
+int xmap_ctx_recommend(xmap_ctx *ctx, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
+                       int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item,
+                       double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
 
 #ifdef __cplusplus
 }

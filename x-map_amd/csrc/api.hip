@@ -6,6 +6,7 @@
 //                                              -> xmap_ctx_generate     (generator_pipeline, assist.py:136-150)
 //   the recommender tail over the AlterEgo rows, device-resident:   -> xmap_ctx_rec_sim (assist.py:153-177)
 //                     -> xmap_ctx_rec_select | xmap_ctx_rec_set_neighbors (assist.py:179-192) -> xmap_ctx_predict (assist.py:195-207)
+//                                                                                  | xmap_ctx_recommend (top-N per query user)
 //   xmap_ctx_*_download copy results into caller-allocated host buffers whose sizes the stage call reported.
 //
 // Everything below is orchestration of the kernels' own entry points (include/xmap_hip.h): buffer sizes, prefix sums,
@@ -816,6 +817,36 @@ int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, cons
     XM_TRY(d2h(out_plain, (const double *)d_plain, n, c->st));
     XM_TRY(d2h(out_decay, (const double *)d_decay, n, c->st));
     XM_TRY(d2h(status, (const int32_t *)d_status, n, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                       const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
+                       int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(n_top >= 1 && n_top <= 64);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query >= 0 && (n_query == 0 || (query_user && out_cnt && out_item && out_plain && out_decay)));
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (n_query == 0) return XMAP_OK;
+    ScratchPool tmp;
+    int32_t *d_user, *d_cnt, *d_item;
+    double *d_w, *d_plain, *d_decay;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_user, query_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
+    XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, c->R.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim,
+                          c->pf_ptr, c->pf_item, c->pf_rating, c->pf_time, c->rs_avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
     return XMAP_OK;
 }

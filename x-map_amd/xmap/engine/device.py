@@ -1491,6 +1491,32 @@ class Engine(object):
                                         vp(plain), vp(decay), vp(status), C.byref(h)))
         return plain[:T], decay[:T], status[:T], int(h.value)
 
+    def topn(self, P, neighbors, query_user, item_avg, wtab, n_top, rank_by=0, keep_held=False):
+        """Top-N recommendation on the device (xmap_topn_rows) over the profiles P of alterego_profiles: per query user the
+        n_top (1..64) best items its own rows give evidence for, by the unrounded prediction (rank_by 0: plain, 1: decayed;
+        score descending, item index ascending); items the user holds are left out unless keep_held.  neighbors, item_avg,
+        wtab as predict() takes them; query_user an int32 tensor (any order, repeats allowed; an index outside the users: no
+        items).  Returns (cnt [Q], item [Q][n_top] (-1 behind the count), plain, decayed [Q][n_top], stats) with stats =
+        (candidates scored, candidates dropped, largest `now`, largest candidate count of a query): candidates were dropped
+        for a short table when stats[2] > len(wtab)."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        Q, n_top = int(query_user.numel()), int(n_top)
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        if not 1 <= n_top <= 64:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 64" % n_top)
+        out_cnt = self._empty(max(Q, 1), torch.int32)
+        out_item = self._empty((max(Q, 1), n_top), torch.int32)
+        out_plain = self._empty((max(Q, 1), n_top), torch.float64)
+        out_decay = self._empty((max(Q, 1), n_top), torch.float64)
+        h = (C.c_int64 * 4)(0, 0, 0, 0)
+        with self.timed("topn"):
+            check(lib.xmap_topn_rows(st, i64(Q), vp(query_user.contiguous()), i32(n_top), i32(rank_by), i32(abi.TOPN_KEEP_HELD if keep_held else 0),
+                                     i64(P.n_users), i32(P.n_items), i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
+                                     vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()),
+                                     vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
+        return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
+
     def mae(self, status, real, plain, decay):
         """calculate_mae's sums on the device (xmap_mae): tensor [3] = (predicted pairs, sum |real - plain|, sum |real - decayed|)"""
         out = self._empty(3, torch.float64)

@@ -263,19 +263,13 @@ def time_rank(state):
     return key
 
 
-def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
-    """The recommender tail on the device, from an AlterEgoRDD handle to the records of
-    RecommenderPrediction.item_based_recommendation: profiles of the AlterEgo rows (Engine.alterego_profiles), RecommenderSim
-    (rec_sim, cap), neighbour selection (rec_select, keep = mapping_range; or `neighbors`: the lists a host-side selection
-    made, [(iid, [(nid, sim)*])*] or a dict of them -- the private route), prediction with temporal decay alpha and no limit
-    on the evidence of a pair (Engine.predict).  Returns a LocalRDD of (uid, [(iid, real, plain, decayed) | ()]) in testRDD
-    order, usable with calculate_mae; it carries .mae (count, sum |real - plain|, sum |real - decayed| from the device, or
-    None when a real rating is not a number), .item_info {iid: (avg, norm, n)} and .sim_pairs {iid: [(nid, sim)*]}: the
-    dictionaries the Python statement takes.  A user id matches by equality."""
+def _tail_setup(alterEgoRDD, cap, keep, neighbors, who):
+    """what recommend and recommend_topn share: profiles of the AlterEgo rows -> RecommenderSim -> neighbour lists (selected on
+    the device, or the caller's lists as arrays).  Returns (state, engine over the profiles, P, S, (cnt, col, sim), item_avg)."""
     import torch
     from . import device
     if not isinstance(alterEgoRDD, AlterEgoRDD):
-        raise TypeError("recommend() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device)")
+        raise TypeError("%s() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device)" % who)
     st, G = alterEgoRDD.state, alterEgoRDD.G
     eng, idt = st.engine, st.idt
     dev = eng.dev
@@ -303,6 +297,35 @@ def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
                 col[i, q] = idt.iidx[nid]
                 sim[i, q] = sv
         nb = tuple(torch.from_numpy(a).to(dev) for a in (cnt, col, sim))
+    return st, eng2, P, S, nb, item_avg
+
+
+def _decay_table(alpha, n_w, dev):
+    import torch
+    return torch.from_numpy(np.asarray([np.exp(- alpha * d) for d in range(n_w)], np.float64)).to(dev)     # scalar np.exp, like the reference
+
+
+def _tail_dicts(res, st, S, nb):
+    """.item_info {iid: (avg, norm, n)} and .sim_pairs {iid: [(nid, sim)*]} of a tail result"""
+    cnt, col, sim = [x.cpu().numpy() for x in nb]
+    info, iids = S.info.cpu().numpy(), st.idt.iids
+    I = len(iids)
+    res.item_info = {iids[i]: (float(info[i, 0]), float(info[i, 1]), int(info[i, 3])) for i in range(I) if info[i, 3] > 0}
+    res.sim_pairs = {iids[i]: [(iids[col[i, t]], float(sim[i, t])) for t in range(cnt[i])] for i in range(I) if cnt[i] > 0}
+
+
+def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
+    """The recommender tail on the device, from an AlterEgoRDD handle to the records of
+    RecommenderPrediction.item_based_recommendation: profiles of the AlterEgo rows (Engine.alterego_profiles), RecommenderSim
+    (rec_sim, cap), neighbour selection (rec_select, keep = mapping_range; or `neighbors`: the lists a host-side selection
+    made, [(iid, [(nid, sim)*])*] or a dict of them -- the private route), prediction with temporal decay alpha and no limit
+    on the evidence of a pair (Engine.predict).  Returns a LocalRDD of (uid, [(iid, real, plain, decayed) | ()]) in testRDD
+    order, usable with calculate_mae; it carries .mae (count, sum |real - plain|, sum |real - decayed| from the device, or
+    None when a real rating is not a number), .item_info {iid: (avg, norm, n)} and .sim_pairs {iid: [(nid, sim)*]}: the
+    dictionaries the Python statement takes.  A user id matches by equality."""
+    import torch
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend")
+    idt, dev = st.idt, st.engine.dev
     recs = records_of(testRDD)
     uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
     tu = np.fromiter((uidx.get(uid, -1) for uid, pairs in recs for _ in pairs), np.int32)
@@ -314,7 +337,7 @@ def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
     d_tu, d_ti = torch.from_numpy(tu).to(dev), torch.from_numpy(ti).to(dev)
     n_w = 66
     while True:
-        wtab = torch.from_numpy(np.asarray([np.exp(- alpha * d) for d in range(n_w)], np.float64)).to(dev)     # scalar np.exp, like the reference
+        wtab = _decay_table(alpha, n_w, dev)
         plain, decay, status, max_now = eng2.predict(P, nb, d_tu, d_ti, item_avg, wtab)
         if max_now <= n_w:
             break
@@ -323,8 +346,6 @@ def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
     if real is not None and len(tu):
         mae = tuple(eng2.mae(status, torch.from_numpy(real).to(dev), plain, decay).tolist())
     plain, decay, status = plain.cpu().numpy(), decay.cpu().numpy(), status.cpu().numpy()
-    cnt, col, sim = [x.cpu().numpy() for x in nb]
-    info, iids = S.info.cpu().numpy(), idt.iids
     out, q = [], 0
     for uid, pairs in recs:
         line = []
@@ -340,8 +361,37 @@ def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
         out.append((uid, line))
     res = LocalRDD(out, getattr(testRDD, "ctx", None))
     res.mae = mae
-    res.item_info = {iids[i]: (float(info[i, 0]), float(info[i, 1]), int(info[i, 3])) for i in range(I) if info[i, 3] > 0}
-    res.sim_pairs = {iids[i]: [(iids[col[i, t]], float(sim[i, t])) for t in range(cnt[i])] for i in range(I) if cnt[i] > 0}
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
+def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None):
+    """Top-N recommendation on the device from an AlterEgoRDD handle: the set-up of recommend (profiles -> RecommenderSim ->
+    neighbour lists, or `neighbors`), then for every uid of `users` the n (1..64) best items its own rows give evidence for,
+    ranked by the unrounded prediction -- without temporal decay, or with (decay=True, alpha) -- score descending, item id
+    ascending on equal scores; items the user already holds are left out unless keep_held (Engine.topn).  Returns a LocalRDD
+    of (uid, [(iid, plain, decayed)*]) in the order of `users`; a uid the train set does not know gives (uid, []).  It carries
+    .sim_pairs and .item_info like recommend, and .stats = (candidates scored, candidates dropped, largest `now`, largest
+    candidate count of a user)."""
+    import torch
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn")
+    idt, dev = st.idt, st.engine.dev
+    uids = list(users.collect()) if hasattr(users, "collect") else list(users)
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    d_q = torch.from_numpy(np.fromiter((uidx.get(uid, -1) for uid in uids), np.int32, len(uids))).to(dev)
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        cnt, item, plain, decayed, stats = eng2.topn(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_held)
+        if stats[2] <= n_w:
+            break
+        n_w = stats[2]
+    cnt, item, plain, decayed = cnt.cpu().numpy(), item.cpu().numpy(), plain.cpu().numpy(), decayed.cpu().numpy()
+    iids = idt.iids
+    out = [(uid, [(iids[item[q, t]], float(plain[q, t]), float(decayed[q, t])) for t in range(cnt[q])]) for q, uid in enumerate(uids)]
+    res = LocalRDD(out, getattr(users, "ctx", None))
+    res.stats = stats
+    _tail_dicts(res, st, S, nb)
     return res
 
 
