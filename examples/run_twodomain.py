@@ -9,8 +9,9 @@ work directory (the reference ships none).
     python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
-(xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the top 5
-target items of three test users (xmap.engine.session.recommend_topn).
+(xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
+metrics of the top-20 lists against the held-out ratings (xmap.engine.session.evaluate_topn), then the top 5 target items of
+three test users (xmap.engine.session.recommend_topn).
 """
 import argparse
 import os
@@ -125,6 +126,13 @@ def main(argv=None):
     print("MAE (no decay; decay):", mae)
     from xmap.engine import session
     if isinstance(alterEgo_profile, session.AlterEgoRDD) and not rc["private_flag"]:
+        # the ranking quality of the lists against the held-out ratings (relevant: 4 stars and more), scored on the device
+        ev = session.evaluate_topn(alterEgo_profile, testRDD, rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"], 20,
+                                   cutoffs=(5, 10, 20), rel_min=4.0)
+        for c in sorted(ev.at):
+            m = ev.at[c]
+            print("top-%d over %d users: hit rate %.4f, precision %.4f, recall %.4f, NDCG %.4f, MAP %.4f, MRR %.4f, %d items covered" % (
+                c, m["users"], m["hit_rate"], m["precision"], m["recall"], m["ndcg"], m["map"], m["mrr"], m["coverage"]))
         # what the library is for: target-domain items for users known through their source-domain ratings
         top = session.recommend_topn(alterEgo_profile, [uid for uid, _ in testRDD.take(3)], rc["calculate_xmap_weighting"],
                                      rc["mapping_range"], rc["decay_alpha"], 5)

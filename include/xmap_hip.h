@@ -617,6 +617,43 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                    int64_t *h_stats /* host, [4] or NULL: candidates scored, candidates dropped (status 2),
                                        largest `now`, largest candidate count of one query */);
 
+/* ---- hold-out evaluation of the top-N lists (csrc/stage_e_eval.hip): what xmap_mae is to xmap_predict_rows.  The lists stay
+ * where xmap_topn_rows wrote them; the held-out (user, item, rating) pairs are the ones xmap_ctx_predict takes.
+ * xmap_eval_users: held-out pairs -> the users worth ranking for.  A pair is IGNORED if user is outside [0, U), item outside
+ *   [0, I) or the rating is NaN; otherwise RELEVANT iff rating >= rel_min (rel_min NaN: XMAP_ERR_ARG).  n_rel[u] = relevant
+ *   pairs of u (occurrences: the caller passes every (user, item) once, as baselinerSplit does; a repeated relevant pair counts
+ *   as often as it occurs here and once as a hit).  eval_user[0 .. n_eval) = the users with n_rel > 0, ascending.
+ *   h_counts = {n_eval, relevant pairs, ignored pairs, pairs below rel_min}.  Syncs.
+ * xmap_topn_eval: lists as xmap_topn_rows wrote them (out_cnt [Q], out_item [Q][n_top], 1 <= n_top <= 64) for DISTINCT
+ *   in-range query users (a repeated user: XMAP_ERR_ARG, found on the device) + the same pairs -> per query the hit mask
+ *   (bit r = out_item[q][r] is a relevant held-out item of query_user[q], r < out_cnt[q]), per query and cutoff the five
+ *   metrics, and the aggregates.  h_cut: 1 <= n_cut <= 8 cutoffs, strictly ascending, 1 <= c <= n_top.
+ *   dtab[r], r < n_top: the rank discount, made by the caller (1 / log2(r + 2)), like wtab.
+ *   Per evaluated query -- L the list, R the relevant set, n = n_rel[user], c the cutoff -- every operation fp64 IEEE, the
+ *   divisions correctly rounded, sums left to right in ascending rank:
+ *       h = 0; dcg = ap = rr = 0.0
+ *       for r in range(min(c, len(L))):
+ *           if L[r] in R:
+ *               h += 1; dcg = dcg + dtab[r]; ap = ap + h / (r + 1)
+ *               if rr == 0.0: rr = 1.0 / (r + 1)
+ *       idcg = 0.0
+ *       for r in range(min(c, n)): idcg = idcg + dtab[r]
+ *       precision, recall, ndcg, ap, rr = h / c, h / n, dcg / idcg, ap / min(c, n), rr
+ *   q_metric [Q][n_cut][5] = (precision, recall, ndcg, ap, rr); may be NULL.
+ *   A query whose user is out of range or has n_rel == 0 is not evaluated: mask 0, metrics 0.0, not counted.
+ *   agg [n_cut][8] (device) = {evaluated queries, queries with a hit within c, hits within c, sum precision, sum recall,
+ *   sum ndcg, sum ap, sum rr}: the first three exact integers, the sums exact double-double sums rounded once (as xmap_mae),
+ *   so independent of grid and order.  cover [n_cut] (device) = distinct items in the first min(c, out_cnt[q]) positions
+ *   over ALL queries.  Temporaries from the stream's arena.  Syncs. */
+int xmap_eval_users(void *stream, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
+                    const double *test_rating, double rel_min, int64_t n_users, int32_t n_items,
+                    int32_t *n_rel /*[U]*/, int32_t *eval_user /*[U]*/, int64_t *h_counts /*[4]*/);
+int xmap_topn_eval(void *stream, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
+                   const double *test_rating, double rel_min, int64_t n_users, int32_t n_items, const int32_t *n_rel,
+                   int64_t n_query, const int32_t *query_user, int32_t n_top, const int32_t *out_cnt,
+                   const int32_t *out_item, int32_t n_cut, const int32_t *h_cut, const double *dtab,
+                   uint64_t *q_mask /*[Q]*/, double *q_metric /*[Q][n_cut][5] or NULL*/, double *agg, int64_t *cover);
+
 /* ---- stage C: generator_pipeline (utils/assist.py:136-150) ---------------------------------- */
 
 /* Generator.cross_private_mapping / cross_nonprivate_mapping (core/generator.py:27-111) + map_to_dict
@@ -657,7 +694,7 @@ int xmap_alterego_fill(void *stream, const xmap_ratings *R, const int32_t *map_s
  *                             choice [I] (or NULL) receives the chosen source item per start (-1: none)
  *   xmap_ctx_gen_download   : AlterEgo rows (user, item, rating fp64, time), pass-through target rows first
  * The recommender tail over those rows, all on the device (call order: generate -> rec_sim -> rec_select or
- * rec_set_neighbors -> predict | recommend; any of item_sim / extend / generate / upload drops the tail):
+ * rec_set_neighbors -> predict | recommend | evaluate_topn; any of item_sim / extend / generate / upload drops the tail):
  *   xmap_ctx_rec_sim        : recommender_calculate_sim_pipeline (assist.py:153-177): user-major profiles of the AlterEgo
  *                             rows, then RecommenderSim (cosine branch, cap) -> n_pairs directed pairs, a self pair once
  *   xmap_ctx_rec_profiles_download : the profiles (prof_ptr [U+1], item / rating / time [n_rows]); any pointer may be NULL
@@ -677,6 +714,15 @@ int xmap_alterego_fill(void *stream, const xmap_ratings *R, const int32_t *map_s
  *                             0 or XMAP_TOPN_KEEP_HELD; out_cnt [n_query], out_item / out_plain / out_decay [n_query][n_top];
  *                             stats [4] (may be NULL) as h_stats; stats[2] > n_w: call again with a table of that length.
  *                             Needs the same stages as xmap_ctx_predict and is dropped by the same calls
+ *   xmap_ctx_evaluate_topn  : hold-out evaluation of the top-N lists (xmap_eval_users -> xmap_topn_rows over eval_user with the
+ *                             resident profiles, lists and averages -> xmap_topn_eval): host arrays in and out; the n_test
+ *                             pairs (user, item, rating) of xmap_ctx_predict, every (user, item) once; rel_min, n_cut cutoffs
+ *                             `cut` and the discounts dtab [n_top] as xmap_topn_eval takes them; n_top, rank_by, flags, wtab,
+ *                             n_w as xmap_ctx_recommend.  agg [n_cut][8], cover [n_cut]; user_nrel [U] and user_mask [U] (0
+ *                             for a user not evaluated) may be NULL; stats [8] (may be NULL) = the four h_counts of
+ *                             xmap_eval_users, then the four h_stats of xmap_topn_rows; stats[6] > n_w: call again with a
+ *                             table of that length.  n_test == 0 or no evaluated user: zeroed outputs.  Needs the same
+ *                             stages as xmap_ctx_recommend and is dropped by the same calls
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -737,6 +783,12 @@ int xmap_ctx_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, co
 int xmap_ctx_recommend(xmap_ctx *ctx, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
                        int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item,
                        double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
+int xmap_ctx_evaluate_topn(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
+                           const double *test_rating, double rel_min, int32_t n_top, int32_t rank_by, int32_t flags,
+                           const double *wtab, int32_t n_w, int32_t n_cut, const int32_t *cut, const double *dtab,
+                           double *agg /*[n_cut][8]*/, int64_t *cover /*[n_cut]*/,
+                           int32_t *user_nrel /*[U] or NULL*/, uint64_t *user_mask /*[U] or NULL: 0 for a user not evaluated*/,
+                           int64_t *stats /*[8] or NULL*/);
 
 #ifdef __cplusplus
 }

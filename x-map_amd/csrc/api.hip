@@ -7,6 +7,7 @@
 //   the recommender tail over the AlterEgo rows, device-resident:   -> xmap_ctx_rec_sim (assist.py:153-177)
 //                     -> xmap_ctx_rec_select | xmap_ctx_rec_set_neighbors (assist.py:179-192) -> xmap_ctx_predict (assist.py:195-207)
 //                                                                                  | xmap_ctx_recommend (top-N per query user)
+//                                                                                  | xmap_ctx_evaluate_topn (top-N against held-out pairs)
 //   xmap_ctx_*_download copy results into caller-allocated host buffers whose sizes the stage call reported.
 //
 // Everything below is orchestration of the kernels' own entry points (include/xmap_hip.h): buffer sizes, prefix sums,
@@ -847,6 +848,74 @@ int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, 
     XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
     XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+int xmap_ctx_evaluate_topn(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                           double rel_min, int32_t n_top, int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t n_cut,
+                           const int32_t *cut, const double *dtab, double *agg, int64_t *cover, int32_t *user_nrel, uint64_t *user_mask,
+                           int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(n_top >= 1 && n_top <= 64);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_cut >= 1 && n_cut <= 8 && cut && dtab && agg && cover);
+    for (int k = 0; k < n_cut; k++) XM_ARG(cut[k] >= 1 && cut[k] <= n_top && (k == 0 || cut[k] > cut[k - 1]));
+    XM_ARG(rel_min == rel_min);
+    XM_ARG(n_test >= 0 && (n_test == 0 || (test_user && test_item && test_rating)));
+    XM_HIP(hipSetDevice(c->device));
+    const size_t U = (size_t)c->R.n_users;
+    for (int k = 0; k < n_cut * 8; k++) agg[k] = 0.0;
+    for (int k = 0; k < n_cut; k++) cover[k] = 0;
+    if (user_nrel) memset(user_nrel, 0, sizeof(int32_t) * U);
+    if (user_mask) memset(user_mask, 0, sizeof(uint64_t) * U);
+    if (stats) memset(stats, 0, sizeof(int64_t) * 8);
+    if (n_test == 0 || U == 0) return XMAP_OK;
+    ScratchPool tmp;
+    int32_t *d_tu, *d_ti, *d_nrel, *d_eval;
+    double *d_tr;
+    const size_t n = (size_t)n_test;
+    XM_TRY(h2d(tmp, &d_tu, test_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_ti, test_item, n, c->st));
+    XM_TRY(h2d(tmp, &d_tr, test_rating, n, c->st));
+    XM_TRY(dalloc(tmp, &d_nrel, U, c->st)); XM_TRY(dalloc(tmp, &d_eval, U, c->st));
+    int64_t counts[4] = {0, 0, 0, 0};
+    XM_TRY(xmap_eval_users(c->st, n_test, d_tu, d_ti, d_tr, rel_min, c->R.n_users, c->R.n_items, d_nrel, d_eval, counts));
+    if (stats) memcpy(stats, counts, sizeof(counts));
+    if (user_nrel) XM_TRY(d2h(user_nrel, (const int32_t *)d_nrel, U, c->st));
+    const size_t Q = (size_t)counts[0], m = Q * (size_t)n_top;
+    if (Q == 0) {
+        XM_HIP(hipStreamSynchronize(c->st));
+        return XMAP_OK;
+    }
+    // ---- the lists of the users with relevant pairs: they stay on the device
+    int32_t *d_cnt, *d_item;
+    double *d_w, *d_dtab, *d_plain, *d_decay, *d_agg;
+    uint64_t *d_mask;
+    int64_t *d_cover;
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(h2d(tmp, &d_dtab, dtab, (size_t)n_top, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, Q, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
+    XM_TRY(dalloc(tmp, &d_mask, Q, c->st)); XM_TRY(dalloc(tmp, &d_agg, (size_t)n_cut * 8, c->st));
+    XM_TRY(dalloc(tmp, &d_cover, (size_t)n_cut, c->st));
+    XM_TRY(xmap_topn_rows(c->st, (int64_t)Q, d_eval, n_top, rank_by, flags, c->R.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col,
+                          c->nb_sim, c->pf_ptr, c->pf_item, c->pf_rating, c->pf_time, c->rs_avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay,
+                          stats ? stats + 4 : nullptr));
+    XM_TRY(xmap_topn_eval(c->st, n_test, d_tu, d_ti, d_tr, rel_min, c->R.n_users, c->R.n_items, d_nrel, (int64_t)Q, d_eval, n_top, d_cnt,
+                          d_item, n_cut, cut, d_dtab, d_mask, nullptr, d_agg, d_cover));
+    XM_TRY(d2h(agg, (const double *)d_agg, (size_t)n_cut * 8, c->st));
+    XM_TRY(d2h(cover, (const int64_t *)d_cover, (size_t)n_cut, c->st));
+    if (user_mask) {                // per user, from the per-query masks
+        std::vector<uint64_t> h_mask(Q);
+        std::vector<int32_t> h_eval(Q);
+        XM_TRY(d2h(h_mask.data(), (const uint64_t *)d_mask, Q, c->st));
+        XM_TRY(d2h(h_eval.data(), (const int32_t *)d_eval, Q, c->st));
+        XM_HIP(hipStreamSynchronize(c->st));
+        for (size_t q = 0; q < Q; q++) user_mask[h_eval[q]] = h_mask[q];
+    }
     XM_HIP(hipStreamSynchronize(c->st));
     return XMAP_OK;
 }

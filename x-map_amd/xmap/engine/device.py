@@ -1517,6 +1517,45 @@ class Engine(object):
                                      vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
         return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
 
+    def eval_users(self, test_user, test_item, test_rating, rel_min, n_users, n_items):
+        """The users worth ranking for (xmap_eval_users): held-out pairs as int32 / int32 / fp64 tensors -> (n_rel [U] int32:
+        relevant pairs per user, eval_user int32: the users with n_rel > 0 ascending, counts = (evaluated users, relevant
+        pairs, ignored pairs, pairs below rel_min)).  A pair with a user or item outside the index space or a NaN rating is
+        ignored; relevant means rating >= rel_min."""
+        T, U = int(test_user.numel()), int(n_users)
+        n_rel = self._empty(max(U, 1), torch.int32)
+        users = self._empty(max(U, 1), torch.int32)
+        h = (C.c_int64 * 4)(0, 0, 0, 0)
+        with self.timed("eval_users"):
+            check(lib.xmap_eval_users(_stream(self.dev), i64(T), vp(test_user.contiguous()), vp(test_item.contiguous()),
+                                      vp(test_rating.contiguous()), C.c_double(rel_min), i64(U), i32(n_items), vp(n_rel), vp(users), h))
+        return n_rel[:U], users[:int(h[0])], tuple(int(x) for x in h)
+
+    def topn_eval(self, test_user, test_item, test_rating, rel_min, n_rel, query_user, out_cnt, out_item, cutoffs, n_items,
+                  per_query=False):
+        """Hold-out evaluation of top-N lists on the device (xmap_topn_eval): the lists (out_cnt [Q], out_item [Q][n_top]) as
+        topn() returned them for the DISTINCT users query_user, the held-out pairs and n_rel of eval_users(), cutoffs strictly
+        ascending within 1 .. n_top (at most 8).  Returns (mask [Q] int64: bit r = position r is a relevant held-out item,
+        q_metric [Q][n_cut][5] = (precision, recall, ndcg, ap, rr) or None without per_query, agg [n_cut][8] = (evaluated
+        queries, queries with a hit, hits, sum precision, sum recall, sum ndcg, sum ap, sum rr), cover [n_cut] int64 = distinct
+        items within the cutoff)."""
+        st = _stream(self.dev)
+        T, Q = int(test_user.numel()), int(query_user.numel())
+        n_top = int(out_item.shape[1]) if out_item.dim() == 2 else 1
+        cuts = np.ascontiguousarray([int(c) for c in cutoffs], np.int32)
+        n_cut = len(cuts)
+        dtab = torch.from_numpy(np.asarray([1.0 / np.log2(r + 2) for r in range(n_top)], np.float64)).to(self.dev)
+        mask = self._empty(max(Q, 1), torch.int64)
+        q_metric = self._empty((max(Q, 1), max(n_cut, 1), 5), torch.float64) if per_query else None
+        agg = self._empty((max(n_cut, 1), 8), torch.float64)
+        cover = self._empty(max(n_cut, 1), torch.int64)
+        with self.timed("topn_eval"):
+            check(lib.xmap_topn_eval(st, i64(T), vp(test_user.contiguous()), vp(test_item.contiguous()), vp(test_rating.contiguous()),
+                                     C.c_double(rel_min), i64(n_rel.numel()), i32(n_items), vp(n_rel.contiguous()), i64(Q),
+                                     vp(query_user.contiguous()), i32(n_top), vp(out_cnt.contiguous()), vp(out_item.contiguous()),
+                                     i32(n_cut), cuts.ctypes.data_as(C.c_void_p), vp(dtab), vp(mask), vp(q_metric), vp(agg), vp(cover)))
+        return mask[:Q], (q_metric[:Q] if per_query else None), agg[:n_cut], cover[:n_cut]
+
     def mae(self, status, real, plain, decay):
         """calculate_mae's sums on the device (xmap_mae): tensor [3] = (predicted pairs, sum |real - plain|, sum |real - decayed|)"""
         out = self._empty(3, torch.float64)

@@ -395,6 +395,73 @@ def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_he
     return res
 
 
+class TopnEvaluation(object):
+    """what evaluate_topn returns: .at {cutoff: dict(users, hit_rate, precision, recall, ndcg, map, mrr, coverage)}, .stats,
+    .masks {uid: hit mask}, .sim_pairs, .item_info"""
+
+    def __init__(self):
+        self.at, self.stats, self.masks = {}, (0,) * 8, {}
+
+
+def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20), rel_min=4.0, decay=False, keep_held=False,
+                  neighbors=None):
+    """Hold-out evaluation of the top-N recommendation on the device: the set-up of recommend, then the held-out pairs of
+    testRDD ((uid, [(iid, rating, ...)*]) records as recommend takes them, every (uid, iid) once) pick the users with a rating
+    >= rel_min (Engine.eval_users), those users get their n best items (Engine.topn: recommend_topn's lists), and the lists
+    are scored against the relevant pairs where they lie (Engine.topn_eval); no list is copied to the host.  A pair whose uid
+    or iid the train set does not know is ignored.  Returns a TopnEvaluation: .at[c] for every cutoff c (ascending, 1 .. n, at
+    most 8) = dict(users = evaluated users, hit_rate, precision, recall, ndcg, map, mrr = the means over them, coverage =
+    distinct items within c over their lists); .stats = (evaluated users, relevant pairs, ignored pairs, pairs below rel_min,
+    candidates scored, candidates dropped, largest `now`, largest candidate count); .masks {uid: int} for the evaluated users
+    (bit r = the item at rank r is a relevant held-out item); .sim_pairs / .item_info like recommend.  ValueError on a
+    repeated (uid, iid) or a rating that is not a number."""
+    import torch
+    if not isinstance(alterEgoRDD, AlterEgoRDD):
+        raise TypeError("evaluate_topn() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device)")
+    recs = records_of(testRDD)
+    seen = set()
+    for uid, pairs in recs:
+        for pair in pairs:
+            if (uid, pair[0]) in seen:
+                raise ValueError("held-out pair (%r, %r) occurs more than once" % (uid, pair[0]))
+            seen.add((uid, pair[0]))
+    try:
+        real = np.fromiter((float(pair[1]) for _, pairs in recs for pair in pairs), np.float64)
+    except (TypeError, ValueError):
+        real = None
+    if real is None or np.isnan(real).any():
+        raise ValueError("a held-out rating is not a number")
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "evaluate_topn")
+    idt, dev = st.idt, st.engine.dev
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    tu = np.fromiter((uidx.get(uid, -1) for uid, pairs in recs for _ in pairs), np.int32)
+    ti = np.fromiter((idt.iidx.get(pair[0], -1) for _, pairs in recs for pair in pairs), np.int32)
+    cuts = [int(c) for c in cutoffs]
+    d_tu, d_ti, d_tr = torch.from_numpy(tu).to(dev), torch.from_numpy(ti).to(dev), torch.from_numpy(real).to(dev)
+    U, I = len(idt.uids), len(idt.iids)
+    n_rel, users, counts = eng2.eval_users(d_tu, d_ti, d_tr, float(rel_min), U, I)
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        cnt, item, _, _, stats = eng2.topn(P, nb, users, item_avg, wtab, int(n), 1 if decay else 0, keep_held)
+        if stats[2] <= n_w:
+            break
+        n_w = stats[2]
+    mask, _, agg, cover = eng2.topn_eval(d_tu, d_ti, d_tr, float(rel_min), n_rel, users, cnt, item, cuts, I)
+    res = TopnEvaluation()
+    agg, cover = agg.cpu().numpy(), cover.cpu().numpy()
+    for k, c in enumerate(cuts):
+        m = float(agg[k, 0])
+        mean = (lambda x: x / m) if m else (lambda x: 0.0)
+        res.at[c] = dict(users=int(agg[k, 0]), hit_rate=mean(float(agg[k, 1])), precision=mean(float(agg[k, 3])),
+                         recall=mean(float(agg[k, 4])), ndcg=mean(float(agg[k, 5])), map=mean(float(agg[k, 6])),
+                         mrr=mean(float(agg[k, 7])), coverage=int(cover[k]))
+    res.stats = tuple(counts) + tuple(stats)
+    res.masks = {idt.uids[u]: int(b) & 0xffffffffffffffff for u, b in zip(users.cpu().tolist(), mask.cpu().tolist())}
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
 # ---------------------------------------------------------------------------------------------
 def sim_from_records(state, records):
     """Device SimResult from generic ((iid1,iid2),(sim,mutu,frac,label)) records (any order)."""
