@@ -6,12 +6,17 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
 metrics of the top-20 lists against the held-out ratings (xmap.engine.session.evaluate_topn), then the top 5 target items of
 three test users (xmap.engine.session.recommend_topn).
+
+--fold-in (with --device-tail): five test users are kept out of training altogether, as users who arrive afterwards would be.
+The model is trained without them; their ratings (the source domain's, for a user known only there) are then folded in
+(xmap.engine.session.recommend_topn_profiles / recommend_profiles: AlterEgo profiles from the resident replacement map, the
+model unchanged), and the run prints their top 5 target items and the MAE of their held-out target ratings.
 """
 import argparse
 import os
@@ -74,6 +79,7 @@ def main(argv=None):
     ap.add_argument("--workdir", default="/tmp/xmap_demo")
     ap.add_argument("--private", action="store_true")
     ap.add_argument("--device-tail", action="store_true")
+    ap.add_argument("--fold-in", action="store_true")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -99,6 +105,13 @@ def main(argv=None):
     targetRDD = timed("clean_target", assist.baseliner_clean_data_pipeline, sc, clean_t,
                       os.path.join(hdfs, para["init"]["path_movie"]), para["init"]["is_debug"], para["init"]["num_partition"])
     trainRDD, testRDD = timed("split", assist.baseliner_split_data_pipeline, sc, split, sourceRDD, targetRDD)
+    late = []                   # (uid, profile) of the users who arrive after training
+    if args.fold_in:
+        if not args.device_tail or para["recommender"]["private_flag"]:
+            ap.error("--fold-in needs --device-tail and the non-private recommender")
+        late_uids = set(uid for uid, _ in testRDD.take(5))
+        late = trainRDD.filter(lambda rec: rec[0] in late_uids).collect()
+        trainRDD = trainRDD.filter(lambda rec: rec[0] not in late_uids).cache()
     item2item_simRDD = timed("A_item_sim", assist.baseliner_calculate_sim_pipeline, sc, sim_tool, trainRDD)
     ext_tool = ExtendSim(para["extender"]["extend_among_topk"])
     extendedsimRDD = timed("B_extend", assist.extender_pipeline, sc, sqlContext, sim_tool, ext_tool, item2item_simRDD)
@@ -138,6 +151,16 @@ def main(argv=None):
                                      rc["mapping_range"], rc["decay_alpha"], 5)
         for uid, lst in top.collect():
             print("top 5 for %s:" % uid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "no evidence")
+    if late:
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        top = timed("fold_in_topn", session.recommend_topn_profiles, alterEgo_profile, late, w, k, alpha, 5)
+        print("fold-in: %d users kept out of training, %d ratings -> %d AlterEgo rows (%d pass-through), %d unknown items" % (
+            len(late), sum(len(p) for _, p in late), top.counts[0], top.counts[1], top.unknown_items))
+        for uid, lst in top.collect():
+            print("top 5 for %s (folded in):" % uid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "no evidence")
+        held = testRDD.filter(lambda rec: rec[0] in late_uids)
+        print("MAE of their held-out target ratings (no decay; decay):",
+              rpred.calculate_mae(session.recommend_profiles(alterEgo_profile, late, held, w, k, alpha)))
     print("seconds:", {k: round(v, 3) for k, v in t.items()})
     return mae
 

@@ -672,6 +672,32 @@ int xmap_alterego_count(void *stream, const xmap_ratings *R, const int32_t *map_
 int xmap_alterego_fill(void *stream, const xmap_ratings *R, const int32_t *map_src2tgt, const int64_t *off_t,
                        const int64_t *off_m, int64_t n_t_total, int32_t *out_user, int32_t *out_item,
                        double *out_rating, int64_t *out_time);
+/* The count pass reads n_users, user_ptr, user_item and flags of R; the fill pass user_rating and user_time as well. */
+
+/* ---- fold-in (csrc/stage_c_foldin.hip): AlterEgo profiles of raw profiles that were NOT rows of the ratings upload -- a user
+ * who arrived after training, a trained user whose profile changed -- with the replacement map of a finished generate pass.
+ * The model stays frozen (the standard item-based fold-in): the profiles enter neither RecommenderSim nor the neighbour lists
+ * nor the item averages; they are a second set of user-major profiles for xmap_predict_rows / xmap_topn_rows (n_users = n_new).
+ * The batch: n_new profiles as a CSR, ptr [n_new + 1], item / rating / time [nnz], items in the index space of flags and
+ * map_src2tgt ([n_items]), source and target items mixed, repeats allowed.  The AlterEgo profile of one raw profile is what
+ * xmap_alterego_fill + xmap_rec_profiles give a row of the upload (the same device code): its pass-through rows first (flag
+ * bit 1, "T:" in iid) in profile order, then one row per distinct map_src2tgt[item] >= 0 in first-seen order (rating = the
+ * fp64 mean of the group's fp32 ratings, time = that of the group's first entry); an entry that is neither gives no row, one
+ * that is both gives two.  rows <= 2 nnz.
+ * xmap_foldin_count: FIRST checks the batch on the device, reading ptr[0 .. n_new] and item[0 .. nnz) only: ptr[0] == 0, ptr
+ *   non-decreasing, ptr[n_new] == nnz, 0 <= item < n_items.  A batch that fails: XMAP_ERR_ARG, xmap_last_error() names the first
+ *   bad position, no output is written and nothing has indexed flags or map_src2tgt.  Otherwise cnt_t / cnt_m [n_new] = the
+ *   pass-through / mapped rows per profile, prof_ptr [n_new + 1] = the exclusive scan of their sums, h_counts (host) = {rows,
+ *   pass-through rows, profiles with at least one row}.  Syncs.
+ * xmap_foldin_fill: the rows, into buffers of exactly h_counts[0] entries (not read when that is 0), with the arrays
+ *   xmap_foldin_count accepted and its cnt_t and prof_ptr.  Does not sync.
+ * n_new == 0 is valid for both (nnz must then be 0).  nnz < 2^31 - 1.  Temporaries from the stream's arena. */
+int xmap_foldin_count(void *stream, int64_t n_new, int64_t nnz, const int64_t *ptr, const int32_t *item, int32_t n_items,
+                      const uint8_t *flags, const int32_t *map_src2tgt, int32_t *cnt_t /*[n_new]*/, int32_t *cnt_m /*[n_new]*/,
+                      int64_t *prof_ptr /*[n_new+1]*/, int64_t *h_counts /* host [3]: rows, pass-through rows, profiles with a row */);
+int xmap_foldin_fill(void *stream, int64_t n_new, int64_t nnz, const int64_t *ptr, const int32_t *item, const float *rating,
+                     const int64_t *time, int32_t n_items, const uint8_t *flags, const int32_t *map_src2tgt,
+                     const int32_t *cnt_t, const int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time);
 
 /* ==== coarse, handle-based entry points =============================================================
  * What a host in any language binds to replace the three pipelines: plain host buffers in, plain host buffers out,
@@ -723,6 +749,21 @@ int xmap_alterego_fill(void *stream, const xmap_ratings *R, const int32_t *map_s
  *                             xmap_eval_users, then the four h_stats of xmap_topn_rows; stats[6] > n_w: call again with a
  *                             table of that length.  n_test == 0 or no evaluated user: zeroed outputs.  Needs the same
  *                             stages as xmap_ctx_recommend and is dropped by the same calls
+ * Fold-in, for profiles that were not rows of the upload (call order: generate -> foldin; rec_sim -> rec_select or
+ * rec_set_neighbors before foldin_predict / foldin_recommend, on either side of foldin).  The batch hangs on the replacement
+ * map: upload, item_sim, extend and generate drop it; rec_sim, rec_select and rec_set_neighbors leave it.  No fold-in call
+ * changes what a resident call returns.
+ *   xmap_ctx_foldin         : n_new raw profiles (ptr [n_new + 1], item / rating / time [ptr[n_new]], item indices of the upload)
+ *                             -> their AlterEgo profiles (xmap_foldin_count / xmap_foldin_fill with the resident map and flags),
+ *                             kept on the device; the batch replaces the previous one.  The input is checked on the host first
+ *                             (ptr[0] == 0, ptr non-decreasing, 0 <= item < n_items): XMAP_ERR_ARG naming the position, no device
+ *                             work started.  A failed call leaves the context as it was, the previous batch included.  counts
+ *                             [3] (may be NULL) = {rows, pass-through rows, profiles with a row}.  n_new == 0 is valid
+ *   xmap_ctx_foldin_download : the batch's profiles (prof_ptr [n_new + 1], item / rating / time [rows]); any pointer may be NULL
+ *   xmap_ctx_foldin_recommend : xmap_ctx_recommend over the batch: query_user = indices into the batch
+ *   xmap_ctx_foldin_predict : xmap_ctx_predict over the batch: test_user = indices into the batch
+ *                             (both: an index outside [0, n_new) behaves like a user without rows; they need a batch and the
+ *                             neighbour lists)
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -789,6 +830,15 @@ int xmap_ctx_evaluate_topn(xmap_ctx *ctx, int64_t n_test, const int32_t *test_us
                            double *agg /*[n_cut][8]*/, int64_t *cover /*[n_cut]*/,
                            int32_t *user_nrel /*[U] or NULL*/, uint64_t *user_mask /*[U] or NULL: 0 for a user not evaluated*/,
                            int64_t *stats /*[8] or NULL*/);
+int xmap_ctx_foldin(xmap_ctx *ctx, int64_t n_new, const int64_t *ptr, const int32_t *item, const float *rating,
+                    const int64_t *time, int64_t *counts /*[3] or NULL*/);
+int xmap_ctx_foldin_download(xmap_ctx *ctx, int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time);
+int xmap_ctx_foldin_recommend(xmap_ctx *ctx, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
+                              int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item,
+                              double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
+int xmap_ctx_foldin_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                            const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
+                            int32_t *max_now);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,8 @@
 //                     -> xmap_ctx_rec_select | xmap_ctx_rec_set_neighbors (assist.py:179-192) -> xmap_ctx_predict (assist.py:195-207)
 //                                                                                  | xmap_ctx_recommend (top-N per query user)
 //                                                                                  | xmap_ctx_evaluate_topn (top-N against held-out pairs)
+//   fold-in, for profiles that were not rows of the upload:  xmap_ctx_generate -> xmap_ctx_foldin (the batch's AlterEgo profiles)
+//                     -> [rec_sim -> rec_select] -> xmap_ctx_foldin_predict | xmap_ctx_foldin_recommend (the same kernels, the batch's rows)
 //   xmap_ctx_*_download copy results into caller-allocated host buffers whose sizes the stage call reported.
 //
 // Everything below is orchestration of the kernels' own entry points (include/xmap_hip.h): buffer sizes, prefix sums,
@@ -68,6 +70,7 @@ struct xmap_ctx {
     int64_t *g_time = nullptr;
     int64_t n_rows = 0, n_target_rows = 0;
     int64_t *g_off_t = nullptr, *g_off_m = nullptr;     // per-user offsets of the two row segments (exclusive scans, [U+1])
+    int32_t *g_map = nullptr;                           // the replacement map (source item -> target item, -1: none) in p_gen
     // the recommender tail: profiles of the AlterEgo rows, RecommenderSim over them, neighbour lists
     Pool p_rec, p_nb;
     bool have_rec = false, have_nb = false;
@@ -81,6 +84,13 @@ struct xmap_ctx {
     int keep = 0;
     int32_t *nb_cnt = nullptr, *nb_col = nullptr;
     double *nb_sim = nullptr, *nb_ls = nullptr;
+    // fold-in: the AlterEgo profiles of the last batch (user-major, as pf_*), built with g_map: dropped with the map
+    Pool p_fold;
+    bool have_fold = false;
+    int64_t f_users = 0, f_rows = 0;
+    int64_t *f_ptr = nullptr, *f_time = nullptr;
+    int32_t *f_item = nullptr;
+    double *f_rating = nullptr;
 };
 
 namespace xmap {
@@ -115,6 +125,13 @@ static int d2h(T *host, const T *dev, size_t n, hipStream_t st) {
 static void drop_tail(xmap_ctx *c) {
     c->p_nb.release(); c->p_rec.release();
     c->have_rec = c->have_nb = false;
+}
+
+// the fold-in batch hangs on the replacement map: upload, item_sim, extend and generate drop it; the tail calls leave it
+static void drop_fold(xmap_ctx *c) {
+    c->p_fold.release();
+    c->have_fold = false;
+    c->f_users = c->f_rows = 0;
 }
 
 // one reverse adjacency: count -> scan -> fill
@@ -332,6 +349,7 @@ void xmap_ctx_destroy(xmap_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->st);
     drop_tail(c);
+    drop_fold(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_rows.release(); c->p_ratings.release();
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
@@ -366,6 +384,7 @@ int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const
     XM_ARG(c && user_ptr && prefix_cls && suffix_cls && contains_mask && flags && n_users >= 0 && n_items >= 0);
     XM_HIP(hipSetDevice(c->device));
     drop_tail(c);
+    drop_fold(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_ratings.release();
     c->have_sim = c->have_ext = c->have_gen = false;
     const int64_t nnz = user_ptr[n_users];
@@ -405,6 +424,7 @@ int xmap_ctx_item_sim(xmap_ctx *c, int method, int cap, int64_t *n_kept, int64_t
     XM_ARG(c && c->have_ratings && (method == XMAP_COSINE || method == XMAP_ADJUST_COSINE) && cap > 0);
     XM_HIP(hipSetDevice(c->device));
     drop_tail(c);
+    drop_fold(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release();
     c->have_sim = c->have_ext = c->have_gen = false;
     xmap_ratings &R = c->R;
@@ -450,6 +470,7 @@ int xmap_ctx_extend(xmap_ctx *c, int top_k, int64_t *n_out, int64_t *n_paths) {
     XM_ARG(c && c->have_sim && top_k >= 1);
     XM_HIP(hipSetDevice(c->device));
     drop_tail(c);
+    drop_fold(c);
     c->p_gen.release(); c->p_ext.release();
     c->have_ext = c->have_gen = false;
     const int I = c->R.n_items, k = top_k;
@@ -609,6 +630,7 @@ int xmap_ctx_generate(xmap_ctx *c, int private_flag, const int32_t *picks, int32
     XM_ARG(c && c->have_ext);
     XM_HIP(hipSetDevice(c->device));
     drop_tail(c);
+    drop_fold(c);
     c->p_gen.release();
     c->have_gen = false;
     const int I = c->R.n_items;
@@ -630,6 +652,7 @@ int xmap_ctx_generate(xmap_ctx *c, int private_flag, const int32_t *picks, int32
     XM_HIP(hipStreamSynchronize(c->st));
     c->n_rows = n; c->n_target_rows = nt;
     c->g_off_t = off_t; c->g_off_m = off_m;
+    c->g_map = d_map;
     c->have_gen = true;
     if (n_rows) *n_rows = n;
     if (n_target_rows) *n_target_rows = nt;
@@ -789,10 +812,19 @@ int xmap_ctx_rec_neighbors_download(xmap_ctx *c, int32_t *cnt, int32_t *col, dou
     return XMAP_OK;
 }
 
-int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
-                     const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
-                     int32_t *max_now) {
-    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+// user-major profiles the prediction and ranking kernels read: the resident AlterEgo rows, or a fold-in batch
+struct Profiles {
+    int64_t n_users;
+    const int64_t *ptr, *time;
+    const int32_t *item;
+    const double *rating;
+};
+static Profiles resident_profiles(const xmap_ctx *c) { return Profiles{c->R.n_users, c->pf_ptr, c->pf_time, c->pf_item, c->pf_rating}; }
+static Profiles foldin_profiles(const xmap_ctx *c) { return Profiles{c->f_users, c->f_ptr, c->f_time, c->f_item, c->f_rating}; }
+
+static int predict_over(xmap_ctx *c, const Profiles &P, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
+                        const double *test_rating, const double *wtab, int32_t n_w, double *out_plain, double *out_decay,
+                        int32_t *status, double *mae, int32_t *max_now) {
     XM_ARG(n_test >= 0 && wtab && n_w >= 1 && (n_test == 0 || (test_user && test_item && out_plain && out_decay && status)));
     XM_ARG(!mae || test_rating || n_test == 0);
     XM_HIP(hipSetDevice(c->device));
@@ -809,8 +841,8 @@ int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, cons
     if (test_rating) XM_TRY(h2d(tmp, &d_real, test_rating, n, c->st));
     XM_TRY(dalloc(tmp, &d_plain, n, c->st, true)); XM_TRY(dalloc(tmp, &d_decay, n, c->st, true));
     XM_TRY(dalloc(tmp, &d_status, n, c->st, true)); XM_TRY(dalloc(tmp, &d_mae, 3, c->st, true));
-    XM_TRY(xmap_predict_rows(c->st, n_test, d_user, d_item, c->R.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim, c->pf_ptr,
-                             c->pf_item, c->pf_rating, c->pf_time, c->rs_avg, d_w, n_w, d_plain, d_decay, d_status, max_now));
+    XM_TRY(xmap_predict_rows(c->st, n_test, d_user, d_item, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim, P.ptr,
+                             P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_plain, d_decay, d_status, max_now));
     if (mae) {
         XM_TRY(xmap_mae(c->st, n_test, d_status, d_real, d_plain, d_decay, d_mae));
         XM_TRY(d2h(mae, (const double *)d_mae, 3, c->st));
@@ -822,10 +854,9 @@ int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, cons
     return XMAP_OK;
 }
 
-int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
-                       const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
-                       int64_t *stats) {
-    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+static int recommend_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
+                          int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                          double *out_decay, int64_t *stats) {
     XM_ARG(n_top >= 1 && n_top <= 64);
     XM_ARG(rank_by == 0 || rank_by == 1);
     XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
@@ -842,14 +873,103 @@ int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, 
     XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
     XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
-    XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, c->R.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim,
-                          c->pf_ptr, c->pf_item, c->pf_rating, c->pf_time, c->rs_avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
+    XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim,
+                          P.ptr, P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
     XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
     return XMAP_OK;
+}
+
+int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                     const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
+                     int32_t *max_now) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    return predict_over(c, resident_profiles(c), n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
+                        max_now);
+}
+
+int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                       const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
+                       int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    return recommend_over(c, resident_profiles(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
+                          out_decay, stats);
+}
+
+// ---- fold-in ------------------------------------------------------------------------------------------------------------
+
+int xmap_ctx_foldin(xmap_ctx *c, int64_t n_new, const int64_t *ptr, const int32_t *item, const float *rating, const int64_t *time,
+                    int64_t *counts) {
+    XM_ARG(c && c->have_gen && n_new >= 0 && ptr);
+    // the batch is checked here, on the host: bad input starts no device work (xmap_foldin_count's own check then passes)
+    if (ptr[0] != 0) { set_error("fold-in batch: ptr[0] = %lld, not 0", (long long)ptr[0]); return XMAP_ERR_ARG; }
+    for (int64_t u = 0; u < n_new; u++)
+        if (ptr[u + 1] < ptr[u]) { set_error("fold-in batch: ptr[%lld] < ptr[%lld]", (long long)u + 1, (long long)u); return XMAP_ERR_ARG; }
+    const int64_t nnz = ptr[n_new];
+    XM_ARG(nnz < 2147483647ll && (nnz == 0 || (item && rating && time)));
+    const int I = c->R.n_items;
+    for (int64_t e = 0; e < nnz; e++)
+        if (item[e] < 0 || item[e] >= I) {
+            set_error("fold-in batch: item[%lld] = %d outside [0, %d)", (long long)e, (int)item[e], I);
+            return XMAP_ERR_ARG;
+        }
+    XM_HIP(hipSetDevice(c->device));
+    // built beside the previous batch, which is replaced only when everything has succeeded
+    ScratchPool tmp, fresh;
+    int64_t *d_ptr, *d_time, *f_ptr, *f_time, h[3] = {0, 0, 0};
+    int32_t *d_item, *cnt_t, *cnt_m, *f_item;
+    float *d_rating;
+    double *f_rating;
+    XM_TRY(h2d(tmp, &d_ptr, ptr, (size_t)n_new + 1, c->st));
+    XM_TRY(h2d(tmp, &d_item, item, (size_t)nnz, c->st));
+    XM_TRY(h2d(tmp, &d_rating, rating, (size_t)nnz, c->st));
+    XM_TRY(h2d(tmp, &d_time, time, (size_t)nnz, c->st));
+    XM_TRY(dalloc(tmp, &cnt_t, (size_t)n_new, c->st)); XM_TRY(dalloc(tmp, &cnt_m, (size_t)n_new, c->st));
+    XM_TRY(dalloc(fresh, &f_ptr, (size_t)n_new + 1, c->st));
+    XM_TRY(xmap_foldin_count(c->st, n_new, nnz, d_ptr, d_item, I, c->R.flags, c->g_map, cnt_t, cnt_m, f_ptr, h));
+    XM_TRY(dalloc(fresh, &f_item, (size_t)h[0], c->st)); XM_TRY(dalloc(fresh, &f_rating, (size_t)h[0], c->st));
+    XM_TRY(dalloc(fresh, &f_time, (size_t)h[0], c->st));
+    XM_TRY(xmap_foldin_fill(c->st, n_new, nnz, d_ptr, d_item, d_rating, d_time, I, c->R.flags, c->g_map, cnt_t, f_ptr, f_item, f_rating,
+                            f_time));
+    XM_HIP(hipStreamSynchronize(c->st));
+    drop_fold(c);
+    c->p_fold.ptrs.swap(fresh.ptrs);
+    c->f_users = n_new; c->f_rows = h[0];
+    c->f_ptr = f_ptr; c->f_item = f_item; c->f_rating = f_rating; c->f_time = f_time;
+    c->have_fold = true;
+    if (counts) { counts[0] = h[0]; counts[1] = h[1]; counts[2] = h[2]; }
+    return XMAP_OK;
+}
+
+int xmap_ctx_foldin_download(xmap_ctx *c, int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time) {
+    XM_ARG(c && c->have_fold);
+    XM_HIP(hipSetDevice(c->device));
+    const size_t n = (size_t)c->f_rows;
+    if (prof_ptr) XM_TRY(d2h(prof_ptr, (const int64_t *)c->f_ptr, (size_t)c->f_users + 1, c->st));
+    if (prof_item) XM_TRY(d2h(prof_item, (const int32_t *)c->f_item, n, c->st));
+    if (prof_rating) XM_TRY(d2h(prof_rating, (const double *)c->f_rating, n, c->st));
+    if (prof_time) XM_TRY(d2h(prof_time, (const int64_t *)c->f_time, n, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+int xmap_ctx_foldin_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                              const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                              double *out_decay, int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
+    return recommend_over(c, foldin_profiles(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
+                          out_decay, stats);
+}
+
+int xmap_ctx_foldin_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                            const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
+                            int32_t *max_now) {
+    XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
+    return predict_over(c, foldin_profiles(c), n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
+                        max_now);
 }
 
 int xmap_ctx_evaluate_topn(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,

@@ -46,7 +46,7 @@ __device__ __forceinline__ void alterego_group16(bool on, long long u, long long
     bool is_t = false;
     if (act) {
         it = item[a + gl];
-        r = rating[a + gl];
+        if (FILL) r = rating[a + gl];         // (the count pass reads no rating: its caller may have none, stage_c_foldin.hip)
         is_t = (flags[it] & 2) != 0;          // "T:" in iid: pass-through row
         m = map[it];
     }
@@ -100,7 +100,7 @@ __device__ __forceinline__ void alterego_wave(long long u, long long a, int d, i
         bool is_t = false;
         if (act) {
             it = item[a + e];
-            r = rating[a + e];
+            if (FILL) r = rating[a + e];
             is_t = (flags[it] & 2) != 0;
             m = map[it];
         }
@@ -112,7 +112,7 @@ __device__ __forceinline__ void alterego_wave(long long u, long long a, int d, i
             float orr = r;
             if (ob != cb) {
                 om = -1; orr = 0.f;
-                if (ob + lane < d) { om = map[item[a + ob + lane]]; orr = rating[a + ob + lane]; }
+                if (ob + lane < d) { om = map[item[a + ob + lane]]; if (FILL) orr = rating[a + ob + lane]; }
             }
             const int lim = min(64, d - ob);
             for (int t = 0; t < lim; t++) {

@@ -1434,6 +1434,7 @@ class Engine(object):
         G.cnt_t, G.cnt_m = cnt_t, cnt_m
         G.off_t, G.off_m = off_t, off_m      # (the device-resident tail groups the rows by user from these: alterego_profiles)
         G.n_profiles = n_prof
+        G.map = mp                           # (fold-in builds the profiles of later arrivals with it: foldin_profiles)
         G.user, G.item, G.rating, G.time = G.user[:n], G.item[:n], G.rating[:n], G.time[:n]
         return G
 
@@ -1454,6 +1455,13 @@ class Engine(object):
         with self.timed("rec_profiles"):
             check(lib.xmap_rec_profiles(st, i64(U), i64(n), i64(G.n_target_rows), vp(G.off_t), vp(G.off_m), vp(G.user), vp(G.item),
                                         vp(G.rating), vp(tm), vp(ptr), vp(item), vp(rating), vp(time)))
+        return self._profile_view(U, n, ptr, item, rating, time)
+
+    def _profile_view(self, U, n, ptr, item, rating, time):
+        """user-major AlterEgo profiles (ptr [U + 1], item / rating fp64 / time of max(n, 1) entries) as a
+        DeviceRatings-compatible view over the item space of the engine's ratings"""
+        R = self.R
+        n1 = max(n, 1)
         P = object.__new__(DeviceRatings)
         P.device, P.n_users, P.n_items, P.nnz = R.device, U, R.n_items, n
         P.plain_exact = False
@@ -1469,6 +1477,43 @@ class Engine(object):
         P.c = abi.Ratings(U, R.n_items, n, ptr.data_ptr(), item.data_ptr(), P.user_rating.data_ptr(), time.data_ptr(),
                           P.item_ptr.data_ptr(), P.item_user.data_ptr(), P.item_rating.data_ptr(), R.prefix_cls.data_ptr(),
                           R.suffix_cls.data_ptr(), R.contains_mask.data_ptr(), R.flags.data_ptr())
+        return P
+
+    def foldin_profiles(self, ptr, item, rating, time, mp):
+        """Fold-in (xmap_foldin_count / xmap_foldin_fill): the AlterEgo profiles of a batch of raw profiles that are not rows
+        of the engine's ratings, with the replacement map mp of select() / alterego().map.  ptr [B + 1] int64, item int32 (the
+        engine's index space, source and target items mixed, repeats allowed), rating float32, time int64 -- NumPy arrays or
+        tensors.  The batch is checked on the device before anything indexes the map (an item outside [0, n_items), a ptr that
+        is not a CSR's: XmapError, code ERR_ARG).  Returns the DeviceRatings-compatible view alterego_profiles returns, with
+        n_users = B -- predict() and topn() take it as is, user indices then count within the batch -- and .counts = (rows,
+        pass-through rows, profiles with a row).  The model stays frozen: nothing resident changes."""
+        R = self.R
+        st = _stream(self.dev)
+
+        def dev(a, dt):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a, dt))
+            return a.to(device=self.dev, dtype=getattr(torch, np.dtype(dt).name)).contiguous()
+        ptr, item, rating, time = dev(ptr, np.int64), dev(item, np.int32), dev(rating, np.float32), dev(time, np.int64)
+        B, nnz = int(ptr.numel()) - 1, int(item.numel())
+        if B < 0 or rating.numel() != nnz or time.numel() != nnz:
+            raise ValueError("fold-in batch: ptr needs an entry, item / rating / time one length")
+        cnt_t = self._empty(max(B, 1), torch.int32)
+        cnt_m = self._empty(max(B, 1), torch.int32)
+        pptr = self._empty(B + 1, torch.int64)
+        h = (C.c_int64 * 3)(0, 0, 0)
+        with self.timed("foldin_count"):
+            check(lib.xmap_foldin_count(st, i64(B), i64(nnz), vp(ptr), vp(item), i32(R.n_items), vp(R.flags), vp(mp), vp(cnt_t),
+                                        vp(cnt_m), vp(pptr), h))
+        n = int(h[0])
+        pit = self._empty(max(n, 1), torch.int32)
+        pra = self._empty(max(n, 1), torch.float64)
+        pti = self._empty(max(n, 1), torch.int64)
+        with self.timed("foldin_fill"):
+            check(lib.xmap_foldin_fill(st, i64(B), i64(nnz), vp(ptr), vp(item), vp(rating), vp(time), i32(R.n_items), vp(R.flags),
+                                       vp(mp), vp(cnt_t), vp(pptr), vp(pit), vp(pra), vp(pti)))
+        P = self._profile_view(B, n, pptr, pit, pra, pti)
+        P.counts = tuple(int(x) for x in h)
         return P
 
     def predict(self, P, neighbors, test_user, test_item, item_avg, wtab):

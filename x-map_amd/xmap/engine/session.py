@@ -323,11 +323,20 @@ def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
     order, usable with calculate_mae; it carries .mae (count, sum |real - plain|, sum |real - decayed| from the device, or
     None when a real rating is not a number), .item_info {iid: (avg, norm, n)} and .sim_pairs {iid: [(nid, sim)*]}: the
     dictionaries the Python statement takes.  A user id matches by equality."""
-    import torch
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend")
+    idt = st.idt
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    res = _predict_records(st, eng2, P, nb, item_avg, uidx, testRDD, alpha)
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
+def _predict_records(st, eng2, P, nb, item_avg, uidx, testRDD, alpha):
+    """what recommend and recommend_profiles share: the held-out pairs of testRDD against the profiles P (uidx: uid -> user index
+    of P) -> the LocalRDD of (uid, [(iid, real, plain, decayed) | ()]) with .mae"""
+    import torch
     idt, dev = st.idt, st.engine.dev
     recs = records_of(testRDD)
-    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
     tu = np.fromiter((uidx.get(uid, -1) for uid, pairs in recs for _ in pairs), np.int32)
     ti = np.fromiter((idt.iidx.get(pair[0], -1) for _, pairs in recs for pair in pairs), np.int32)
     try:
@@ -361,7 +370,6 @@ def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
         out.append((uid, line))
     res = LocalRDD(out, getattr(testRDD, "ctx", None))
     res.mae = mae
-    _tail_dicts(res, st, S, nb)
     return res
 
 
@@ -373,12 +381,22 @@ def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_he
     of (uid, [(iid, plain, decayed)*]) in the order of `users`; a uid the train set does not know gives (uid, []).  It carries
     .sim_pairs and .item_info like recommend, and .stats = (candidates scored, candidates dropped, largest `now`, largest
     candidate count of a user)."""
-    import torch
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn")
-    idt, dev = st.idt, st.engine.dev
+    idt = st.idt
     uids = list(users.collect()) if hasattr(users, "collect") else list(users)
     uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
-    d_q = torch.from_numpy(np.fromiter((uidx.get(uid, -1) for uid in uids), np.int32, len(uids))).to(dev)
+    res = _topn_records(st, eng2, P, nb, item_avg, [uidx.get(uid, -1) for uid in uids], uids, alpha, n, decay, keep_held,
+                        getattr(users, "ctx", None))
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
+def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, ctx):
+    """what recommend_topn and recommend_topn_profiles share: the lists of the user indices `query` of P, labelled `uids` -> the
+    LocalRDD of (uid, [(iid, plain, decayed)*]) with .stats"""
+    import torch
+    idt, dev = st.idt, st.engine.dev
+    d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
     n_w = 66
     while True:
         wtab = _decay_table(alpha, n_w, dev)
@@ -389,8 +407,69 @@ def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_he
     cnt, item, plain, decayed = cnt.cpu().numpy(), item.cpu().numpy(), plain.cpu().numpy(), decayed.cpu().numpy()
     iids = idt.iids
     out = [(uid, [(iids[item[q, t]], float(plain[q, t]), float(decayed[q, t])) for t in range(cnt[q])]) for q, uid in enumerate(uids)]
-    res = LocalRDD(out, getattr(users, "ctx", None))
+    res = LocalRDD(out, ctx)
     res.stats = stats
+    return res
+
+
+def _fold_in(st, G, profiles):
+    """raw profiles [(uid, [(iid, rating, time)*])*] (an RDD or a list) -> (their AlterEgo profiles on the device:
+    Engine.foldin_profiles with the map of G, {uid: index in the batch}, entries dropped for an iid the id table does not know).
+    The uids are labels (never looked up in the train set); the device gets the dense rank of the times over the batch."""
+    idt = st.idt
+    if getattr(G, "map", None) is None:
+        raise ValueError("fold-in needs the replacement map of the generate pass (Engine.alterego keeps it on its result)")
+    recs = records_of(profiles)
+    index = {}
+    for k, rec in enumerate(recs):
+        if rec[0] in index:
+            raise ValueError("fold-in profile of user %r occurs more than once" % (rec[0],))
+        index[rec[0]] = k
+    ptr = np.zeros(len(recs) + 1, np.int64)
+    item, rating, times, unknown = [], [], [], 0
+    for k, (_, prof) in enumerate(recs):
+        for iid, r, t in prof:
+            i = idt.iidx.get(iid)
+            if i is None:
+                unknown += 1
+                continue
+            item.append(i); rating.append(r); times.append(t)
+        ptr[k + 1] = len(item)
+    item = np.asarray(item, np.int32)
+    rating = np.asarray(rating, np.float64)
+    check_float32(ptr, item, rating, [rec[0] for rec in recs], idt.iids)
+    order = {t: k for k, t in enumerate(sorted(set(times)))}
+    rank = np.fromiter((order[t] for t in times), np.int64, len(times))
+    return st.engine.foldin_profiles(ptr, item, rating.astype(np.float32), rank, G.map), index, unknown
+
+
+def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None):
+    """recommend_topn for users that are not rows of the train set -- a user who arrived after training, a trained user whose
+    profile changed: `profiles` is an RDD or list of (uid, [(iid, rating, time)*]) raw profiles, source and target items mixed.
+    Each gets its AlterEgo profile with the replacement map behind alterEgoRDD (fold-in: Engine.foldin_profiles) and then the
+    lists of recommend_topn from the model trained on alterEgoRDD's rows, which stays as it is.  The uids are labels only, a
+    repeated one raises ValueError; an entry whose iid the train set does not know is dropped and counted in .unknown_items; a
+    rating float32 does not hold raises as the train set's does; times are any mutually comparable objects.  Returns the LocalRDD of
+    recommend_topn in the order of `profiles`, with .stats, .sim_pairs, .item_info, .unknown_items and .counts = (AlterEgo rows,
+    pass-through rows, profiles with a row)."""
+    st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    uids = sorted(index, key=index.get)
+    res = _topn_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, n, decay, keep_held, getattr(profiles, "ctx", None))
+    res.unknown_items, res.counts = unknown, F.counts
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
+def recommend_profiles(alterEgoRDD, profiles, testRDD, cap, keep, alpha, neighbors=None):
+    """recommend for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them, testRDD the
+    held-out (uid, [(iid, rating, ...)*]) records of those users -- a uid is looked up among the profiles' labels, one without a
+    profile is a user without ratings.  Returns the LocalRDD of recommend (with .mae, .sim_pairs, .item_info) and .unknown_items,
+    .counts."""
+    st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    res = _predict_records(st, eng2, F, nb, item_avg, index, testRDD, alpha)
+    res.unknown_items, res.counts = unknown, F.counts
     _tail_dicts(res, st, S, nb)
     return res
 
