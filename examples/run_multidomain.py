@@ -5,7 +5,12 @@ The reference's own multi-domain driver cannot run as shipped (SURVEY.md 2.1 row
 the drop-in API.  On a multi-GPU node the per-domain problems are independent and can be placed on different GPUs
 (domain-parallel replicas).
 
-    python examples/run_multidomain.py [--users 2000] [--items 400] [--sources 2] [--workdir /tmp/xmap_multi]
+    python examples/run_multidomain.py [--users 2000] [--items 400] [--sources 2] [--workdir /tmp/xmap_multi] [--device-tail]
+
+--device-tail: after the host route's MAE line the same recommender stages run over the UNION of the AlterEgo rows where they
+lie, in HBM (xmap.engine.session.union_alterego -> session.recommend with the host route's neighbour lists), and print their MAE
+line -- the same string --, then the ranking metrics of the top-20 lists against the held-out ratings (session.evaluate_topn)
+and the top 5 target items of three test users (session.recommend_topn), as run_twodomain.py --device-tail does for one source.
 """
 import argparse
 import os
@@ -61,6 +66,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=41)
     ap.add_argument("--topk", type=int, default=10)
     ap.add_argument("--workdir", default="/tmp/xmap_multi")
+    ap.add_argument("--device-tail", action="store_true")
     args = ap.parse_args(argv)
     src_paths, tgt_path = write_inputs(args.workdir, args.users, args.items, args.sources, args.seed)
     sc = SparkContext(conf=SparkConf().setAppName("xmap multi-domain on MI355X"))
@@ -82,7 +88,7 @@ def main(argv=None):
             testRDD = testRDD or te
     sim_tool = BaselinerSim("adjust_cosine", 50)
     gen_tool = Generator(1, 0.6, "adjust_cosine", 0.1)
-    alterEgo = None
+    alterEgo, profiles = None, []
     for d, trainRDD in enumerate(trains):       # independent two-domain problems
         trainRDD = trainRDD.filter(lambda rec: len(rec[1]) > 0).cache()
         sim = assist.baseliner_calculate_sim_pipeline(sc, sim_tool, trainRDD)
@@ -91,12 +97,31 @@ def main(argv=None):
         n_starts = int((ext.E.n_cand > 0).sum().item())     # the lazy handle's candidate counts (ext.count() would build the lists)
         print("source %d: %d sim pairs, %d start items, %d AlterEgo rows" % (d + 1, sim.count(), n_starts, profile.count()))
         alterEgo = profile if alterEgo is None else alterEgo.union(profile)
+        profiles.append(profile)
     rsim = RecommenderSim("cosine_item", 50)
     _, _, ubd, ibd, uinfo, iinfo, alterEgo_sim = assist.recommender_calculate_sim_pipeline(sc, rsim, alterEgo.distinct())
     kept = assist.recommender_privacy_pipeline(RecommenderPrivacy(10, 0.6, 0.1), alterEgo_sim, False)
     mae = assist.recommender_prediction_pipeline(RecommenderPrediction(0.03, "cosine_item"), rsim, testRDD,
                                                  sc.broadcast(kept.collectAsMap()), ubd, ibd, uinfo, iinfo)
     print("MAE (no decay; decay):", mae, " [%.1f s]" % (time.time() - t0))
+    if args.device_tail:
+        from xmap.engine import session
+        t1 = time.time()
+        union = session.union_alterego(profiles, distinct=True)
+        lists = kept.collectAsMap()                 # the host route's neighbour lists: ties in the selection are its own
+        predicted = session.recommend(union, testRDD, 50, 10, 0.03, neighbors=lists)
+        mae_dev = RecommenderPrediction(0.03, "cosine_item").calculate_mae(predicted)
+        print("MAE (no decay; decay):", mae_dev, " [device tail over the union, %.1f s]" % (time.time() - t1))
+        print("union: %d rows, %d duplicates removed, %d dropped, %d users with a row; the two MAE lines %s" % (
+            union.counts + ("agree" if mae_dev == mae else "DIFFER",)))
+        ev = session.evaluate_topn(union, testRDD, 50, 10, 0.03, 20, cutoffs=(5, 10, 20), rel_min=4.0)
+        for c in sorted(ev.at):
+            m = ev.at[c]
+            print("top-%d over %d users: hit rate %.4f, precision %.4f, recall %.4f, NDCG %.4f, MAP %.4f, MRR %.4f, %d items covered" % (
+                c, m["users"], m["hit_rate"], m["precision"], m["recall"], m["ndcg"], m["map"], m["mrr"], m["coverage"]))
+        top = session.recommend_topn(union, [uid for uid, _ in testRDD.take(3)], 50, 10, 0.03, 5)
+        for uid, lst in top.collect():
+            print("top 5 for %s:" % uid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "no evidence")
     return mae
 
 

@@ -699,6 +699,51 @@ int xmap_foldin_fill(void *stream, int64_t n_new, int64_t nnz, const int64_t *pt
                      const int64_t *time, int32_t n_items, const uint8_t *flags, const int32_t *map_src2tgt,
                      const int32_t *cnt_t, const int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time);
 
+/* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
+ * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
+ * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
+ * xmap_topn_eval and xmap_mae take it as they take one domain's profiles.
+ * A part = one domain's stage-C output as xmap_alterego_fill leaves it (rows [0, n_target_rows) pass-through, then the mapped
+ * rows, both in user order; off_t / off_m [n_users + 1] the exclusive scans the fill pass took; `time` may point at any int64
+ * column of n_rows entries to carry instead, e.g. ranks that compare across the parts; `user` is not read) + two maps:
+ * user_map [n_users] -> union user, injective within the part; item_map [n_items] -> union item, or -1: rows of that item are
+ * dropped.  `parts` is a HOST array of 1 <= n_parts <= 16 descriptors holding device pointers.  n_rows < 2^31 - 1 in all.
+ * The rows of union user g, in this order: parts in the order given; within a part the rows of the local user u with
+ * user_map[u] = g, its pass-through rows first, then its mapped rows, each in stage-C order (what xmap_rec_profiles gives).
+ * flags = XMAP_UNION_DISTINCT: a row is removed if an earlier kept row of the same union user has the same union item, the same
+ * time and a rating equal as a number (-0.0 == 0.0; the first occurrence stays, bits included; ratings are finite) --
+ * LocalRDD.distinct() over (uid, iid, rating, time) in first-occurrence order.  flags = 0: nothing is removed (plain union).
+ * xmap_union_count: FIRST checks every part on the device -- user_map within [0, n_users) and injective, item_map within
+ *   [-1, n_items), off_t / off_m starting at 0, non-decreasing and ending at n_target_rows / n_rows - n_target_rows, row items
+ *   within [0, the part's n_items) -- and returns XMAP_ERR_ARG (xmap_last_error() names the first bad position) with no output
+ *   written and nothing indexed by an unchecked value.  Otherwise prof_ptr [n_users + 1] and h_counts (host) = {rows out, rows
+ *   removed as duplicates, rows dropped by item_map == -1, union users with a row}.  Syncs.
+ * xmap_union_fill: the rows, into buffers of n_out = h_counts[0] entries (not read when that is 0), with the parts
+ *   xmap_union_count accepted and its prof_ptr.  Does not sync.
+ * The result is a pure function of the inputs: positions come from counts and scans.  Users of up to 32 rows take a 32-lane
+ * group each, up to 2048 rows a block with an LDS hash set, beyond that a block with a hash set in global memory.
+ * Temporaries from the stream's arena. */
+#define XMAP_UNION_DISTINCT 1
+typedef struct xmap_union_part {
+    int64_t n_users;            /* users of the part's index space (rows of off_t / off_m, entries of user_map) */
+    int32_t n_items;            /* items of the part's index space (entries of item_map) */
+    int64_t n_rows, n_target_rows;
+    const int32_t *user;        /* [n_rows] not read */
+    const int32_t *item;        /* [n_rows] */
+    const double *rating;       /* [n_rows] */
+    const int64_t *time;        /* [n_rows] */
+    const int64_t *off_t;       /* [n_users + 1] */
+    const int64_t *off_m;       /* [n_users + 1] */
+    const int32_t *user_map;    /* [n_users] */
+    const int32_t *item_map;    /* [n_items] */
+} xmap_union_part;
+int xmap_union_count(void *stream, int32_t n_parts, const xmap_union_part *parts /* host */, int64_t n_users, int32_t n_items,
+                     int32_t flags, int64_t *prof_ptr /*[n_users+1]*/,
+                     int64_t *h_counts /* host [4]: rows, duplicates removed, rows dropped, users with a row */);
+int xmap_union_fill(void *stream, int32_t n_parts, const xmap_union_part *parts /* host */, int64_t n_users, int32_t n_items,
+                    int32_t flags, const int64_t *prof_ptr, int64_t n_out, int32_t *prof_item, double *prof_rating,
+                    int64_t *prof_time);
+
 /* ==== coarse, handle-based entry points =============================================================
  * What a host in any language binds to replace the three pipelines: plain host buffers in, plain host buffers out,
  * sizes reported by the stage call; the library owns every device buffer, prefix sum, overflow retry and work-unit
@@ -764,6 +809,18 @@ int xmap_foldin_fill(void *stream, int64_t n_new, int64_t nnz, const int64_t *pt
  *   xmap_ctx_foldin_predict : xmap_ctx_predict over the batch: test_user = indices into the batch
  *                             (both: an index outside [0, n_new) behaves like a user without rows; they need a batch and the
  *                             neighbour lists)
+ * Multi-domain: the union of the AlterEgo rows of n_parts contexts (one two-domain problem each, after xmap_ctx_generate).
+ *   xmap_ctx_union          : dst becomes a TAIL-ONLY context over the union (xmap_union_count / xmap_union_fill): n_users union
+ *                             users, n_items union items, the profiles of the union in place of stage-C rows.  src [n_parts]
+ *                             (1 .. 16): contexts with generated rows on dst's device, read only and unchanged; user_map[d]
+ *                             [users of src[d]] / item_map[d] [items of src[d]] (host arrays) as xmap_union_part takes them --
+ *                             checked on the device, XMAP_ERR_ARG leaves dst as it was; times are the contexts' own int64 times;
+ *                             flags 0 or XMAP_UNION_DISTINCT; counts [4] (may be NULL) as h_counts.  dst holds copies and no
+ *                             pointer into a source: destroying a source afterwards is legal.  On dst xmap_ctx_rec_sim,
+ *                             _rec_profiles_download, _rec_download, _rec_select, _rec_set_neighbors, _rec_neighbors_download,
+ *                             _predict, _recommend and _evaluate_topn work as on a two-domain context; the stage entries,
+ *                             xmap_ctx_gen_download and the fold-in entries return XMAP_ERR_ARG.  A later xmap_ctx_union into
+ *                             dst or xmap_ctx_upload_ratings drops the union and its tail.  dst may not be one of src
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -839,6 +896,8 @@ int xmap_ctx_foldin_recommend(xmap_ctx *ctx, int64_t n_query, const int32_t *que
 int xmap_ctx_foldin_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
                             const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
                             int32_t *max_now);
+int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
+                   int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 
 #ifdef __cplusplus
 }

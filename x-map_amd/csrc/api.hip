@@ -91,6 +91,13 @@ struct xmap_ctx {
     int64_t *f_ptr = nullptr, *f_time = nullptr;
     int32_t *f_item = nullptr;
     double *f_rating = nullptr;
+    // multi-domain: this context holds the union of other contexts' AlterEgo rows as user-major profiles (xmap_ctx_union) and
+    // nothing of the stages; have_gen is set, n_rows = the union's rows, R carries the union's sizes and all-target flags
+    Pool p_union;
+    bool is_union = false;
+    int64_t *un_ptr = nullptr, *un_time = nullptr;
+    int32_t *un_item = nullptr;
+    double *un_rating = nullptr;
 };
 
 namespace xmap {
@@ -128,6 +135,13 @@ static void drop_tail(xmap_ctx *c) {
 }
 
 // the fold-in batch hangs on the replacement map: upload, item_sim, extend and generate drop it; the tail calls leave it
+// the union of other contexts' rows goes with whatever replaces it: an upload, or the next union
+static void drop_union(xmap_ctx *c) {
+    c->p_union.release();
+    if (c->is_union) c->have_gen = false;
+    c->is_union = false;
+}
+
 static void drop_fold(xmap_ctx *c) {
     c->p_fold.release();
     c->have_fold = false;
@@ -350,6 +364,7 @@ void xmap_ctx_destroy(xmap_ctx *c) {
     (void)hipStreamSynchronize(c->st);
     drop_tail(c);
     drop_fold(c);
+    drop_union(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_rows.release(); c->p_ratings.release();
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
@@ -385,6 +400,7 @@ int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const
     XM_HIP(hipSetDevice(c->device));
     drop_tail(c);
     drop_fold(c);
+    drop_union(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_ratings.release();
     c->have_sim = c->have_ext = c->have_gen = false;
     const int64_t nnz = user_ptr[n_users];
@@ -660,7 +676,7 @@ int xmap_ctx_generate(xmap_ctx *c, int private_flag, const int32_t *picks, int32
 }
 
 int xmap_ctx_gen_download(xmap_ctx *c, int32_t *user, int32_t *item, double *rating, int64_t *time) {
-    XM_ARG(c && c->have_gen);
+    XM_ARG(c && c->have_gen && !c->is_union);
     XM_HIP(hipSetDevice(c->device));
     const size_t n = (size_t)c->n_rows;
     if (user) XM_TRY(d2h(user, (const int32_t *)c->g_user, n, c->st));
@@ -684,8 +700,17 @@ int xmap_ctx_rec_sim(xmap_ctx *c, int cap, int64_t *n_pairs) {
     // (a) user-major profiles in stage-C row order
     XM_ALLOCZ(c->p_rec, c->pf_ptr, U + 1);
     XM_ALLOC(c->p_rec, c->pf_item, n1); XM_ALLOC(c->p_rec, c->pf_rating, n1); XM_ALLOC(c->p_rec, c->pf_time, n1);
-    XM_TRY(xmap_rec_profiles(c->st, U, nnz, c->n_target_rows, c->g_off_t, c->g_off_m, c->g_user, c->g_item, c->g_rating, c->g_time,
-                             c->pf_ptr, c->pf_item, c->pf_rating, c->pf_time));
+    if (c->is_union) {              // the union's rows are profiles already
+        XM_HIP(hipMemcpyAsync(c->pf_ptr, c->un_ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyDeviceToDevice, c->st));
+        if (nnz) {
+            XM_HIP(hipMemcpyAsync(c->pf_item, c->un_item, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToDevice, c->st));
+            XM_HIP(hipMemcpyAsync(c->pf_rating, c->un_rating, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, c->st));
+            XM_HIP(hipMemcpyAsync(c->pf_time, c->un_time, sizeof(int64_t) * (size_t)nnz, hipMemcpyDeviceToDevice, c->st));
+        }
+    } else {
+        XM_TRY(xmap_rec_profiles(c->st, U, nnz, c->n_target_rows, c->g_off_t, c->g_off_m, c->g_user, c->g_item, c->g_rating, c->g_time,
+                                 c->pf_ptr, c->pf_item, c->pf_rating, c->pf_time));
+    }
     XM_ALLOCZ(c->p_rec, c->rs_row_ptr, I + 1);
     XM_ALLOCZ(c->p_rec, c->rs_avg, i1); XM_ALLOCZ(c->p_rec, c->rs_norm, i1);
     c->rec_pairs = 0;
@@ -903,7 +928,7 @@ int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, 
 
 int xmap_ctx_foldin(xmap_ctx *c, int64_t n_new, const int64_t *ptr, const int32_t *item, const float *rating, const int64_t *time,
                     int64_t *counts) {
-    XM_ARG(c && c->have_gen && n_new >= 0 && ptr);
+    XM_ARG(c && c->have_gen && !c->is_union && n_new >= 0 && ptr);
     // the batch is checked here, on the host: bad input starts no device work (xmap_foldin_count's own check then passes)
     if (ptr[0] != 0) { set_error("fold-in batch: ptr[0] = %lld, not 0", (long long)ptr[0]); return XMAP_ERR_ARG; }
     for (int64_t u = 0; u < n_new; u++)
@@ -970,6 +995,69 @@ int xmap_ctx_foldin_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_use
     XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
     return predict_over(c, foldin_profiles(c), n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
                         max_now);
+}
+
+// ---- multi-domain: the union of other contexts' AlterEgo rows ----------------------------------------------------------
+
+int xmap_ctx_union(xmap_ctx *c, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
+                   int64_t n_users, int32_t n_items, int flags, int64_t *counts) {
+    XM_ARG(c && src && user_map && item_map && n_parts >= 1 && n_parts <= 16 && n_users >= 0 && n_items >= 0);
+    XM_ARG((flags & ~XMAP_UNION_DISTINCT) == 0);
+    for (int d = 0; d < n_parts; d++) {
+        const xmap_ctx *s = src[d];
+        if (!s || s == c || !s->have_gen || s->is_union || s->device != c->device) {
+            set_error("xmap_ctx_union: source %d must be another context on device %d that holds generated rows", d, c->device);
+            return XMAP_ERR_ARG;
+        }
+        XM_ARG((s->R.n_users == 0 || user_map[d]) && (s->R.n_items == 0 || item_map[d]));
+    }
+    XM_HIP(hipSetDevice(c->device));
+    // built beside whatever dst holds, which is replaced only when everything has succeeded
+    ScratchPool tmp, fresh;
+    xmap_union_part parts[16];
+    memset(parts, 0, sizeof(parts));
+    for (int d = 0; d < n_parts; d++) {
+        const xmap_ctx *s = src[d];
+        int32_t *d_umap, *d_imap;
+        XM_TRY(h2d(tmp, &d_umap, user_map[d], (size_t)s->R.n_users, c->st));
+        XM_TRY(h2d(tmp, &d_imap, item_map[d], (size_t)s->R.n_items, c->st));
+        xmap_union_part &p = parts[d];
+        p.n_users = s->R.n_users; p.n_items = s->R.n_items; p.n_rows = s->n_rows; p.n_target_rows = s->n_target_rows;
+        p.user = s->g_user; p.item = s->g_item; p.rating = s->g_rating; p.time = s->g_time;
+        p.off_t = s->g_off_t; p.off_m = s->g_off_m; p.user_map = d_umap; p.item_map = d_imap;
+    }
+    int64_t *un_ptr, *un_time, h[4] = {0, 0, 0, 0};
+    int32_t *un_item, *d_pre, *d_suf;
+    uint32_t *d_mask;
+    uint8_t *d_flags;
+    double *un_rating;
+    const size_t i1 = (size_t)(n_items ? n_items : 1);
+    XM_TRY(dalloc(fresh, &un_ptr, (size_t)n_users + 1, c->st, true));
+    XM_TRY(xmap_union_count(c->st, n_parts, parts, n_users, n_items, flags, un_ptr, h));
+    XM_TRY(dalloc(fresh, &un_item, (size_t)h[0], c->st)); XM_TRY(dalloc(fresh, &un_rating, (size_t)h[0], c->st));
+    XM_TRY(dalloc(fresh, &un_time, (size_t)h[0], c->st));
+    XM_TRY(xmap_union_fill(c->st, n_parts, parts, n_users, n_items, flags, un_ptr, h[0], un_item, un_rating, un_time));
+    // every union item is a target item ("T:" in iid); the other predicates are never asked of a tail-only context
+    XM_TRY(dalloc(fresh, &d_pre, i1, c->st, true)); XM_TRY(dalloc(fresh, &d_suf, i1, c->st, true));
+    XM_TRY(dalloc(fresh, &d_mask, i1, c->st, true)); XM_TRY(dalloc(fresh, &d_flags, i1, c->st));
+    XM_HIP(hipMemsetAsync(d_flags, 2, i1, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    drop_tail(c);
+    drop_fold(c);
+    drop_union(c);
+    c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_ratings.release();
+    c->have_ratings = c->have_sim = c->have_ext = false;
+    c->p_union.ptrs.swap(fresh.ptrs);
+    memset(&c->R, 0, sizeof(c->R));
+    c->R.n_users = n_users; c->R.n_items = n_items;
+    c->R.prefix_cls = d_pre; c->R.suffix_cls = d_suf; c->R.contains_mask = d_mask; c->R.flags = d_flags;
+    c->un_ptr = un_ptr; c->un_item = un_item; c->un_rating = un_rating; c->un_time = un_time;
+    c->n_rows = c->n_target_rows = h[0];
+    c->g_user = c->g_item = nullptr; c->g_rating = nullptr; c->g_time = nullptr; c->g_off_t = c->g_off_m = nullptr; c->g_map = nullptr;
+    c->is_union = true;
+    c->have_gen = true;
+    if (counts) memcpy(counts, h, sizeof(h));
+    return XMAP_OK;
 }
 
 int xmap_ctx_evaluate_topn(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,

@@ -1516,6 +1516,72 @@ class Engine(object):
         P.counts = tuple(int(x) for x in h)
         return P
 
+    @staticmethod
+    def union_profiles(parts, n_users, n_items, distinct=True, timers=None):
+        """The union of the AlterEgo rows of several two-domain problems as ONE set of user-major profiles
+        (xmap_union_count / xmap_union_fill): the reference's alterEgo_profile1.union(alterEgo_profile2) and, with distinct,
+        .distinct() (code/multidomain_demo.py:128), without a host copy.  The union space belongs to no single engine's ratings,
+        hence a static method.  parts = [(G, user_map, item_map, time_key or None)*], 1 .. 16 of them on one device: G the
+        result of alterego(); user_map [users of G's engine] -> union user (injective within a part), item_map [items of G's
+        engine] -> union item or -1 (rows of that item are dropped) -- int32 tensors or NumPy arrays; time_key as
+        alterego_profiles takes it (ranks must compare ACROSS the parts).  A union user's rows: parts in the order given, within
+        a part pass-through rows, then mapped rows, in stage-C order; distinct removes a row equal (item, time, rating as a number)
+        to an earlier one of the same user.  The maps, offsets and row items are checked on the device first (XmapError, code
+        ERR_ARG).  Returns the DeviceRatings-compatible view alterego_profiles returns, over the union item space with every
+        item in the target class -- Engine(view).rec_sim / rec_select / predict / topn / topn_eval / mae work as for one domain --
+        with .counts = (rows, duplicates removed, rows dropped by item_map == -1, union users with a row).  timers: a dict that
+        collects the HIP-event brackets "union_count" / "union_fill", like Engine.timers."""
+        parts = list(parts)
+        if not 1 <= len(parts) <= abi.UNION_MAX_PARTS:
+            raise ValueError("a union takes 1 .. %d parts, not %d" % (abi.UNION_MAX_PARTS, len(parts)))
+        dev = parts[0][0].item.device
+        U, I = int(n_users), int(n_items)
+
+        def dmap(a):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a, np.int32))
+            return a.to(device=dev, dtype=torch.int32).contiguous()
+        keep = []                                   # the tensors behind the descriptors' pointers
+        desc = (abi.UnionPart * len(parts))()
+        for d, (G, user_map, item_map, time_key) in enumerate(parts):
+            um, im = dmap(user_map), dmap(item_map)
+            tm = G.time if time_key is None else time_key.contiguous()
+            n = int(G.n_rows)
+            if G.item.device != dev or int(G.off_t.numel()) != int(um.numel()) + 1 or int(G.off_m.numel()) != int(um.numel()) + 1 \
+                    or int(tm.numel()) < n:
+                raise ValueError("union part %d: one device, user_map of one entry per user of the part, a time per row" % d)
+            keep += [um, im, tm]
+            desc[d] = abi.UnionPart(int(um.numel()), int(im.numel()), n, int(G.n_target_rows), G.user.data_ptr(), G.item.data_ptr(),
+                                    G.rating.data_ptr(), tm.data_ptr(), G.off_t.data_ptr(), G.off_m.data_ptr(), um.data_ptr(),
+                                    im.data_ptr())
+        eng = object.__new__(Engine)
+        eng.dev, eng.timers, eng._scratch = dev, timers, {}
+        flags = abi.UNION_DISTINCT if distinct else 0
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            ptr = torch.empty(U + 1, dtype=torch.int64, device=dev)
+            h = (C.c_int64 * 4)(0, 0, 0, 0)
+            with eng.timed("union_count"):
+                check(lib.xmap_union_count(st, i32(len(parts)), desc, i64(U), i32(I), i32(flags), vp(ptr), h))
+            n = int(h[0])
+            item = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            rating = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+            time = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+            with eng.timed("union_fill"):
+                check(lib.xmap_union_fill(st, i32(len(parts)), desc, i64(U), i32(I), i32(flags), vp(ptr), i64(n), vp(item), vp(rating),
+                                          vp(time)))
+        del keep
+        # the union's item space: every item a target item ("T:" in iid, flag bit 1); no other predicate is asked of the tail
+        R = object.__new__(DeviceRatings)
+        R.device, R.n_items = dev, I
+        z = torch.zeros(max(I, 1), dtype=torch.int32, device=dev)
+        R.prefix_cls, R.suffix_cls, R.contains_mask = z, z, z
+        R.flags = torch.full((max(I, 1),), 2, dtype=torch.uint8, device=dev)
+        eng.R = R
+        P = eng._profile_view(U, n, ptr, item, rating, time)
+        P.counts = tuple(int(x) for x in h)
+        return P
+
     def predict(self, P, neighbors, test_user, test_item, item_avg, wtab):
         """RecommenderPrediction.item_based_prediction on the device (xmap_predict_rows, one wave per test pair) over the
         profiles P of alterego_profiles: neighbors = (cnt [I], col [I][keep], sim [I][keep], ...) as rec_select returns

@@ -28,12 +28,22 @@ def domain_groups(n_domains, world):
     return [([r], list(range(r, n_domains, world))) for r in range(world)]
 
 
-def run_multidomain(make_engine, n_domains, method, cap, k, private, dist=None):
+def run_multidomain(make_engine, n_domains, method, cap, k, private, dist=None, device_tail=False, distinct=True):
     """make_engine(d) -> (Engine over domain d's ratings, n_src_items of that domain); called only on the ranks that own
     domain d.  Returns the union of the AlterEgo rows of all domains on EVERY rank, domain by domain:
-    dict(user, item (common target numbering), rating, time, domain, n_paths, n_rows per domain)."""
+    dict(user, item (common target numbering), rating, time, domain, n_paths, n_rows per domain).
+    device_tail (one rank only; NotImplementedError with more): the rows stay on the device and are united there
+    (Engine.union_profiles; distinct: the reference driver's .distinct()) -- the result carries "P", the union's user-major
+    profiles over the common users and the common target numbering (Engine(P).rec_sim / rec_select / predict / topn /
+    topn_eval / mae take it), and "counts" = (rows, duplicates removed, rows dropped, users with a row) in place of the five
+    host row columns; n_paths and n_rows as above."""
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
+    if device_tail:
+        if world > 1:
+            raise NotImplementedError("device_tail unites the rows on one device: run it with one rank (the sharded gather "
+                                      "returns host rows)")
+        return _run_device_tail(make_engine, n_domains, method, cap, k, private, distinct)
     plan = domain_groups(n_domains, world)
     groups = []
     for ranks, _ in plan:           # every rank creates every group (torch.distributed requires it), in the same order
@@ -69,3 +79,24 @@ def run_multidomain(make_engine, n_domains, method, cap, k, private, dist=None):
     out = {k_: v[o].numpy() for k_, v in out.items()}
     out["n_paths"], out["n_rows"] = stats[:, 0].numpy(), stats[:, 1].numpy()
     return out
+
+
+def _run_device_tail(make_engine, n_domains, method, cap, k, private, distinct):
+    """run_multidomain(device_tail=True): every domain's stage-C rows stay where stage C wrote them; users are common
+    (identity maps), a target item maps to `item - n_src_items`, a source item (it has no AlterEgo row) to -1"""
+    from . import device
+    parts, n_users, n_target = [], 0, 0
+    stats = np.zeros((n_domains, 2), np.int64)
+    for d in range(n_domains):
+        eng, n_src = make_engine(d)
+        res = sharded.run_step(eng, method, cap, k, private, None, group=None)
+        G = res["G"]
+        U, I = eng.R.n_users, eng.R.n_items
+        item_map = torch.arange(I, dtype=torch.int32, device=eng.dev) - int(n_src)
+        item_map[:int(n_src)] = -1
+        parts.append((G, torch.arange(U, dtype=torch.int32, device=eng.dev), item_map, None))
+        n_users, n_target = max(n_users, U), max(n_target, I - int(n_src))
+        stats[d, 0], stats[d, 1] = int(res["n_paths"]), int(G.n_rows)
+        del eng, res
+    P = device.Engine.union_profiles(parts, n_users, n_target, distinct)
+    return dict(P=P, counts=P.counts, n_paths=stats[:, 0], n_rows=stats[:, 1])

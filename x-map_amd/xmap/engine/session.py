@@ -263,19 +263,114 @@ def time_rank(state):
     return key
 
 
+class _UnionState(object):
+    """what the tail reads of a train state, over the id tables of a union: .idt (uids, iids, uidx, iidx) and .engine (its
+    device and timers: the first part's)"""
+
+    def __init__(self, idt, engine):
+        self.idt, self.engine = idt, engine
+
+
+class AlterEgoUnion(LocalRDD):
+    """union_alterego's handle: the AlterEgo rows of several two-domain problems as ONE set of profiles on the device
+    (Engine.union_profiles), over joint id tables.  Iterates like handles[0].union(handles[1]) ... [.distinct()]: the same
+    tuples in the same order (that order is part-major, so iterating collects the parts' rows on the host; the tail does not).
+    .state.idt holds the joint tables, .counts = (rows, duplicates removed, rows dropped, users with a row)."""
+
+    def __init__(self, handles, distinct, state, parts, ctx=None):
+        LocalRDD.__init__(self, None, ctx)
+        self.handles, self.distinct_rows, self.state, self._parts = list(handles), bool(distinct), state, parts
+        self._P = None
+
+    def _rows(self):
+        out = [row for h in self.handles for row in h.collect()]
+        return LocalRDD(out).distinct().collect() if self.distinct_rows else out
+
+    def profiles(self):
+        """the union's user-major profiles (built once): the view Engine.union_profiles returns"""
+        if self._P is None:
+            from . import device
+            idt = self.state.idt
+            self._P = device.Engine.union_profiles(self._parts, len(idt.uids), len(idt.iids), self.distinct_rows,
+                                                   timers=self.state.engine.timers)
+        return self._P
+
+    @property
+    def counts(self):
+        return self.profiles().counts
+
+
+def _common_time_ranks(states):
+    """per train state the int64 device tensor time_rank gives, but ranked over the time objects of ALL the states, so that
+    the ranks of different domains compare (their order and their ties)"""
+    import torch
+    whens = [getattr(st.times, "when", None) for st in states]
+    if all(w is not None for w in whens):               # native feeds: numbers already
+        arrs = [np.asarray(w).reshape(-1) for w in whens]
+        inv = np.unique(np.concatenate(arrs), return_inverse=True)[1].reshape(-1)
+        cuts = np.cumsum([0] + [len(a) for a in arrs])
+        ranks = [inv[cuts[k]:cuts[k + 1]] for k in range(len(arrs))]
+    else:
+        times = [list(w) if w is not None else st.times for st, w in zip(states, whens)]
+        order = {t: k for k, t in enumerate(sorted(set().union(*[set(ts) for ts in times])))}
+        ranks = [np.fromiter((order[t] for t in ts), np.int64, len(ts)) for ts in times]
+    return [torch.from_numpy(np.ascontiguousarray(r, np.int64)).to(st.engine.dev) for r, st in zip(ranks, states)]
+
+
+def union_alterego(handles, distinct=True):
+    """The union of the AlterEgoRDD handles of several two-domain problems -- the multi-domain pipeline's
+    alterEgo_profile1.union(alterEgo_profile2) and, with distinct, .distinct() (reference code/multidomain_demo.py:128) -- kept on
+    the device.  The host builds only the tables: the joint uids (sorted) and iids (sorted; the items that occur in AlterEgo rows
+    -- every other item of a part maps to -1), each part's user and item map into them, and ONE dense rank of the time objects of
+    all parts.  Returns an AlterEgoUnion; recommend, recommend_topn and evaluate_topn take it wherever they take an AlterEgoRDD
+    (fold-in does not: it needs one replacement map)."""
+    import torch
+    handles = list(handles)
+    if not handles or not all(isinstance(h, AlterEgoRDD) for h in handles):
+        raise TypeError("union_alterego() takes a list of AlterEgoRDD handles of generator_pipeline")
+    states = [h.state for h in handles]
+    held = []                                           # per part: the local items that occur in its rows
+    for h in handles:
+        held.append(torch.unique(h.G.item[:h.G.n_rows]).cpu().numpy() if h.G.n_rows else np.zeros(0, np.int64))
+    uids = sorted(set().union(*[set(st.idt.uids) for st in states]))
+    iids = sorted(set().union(*[{st.idt.iids[i] for i in its.tolist()} for st, its in zip(states, held)]))
+    idt = xids.IdTable(uids, iids)
+    ranks = _common_time_ranks(states)
+    parts = []
+    for h, st, its, rank in zip(handles, states, held, ranks):
+        user_map = np.fromiter((idt.uidx[u] for u in st.idt.uids), np.int32, len(st.idt.uids))
+        item_map = np.full(len(st.idt.iids), -1, np.int32)
+        for i in its.tolist():
+            item_map[i] = idt.iidx[st.idt.iids[i]]
+        parts.append((h.G, user_map, item_map, rank[h.G.time] if h.G.n_rows else h.G.time))
+    return AlterEgoUnion(handles, distinct, _UnionState(idt, states[0].engine), parts, getattr(handles[0], "ctx", None))
+
+
+def _no_fold_in(alterEgoRDD, who):
+    if isinstance(alterEgoRDD, AlterEgoUnion):
+        raise TypeError("%s(): fold-in needs one replacement map, and a union of AlterEgo rows has one per part; fold the "
+                        "profiles in against one part's AlterEgoRDD" % who)
+
+
 def _tail_setup(alterEgoRDD, cap, keep, neighbors, who):
     """what recommend and recommend_topn share: profiles of the AlterEgo rows -> RecommenderSim -> neighbour lists (selected on
     the device, or the caller's lists as arrays).  Returns (state, engine over the profiles, P, S, (cnt, col, sim), item_avg)."""
     import torch
     from . import device
-    if not isinstance(alterEgoRDD, AlterEgoRDD):
-        raise TypeError("%s() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device)" % who)
-    st, G = alterEgoRDD.state, alterEgoRDD.G
-    eng, idt = st.engine, st.idt
+    if isinstance(alterEgoRDD, AlterEgoUnion):
+        st = alterEgoRDD.state
+        eng, idt = st.engine, st.idt
+        P = alterEgoRDD.profiles()
+    elif isinstance(alterEgoRDD, AlterEgoRDD):
+        st, G = alterEgoRDD.state, alterEgoRDD.G
+        eng, idt = st.engine, st.idt
+        key = time_rank(st)[G.time] if G.n_rows else G.time
+        P = eng.alterego_profiles(G, time_key=key)
+    else:
+        raise TypeError("%s() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device) or the "
+                        "AlterEgoUnion of union_alterego" % who)
     dev = eng.dev
     I = len(idt.iids)
-    key = time_rank(st)[G.time] if G.n_rows else G.time
-    P = eng.alterego_profiles(G, time_key=key)
     eng2 = device.Engine(P)
     eng2.timers = eng.timers
     S = eng2.rec_sim(int(cap))
@@ -452,6 +547,7 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     rating float32 does not hold raises as the train set's does; times are any mutually comparable objects.  Returns the LocalRDD of
     recommend_topn in the order of `profiles`, with .stats, .sim_pairs, .item_info, .unknown_items and .counts = (AlterEgo rows,
     pass-through rows, profiles with a row)."""
+    _no_fold_in(alterEgoRDD, "recommend_topn_profiles")
     st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn_profiles")
     F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
     uids = sorted(index, key=index.get)
@@ -466,6 +562,7 @@ def recommend_profiles(alterEgoRDD, profiles, testRDD, cap, keep, alpha, neighbo
     held-out (uid, [(iid, rating, ...)*]) records of those users -- a uid is looked up among the profiles' labels, one without a
     profile is a user without ratings.  Returns the LocalRDD of recommend (with .mae, .sim_pairs, .item_info) and .unknown_items,
     .counts."""
+    _no_fold_in(alterEgoRDD, "recommend_profiles")
     st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_profiles")
     F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
     res = _predict_records(st, eng2, F, nb, item_avg, index, testRDD, alpha)
@@ -495,8 +592,9 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     (bit r = the item at rank r is a relevant held-out item); .sim_pairs / .item_info like recommend.  ValueError on a
     repeated (uid, iid) or a rating that is not a number."""
     import torch
-    if not isinstance(alterEgoRDD, AlterEgoRDD):
-        raise TypeError("evaluate_topn() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device)")
+    if not isinstance(alterEgoRDD, (AlterEgoRDD, AlterEgoUnion)):
+        raise TypeError("evaluate_topn() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device) or the "
+                        "AlterEgoUnion of union_alterego")
     recs = records_of(testRDD)
     seen = set()
     for uid, pairs in recs:
