@@ -751,7 +751,16 @@ int xmap_union_fill(void *stream, int32_t n_parts, const xmap_union_part *parts 
  * per-item predicate arrays are the string tests of the reference evaluated once per item (xmap/engine/ids.py):
  * prefix_cls (iid[:2] class, baselinerSim.py:191), suffix_cls (iid[-2:] class), contains_mask (bit c: the suffix of
  * class c occurs in the id, extender.py:29-35), flags (bit 0 "S:" in iid, bit 1 "T:" in iid).
- *   xmap_ctx_upload_ratings : trainRDD in index space, CSR by user in trainRDD / profile order      (assist.py:66)
+ *   xmap_ctx_upload_ratings : trainRDD in index space, CSR by user in trainRDD / profile order      (assist.py:66).  The input
+ *                             is checked on the host first (xmap_check_ratings, no repeats allowed): XMAP_ERR_ARG naming the first
+ *                             offending position, nothing dropped, allocated or launched -- the context stays as it was, the
+ *                             previous upload and its results included.  NaN and +-inf ratings pass
+ *   xmap_check_ratings      : that check on its own (host code, O(nnz), one int64 stamp per item; no device, no context):
+ *                             user_ptr[0] == 0; user_ptr non-decreasing (a decrease is a negative profile length in every kernel
+ *                             of stage A); user_ptr[n_users] < 2^31 - 1; 0 <= item < n_items; no item twice in one profile unless
+ *                             allow_repeats (a trainRDD holds one rating per (user, item): remove_invalid; stage A sizes its tables
+ *                             for that -- only RecommenderSim's AlterEgo profiles may repeat an item); suffix_cls in [0, 32) (a
+ *                             shift count of stage B); prefix_cls >= 0.  prefix_cls / suffix_cls may be NULL (not checked)
  *   xmap_ctx_item_sim       : baseliner_calculate_sim_pipeline (assist.py:66-77) -> n_kept directed pairs kept
  *   xmap_ctx_sim_download   : CSR by first item (row_ptr [I+1], col/sim/mutu/n_ij [n_kept]; rows not sorted), item info
  *                             [I][4], user averages [U]; any pointer may be NULL
@@ -855,6 +864,8 @@ int xmap_feed_format(int64_t n_users, const int64_t *user_ptr, const int32_t *it
 
 int xmap_ctx_create(int device, xmap_ctx **out);
 void xmap_ctx_destroy(xmap_ctx *ctx);
+int xmap_check_ratings(int64_t n_users, int32_t n_items, const int64_t *user_ptr, const int32_t *item, const int32_t *prefix_cls,
+                       const int32_t *suffix_cls, int32_t allow_repeats);
 int xmap_ctx_upload_ratings(xmap_ctx *ctx, int64_t n_users, int32_t n_items, const int64_t *user_ptr, const int32_t *item,
                             const float *rating, const int64_t *time, const int32_t *prefix_cls, const int32_t *suffix_cls,
                             const uint32_t *contains_mask, const uint8_t *flags);

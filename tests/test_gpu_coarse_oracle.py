@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
-from golden_util import CAP, METHODS, csr_to_pairs
+from golden_util import CAP, METHODS, census, check_census, csr_to_pairs
 from test_gpu_coarse_abi import Ctx, _draw, _p
-from test_gpu_parity import SWEEP, hub_ratings
+from test_gpu_parity import GAPS, SWEEP, SWEEP_B, gap_case, hub_ratings, knn_chunk_ratings, sweep_ratings
 
 pytestmark = pytest.mark.gpu
 
@@ -138,9 +138,11 @@ class Oracle(object):
                     uavg=self.xo.user_info(self.T)[0])
 
     def stage_b(self, k):
-        if self.Xo is not None:
-            self.xo.ext_free(self.Xo)
-        Xo = self.Xo = self.xo.extend(self.T, self.So, k)
+        if self.Xo is None or self.Xo.k != k:           # (asked twice where a census precedes the comparison)
+            if self.Xo is not None:
+                self.xo.ext_free(self.Xo)
+            self.Xo = self.xo.extend(self.T, self.So, k)
+        Xo = self.Xo
         n_cand = np.diff(Xo.xs_ptr).astype(np.int32)
         rows, ends = csr_to_pairs(Xo.xs_ptr, Xo.xs_end)
         lists = (rows, ends, Xo.xs_val)
@@ -155,6 +157,11 @@ class Oracle(object):
         ae = self.xo.alterego(self.T, m)
         return dict(choice=choice, n_target_rows=ae["n_target_rows"], user=ae["user"], item=ae["item"], rating=ae["rating"],
                     time=ae["time"])
+
+    def census(self, private, picks):
+        """golden_util.census of the extension last made and the generation it leads to"""
+        _, _, m = self.xo.select(self.T, self.Xo, private, picks)
+        return census(self.So, self.Xo, m, self.xo.alterego(self.T, m))
 
     def close(self):
         if self.Xo is not None:
@@ -197,16 +204,33 @@ class EngineStagesBC(Oracle):
                     item=G.item.cpu().numpy(), rating=G.rating.cpu().numpy(), time=G.time.cpu().numpy())
 
 
-def check_coarse(r, method, ks, private=True, picks_seed=None, ref=Oracle, ctx=None):
+def _gen_args(n_top, private, picks_seed):
+    """(private, picks) of one generation: seeded picks from n_top, or private where the reference's draw refuses"""
+    if private:
+        return True, None
+    np.random.seed(picks_seed)
+    try:
+        return False, _draw(n_top)
+    except ValueError:
+        return True, None
+
+
+def check_coarse(r, method, ks, private=True, picks_seed=None, ref=Oracle, ctx=None, need=None):
     """every stage of the coarse ABI on r against `ref`: stage A; for each k stage B, the non-private candidate counts and
     stage C (private, or non-private with seeded picks; a start with a single candidate makes the reference's randint
-    refuse the draw: then private, as in test_gpu_parity._check_all_stages).  Returns the coarse results."""
+    refuse the draw: then private, as in test_gpu_parity._check_all_stages).  need: lower bounds on the oracle's census
+    (golden_util.census) at every k, checked on the oracle's results before the context is touched.  Returns the coarse
+    results."""
     I, U = r.n_items, len(r.user_ptr) - 1
     want = ref(r, method)
     own = ctx is None
-    ctx = ctx or Ctx()
     out = []
     try:
+        if need is not None:
+            for k in ks:
+                want.stage_b(k)
+                check_census(want.census(*_gen_args(want.n_top4(), private, picks_seed)), need, "%s, k = %d" % (method, k))
+        ctx = ctx or Ctx()
         upload(ctx, r)
         A = stage_a(ctx, method, I, U)
         _same(A, want.stage_a(), "stage A")
@@ -216,19 +240,13 @@ def check_coarse(r, method, ks, private=True, picks_seed=None, ref=Oracle, ctx=N
             assert int(B["n_cand"].sum()) == B["n_out"]
             n_top = candidates(ctx, I)
             assert np.array_equal(n_top, want.n_top4())
-            priv, picks = private, None
-            if not private:
-                np.random.seed(picks_seed)
-                try:
-                    picks = _draw(n_top)
-                except ValueError:
-                    priv = True
+            priv, picks = _gen_args(n_top, private, picks_seed)
             Cc = stage_c(ctx, I, priv, picks)
             _same(Cc, want.stage_c(priv, picks), "stage C, k = %d" % k)
             out.append((A, B, Cc))
     finally:
         want.close()
-        if own:
+        if own and ctx is not None:
             ctx.close()
     return out
 
@@ -250,14 +268,13 @@ def test_c1_through_the_coarse_abi(method):
     check_coarse(r, method, (20,), ref=EngineStagesBC)
 
 
-@pytest.mark.parametrize("cfg", SWEEP, ids=lambda c: "s%d" % c["seed"])
+@pytest.mark.parametrize("cfg", SWEEP + SWEEP_B, ids=lambda c: "s%d" % c["seed"])
 @pytest.mark.parametrize("method", METHODS)
 def test_shape_sweep_through_the_coarse_abi(method, cfg):
-    """test_gpu_parity's sweep: tiny, skewed and one-sided shapes, k up to 100"""
-    from xmap.engine import synth
-    kw = {n: cfg[n] for n in ("overlap", "mu", "sigma", "zipf") if n in cfg}
-    r = synth.make_two_domain(cfg["seed"], cfg["users"], cfg["src"], cfg["tgt"], **kw)
-    check_coarse(r, method, (cfg["k"],), private=(cfg["seed"] % 2 == 0), picks_seed=cfg["seed"])
+    """test_gpu_parity's sweeps: tiny, skewed and one-sided shapes, k up to 100; SWEEP_B's entries with the work for stages
+    B and C that their census demands"""
+    check_coarse(sweep_ratings(cfg), method, (cfg["k"],), private=(cfg["seed"] % 2 == 0), picks_seed=cfg["seed"],
+                 need=cfg.get("need"))
 
 
 def test_k50_through_the_coarse_abi():
@@ -284,9 +301,8 @@ def test_long_profiles_through_the_coarse_abi(method):
 
 
 def test_rows_longer_than_one_knn_chunk_through_the_coarse_abi():
-    from xmap.engine import synth
-    r = synth.make_two_domain(17, 2500, 3000, 3000, overlap=0.5, mu=3.2, sigma=1.0)
-    (A, _, _), = check_coarse(r, "cosine", (3,))
+    r = knn_chunk_ratings()
+    (A, _, _), = check_coarse(r, "cosine", (3,), need=dict(paths=10 ** 5, mapped=50))
     ln = np.bincount(A["rows"], minlength=r.n_items)
     assert (ln > 2048).sum() > 200 and ln.max() > 4096
 
@@ -369,6 +385,115 @@ def test_degenerate_inputs_through_the_coarse_abi(method):
             ctx.call("xmap_ctx_gen_download", None, None, None, None)
         finally:
             ctx.close()
+
+
+# ------------------------------------------------------------------------------------------ 1b. index spaces with gaps
+@pytest.mark.parametrize("seed,ext_kw,env", GAPS, ids=["tiny", "heavy", "tiny-partitioned-count"])
+@pytest.mark.parametrize("method", METHODS)
+def test_index_spaces_with_gaps_through_the_coarse_abi(method, seed, ext_kw, env, monkeypatch):
+    """test_gpu_parity.test_index_spaces_with_gaps through the coarse door: the stretched upload (unrated item indices, users
+    without ratings, in runs of thousands) against the oracle, and against the compact upload's own results re-indexed"""
+    from golden_util import reindexed
+    cfg, r, g, item_map, user_map = gap_case(seed)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    kw = dict(private=(seed % 2 == 0), picks_seed=seed, need=cfg["need"])
+    (A, B, Cc), = check_coarse(r, method, (cfg["k"],), **kw)
+    (Ag, Bg, Cg), = check_coarse(g, method, (cfg["k"],), **kw)                                      # (a)
+    for got, compact, what in ((Ag, A, "stage A"), (Bg, B, "stage B"), (Cg, Cc, "stage C")):            # (b)
+        _same(got, reindexed(compact, item_map, user_map, g.n_items, g.n_users), what + ", stretched vs compact")
+    unrated = np.ones(g.n_items, bool)
+    unrated[item_map] = False
+    assert not Ag["info"][unrated].any() and not Bg["n_cand"][unrated].any() and (Cg["choice"][unrated] == -1).all()
+    empty = np.ones(g.n_users, bool)
+    empty[user_map] = False
+    assert not Ag["uavg"][empty].any() and not empty[Cg["user"]].any()
+    assert B["n_paths"] > 0 and len(Cc["user"]) > Cc["n_target_rows"]
+
+
+# ------------------------------------------------------------------------------------- 1c. uploads the stages cannot take
+def _arrays(r):
+    pre, suf, mask, flags = [np.ascontiguousarray(a, t).copy() for a, t in zip(r.item_attrs(), (np.int32, np.int32, np.uint32, np.uint8))]
+    return dict(ptr=np.ascontiguousarray(r.user_ptr, np.int64).copy(), item=np.ascontiguousarray(r.item, np.int32).copy(),
+                rating=np.ascontiguousarray(r.rating, np.float32), time=np.ascontiguousarray(r.time, np.int64), pre=pre, suf=suf,
+                mask=mask, flags=flags)
+
+
+def _upload_rc(ctx, a, n_items):
+    rc = ctx.lib.xmap_ctx_upload_ratings(ctx.h, len(a["ptr"]) - 1, n_items, _p(a["ptr"], C.c_int64), _p(a["item"], C.c_int32),
+                                         _p(a["rating"], C.c_float), _p(a["time"], C.c_int64), _p(a["pre"], C.c_int32),
+                                         _p(a["suf"], C.c_int32), _p(a["mask"], C.c_uint32), _p(a["flags"], C.c_uint8))
+    return rc, ctx.lib.xmap_last_error().decode()
+
+
+def _bad_uploads(r):
+    """(what, arrays, the text xmap_last_error() has to hold): one offence each, the first offending position named"""
+    u = r.n_users // 2
+    e = int(r.user_ptr[u])                                   # user u holds at least five ratings (synth.make_two_domain)
+    out = []
+    a = _arrays(r); a["ptr"][0] = 1
+    out.append(("user_ptr[0] != 0", a, r"user_ptr\[0\] = 1, not 0"))
+    a = _arrays(r); a["ptr"][u + 1] = a["ptr"][u] - 1        # (user_ptr[n_users], all the old check read, is unchanged)
+    out.append(("user_ptr decreases", a, r"user_ptr\[%d\] < user_ptr\[%d\]" % (u + 1, u)))
+    a = _arrays(r); a["item"][e + 3] = a["item"][e + 1]
+    out.append(("an item twice in a profile", a, r"user %d holds item %d twice \(item\[%d\] and item\[%d\]\)"
+                % (u, a["item"][e + 1], e + 1, e + 3)))
+    a = _arrays(r); a["item"][e + 2] = r.n_items
+    out.append(("item out of range", a, r"item\[%d\] = %d outside \[0, %d\)" % (e + 2, r.n_items, r.n_items)))
+    a = _arrays(r); a["suf"][7] = 32
+    out.append(("suffix_cls = 32", a, r"suffix_cls\[7\] = 32 outside \[0, 32\)"))
+    a = _arrays(r); a["suf"][r.n_items - 1] = -1
+    out.append(("suffix_cls < 0", a, r"suffix_cls\[%d\] = -1 outside \[0, 32\)" % (r.n_items - 1)))
+    a = _arrays(r); a["pre"][3] = -2
+    out.append(("prefix_cls < 0", a, r"prefix_cls\[3\] = -2 is negative"))
+    return out
+
+
+def test_uploads_the_stages_cannot_take_are_refused():
+    """xmap_ctx_upload_ratings checks what every stage assumes (xmap_check_ratings) before it drops, allocates or launches
+    anything: XMAP_ERR_ARG with the first offending position in xmap_last_error(), on a fresh context and on one that holds
+    an upload -- which then still answers xmap_ctx_item_sim with its previous result.  No stage is called after a refused
+    upload on a context without a good one."""
+    from xmap.engine import synth
+    r = synth.make_two_domain(9, 300, 70, 70, overlap=0.4)
+    bad = _bad_uploads(r)
+    fresh = Ctx()
+    try:
+        for what, a, text in bad:
+            rc, msg = _upload_rc(fresh, a, r.n_items)
+            assert rc == fresh.abi.ERR_ARG, (what, msg)
+            assert re.search(text, msg), (what, msg)
+    finally:
+        fresh.close()
+    ctx = Ctx()
+    try:
+        upload(ctx, r)
+        A = stage_a(ctx, "adjust_cosine", r.n_items, r.n_users)
+        assert A["rows"].size > 0
+        for what, a, text in bad:
+            rc, msg = _upload_rc(ctx, a, r.n_items)
+            assert rc == ctx.abi.ERR_ARG and re.search(text, msg), (what, msg)
+            _same(stage_a(ctx, "adjust_cosine", r.n_items, r.n_users), A, "stage A after the refused upload: " + what)
+    finally:
+        ctx.close()
+
+
+def test_the_engine_door_refuses_the_same_uploads():
+    """DeviceRatings raises ValueError with the coarse door's text before anything is uploaded; AlterEgo profiles (rating64)
+    may hold an item twice, nothing else"""
+    from xmap.engine import device, synth
+    r = synth.make_two_domain(9, 300, 70, 70, overlap=0.4)
+    for what, a, text in _bad_uploads(r):
+        attrs = (a["pre"], a["suf"], a["mask"], a["flags"])
+        with pytest.raises(ValueError, match=text):
+            device.DeviceRatings(a["ptr"], a["item"], a["rating"], a["time"], r.n_items, attrs)
+        if what != "an item twice in a profile":
+            with pytest.raises(ValueError, match=text):
+                device.DeviceRatings(a["ptr"], a["item"], a["rating"], a["time"], r.n_items, attrs, rating64=True)
+    a = [x for x in _bad_uploads(r) if x[0] == "an item twice in a profile"][0][1]
+    P = device.DeviceRatings(a["ptr"], a["item"], a["rating"], a["time"], r.n_items, (a["pre"], a["suf"], a["mask"], a["flags"]),
+                             rating64=True)
+    assert P.nnz == r.nnz
 
 
 # ---------------------------------------------------------------------------------------------- 2. context lifecycle

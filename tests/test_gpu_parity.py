@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from golden_util import CASES, METHODS, CAP, FRACTIONAL, FRACTIONAL_RTOL, Golden, csr_to_pairs
+from golden_util import CASES, METHODS, CAP, FRACTIONAL, FRACTIONAL_RTOL, Golden, census, check_census, csr_to_pairs
 
 pytestmark = pytest.mark.gpu
 
@@ -140,13 +140,31 @@ def test_golden_all_stages(dev, case, method):
             assert np.array_equal(G.time.cpu().numpy(), gold[gtag + ".ae_time"])
 
 
-def _check_all_stages(dev, r, method, k, private=True, picks_seed=None, **sim_kw):
-    """every stage of one pass against the CPU oracle, bit for bit (ratings of the AlterEgo rows: fp32, atol 1e-5)"""
+def _check_all_stages(dev, r, method, k, private=True, picks_seed=None, need=None, ext_kw=None, **sim_kw):
+    """every stage of one pass against the CPU oracle, bit for bit (ratings of the AlterEgo rows: fp32, atol 1e-5).
+    need: lower bounds on golden_util.census() of the oracle's own results -- how many non-bridge items, paths, candidates,
+    replacements and AlterEgo rows of replaced items the input must produce for the comparison to say something about
+    stages B and C; checked before anything of the GPU's is compared.  ext_kw: arguments of Engine.extend (chunk, n_slots).
+    Returns the engine and its results (stage A, extension, (n_top, choice, map), AlterEgo rows)."""
     from oracle import xmap_oracle as xo
     attrs = r.item_attrs()
-    eng = _engine(dev, r.user_ptr, r.item, r.rating, r.time, r.n_items, attrs)
     T = xo.Train(r.user_ptr, r.item, r.rating, r.time, r.n_items, *attrs)
     So = xo.item_sim(T, method, CAP, nthreads=8)
+    Xo = xo.extend(T, So, k)
+    picks = None
+    if not private:
+        n_top_probe, _, _ = xo.select(T, Xo, True, None)
+        np.random.seed(picks_seed)
+        try:
+            picks = dev.draw_picks(np.minimum(n_top_probe, 4))
+        except ValueError:       # a start with a single candidate: the reference's randint(0, 0) raises (generator.py:109)
+            picks = None
+            private = True
+    n_top_o, choice_o, m_o = xo.select(T, Xo, private, picks)
+    ae = xo.alterego(T, m_o)
+    if need is not None:
+        check_census(census(So, Xo, m_o, ae), need, "%s, k = %d" % (method, k))
+    eng = _engine(dev, r.user_ptr, r.item, r.rating, r.time, r.n_items, attrs)
     S = eng.item_sim_tri(method, CAP, **sim_kw) if sim_kw else eng.item_sim(method, CAP)
     assert S.n_eval == So.n_eval and S.n_contrib == So.n_contrib
     rows, cols, sim, mutu, nij = _sorted_sim(S)
@@ -156,8 +174,7 @@ def _check_all_stages(dev, r, method, k, private=True, picks_seed=None, **sim_kw
     # both sides sum error-free (cosine: integer-exact) -> bit-identical in both modes
     assert np.array_equal(S.info.cpu().numpy(), So.info)
     assert np.array_equal(sim, So.sim)
-    Xo = xo.extend(T, So, k)
-    E = eng.extend(S, k, full=True)
+    E = eng.extend(S, k, full=True, **(ext_kw or {}))
     assert np.array_equal(E.bb.cpu().numpy()[:T.I], Xo.bb)
     assert np.array_equal(E.cls.cpu().numpy()[:T.I], Xo.cls)
     assert np.array_equal(E.kcnt.cpu().numpy()[:T.I], Xo.cnt)
@@ -170,28 +187,18 @@ def _check_all_stages(dev, r, method, k, private=True, picks_seed=None, **sim_kw
     assert np.array_equal(st, ost) and np.array_equal(en, oen)
     # path values are bit-identical and both sides sum them error-free (double-double)
     assert np.array_equal(va, Xo.xs_val)
-    picks = None
-    if not private:
-        n_top_probe, _, _ = xo.select(T, Xo, True, None)
-        np.random.seed(picks_seed)
-        try:
-            picks = dev.draw_picks(np.minimum(n_top_probe, 4))
-        except ValueError:       # a start with a single candidate: the reference's randint(0, 0) raises (generator.py:109)
-            picks = None
-            private = True
-    n_top_o, choice_o, m_o = xo.select(T, Xo, private, picks)
     n_top, choice, mp = eng.select(E, private, picks)
     assert np.array_equal(n_top.cpu().numpy()[:T.I], n_top_o)
     assert np.array_equal(choice.cpu().numpy()[:T.I], choice_o)
     assert np.array_equal(mp.cpu().numpy()[:T.I], m_o)
     G = eng.alterego(mp)
-    ae = xo.alterego(T, m_o)
     assert np.array_equal(G.user.cpu().numpy(), ae["user"]) and np.array_equal(G.item.cpu().numpy(), ae["item"])
     assert np.array_equal(G.rating.cpu().numpy(), ae["rating"])
     assert np.array_equal(G.time.cpu().numpy(), ae["time"])
     assert eng.n_profiles(G) == ae["n_profiles"]
     xo.ext_free(Xo)
     xo.sim_free(So)
+    return eng, S, E, (n_top, choice, mp), G
 
 
 @pytest.mark.parametrize("method", METHODS)
@@ -216,14 +223,52 @@ SWEEP = [
 ]
 
 
-@pytest.mark.parametrize("cfg", SWEEP, ids=lambda c: "s%d" % c["seed"])
+# The same shapes with work for stages B and C.  In SWEEP almost every item has a neighbour of the other domain, paths
+# start from the items that have none, and so most entries enumerate no path at all (seeds 101, 102, 104, 106, 109: none in
+# either method).  Here few users rate in both domains (overlap 0.03 .. 0.15): each entry carries the lower bounds its
+# oracle census (golden_util.census) has to meet -- all but the tiny one 10^5 paths, 50 replaced items, an AlterEgo row of a
+# replaced item and a candidate list the fused top-10 cuts; s209 lists of more than 2048 candidates, which one wave's
+# selection cuts back more than once.  Behind each entry: the oracle's census (cosine | adjusted cosine; nb, paths, n_out,
+# starts, max_cand, neg, mapped, mapped_rows) and the seconds of its one-thread extension.
+_WORK = dict(paths=10 ** 5, mapped=50, mapped_rows=1, max_cand=11)
+SWEEP_B = [
+    # tiny.  44, 1 227, 467, 41, 26, 0, 15, 100 | 43, 410, 195, 19, 33, 52, 13, 94; 0.0 s
+    dict(seed=201, users=60, src=60, tgt=60, overlap=0.1, k=2, need=dict(paths=1, mapped=1)),
+    # source 14 times the target (1 643 + 120 items).  861, 135 655, 52 119, 118, 1 463, 0, 66, 1 340 |
+    # 851, 133 023, 52 080, 119, 1 400, 12 153, 65, 575; 0.3 s
+    dict(seed=202, users=2500, src=1800, tgt=120, overlap=0.1, k=6, need=_WORK),
+    # target 11 times the source (320 + 3 651 items).  3 023, 5 220 852, 433 912, 3 247, 199, 0, 117, 6 056 |
+    # 2 966, 1 178 871, 260 731, 3 274, 212, 84 007, 197, 7 742; 1.5 | 0.8 s
+    dict(seed=203, users=2500, src=320, tgt=6000, overlap=0.04, k=5, mu=1.0, need=_WORK),
+    # Zipf 1.3.  713, 13 565 319, 237 539, 578, 517, 0, 56, 3 528 | 686, 9 364 396, 225 757, 567, 499, 194 312, 76, 3 867; 2.9 | 1.9 s
+    dict(seed=204, users=2500, src=900, tgt=900, overlap=0.1, k=6, zipf=1.3, need=_WORK),
+    # k = 100 (BASELINE configs[3]'s top-k; similarity rows of up to 131 entries).  415, 7 288 193, 57 169, 243, 251, 0, 60, 338 |
+    # 399, 5 260 779, 50 363, 227, 241, 11 951, 50, 209; 1.3 | 0.9 s
+    dict(seed=205, users=500, src=300, tgt=300, overlap=0.03, k=100, d_min=3, mu=0.3, need=_WORK),
+    # heavy rows forced in stage A.  326, 3 410 856, 107 593, 503, 374, 0, 54, 4 366 | 329, 824 794, 119 426, 554, 436, 25 965, 111, 5 758;
+    # 0.6 | 0.2 s
+    dict(seed=206, users=1500, src=600, tgt=600, overlap=0.06, k=5, mu=2.4, sigma=0.8, sim_kw=dict(ch_min=64), need=_WORK),
+    # k = 64.  491, 26 857 963, 84 805, 311, 284, 0, 74, 368 | 471, 19 783 497, 76 689, 298, 270, 13 331, 55, 212; 5.6 | 3.9 s
+    dict(seed=207, users=600, src=350, tgt=350, overlap=0.03, k=64, d_min=3, mu=0.3, need=_WORK),
+    # many partitions.  303, 1 046 668, 162 735, 748, 534, 0, 104, 3 786 | 304, 486 985, 159 382, 748, 540, 45 747, 153, 3 937; 0.3 | 0.2 s
+    dict(seed=208, users=2500, src=800, tgt=800, overlap=0.1, k=6, mu=1.2, sim_kw=dict(slot_target=32), need=_WORK),
+    # candidate lists of more than 2048 entries.  2 809, 2 947 119, 1 120 204, 3 628, 2 483, 0, 827, 5 362 |
+    # 2 819, 3 242 716, 1 324 750, 3 593, 2 546, 503 718, 1 054, 8 456; 1.5 | 1.4 s
+    dict(seed=209, users=4000, src=4000, tgt=4000, overlap=0.15, k=5, mu=1.5, need=dict(_WORK, max_cand=2049)),
+]
+
+
+def sweep_ratings(cfg):
+    from xmap.engine import synth
+    kw = {n: cfg[n] for n in ("overlap", "mu", "sigma", "zipf", "d_min") if n in cfg}
+    return synth.make_two_domain(cfg["seed"], cfg["users"], cfg["src"], cfg["tgt"], **kw)
+
+
+@pytest.mark.parametrize("cfg", SWEEP + SWEEP_B, ids=lambda c: "s%d" % c["seed"])
 @pytest.mark.parametrize("method", METHODS)
 def test_shape_sweep_vs_oracle(dev, method, cfg):
-    from xmap.engine import synth
-    kw = {n: cfg[n] for n in ("overlap", "mu", "sigma", "zipf") if n in cfg}
-    r = synth.make_two_domain(cfg["seed"], cfg["users"], cfg["src"], cfg["tgt"], **kw)
-    _check_all_stages(dev, r, method, cfg["k"], private=(cfg["seed"] % 2 == 0), picks_seed=cfg["seed"],
-                      **cfg.get("sim_kw", {}))
+    _check_all_stages(dev, sweep_ratings(cfg), method, cfg["k"], private=(cfg["seed"] % 2 == 0), picks_seed=cfg["seed"],
+                      need=cfg.get("need"), **cfg.get("sim_kw", {}))
 
 
 def test_edge_cases(dev):
@@ -524,19 +569,28 @@ def test_long_rows_of_the_reverse_lists(dev, method, monkeypatch):
     oracle."""
     monkeypatch.setenv("XMAP_REV_LONG", "64")
     from xmap.engine import synth
-    _check_all_stages(dev, synth.make_two_domain(5, 2000, 400, 400), method, 5)
+    # (oracle census, cosine | adjusted cosine: 415 704 | 270 038 paths, longest candidate list 469 | 467, 99 | 131 replaced items)
+    _check_all_stages(dev, synth.make_two_domain(5, 2000, 600, 600, overlap=0.1), method, 5, need=dict(paths=10 ** 5))
+
+
+def knn_chunk_ratings():
+    """test_rows_longer_than_one_knn_chunk's input (also run through the coarse ABI: test_gpu_coarse_oracle.py)"""
+    from xmap.engine import synth
+    return synth.make_two_domain(17, 2500, 3000, 3000, overlap=0.12, mu=3.6, sigma=1.0)
 
 
 def test_rows_longer_than_one_knn_chunk(dev):
     """similarity rows of several thousand entries (k_knn_classify streams what follows its first 2048-entry chunk
-    against the lists' thresholds): knn tables and everything downstream against the oracle."""
-    from xmap.engine import synth
-    r = synth.make_two_domain(17, 2500, 3000, 3000, overlap=0.5, mu=3.2, sigma=1.0)
+    against the lists' thresholds): knn tables and everything downstream against the oracle.  One user in eight rates in
+    both domains, so the long rows also feed paths (oracle census: 438 non-bridge items, 234 118 paths, 622 starts, longest
+    candidate list 387, 127 replaced items, 14 402 AlterEgo rows of replaced items)."""
+    r = knn_chunk_ratings()
     eng = _engine(dev, r.user_ptr, r.item, r.rating, r.time, r.n_items, r.item_attrs())
     S = eng.item_sim("cosine", CAP)
     ln = np.diff(S.row_ptr.cpu().numpy())
     assert (ln > 2048).sum() > 200 and ln.max() > 4096
-    _check_all_stages(dev, r, "cosine", 3)
+    del eng, S
+    _check_all_stages(dev, r, "cosine", 3, need=dict(paths=10 ** 5, mapped=50))
 
 
 def _ext_bytes(E, I):
@@ -574,3 +628,69 @@ def test_second_pass_after_a_capacity_refusal(dev, case, monkeypatch):
         for x, y in zip(_ext_bytes(eng.extend(S, 5, full=True, **kw), I), want):
             assert np.array_equal(x, y), (name, "after")
         monkeypatch.delenv("XMAP_SLOW_DIV", raising=False)
+
+
+# ---------------------------------------------------------------------------------------------- index spaces with gaps
+def engine_result(eng, S, E, sel, G, I, U, k):
+    """what _check_all_stages returns, downloaded into a dict with the names golden_util.reindexed knows (entries of the knn
+    tables behind a list's count: -1 / 0)"""
+    rows, cols, sim, mutu, nij = _sorted_sim(S)
+    n_top, choice, mp = sel
+    cut = lambda t: t.cpu().numpy()[:I]
+    kcnt = cut(E.kcnt)
+    held = np.arange(k)[None, None, :] < kcnt[:, :, None]
+    return dict(rows=rows, cols=cols, sim=sim, mutu=mutu, nij=nij, info=S.info.cpu().numpy(), uavg=S.u_avg.cpu().numpy()[:U],
+                bb=cut(E.bb), cls=cut(E.cls), kcnt=kcnt, kcol=np.where(held, cut(E.kcol), -1), kval=np.where(held[..., None], cut(E.kval), 0.0),      # (kval: [I][2][k][3])
+                n_paths=E.n_paths, n_out=E.n_out, n_cand=cut(E.n_cand), top_end=cut(E.top_end), top_val=cut(E.top_val),
+                lists=_xsim_lists(E, I), n_top=cut(n_top), choice=cut(choice), map=cut(mp), user=G.user.cpu().numpy(),
+                item=G.item.cpu().numpy(), rating=G.rating.cpu().numpy(), time=G.time.cpu().numpy(),
+                n_target_rows=G.n_target_rows, n_profiles=eng.n_profiles(G))
+
+
+def assert_same_results(got, want, what):
+    assert got.keys() == want.keys(), what
+    for name in got:
+        x, y = got[name], want[name]
+        for xx, yy in (zip(x, y) if isinstance(x, tuple) else [(x, y)]):
+            assert np.array_equal(np.asarray(xx), np.asarray(yy)), (what, name)
+
+
+# (SWEEP_B entry, arguments of Engine.extend, environment): the tiny entry; the entry with stage A's heavy rows, its starts
+# split over dedicated rows as well; the tiny entry with the partitioned rater count, whole buckets of which are empty
+GAPS = [(201, None, {}), (206, dict(chunk=64, n_slots=64), {}), (201, None, {"XMAP_COUNT_PART_MIN": "1"})]
+
+
+def gap_case(seed):
+    """(the SWEEP_B entry, its ratings, the stretched ratings, item map, user map)"""
+    from golden_util import with_gaps
+    cfg, = [c for c in SWEEP_B if c["seed"] == seed]
+    r = sweep_ratings(cfg)
+    return (cfg, r) + with_gaps(r, seed)
+
+
+@pytest.mark.parametrize("seed,ext_kw,env", GAPS, ids=["tiny", "heavy", "tiny-partitioned-count"])
+@pytest.mark.parametrize("method", METHODS)
+def test_index_spaces_with_gaps(dev, method, seed, ext_kw, env, monkeypatch):
+    """Item indices nobody rated and users without ratings, singly and in runs that empty whole waves, blocks, tiles and
+    count buckets (golden_util.with_gaps), as a host that does not compact its ids uploads them: (a) every stage of the
+    stretched input against the oracle, bit for bit; (b) against the engine's own results on the compact input, re-indexed
+    -- pairs, similarities, item info, user averages, bridge flags, classes, knn tables, paths, candidate lists, top-10,
+    choices, replacement map and AlterEgo rows; an unrated item has zero info, no class, no candidate and no replacement,
+    a user without ratings the average 0.0 and no row.  (b) does not involve the oracle."""
+    from golden_util import reindexed
+    cfg, r, g, item_map, user_map = gap_case(seed)
+    assert g.n_items > r.n_items + 4500 and g.n_users > r.n_users + 1470
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    kw = dict(private=(seed % 2 == 0), picks_seed=seed, need=cfg["need"], ext_kw=ext_kw)
+    sim_kw = dict(cfg.get("sim_kw", {}))
+    if env and not sim_kw:
+        sim_kw = dict(slot_target=96)            # (item_sim_tri, the formulation test_keys_larger_than_a_tile forces the count on)
+    res = _check_all_stages(dev, r, method, cfg["k"], **kw, **sim_kw)
+    if ext_kw:
+        assert res[2].units.n_heavy > 0
+    compact = engine_result(*res, r.n_items, r.n_users, cfg["k"])
+    del res
+    stretched = engine_result(*_check_all_stages(dev, g, method, cfg["k"], **kw, **sim_kw), g.n_items, g.n_users, cfg["k"])   # (a)
+    assert_same_results(stretched, reindexed(compact, item_map, user_map, g.n_items, g.n_users), "stretched vs compact")   # (b)
+    assert compact["n_paths"] > 0 and (compact["map"] >= 0).any()

@@ -331,10 +331,12 @@ def test_exact_route_equals_fast_route_on_integers(dev, method, monkeypatch):
 @pytest.mark.parametrize("method", METHODS)
 def test_rating_edges_vs_oracle(dev, method):
     """an item rated only 0 (zero norm: sim 0.0, every pair filtered), negative ratings (negative similarities through the
-    top-k lists and X-Sim), ratings equal to their item's average (the mutuality test is `>=`)"""
+    top-k lists and X-Sim), ratings equal to their item's average (the mutuality test is `>=`).  One user in ten rates in
+    both domains, so a quarter of the items have no neighbour of the other domain and paths start from them (oracle census,
+    cosine | adjusted cosine: 155 455 | 114 456 paths, 189 | 15 220 candidates with a negative X-Sim, 74 | 98 replaced items)"""
     from xmap.engine import synth
     P = _parity()
-    base = synth.make_two_domain(12, 1500, 200, 200, overlap=0.5)
+    base = synth.make_two_domain(12, 1500, 400, 400, overlap=0.1)
     rating = base.rating.astype(np.float32) - np.float32(3.0)          # -2 .. 2
     zero_item = int(np.bincount(base.item).argmax())
     rating[base.item == zero_item] = 0.0
@@ -350,7 +352,7 @@ def test_rating_edges_vs_oracle(dev, method):
         E = eng.extend(S, 5, full=True)
         assert (E.kval.cpu().numpy()[..., 0] < 0).any()
     assert set(flat.tolist()) & set(rows.tolist())
-    P._check_all_stages(dev, r, method, 5)
+    P._check_all_stages(dev, r, method, 5, need=dict(paths=10 ** 4, neg=1, mapped=10))
 
 
 @gpu

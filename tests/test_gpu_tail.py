@@ -613,3 +613,87 @@ def test_tail_lifecycle():
     finally:
         c1.close()
         c2.close()
+
+
+# ------------------------------------------------------------------------------------- 9. index spaces with gaps
+def _tail_results(ctx, r, tu, ti, real, keep=10):
+    """the tail of one upload: the stage-C rows, the profiles and RecommenderSim (rows sorted by column), the neighbour lists
+    (entries behind a list's count: -1 / 0), the predictions"""
+    I, U = r.n_items, len(r.user_ptr) - 1
+    rows = generate(ctx, r)
+    T = rec_sim(ctx, I, U, len(rows["user"]))
+    pair_row = np.repeat(np.arange(I, dtype=np.int64), np.diff(T["row_ptr"]))
+    o = np.lexsort((T["col"], pair_row))
+    for name in ("col", "sim", "ls", "nij"):
+        T[name] = T[name][o]
+    cnt, col, sim, ls = select(ctx, I, keep)
+    held = np.arange(keep)[None, :] < cnt[:, None]
+    nb = (cnt, np.where(held, col, -1), np.where(held, sim, 0.0), np.where(held, ls, 0.0))
+    return rows, T, pair_row, nb, predict(ctx, tu, ti, real, 0.2)
+
+
+def test_tail_on_index_spaces_with_gaps():
+    """xmap_ctx_rec_sim, _rec_select and _predict on an upload whose item and user indices have gaps (golden_util.with_gaps:
+    unrated item indices and users without ratings, singly and in runs of more than a thousand): every result equals the
+    compact upload's, re-indexed.  The input replaces 54 items (SWEEP_B's s206 at the tail driver's k = 5, cosine, private
+    mapping), so the profiles hold rows of replaced items.  (No id strings here: the two tails are compared array by array.)"""
+    from golden_util import check_census, with_gaps
+    from test_gpu_coarse_oracle import Oracle
+    from test_gpu_parity import SWEEP_B, sweep_ratings
+    cfg, = [c for c in SWEEP_B if c["seed"] == 206]
+    r = _few_times(sweep_ratings(cfg))
+    want = Oracle(r, "cosine")
+    try:
+        want.stage_b(5)
+        check_census(want.census(True, None), dict(mapped=50, mapped_rows=1), "the tail's input")
+    finally:
+        want.close()
+    g, item_map, user_map = with_gaps(r, 206)
+    I, U, I2, U2 = r.n_items, r.n_users, g.n_items, g.n_users
+    rng = np.random.default_rng(206)
+    n = 1500
+    tu, ti = rng.integers(0, U, n), rng.integers(r.n_src_items, I, n)
+    ti[::17] = 0                                     # a source item: no neighbour list
+    tu[5::23] = -1                                   # a user the upload does not know
+    real = rng.integers(1, 6, n).astype(np.float64)
+    tu2, ti2 = np.where(tu >= 0, user_map[np.maximum(tu, 0)], -1), item_map[ti]
+    tu2[7::29] = user_map[0] - 1                     # users without ratings: of the run at the start, the middle and the end
+    tu2[8::29] = user_map[U // 2] - 1
+    tu2[9::29] = U2 - 1
+    tu[7::29] = tu[8::29] = tu[9::29] = -1           # (on the compact side: unknown users)
+    c1, c2 = Ctx(), Ctx()
+    try:
+        rows, T, pair_row, nb, P = _tail_results(c1, r, tu, ti, real)
+        rows2, T2, pair_row2, nb2, P2 = _tail_results(c2, g, tu2, ti2, real)
+    finally:
+        c1.close()
+        c2.close()
+    same = lambda a, b: np.array_equal(np.asarray(a), np.asarray(b))
+    items = lambda a: np.where(a >= 0, item_map[np.maximum(a, 0)], -1)
+
+    def scatter(a, m, n, fill=0):
+        out = np.full((n,) + a.shape[1:], fill, a.dtype)
+        out[m] = a
+        return out
+    # stage C's rows and the profiles
+    assert rows2["n_target_rows"] == rows["n_target_rows"] and len(rows["user"]) > rows["n_target_rows"]
+    assert same(rows2["user"], user_map[rows["user"]]) and same(rows2["item"], item_map[rows["item"]])
+    assert same(rows2["rating"], rows["rating"]) and same(rows2["time"], rows["time"]) and same(rows2["choice"], scatter(items(rows["choice"]), item_map, I2, -1))
+    assert same(np.diff(T2["ptr"]), scatter(np.diff(T["ptr"]), user_map, U2))
+    assert same(T2["item"], item_map[T["item"]]) and same(T2["rating"], T["rating"]) and same(T2["time"], T["time"])
+    # RecommenderSim
+    assert len(T["col"]) > 1000
+    assert same(np.diff(T2["row_ptr"]), scatter(np.diff(T["row_ptr"]), item_map, I2))
+    assert same(pair_row2, item_map[pair_row]) and same(T2["col"], item_map[T["col"]])
+    for name in ("sim", "ls", "nij"):
+        assert same(T2[name], T[name]), name
+    for name in ("avg", "norm"):
+        assert same(T2[name], scatter(T[name], item_map, I2)), name
+    # neighbour lists
+    assert nb[0].max() == 10
+    assert same(nb2[0], scatter(nb[0], item_map, I2)) and same(nb2[1], scatter(items(nb[1]), item_map, I2, -1))
+    assert same(nb2[2], scatter(nb[2], item_map, I2)) and same(nb2[3], scatter(nb[3], item_map, I2))
+    # predictions: the same numbers, status and sums
+    assert int((P[2] == 0).sum()) > 500 and int((P[2] == 1).sum()) > 50
+    for a, b, what in zip(P2, P, ("plain", "decayed", "status", "mae", "max_now")):
+        assert same(a, b), what

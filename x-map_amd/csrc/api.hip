@@ -393,10 +393,59 @@ static bool plain_sums_exact(int64_t U, int64_t nnz, const float *rating) {
     return (uint64_t)U <= (1ull << 53) / m2;
 }
 
+/* What the stages assume of an upload and never test themselves (host code, O(nnz), no device call): profile lengths are
+ * differences of user_ptr, stage A sizes its tables for profiles without a repeated item (dups = 0; only RecommenderSim's
+ * AlterEgo profiles may hold one: allow_repeats), suffix_cls is a shift count of stage B.  The first offending position is
+ * named in xmap_last_error().  stamp[i] = the last position of item i: a repeat is a stamp inside the running profile. */
+int xmap_check_ratings(int64_t n_users, int32_t n_items, const int64_t *user_ptr, const int32_t *item, const int32_t *prefix_cls,
+                       const int32_t *suffix_cls, int32_t allow_repeats) {
+    XM_ARG(user_ptr && n_users >= 0 && n_items >= 0);
+    if (user_ptr[0] != 0) { set_error("ratings: user_ptr[0] = %lld, not 0", (long long)user_ptr[0]); return XMAP_ERR_ARG; }
+    for (int64_t u = 0; u < n_users; u++)
+        if (user_ptr[u + 1] < user_ptr[u]) {
+            set_error("ratings: user_ptr[%lld] < user_ptr[%lld]", (long long)u + 1, (long long)u);
+            return XMAP_ERR_ARG;
+        }
+    const int64_t nnz = user_ptr[n_users];
+    if (nnz >= 2147483647ll) { set_error("ratings: user_ptr[%lld] = %lld does not fit int32", (long long)n_users, (long long)nnz); return XMAP_ERR_ARG; }
+    XM_ARG(nnz == 0 || item);
+    for (int64_t e = 0; e < nnz; e++)
+        if (item[e] < 0 || item[e] >= n_items) {
+            set_error("ratings: item[%lld] = %d outside [0, %d)", (long long)e, (int)item[e], (int)n_items);
+            return XMAP_ERR_ARG;
+        }
+    if (!allow_repeats && nnz > 0) {
+        std::vector<int64_t> stamp;
+        try { stamp.assign((size_t)n_items, -1); }
+        catch (const std::bad_alloc &) { set_error("ratings: out of host memory for %d stamps", (int)n_items); return XMAP_ERR_CAPACITY; }
+        for (int64_t u = 0; u < n_users; u++)
+            for (int64_t e = user_ptr[u]; e < user_ptr[u + 1]; e++) {
+                int64_t &s = stamp[item[e]];
+                if (s >= user_ptr[u]) {
+                    set_error("ratings: user %lld holds item %d twice (item[%lld] and item[%lld])", (long long)u, (int)item[e],
+                              (long long)s, (long long)e);
+                    return XMAP_ERR_ARG;
+                }
+                s = e;
+            }
+    }
+    for (int32_t i = 0; suffix_cls && i < n_items; i++)
+        if (suffix_cls[i] < 0 || suffix_cls[i] >= 32) {
+            set_error("ratings: suffix_cls[%d] = %d outside [0, 32)", (int)i, (int)suffix_cls[i]);
+            return XMAP_ERR_ARG;
+        }
+    for (int32_t i = 0; prefix_cls && i < n_items; i++)
+        if (prefix_cls[i] < 0) { set_error("ratings: prefix_cls[%d] = %d is negative", (int)i, (int)prefix_cls[i]); return XMAP_ERR_ARG; }
+    return XMAP_OK;
+}
+
 int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const int64_t *user_ptr, const int32_t *item,
                             const float *rating, const int64_t *time, const int32_t *prefix_cls, const int32_t *suffix_cls,
                             const uint32_t *contains_mask, const uint8_t *flags) {
     XM_ARG(c && user_ptr && prefix_cls && suffix_cls && contains_mask && flags && n_users >= 0 && n_items >= 0);
+    // a refused upload leaves the context as it was: nothing is dropped, allocated or launched before the input has passed
+    XM_TRY(xmap_check_ratings(n_users, n_items, user_ptr, item, prefix_cls, suffix_cls, 0));
+    XM_ARG(user_ptr[n_users] == 0 || (rating && time));
     XM_HIP(hipSetDevice(c->device));
     drop_tail(c);
     drop_fold(c);
@@ -404,8 +453,6 @@ int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_ratings.release();
     c->have_sim = c->have_ext = c->have_gen = false;
     const int64_t nnz = user_ptr[n_users];
-    XM_ARG(nnz >= 0 && nnz < 2147483647ll && (nnz == 0 || (item && rating && time)));
-    for (int64_t e = 0; e < nnz; e++) XM_ARG(item[e] >= 0 && item[e] < n_items);
     xmap_ratings &R = c->R;
     memset(&R, 0, sizeof(R));
     R.n_users = n_users; R.n_items = n_items; R.nnz = nnz;

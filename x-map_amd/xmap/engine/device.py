@@ -35,10 +35,21 @@ class DeviceRatings(object):
 
     def __init__(self, user_ptr, item, rating, time, n_items, attrs, device="cuda:0", rating64=False):
         """rating64: also keep the ratings as fp64 (RecommenderSim runs over AlterEgo rows, whose ratings are np.float64 means,
-        reference core/generator.py:123-138 -> core/recommenderSim.py:64-133; the three stages of the path read float32)"""
+        reference core/generator.py:123-138 -> core/recommenderSim.py:64-133; the three stages of the path read float32).
+        The arrays are checked on the host before anything is uploaded (xmap_check_ratings, the coarse upload's check):
+        ValueError naming the first offending position.  A trainRDD holds one rating per (user, item); only the AlterEgo
+        profiles (rating64) may hold an item twice -- RecommenderSim sizes its tables for that, stage A does not."""
         self.device = torch.device(device)
         user_ptr = np.ascontiguousarray(user_ptr, np.int64)
         item = np.ascontiguousarray(item, np.int32)
+        if user_ptr.ndim != 1 or len(user_ptr) < 1:
+            raise ValueError("user_ptr must hold n_users + 1 entries")
+        prefix_cls, suffix_cls = [np.ascontiguousarray(a, np.int32) for a in attrs[:2]]
+        if len(prefix_cls) != int(n_items) or len(suffix_cls) != int(n_items) or len(item) < max(int(user_ptr[-1]), 0):
+            raise ValueError("prefix_cls / suffix_cls must hold n_items entries, item user_ptr[-1]")
+        if abi.lib.xmap_check_ratings(len(user_ptr) - 1, int(n_items), user_ptr.ctypes.data, item.ctypes.data, prefix_cls.ctypes.data,
+                                      suffix_cls.ctypes.data, 1 if rating64 else 0):
+            raise ValueError((abi.lib.xmap_last_error() or b"").decode())
         r64 = np.ascontiguousarray(rating, np.float64) if rating64 else None
         rating = np.ascontiguousarray(rating, np.float32)
         time = np.ascontiguousarray(time, np.int64)
@@ -51,11 +62,7 @@ class DeviceRatings(object):
         # lengths, so the engine sizes its pair buffers and unit arrays without asking the device
         d = np.diff(user_ptr)
         self.half_contrib = int((d * (d - 1) // 2).sum())
-        if self.nnz >= 2 ** 31 - 1:
-            raise ValueError("nnz must fit int32")
-        if self.nnz and (item.min() < 0 or item.max() >= self.n_items):
-            raise ValueError("item index out of range")
-        prefix_cls, suffix_cls, contains_mask, flags = attrs
+        contains_mask, flags = attrs[2:]
         d = self.device
         t = torch.from_numpy
         self.user_ptr = t(user_ptr).to(d)
@@ -67,8 +74,8 @@ class DeviceRatings(object):
         self.item_user = torch.zeros(max(self.nnz, 1), dtype=torch.int32, device=d)
         self.item_rating = torch.zeros(max(self.nnz, 1), dtype=torch.float32, device=d)
         self.csc_ready = False
-        self.prefix_cls = t(np.ascontiguousarray(prefix_cls, np.int32)).to(d)
-        self.suffix_cls = t(np.ascontiguousarray(suffix_cls, np.int32)).to(d)
+        self.prefix_cls = t(prefix_cls).to(d)
+        self.suffix_cls = t(suffix_cls).to(d)
         self.contains_mask = t(np.ascontiguousarray(contains_mask, np.uint32).view(np.int32)).to(d)
         self.flags = t(np.ascontiguousarray(flags, np.uint8)).to(d)
         self.c = abi.Ratings(self.n_users, self.n_items, self.nnz,

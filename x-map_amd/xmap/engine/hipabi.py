@@ -94,7 +94,7 @@ EXPORTS = [
     "xmap_reverse_fill", "xmap_topc_from_lists", "xmap_path_weights", "xmap_extend_paths", 
     "xmap_mid_rows_count", "xmap_mid_rows_place", "xmap_edge_ranges", "xmap_end_universe", "xmap_extend_cols", "xmap_extend_cols_slots", "xmap_nb_index", "xmap_path_plan", "xmap_end_order", "xmap_dense_normalize", "xmap_dense_layout", "xmap_dense_topk", "xmap_rec_select", "xmap_predict", "xmap_rec_profiles", "xmap_predict_rows", "xmap_mae", "xmap_topn_rows", "xmap_eval_users", "xmap_topn_eval", "xmap_select_map", "xmap_alterego_count", "xmap_alterego_fill", "xmap_foldin_count", "xmap_foldin_fill", "xmap_union_count", "xmap_union_fill",
     "xmap_feed_text", "xmap_feed_texts", "xmap_feed_merge", "xmap_feed_sizes", "xmap_feed_arrays", "xmap_feed_ids", "xmap_feed_free",
-    "xmap_ctx_upload_feed", "xmap_feed_format", "xmap_ctx_create", "xmap_ctx_destroy", "xmap_ctx_upload_ratings", "xmap_ctx_item_sim", "xmap_ctx_sim_download", "xmap_ctx_extend",
+    "xmap_ctx_upload_feed", "xmap_feed_format", "xmap_ctx_create", "xmap_ctx_destroy", "xmap_check_ratings", "xmap_ctx_upload_ratings", "xmap_ctx_item_sim", "xmap_ctx_sim_download", "xmap_ctx_extend",
     "xmap_ctx_ext_download", "xmap_ctx_ext_lists", "xmap_ctx_candidates", "xmap_ctx_generate", "xmap_ctx_gen_download",
     "xmap_ctx_rec_sim", "xmap_ctx_rec_profiles_download", "xmap_ctx_rec_download", "xmap_ctx_rec_select", "xmap_ctx_rec_set_neighbors",
     "xmap_ctx_rec_neighbors_download", "xmap_ctx_predict", "xmap_ctx_recommend", "xmap_ctx_evaluate_topn",
