@@ -6,12 +6,15 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
 metrics of the top-20 lists against the held-out ratings (xmap.engine.session.evaluate_topn), then the top 5 target items of
 three test users (xmap.engine.session.recommend_topn).
+
+--explain (with --device-tail): under each of those lists, why every item is there (the explain= option of recommend_topn: the
+three strongest evidence entries of its score with their share, and the user's own ratings each AlterEgo row came from).
 
 --fold-in (with --device-tail): five test users are kept out of training altogether, as users who arrive afterwards would be.
 The model is trained without them; their ratings (the source domain's, for a user known only there) are then folded in
@@ -80,6 +83,7 @@ def main(argv=None):
     ap.add_argument("--private", action="store_true")
     ap.add_argument("--device-tail", action="store_true")
     ap.add_argument("--fold-in", action="store_true")
+    ap.add_argument("--explain", action="store_true")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -148,9 +152,14 @@ def main(argv=None):
                 c, m["users"], m["hit_rate"], m["precision"], m["recall"], m["ndcg"], m["map"], m["mrr"], m["coverage"]))
         # what the library is for: target-domain items for users known through their source-domain ratings
         top = session.recommend_topn(alterEgo_profile, [uid for uid, _ in testRDD.take(3)], rc["calculate_xmap_weighting"],
-                                     rc["mapping_range"], rc["decay_alpha"], 5)
-        for uid, lst in top.collect():
+                                     rc["mapping_range"], rc["decay_alpha"], 5, explain=(3, 4) if args.explain else None)
+        for q, (uid, lst) in enumerate(top.collect()):
             print("top 5 for %s:" % uid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "no evidence")
+            for iid, entries in (top.explanations[q][1] if args.explain else []):
+                print("  %s, because of" % iid)
+                for nid, s, rating, share, sources, n_all in entries:
+                    cited = ", ".join("%s rated %s" % (sid, sr) for sid, sr, _ in sources) + (", ..." if n_all > len(sources) else "")
+                    print("    %+.3f  %s (similarity %.3f, your AlterEgo rating %.2f)  <-  %s" % (share, nid, s, rating, cited))
     if late:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         top = timed("fold_in_topn", session.recommend_topn_profiles, alterEgo_profile, late, w, k, alpha, 5)

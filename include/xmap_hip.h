@@ -617,6 +617,49 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                    int64_t *h_stats /* host, [4] or NULL: candidates scored, candidates dropped (status 2),
                                        largest `now`, largest candidate count of one query */);
 
+/* ---- explanation of a recommendation (csrc/stage_e_explain.hip): WHY the score of a (user, item) pair is what it is -- the
+ * strongest evidence entries of the score, and for each of those AlterEgo rows the raw ratings stage C made it from.
+ * xmap_explain_rows: n_pairs pairs (typically the lists of xmap_topn_rows) against the arrays of xmap_predict_rows, in its
+ *   order.  The pair body is the prediction's own (csrc/predict_rows.h, one more compile-time mode), so the evidence list of a
+ *   pair -- for l in range(min(nb_cnt[i], keep)), nb = nb_col[i][l] (outside [0, n_items): skipped), for p in
+ *   range(prof_ptr[u], prof_ptr[u + 1]) with prof_item[p] == nb: entry q with slot l, row p, e0 = s (prof_rating[p] -
+ *   item_avg[nb]), e1 = |s|, time prof_time[p]; n entries --, p1, d1, now, the time ranks, the decay weight wt_q =
+ *   wtab[now - rank_q] and the status are exactly what xmap_predict_rows computes.
+ *   share of entry q: rank_by 0: e0[q] / p1; rank_by 1: (e0[q] * wt_q) / d1 -- the product rounded first (the same product the
+ *   decayed sum adds), then one division.  The shares are what an entry adds to score - item_avg[i]; their rounded sum is NOT
+ *   required to reproduce that difference bit for bit (the score divides the sum once, the shares divide every term).
+ *   ranking: |share| descending, compared as numbers; ties to the smaller evidence index q (list order, then profile order: the
+ *   index before the time sort, also for rank_by 1).  The first min(n_ev, n) entries are reported, 1 <= n_ev <= 16.
+ *   outputs per pair t (device): ex_status[t] = the status xmap_predict_rows gives the pair with the same table (0 predicted, 1
+ *   no neighbour list, 2 the Python statement raises or now > n_w); ex_total[t] = n (0 when the status is not 0; status 0 with
+ *   n = 0 is legal: the score is item_avg[i]); ex_cnt[t] = min(n_ev, n); ex_score[t] = the unrounded score of rank_by (0.0 when
+ *   the status is not 0); ex_row [t][n_ev] = absolute index into the profile arrays (-1 behind the count); ex_slot [t][n_ev] =
+ *   the list position l (-1 behind the count); ex_share [t][n_ev] (0.0 behind the count).  *h_max_now as xmap_predict_rows.
+ *   No limit on n (more than 128 entries: the second launch, as the prediction).  A pure function of the inputs.  Syncs.
+ * xmap_explain_sources: the provenance of the reported rows through stage C (k_alterego_grp), which writes a user's profile as
+ *   its cnt_t[u] pass-through rows (the raw entries with flags[item] & 2, in raw order), then one row per distinct
+ *   map_src2tgt[item] >= 0 in first-seen order carrying the fp64 mean of the group's ratings.  For row p of user u, k = p -
+ *   prof_ptr[u]: k < cnt_t[u]: the source is the k-th raw entry of u with flags[item] & 2, src_total = 1; otherwise the sources
+ *   are all raw entries e of u with map_src2tgt[raw_item[e]] == prof_item[p], in raw order, src_total their number (the row's
+ *   rating is the left-to-right fp64 mean of their fp32 ratings).  Pass cnt_t [n_users] OR off_t [n_users + 1] (its exclusive
+ *   scan, as xmap_alterego_fill takes it): exactly one of the two, the other NULL.  raw_ptr [n_users + 1] / raw_item: the raw
+ *   profiles the rows were made from (the upload's CSR; a fold-in batch's CSR with its cnt_t).
+ *   outputs per (pair, entry): src_total [t][n_ev] (0 behind ex_cnt[t]; -1 for an ex_row outside [prof_ptr[u], prof_ptr[u + 1])
+ *   or a pair_user outside [0, n_users): nothing is indexed), src_pos [t][n_ev][n_src] = absolute positions of the first
+ *   min(n_src, src_total) sources in the raw arrays (-1 behind that), 1 <= n_src <= 8.  A raw item outside [0, n_items) matches
+ *   nothing.  One wave per (pair, entry), no atomics.  Does not sync. */
+int xmap_explain_rows(void *stream, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,
+                      int32_t n_ev, int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                      const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                      const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *ex_status,
+                      int32_t *ex_total, int32_t *ex_cnt, double *ex_score, int64_t *ex_row, int32_t *ex_slot, double *ex_share,
+                      int32_t *h_max_now);
+int xmap_explain_sources(void *stream, int64_t n_pairs, const int32_t *pair_user, int32_t n_ev, const int32_t *ex_cnt,
+                         const int64_t *ex_row, int64_t n_users, int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item,
+                         const int32_t *cnt_t /*[n_users] or NULL*/, const int64_t *off_t /*[n_users + 1] or NULL: exactly one of the two*/,
+                         const int64_t *raw_ptr, const int32_t *raw_item, const uint8_t *flags, const int32_t *map_src2tgt,
+                         int32_t n_src, int32_t *src_total, int64_t *src_pos);
+
 /* ---- hold-out evaluation of the top-N lists (csrc/stage_e_eval.hip): what xmap_mae is to xmap_predict_rows.  The lists stay
  * where xmap_topn_rows wrote them; the held-out (user, item, rating) pairs are the ones xmap_ctx_predict takes.
  * xmap_eval_users: held-out pairs -> the users worth ranking for.  A pair is IGNORED if user is outside [0, U), item outside
@@ -830,6 +873,20 @@ int xmap_union_fill(void *stream, int32_t n_parts, const xmap_union_part *parts 
  *                             _predict, _recommend and _evaluate_topn work as on a two-domain context; the stage entries,
  *                             xmap_ctx_gen_download and the fold-in entries return XMAP_ERR_ARG.  A later xmap_ctx_union into
  *                             dst or xmap_ctx_upload_ratings drops the union and its tail.  dst may not be one of src
+ * Explanations (needs the same stages as xmap_ctx_predict and is dropped by the same calls):
+ *   xmap_ctx_explain        : xmap_explain_rows over the resident profiles, lists and averages, and with n_src > 0
+ *                             xmap_explain_sources over the upload's own CSR: host arrays in and out.  n_pairs pairs (user,
+ *                             item), rank_by 0 / 1, 1 <= n_ev <= 16, 0 <= n_src <= 8, wtab / n_w / *max_now as xmap_ctx_predict;
+ *                             ex_status / ex_total / ex_cnt / ex_score [n_pairs], ex_row / ex_slot / ex_share [n_pairs][n_ev];
+ *                             ex_row indexes the profiles of xmap_ctx_rec_profiles_download.  n_src > 0: src_total
+ *                             [n_pairs][n_ev], src_pos [n_pairs][n_ev][n_src] = positions in the item / rating / time arrays of
+ *                             the UPLOAD, which the host holds: it can print "this item, because of these ratings of yours"
+ *                             without downloading anything else; n_src == 0: both may be NULL and are not written.  On a union
+ *                             context n_src == 0 works (evidence only) and n_src > 0 is XMAP_ERR_ARG: a union has one map and one
+ *                             raw profile per part.  n_pairs == 0 is valid.  Argument errors start no device work
+ *   xmap_ctx_foldin_explain : the same over the fold-in batch: pair_user = indices into the batch, ex_row indexes the profiles of
+ *                             xmap_ctx_foldin_download, src_pos the batch's own item / rating / time arrays (xmap_ctx_foldin
+ *                             keeps the batch's raw ptr / item and its pass-through counts on the device, swapped in on success)
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -909,6 +966,15 @@ int xmap_ctx_foldin_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_u
                             int32_t *max_now);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
+int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,
+                     int32_t n_ev, int32_t n_src, const double *wtab, int32_t n_w, int32_t *ex_status, int32_t *ex_total,
+                     int32_t *ex_cnt, double *ex_score, int64_t *ex_row, int32_t *ex_slot, double *ex_share,
+                     int32_t *src_total /*[n_pairs][n_ev]; NULL with n_src == 0*/,
+                     int64_t *src_pos /*[n_pairs][n_ev][n_src]; NULL with n_src == 0*/, int32_t *max_now /*or NULL*/);
+int xmap_ctx_foldin_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,
+                            int32_t n_ev, int32_t n_src, const double *wtab, int32_t n_w, int32_t *ex_status, int32_t *ex_total,
+                            int32_t *ex_cnt, double *ex_score, int64_t *ex_row, int32_t *ex_slot, double *ex_share,
+                            int32_t *src_total, int64_t *src_pos, int32_t *max_now);
 
 #ifdef __cplusplus
 }

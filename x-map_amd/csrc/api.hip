@@ -10,6 +10,7 @@
 //                                                                                  | xmap_ctx_evaluate_topn (top-N against held-out pairs)
 //   fold-in, for profiles that were not rows of the upload:  xmap_ctx_generate -> xmap_ctx_foldin (the batch's AlterEgo profiles)
 //                     -> [rec_sim -> rec_select] -> xmap_ctx_foldin_predict | xmap_ctx_foldin_recommend (the same kernels, the batch's rows)
+//   explanations of (user, item) pairs: xmap_ctx_explain | xmap_ctx_foldin_explain, wherever xmap_ctx_predict | xmap_ctx_foldin_predict work
 //   xmap_ctx_*_download copy results into caller-allocated host buffers whose sizes the stage call reported.
 //
 // Everything below is orchestration of the kernels' own entry points (include/xmap_hip.h): buffer sizes, prefix sums,
@@ -70,6 +71,7 @@ struct xmap_ctx {
     int64_t *g_time = nullptr;
     int64_t n_rows = 0, n_target_rows = 0;
     int64_t *g_off_t = nullptr, *g_off_m = nullptr;     // per-user offsets of the two row segments (exclusive scans, [U+1])
+                                                        // (g_off_t also tells an explanation which rows of a profile are pass-through rows)
     int32_t *g_map = nullptr;                           // the replacement map (source item -> target item, -1: none) in p_gen
     // the recommender tail: profiles of the AlterEgo rows, RecommenderSim over them, neighbour lists
     Pool p_rec, p_nb;
@@ -91,6 +93,9 @@ struct xmap_ctx {
     int64_t *f_ptr = nullptr, *f_time = nullptr;
     int32_t *f_item = nullptr;
     double *f_rating = nullptr;
+    // the batch's raw CSR and pass-through counts, for the sources of an explanation (xmap_ctx_foldin_explain)
+    int64_t *f_raw_ptr = nullptr;
+    int32_t *f_raw_item = nullptr, *f_cnt_t = nullptr;
     // multi-domain: this context holds the union of other contexts' AlterEgo rows as user-major profiles (xmap_ctx_union) and
     // nothing of the stages; have_gen is set, n_rows = the union's rows, R carries the union's sizes and all-target flags
     Pool p_union;
@@ -995,11 +1000,12 @@ int xmap_ctx_foldin(xmap_ctx *c, int64_t n_new, const int64_t *ptr, const int32_
     int32_t *d_item, *cnt_t, *cnt_m, *f_item;
     float *d_rating;
     double *f_rating;
-    XM_TRY(h2d(tmp, &d_ptr, ptr, (size_t)n_new + 1, c->st));
-    XM_TRY(h2d(tmp, &d_item, item, (size_t)nnz, c->st));
+    // the raw ptr / item and the pass-through counts stay with the batch: the sources of an explanation walk them
+    XM_TRY(h2d(fresh, &d_ptr, ptr, (size_t)n_new + 1, c->st));
+    XM_TRY(h2d(fresh, &d_item, item, (size_t)nnz, c->st));
     XM_TRY(h2d(tmp, &d_rating, rating, (size_t)nnz, c->st));
     XM_TRY(h2d(tmp, &d_time, time, (size_t)nnz, c->st));
-    XM_TRY(dalloc(tmp, &cnt_t, (size_t)n_new, c->st)); XM_TRY(dalloc(tmp, &cnt_m, (size_t)n_new, c->st));
+    XM_TRY(dalloc(fresh, &cnt_t, (size_t)n_new, c->st)); XM_TRY(dalloc(tmp, &cnt_m, (size_t)n_new, c->st));
     XM_TRY(dalloc(fresh, &f_ptr, (size_t)n_new + 1, c->st));
     XM_TRY(xmap_foldin_count(c->st, n_new, nnz, d_ptr, d_item, I, c->R.flags, c->g_map, cnt_t, cnt_m, f_ptr, h));
     XM_TRY(dalloc(fresh, &f_item, (size_t)h[0], c->st)); XM_TRY(dalloc(fresh, &f_rating, (size_t)h[0], c->st));
@@ -1011,6 +1017,7 @@ int xmap_ctx_foldin(xmap_ctx *c, int64_t n_new, const int64_t *ptr, const int32_
     c->p_fold.ptrs.swap(fresh.ptrs);
     c->f_users = n_new; c->f_rows = h[0];
     c->f_ptr = f_ptr; c->f_item = f_item; c->f_rating = f_rating; c->f_time = f_time;
+    c->f_raw_ptr = d_ptr; c->f_raw_item = d_item; c->f_cnt_t = cnt_t;
     c->have_fold = true;
     if (counts) { counts[0] = h[0]; counts[1] = h[1]; counts[2] = h[2]; }
     return XMAP_OK;
@@ -1042,6 +1049,87 @@ int xmap_ctx_foldin_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_use
     XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
     return predict_over(c, foldin_profiles(c), n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
                         max_now);
+}
+
+// ---- explanations -------------------------------------------------------------------------------------------------------
+
+// the raw profiles a set of AlterEgo profiles was made from, with the count (or the scan) of each profile's pass-through rows
+struct RawProfiles {
+    const int64_t *ptr;
+    const int32_t *item, *cnt_t;
+    const int64_t *off_t;
+};
+
+static int explain_over(xmap_ctx *c, const Profiles &P, const RawProfiles &W, int64_t n_pairs, const int32_t *pair_user,
+                        const int32_t *pair_item, int32_t rank_by, int32_t n_ev, int32_t n_src, const double *wtab, int32_t n_w,
+                        int32_t *ex_status, int32_t *ex_total, int32_t *ex_cnt, double *ex_score, int64_t *ex_row, int32_t *ex_slot,
+                        double *ex_share, int32_t *src_total, int64_t *src_pos, int32_t *max_now) {
+    XM_ARG(n_ev >= 1 && n_ev <= 16);
+    XM_ARG(n_src >= 0 && n_src <= 8);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_pairs >= 0 && (n_pairs == 0 || (pair_user && pair_item)));
+    XM_ARG(n_pairs == 0 || (ex_status && ex_total && ex_cnt && ex_score && ex_row && ex_slot && ex_share));
+    XM_ARG(n_pairs == 0 || n_src == 0 || (src_total && src_pos));
+    if (n_src > 0 && c->is_union) {
+        set_error("explain with n_src > 0 on a union context: a union of AlterEgo rows has one replacement map and one raw profile "
+                  "per part, so a row has no single source; call with n_src = 0 (evidence only)");
+        return XMAP_ERR_ARG;
+    }
+    XM_HIP(hipSetDevice(c->device));
+    if (max_now) *max_now = 0;
+    if (n_pairs == 0) return XMAP_OK;
+    ScratchPool tmp;
+    int32_t *d_user, *d_item, *d_status, *d_total, *d_cnt, *d_slot, *d_stotal = nullptr;
+    int64_t *d_row, *d_spos = nullptr;
+    double *d_w, *d_score, *d_share;
+    const size_t n = (size_t)n_pairs, m = n * (size_t)n_ev;
+    XM_TRY(h2d(tmp, &d_user, pair_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_item, pair_item, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_status, n, c->st)); XM_TRY(dalloc(tmp, &d_total, n, c->st)); XM_TRY(dalloc(tmp, &d_cnt, n, c->st));
+    XM_TRY(dalloc(tmp, &d_score, n, c->st));
+    XM_TRY(dalloc(tmp, &d_row, m, c->st)); XM_TRY(dalloc(tmp, &d_slot, m, c->st)); XM_TRY(dalloc(tmp, &d_share, m, c->st));
+    XM_TRY(xmap_explain_rows(c->st, n_pairs, d_user, d_item, rank_by, n_ev, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col,
+                             c->nb_sim, P.ptr, P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_status, d_total, d_cnt, d_score, d_row,
+                             d_slot, d_share, max_now));
+    if (n_src > 0) {
+        XM_TRY(dalloc(tmp, &d_stotal, m, c->st)); XM_TRY(dalloc(tmp, &d_spos, m * (size_t)n_src, c->st));
+        XM_TRY(xmap_explain_sources(c->st, n_pairs, d_user, n_ev, d_cnt, d_row, P.n_users, c->R.n_items, P.ptr, P.item, W.cnt_t, W.off_t,
+                                    W.ptr, W.item, c->R.flags, c->g_map, n_src, d_stotal, d_spos));
+        XM_TRY(d2h(src_total, (const int32_t *)d_stotal, m, c->st));
+        XM_TRY(d2h(src_pos, (const int64_t *)d_spos, m * (size_t)n_src, c->st));
+    }
+    XM_TRY(d2h(ex_status, (const int32_t *)d_status, n, c->st));
+    XM_TRY(d2h(ex_total, (const int32_t *)d_total, n, c->st));
+    XM_TRY(d2h(ex_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(ex_score, (const double *)d_score, n, c->st));
+    XM_TRY(d2h(ex_row, (const int64_t *)d_row, m, c->st));
+    XM_TRY(d2h(ex_slot, (const int32_t *)d_slot, m, c->st));
+    XM_TRY(d2h(ex_share, (const double *)d_share, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+int xmap_ctx_explain(xmap_ctx *c, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by, int32_t n_ev,
+                     int32_t n_src, const double *wtab, int32_t n_w, int32_t *ex_status, int32_t *ex_total, int32_t *ex_cnt,
+                     double *ex_score, int64_t *ex_row, int32_t *ex_slot, double *ex_share, int32_t *src_total, int64_t *src_pos,
+                     int32_t *max_now) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    const RawProfiles W = c->is_union ? RawProfiles{nullptr, nullptr, nullptr, nullptr}
+                                      : RawProfiles{c->R.user_ptr, c->R.user_item, nullptr, c->g_off_t};
+    return explain_over(c, resident_profiles(c), W, n_pairs, pair_user, pair_item, rank_by, n_ev, n_src, wtab, n_w, ex_status, ex_total,
+                        ex_cnt, ex_score, ex_row, ex_slot, ex_share, src_total, src_pos, max_now);
+}
+
+int xmap_ctx_foldin_explain(xmap_ctx *c, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,
+                            int32_t n_ev, int32_t n_src, const double *wtab, int32_t n_w, int32_t *ex_status, int32_t *ex_total,
+                            int32_t *ex_cnt, double *ex_score, int64_t *ex_row, int32_t *ex_slot, double *ex_share, int32_t *src_total,
+                            int64_t *src_pos, int32_t *max_now) {
+    XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
+    const RawProfiles W{c->f_raw_ptr, c->f_raw_item, c->f_cnt_t, nullptr};
+    return explain_over(c, foldin_profiles(c), W, n_pairs, pair_user, pair_item, rank_by, n_ev, n_src, wtab, n_w, ex_status, ex_total,
+                        ex_cnt, ex_score, ex_row, ex_slot, ex_share, src_total, src_pos, max_now);
 }
 
 // ---- multi-domain: the union of other contexts' AlterEgo rows ----------------------------------------------------------

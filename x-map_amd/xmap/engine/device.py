@@ -1462,7 +1462,11 @@ class Engine(object):
         with self.timed("rec_profiles"):
             check(lib.xmap_rec_profiles(st, i64(U), i64(n), i64(G.n_target_rows), vp(G.off_t), vp(G.off_m), vp(G.user), vp(G.item),
                                         vp(G.rating), vp(tm), vp(ptr), vp(item), vp(rating), vp(time)))
-        return self._profile_view(U, n, ptr, item, rating, time)
+        P = self._profile_view(U, n, ptr, item, rating, time)
+        if getattr(G, "map", None) is not None and int(G.off_t.numel()) == U + 1:
+            # what explain_sources walks: the raw profiles the rows were made from, the scan of the pass-through counts, the map
+            P.sources = (R.user_ptr, R.user_item, None, G.off_t, R.flags, G.map)
+        return P
 
     def _profile_view(self, U, n, ptr, item, rating, time):
         """user-major AlterEgo profiles (ptr [U + 1], item / rating fp64 / time of max(n, 1) entries) as a
@@ -1521,6 +1525,7 @@ class Engine(object):
                                        vp(mp), vp(cnt_t), vp(pptr), vp(pit), vp(pra), vp(pti)))
         P = self._profile_view(B, n, pptr, pit, pra, pti)
         P.counts = tuple(int(x) for x in h)
+        P.sources = (ptr, item, cnt_t, None, R.flags, mp)       # the batch's own raw profiles (explain_sources)
         return P
 
     @staticmethod
@@ -1634,6 +1639,61 @@ class Engine(object):
                                      vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()),
                                      vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
         return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
+
+    def explain(self, P, neighbors, pair_user, pair_item, item_avg, wtab, n_ev, rank_by=0):
+        """Why a pair scores what it scores (xmap_explain_rows, the pair body of predict() in its explain mode): for the (user,
+        item) pairs -- int32 tensors, typically the lists of topn() -- the n_ev (1..16) strongest evidence entries of the
+        unrounded score of rank_by (0 plain, 1 decayed), ranked by |share| descending, evidence order on ties.  P, neighbors,
+        item_avg, wtab as predict() takes them.  Returns (status [T] as predict(), total [T] = evidence entries of the pair,
+        cnt [T] = min(n_ev, total), score [T], row [T][n_ev] int64 = index into P's profile arrays (-1 behind the count), slot
+        [T][n_ev] = position in the item's neighbour list (-1), share [T][n_ev] = what the entry adds to score - item_avg
+        (0.0), max_now)."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        T, n_ev = int(pair_user.numel()), int(n_ev)
+        if not 1 <= n_ev <= abi.EXPLAIN_MAX_EV:
+            raise ValueError("n_ev = %d: an explanation reports 1 .. %d entries" % (n_ev, abi.EXPLAIN_MAX_EV))
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        T1 = max(T, 1)
+        status, total, n_rep = [self._empty(T1, torch.int32) for _ in range(3)]
+        score = self._empty(T1, torch.float64)
+        row = self._empty((T1, n_ev), torch.int64)
+        slot = self._empty((T1, n_ev), torch.int32)
+        share = self._empty((T1, n_ev), torch.float64)
+        h = C.c_int32(0)
+        with self.timed("explain_rows"):
+            check(lib.xmap_explain_rows(st, i64(T), vp(pair_user.contiguous()), vp(pair_item.contiguous()), i32(rank_by), i32(n_ev),
+                                        i64(P.n_users), i32(P.n_items), i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr),
+                                        vp(P.user_item), vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab),
+                                        i32(wtab.numel()), vp(status), vp(total), vp(n_rep), vp(score), vp(row), vp(slot), vp(share),
+                                        C.byref(h)))
+        return status[:T], total[:T], n_rep[:T], score[:T], row[:T], slot[:T], share[:T], int(h.value)
+
+    def explain_sources(self, P, pair_user, ex_cnt, ex_row, n_src, sources=None):
+        """The provenance of explained rows through stage C (xmap_explain_sources): for every reported row of explain() the raw
+        ratings of the user it was made from -- the one raw entry of a pass-through row, the group of raw entries a mapped row
+        averages.  P as explain() took it; its .sources (set by alterego_profiles and foldin_profiles) names the raw profiles, or
+        pass sources = (raw_ptr, raw_item, cnt_t or None, off_t or None, flags, map) yourself; the profiles of a union have
+        none (one map and one raw profile per part).  Returns (src_total [T][n_ev] int32: 0 behind the count, -1 for a row
+        outside the user's profile, src_pos [T][n_ev][n_src] int64: positions in the raw item / rating / time arrays, -1 behind
+        min(n_src, src_total)); 1 <= n_src <= 8."""
+        src = sources if sources is not None else getattr(P, "sources", None)
+        if src is None:
+            raise ValueError("these profiles carry no raw profiles to walk (a union of AlterEgo rows has one per part)")
+        raw_ptr, raw_item, cnt_t, off_t, flags, mp = src
+        T, n_src = int(pair_user.numel()), int(n_src)
+        n_ev = int(ex_row.shape[1]) if ex_row.dim() == 2 else 1
+        if not 1 <= n_src <= abi.EXPLAIN_MAX_SRC:
+            raise ValueError("n_src = %d: an explanation reports 1 .. %d sources per entry" % (n_src, abi.EXPLAIN_MAX_SRC))
+        T1 = max(T, 1)
+        src_total = self._empty((T1, n_ev), torch.int32)
+        src_pos = self._empty((T1, n_ev, n_src), torch.int64)
+        with self.timed("explain_sources"):
+            check(lib.xmap_explain_sources(_stream(self.dev), i64(T), vp(pair_user.contiguous()), i32(n_ev), vp(ex_cnt.contiguous()),
+                                           vp(ex_row.contiguous()), i64(P.n_users), i32(P.n_items), vp(P.user_ptr), vp(P.user_item),
+                                           vp(cnt_t), vp(off_t), vp(raw_ptr), vp(raw_item), vp(flags), vp(mp), i32(n_src),
+                                           vp(src_total), vp(src_pos)))
+        return src_total[:T], src_pos[:T]
 
     def eval_users(self, test_user, test_item, test_rating, rel_min, n_users, n_items):
         """The users worth ranking for (xmap_eval_users): held-out pairs as int32 / int32 / fp64 tensors -> (n_rel [U] int32:

@@ -468,21 +468,25 @@ def _predict_records(st, eng2, P, nb, item_avg, uidx, testRDD, alpha):
     return res
 
 
-def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None):
+def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None):
     """Top-N recommendation on the device from an AlterEgoRDD handle: the set-up of recommend (profiles -> RecommenderSim ->
     neighbour lists, or `neighbors`), then for every uid of `users` the n (1..64) best items its own rows give evidence for,
     ranked by the unrounded prediction -- without temporal decay, or with (decay=True, alpha) -- score descending, item id
     ascending on equal scores; items the user already holds are left out unless keep_held (Engine.topn).  Returns a LocalRDD
     of (uid, [(iid, plain, decayed)*]) in the order of `users`; a uid the train set does not know gives (uid, []).  It carries
     .sim_pairs and .item_info like recommend, and .stats = (candidates scored, candidates dropped, largest `now`, largest
-    candidate count of a user)."""
+    candidate count of a user).  explain = n_ev or (n_ev, n_src) (n_src defaults to 4): the result also carries .explanations
+    = [(uid, [(iid, [entry*])*])*], the explanation of exactly the (user, item) pairs of the returned lists in their order,
+    entries as explain() gives them; without it the call returns what it always returned."""
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn")
     idt = st.idt
     uids = list(users.collect()) if hasattr(users, "collect") else list(users)
     uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
-    res = _topn_records(st, eng2, P, nb, item_avg, [uidx.get(uid, -1) for uid in uids], uids, alpha, n, decay, keep_held,
-                        getattr(users, "ctx", None))
+    query = [uidx.get(uid, -1) for uid in uids]
+    res = _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, getattr(users, "ctx", None))
     _tail_dicts(res, st, S, nb)
+    if explain is not None:
+        _explain_lists(res, st, eng2, P, nb, item_avg, query, alpha, decay, explain, (st.ratings, st.times) if hasattr(st, "ratings") else None)
     return res
 
 
@@ -504,6 +508,94 @@ def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_
     out = [(uid, [(iids[item[q, t]], float(plain[q, t]), float(decayed[q, t])) for t in range(cnt[q])]) for q, uid in enumerate(uids)]
     res = LocalRDD(out, ctx)
     res.stats = stats
+    return res
+
+
+def _explain_pairs(st, eng2, P, nb, item_avg, pair_user, pair_item, alpha, n_ev, n_src, decay, raw_host):
+    """what explain and the explain= option share: the pairs (user index of P, item index) -> per pair (status, score, [entry*])
+    with entry = (neighbour iid, sim, the user's AlterEgo rating of it, share, [(source iid, rating, time)*], src_total).
+    raw_host = (ratings, times) by raw position: the caller's objects a source cites.  Profiles without raw profiles (a union)
+    or n_src = 0: evidence only, every entry ends with ([], None)."""
+    import torch
+    idt, dev = st.idt, st.engine.dev
+    iids, I = idt.iids, len(idt.iids)
+    d_u = torch.from_numpy(np.ascontiguousarray(pair_user, np.int32)).to(dev)
+    d_i = torch.from_numpy(np.ascontiguousarray(pair_item, np.int32)).to(dev)
+    T = int(d_u.numel())
+    if T == 0:
+        return []
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        status, total, cnt, score, row, slot, share, max_now = eng2.explain(P, nb, d_u, d_i, item_avg, wtab, int(n_ev), 1 if decay else 0)
+        if max_now <= n_w:
+            break
+        n_w = max_now
+    with_src = int(n_src) > 0 and getattr(P, "sources", None) is not None and raw_host is not None
+    # the neighbour behind a slot and the user's AlterEgo rating of it, gathered on the device
+    at_i = d_i.clamp(0, max(I - 1, 0)).long()[:, None].expand_as(slot)
+    at_s = slot.clamp(min=0).long()
+    e_col, e_sim = nb[1][at_i, at_s].cpu().numpy(), nb[2][at_i, at_s].cpu().numpy()
+    e_rating = P.user_rating64[row.clamp(min=0)].cpu().numpy()
+    if with_src:
+        s_total, s_pos = eng2.explain_sources(P, d_u, cnt, row, int(n_src))
+        s_item = P.sources[1][s_pos.clamp(min=0)].cpu().numpy() if int(P.sources[1].numel()) else None
+        s_total, s_pos = s_total.cpu().numpy(), s_pos.cpu().numpy()
+    status, cnt, score, share = status.cpu().numpy(), cnt.cpu().numpy(), score.cpu().numpy(), share.cpu().numpy()
+    out = []
+    for t in range(T):
+        entries = []
+        for e in range(int(cnt[t])):
+            srcs, n_all = [], None
+            if with_src:
+                n_all = int(s_total[t, e])
+                for k in range(min(max(n_all, 0), int(n_src))):
+                    pos = int(s_pos[t, e, k])
+                    srcs.append((iids[int(s_item[t, e, k])], raw_host[0][pos], raw_host[1][pos]))
+            entries.append((iids[int(e_col[t, e])], float(e_sim[t, e]), float(e_rating[t, e]), float(share[t, e]), srcs, n_all))
+        out.append((int(status[t]), float(score[t]), entries))
+    return out
+
+
+def _explain_lists(res, st, eng2, P, nb, item_avg, query, alpha, decay, explain, raw_host):
+    """.explanations of a top-N result: exactly the (user, item) pairs of its lists, in their order"""
+    n_ev, n_src = (explain if isinstance(explain, (tuple, list)) else (explain, 4))
+    lists = res.collect()
+    iidx = st.idt.iidx
+    pu = [q for q, (_, lst) in zip(query, lists) for _ in lst]
+    pi = [iidx[c[0]] for _, lst in lists for c in lst]
+    got = iter(_explain_pairs(st, eng2, P, nb, item_avg, pu, pi, alpha, n_ev, n_src, decay, raw_host))
+    res.explanations = [(uid, [(c[0], next(got)[2]) for c in lst]) for uid, lst in lists]
+
+
+def explain(alterEgoRDD, pairs, cap, keep, alpha, n_ev=3, n_src=4, decay=False, neighbors=None):
+    """Why an item is (or would be) recommended to a user, on the device: the set-up of recommend, then for every (uid, iid) of
+    `pairs` (an RDD or a list) the n_ev (1..16) strongest evidence entries of the unrounded prediction -- plain, or decayed with
+    decay=True -- and for each of them the user's own raw ratings behind it (Engine.explain, Engine.explain_sources).  Returns a
+    LocalRDD of (uid, iid, score, [entry*]) in the order of `pairs`: entry = (neighbour iid, its similarity to iid, the user's
+    AlterEgo rating of the neighbour, share, [(source iid, rating, time)*], src_total) -- share is what the entry adds to
+    score - item average, entries by |share| descending; the sources are the first n_src (0..8) of the src_total train ratings of
+    the user that stage C made the AlterEgo row from (the row itself for a target item the user rated; the ratings of the
+    source items the replacement map sends to the neighbour otherwise), as the caller passed them.  An item without a neighbour
+    list gives (uid, iid, None, []); a uid or iid the train set does not know is a user without ratings / an item without a
+    list.  On the AlterEgoUnion of union_alterego: evidence without sources ([] and None) -- a union has one replacement map per
+    part.  It carries .sim_pairs and .item_info like recommend."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "explain")
+    if not 0 <= int(n_src) <= 8:
+        raise ValueError("n_src = %d: an explanation reports 0 .. 8 sources per entry" % n_src)
+    idt = st.idt
+    todo = list(pairs.collect()) if hasattr(pairs, "collect") else list(pairs)
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    raw_host = (st.ratings, st.times) if hasattr(st, "ratings") else None
+    got = _explain_pairs(st, eng2, P, nb, item_avg, [uidx.get(p[0], -1) for p in todo], [idt.iidx.get(p[1], -1) for p in todo], alpha,
+                         n_ev, n_src, decay, raw_host)
+    out = []
+    for (uid, iid), (status, score, entries) in zip([(p[0], p[1]) for p in todo], got):
+        if status == 2:
+            raise ZeroDivisionError("explanation of (%r, %r): zero weight sum or non-finite value (the reference raises here)" % (uid, iid))
+        out.append((uid, iid, score if status == 0 else None, entries))
+    res = LocalRDD(out, getattr(pairs, "ctx", None))
+    _tail_dicts(res, st, S, nb)
     return res
 
 
@@ -535,10 +627,12 @@ def _fold_in(st, G, profiles):
     check_float32(ptr, item, rating, [rec[0] for rec in recs], idt.iids)
     order = {t: k for k, t in enumerate(sorted(set(times)))}
     rank = np.fromiter((order[t] for t in times), np.int64, len(times))
-    return st.engine.foldin_profiles(ptr, item, rating.astype(np.float32), rank, G.map), index, unknown
+    F = st.engine.foldin_profiles(ptr, item, rating.astype(np.float32), rank, G.map)
+    F.raw_host = (rating, times)            # the caller's ratings and time objects by batch position (explanations cite them)
+    return F, index, unknown
 
 
-def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None):
+def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None):
     """recommend_topn for users that are not rows of the train set -- a user who arrived after training, a trained user whose
     profile changed: `profiles` is an RDD or list of (uid, [(iid, rating, time)*]) raw profiles, source and target items mixed.
     Each gets its AlterEgo profile with the replacement map behind alterEgoRDD (fold-in: Engine.foldin_profiles) and then the
@@ -546,7 +640,8 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     repeated one raises ValueError; an entry whose iid the train set does not know is dropped and counted in .unknown_items; a
     rating float32 does not hold raises as the train set's does; times are any mutually comparable objects.  Returns the LocalRDD of
     recommend_topn in the order of `profiles`, with .stats, .sim_pairs, .item_info, .unknown_items and .counts = (AlterEgo rows,
-    pass-through rows, profiles with a row)."""
+    pass-through rows, profiles with a row).  explain as recommend_topn takes it: the sources are then entries of the profile
+    passed in (its iid, rating and time objects)."""
     _no_fold_in(alterEgoRDD, "recommend_topn_profiles")
     st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn_profiles")
     F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
@@ -554,6 +649,8 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     res = _topn_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, n, decay, keep_held, getattr(profiles, "ctx", None))
     res.unknown_items, res.counts = unknown, F.counts
     _tail_dicts(res, st, S, nb)
+    if explain is not None:
+        _explain_lists(res, st, eng2, F, nb, item_avg, range(len(uids)), alpha, decay, explain, F.raw_host)
     return res
 
 
