@@ -371,106 +371,13 @@ int xmap_reverse_fill(void *stream, const xmap_sim *S, int mode, int top_k, cons
                       uint8_t *eflag /*as left by xmap_reverse_count of the same mode and rows, or NULL*/, const int64_t *rptr /*[I+1]*/,
                       int32_t *ridx, double *rval /*[n][3]*/, uint8_t *rflag, int32_t row_lo, int32_t row_hi);
 
-/* Scheduling weights of the path enumeration: paths[start] = number of paths that start at `start`
- * (exact; tails(s) summed over src(t), heads over NB_BB / rnn).  tmp: 4*n_items int64 of scratch. */
-int xmap_path_weights(void *stream, int32_t n_items, int top_k, const uint8_t *cls, const int32_t *kcnt,
-                      const int32_t *kcol, const uint8_t *flags, const int64_t *att_ptr, const int32_t *att_idx,
-                      const int64_t *src_ptr, const int32_t *src_idx, const uint8_t *src_flag, const int64_t *rnn_ptr,
-                      const int32_t *rnn_idx, int64_t *tmp /*[4][I]*/, int64_t *paths /*[I]*/);
-
-/* ExtendSim.sim_extend + get_final_extension (core/extender.py:46-217), start-sharded and streamed:
- * every path of final_nonjoint_extend / final_joint_extend is enumerated in registers with its
- * s_p, c_p (calculate_path_confidence, :83-89) and accumulated into (sum s_p c_p, sum c_p) per
- * (start, end); xsim = ratio (:198-201).  The sums are kept as double-double (error-free two-sum), so
- * they do not depend on the enumeration order.
- * Work units (built by the caller from xmap_path_weights): unit u = (unit_start, chunk unit_c of unit_G).
- *   unit_G == 1, unit_row == -1: one wave owns the start, uses its slot row and finalises it;
- *   unit_G  > 1: the start's (head, t) entries are dealt round-robin to unit_G consecutive units with
- *   dedicated rows unit_row .. unit_row+G-1 of hacc/htouched; heavy_unit0[h] = first unit of heavy start h;
- *   the rows are merged and finalised after the enumeration.
- * For every start that has a unit: n_cand[start] = number of distinct ends, top_end/top_val[start][XMAP_TOPC]
- * = the candidates a Generator reads (stable sort by -|xsim|, generator.py:85,109; ties by ascending end).
- * If xs_cap > 0 the full candidate lists are also written: xs_off[start], entries (xs_end, xs_val);
- * needs xs_cap >= total (reported in h_counters[0]; XMAP_ERR_CAPACITY otherwise).  h_counters[1] = paths.
- * scratch (zero-filled by the caller, left zero): acc[n_slots][I][4], hacc[n_rows][I][4] doubles;
- * touched[n_slots][I], htouched[n_rows][I] int32. */
-int xmap_extend_paths(void *stream, int32_t n_items, int top_k, const uint8_t *cls, const int32_t *kcnt,
-                      const int32_t *kcol, const double *kval, const uint8_t *flags, const int64_t *att_ptr,
-                      const int32_t *att_idx, const double *att_val, const int64_t *src_ptr, const int32_t *src_idx,
-                      const double *src_val, const uint8_t *src_flag, const int64_t *rnn_ptr, const int32_t *rnn_idx,
-                      const double *rnn_val, int32_t n_units, const int32_t *unit_start, const int32_t *unit_c,
-                      const int32_t *unit_G, const int32_t *unit_row, int32_t *unit_nt, int32_t n_heavy,
-                      const int32_t *heavy_unit0, int32_t n_slots, double *acc, int32_t *touched, double *hacc,
-                      int32_t *htouched, int32_t *n_cand, int32_t *top_end, double *top_val, int64_t xs_cap,
-                      int64_t *xs_off, int32_t *xs_end, double *xs_val, int64_t *d_counters /*[4] device*/,
-                      int64_t *h_counters /*[4]*/);
-
-/* Second formulation of the enumeration ("middle lists", stage_b.hip): per non-bridge record x' (nb_list, n_nb of
- * them; nb_id[i] = position of i in nb_list or -1) the middles (t,s,x) of all joint paths through x' are materialised
- * once as 64-byte records grouped per tile (x', x).  A dense n_nb x n_nb table gives the tile sizes:
- *   xmap_mid_tally : tile_cnt[x'][x] and ng[x'] = number of non-empty tiles of x';
- *   (caller: exclusive scans tile_cnt -> tile_off [n_nb*n_nb+1], ng -> dir_ptr [n_nb+1]; allocates dir, midX)
- *   xmap_mid_place : the tile directory of every x' (24 B per tile: x, 1+|NN(x)|, count, offset) and the records.
- * xmap_extend_paths2 is xmap_extend_paths with the joint paths streamed from these lists, tile-major: the (up to 64)
- * heads of a start are merged by x, a lane keeps its end's double-double sums in registers across all tiles (x', x)
- * of the start's heads, so a start's row is touched once per (start, x) instead of once per path.  Same results
- * (the sums are exact). */
-#ifdef XMAP_CROSSCHECK   /* test formulation: exported by libxmap_hip_xcheck.so only (csrc/Makefile), never by the product library */
-int xmap_mid_tally(void *stream, int32_t n_items, int top_k, const uint8_t *cls, const int32_t *kcnt, const int32_t *kcol,
-                   const double *kval, const uint8_t *flags, const int64_t *att_ptr, const int32_t *att_idx,
-                   const double *att_val, const int64_t *src_ptr, const int32_t *src_idx, const double *src_val,
-                   const uint8_t *src_flag, int32_t n_nb, const int32_t *nb_list, const int32_t *nb_id,
-                   int32_t *tile_cnt /*[n_nb*n_nb]*/, int32_t *ng /*[n_nb]*/);
-int xmap_mid_place(void *stream, int32_t n_items, int top_k, const uint8_t *cls, const int32_t *kcnt, const int32_t *kcol,
-                   const double *kval, const uint8_t *flags, const int64_t *att_ptr, const int32_t *att_idx,
-                   const double *att_val, const int64_t *src_ptr, const int32_t *src_idx, const double *src_val,
-                   const uint8_t *src_flag, int32_t n_nb, const int32_t *nb_list, const int32_t *nb_id,
-                   int32_t *tile_cnt, const int64_t *tile_off /*[n_nb*n_nb+1]*/, const int64_t *dir_ptr /*[n_nb+1]*/,
-                   void *dir /*24 B per tile*/, void *midX /*64 B per record*/);
-#endif /* XMAP_CROSSCHECK */
-/* Row-wise construction of the same lists (default, any n_nb): one block per x' keeps the tile sizes of its row in LDS --
- * XMAP_MID_ROWS_SPAN columns at a time; a row with more non-bridge items is built in column ranges, one after the
- * other -- so there is no n_nb x n_nb table and no global atomic:
- *   xmap_mid_rows_count : ng[x'] = non-empty tiles, nrec[x'] = records of x';
- *   (caller: exclusive scans ng -> dir_ptr [n_nb+1], nrec -> rec_ptr [n_nb+1]; allocates dir, midX)
- *   xmap_mid_rows_place : the tile directory (in x order) and the records of every x'.
- * Output identical to xmap_mid_tally / xmap_mid_place up to the order of the records inside a tile. */
-#define XMAP_MID_ROWS_SPAN 36864   /* columns of a row whose counters fit the LDS of a block (4 B each; 160 KB per CU on gfx950, 7 KB of it the walk's tables) */
-int xmap_mid_rows_count(void *stream, int32_t n_items, int top_k, const uint8_t *cls, const int32_t *kcnt, const int32_t *kcol,
-                        const double *kval, const uint8_t *flags, const int64_t *att_ptr, const int32_t *att_idx,
-                        const double *att_val, const int64_t *src_ptr, const int32_t *src_idx, const double *src_val,
-                        const uint8_t *src_flag, int32_t n_nb, const int32_t *nb_list, const int32_t *nb_id,
-                        int32_t *ng /*[n_nb]*/, int64_t *nrec /*[n_nb]*/);
-int xmap_mid_rows_place(void *stream, int32_t n_items, int top_k, const uint8_t *cls, const int32_t *kcnt, const int32_t *kcol,
-                        const double *kval, const uint8_t *flags, const int64_t *att_ptr, const int32_t *att_idx,
-                        const double *att_val, const int64_t *src_ptr, const int32_t *src_idx, const double *src_val,
-                        const uint8_t *src_flag, int32_t n_nb, const int32_t *nb_list, const int32_t *nb_id,
-                        const int64_t *dir_ptr /*[n_nb+1]*/, const int64_t *rec_ptr /*[n_nb+1]*/, void *dir /*24 B per tile*/,
-                        void *midX /*64 B per record*/);
-#ifdef XMAP_CROSSCHECK   /* test formulation: exported by libxmap_hip_xcheck.so only (csrc/Makefile), never by the product library */
-int xmap_extend_paths2(void *stream, int32_t n_items, int top_k, const uint8_t *cls, const int32_t *kcnt,
-                       const int32_t *kcol, const double *kval, const uint8_t *flags, const int64_t *att_ptr,
-                       const int32_t *att_idx, const double *att_val, const int64_t *src_ptr, const int32_t *src_idx,
-                       const double *src_val, const uint8_t *src_flag, const int64_t *rnn_ptr, const int32_t *rnn_idx,
-                       const double *rnn_val, int32_t n_units, const int32_t *unit_start, const int32_t *unit_c,
-                       const int32_t *unit_G, const int32_t *unit_row, int32_t *unit_nt, int32_t n_heavy,
-                       const int32_t *heavy_unit0, int32_t n_slots, double *acc, int32_t *touched, double *hacc,
-                       int32_t *htouched, int32_t *n_cand, int32_t *top_end, double *top_val, int64_t xs_cap,
-                       int64_t *xs_off, int32_t *xs_end, double *xs_val, int64_t *d_counters, int64_t *h_counters,
-                       const int32_t *nb_id, const int32_t *nb_list, int32_t n_nb, const void *midX, const void *dir,
-                       const int64_t *dir_ptr, const int32_t *ng);
-#endif /* XMAP_CROSSCHECK */
-
-/* ---- extension, column form (default) ----------------------------------------------------------------------------
- * Same work units and results as xmap_extend_paths2 (units = starts, heavy starts cut into unit_G chunks with dedicated
- * rows), rebuilt around what bounds it (DESIGN.md 4): a column (start, x) is ONE set of lanes -- W ends x S record
- * slices, S = 4 / 2 / 1 by the column's width -- and one row update; rows are indexed by the rank of the end among
- * the n_ends items that can end a path at all (xmap_end_universe: urank[item] / uitem[rank]) instead of by item; the
- * ends of a column come from one table of 32-byte records; sums are (value, error) pairs folded at the end.
- * Scratch (zero-filled by the caller once, returned zeroed): acc [n_slots][n_ends][4] doubles, touched
- * [n_slots][n_ends], hacc [rows][n_ends][4], htouched [rows][n_ends].  fast_div: every edge has a positive mutuality
- * and |sim * mutu| within 2^+-400 (what stage A produces), so the division of a path is the bare
- * reciprocal-refinement sequence.  Results as xmap_extend_paths (same exact sums). */
+/* The stage-B tables of one pass, as every entry point below that reads them takes them (device pointers).  Members a call
+ * does not read may be NULL / 0; each entry point says which it reads.
+ *   cls .. flags : the classified top-k lists (xmap_knn_classify) and the item flags of xmap_ratings;
+ *   att_* / src_* / rnn_* : the reverse adjacencies (xmap_reverse_*: ptr [I+1], idx, val [n][3]; src_flag bit 0 = joint);
+ *   n_nb, nb_id, nb_list : the non-bridge records (xmap_nb_index); midX, dir, dir_ptr: their middle lists (xmap_mid_rows_*);
+ *   n_ends, urank, uitem : the end universe (xmap_end_universe), read by xmap_extend_cols only.
+ * xmap_path_units: the work units (xmap_path_plan); xmap_path_rows: the accumulator rows; xmap_path_out: the results. */
 typedef struct xmap_ext_tables {
     int32_t n_items, top_k;
     const uint8_t *cls; const int32_t *kcnt; const int32_t *kcol; const double *kval; const uint8_t *flags;
@@ -488,6 +395,78 @@ typedef struct xmap_path_rows { int32_t n_slots; double *acc; int32_t *touched; 
 typedef struct xmap_path_out {
     int32_t *n_cand; int32_t *top_end; double *top_val; int64_t xs_cap; int64_t *xs_off; int32_t *xs_end; double *xs_val;
 } xmap_path_out;
+
+/* Scheduling weights of the path enumeration: paths[start] = number of paths that start at `start`
+ * (exact; tails(s) summed over src(t), heads over NB_BB / rnn).  tmp: 4*n_items int64 of scratch.
+ * Reads n_items, top_k, cls, kcnt, kcol, flags, att_ptr, att_idx, src_ptr, src_idx, src_flag, rnn_ptr, rnn_idx (no value
+ * column, no middle-list member). */
+int xmap_path_weights(void *stream, const xmap_ext_tables *T, int64_t *tmp /*[4][I]*/, int64_t *paths /*[I]*/);
+
+/* ExtendSim.sim_extend + get_final_extension (core/extender.py:46-217), start-sharded and streamed:
+ * every path of final_nonjoint_extend / final_joint_extend is enumerated in registers with its
+ * s_p, c_p (calculate_path_confidence, :83-89) and accumulated into (sum s_p c_p, sum c_p) per
+ * (start, end); xsim = ratio (:198-201).  The sums are kept as double-double (error-free two-sum), so
+ * they do not depend on the enumeration order.
+ * Reads of T: n_items, top_k, cls .. flags, att_*, src_*, rnn_* (rows are indexed by item: n_ends, urank, uitem and the
+ * middle-list members are ignored).
+ * Work units U (built by the caller from xmap_path_weights: xmap_path_plan): unit u = (unit_start, chunk unit_c of unit_G).
+ *   unit_G == 1, unit_row == -1: one wave owns the start, uses its slot row and finalises it;
+ *   unit_G  > 1: the start's (head, t) entries are dealt round-robin to unit_G consecutive units with
+ *   dedicated rows unit_row .. unit_row+G-1 of R->hacc / R->htouched; heavy_unit0[h] = first unit of heavy start h
+ *   (n_heavy of them); the rows are merged and finalised after the enumeration.
+ * For every start that has a unit: O->n_cand[start] = number of distinct ends, O->top_end / O->top_val[start][XMAP_TOPC]
+ * = the candidates a Generator reads (stable sort by -|xsim|, generator.py:85,109; ties by ascending end).
+ * If O->xs_cap > 0 the full candidate lists are also written: xs_off[start], entries (xs_end, xs_val);
+ * needs xs_cap >= total (reported in h_counters[0]; XMAP_ERR_CAPACITY otherwise).  h_counters[1] = paths.
+ * scratch R (zero-filled by the caller, left zero): acc[n_slots][I][4], hacc[n_rows][I][4] doubles;
+ * touched[n_slots][I], htouched[n_rows][I] int32. */
+int xmap_extend_paths(void *stream, const xmap_ext_tables *T, const xmap_path_units *U, const xmap_path_rows *R,
+                      const xmap_path_out *O, int64_t *d_counters /*[4] device*/, int64_t *h_counters /*[4]*/);
+
+/* Second formulation of the enumeration ("middle lists"): per non-bridge record x' (nb_list, n_nb of
+ * them; nb_id[i] = position of i in nb_list or -1) the middles (t,s,x) of all joint paths through x' are materialised
+ * once as 64-byte records grouped per tile (x', x).  A dense n_nb x n_nb table gives the tile sizes (stage_b_xcheck.hip):
+ *   xmap_mid_tally : tile_cnt[x'][x] and ng[x'] = number of non-empty tiles of x';
+ *   (caller: exclusive scans tile_cnt -> tile_off [n_nb*n_nb+1], ng -> dir_ptr [n_nb+1]; allocates dir, midX)
+ *   xmap_mid_place : the tile directory of every x' (24 B per tile: x, 1+|NN(x)|, count, offset) and the records.
+ * Both read n_items, top_k, cls .. flags, att_*, src_*; n_nb, nb_list, nb_id; xmap_mid_place also dir_ptr (it writes
+ * through its dir / midX arguments: the members of T are const).
+ * xmap_extend_paths2 is xmap_extend_paths with the joint paths streamed from these lists, tile-major: the (up to 64)
+ * heads of a start are merged by x, a lane keeps its end's double-double sums in registers across all tiles (x', x)
+ * of the start's heads, so a start's row is touched once per (start, x) instead of once per path.  Same results
+ * (the sums are exact).  Reads what xmap_extend_paths reads + n_nb (> 0), nb_id, nb_list, midX, dir, dir_ptr. */
+#ifdef XMAP_CROSSCHECK   /* test formulation: exported by libxmap_hip_xcheck.so only (csrc/Makefile), never by the product library */
+int xmap_mid_tally(void *stream, const xmap_ext_tables *T, int32_t *tile_cnt /*[n_nb*n_nb]*/, int32_t *ng /*[n_nb]*/);
+int xmap_mid_place(void *stream, const xmap_ext_tables *T, int32_t *tile_cnt, const int64_t *tile_off /*[n_nb*n_nb+1]*/,
+                   void *dir /*24 B per tile*/, void *midX /*64 B per record*/);
+int xmap_extend_paths2(void *stream, const xmap_ext_tables *T, const xmap_path_units *U, const xmap_path_rows *R,
+                       const xmap_path_out *O, const int32_t *ng /*[n_nb] of xmap_mid_tally / xmap_mid_rows_count*/,
+                       int64_t *d_counters, int64_t *h_counters);
+#endif /* XMAP_CROSSCHECK */
+/* Row-wise construction of the same lists (default, any n_nb; mid_rows.hip): one block per x' keeps the tile sizes of its
+ * row in LDS -- XMAP_MID_ROWS_SPAN columns at a time; a row with more non-bridge items is built in column ranges, one after
+ * the other -- so there is no n_nb x n_nb table and no global atomic:
+ *   xmap_mid_rows_count : ng[x'] = non-empty tiles, nrec[x'] = records of x';
+ *   (caller: exclusive scans ng -> dir_ptr [n_nb+1], nrec -> rec_ptr [n_nb+1]; allocates dir, midX)
+ *   xmap_mid_rows_place : the tile directory (in x order) and the records of every x'.
+ * Both read n_items, top_k, cls .. flags, att_*, src_*; n_nb, nb_list, nb_id; xmap_mid_rows_place also dir_ptr (it writes
+ * through its dir / midX arguments).
+ * Output identical to xmap_mid_tally / xmap_mid_place up to the order of the records inside a tile. */
+#define XMAP_MID_ROWS_SPAN 36864   /* columns of a row whose counters fit the LDS of a block (4 B each; 160 KB per CU on gfx950, 7 KB of it the walk's tables) */
+int xmap_mid_rows_count(void *stream, const xmap_ext_tables *T, int32_t *ng /*[n_nb]*/, int64_t *nrec /*[n_nb]*/);
+int xmap_mid_rows_place(void *stream, const xmap_ext_tables *T, const int64_t *rec_ptr /*[n_nb+1]*/, void *dir /*24 B per tile*/,
+                        void *midX /*64 B per record*/);
+
+/* ---- extension, column form (default) ----------------------------------------------------------------------------
+ * Same work units and results as xmap_extend_paths2 (units = starts, heavy starts cut into unit_G chunks with dedicated
+ * rows), rebuilt around what bounds it (DESIGN.md 4): a column (start, x) is ONE set of lanes -- W ends x S record
+ * slices, S = 4 / 2 / 1 by the column's width -- and one row update; rows are indexed by the rank of the end among
+ * the n_ends items that can end a path at all (xmap_end_universe: urank[item] / uitem[rank]) instead of by item; the
+ * ends of a column come from one table of 32-byte records; sums are (value, error) pairs folded at the end.
+ * Scratch (zero-filled by the caller once, returned zeroed): acc [n_slots][n_ends][4] doubles, touched
+ * [n_slots][n_ends], hacc [rows][n_ends][4], htouched [rows][n_ends].  fast_div: every edge has a positive mutuality
+ * and |sim * mutu| within 2^+-400 (what stage A produces), so the division of a path is the bare
+ * reciprocal-refinement sequence.  Results as xmap_extend_paths (same exact sums). */
 /* fast_div precondition of xmap_extend_cols over a similarity matrix: *h_fast_ok = 1 iff every kept pair has mutu >= 1
  * and sim * mutu is zero or within 2^+-400 (always true for what stage A produces; 0 for a matrix that carries its own
  * frac column, i.e. generic records).  One pass over the pairs; synchronises. */

@@ -35,8 +35,7 @@ nn = C.c_int64(0)
 check(lib.xmap_nb_index(st, i32(I), vp(E.cls), vp(nb_list), vp(nb_id), C.byref(nn)))
 n_nb = int(nn.value)
 ng = eng._empty(n_nb, torch.int32); nrec = eng._empty(n_nb, torch.int64)
-R = eng.R
-common = (i32(I), E.k, vp(E.cls), vp(E.kcnt), vp(E.kcol), vp(E.kval), vp(R.flags), vp(E.att[0]), vp(E.att[1]), vp(E.att[2]),
-          vp(E.src[0]), vp(E.src[1]), vp(E.src[2]), vp(E.src[3]), i32(n_nb), vp(nb_list[:n_nb]), vp(nb_id))
-check(lib.xmap_mid_rows_count(st, *common, vp(ng), vp(nrec)))
+M = device.ExtResult()
+M.n_nb, M.nb_list, M.nb_id = n_nb, nb_list[:n_nb], nb_id
+check(lib.xmap_mid_rows_count(st, C.byref(eng._ext_tables(E, M)), vp(ng), vp(nrec)))
 print("middle lists: records %.4g (%.1f GB) tiles %.4g" % (float(nrec.sum().item()), float(nrec.sum().item()) * 64 / 1e9, float(ng.sum().item())))

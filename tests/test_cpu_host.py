@@ -53,6 +53,24 @@ def test_abi_exports_every_declared_symbol():
         assert [f[0] for f in cls._fields_] == re.findall(r"\*?(\w+)\s*[;,]", body.split("{", 1)[1]), st_name
 
 
+def test_struct_layouts_match_the_header():
+    """every ctypes.Structure the engine passes by pointer has the header's members: names and kinds (pointer / int32_t /
+    int64_t), in order -- all pointers are c_void_p, so nothing else catches a member out of place"""
+    import ctypes
+    from xmap.engine import hipabi
+    structs = hipabi.header_structs()
+    classes = dict(xmap_ratings=hipabi.Ratings, xmap_sim=hipabi.Sim, xmap_ext_tables=hipabi.ExtTables,
+                   xmap_path_units=hipabi.PathUnits, xmap_path_rows=hipabi.PathRows, xmap_path_out=hipabi.PathOut,
+                   xmap_union_part=hipabi.UnionPart)
+    assert set(structs) == set(classes)
+    for name, cls in sorted(classes.items()):
+        assert len(structs[name]) >= 5 and all(t in (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64) for _, t in structs[name]), name
+        assert list(cls._fields_) == structs[name], name
+    assert structs["xmap_ext_tables"][:3] == [("n_items", ctypes.c_int32), ("top_k", ctypes.c_int32), ("cls", ctypes.c_void_p)]
+    assert structs["xmap_ratings"][:3] == [("n_users", ctypes.c_int64), ("n_items", ctypes.c_int32), ("nnz", ctypes.c_int64)]
+    assert structs["xmap_path_out"][3] == ("xs_cap", ctypes.c_int64)
+
+
 def test_item_attrs_predicates():
     from xmap.engine import ids
     iids = ["00aS:", "B0xT:", "T:zS:", "00T:bT:", "1xqS:1:", "S:pT:"]

@@ -210,15 +210,9 @@ static int run_enumeration(xmap_ctx *c, int64_t xs_cap, int64_t *xs_off, int32_t
     XM_ALLOCZ(c->p_ext, d_cnt, 8);
     int64_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int rc;
-    if (c->T.n_nb > 0) {
-        rc = xmap_extend_cols(c->st, &c->T, &c->Un, &Rw, &O, c->fast_div, d_cnt, h_cnt);
-    } else {    // nothing joint: the per-path kernel over item-indexed rows (the same row buffers, U = I)
-        rc = xmap_extend_paths(c->st, I, c->top_k, c->T.cls, c->T.kcnt, c->T.kcol, c->T.kval, c->T.flags, c->T.att_ptr, c->T.att_idx,
-                               c->T.att_val, c->T.src_ptr, c->T.src_idx, c->T.src_val, c->T.src_flag, c->T.rnn_ptr, c->T.rnn_idx,
-                               c->T.rnn_val, c->Un.n_units, c->Un.unit_start, c->Un.unit_c, c->Un.unit_G, c->Un.unit_row,
-                               c->Un.unit_nt, c->Un.n_heavy, c->Un.heavy_unit0, c->n_slots, c->acc, c->touched, c->hacc, c->htouched,
-                               c->n_cand, c->top_end, c->top_val, xs_cap, xs_off, xs_end, xs_val, d_cnt, h_cnt);
-    }
+    // n_nb == 0 (nothing joint): the per-path kernel over item-indexed rows (the same row buffers, U = I)
+    if (c->T.n_nb > 0) rc = xmap_extend_cols(c->st, &c->T, &c->Un, &Rw, &O, c->fast_div, d_cnt, h_cnt);
+    else rc = xmap_extend_paths(c->st, &c->T, &c->Un, &Rw, &O, d_cnt, h_cnt);
     if (rc && rc != XMAP_ERR_CAPACITY) {     // a failed pass may leave partial sums in the rows
         c->p_rows.release();
         c->acc = nullptr;
@@ -583,8 +577,7 @@ int xmap_ctx_extend(xmap_ctx *c, int top_k, int64_t *n_out, int64_t *n_paths) {
     // exact per-start path counts -> work units
     int64_t *wtmp, *P;
     XM_ALLOCZ(c->p_ext, wtmp, (size_t)4 * I); XM_ALLOCZ(c->p_ext, P, I);
-    XM_TRY(xmap_path_weights(c->st, I, k, cls, kcnt, kcol, c->R.flags, T.att_ptr, T.att_idx, T.src_ptr, T.src_idx, T.src_flag, T.rnn_ptr,
-                             T.rnn_idx, wtmp, P));
+    XM_TRY(xmap_path_weights(c->st, &T, wtmp, P));
     // middle lists of the joint paths (row-wise construction)
     int32_t *nb_list, *nb_id;
     int64_t n_nb = 0;
@@ -596,17 +589,16 @@ int xmap_ctx_extend(xmap_ctx *c, int top_k, int64_t *n_out, int64_t *n_paths) {
         int64_t *nrec, *dir_ptr, *rec_ptr, n_tiles = 0, n_records = 0;
         void *dir, *midX;
         XM_ALLOC(c->p_ext, ng, n_nb); XM_ALLOC(c->p_ext, nrec, n_nb); XM_ALLOCZ(c->p_ext, dir_ptr, n_nb + 1); XM_ALLOCZ(c->p_ext, rec_ptr, n_nb + 1);
-        XM_TRY(xmap_mid_rows_count(c->st, I, k, cls, kcnt, kcol, kval, c->R.flags, T.att_ptr, T.att_idx, T.att_val, T.src_ptr, T.src_idx,
-                                   T.src_val, T.src_flag, (int32_t)n_nb, nb_list, nb_id, ng, nrec));
+        XM_TRY(xmap_mid_rows_count(c->st, &T, ng, nrec));
         XM_TRY(xmap_exclusive_scan_i32_to_i64(c->st, ng, dir_ptr, n_nb, &n_tiles));
         XM_TRY(xmap_exclusive_scan_i64(c->st, nrec, rec_ptr, n_nb, &n_records));
         char *dir_c, *mid_c;
         XM_ALLOC(c->p_ext, dir_c, (size_t)(n_tiles ? n_tiles : 1) * 24);
         XM_ALLOC(c->p_ext, mid_c, (size_t)(n_records ? n_records : 1) * 64);
         dir = dir_c; midX = mid_c;
-        XM_TRY(xmap_mid_rows_place(c->st, I, k, cls, kcnt, kcol, kval, c->R.flags, T.att_ptr, T.att_idx, T.att_val, T.src_ptr, T.src_idx,
-                                   T.src_val, T.src_flag, (int32_t)n_nb, nb_list, nb_id, dir_ptr, rec_ptr, dir, midX));
-        T.dir = dir; T.midX = midX; T.dir_ptr = dir_ptr;
+        T.dir_ptr = dir_ptr;
+        XM_TRY(xmap_mid_rows_place(c->st, &T, rec_ptr, dir, midX));
+        T.dir = dir; T.midX = midX;
     }
     // end universe (rows are indexed by end rank, in column order)
     int64_t len = I;

@@ -1,6 +1,13 @@
-// paths.h -- what the two path enumerations of stage B share: the arguments, the carry of a path and its per-path walks,
-// the finalisation of a start's row, the middle-list records and the column tables.  stage_b.hip: the per-path fallback
-// k_paths, the middle lists, k_paths2 (XMAP_CROSSCHECK); paths4.hip: k_paths4 and the merges of the heavy starts.
+// paths.h -- what the files of stage B share: the kernel arguments (PathArgs, Path2Args, MidArgs) and how the host fills them
+// from the structs of the C ABI, the carry of a path and its per-path walks, the row accumulator of the per-path kernels,
+// the finalisation of a start's row, the middle-list records, the column tables and the list thresholds.
+//   knn.hip        bridge flags, the classified top-k lists and their thresholds
+//   reverse.hip    the reverse adjacencies (attach / src / rnn)
+//   mid_rows.hip   the middle lists, built row-wise (k_mid_rows)
+//   paths_enum.hip the per-start path counts, the per-path fallback k_paths, k_topc_lists
+//   paths4.hip     the default enumeration k_paths4 and the merges of the heavy starts
+//   plan.hip       the planning steps (work units, the order of the end universe)
+//   stage_b_xcheck.hip (libxmap_hip_xcheck.so only): the dense-table middle lists and k_paths2
 #pragma once
 #include "common.h"
 
@@ -98,6 +105,29 @@ __device__ __forceinline__ void through_t(const PathArgs &A, ACC &W, int t, bool
         }
     }
 }
+
+// Error-free accumulation (Knuth two-sum, double-double running sums): the per-(start,end) sums become
+// independent of the order in which paths are enumerated (to ~2^-104), so items with identical
+// path multisets tie exactly and the tie-break (ascending end index) is well defined.
+struct WaveAcc {
+    double *acc; int *touched; int nt; unsigned long long paths;
+    __device__ __forceinline__ void add(bool active, int end, Carry p) {
+        bool first = false;
+        if (active) {
+            double sp = (p.mu != 0.0) ? 1.0 * p.sm / p.mu : 0.0;   // calculate_path_confidence (extender.py:83-89)
+            double *a = acc + (size_t)end * 4;
+            double s_hi = a[0], s_lo = a[1], c_hi = a[2], c_lo = a[3];
+            first = (c_hi == 0.0);
+            dd_add(s_hi, s_lo, sp * p.c);
+            dd_add(c_hi, c_lo, p.c);
+            a[0] = s_hi; a[1] = s_lo; a[2] = c_hi; a[3] = c_lo;
+        }
+        unsigned long long m = __ballot(first);
+        if (first) touched[nt + __popcll(m & lanemask_lt())] = end;
+        nt += __popcll(m);
+        paths += __popcll(__ballot(active));
+    }
+};
 
 // wave-wide selection of the XMAP_TOPC best of nt candidates in the order (|xsim| desc, end asc);
 // get(b, end, val) returns candidate b.  Lane 0 writes the result.
@@ -222,9 +252,33 @@ __device__ __forceinline__ int finalize_start(const PathArgs &A, FinBuf &F, doub
     return nt;
 }
 
-// a middle-list record and a tile directory entry (built by k_mid_rows, stage_b.hip)
+// a middle-list record and a tile directory entry (built by k_mid_rows, mid_rows.hip)
 struct MidX { double sm2, sm3, sm4, f2, f3, f4, mu; int xid; int pad; };   // 64 B; xid = index of x in nb_list
 struct MidDir { int x; int ne; int cnt; int pad; long long off; };          // one tile of x': item x, 1+|NN(x)| ends, records [off, off+cnt); pad = index of x in nb_list
+
+// Second formulation of the enumeration ("middle lists").  Every joint path has the shape
+//   [y'] - x' - t - s - [x - [y]]      with x', x non-bridge items, t in NB_BB(x'), (t,s) joint.
+// For each non-bridge x' the middles (t,s,x) are materialised ONCE, grouped by x (one "tile" per (x', x); a dense
+// n_nb x n_nb count table gives the tile offsets, so the build is a tally pass + a placement pass over
+// (x', t) work items -- no per-x' serial section).  A head (start, x') then streams the tiles of x': all
+// records of one tile hit the same ends {x} U NN(x), so each lane keeps its end's double-double sums in
+// REGISTERS across the tile and the start's row in HBM is touched once per (head, tile) instead of once per
+// path.  The edge products sim*mutu and the fractions are stored per edge, so a path's (sum sim*mutu, sum
+// mutu, prod frac) is rebuilt in the reference's left-to-right order, bit for bit.
+
+struct MidArgs {
+    int I, k;
+    const uint8_t *cls; const int *kcnt; const int *kcol; const double *kval; const uint8_t *flags;
+    const long long *att_ptr; const int *att_idx; const double *att_val;
+    const long long *src_ptr; const int *src_idx; const double *src_val; const uint8_t *src_flag;
+    int n_nb; const int *nb_list; const int *nb_id;
+    const long long *jptr; const int *joff;     // joint (t, s) of every t, compacted: offsets into src(t) (k_joint_list; k_mid_rows)
+    const int *axid;                            // column of every attach entry (k_att_columns)
+    const long long *xoff; int *xl;             // rows wider than the LDS span: the columns of a row's records in walk order, [xoff[x'], xoff[x'+1])
+    int *tile_cnt;                 // [n_nb * n_nb] tally, then placement cursor
+    const long long *tile_off;     // [n_nb * n_nb + 1]
+    MidX *midX;
+};
 
 // the value of lane SRC of every quad, in all four lanes of the quad (DPP quad_perm: no LDS traffic)
 template <int SRC>
@@ -270,7 +324,79 @@ __device__ __forceinline__ void head_S(const PathArgs &A, ACC &W, int xp, bool h
     }
 }
 
+// the last entry of every top-k list as one 16-byte record (12.8 MB for 4e5 items: resident in the Infinity Cache, where the
+// lists themselves, 1.1 GB, are not): written by k_knn_thresholds (knn.hip), read by the membership tests of reverse.hip
+struct KnnThr { double la; int col; int cnt; };
+
 // the partial rows of the heavy starts added up and finalised (k_merge_groups, k_merge: paths4.hip)
 int merge_heavy(hipStream_t st, const PathArgs &A, int n_heavy, const int *heavy_unit0);
+
+// ---- host side: the kernel arguments from the structs of the C ABI (include/xmap_hip.h) ---------------------------------
+// item-indexed rows (U = I, no rank tables): what k_paths and k_paths2 take; xmap_extend_cols puts the end universe on top
+inline PathArgs path_args(const xmap_ext_tables *T, const xmap_path_units *U, const xmap_path_rows *R, const xmap_path_out *O,
+                          int64_t *d_counters) {
+    PathArgs A;
+    A.I = T->n_items; A.k = T->top_k;
+    A.cls = T->cls; A.kcnt = T->kcnt; A.kcol = T->kcol; A.kval = T->kval; A.flags = T->flags;
+    A.att_ptr = (const long long *)T->att_ptr; A.att_idx = T->att_idx; A.att_val = T->att_val;
+    A.src_ptr = (const long long *)T->src_ptr; A.src_idx = T->src_idx; A.src_val = T->src_val; A.src_flag = T->src_flag;
+    A.rnn_ptr = (const long long *)T->rnn_ptr; A.rnn_idx = T->rnn_idx; A.rnn_val = T->rnn_val;
+    A.n_units = U->n_units; A.unit_start = U->unit_start; A.unit_c = U->unit_c; A.unit_G = U->unit_G; A.unit_row = U->unit_row;
+    A.unit_nt = U->unit_nt;
+    A.n_slots = R->n_slots < U->n_units ? R->n_slots : U->n_units;
+    A.acc = R->acc; A.touched = R->touched; A.hacc = R->hacc; A.htouched = R->htouched;
+    A.n_cand = O->n_cand; A.top_end = O->top_end; A.top_val = O->top_val;
+    A.xs_cap = O->xs_cap; A.xs_off = (long long *)O->xs_off; A.xs_end = O->xs_end; A.xs_val = O->xs_val;
+    A.counters = (unsigned long long *)d_counters;
+    A.U = T->n_items; A.urank = nullptr; A.uitem = nullptr; A.row_stride = T->n_items;
+    return A;
+}
+
+// what the middle-list builders read of the tables (the call's own temporaries and outputs stay zero)
+inline MidArgs mid_args(const xmap_ext_tables *T) {
+    MidArgs A;
+    memset(&A, 0, sizeof(A));
+    A.I = T->n_items; A.k = T->top_k; A.cls = T->cls; A.kcnt = T->kcnt; A.kcol = T->kcol; A.kval = T->kval; A.flags = T->flags;
+    A.att_ptr = (const long long *)T->att_ptr; A.att_idx = T->att_idx; A.att_val = T->att_val;
+    A.src_ptr = (const long long *)T->src_ptr; A.src_idx = T->src_idx; A.src_val = T->src_val; A.src_flag = T->src_flag;
+    A.n_nb = T->n_nb; A.nb_list = T->nb_list; A.nb_id = T->nb_id;
+    return A;
+}
+
+// A per-path enumeration over item-indexed rows (xmap_extend_paths: paths_enum.hip; xmap_extend_paths2: stage_b_xcheck.hip):
+// the argument checks, the counters, launch(A, grid, stream) of the caller's kernel, the merge of the heavy starts and the
+// counters read back.
+template <class Launch>
+inline int extend_paths_run(void *stream, const xmap_ext_tables *T, const xmap_path_units *U, const xmap_path_rows *R,
+                            const xmap_path_out *O, int64_t *d_counters, int64_t *h_counters, Launch &&launch) {
+    XM_ARG(T && U && R && O);
+    XM_ARG(T->cls && T->kcnt && T->kcol && T->kval && T->flags && T->att_ptr && T->src_ptr && T->rnn_ptr);
+    XM_ARG(R->acc && R->touched && O->n_cand && O->top_end && O->top_val && d_counters);
+    XM_ARG(R->n_slots > 0 && U->n_units >= 0 && U->n_heavy >= 0);
+    XM_ARG(U->n_units == 0 || (U->unit_start && U->unit_c && U->unit_G && U->unit_row && U->unit_nt));
+    XM_ARG(U->n_heavy == 0 || (U->heavy_unit0 && R->hacc && R->htouched));
+    XM_ARG(O->xs_cap == 0 || (O->xs_off && O->xs_end && O->xs_val));
+    hipStream_t st = (hipStream_t)stream;
+    XM_HIP(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
+    if (U->n_units > 0) {
+        const PathArgs A = path_args(T, U, R, O, d_counters);
+        launch(A, dim3((unsigned)((A.n_slots + 3) / 4)), st);
+        XM_LAUNCH_CHECK();
+        if (U->n_heavy > 0) {
+            const int rc = merge_heavy(st, A, U->n_heavy, U->heavy_unit0);
+            if (rc) return rc;
+        }
+    }
+    if (h_counters) {
+        XM_HIP(hipMemcpyAsync(h_counters, d_counters, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        XM_HIP(hipStreamSynchronize(st));
+        if (O->xs_cap > 0 && h_counters[0] > O->xs_cap) {
+            set_error("candidate buffer too small: need %lld entries, have %lld", (long long)h_counters[0],
+                      (long long)O->xs_cap);
+            return XMAP_ERR_CAPACITY;
+        }
+    }
+    return XMAP_OK;
+}
 
 }  // namespace xmap

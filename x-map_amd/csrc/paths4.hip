@@ -684,22 +684,10 @@ int xmap_extend_cols(void *stream, const xmap_ext_tables *T, const xmap_path_uni
         Path2Args B;
         memset(&B, 0, sizeof(B));
         PathArgs &A = B.P;
-        A.I = T->n_items; A.k = T->top_k;
-        A.cls = T->cls; A.kcnt = T->kcnt; A.kcol = T->kcol; A.kval = T->kval; A.flags = T->flags;
-        A.att_ptr = (const long long *)T->att_ptr; A.att_idx = T->att_idx; A.att_val = T->att_val;
-        A.src_ptr = (const long long *)T->src_ptr; A.src_idx = T->src_idx; A.src_val = T->src_val; A.src_flag = T->src_flag;
-        A.rnn_ptr = (const long long *)T->rnn_ptr; A.rnn_idx = T->rnn_idx; A.rnn_val = T->rnn_val;
-        A.n_units = Un->n_units; A.unit_start = Un->unit_start; A.unit_c = Un->unit_c; A.unit_G = Un->unit_G;
-        A.unit_row = Un->unit_row; A.unit_nt = Un->unit_nt;
-        A.acc = R->acc; A.touched = R->touched; A.hacc = R->hacc; A.htouched = R->htouched;
-        A.n_cand = O->n_cand; A.top_end = O->top_end; A.top_val = O->top_val;
-        A.xs_cap = O->xs_cap; A.xs_off = (long long *)O->xs_off; A.xs_end = O->xs_end; A.xs_val = O->xs_val;
-        A.counters = (unsigned long long *)d_counters;
-        A.U = T->n_ends; A.urank = T->urank; A.uitem = T->uitem;
-        A.n_slots = R->n_slots < Un->n_units ? R->n_slots : Un->n_units;
+        A = path_args(T, Un, R, O, d_counters);
+        A.U = T->n_ends; A.urank = T->urank; A.uitem = T->uitem; A.row_stride = T->n_ends;      // rows indexed by end rank
         B.nb_id = T->nb_id; B.nb_list = T->nb_list; B.n_nb = T->n_nb; B.midX = (const MidX *)T->midX; B.dir = (const MidDir *)T->dir;
         B.dir_ptr = (const long long *)T->dir_ptr; B.ng = nullptr;
-        A.row_stride = T->n_ends;
         ColEnd *cend = nullptr;
         int *home = nullptr;
         if (T->n_nb > 0) {

@@ -911,9 +911,7 @@ class Engine(object):
         tmp = self._zeros(4 * max(I, 1), torch.int64)
         P = self._zeros(max(I, 1), torch.int64)
         with self.timed("path_weights"):
-            check(lib.xmap_path_weights(st, i32(I), E.k, vp(E.cls), vp(E.kcnt), vp(E.kcol), vp(R.flags),
-                                        vp(E.att[0]), vp(E.att[1]), vp(E.src[0]), vp(E.src[1]), vp(E.src[3]),
-                                        vp(E.rnn[0]), vp(E.rnn[1]), vp(tmp), vp(P)))
+            check(lib.xmap_path_weights(st, C.byref(self._ext_tables(E)), vp(tmp), vp(P)))
         # planning in the library (xmap_path_plan: chunk counts, heaviest-first order by its own radix sort, unit arrays)
         if start_split is not None:   # (rank, world): contiguous start ranges of equal path counts
             from .sharded import balanced_ranges
@@ -949,7 +947,7 @@ class Engine(object):
         R = self.R
         st = _stream(self.dev)
         I = R.n_items
-        T = self._ext_tables(E, None)
+        T = self._ext_tables(E)
         mark = self._empty(max(I, 1), torch.int32)
         rank = self._empty(I + 1, torch.int64)
         E.urank = self._empty(max(I, 1), torch.int32)
@@ -963,19 +961,20 @@ class Engine(object):
             check(lib.xmap_end_order(st, i32(I), E.k, i32(M.n_nb), vp(M.nb_list), vp(E.kcnt), vp(E.kcol), i32(E.n_ends),
                                      vp(E.urank), vp(E.uitem)))
 
-    def _ext_tables(self, E, M):
-        R = self.R
+    def _ext_tables(self, E, M=None):
+        """xmap_ext_tables of a pass: the one place that maps an ExtResult (and its middle lists M) to pointers.  What E or
+        M does not hold yet (reverse lists, middle lists, end universe) comes out 0."""
         p = lambda t: (t.data_ptr() if t is not None else 0)
         g = lambda o, n: getattr(o, n, None) if o is not None else None
-        return abi.ExtTables(R.n_items, E.k, p(E.cls), p(E.kcnt), p(E.kcol), p(E.kval), p(R.flags),
-                             p(E.att[0]), p(E.att[1]), p(E.att[2]), p(E.src[0]), p(E.src[1]), p(E.src[2]), p(E.src[3]),
-                             p(E.rnn[0]), p(E.rnn[1]), p(E.rnn[2]),
+        lst = lambda n, w: [p(t) for t in (g(E, n) or (None,) * w)[:w]]      # (ptr, idx, val[, flag]) of a reverse list
+        return abi.ExtTables(self.R.n_items, E.k, p(E.cls), p(E.kcnt), p(E.kcol), p(E.kval), p(self.R.flags),
+                             *lst("att", 3), *lst("src", 4), *lst("rnn", 3),
                              (M.n_nb if M is not None else 0), p(g(M, "nb_id")), p(g(M, "nb_list")), p(g(M, "midX")),
                              p(g(M, "dir")), p(g(M, "dir_ptr")),
-                             getattr(E, "n_ends", 0), p(getattr(E, "urank", None)), p(getattr(E, "uitem", None)))
+                             getattr(E, "n_ends", 0), p(g(E, "urank")), p(g(E, "uitem")))
 
     def mid_lists(self, E, table_budget=24 << 30, rows=None):
-        """middle lists of all joint paths, one tile of records per (x', x) (stage_b.hip, second formulation).
+        """middle lists of all joint paths, one tile of records per (x', x) (csrc/mid_rows.hip).
         rows (default): built row-wise, one block per x' with the row's tile sizes in LDS (abi.MID_ROWS_SPAN columns at a
         time); rows=False / XMAP_MID_TABLE=1: through the dense n_nb x n_nb tile table (cross-check; None when it does not
         fit the budget -- callers fall back to the per-path enumeration)."""
@@ -995,14 +994,12 @@ class Engine(object):
         M = ExtResult()
         M.n_nb, M.nb_list = n_nb, nb_list
         M.nb_id = nb_id
-        common = (i32(I), E.k, vp(E.cls), vp(E.kcnt), vp(E.kcol), vp(E.kval), vp(R.flags), vp(E.att[0]), vp(E.att[1]),
-                  vp(E.att[2]), vp(E.src[0]), vp(E.src[1]), vp(E.src[2]), vp(E.src[3]), i32(n_nb), vp(M.nb_list),
-                  vp(M.nb_id))
+        T = self._ext_tables(E, M)
         if rows:
             with self.timed("mid_build"):
                 M.ng = self._empty(n_nb, torch.int32)
                 nrec = self._empty(n_nb, torch.int64)
-                check(lib.xmap_mid_rows_count(st, *common, vp(M.ng), vp(nrec)))
+                check(lib.xmap_mid_rows_count(st, C.byref(T), vp(M.ng), vp(nrec)))
                 M.dir_ptr = self._zeros(n_nb + 1, torch.int64)
                 rec_ptr = self._zeros(n_nb + 1, torch.int64)
                 tx, tg = C.c_int64(0), C.c_int64(0)
@@ -1014,12 +1011,13 @@ class Engine(object):
                     return None         # the lists do not fit: the caller enumerates path by path
                 M.dir = self._empty(max(M.n_tiles, 1) * 3, torch.int64)
                 M.midX = self._empty(max(M.n_records, 1) * 8, torch.float64)
-                check(lib.xmap_mid_rows_place(st, *common, vp(M.dir_ptr), vp(rec_ptr), vp(M.dir), vp(M.midX)))
+                T.dir_ptr = M.dir_ptr.data_ptr()
+                check(lib.xmap_mid_rows_place(st, C.byref(T), vp(rec_ptr), vp(M.dir), vp(M.midX)))
             return M
         with self.timed("mid_build"):
             tile_cnt = self._empty(n_nb * n_nb, torch.int32)
             M.ng = self._zeros(n_nb, torch.int32)
-            abi.xcheck(abi.xlib().xmap_mid_tally(st, *common, vp(tile_cnt), vp(M.ng)))
+            abi.xcheck(abi.xlib().xmap_mid_tally(st, C.byref(T), vp(tile_cnt), vp(M.ng)))
             tile_off = self._empty(n_nb * n_nb + 1, torch.int64)
             M.dir_ptr = self._zeros(n_nb + 1, torch.int64)
             tx, tg = C.c_int64(0), C.c_int64(0)
@@ -1028,13 +1026,58 @@ class Engine(object):
             M.n_records, M.n_tiles = int(tx.value), int(tg.value)
             M.dir = self._empty(max(M.n_tiles, 1) * 3, torch.int64)
             M.midX = self._empty(max(M.n_records, 1) * 8, torch.float64)
-            abi.xcheck(abi.xlib().xmap_mid_place(st, *common, vp(tile_cnt), vp(tile_off), vp(M.dir_ptr), vp(M.dir), vp(M.midX)))
+            T.dir_ptr = M.dir_ptr.data_ptr()
+            abi.xcheck(abi.xlib().xmap_mid_place(st, C.byref(T), vp(tile_cnt), vp(tile_off), vp(M.dir), vp(M.midX)))
         return M
+
+    def _enumerate(self, E, U, M, full, xs_cap, start_range, row_len, scratch, n_slots, slot_budget, n_cnt, call, chk=check):
+        """What the forms of the enumeration share: n_slots (capped by slot_budget and the units) + U.n_rows zero-filled
+        accumulator rows of row_len entries -- scratch = the names of the two buffers --, the candidate arrays, n_cnt
+        counters and the list buffers, sized again when the pass reports ERR_CAPACITY.  call(T, Un, Rw, O, d_cnt, h_cnt)
+        makes the one library call and returns its code (chk raises on it).  Returns (n_slots, h_cnt)."""
+        I = self.R.n_items
+        n_slots = int(max(4, min(n_slots, slot_budget // (36 * row_len), max(U.n_units, 4))))
+        acc = self._zero_scratch(scratch[0], n_slots * row_len * 4, torch.float64)
+        touched = self._empty(n_slots * row_len, torch.int32)
+        hacc = self._zero_scratch(scratch[1], max(U.n_rows, 1) * row_len * 4, torch.float64) if U.n_rows else None
+        htouched = self._empty(max(U.n_rows, 1) * row_len, torch.int32) if U.n_rows else None
+        E.n_cand = self._zeros(max(I, 1), torch.int32)
+        E.top_end = torch.full((max(I, 1), abi.TOPC), -1, dtype=torch.int32, device=self.dev)
+        E.top_val = self._zeros((max(I, 1), abi.TOPC), torch.float64)
+        d_cnt = self._zeros(n_cnt, torch.int64)
+        h_cnt = (C.c_int64 * n_cnt)()
+        T = self._ext_tables(E, M)
+        Un = abi.PathUnits(U.n_units, U.unit_start.data_ptr(), U.unit_c.data_ptr(), U.unit_G.data_ptr(), U.unit_row.data_ptr(),
+                           U.unit_nt.data_ptr(), U.n_heavy, U.heavy_unit0.data_ptr())
+        Rw = abi.PathRows(n_slots, acc.data_ptr(), touched.data_ptr(), hacc.data_ptr() if hacc is not None else 0,
+                          htouched.data_ptr() if htouched is not None else 0)
+        cap = 0
+        if full:
+            cap = int(xs_cap) if xs_cap else 1 << 22
+        while True:
+            xs_off = self._zeros(max(I, 1), torch.int64) if cap else None
+            xs_end = self._empty(max(cap, 1), torch.int32) if cap else None
+            xs_val = self._empty(max(cap, 1), torch.float64) if cap else None
+            O = abi.PathOut(E.n_cand.data_ptr(), E.top_end.data_ptr(), E.top_val.data_ptr(), cap,
+                            xs_off.data_ptr() if cap else 0, xs_end.data_ptr() if cap else 0, xs_val.data_ptr() if cap else 0)
+            try:
+                with self.timed("paths"):
+                    rc = call(T, Un, Rw, O, d_cnt, h_cnt)
+                if rc == abi.ERR_CAPACITY:      # the pass itself completed (rows are back to zero): lists did not fit
+                    cap = int(h_cnt[0])
+                    continue
+                chk(rc)
+            except BaseException:
+                self._drop_scratch(*scratch)    # a failed pass may leave partial sums behind
+                raise
+            break
+        E.n_out, E.n_paths = int(h_cnt[0]), int(h_cnt[1])
+        E.xs_off, E.xs_end, E.xs_val = xs_off, xs_end, xs_val
+        E.start_range = (0, I) if start_range is None else tuple(start_range)
+        return n_slots, h_cnt
 
     def _extend_cols(self, E, U, M, full, xs_cap, start_range, n_slots):
         """xmap_extend_cols: one set of lanes and one row update per column, rows indexed by end rank"""
-        R = self.R
-        I = R.n_items
         st = _stream(self.dev)
         with self.timed("paths_prep"):
             self.end_universe(E)
@@ -1050,47 +1093,14 @@ class Engine(object):
             ns = C.c_int32(0)
             check(lib.xmap_extend_cols_slots(C.byref(ns)))
             n_slots = min(n_slots, int(ns.value))
-        n_slots = int(max(4, min(n_slots, slot_budget // (36 * nU), max(U.n_units, 4))))
-        acc = self._zero_scratch("qacc", n_slots * nU * 4, torch.float64)
-        touched = self._empty(n_slots * nU, torch.int32)
-        hacc = self._zero_scratch("qhacc", max(U.n_rows, 1) * nU * 4, torch.float64) if U.n_rows else None
-        htouched = self._empty(max(U.n_rows, 1) * nU, torch.int32) if U.n_rows else None
-        E.n_cand = self._zeros(max(I, 1), torch.int32)
-        E.top_end = torch.full((max(I, 1), abi.TOPC), -1, dtype=torch.int32, device=self.dev)
-        E.top_val = self._zeros((max(I, 1), abi.TOPC), torch.float64)
-        d_cnt = self._zeros(8, torch.int64)
-        h_cnt = (C.c_int64 * 8)()
-        T = self._ext_tables(E, M)
-        Un = abi.PathUnits(U.n_units, U.unit_start.data_ptr(), U.unit_c.data_ptr(), U.unit_G.data_ptr(), U.unit_row.data_ptr(),
-                           U.unit_nt.data_ptr(), U.n_heavy, U.heavy_unit0.data_ptr())
-        Rw = abi.PathRows(n_slots, acc.data_ptr(), touched.data_ptr(), hacc.data_ptr() if hacc is not None else 0,
-                          htouched.data_ptr() if htouched is not None else 0)
-        cap = 0
-        if full:
-            cap = int(xs_cap) if xs_cap else 1 << 22
         fast = 0 if os.environ.get("XMAP_SLOW_DIV") == "1" else int(getattr(E, "fast_div", 0))
-        while True:
-            xs_off = self._zeros(max(I, 1), torch.int64) if cap else None
-            xs_end = self._empty(max(cap, 1), torch.int32) if cap else None
-            xs_val = self._empty(max(cap, 1), torch.float64) if cap else None
-            O = abi.PathOut(E.n_cand.data_ptr(), E.top_end.data_ptr(), E.top_val.data_ptr(), cap,
-                            xs_off.data_ptr() if cap else 0, xs_end.data_ptr() if cap else 0, xs_val.data_ptr() if cap else 0)
-            try:
-                with self.timed("paths"):
-                    rc = lib.xmap_extend_cols(st, C.byref(T), C.byref(Un), C.byref(Rw), C.byref(O), fast, vp(d_cnt), h_cnt)
-                if rc == abi.ERR_CAPACITY:      # the pass itself completed (rows are back to zero): lists did not fit
-                    cap = int(h_cnt[0])
-                    continue
-                check(rc)
-            except BaseException:
-                self._drop_scratch("qacc", "qhacc")    # a failed pass may leave partial sums behind
-                raise
-            break
-        E.n_out, E.n_paths, E.n_updates = int(h_cnt[0]), int(h_cnt[1]), int(h_cnt[4])
+        n_slots, h_cnt = self._enumerate(
+            E, U, M, full, xs_cap, start_range, nU, ("qacc", "qhacc"), n_slots, slot_budget, 8,
+            lambda T, Un, Rw, O, d_cnt, h_cnt: lib.xmap_extend_cols(st, C.byref(T), C.byref(Un), C.byref(Rw), C.byref(O), fast,
+                                                                    vp(d_cnt), h_cnt))
+        E.n_updates = int(h_cnt[4])
         E.row_info = dict(n_slots=n_slots, ends=nU, slot_rows_gb=n_slots * nU * 36 / 1e9, heavy_rows=int(U.n_rows),
                           heavy_rows_gb=int(U.n_rows) * nU * 36 / 1e9, slot_budget_gb=slot_budget / 1e9)
-        E.xs_off, E.xs_end, E.xs_val = xs_off, xs_end, xs_val
-        E.start_range = (0, I) if start_range is None else tuple(start_range)
         return E
 
     def ext_tables(self, S, top_k, comm=None):
@@ -1285,48 +1295,14 @@ class Engine(object):
         # one private accumulator row (36 B per item) per resident wave: 5 waves per SIMD = 5120 rows on 256 CUs
         slot_budget = int(float(os.environ.get("XMAP_SLOT_BUDGET_GB", "100")) * (1 << 30))
         n_slots = int(os.environ.get("XMAP_N_SLOTS", n_slots))
-        n_slots = int(max(4, min(n_slots, slot_budget // (36 * max(I, 1)), max(U.n_units, 4))))
-        acc = self._zero_scratch("acc", n_slots * max(I, 1) * 4, torch.float64)
-        touched = self._empty(n_slots * max(I, 1), torch.int32)
-        hacc = self._zero_scratch("hacc", max(U.n_rows, 1) * max(I, 1) * 4, torch.float64) if U.n_rows else None
-        htouched = self._empty(max(U.n_rows, 1) * max(I, 1), torch.int32) if U.n_rows else None
-        E.n_cand = self._zeros(max(I, 1), torch.int32)
-        E.top_end = torch.full((max(I, 1), abi.TOPC), -1, dtype=torch.int32, device=self.dev)
-        E.top_val = self._zeros((max(I, 1), abi.TOPC), torch.float64)
-        d_cnt = self._zeros(4, torch.int64)
-        h_cnt = (C.c_int64 * 4)()
-        cap = 0
-        if full:
-            cap = int(xs_cap) if xs_cap else 1 << 22
-        while True:
-            xs_off = self._zeros(max(I, 1), torch.int64) if cap else None
-            xs_end = self._empty(max(cap, 1), torch.int32) if cap else None
-            xs_val = self._empty(max(cap, 1), torch.float64) if cap else None
-            args = (st, i32(I), E.k, vp(E.cls), vp(E.kcnt), vp(E.kcol), vp(E.kval), vp(R.flags),
-                    vp(E.att[0]), vp(E.att[1]), vp(E.att[2]),
-                    vp(E.src[0]), vp(E.src[1]), vp(E.src[2]), vp(E.src[3]),
-                    vp(E.rnn[0]), vp(E.rnn[1]), vp(E.rnn[2]),
-                    i32(U.n_units), vp(U.unit_start), vp(U.unit_c), vp(U.unit_G), vp(U.unit_row), vp(U.unit_nt),
-                    i32(U.n_heavy), vp(U.heavy_unit0),
-                    i32(n_slots), vp(acc), vp(touched), vp(hacc), vp(htouched),
-                    vp(E.n_cand), vp(E.top_end), vp(E.top_val),
-                    i64(cap), vp(xs_off), vp(xs_end), vp(xs_val), vp(d_cnt), h_cnt)
-            with self.timed("paths"):
-                if M is not None:
-                    rc = abi.xlib().xmap_extend_paths2(*args, vp(M.nb_id), vp(M.nb_list), i32(M.n_nb), vp(M.midX), vp(M.dir),
-                                                vp(M.dir_ptr), vp(M.ng))
-                else:
-                    rc = lib.xmap_extend_paths(*args)
-            if rc == abi.ERR_CAPACITY:
-                cap = int(h_cnt[0])
-                continue
-            if rc != 0:
-                self._drop_scratch("acc", "hacc")
-            (abi.xcheck if M is not None else check)(rc)
-            break
-        E.n_out, E.n_paths = int(h_cnt[0]), int(h_cnt[1])
-        E.xs_off, E.xs_end, E.xs_val = xs_off, xs_end, xs_val
-        E.start_range = (0, I) if start_range is None else tuple(start_range)
+        if M is not None:       # algo="mid": the tile-major test formulation over the middle lists
+            call = lambda T, Un, Rw, O, d_cnt, h_cnt: abi.xlib().xmap_extend_paths2(
+                st, C.byref(T), C.byref(Un), C.byref(Rw), C.byref(O), vp(M.ng), vp(d_cnt), h_cnt)
+        else:
+            call = lambda T, Un, Rw, O, d_cnt, h_cnt: lib.xmap_extend_paths(
+                st, C.byref(T), C.byref(Un), C.byref(Rw), C.byref(O), vp(d_cnt), h_cnt)
+        self._enumerate(E, U, M, full, xs_cap, start_range, max(I, 1), ("acc", "hacc"), n_slots, slot_budget, 4, call,
+                        abi.xcheck if M is not None else check)
         return E
 
     # ------------------------------------------------------------------ dense item-factor variant

@@ -154,6 +154,22 @@ def header_constants(prefixes=("XMAP_PAIRS_", "XMAP_LAYOUT_"), path=HEADER_PATH)
             if n.startswith(tuple(prefixes))}
 
 
+def header_structs(path=HEADER_PATH):
+    """{struct name: [(member, ctypes type)] in order} of the header's `typedef struct xmap_* { ... }`: a pointer of any
+    kind -> c_void_p, int32_t -> c_int32, int64_t -> c_int64 (tests/test_cpu_host.py holds the Structure classes to it)"""
+    import re
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(xmap_\w+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        out[name] = fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            kind = C.c_int64 if "int64_t" in decl else C.c_int32 if "int32_t" in decl else None
+            for m in decl.split(","):       # (`int32_t n_items, top_k;`: every declarator carries its own `*`)
+                fields.append((re.search(r"(\w+)\s*$", m).group(1), C.c_void_p if "*" in m else kind))
+    return out
+
+
 # argtypes of every export: a mis-ordered or mis-typed argument raises in ctypes instead of corrupting device memory
 PROTOTYPES = header_prototypes()
 
