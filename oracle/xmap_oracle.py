@@ -132,9 +132,37 @@ def item_sim(T, method, cap, uavg=None, info=None, nthreads=1, rows=None):
     return out
 
 
+def sim_from_arrays(I, row_ptr, col, sim, mutu, nij, info):
+    """A kept-pair matrix fed by the caller (CSR by first item, columns ascending; info [I][4] as item_info returns it) as a
+    Sim that extend() takes: xo_extend reads I, row_ptr, col, sim, mutu and nij of the struct and nothing else.  The struct is
+    built here over NumPy arrays the Sim keeps alive, so sim_free() drops it without handing it to xo_sim_free()."""
+    out = Sim()
+    out.I = int(I)
+    out.row_ptr = np.ascontiguousarray(row_ptr, np.int64)
+    assert out.row_ptr.shape == (out.I + 1,) and out.row_ptr[0] == 0 and np.all(np.diff(out.row_ptr) >= 0)
+    D = int(out.row_ptr[-1])
+    pad = lambda a, dt: np.ascontiguousarray(a if D else np.zeros(1), dt)      # (never a null pointer)
+    out.col, out.sim, out.mutu, out.nij = pad(col, np.int32), pad(sim, np.float64), pad(mutu, np.int32), pad(nij, np.int32)
+    assert all(len(a) == max(D, 1) for a in (out.col, out.sim, out.mutu, out.nij))
+    assert D == 0 or (out.col.min() >= 0 and out.col.max() < out.I)
+    out.info = np.ascontiguousarray(info, np.float64)
+    assert out.info.shape == (out.I, 4)
+    out.uavg = None
+    out.n_eval = out.n_contrib = 0
+    out.seconds = (0.0, 0.0, 0.0)
+    out._own = _XoSim(I=out.I, n_eval=0, n_contrib=0, row_ptr=_p(out.row_ptr, C.c_int64), col=_p(out.col, C.c_int32),
+                      sim=_p(out.sim, C.c_double), mutu=_p(out.mutu, C.c_int32), nij=_p(out.nij, C.c_int32))
+    out._h = C.pointer(out._own)
+    out._borrowed = True         # the arrays are NumPy's: never free()d by the library
+    if D == 0:
+        out.col, out.sim, out.mutu, out.nij = out.col[:0], out.sim[:0], out.mutu[:0], out.nij[:0]
+    return out
+
+
 def sim_free(S):
     if getattr(S, "_h", None) is not None:
-        lib().xo_sim_free(S._h)
+        if not getattr(S, "_borrowed", False):
+            lib().xo_sim_free(S._h)
         S._h = None
 
 

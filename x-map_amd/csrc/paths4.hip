@@ -421,9 +421,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(P_WAVES, P_
     }
 }
 
-// precondition of the bare division sequence (div_mid): every kept pair has a positive, finite mutuality within 2^+-100
-// and a product sim * mutu that is zero or within 2^+-400 -- then a path's mutuality sum is never zero and no operand is
-// near the ends of the exponent range.  What stage A produces always qualifies; records fed by a caller are checked.
+// precondition of the bare division sequence (div_mid): every kept pair has a mutuality >= 1 (an int32 count, so at most
+// 2^31 - 1) and a product sim * mutu that is zero (either sign) or strictly inside (2^-400, 2^400); NaN and inf fail both
+// tests -- then a path's mutuality sum is never zero and no operand is near the ends of the exponent range.  What stage A
+// produces always qualifies; records fed by a caller are checked (every kept pair here; the listed pairs alone by the NumPy
+// twin in Engine.ext_tables_from_knn).  tests/test_gpu_fed_sim.py pins the answer at the bounds and compares the two
+// divisions bit for bit over the admitted range.
 __global__ __launch_bounds__(256) void k_edge_ranges(long long n, const double *sim, const int *mutu, int *bad) {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
