@@ -133,8 +133,10 @@ def item_sim(T, method, cap, uavg=None, info=None, nthreads=1, rows=None):
 
 
 def sim_from_arrays(I, row_ptr, col, sim, mutu, nij, info):
-    """A kept-pair matrix fed by the caller (CSR by first item, columns ascending; info [I][4] as item_info returns it) as a
-    Sim that extend() takes: xo_extend reads I, row_ptr, col, sim, mutu and nij of the struct and nothing else.  The struct is
+    """A kept-pair matrix fed by the caller (CSR by first item; info [I][4] as item_info returns it) as a Sim that extend()
+    takes: xo_extend reads I, row_ptr, col, sim, mutu and nij of the struct and nothing else.  The entries of a row may come in
+    any order: B1-B4 sort them by (|sim| descending, column ascending), an explicit tie-break, so the tables do not depend on
+    it (tests/test_cpu_topk_rows.py: five storage orders, identical tables); item_sim's own rows have ascending columns.  The struct is
     built here over NumPy arrays the Sim keeps alive, so sim_free() drops it without handing it to xo_sim_free()."""
     out = Sim()
     out.I = int(I)

@@ -66,6 +66,120 @@ def test_dense_pieces(n_t, n_s):
     assert np.array_equal(val.cpu().numpy().view(np.uint32), ov.view(np.uint32))
 
 
+# ------------------------------------------------------------------------------------------------ designed families
+D_ROWS, D_TILE, D_MAXSPLIT = 256, 32, 16      # csrc/stage_d.hip
+
+
+def dense_segments(n_t, n_s, cus):
+    """Python restatement of dense_layout and of the segment loop of k_dense_topk (csrc/stage_d.hip): the (row block, first
+    tile, end tile) of every piece, and the largest number of pieces of a row block"""
+    n_tiles = max((n_s + D_TILE - 1) // D_TILE, 1)
+    n_rb = (n_t + D_ROWS - 1) // D_ROWS
+    total = n_rb * n_tiles
+    share = max((total + cus - 1) // cus, (n_tiles + D_MAXSPLIT - 3) // (D_MAXSPLIT - 2), 16)
+    n_wg = (total + share - 1) // share
+    segs = []
+    for wg in range(n_wg):
+        at, w_hi = wg * share, min(total, (wg + 1) * share)
+        while at < w_hi:
+            rb = at // n_tiles
+            t0 = at - rb * n_tiles
+            t1 = min(n_tiles, t0 + (w_hi - at))
+            segs.append((rb, t0, t1))
+            at += t1 - t0
+    n_pieces = max(((rb + 1) * n_tiles - 1) // share - (rb * n_tiles) // share + 1 for rb in range(n_rb))
+    return segs, n_pieces
+
+
+def designed_factors(family, n_t, n_s, K):
+    """(F_t, F_s) of one designed family (test_dense_topk_designed)"""
+    rng = np.random.RandomState(77)
+    Ft, Fs = np.zeros((n_t, K), np.float32), np.zeros((n_s, K), np.float32)
+    theta = (np.arange(n_s) + 1.0) / (n_s + 1.0) * (np.pi / 2)
+    if family in ("alphabet8", "short_piece"):      # source rows: +- copies of 8 prototypes
+        Ft = rng.standard_normal((n_t, K)).astype(np.float32)
+        proto = rng.standard_normal((8, K)).astype(np.float32)
+        Fs = proto[rng.randint(0, 8, n_s)] * np.where(rng.rand(n_s) < 0.5, -1.0, 1.0).astype(np.float32)[:, None]
+    elif family == "all_equal":                     # one source row repeated
+        Ft = rng.standard_normal((n_t, K)).astype(np.float32)
+        Fs[:] = rng.standard_normal(K).astype(np.float32)
+    elif family in ("ascending", "descending"):     # |sim| grows (falls) with the column: every tile raises the bar (none passes)
+        Ft[:, 0] = 1.0
+        Fs[:, 0], Fs[:, 1] = np.sin(theta), np.cos(theta)
+        if family == "descending":
+            Fs = Fs[::-1].copy()
+    elif family == "subnormal":                     # every product is m_j * 2^-140: an fp32 subnormal
+        Ft[:, 0], Ft[:, 1] = 1.0, 2.0 ** -70
+        Fs[:, 1] = 2.0 ** -70 * rng.randint(1, 1001, n_s)
+        Fs[:, 2] = 1.0
+    else:
+        raise ValueError(family)
+    return Ft, Fs
+
+
+DESIGNED = [(f, 300, 4500, 50) for f in ("alphabet8", "all_equal", "ascending", "descending", "subnormal")] + \
+           [("short_piece", 300, 4609, 64)]
+
+
+@pytest.mark.parametrize("K", [64, 128])
+@pytest.mark.parametrize("family,n_t,n_s,k", DESIGNED, ids=[d[0] for d in DESIGNED])
+def test_dense_topk_designed(family, n_t, n_s, k, K):
+    """The register insertion of k_dense_topk (a candidate passes |v| >= thr, its place comes from ballot + popcount, place
+    >= k drops it) and k_dense_merge on inputs standard_normal factors never give -- the comparison of
+    test_dense_topk_bit_exact, on several pieces per row block:
+      alphabet8    8 values of |sim| per row: every list is cut inside a tie of hundreds, and the tie spans the pieces
+      all_equal    one value: the first k columns win, every later candidate passes the threshold and loses on the index
+      ascending    every tile raises the bar: the last k columns, the last one first
+      descending   no tile passes after the first two of a piece: the first k columns
+      subnormal    all listed values are fp32 subnormals (the guide: MFMA keeps them; not measured on this kernel before)
+      short_piece  k = 64 and a piece of ONE tile that holds fewer than 64 columns: a partial list with padding is merged"""
+    import ctypes as C
+    import torch
+    from oracle import xmap_oracle as xo
+    from xmap.engine import hipabi as abi
+    eng, _ = engine()
+    npc = C.c_int32(0)
+    abi.check(abi.lib.xmap_dense_layout(abi.i32(n_t), abi.i32(n_s), C.byref(npc)))
+    assert npc.value > 1
+    segs, n_pieces = dense_segments(n_t, n_s, torch.cuda.get_device_properties(0).multi_processor_count)
+    assert n_pieces == npc.value
+    if family == "short_piece":
+        assert any(t1 - t0 == 1 and min(n_s, t1 * D_TILE) - t0 * D_TILE < 64 for _, t0, t1 in segs)
+    Ft, Fs = designed_factors(family, n_t, n_s, K)
+    oi, ov = xo.dense_topk(xo.dense_normalize(Ft), xo.dense_normalize(Fs), k)
+    oa = np.abs(ov)
+    # what the family is there for, on the oracle
+    if family in ("alphabet8", "short_piece"):
+        assert np.all(oa[:, k - 1] == oa[:, k - 2]) and np.all(oa[:, 0] == oa[:, k - 1])
+        _, proto = np.unique(np.abs(Fs), axis=0, return_inverse=True)      # the tie of every prototype has columns in the pieces:
+        proto = proto.reshape(-1)                                          # full partial lists of it lose in the merge
+        assert proto.max() == 7 and np.bincount(proto).min() > 8 * k
+        for p in range(8):
+            assert sum(1 for _, t0, t1 in segs if (proto[t0 * D_TILE:t1 * D_TILE] == p).sum() >= k // 2) >= len(segs) - 2
+    if family in ("all_equal", "descending"):
+        assert np.array_equal(oi, np.tile(np.arange(k, dtype=np.int32), (n_t, 1)))
+    if family == "ascending":
+        assert np.array_equal(oi, np.tile(np.arange(n_s - 1, n_s - 1 - k, -1, dtype=np.int32), (n_t, 1)))
+    if family in ("ascending", "descending"):
+        assert np.all(oa[:, :-1] > oa[:, 1:])
+    if family == "subnormal":
+        assert ov.size == 15000 and np.all(oa > 0) and np.all(oa < np.finfo(np.float32).tiny)
+    idx, val = eng.dense_topk(Ft, Fs, k)
+    idx, val = idx.cpu().numpy(), val.cpu().numpy()
+    if family == "subnormal" and not np.array_equal(val.view(np.uint32), ov.view(np.uint32)):
+        bad = np.nonzero(val.view(np.uint32) != ov.view(np.uint32))
+        print("subnormal: %d of %d values differ; first: device %08x (index %d), oracle %08x (index %d)" % (
+            len(bad[0]), val.size, val.view(np.uint32)[bad][0], idx[bad][0], ov.view(np.uint32)[bad][0], oi[bad][0]))
+    assert np.array_equal(idx, oi)
+    assert np.array_equal(val.view(np.uint32), ov.view(np.uint32))
+    # size-independent properties: sorted by (|v| desc, idx asc), padding only at the tail
+    a = np.abs(val)
+    assert np.all(a[:, :-1] >= a[:, 1:])
+    tie = (a[:, :-1] == a[:, 1:]) & (idx[:, 1:] >= 0)
+    assert np.all(idx[:, :-1][tie] < idx[:, 1:][tie])
+    assert np.all((idx >= 0).sum(1) == min(k, n_s))
+
+
 def test_dense_normalize_matches_oracle_and_fp64():
     import torch
     from oracle import xmap_oracle as xo
