@@ -293,6 +293,18 @@ def test_hub_items_through_the_coarse_abi(method):
 
 
 @pytest.mark.parametrize("method", METHODS)
+def test_wide_light_rows_through_the_coarse_abi(method):
+    """light rows of 2 048 raters and more (test_cpu_stage_a_layout.wide_few: at the coarse stage A's own parameters, ch_min = 2048
+    and slot_target = 768, two hubs of exactly 2 048 raters are class 4, five heavier ones heavy): the default route launches
+    the 16-wave table; every stage against the oracle"""
+    from test_cpu_stage_a_layout import plan_of, wide_few
+    r, hubs = wide_few()
+    P = plan_of("wide_few", 2048, 768)
+    assert int((P.cls == 4).sum()) == 2 and P.n_heavy == 5
+    check_coarse(r, method, (5,), need=dict(paths=1000, mapped=1))
+
+
+@pytest.mark.parametrize("method", METHODS)
 def test_long_profiles_through_the_coarse_abi(method):
     from xmap.engine import synth
     r = synth.make_two_domain(21, 600, 1500, 1500, overlap=0.5, mu=4.0, sigma=1.6)

@@ -307,7 +307,11 @@ def test_long_profiles_and_popular_items(dev, method):
     T = xo.Train(r.user_ptr, r.item, r.rating, r.time, r.n_items, *attrs)
     So = xo.item_sim(T, method, CAP, nthreads=8)
     orow, ocol = csr_to_pairs(So.row_ptr, So.col)
-    for S in (eng.item_sim(method, CAP), eng.item_sim_tri(method, CAP, ch_min=64), eng.item_sim(method, CAP, algo="rows")):
+    from test_cpu_stage_a_layout import check_plan
+    for ch_min, S in ((2048, eng.item_sim(method, CAP)), (64, eng.item_sim_tri(method, CAP, ch_min=64)),
+                      (None, eng.item_sim(method, CAP, algo="rows"))):
+        if ch_min is not None:      # the device's plan against its NumPy statement (test_cpu_stage_a_layout.py); 600 users: at 2048
+            check_plan(S, r, ch_min)    # no threshold is searched (test_keys_larger_than_a_tile has the default one), at 64 one is
         assert S.n_eval == So.n_eval and S.n_contrib == So.n_contrib
         rows, cols, sim, mutu, nij = _sorted_sim(S)
         assert np.array_equal(rows, orow) and np.array_equal(cols, ocol)
@@ -356,6 +360,7 @@ def test_keys_larger_than_a_tile(dev, method):
     (round 3: one transposition, tile-sorted mirror; round 2: CSC + cursor-atomic mirror) against the oracle, bit for bit."""
     from oracle import xmap_oracle as xo
     from xmap.engine import synth
+    from test_cpu_stage_a_layout import check_plan
     r, hubs = hub_ratings()
     ptr, item, rating, time = r.user_ptr, r.item, r.rating, r.time
     assert np.bincount(item, minlength=r.n_items)[list(hubs)].tolist() == [r.n_users, r.n_users]
@@ -371,6 +376,7 @@ def test_keys_larger_than_a_tile(dev, method):
             os.environ["XMAP_A_V2"] = v2
             for ch_min in (1024, 64):
                 S = eng.item_sim_tri(method, CAP, ch_min=ch_min)
+                check_plan(S, r, ch_min)      # the device's plan against its NumPy statement (test_cpu_stage_a_layout.py)
                 assert S.n_eval == So.n_eval and S.n_contrib == So.n_contrib
                 rows, cols, sim, mutu, nij = _sorted_sim(S)
                 assert np.array_equal(rows, orow) and np.array_equal(cols, ocol)
@@ -388,6 +394,7 @@ def test_keys_larger_than_a_tile(dev, method):
     os.environ["XMAP_COUNT_PART_MIN"] = "1"
     try:
         S = eng.item_sim_tri(method, CAP)
+        assert check_plan(S, r, 2048).n_heavy == 2      # the default threshold, found among 8000 users: the two hubs are heavy
         rows, cols, sim, mutu, nij = _sorted_sim(S)
         assert np.array_equal(rows, orow) and np.array_equal(cols, ocol) and np.array_equal(sim, So.sim)
         assert np.array_equal(S.info.cpu().numpy(), So.info)

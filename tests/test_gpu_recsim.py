@@ -80,9 +80,18 @@ def _alterego_rows(seed, users, items):
     return u[o], it[o], ra[o], r
 
 
+# Rows of at least 2 048 entries (class 4 of the pair tables, here in its local-sensitivity form with 32-bit count halves): the
+# census of the two inputs below with the plan's statement (test_cpu_stage_a_layout.plan_statement; duplicates allowed, no heavy
+# set: ch_min = users + 2) finds none in the smaller one (600 items, 16 278 rows, the longest 940) and three in the larger one
+# (3 000 items, 114 749 rows, the longest 4 590), at both slot targets: the class runs below full size, so no input is added.
+WIDE_ROWS = {(3000, 600): 0, (20000, 3000): 3}
+
+
 @pytest.mark.parametrize("users,items", [(3000, 600), (20000, 3000)])
 def test_rec_sim_vs_oracle_on_alterego_rows(users, items):
+    import types
     from oracle import xmap_oracle as xo
+    from test_cpu_stage_a_layout import check_plan
     u, it, ra, r = _alterego_rows(7, users, items)
     # make sure items held twice by a user (a pass-through and a mapped rating of one target item) are present, also
     # three times, also in long profiles: every 7th user repeats its first (and every 21st also its last) item
@@ -111,6 +120,8 @@ def test_rec_sim_vs_oracle_on_alterego_rows(users, items):
     O = xo.rec_sim(ptr, item, rating, len(ii), 50)
     for slot_target in (640, 24):           # 24: rows cut into many hash partitions
         S = eng.rec_sim(50, slot_target=slot_target)
+        P = check_plan(S, types.SimpleNamespace(user_ptr=ptr, item=item, n_items=len(ii)), len(uu) + 2, dups=True)
+        assert int((P.cls == 4).sum()) == int((P.n >= 2048).sum()) == WIDE_ROWS[(users, items)] and P.n_heavy == 0
         a, b, sim, ls, nij = _pairs(S, len(ii))
         orow, ocol, osim, ols, onij = _oracle_pairs(O, len(ii))
         assert np.array_equal(a, orow) and np.array_equal(b, ocol) and np.array_equal(nij, onij)

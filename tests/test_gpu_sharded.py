@@ -51,17 +51,20 @@ def _summary(res):
                 ae_user=G.user.cpu().numpy(), ae_item=G.item.cpu().numpy(), ae_rating=G.rating.cpu().numpy())
 
 
-def _ratings(frac=False):
+def _ratings(frac=False, name=None):
     """the input of these tests; frac: the same structure with non-integer ratings (synth.fractional, seeded: every
-    spawned worker rebuilds the same input)"""
+    spawned worker rebuilds the same input); name: a designed layout of test_cpu_stage_a_layout.py instead (seeded as well)"""
     from xmap.engine import synth
+    if name is not None:
+        from test_cpu_stage_a_layout import family
+        return family(name)
     r = synth.make_two_domain(21, 4000, 700, 700)
     return synth.fractional(r, seed=21) if frac else r
 
 
-def _engine(dev="cuda:0", frac=False):
+def _engine(dev="cuda:0", frac=False, name=None):
     from xmap.engine import device
-    r = _ratings(frac)
+    r = _ratings(frac, name)
     return device.Engine(device.DeviceRatings(r.user_ptr, r.item, r.rating, r.time, r.n_items, r.item_attrs(), dev))
 
 
@@ -89,10 +92,10 @@ def _rccl_world():
     return n
 
 
-def _worker(rank, world, port, q, backend="gloo", method="adjust_cosine", frac=False):
+def _worker(rank, world, port, q, backend="gloo", method="adjust_cosine", frac=False, name=None):
     dist, dev = _init(rank, world, port, backend)
     from xmap.engine import sharded
-    res = sharded.run_step(_engine(dev, frac), method, 50, 5, True, dist, rank, world)
+    res = sharded.run_step(_engine(dev, frac, name), method, 50, 5, True, dist, rank, world)
     q.put((rank, _summary(res)))
     dist.barrier()
     dist.destroy_process_group()
@@ -134,28 +137,36 @@ def test_item_sharded_over_rccl_equals_world1():
     _check_world_equals_world1(_rccl_world(), "nccl")
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_world2_equals_world1(world):
-    _check_world_equals_world1(world, "gloo")
+@pytest.mark.parametrize("world,name", [pytest.param(2, None, id="2"), pytest.param(3, None, id="3"),
+                                        pytest.param(2, "wide_many", id="2-wide_many")])
+def test_world2_equals_world1(world, name):
+    """name = wide_many (test_cpu_stage_a_layout.py) at the step's own parameters (ch_min 2048, slot_target 768): 47 heavy rows,
+    dealt round-robin over the ranks, next to a class-4 row.  Every item of that input has a neighbour in the other domain (the
+    hubs), so no path starts: its comparison is about stage A, the knn tables and the AlterEgo rows."""
+    if name is not None:
+        from test_cpu_stage_a_layout import plan_of
+        P = plan_of(name, 2048, 768)
+        assert P.n_heavy == 47 and int((P.cls == 4).sum()) == 1 and int((P.C > 0).sum()) == 46
+    _check_world_equals_world1(world, "gloo", name=name, paths=name is None)
 
 
-def _check_world_equals_world1(world, backend, method="adjust_cosine", frac=False):
+def _check_world_equals_world1(world, backend, method="adjust_cosine", frac=False, name=None, paths=True):
     import torch
     import torch.multiprocessing as mp
     assert torch.cuda.is_available()
     from xmap.engine import sharded
-    ref = _summary(sharded.run_step(_engine(frac=frac), method, 50, 5, True))
+    ref = _summary(sharded.run_step(_engine(frac=frac, name=name), method, 50, 5, True))
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q, backend, method, frac)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, backend, method, frac, name)) for r in range(world)]
     for p in procs:
         p.start()
     got = _collect(q, procs, world)
     for p in procs:
         p.join(120)
         assert p.exitcode == 0
-    assert ref["n_kept"] > 0 and ref["n_paths"] > 0 and ref["n_rows"] > 0
+    assert ref["n_kept"] > 0 and (ref["n_paths"] > 0) == paths and ref["n_rows"] > 0      # (paths=False: an input known to start none)
     for rank, out in got:
         for key, v in ref.items():
             if key in ("row_ptr", "col", "sim"):
@@ -236,21 +247,27 @@ def _check_multidomain(world, backend):
             assert np.array_equal(out[key], v), (rank, key)
 
 
-def _user_share(rank, world, dev="cuda:0", frac=False):
-    """the complete profiles of a contiguous share of the users (items indexed globally)"""
-    from xmap.engine import device
-    r = _ratings(frac)
+def _share_arrays(r, rank, world):
+    """(first user, user_ptr, item, rating, time) of rank's contiguous share of the users"""
     lo, hi = r.n_users * rank // world, r.n_users * (rank + 1) // world
     e0, e1 = int(r.user_ptr[lo]), int(r.user_ptr[hi])
     ptr = (r.user_ptr[lo:hi + 1] - r.user_ptr[lo]).astype(np.int64)
-    R = device.DeviceRatings(ptr, r.item[e0:e1].copy(), r.rating[e0:e1].copy(), r.time[e0:e1].copy(), r.n_items, r.item_attrs(), dev)
+    return lo, ptr, r.item[e0:e1].copy(), r.rating[e0:e1].copy(), r.time[e0:e1].copy()
+
+
+def _user_share(rank, world, dev="cuda:0", frac=False, name=None):
+    """the complete profiles of a contiguous share of the users (items indexed globally)"""
+    from xmap.engine import device
+    r = _ratings(frac, name)
+    lo, ptr, item, rating, time = _share_arrays(r, rank, world)
+    R = device.DeviceRatings(ptr, item, rating, time, r.n_items, r.item_attrs(), dev)
     return device.Engine(R), lo
 
 
-def _users_worker(rank, world, port, method, q, backend="gloo", frac=False):
+def _users_worker(rank, world, port, method, q, backend="gloo", frac=False, name=None):
     dist, dev = _init(rank, world, port, backend)
     from xmap.engine import sharded
-    eng, lo = _user_share(rank, world, dev, frac)
+    eng, lo = _user_share(rank, world, dev, frac, name)
     res = sharded.run_step_users(eng, lo, method, 50, 5, True, dist)
     out = _summary(res)
     out["info"] = res["info"].cpu().numpy()
@@ -265,26 +282,41 @@ def test_user_sharded_over_rccl_equals_world1():
     _check_user_sharded(_rccl_world(), "adjust_cosine", "nccl")
 
 
-@pytest.mark.parametrize("world,method", [(2, "adjust_cosine"), (3, "cosine"), (4, "adjust_cosine")])
-def test_user_sharded_equals_world1(world, method):
+@pytest.mark.parametrize("world,method,name", [
+    pytest.param(2, "adjust_cosine", None, id="2-adjust_cosine"), pytest.param(3, "cosine", None, id="3-cosine"),
+    pytest.param(4, "adjust_cosine", None, id="4-adjust_cosine"),
+    pytest.param(2, "adjust_cosine", "wide_few", id="2-adjust_cosine-wide_few"), pytest.param(2, "cosine", "wide_few", id="2-cosine-wide_few")])
+def test_user_sharded_equals_world1(world, method, name):
     """BASELINE configs[2]'s other split: every rank holds a share of the USERS, the partial similarities of a pair are
     sent to the rank that owns it and added up there (sharded.run_step_users).  Item statistics, similarity matrix, extension,
-    replacements and AlterEgo rows must be those of one rank over all ratings, bit for bit."""
-    _check_user_sharded(world, method, "gloo")
+    replacements and AlterEgo rows must be those of one rank over all ratings, bit for bit.
+    name = wide_few (test_cpu_stage_a_layout.py): a share of 2 000 users of the default input cannot hold an item of 2 048
+    raters, so its popular items never reach the 16-wave table of the raw step (no heavy set, nothing filtered); each half of
+    wide_few's 4 300 users holds the two all-user hubs with 2 150 raters -- checked here on the shares' own arrays, with the
+    plan's statement at the step's parameters (ch_min = users of the share + 2, slot_target 768)."""
+    if name is not None:
+        from test_cpu_stage_a_layout import plan_statement
+        r = _ratings(name=name)
+        for rank in range(world):
+            lo, ptr, item, _, _ = _share_arrays(r, rank, world)
+            assert np.bincount(item, minlength=r.n_items).max() >= 2048, rank
+            P = plan_statement(ptr, item, r.n_items, max(64, len(ptr) - 1 + 2), 768)
+            assert P.n_heavy == 0 and int((P.cls == 4).sum()) == 1, rank           # (the heavier all-user hub has no heavier partner)
+    _check_user_sharded(world, method, "gloo", name=name)
 
 
-def _check_user_sharded(world, method, backend, frac=False):
+def _check_user_sharded(world, method, backend, frac=False, name=None):
     import torch
     import torch.multiprocessing as mp
     assert torch.cuda.is_available()
     from xmap.engine import sharded
-    one = sharded.run_step(_engine(frac=frac), method, 50, 5, True)
+    one = sharded.run_step(_engine(frac=frac, name=name), method, 50, 5, True)
     ref = _summary(one)
     ref["info"] = one["S"].info.cpu().numpy()
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_users_worker, args=(r, world, port, method, q, backend, frac)) for r in range(world)]
+    procs = [ctx.Process(target=_users_worker, args=(r, world, port, method, q, backend, frac, name)) for r in range(world)]
     for p in procs:
         p.start()
     got = _collect(q, procs, world)
