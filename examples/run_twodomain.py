@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -15,6 +15,10 @@ three test users (xmap.engine.session.recommend_topn).
 
 --explain (with --device-tail): under each of those lists, why every item is there (the explain= option of recommend_topn: the
 three strongest evidence entries of its score with their share, and the user's own ratings each AlterEgo row came from).
+
+--audience (with --device-tail): the other direction -- for three target items the ten users to tell about them
+(xmap.engine.session.recommend_audience: the users whose own rows give evidence for the item and who do not hold it yet, by
+the same unrounded prediction).
 
 --fold-in (with --device-tail): five test users are kept out of training altogether, as users who arrive afterwards would be.
 The model is trained without them; their ratings (the source domain's, for a user known only there) are then folded in
@@ -84,6 +88,7 @@ def main(argv=None):
     ap.add_argument("--device-tail", action="store_true")
     ap.add_argument("--fold-in", action="store_true")
     ap.add_argument("--explain", action="store_true")
+    ap.add_argument("--audience", action="store_true")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -109,6 +114,8 @@ def main(argv=None):
     targetRDD = timed("clean_target", assist.baseliner_clean_data_pipeline, sc, clean_t,
                       os.path.join(hdfs, para["init"]["path_movie"]), para["init"]["is_debug"], para["init"]["num_partition"])
     trainRDD, testRDD = timed("split", assist.baseliner_split_data_pipeline, sc, split, sourceRDD, targetRDD)
+    if args.audience and (not args.device_tail or para["recommender"]["private_flag"]):
+        ap.error("--audience needs --device-tail and the non-private recommender")
     late = []                   # (uid, profile) of the users who arrive after training
     if args.fold_in:
         if not args.device_tail or para["recommender"]["private_flag"]:
@@ -160,6 +167,12 @@ def main(argv=None):
                 for nid, s, rating, share, sources, n_all in entries:
                     cited = ", ".join("%s rated %s" % (sid, sr) for sid, sr, _ in sources) + (", ..." if n_all > len(sources) else "")
                     print("    %+.3f  %s (similarity %.3f, your AlterEgo rating %.2f)  <-  %s" % (share, nid, s, rating, cited))
+    if args.audience:
+        # the other direction: whom to tell about an item (here: the first three items that have a neighbour list)
+        aud = timed("audience", session.recommend_audience, alterEgo_profile, sorted(top.sim_pairs)[:3], rc["calculate_xmap_weighting"],
+                    rc["mapping_range"], rc["decay_alpha"], 10)
+        for iid, lst in aud.collect():
+            print("audience of %s:" % iid, ", ".join("%s (%.3f)" % (uid, plain) for uid, plain, _ in lst) or "no evidence")
     if late:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         top = timed("fold_in_topn", session.recommend_topn_profiles, alterEgo_profile, late, w, k, alpha, 5)

@@ -596,6 +596,36 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                    int64_t *h_stats /* host, [4] or NULL: candidates scored, candidates dropped (status 2),
                                        largest `now`, largest candidate count of one query */);
 
+/* ---- audience of an item (csrc/stage_e_audience.hip): per query item the n_top best USERS among those whose own rows give
+ * evidence for it, ranked by the UNROUNDED prediction -- xmap_topn_rows seen from the item.  Same arrays as xmap_topn_rows, in its
+ * order; query_item replaces query_user and out_user replaces out_item.
+ *   candidates of item i: the users u whose profile holds at least one of the first min(nb_cnt[i], keep) neighbours of i (an
+ *     entry outside [0, I) is ignored) and -- without XMAP_AUDIENCE_KEEP_HOLDERS -- who do not hold i itself.  (u, i) is a
+ *     candidate pair here iff i is a candidate of u in xmap_topn_rows (KEEP_HOLDERS <-> KEEP_HELD).  Within a query the
+ *     candidates are scored in ascending user index, each once (also a user who holds a neighbour twice, or two neighbours).
+ *   scores: `plain` and `decayed` of the pair (u, i), the values xmap_predict_rows holds before bound_rating -- the same kernel
+ *     body over the candidate list, so the same bits as xmap_topn_rows gives the pair.  A candidate xmap_predict_rows would give
+ *     status 2 (zero weight sum, non-finite value, now > n_w) is dropped and counted.
+ *   ranking: by rank_by (0 plain, 1 decayed) descending, user index ascending on equal scores (scores compare as numbers:
+ *     -0.0 == 0.0).
+ *   outputs per query q (device): out_cnt[q] = min(n_top, candidates kept); out_user [q][n_top] (-1 behind the count),
+ *     out_plain / out_decay [q][n_top] (0.0 behind the count).  1 <= n_top <= 1024; keep <= 64; n_users < 2^31.  A query item
+ *     outside [0, n_items) or with nb_cnt <= 0 gets count 0; query items may repeat, in any order.  The result is a pure function
+ *     of the inputs: it depends neither on the grid nor on the order of any atomic.
+ *   h_stats (host, [4] or NULL): candidates scored, candidates dropped, the largest `now` met (beyond n_w: call again with a
+ *     table of that length, as with xmap_predict_rows), the largest candidate count of one query.
+ * Passes: holders = the profiles by item (count, scan, fill: 8 B per profile row, built inside every call) -> candidates per
+ * query through an LDS bitmap of the user space, window by window (count, scan, fill: buffers of exactly the counted size) ->
+ * scores -> segmented selection, one block per query.  Temporaries from the stream's arena.  Syncs. */
+#define XMAP_AUDIENCE_KEEP_HOLDERS 1
+int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                       int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                       const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                       const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
+                       int32_t *out_cnt, int32_t *out_user, double *out_plain, double *out_decay,
+                       int64_t *h_stats /* host, [4] or NULL: candidates scored, candidates dropped (status 2),
+                                           largest `now`, largest candidate count of one query */);
+
 /* ---- explanation of a recommendation (csrc/stage_e_explain.hip): WHY the score of a (user, item) pair is what it is -- the
  * strongest evidence entries of the score, and for each of those AlterEgo rows the raw ratings stage C made it from.
  * xmap_explain_rows: n_pairs pairs (typically the lists of xmap_topn_rows) against the arrays of xmap_predict_rows, in its
@@ -866,6 +896,14 @@ int xmap_union_fill(void *stream, int32_t n_parts, const xmap_union_part *parts 
  *   xmap_ctx_foldin_explain : the same over the fold-in batch: pair_user = indices into the batch, ex_row indexes the profiles of
  *                             xmap_ctx_foldin_download, src_pos the batch's own item / rating / time arrays (xmap_ctx_foldin
  *                             keeps the batch's raw ptr / item and its pass-through counts on the device, swapped in on success)
+ * Audience of an item (needs the same stages as xmap_ctx_recommend and is dropped by the same calls; works on a union context):
+ *   xmap_ctx_audience       : xmap_audience_rows over the resident profiles, lists and averages: host arrays in and out;
+ *                             n_query item indices, 1 <= n_top <= 1024, rank_by 0 plain / 1 decayed, flags 0 or
+ *                             XMAP_AUDIENCE_KEEP_HOLDERS; out_cnt [n_query], out_user / out_plain / out_decay [n_query][n_top];
+ *                             stats [4] (may be NULL) as h_stats; stats[2] > n_w: call again with a table of that length.
+ *                             Argument errors start no device work and leave the outputs untouched
+ *   xmap_ctx_foldin_audience : the same over the fold-in batch: out_user = indices into the batch ("which of the users who
+ *                             arrived today"); needs a batch and the neighbour lists, as xmap_ctx_foldin_recommend
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -943,6 +981,12 @@ int xmap_ctx_foldin_recommend(xmap_ctx *ctx, int64_t n_query, const int32_t *que
 int xmap_ctx_foldin_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
                             const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
                             int32_t *max_now);
+int xmap_ctx_audience(xmap_ctx *ctx, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
+                      int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user,
+                      double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
+int xmap_ctx_foldin_audience(xmap_ctx *ctx, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
+                             int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user,
+                             double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

@@ -7,6 +7,7 @@
 //   the recommender tail over the AlterEgo rows, device-resident:   -> xmap_ctx_rec_sim (assist.py:153-177)
 //                     -> xmap_ctx_rec_select | xmap_ctx_rec_set_neighbors (assist.py:179-192) -> xmap_ctx_predict (assist.py:195-207)
 //                                                                                  | xmap_ctx_recommend (top-N per query user)
+//                                                                                  | xmap_ctx_audience (top-N users per query item)
 //                                                                                  | xmap_ctx_evaluate_topn (top-N against held-out pairs)
 //   fold-in, for profiles that were not rows of the upload:  xmap_ctx_generate -> xmap_ctx_foldin (the batch's AlterEgo profiles)
 //                     -> [rec_sim -> rec_select] -> xmap_ctx_foldin_predict | xmap_ctx_foldin_recommend (the same kernels, the batch's rows)
@@ -952,6 +953,35 @@ static int recommend_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const
     return XMAP_OK;
 }
 
+static int audience_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
+                         int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain,
+                         double *out_decay, int64_t *stats) {
+    XM_ARG(n_top >= 1 && n_top <= 1024);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((flags & ~XMAP_AUDIENCE_KEEP_HOLDERS) == 0);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query >= 0 && (n_query == 0 || (query_item && out_cnt && out_user && out_plain && out_decay)));
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (n_query == 0) return XMAP_OK;
+    ScratchPool tmp;
+    int32_t *d_item, *d_cnt, *d_user;
+    double *d_w, *d_plain, *d_decay;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_item, query_item, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_user, m, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
+    XM_TRY(xmap_audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col,
+                              c->nb_sim, P.ptr, P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay, stats));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_user, (const int32_t *)d_user, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
 int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
                      const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
                      int32_t *max_now) {
@@ -966,6 +996,14 @@ int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, 
     XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
     return recommend_over(c, resident_profiles(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
                           out_decay, stats);
+}
+
+int xmap_ctx_audience(xmap_ctx *c, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                      const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain, double *out_decay,
+                      int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    return audience_over(c, resident_profiles(c), n_query, query_item, n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain,
+                         out_decay, stats);
 }
 
 // ---- fold-in ------------------------------------------------------------------------------------------------------------
@@ -1033,6 +1071,14 @@ int xmap_ctx_foldin_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query
     XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
     return recommend_over(c, foldin_profiles(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
                           out_decay, stats);
+}
+
+int xmap_ctx_foldin_audience(xmap_ctx *c, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                             const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain,
+                             double *out_decay, int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
+    return audience_over(c, foldin_profiles(c), n_query, query_item, n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain,
+                         out_decay, stats);
 }
 
 int xmap_ctx_foldin_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,

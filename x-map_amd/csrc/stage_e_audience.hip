@@ -1,0 +1,355 @@
+// stage_e_audience.hip -- the audience of an item on the device: for every query item the N best users among those whose own
+// rows give evidence for it, ranked by the unrounded prediction (DESIGN.md 4 "Audience").  The top-N recommendation seen from
+// the item: (u, i) is a candidate pair here iff i is a candidate of u in stage_e_topn.hip, and its two scores are the same
+// kernel's.  Everything it reads is what the tail leaves resident: user-major profiles, neighbour lists [I][keep], item averages.
+//
+//   k_au_holders<count | fill> : the item-major transposition of the profiles -- for item n the users whose profile holds n, one
+//                     entry per profile row (a user who holds an item twice appears twice) -- by count -> xmap_exclusive_scan ->
+//                     fill.  One thread per profile row (its user by bisection of prof_ptr); rows with an item outside [0, I)
+//                     are skipped; the order inside a row is whatever the atomics give: the candidate pass de-duplicates
+//                     through a bitmap and emits in index order.
+//   k_au_candidates : one block per query item, run twice (count, then fill into buffers of exactly the counted size).  The user
+//                     space is walked in windows of AU_WINDOW users; an LDS bitmap of the window takes the union of hold[n] over
+//                     the item's first min(cnt, keep) neighbours n -- at most 64 rows, each as long as the neighbour is popular,
+//                     so the whole block strides one row after the other, coalesced -- the holders of the item itself are
+//                     cleared again unless XMAP_AUDIENCE_KEEP_HOLDERS, and the marked users leave in ascending index.  The
+//                     second-level bitmap of stage_e_topn.hip (one bit per bitmap word that was touched) is all the emit pass
+//                     scans, and it zeroes exactly the words it visits: the window is cleared once per block, never per query.
+//   scoring         : k_predict_rows<., RAW = true> (predict_rows.h) over the (user, item) candidate list, unchanged.
+//   k_au_select     : segmented top-N, one block per query, for segments of up to a million candidates and N up to 1024.  The
+//                     block keeps the best CAP >= n_top keys seen so far sorted in LDS; the segment streams through in tiles,
+//                     a candidate that beats the current N-th key is staged behind them, and when the staging area cannot take
+//                     another tile the whole array is sorted again by a bitonic network.  A key is (score as an ordered
+//                     integer, position in the segment): the positions ascend with the user index, keys are distinct, and the
+//                     sorted prefix is the same whatever order the survivors were staged in.  Status 2: dropped and counted.
+// Every output position follows from the scans, so the result does not depend on the grid or on the order of the atomics.
+#include "common.h"
+#include "predict_rows.h"
+
+namespace xmap {
+
+constexpr int AU_WINDOW = 1 << 20;              // users per bitmap pass (128 KB of LDS + 4 KB of summary: one block per CU)
+constexpr int AU_WORDS = AU_WINDOW / 32;
+constexpr int AU_SUMMARY = AU_WORDS / 32;       // second level: bit w of word s = bitmap word 32 s + w was touched
+constexpr int AU_THREADS = 1024;                // 16 waves stride a holder row; thread t emits summary word t (thread order = user order)
+static_assert(AU_SUMMARY == AU_THREADS, "one summary word per thread");
+constexpr int AU_MAX_BLOCKS = 512;              // blocks of the candidate pass (grid-stride over the queries: the window is zeroed once per block)
+constexpr int AU_MAX_TOP = 1024;
+constexpr int AU_ROW_BLOCKS = 2048;             // blocks of the holders pass (grid-stride over the profile rows)
+constexpr int AU_SEL_THREADS = 256;             // threads of a selection block = candidates of a tile
+constexpr unsigned long long AU_NO_KEY = ~0ull; // behind every key of a finite score
+constexpr unsigned AU_NO_POS = 0xffffffffu;
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_au_holders(long long U, int I, const long long *pptr, const int *pitem, int *hcnt,
+                                                    const long long *hptr, int *huser) {
+    const long long n_rows = pptr[U];
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (long long)gridDim.x * blockDim.x) {
+        const int it = pitem[r];
+        if (it < 0 || it >= I) continue;
+        long long lo = 0, hi = U;               // the user of row r: the last u with pptr[u] <= r (users without rows are passed over)
+        while (hi - lo > 1) {
+            const long long mid = (lo + hi) >> 1;
+            if (pptr[mid] <= r) lo = mid; else hi = mid;
+        }
+        const int at = atomicAdd(&hcnt[it], 1);
+        if constexpr (FILL) huser[hptr[it] + at] = (int)lo;
+    }
+}
+
+__device__ __forceinline__ int au_block_scan(int v, int *total, int *smem) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) smem[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int k = 0; k < AU_THREADS / 64; k++) {
+        const int s = smem[k];
+        if (k < w) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query, const int *query_item, long long U, int I, int keep,
+                                                              int keep_holders, const int *nb_cnt, const int *nb_col,
+                                                              const long long *hptr, const int *huser, int *cand_cnt,
+                                                              const long long *cand_ptr, int *cand_user, int *cand_item) {
+    extern __shared__ unsigned int au_lds[];    // [AU_WORDS] bitmap of the window, [AU_SUMMARY] touched words (zero between queries),
+    unsigned int *bits = au_lds, *summ = au_lds + AU_WORDS;                                      // [AU_THREADS / 64] scan scratch
+    int *s_scan = (int *)(au_lds + AU_WORDS + AU_SUMMARY);
+    const int tid = threadIdx.x;
+    for (int k = tid; k < AU_WORDS + AU_SUMMARY; k += AU_THREADS) au_lds[k] = 0u;
+    __syncthreads();
+    for (long long q = blockIdx.x; q < n_query; q += gridDim.x) {
+        const int it = query_item[q];
+        int cnt = (it >= 0 && it < I) ? nb_cnt[it] : 0;
+        cnt = cnt < keep ? cnt : keep;
+        long long total = 0;
+        const long long out0 = FILL ? cand_ptr[q] : 0;
+        for (long long lo = 0; lo < U && cnt > 0; lo += AU_WINDOW) {
+            // mark: the block strides the holders of one neighbour after the other
+            for (int l = 0; l < cnt; l++) {
+                const int nb = nb_col[(size_t)it * keep + l];
+                if (nb < 0 || nb >= I) continue;        // ignored, as in the prediction
+                const long long r1 = hptr[nb + 1];
+                for (long long r = hptr[nb] + tid; r < r1; r += AU_THREADS) {
+                    const long long x = (long long)huser[r] - lo;
+                    if (x < 0 || x >= AU_WINDOW) continue;
+                    const int w = (int)(x >> 5);
+                    const unsigned int old = atomicOr(&bits[w], 1u << (x & 31));
+                    if (old == 0u) atomicOr(&summ[w >> 5], 1u << (w & 31));
+                }
+            }
+            __syncthreads();
+            if (!keep_holders) {                // a user who holds the item is no candidate (the word stays listed as touched)
+                const long long r1 = hptr[it + 1];
+                for (long long r = hptr[it] + tid; r < r1; r += AU_THREADS) {
+                    const long long x = (long long)huser[r] - lo;
+                    if (x >= 0 && x < AU_WINDOW) atomicAnd(&bits[x >> 5], ~(1u << (x & 31)));
+                }
+                __syncthreads();
+            }
+            // emit in ascending index: count per thread, scan over the block, write; the visited words are zeroed on the way
+            int c = 0;
+            unsigned int sw = summ[tid];
+            while (sw) {
+                const int j = __ffs(sw) - 1;
+                sw &= sw - 1;
+                c += __popc(bits[tid * 32 + j]);
+            }
+            int tot;
+            const int ex = au_block_scan(c, &tot, s_scan);
+            long long o = out0 + total + ex;
+            sw = summ[tid];
+            summ[tid] = 0u;
+            while (sw) {
+                const int w = tid * 32 + __ffs(sw) - 1;
+                sw &= sw - 1;
+                unsigned int bw = bits[w];
+                bits[w] = 0u;
+                if constexpr (FILL) {
+                    while (bw) {
+                        const int bit = __ffs(bw) - 1;
+                        bw &= bw - 1;
+                        cand_user[o] = (int)(lo + (long long)w * 32 + bit);
+                        cand_item[o] = it;
+                        o++;
+                    }
+                }
+            }
+            total += tot;
+            __syncthreads();
+        }
+        if constexpr (!FILL) {
+            if (tid == 0) cand_cnt[q] = (int)total;
+        }
+    }
+}
+
+// a finite score as an integer that ascends where the score DEscends; -0.0 and 0.0 get one key (scores compare as numbers)
+__device__ __forceinline__ unsigned long long au_key(double s) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(s + 0.0);        // -0.0 + 0.0 = 0.0
+    return (b >> 63) ? b : ~(b | (1ull << 63));         // negative: larger magnitude = later; positive: larger = earlier, before every negative
+}
+
+// ascending bitonic sort of (K, P)[0 .. 2 CAP), all threads of the block; keys (K, P) are distinct except among the blanks
+template <int CAP>
+__device__ __forceinline__ void au_sort(unsigned long long *K, unsigned *P) {
+    constexpr int N = 2 * CAP;
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int j = k >> 1; j >= 1; j >>= 1) {
+            for (int t = threadIdx.x; t < N / 2; t += AU_SEL_THREADS) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long ki = K[i], kl = K[l];
+                const unsigned pi = P[i], pl = P[l];
+                const bool gt = ki > kl || (ki == kl && pi > pl);
+                if (gt == ((i & k) == 0)) { K[i] = kl; K[l] = ki; P[i] = pl; P[l] = pi; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// K / P [0, CAP): the best keys so far, sorted; [CAP, 2 CAP): the staged survivors of the tiles since the last sort
+template <int CAP>
+__global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query, int n_top, int rank_by, const long long *cand_ptr,
+                                                              const int *cand_user, const double *plain, const double *decay,
+                                                              const int *status, int *out_cnt, int *out_user, double *out_plain,
+                                                              double *out_decay,
+                                                              unsigned long long *stats /*[0] dropped candidates, [1] largest segment*/) {
+    static_assert(CAP >= AU_SEL_THREADS && (CAP & (CAP - 1)) == 0, "the staging area takes a tile; bitonic sizes");
+    __shared__ unsigned long long K[2 * CAP];
+    __shared__ unsigned P[2 * CAP];
+    __shared__ int s_staged, s_dropped, s_have;
+    const int tid = threadIdx.x;
+    const long long q = blockIdx.x;
+    if (q >= n_query) return;
+    const long long a = cand_ptr[q], b = cand_ptr[q + 1];
+    const double *score = rank_by ? decay : plain;
+    for (int k = tid; k < 2 * CAP; k += AU_SEL_THREADS) { K[k] = AU_NO_KEY; P[k] = AU_NO_POS; }
+    if (tid == 0) { s_staged = 0; s_dropped = 0; s_have = 0; }
+    __syncthreads();
+    int dropped = 0;
+    long long p = a;
+    while (p < b) {
+        const int staged = s_staged;
+        __syncthreads();                        // every thread has read the count before a tile adds to it
+        const int tiles = (CAP - staged) / AU_SEL_THREADS;
+        if (tiles == 0) {                       // no room for another tile: sort, the best CAP stay, the staging area is blank again
+            au_sort<CAP>(K, P);
+            for (int k = CAP + tid; k < 2 * CAP; k += AU_SEL_THREADS) { K[k] = AU_NO_KEY; P[k] = AU_NO_POS; }
+            if (tid == 0) s_staged = 0;
+            __syncthreads();
+            continue;
+        }
+        // as many tiles as the staging area has room for, against one N-th key
+        const unsigned long long wk = K[n_top - 1];
+        const unsigned wp = P[n_top - 1];
+        for (int t = 0; t < tiles && p < b; t++, p += AU_SEL_THREADS) {
+            const long long x = p + tid;
+            if (x >= b) continue;
+            if (status[x] != 0) { dropped++; continue; }
+            const unsigned long long xk = au_key(score[x]);
+            const unsigned xp = (unsigned)(x - a);
+            if (xk < wk || (xk == wk && xp < wp)) {
+                const int at = CAP + atomicAdd(&s_staged, 1);
+                K[at] = xk; P[at] = xp;
+            }
+        }
+        __syncthreads();
+    }
+    if (s_staged > 0) au_sort<CAP>(K, P);
+    int have = 0;
+    for (int j = tid; j < n_top; j += AU_SEL_THREADS) {
+        const size_t o = (size_t)q * n_top + j;
+        const unsigned pos = P[j];
+        const bool v = pos != AU_NO_POS;
+        have += v ? 1 : 0;
+        out_user[o] = v ? cand_user[a + pos] : -1;
+        out_plain[o] = v ? plain[a + pos] : 0.0;
+        out_decay[o] = v ? decay[a + pos] : 0.0;
+    }
+    if (dropped) atomicAdd(&s_dropped, dropped);
+    if (have) atomicAdd(&s_have, have);
+    __syncthreads();
+    if (tid == 0) {
+        out_cnt[q] = s_have;
+        if (s_dropped) atomicAdd(&stats[0], (unsigned long long)s_dropped);
+        atomicMax(&stats[1], (unsigned long long)(b - a));
+    }
+}
+
+template <int CAP>
+static void au_select_launch(hipStream_t st, long long n_query, int n_top, int rank_by, const long long *cand_ptr, const int *cand_user,
+                             const double *plain, const double *decay, const int *status, int *out_cnt, int *out_user,
+                             double *out_plain, double *out_decay, unsigned long long *stats) {
+    k_au_select<CAP><<<dim3((unsigned)n_query), dim3(AU_SEL_THREADS), 0, st>>>(n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay,
+                                                                               status, out_cnt, out_user, out_plain, out_decay, stats);
+}
+
+}  // namespace xmap
+using namespace xmap;
+
+extern "C" {
+
+int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                       int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                       const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                       const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                       int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats) {
+    XM_SCOPE(stream);
+    hipStream_t st = (hipStream_t)stream;
+    XM_ARG(n_top >= 1 && n_top <= AU_MAX_TOP);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((flags & ~XMAP_AUDIENCE_KEEP_HOLDERS) == 0);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query >= 0 && n_query <= 2147483647ll && n_users >= 0 && n_users <= 2147483647ll && n_items >= 0 && keep >= 1 && keep <= 64 &&
+           prof_ptr);
+    XM_ARG(n_query == 0 || (query_item && out_cnt && out_user && out_plain && out_decay));
+    XM_ARG(n_items == 0 || (nb_cnt && nb_col && nb_sim && item_avg));
+    XM_ARG(n_users == 0 || (prof_item && prof_rating && prof_time));
+    if (h_stats) h_stats[0] = h_stats[1] = h_stats[2] = h_stats[3] = 0;
+    if (n_query == 0) return XMAP_OK;
+    const int I = n_items;
+    const size_t i1 = (size_t)(I ? I : 1);
+    // ---- holders: the profiles by item
+    int *hcnt = nullptr, *huser = nullptr;
+    long long *hptr = nullptr;
+    int64_t n_hold = 0;
+    XM_HIP(xm_malloc_async((void **)&hcnt, sizeof(int) * i1, st));
+    XM_HIP(xm_malloc_async((void **)&hptr, sizeof(long long) * (i1 + 1), st));
+    XM_HIP(hipMemsetAsync(hcnt, 0, sizeof(int) * i1, st));
+    if (I > 0 && n_users > 0) {
+        k_au_holders<false><<<dim3(AU_ROW_BLOCKS), dim3(256), 0, st>>>(n_users, I, (const long long *)prof_ptr, prof_item, hcnt, nullptr,
+                                                                       nullptr);
+        XM_LAUNCH_CHECK();
+    }
+    int rc = xmap_exclusive_scan_i32_to_i64(st, hcnt, (int64_t *)hptr, I, &n_hold);
+    if (rc) return rc;
+    XM_HIP(xm_malloc_async((void **)&huser, sizeof(int) * (size_t)(n_hold ? n_hold : 1), st));
+    if (n_hold > 0) {
+        XM_HIP(hipMemsetAsync(hcnt, 0, sizeof(int) * i1, st));
+        k_au_holders<true><<<dim3(AU_ROW_BLOCKS), dim3(256), 0, st>>>(n_users, I, (const long long *)prof_ptr, prof_item, hcnt, hptr, huser);
+        XM_LAUNCH_CHECK();
+    }
+    // ---- candidates: count, scan, fill
+    int *cand_cnt = nullptr, *cand_user = nullptr, *cand_item = nullptr;
+    long long *cand_ptr = nullptr;
+    int64_t n_pairs = 0;
+    XM_HIP(xm_malloc_async((void **)&cand_cnt, sizeof(int) * (size_t)n_query, st));
+    XM_HIP(xm_malloc_async((void **)&cand_ptr, sizeof(long long) * ((size_t)n_query + 1), st));
+    const size_t lds = sizeof(unsigned int) * (AU_WORDS + AU_SUMMARY + AU_THREADS / 64);
+    const unsigned cblocks = (unsigned)(n_query < AU_MAX_BLOCKS ? n_query : AU_MAX_BLOCKS);
+    const int keep_holders = flags & XMAP_AUDIENCE_KEEP_HOLDERS;
+    XM_HIP(hipFuncSetAttribute((const void *)k_au_candidates<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    XM_HIP(hipFuncSetAttribute((const void *)k_au_candidates<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_au_candidates<false><<<dim3(cblocks), dim3(AU_THREADS), lds, st>>>(n_query, query_item, n_users, I, keep, keep_holders, nb_cnt, nb_col,
+                                                                         hptr, huser, cand_cnt, nullptr, nullptr, nullptr);
+    XM_LAUNCH_CHECK();
+    rc = xmap_exclusive_scan_i32_to_i64(st, cand_cnt, (int64_t *)cand_ptr, n_query, &n_pairs);
+    if (rc) return rc;
+    double *plain = nullptr, *decay = nullptr;
+    int *status = nullptr;
+    int32_t max_now = 0;
+    if (n_pairs > 0) {
+        const size_t np = (size_t)n_pairs;
+        XM_HIP(xm_malloc_async((void **)&cand_user, sizeof(int) * np, st));
+        XM_HIP(xm_malloc_async((void **)&cand_item, sizeof(int) * np, st));
+        XM_HIP(xm_malloc_async((void **)&plain, sizeof(double) * np, st));
+        XM_HIP(xm_malloc_async((void **)&decay, sizeof(double) * np, st));
+        XM_HIP(xm_malloc_async((void **)&status, sizeof(int) * np, st));
+        k_au_candidates<true><<<dim3(cblocks), dim3(AU_THREADS), lds, st>>>(n_query, query_item, n_users, I, keep, keep_holders, nb_cnt,
+                                                                            nb_col, hptr, huser, nullptr, cand_ptr, cand_user, cand_item);
+        XM_LAUNCH_CHECK();
+        // ---- scores: the pair body of the prediction, unrounded
+        rc = predict_rows_run<true>(st, n_pairs, cand_user, cand_item, n_users, I, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
+                                    prof_rating, prof_time, item_avg, wtab, n_w, plain, decay, status, &max_now);
+        if (rc) return rc;
+    }
+    // ---- selection
+    unsigned long long *stats = nullptr;
+    XM_HIP(xm_malloc_async((void **)&stats, sizeof(unsigned long long) * 2, st));
+    XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 2, st));
+    if (n_top <= 256)
+        au_select_launch<256>(st, n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay, status, out_cnt, out_user, out_plain, out_decay,
+                              stats);
+    else
+        au_select_launch<1024>(st, n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay, status, out_cnt, out_user, out_plain,
+                               out_decay, stats);
+    XM_LAUNCH_CHECK();
+    unsigned long long h[2] = {0, 0};
+    XM_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st));
+    XM_HIP(hipStreamSynchronize(st));
+    if (h_stats) { h_stats[0] = n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = max_now; h_stats[3] = (int64_t)h[1]; }
+    return XMAP_OK;
+}
+}

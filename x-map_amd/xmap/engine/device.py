@@ -1616,6 +1616,33 @@ class Engine(object):
                                      vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
         return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
 
+    def audience(self, P, neighbors, query_item, item_avg, wtab, n_top, rank_by=0, keep_holders=False):
+        """The audience of an item on the device (xmap_audience_rows) over the profiles P of alterego_profiles: per query
+        item the n_top (1..1024) best users among those whose own rows give evidence for it, by the unrounded prediction
+        (rank_by 0: plain, 1: decayed; score descending, user index ascending); users who hold the item are left out unless
+        keep_holders.  topn() seen from the item: the same pairs, the same score bits.  neighbors, item_avg, wtab as predict()
+        takes them; query_item an int32 tensor (any order, repeats allowed; an index outside the items or an item without a
+        list: no users).  Returns (cnt [Q], user [Q][n_top] (-1 behind the count), plain, decayed [Q][n_top], stats) with stats
+        as topn() returns them."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        Q, n_top = int(query_item.numel()), int(n_top)
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        if not 1 <= n_top <= 1024:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 1024" % n_top)
+        out_cnt = self._empty(max(Q, 1), torch.int32)
+        out_user = self._empty((max(Q, 1), n_top), torch.int32)
+        out_plain = self._empty((max(Q, 1), n_top), torch.float64)
+        out_decay = self._empty((max(Q, 1), n_top), torch.float64)
+        h = (C.c_int64 * 4)(0, 0, 0, 0)
+        with self.timed("audience"):
+            check(lib.xmap_audience_rows(st, i64(Q), vp(query_item.contiguous()), i32(n_top), i32(rank_by),
+                                         i32(abi.AUDIENCE_KEEP_HOLDERS if keep_holders else 0), i64(P.n_users), i32(P.n_items), i32(keep),
+                                         vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(P.user_time),
+                                         vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()), vp(out_cnt), vp(out_user), vp(out_plain),
+                                         vp(out_decay), h))
+        return out_cnt[:Q], out_user[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
+
     def explain(self, P, neighbors, pair_user, pair_item, item_avg, wtab, n_ev, rank_by=0):
         """Why a pair scores what it scores (xmap_explain_rows, the pair body of predict() in its explain mode): for the (user,
         item) pairs -- int32 tensors, typically the lists of topn() -- the n_ev (1..16) strongest evidence entries of the

@@ -19,6 +19,7 @@ TOPC = 10
 MID_ROWS_SPAN = 36864     # XMAP_MID_ROWS_SPAN: columns of a middle-list row per LDS pass
 ERR_HIP, ERR_ARG, ERR_OVERFLOW, ERR_CAPACITY = -1, -2, -3, -4     # XMAP_ERR_* of include/xmap_hip.h
 TOPN_KEEP_HELD = 1        # XMAP_TOPN_KEEP_HELD: flag of xmap_topn_rows / xmap_ctx_recommend
+AUDIENCE_KEEP_HOLDERS = 1 # XMAP_AUDIENCE_KEEP_HOLDERS: flag of xmap_audience_rows / xmap_ctx_audience
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
 EXPLAIN_MAX_EV, EXPLAIN_MAX_SRC = 16, 8      # evidence entries per pair / source positions per entry of xmap_explain_*
@@ -93,14 +94,14 @@ EXPORTS = [
     "xmap_sim2_pairs", "xmap_sim2_scatter", "xmap_sim3_layout", "xmap_sim3_plan", "xmap_sim3_mircount", "xmap_sim3_mirror", "xmap_item_partials", "xmap_item_merge", "xmap_sim2_pack_partials",
     "xmap_sim2_sort_partials", "xmap_sim2_merge_partials", "xmap_sim2_pack_pairs", "xmap_sim2_unpack_pairs", "xmap_bridge_flags", "xmap_knn_classify", "xmap_knn_thresholds", "xmap_reverse_count", "xmap_reverse_count_att_rnn",
     "xmap_reverse_fill", "xmap_topc_from_lists", "xmap_path_weights", "xmap_extend_paths", 
-    "xmap_mid_rows_count", "xmap_mid_rows_place", "xmap_edge_ranges", "xmap_end_universe", "xmap_extend_cols", "xmap_extend_cols_slots", "xmap_nb_index", "xmap_path_plan", "xmap_end_order", "xmap_dense_normalize", "xmap_dense_layout", "xmap_dense_topk", "xmap_rec_select", "xmap_predict", "xmap_rec_profiles", "xmap_predict_rows", "xmap_mae", "xmap_topn_rows", "xmap_explain_rows", "xmap_explain_sources", "xmap_eval_users", "xmap_topn_eval", "xmap_select_map", "xmap_alterego_count", "xmap_alterego_fill", "xmap_foldin_count", "xmap_foldin_fill", "xmap_union_count", "xmap_union_fill",
+    "xmap_mid_rows_count", "xmap_mid_rows_place", "xmap_edge_ranges", "xmap_end_universe", "xmap_extend_cols", "xmap_extend_cols_slots", "xmap_nb_index", "xmap_path_plan", "xmap_end_order", "xmap_dense_normalize", "xmap_dense_layout", "xmap_dense_topk", "xmap_rec_select", "xmap_predict", "xmap_rec_profiles", "xmap_predict_rows", "xmap_mae", "xmap_topn_rows", "xmap_audience_rows", "xmap_explain_rows", "xmap_explain_sources", "xmap_eval_users", "xmap_topn_eval", "xmap_select_map", "xmap_alterego_count", "xmap_alterego_fill", "xmap_foldin_count", "xmap_foldin_fill", "xmap_union_count", "xmap_union_fill",
     "xmap_feed_text", "xmap_feed_texts", "xmap_feed_merge", "xmap_feed_sizes", "xmap_feed_arrays", "xmap_feed_ids", "xmap_feed_free",
     "xmap_ctx_upload_feed", "xmap_feed_format", "xmap_ctx_create", "xmap_ctx_destroy", "xmap_check_ratings", "xmap_ctx_upload_ratings", "xmap_ctx_item_sim", "xmap_ctx_sim_download", "xmap_ctx_extend",
     "xmap_ctx_ext_download", "xmap_ctx_ext_lists", "xmap_ctx_candidates", "xmap_ctx_generate", "xmap_ctx_gen_download",
     "xmap_ctx_rec_sim", "xmap_ctx_rec_profiles_download", "xmap_ctx_rec_download", "xmap_ctx_rec_select", "xmap_ctx_rec_set_neighbors",
     "xmap_ctx_rec_neighbors_download", "xmap_ctx_predict", "xmap_ctx_recommend", "xmap_ctx_evaluate_topn",
     "xmap_ctx_foldin", "xmap_ctx_foldin_download", "xmap_ctx_foldin_recommend", "xmap_ctx_foldin_predict", "xmap_ctx_union",
-    "xmap_ctx_explain", "xmap_ctx_foldin_explain",
+    "xmap_ctx_explain", "xmap_ctx_foldin_explain", "xmap_ctx_audience", "xmap_ctx_foldin_audience",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -654,6 +654,57 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     return res
 
 
+def recommend_audience(alterEgoRDD, items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None):
+    """The audience of an item on the device from an AlterEgoRDD handle -- recommend_topn the other way round: the set-up of
+    recommend_topn, then for every iid of `items` the n (1..1024) best users among those whose own rows give evidence for it,
+    ranked by the unrounded prediction -- without temporal decay, or with (decay=True, alpha) -- score descending, user INDEX
+    (the order of the train set's users) ascending on equal scores; users who already hold the item are left out unless
+    keep_holders (Engine.audience).  Returns a LocalRDD of (iid, [(uid, plain, decayed)*]) in the order of `items`; an iid the
+    train set does not know gives (iid, []).  It carries .sim_pairs, .item_info and .stats like recommend_topn (.stats[3]: the
+    largest candidate count of an item).  The scores of a (uid, iid) pair are the bits recommend_topn gives it."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_audience")
+    iids = list(items.collect()) if hasattr(items, "collect") else list(items)
+    res = _audience_records(st, eng2, P, nb, item_avg, iids, st.idt.uids, alpha, n, decay, keep_holders, getattr(items, "ctx", None))
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
+def _audience_records(st, eng2, P, nb, item_avg, iids, uids, alpha, n, decay, keep_holders, ctx):
+    """what recommend_audience and recommend_audience_profiles share: the audiences of the items `iids` among the users of P,
+    labelled `uids` by index -> the LocalRDD of (iid, [(uid, plain, decayed)*]) with .stats"""
+    import torch
+    idt, dev = st.idt, st.engine.dev
+    d_q = torch.from_numpy(np.fromiter((idt.iidx.get(iid, -1) for iid in iids), np.int32, len(iids))).to(dev)
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        cnt, user, plain, decayed, stats = eng2.audience(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_holders)
+        if stats[2] <= n_w:
+            break
+        n_w = stats[2]
+    cnt, user, plain, decayed = cnt.cpu().numpy(), user.cpu().numpy(), plain.cpu().numpy(), decayed.cpu().numpy()
+    out = [(iid, [(uids[user[q, t]], float(plain[q, t]), float(decayed[q, t])) for t in range(cnt[q])]) for q, iid in enumerate(iids)]
+    res = LocalRDD(out, ctx)
+    res.stats = stats
+    return res
+
+
+def recommend_audience_profiles(alterEgoRDD, profiles, items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None):
+    """recommend_audience among users that are not rows of the train set ("which of the users who arrived today"): `profiles`
+    as recommend_topn_profiles takes them and folds them in; the audiences of `items` are chosen among these profiles only,
+    from the model trained on alterEgoRDD's rows, which stays as it is.  Equal scores are ordered by the position in `profiles`.
+    Returns the LocalRDD of recommend_audience with .unknown_items and .counts as recommend_topn_profiles."""
+    _no_fold_in(alterEgoRDD, "recommend_audience_profiles")
+    st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_audience_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    iids = list(items.collect()) if hasattr(items, "collect") else list(items)
+    res = _audience_records(st, eng2, F, nb, item_avg, iids, sorted(index, key=index.get), alpha, n, decay, keep_holders,
+                            getattr(items, "ctx", None))
+    res.unknown_items, res.counts = unknown, F.counts
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
 def recommend_profiles(alterEgoRDD, profiles, testRDD, cap, keep, alpha, neighbors=None):
     """recommend for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them, testRDD the
     held-out (uid, [(iid, rating, ...)*]) records of those users -- a uid is looked up among the profiles' labels, one without a
