@@ -15,7 +15,7 @@
 //   level A / B        a workgroup bins a chunk of CH records: the records are loaded whole (coalesced) into registers,
 //                      bucket histogram and ranks by LDS atomics, one returning global atomic per occupied bucket for the
 //                      fragment's place in the bucket's range, the records staged in LDS in bucket order and copied out
-//                      (consecutive lanes write consecutive records of a fragment)
+//                      as flat words (consecutive lanes write consecutive words of a fragment)
 //   level C            one workgroup per tile: the small keys' records get their rank from LDS cursors, are laid out in
 //                      final order in LDS and leave as whole rows
 //
@@ -46,7 +46,6 @@ struct Geo {
     int KW, ts_log, T, NA;
     int ch;                       // records per chunk of the binning levels (Chunk<RW>::CH)
     const long long *ptr;         // [K + 1] first position of every key
-    unsigned *tk;                 // [K] tile | large << 31
     int *tile_key0;               // [T + 1] first key of a tile
     long long *tile_pos0;         // [T + 1] = ptr[tile_key0]
     int *tile_large;              // [T] the tile's large key, or -1
@@ -110,8 +109,10 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
     __shared__ unsigned off[NBK + 1];
     __shared__ long long gbase[NBK];
     __shared__ unsigned wsum[BT / 64];
-    __shared__ unsigned long long stage[CH * RW];
+    __shared__ __attribute__((aligned(16))) unsigned long long stage[CH * RW];
     __shared__ unsigned short sbk[CH];
+    constexpr int NKB = LEVEL_B ? NB : NA_MAX;      // buckets by key: level B's large keys share their tile's
+    __shared__ int bkey0[NKB], blarge[LEVEL_B ? NB : 1];
     const int tid = threadIdx.x;
     long long i0, i1;
     int a = 0;
@@ -127,10 +128,17 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
     }
     const int nbk = LEVEL_B ? 2 * NB : G.NA;
     for (int b = tid; b < nbk; b += BT) hist[b] = 0u;
+    // the first key of every bucket: level A (no key reaches the buckets past NA), level B (the tiles of bucket a and
+    // their large keys)
+    if (LEVEL_B) {
+        for (int b = tid; b < NB; b += BT) { bkey0[b] = G.tile_key0[(a << NB_LOG) + b]; blarge[b] = G.tile_large[(a << NB_LOG) + b]; }
+    } else {
+        for (int b = tid; b < NA_MAX; b += BT) bkey0[b] = b < G.NA ? G.tile_key0[b << NB_LOG] : 0x7fffffff;
+    }
     __syncthreads();
     unsigned long long w[EPT][RW];
     bool on[EPT], rt[EPT];  // there is a record; it is routed
-    unsigned br[EPT];       // tile word, then bucket << 16 | rank
+    unsigned br[EPT];       // bucket, then bucket << 16 | rank
 #pragma unroll
     for (int r = 0; r < EPT; r++) {
         const long long idx = i0 + r * BT + tid;
@@ -142,16 +150,23 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
         }
         rt[r] = on[r] && L.keep(w[r]);
     }
+    // the bucket is monotone in the key: the last b with bkey0[b] <= key (the last of a run of equal ones: buckets
+    // without keys), by bisection in LDS (a table of every key's tile was a gather, at level A over the whole key range)
 #pragma unroll
-    for (int r = 0; r < EPT; r++) br[r] = rt[r] ? G.tk[(unsigned)w[r][0]] : 0u;
+    for (int r = 0; r < EPT; r++) br[r] = 0u;
 #pragma unroll
-    for (int r = 0; r < EPT; r++) {
-        if (!rt[r]) continue;
-        const unsigned tkv = br[r];
-        const int t = (int)(tkv & 0x7fffffffu);
-        const int b = LEVEL_B ? ((t & (NB - 1)) | ((tkv >> 31) ? NB : 0)) : (t >> NB_LOG);
-        br[r] = ((unsigned)b << 16) | atomicAdd(&hist[b], 1u);
+    for (int d = NKB / 2; d > 0; d >>= 1)
+#pragma unroll
+        for (int r = 0; r < EPT; r++)
+            if (bkey0[br[r] + d] <= (int)(unsigned)w[r][0]) br[r] += d;
+    if (LEVEL_B) {
+#pragma unroll
+        for (int r = 0; r < EPT; r++)
+            if (blarge[br[r]] == (int)(unsigned)w[r][0]) br[r] |= NB;
     }
+#pragma unroll
+    for (int r = 0; r < EPT; r++)
+        if (rt[r]) br[r] = (br[r] << 16) | atomicAdd(&hist[br[r]], 1u);
     __syncthreads();
     block_scan_2(hist, off, nbk, wsum);
     for (int b = tid; b < nbk; b += BT) {
@@ -167,7 +182,8 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
             start = G.tile_pos0[b << NB_LOG];
             cur = &G.curA[b];
         }
-        gbase[b] = start + (long long)atomicAdd(cur, (unsigned long long)c);
+        // word 0 of the staged chunk -> its word of `out`, as if the whole chunk went where this fragment goes
+        gbase[b] = (start + (long long)atomicAdd(cur, (unsigned long long)c) - (long long)off[b]) * RW;
     }
 #pragma unroll
     for (int r = 0; r < EPT; r++) {
@@ -179,12 +195,16 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
     }
     L.extra(i0, w, on);
     __syncthreads();
-    const int n = (int)off[nbk];
-    for (int s = tid; s < n; s += BT) {
-        const unsigned b = sbk[s];
-        unsigned long long *o = out + (size_t)(gbase[b] + (long long)(s - off[b])) * RW;
+    // the staged chunk leaves as flat words, VW per lane (16 bytes where a record is a whole number of them): consecutive
+    // lanes write consecutive words of a fragment, so a store instruction covers every line it touches and no line of a
+    // fragment is stored twice (a lane per 24-byte record touched each of its lines with both of its stores)
+    constexpr int VW = RW % 2 == 0 ? 2 : 1;
+    const int nw = (int)off[nbk] * RW;
+#pragma unroll 4
+    for (int q = tid * VW; q < nw; q += BT * VW) {
+        unsigned long long *o = out + (gbase[sbk[q / RW]] + q);
 #pragma unroll
-        for (int x = 0; x < RW; x++) o[x] = stage[s * RW + x];
+        for (int x = 0; x < VW; x++) o[x] = stage[q + x];
     }
 }
 

@@ -426,7 +426,6 @@ __global__ __launch_bounds__(256) void k_ts_plan(Geo G) {
     const long long p = G.ptr[k], cnt = G.ptr[k + 1] - p;
     const int t = (int)(measure(G, k, p) >> G.ts_log);
     const bool large = cnt >= (1ll << G.ts_log);
-    G.tk[k] = (unsigned)t | (large ? 0x80000000u : 0u);
     const int tp = k > 0 ? (int)(measure(G, k - 1, G.ptr[k - 1]) >> G.ts_log) : -1;
     for (int x = tp + 1; x <= t; x++) { G.tile_key0[x] = k; G.tile_pos0[x] = p; }
     if (k == G.K - 1)
@@ -484,7 +483,6 @@ int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr) {
     G.ptr = ptr;
     G.clist_cap = G.M / G.ch + G.NA + 1;
     G.slist_cap = G.M / ts::SL + (G.M >> G.ts_log) + 2;
-    XM_HIP(xm_malloc_async((void **)&G.tk, sizeof(unsigned) * (size_t)(G.K > 0 ? G.K : 1), st));
     XM_HIP(xm_malloc_async((void **)&G.tile_key0, sizeof(int) * ((size_t)G.T + 1), st));
     XM_HIP(xm_malloc_async((void **)&G.tile_pos0, sizeof(long long) * ((size_t)G.T + 1), st));
     XM_HIP(xm_malloc_async((void **)&G.tile_large, sizeof(int) * (size_t)G.T, st));
