@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -19,6 +19,12 @@ three strongest evidence entries of its score with their share, and the user's o
 --audience (with --device-tail): the other direction -- for three target items the ten users to tell about them
 (xmap.engine.session.recommend_audience: the users whose own rows give evidence for the item and who do not hold it yet, by
 the same unrounded prediction).
+
+--new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
+afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
+(xmap.engine.session.recommend_audience_items / recommend_items: one row of RecommenderSim per item against the frozen AlterEgo
+profiles, the model unchanged), and the run prints their neighbour lists' lengths, their audiences and the MAE of their
+held-out ratings.
 
 --fold-in (with --device-tail): five test users are kept out of training altogether, as users who arrive afterwards would be.
 The model is trained without them; their ratings (the source domain's, for a user known only there) are then folded in
@@ -89,6 +95,7 @@ def main(argv=None):
     ap.add_argument("--fold-in", action="store_true")
     ap.add_argument("--explain", action="store_true")
     ap.add_argument("--audience", action="store_true")
+    ap.add_argument("--new-items", action="store_true")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -123,6 +130,18 @@ def main(argv=None):
         late_uids = set(uid for uid, _ in testRDD.take(5))
         late = trainRDD.filter(lambda rec: rec[0] in late_uids).collect()
         trainRDD = trainRDD.filter(lambda rec: rec[0] not in late_uids).cache()
+    new_items = []              # (iid, [(uid, rating)*]) of the items that enter the catalogue after training
+    if args.new_items:
+        if not args.device_tail or para["recommender"]["private_flag"]:
+            ap.error("--new-items needs --device-tail and the non-private recommender")
+        raters = {}
+        for uid, prof in trainRDD.collect():
+            for entry in prof:
+                if "T:" in entry[0]:
+                    raters.setdefault(entry[0], []).append((uid, entry[1]))
+        new_iids = set(sorted(raters, key=lambda iid: (- len(raters[iid]), iid))[10:13])      # well rated, not the very heaviest
+        new_items = [(iid, raters[iid]) for iid in sorted(new_iids)]
+        trainRDD = trainRDD.map(lambda rec: (rec[0], [e for e in rec[1] if e[0] not in new_iids])).filter(lambda rec: rec[1]).cache()
     item2item_simRDD = timed("A_item_sim", assist.baseliner_calculate_sim_pipeline, sc, sim_tool, trainRDD)
     ext_tool = ExtendSim(para["extender"]["extend_among_topk"])
     extendedsimRDD = timed("B_extend", assist.extender_pipeline, sc, sqlContext, sim_tool, ext_tool, item2item_simRDD)
@@ -173,6 +192,18 @@ def main(argv=None):
                     rc["mapping_range"], rc["decay_alpha"], 10)
         for iid, lst in aud.collect():
             print("audience of %s:" % iid, ", ".join("%s (%.3f)" % (uid, plain) for uid, plain, _ in lst) or "no evidence")
+    if new_items:
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)
+        print("item fold-in: %d items kept out of training, %d ratings -> %d records, %d pairs, %d unknown users" % (
+            len(new_items), sum(len(l) for _, l in new_items), aud.counts[1], aud.counts[0], aud.unknown_users))
+        for iid, lst in aud.collect():
+            print("audience of %s (folded in, %d neighbours):" % (iid, len(aud.new_sim_pairs.get(iid, ()))),
+                  ", ".join("%s (%.3f)" % (uid, plain) for uid, plain, _ in lst) or "no evidence")
+        names = set(iid for iid, _ in new_items)
+        held = testRDD.map(lambda rec: (rec[0], [e for e in rec[1] if e[0] in names])).filter(lambda rec: rec[1])
+        print("MAE of their held-out ratings (no decay; decay):",
+              rpred.calculate_mae(session.recommend_items(alterEgo_profile, new_items, held, w, k, alpha)))
     if late:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         top = timed("fold_in_topn", session.recommend_topn_profiles, alterEgo_profile, late, w, k, alpha, 5)

@@ -751,6 +751,55 @@ int xmap_foldin_fill(void *stream, int64_t n_new, int64_t nnz, const int64_t *pt
                      const int64_t *time, int32_t n_items, const uint8_t *flags, const int32_t *map_src2tgt,
                      const int32_t *cnt_t, const int64_t *prof_ptr, int32_t *prof_item, double *prof_rating, int64_t *prof_time);
 
+/* ---- item fold-in (csrc/stage_e_itemfold.hip): one row of RecommenderSim for an ITEM that was not in the ratings upload -- a book
+ * that enters the catalogue -- against the resident user-major profiles, with the frozen norms.  The mirror of the user fold-in:
+ * the model stays frozen, no resident list or average changes, a batch rating is never evidence.
+ * Resident data, read only: prof_ptr [U + 1], prof_item / prof_rating [rows] as xmap_rec_profiles or xmap_union_fill leave them
+ * (items inside [0, n_items)); item_norm [I] = the norms RecommenderSim used; cap = its num_atleast.
+ * The batch: n_new items as a CSR of raters, ptr [n_new + 1], user [nnz] (indices of resident users), rating [nnz] (fp64); a user
+ * may appear more than once under an item, an item may have no entries; there are no times.
+ * Records: entries in batch order, within an entry the rater's profile rows in profile order; (entry, row) is one record (q, j =
+ * prof_item, r0 = batch rating, r1 = prof_rating).  All sums double-double (dd_add), hi is the value used:
+ *   per item q: new_avg = hi(sum r0) / entries, new_norm = nx = sqrt(hi(sum r0 r0)) over its entries (0.0 without entries)
+ *   per (q, j) with a record, records in that order: n = their number, inner = hi(sum fl(r0 r1)), ny = item_norm[j], np = nx ny,
+ *     sim = weighted(np != 0 ? 1.0 inner / np : 0.0, n, cap) with weighted(x, n, cap) = 1.0 x min(n, cap) / cap (NaN != 0 divides);
+ *     ls = the maximum over the records of |weighted(m != 0 ? rest / m : 0.0, n - 1, cap) - sim| for rest = inner - r0 r1 and
+ *     m = sqrt((nx nx - r0 r0)(ny ny)), then m = sqrt((nx nx)(ny ny - r1 r1)); NaN ranks above everything -- the operations of
+ *     RecommenderSim's resident rows (xmap_sim2_pairs, LS variant), so a copy of a resident item gets that item's row (j != i)
+ *   row q of the output: one entry (col = j, sim, ls, nij = n) per such j, in no particular order.  A pure function of the inputs.
+ * xmap_itemfold_count: FIRST checks the batch on the device, reading ptr and user only: ptr[0] == 0, ptr non-decreasing,
+ *   ptr[n_new] == nnz, 0 <= user < n_users.  A batch that fails: XMAP_ERR_ARG, xmap_last_error() names the first bad position, no
+ *   output is written and nothing has been indexed by an unchecked value.  Otherwise cnt [n_new] = entries per row, row_ptr
+ *   [n_new + 1] = their exclusive scan, h_counts (host) = {pairs, records, items with a pair}.  Syncs.
+ * xmap_itemfold_fill: the rows, into buffers of exactly h_counts[0] entries, with the arrays xmap_itemfold_count accepted and its
+ *   row_ptr; new_avg / new_norm [n_new].  Syncs.
+ * Both work in chunks of consecutive batch items whose records number at most max_records (0: the library's default, 2^22; a
+ * single item above the bound is a chunk of its own; a chunk's records stay below 2^31: XMAP_ERR_CAPACITY for a larger single
+ * item): expand -> stable radix sort by (item, partner) -> run heads -> one lane per run.  No lock, no floating-point atomic,
+ * every output position from counts and scans; the result does not depend on max_records.  n_new == 0 is valid.  nnz < 2^31 - 1.
+ * Temporaries from the stream's arena.
+ * The neighbour list of q: xmap_rec_select over these rows with n_items = n_new.  The EXTENDED tables of I' = I + n_new items --
+ * rows [0, I) the resident nb_cnt / nb_col / nb_sim and item_avg, row I + q the list and new_avg of q; list entries are resident
+ * indices < I -- serve xmap_predict_rows, xmap_topn_rows and xmap_explain_rows as they are, with the unchanged profiles.
+ * xmap_itemfold_audience_rows: xmap_audience_rows over the extended tables (n_items = n_resident + n_new; the arguments of
+ *   xmap_audience_rows position for position, then three more): the holders of item n_resident + q are its raters new_user[new_ptr[q]
+ *   .. new_ptr[q + 1]) (device) -- without XMAP_AUDIENCE_KEEP_HOLDERS they are no candidates, with it they are. */
+int xmap_itemfold_count(void *stream, int64_t n_new, int64_t nnz, const int64_t *ptr, const int32_t *user, int64_t n_users,
+                        int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item,
+                        int64_t max_records /* 0: the library's default */, int32_t *cnt /*[n_new]*/, int64_t *row_ptr /*[n_new+1]*/,
+                        int64_t *h_counts /* host [3]: pairs, records, items with a pair */);
+int xmap_itemfold_fill(void *stream, int64_t n_new, int64_t nnz, const int64_t *ptr, const int32_t *user, const double *rating,
+                       int64_t n_users, int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                       const double *item_norm, int32_t cap, int64_t max_records, const int64_t *row_ptr, int32_t *col, double *sim,
+                       double *ls, int32_t *nij, double *new_avg /*[n_new]*/, double *new_norm /*[n_new]*/);
+int xmap_itemfold_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                                int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                                const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                                const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
+                                int32_t *out_cnt, int32_t *out_user, double *out_plain, double *out_decay,
+                                int64_t *h_stats /* host, [4] or NULL, as xmap_audience_rows */,
+                                int32_t n_resident, const int64_t *new_ptr /*[n_new+1]*/, const int32_t *new_user);
+
 /* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
  * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
  * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
@@ -904,6 +953,25 @@ int xmap_union_fill(void *stream, int32_t n_parts, const xmap_union_part *parts 
  *                             Argument errors start no device work and leave the outputs untouched
  *   xmap_ctx_foldin_audience : the same over the fold-in batch: out_user = indices into the batch ("which of the users who
  *                             arrived today"); needs a batch and the neighbour lists, as xmap_ctx_foldin_recommend
+ * Item fold-in, for items that were not in the upload (call order: rec_sim -> rec_select or rec_set_neighbors -> item_foldin; it
+ * reads only the tail, so it works on a union context).  The batch hangs on the tail and its lists: everything that drops the
+ * tail drops it, and so do rec_sim, rec_select and rec_set_neighbors.  No item fold-in call changes what a resident call returns.
+ *   xmap_ctx_item_foldin    : n_new items as a CSR of raters (ptr [n_new + 1], user / rating [ptr[n_new]], indices of resident
+ *                             users) -> their RecommenderSim rows (xmap_itemfold_count / xmap_itemfold_fill with the resident
+ *                             profiles, norms and the cap of xmap_ctx_rec_sim), their lists (xmap_rec_select with the context's
+ *                             keep) and the extended tables of I + n_new items, kept on the device; the batch replaces the
+ *                             previous one.  The input is checked on the host first (ptr[0] == 0, ptr non-decreasing, 0 <= user <
+ *                             n_users): XMAP_ERR_ARG naming the position, no device work started.  A failed call leaves the
+ *                             context as it was, the previous batch included.  counts [3] (may be NULL) = {pairs, records, items
+ *                             with a pair}.  n_new == 0 is valid
+ *   xmap_ctx_item_foldin_download : the batch's rows (row_ptr [n_new + 1], col / sim / ls / nij [pairs], rows not sorted), avg /
+ *                             norm [n_new] and lists (nb_cnt [n_new], nb_col / nb_sim / nb_ls [n_new][keep]); any pointer may be NULL
+ *   xmap_ctx_item_foldin_audience : xmap_ctx_audience for the batch's items: query_item = indices into the batch; their raters
+ *                             are their holders (XMAP_AUDIENCE_KEEP_HOLDERS keeps them)
+ *   xmap_ctx_item_foldin_predict : xmap_ctx_predict for pairs (resident user, batch item): test_item = indices into the batch
+ *                             (both: an index outside [0, n_new) behaves like an item without a list)
+ *   xmap_ctx_item_foldin_recommend : xmap_ctx_recommend over all I + n_new items: a batch item q is returned as I + q.  Limit:
+ *                             top-N does not leave a batch item out of its own raters' lists -- the frozen profiles do not hold it
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -987,6 +1055,19 @@ int xmap_ctx_audience(xmap_ctx *ctx, int64_t n_query, const int32_t *query_item,
 int xmap_ctx_foldin_audience(xmap_ctx *ctx, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
                              int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user,
                              double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
+int xmap_ctx_item_foldin(xmap_ctx *ctx, int64_t n_new, const int64_t *ptr, const int32_t *user, const double *rating,
+                         int64_t *counts /*[3] or NULL*/);
+int xmap_ctx_item_foldin_download(xmap_ctx *ctx, int64_t *row_ptr, int32_t *col, double *sim, double *ls, int32_t *nij, double *avg,
+                                  double *norm, int32_t *nb_cnt, int32_t *nb_col, double *nb_sim, double *nb_ls);
+int xmap_ctx_item_foldin_audience(xmap_ctx *ctx, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
+                                  int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user,
+                                  double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
+int xmap_ctx_item_foldin_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                                 const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
+                                 int32_t *max_now);
+int xmap_ctx_item_foldin_recommend(xmap_ctx *ctx, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
+                                   int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item,
+                                   double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

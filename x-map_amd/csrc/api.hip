@@ -11,6 +11,8 @@
 //                                                                                  | xmap_ctx_evaluate_topn (top-N against held-out pairs)
 //   fold-in, for profiles that were not rows of the upload:  xmap_ctx_generate -> xmap_ctx_foldin (the batch's AlterEgo profiles)
 //                     -> [rec_sim -> rec_select] -> xmap_ctx_foldin_predict | xmap_ctx_foldin_recommend (the same kernels, the batch's rows)
+//   item fold-in, for items that were not in the upload:  rec_sim -> rec_select -> xmap_ctx_item_foldin (rows, lists, extended tables)
+//                     -> xmap_ctx_item_foldin_audience | _predict | _recommend (the same kernels, tables of I + n_new items)
 //   explanations of (user, item) pairs: xmap_ctx_explain | xmap_ctx_foldin_explain, wherever xmap_ctx_predict | xmap_ctx_foldin_predict work
 //   xmap_ctx_*_download copy results into caller-allocated host buffers whose sizes the stage call reported.
 //
@@ -85,8 +87,20 @@ struct xmap_ctx {
     double *rs_sim = nullptr, *rs_ls = nullptr, *rs_avg = nullptr, *rs_norm = nullptr;
     int64_t rec_pairs = 0;
     int keep = 0;
+    int rec_cap = 0;                // the num_atleast of the resident RecommenderSim (an item fold-in weights with the same)
     int32_t *nb_cnt = nullptr, *nb_col = nullptr;
     double *nb_sim = nullptr, *nb_ls = nullptr;
+    // item fold-in: the RecommenderSim rows of the last batch of new items (if_*), the batch's rater CSR, and the EXTENDED tables
+    // of I + if_new items (x_*: rows [0, I) copies of nb_* / rs_avg, row I + q the list and the average of batch item q); hangs
+    // on the tail and the neighbour lists: dropped with them
+    Pool p_ifold;
+    bool have_ifold = false;
+    int64_t if_new = 0, if_pairs = 0;
+    int64_t *if_row_ptr = nullptr, *if_ptr = nullptr;
+    int32_t *if_col = nullptr, *if_nij = nullptr, *if_user = nullptr;
+    double *if_sim = nullptr, *if_ls = nullptr, *if_norm = nullptr;
+    int32_t *x_cnt = nullptr, *x_col = nullptr;
+    double *x_sim = nullptr, *x_ls = nullptr, *x_avg = nullptr;
     // fold-in: the AlterEgo profiles of the last batch (user-major, as pf_*), built with g_map: dropped with the map
     Pool p_fold;
     bool have_fold = false;
@@ -135,7 +149,14 @@ static int d2h(T *host, const T *dev, size_t n, hipStream_t st) {
 }
 
 // any earlier stage run again invalidates the recommender tail (as the stages invalidate each other)
+static void drop_ifold(xmap_ctx *c) {
+    c->p_ifold.release();
+    c->have_ifold = false;
+    c->if_new = c->if_pairs = 0;
+}
+
 static void drop_tail(xmap_ctx *c) {
+    drop_ifold(c);
     c->p_nb.release(); c->p_rec.release();
     c->have_rec = c->have_nb = false;
 }
@@ -759,6 +780,7 @@ int xmap_ctx_rec_sim(xmap_ctx *c, int cap, int64_t *n_pairs) {
     XM_ALLOCZ(c->p_rec, c->rs_row_ptr, I + 1);
     XM_ALLOCZ(c->p_rec, c->rs_avg, i1); XM_ALLOCZ(c->p_rec, c->rs_norm, i1);
     c->rec_pairs = 0;
+    c->rec_cap = cap;
     if (I == 0 || nnz == 0) {
         XM_HIP(hipStreamSynchronize(c->st));
         c->have_rec = true;
@@ -787,6 +809,7 @@ int xmap_ctx_rec_sim(xmap_ctx *c, int cap, int64_t *n_pairs) {
     J.stats_pool = J.mutu_pool = &tmp; J.csr_pool = &c->p_rec; J.row_ptr = c->rs_row_ptr;
     TriResult O;
     XM_TRY(tri_pass(c->st, J, tmp, O));
+    c->rec_cap = cap;
     c->rs_col = O.col; c->rs_sim = O.sim; c->rs_nij = O.nij; c->rs_ls = O.aux;
     // the item averages the prediction reads are the layout's (exact sum / n), the norms its adjusted norms (zero user average)
     XM_HIP(hipMemcpy2DAsync(c->rs_avg, sizeof(double), O.info, 4 * sizeof(double), sizeof(double), (size_t)I, hipMemcpyDeviceToDevice, c->st));
@@ -829,6 +852,7 @@ int xmap_ctx_rec_download(xmap_ctx *c, int64_t *row_ptr, int32_t *col, double *s
 }
 
 static int alloc_neighbors(xmap_ctx *c, int keep) {
+    drop_ifold(c);              // the extended tables copy the lists
     c->p_nb.release();
     c->have_nb = false;
     const size_t m = (size_t)(c->R.n_items ? c->R.n_items : 1) * keep;
@@ -892,7 +916,24 @@ struct Profiles {
 static Profiles resident_profiles(const xmap_ctx *c) { return Profiles{c->R.n_users, c->pf_ptr, c->pf_time, c->pf_item, c->pf_rating}; }
 static Profiles foldin_profiles(const xmap_ctx *c) { return Profiles{c->f_users, c->f_ptr, c->f_time, c->f_item, c->f_rating}; }
 
-static int predict_over(xmap_ctx *c, const Profiles &P, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
+// the tables the same kernels read: neighbour lists [n_items][keep], item averages [n_items]; the resident ones, or the extended
+// ones of an item fold-in (items >= n_resident are the batch's; their holders are the batch's raters, new_ptr / new_user)
+struct Tables {
+    int32_t n_items, keep;
+    const int32_t *cnt, *col;
+    const double *sim, *avg;
+    int32_t n_resident;
+    const int64_t *new_ptr;
+    const int32_t *new_user;
+};
+static Tables resident_tables(const xmap_ctx *c) {
+    return Tables{c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim, c->rs_avg, c->R.n_items, nullptr, nullptr};
+}
+static Tables itemfold_tables(const xmap_ctx *c) {
+    return Tables{(int32_t)(c->R.n_items + c->if_new), c->keep, c->x_cnt, c->x_col, c->x_sim, c->x_avg, c->R.n_items, c->if_ptr, c->if_user};
+}
+
+static int predict_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
                         const double *test_rating, const double *wtab, int32_t n_w, double *out_plain, double *out_decay,
                         int32_t *status, double *mae, int32_t *max_now) {
     XM_ARG(n_test >= 0 && wtab && n_w >= 1 && (n_test == 0 || (test_user && test_item && out_plain && out_decay && status)));
@@ -911,8 +952,8 @@ static int predict_over(xmap_ctx *c, const Profiles &P, int64_t n_test, const in
     if (test_rating) XM_TRY(h2d(tmp, &d_real, test_rating, n, c->st));
     XM_TRY(dalloc(tmp, &d_plain, n, c->st, true)); XM_TRY(dalloc(tmp, &d_decay, n, c->st, true));
     XM_TRY(dalloc(tmp, &d_status, n, c->st, true)); XM_TRY(dalloc(tmp, &d_mae, 3, c->st, true));
-    XM_TRY(xmap_predict_rows(c->st, n_test, d_user, d_item, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim, P.ptr,
-                             P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_plain, d_decay, d_status, max_now));
+    XM_TRY(xmap_predict_rows(c->st, n_test, d_user, d_item, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim, P.ptr,
+                             P.item, P.rating, P.time, T.avg, d_w, n_w, d_plain, d_decay, d_status, max_now));
     if (mae) {
         XM_TRY(xmap_mae(c->st, n_test, d_status, d_real, d_plain, d_decay, d_mae));
         XM_TRY(d2h(mae, (const double *)d_mae, 3, c->st));
@@ -924,7 +965,7 @@ static int predict_over(xmap_ctx *c, const Profiles &P, int64_t n_test, const in
     return XMAP_OK;
 }
 
-static int recommend_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
+static int recommend_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
                           int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain,
                           double *out_decay, int64_t *stats) {
     XM_ARG(n_top >= 1 && n_top <= 64);
@@ -943,8 +984,8 @@ static int recommend_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const
     XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
     XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
-    XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col, c->nb_sim,
-                          P.ptr, P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
+    XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
+                          P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
@@ -953,7 +994,7 @@ static int recommend_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const
     return XMAP_OK;
 }
 
-static int audience_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
+static int audience_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
                          int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain,
                          double *out_decay, int64_t *stats) {
     XM_ARG(n_top >= 1 && n_top <= 1024);
@@ -972,8 +1013,13 @@ static int audience_over(xmap_ctx *c, const Profiles &P, int64_t n_query, const 
     XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
     XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_user, m, c->st));
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
-    XM_TRY(xmap_audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col,
-                              c->nb_sim, P.ptr, P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay, stats));
+    if (T.new_ptr)
+        XM_TRY(xmap_itemfold_audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
+                                           P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay, stats,
+                                           T.n_resident, T.new_ptr, T.new_user));
+    else
+        XM_TRY(xmap_audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
+                                  P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay, stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_user, (const int32_t *)d_user, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
@@ -986,7 +1032,8 @@ int xmap_ctx_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, cons
                      const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
                      int32_t *max_now) {
     XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
-    return predict_over(c, resident_profiles(c), n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
+    return predict_over(c, resident_profiles(c), resident_tables(c),
+                        n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
                         max_now);
 }
 
@@ -994,7 +1041,8 @@ int xmap_ctx_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, 
                        const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
                        int64_t *stats) {
     XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
-    return recommend_over(c, resident_profiles(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
+    return recommend_over(c, resident_profiles(c), resident_tables(c),
+                          n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
                           out_decay, stats);
 }
 
@@ -1002,7 +1050,8 @@ int xmap_ctx_audience(xmap_ctx *c, int64_t n_query, const int32_t *query_item, i
                       const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain, double *out_decay,
                       int64_t *stats) {
     XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
-    return audience_over(c, resident_profiles(c), n_query, query_item, n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain,
+    return audience_over(c, resident_profiles(c), resident_tables(c),
+                         n_query, query_item, n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain,
                          out_decay, stats);
 }
 
@@ -1069,7 +1118,8 @@ int xmap_ctx_foldin_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query
                               const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain,
                               double *out_decay, int64_t *stats) {
     XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
-    return recommend_over(c, foldin_profiles(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
+    return recommend_over(c, foldin_profiles(c), resident_tables(c),
+                          n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt, out_item, out_plain,
                           out_decay, stats);
 }
 
@@ -1077,7 +1127,8 @@ int xmap_ctx_foldin_audience(xmap_ctx *c, int64_t n_query, const int32_t *query_
                              const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain,
                              double *out_decay, int64_t *stats) {
     XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
-    return audience_over(c, foldin_profiles(c), n_query, query_item, n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain,
+    return audience_over(c, foldin_profiles(c), resident_tables(c),
+                         n_query, query_item, n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain,
                          out_decay, stats);
 }
 
@@ -1085,8 +1136,125 @@ int xmap_ctx_foldin_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_use
                             const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
                             int32_t *max_now) {
     XM_ARG(c && c->have_gen && c->have_fold && c->have_rec && c->have_nb);
-    return predict_over(c, foldin_profiles(c), n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
+    return predict_over(c, foldin_profiles(c), resident_tables(c),
+                        n_test, test_user, test_item, test_rating, wtab, n_w, out_plain, out_decay, status, mae,
                         max_now);
+}
+
+// ---- item fold-in -------------------------------------------------------------------------------------------------------
+
+int xmap_ctx_item_foldin(xmap_ctx *c, int64_t n_new, const int64_t *ptr, const int32_t *user, const double *rating, int64_t *counts) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb && n_new >= 0 && ptr);
+    // the batch is checked here, on the host: bad input starts no device work (xmap_itemfold_count's own check then passes)
+    if (ptr[0] != 0) { set_error("item fold-in batch: ptr[0] = %lld, not 0", (long long)ptr[0]); return XMAP_ERR_ARG; }
+    for (int64_t q = 0; q < n_new; q++)
+        if (ptr[q + 1] < ptr[q]) { set_error("item fold-in batch: ptr[%lld] < ptr[%lld]", (long long)q + 1, (long long)q); return XMAP_ERR_ARG; }
+    const int64_t nnz = ptr[n_new];
+    const int I = c->R.n_items;
+    const int64_t U = c->R.n_users;
+    XM_ARG(nnz < 2147483647ll && (nnz == 0 || (user && rating)) && (int64_t)I + n_new <= 2147483647ll);
+    for (int64_t e = 0; e < nnz; e++)
+        if (user[e] < 0 || user[e] >= U) {
+            set_error("item fold-in batch: user[%lld] = %d outside [0, %lld)", (long long)e, (int)user[e], (long long)U);
+            return XMAP_ERR_ARG;
+        }
+    XM_HIP(hipSetDevice(c->device));
+    // built beside the previous batch, which is replaced only when everything has succeeded
+    ScratchPool tmp, fresh;
+    const int keep = c->keep;
+    const size_t n1 = (size_t)n_new, x1 = (size_t)I + n1;
+    int64_t *d_ptr, *row_ptr, h[3] = {0, 0, 0};
+    int32_t *d_user, *cnt, *col, *nij, *x_cnt, *x_col;
+    double *d_rating, *sim, *ls, *norm, *x_sim, *x_ls, *x_avg;
+    XM_TRY(h2d(fresh, &d_ptr, ptr, n1 + 1, c->st));
+    XM_TRY(h2d(fresh, &d_user, user, (size_t)nnz, c->st));
+    XM_TRY(h2d(tmp, &d_rating, rating, (size_t)nnz, c->st));
+    XM_TRY(dalloc(tmp, &cnt, n1, c->st));
+    XM_TRY(dalloc(fresh, &row_ptr, n1 + 1, c->st));
+    XM_TRY(xmap_itemfold_count(c->st, n_new, nnz, d_ptr, d_user, U, I, c->pf_ptr, c->pf_item, 0, cnt, row_ptr, h));
+    const size_t np = (size_t)h[0];
+    XM_TRY(dalloc(fresh, &col, np, c->st)); XM_TRY(dalloc(fresh, &sim, np, c->st)); XM_TRY(dalloc(fresh, &ls, np, c->st));
+    XM_TRY(dalloc(fresh, &nij, np, c->st)); XM_TRY(dalloc(fresh, &norm, n1, c->st));
+    // the extended tables: the resident rows, then the batch's (the fill pass and the selection write them in place)
+    XM_TRY(dalloc(fresh, &x_cnt, x1, c->st, true)); XM_TRY(dalloc(fresh, &x_col, x1 * keep, c->st, true));
+    XM_TRY(dalloc(fresh, &x_sim, x1 * keep, c->st, true)); XM_TRY(dalloc(fresh, &x_ls, x1 * keep, c->st, true));
+    XM_TRY(dalloc(fresh, &x_avg, x1, c->st, true));
+    if (I) {
+        const size_t m = (size_t)I * keep;
+        XM_HIP(hipMemcpyAsync(x_cnt, c->nb_cnt, sizeof(int32_t) * (size_t)I, hipMemcpyDeviceToDevice, c->st));
+        XM_HIP(hipMemcpyAsync(x_col, c->nb_col, sizeof(int32_t) * m, hipMemcpyDeviceToDevice, c->st));
+        XM_HIP(hipMemcpyAsync(x_sim, c->nb_sim, sizeof(double) * m, hipMemcpyDeviceToDevice, c->st));
+        XM_HIP(hipMemcpyAsync(x_ls, c->nb_ls, sizeof(double) * m, hipMemcpyDeviceToDevice, c->st));
+        XM_HIP(hipMemcpyAsync(x_avg, c->rs_avg, sizeof(double) * (size_t)I, hipMemcpyDeviceToDevice, c->st));
+    }
+    XM_TRY(xmap_itemfold_fill(c->st, n_new, nnz, d_ptr, d_user, d_rating, U, I, c->pf_ptr, c->pf_item, c->pf_rating, c->rs_norm, c->rec_cap, 0,
+                              row_ptr, col, sim, ls, nij, x_avg + I, norm));
+    if (h[0] > 0)
+        XM_TRY(xmap_rec_select(c->st, (int32_t)n_new, row_ptr, col, sim, ls, keep, x_cnt + I, x_col + (size_t)I * keep,
+                               x_sim + (size_t)I * keep, x_ls + (size_t)I * keep));
+    XM_HIP(hipStreamSynchronize(c->st));
+    drop_ifold(c);
+    c->p_ifold.ptrs.swap(fresh.ptrs);
+    c->if_new = n_new; c->if_pairs = h[0];
+    c->if_ptr = d_ptr; c->if_user = d_user; c->if_row_ptr = row_ptr;
+    c->if_col = col; c->if_sim = sim; c->if_ls = ls; c->if_nij = nij; c->if_norm = norm;
+    c->x_cnt = x_cnt; c->x_col = x_col; c->x_sim = x_sim; c->x_ls = x_ls; c->x_avg = x_avg;
+    c->have_ifold = true;
+    if (counts) { counts[0] = h[0]; counts[1] = h[1]; counts[2] = h[2]; }
+    return XMAP_OK;
+}
+
+int xmap_ctx_item_foldin_download(xmap_ctx *c, int64_t *row_ptr, int32_t *col, double *sim, double *ls, int32_t *nij, double *avg,
+                                  double *norm, int32_t *nb_cnt, int32_t *nb_col, double *nb_sim, double *nb_ls) {
+    XM_ARG(c && c->have_ifold);
+    XM_HIP(hipSetDevice(c->device));
+    const size_t I = (size_t)c->R.n_items, n1 = (size_t)c->if_new, np = (size_t)c->if_pairs, m = n1 * (size_t)c->keep, o = I * (size_t)c->keep;
+    if (row_ptr) XM_TRY(d2h(row_ptr, (const int64_t *)c->if_row_ptr, n1 + 1, c->st));
+    if (col) XM_TRY(d2h(col, (const int32_t *)c->if_col, np, c->st));
+    if (sim) XM_TRY(d2h(sim, (const double *)c->if_sim, np, c->st));
+    if (ls) XM_TRY(d2h(ls, (const double *)c->if_ls, np, c->st));
+    if (nij) XM_TRY(d2h(nij, (const int32_t *)c->if_nij, np, c->st));
+    if (avg) XM_TRY(d2h(avg, (const double *)(c->x_avg + I), n1, c->st));
+    if (norm) XM_TRY(d2h(norm, (const double *)c->if_norm, n1, c->st));
+    if (nb_cnt) XM_TRY(d2h(nb_cnt, (const int32_t *)(c->x_cnt + I), n1, c->st));
+    if (nb_col) XM_TRY(d2h(nb_col, (const int32_t *)(c->x_col + o), m, c->st));
+    if (nb_sim) XM_TRY(d2h(nb_sim, (const double *)(c->x_sim + o), m, c->st));
+    if (nb_ls) XM_TRY(d2h(nb_ls, (const double *)(c->x_ls + o), m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+// indices into the batch -> items of the extended tables (I + q); an index outside the batch -> -1, an item without a list
+static std::vector<int32_t> batch_items(const xmap_ctx *c, int64_t n, const int32_t *item) {
+    std::vector<int32_t> out((size_t)(item ? n : 0));
+    for (size_t k = 0; k < out.size(); k++) out[k] = (item[k] >= 0 && item[k] < c->if_new) ? c->R.n_items + item[k] : -1;
+    return out;
+}
+
+int xmap_ctx_item_foldin_audience(xmap_ctx *c, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                                  const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain,
+                                  double *out_decay, int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb && c->have_ifold && n_query >= 0);
+    const std::vector<int32_t> q = batch_items(c, n_query, query_item);
+    return audience_over(c, resident_profiles(c), itemfold_tables(c), n_query, query_item ? q.data() : nullptr, n_top, rank_by, flags, wtab,
+                         n_w, out_cnt, out_user, out_plain, out_decay, stats);
+}
+
+int xmap_ctx_item_foldin_predict(xmap_ctx *c, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const double *test_rating,
+                                 const double *wtab, int32_t n_w, double *out_plain, double *out_decay, int32_t *status, double *mae,
+                                 int32_t *max_now) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb && c->have_ifold && n_test >= 0);
+    const std::vector<int32_t> t = batch_items(c, n_test, test_item);
+    return predict_over(c, resident_profiles(c), itemfold_tables(c), n_test, test_user, test_item ? t.data() : nullptr, test_rating, wtab,
+                        n_w, out_plain, out_decay, status, mae, max_now);
+}
+
+int xmap_ctx_item_foldin_recommend(xmap_ctx *c, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                                   const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                                   double *out_decay, int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb && c->have_ifold);
+    return recommend_over(c, resident_profiles(c), itemfold_tables(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt,
+                          out_item, out_plain, out_decay, stats);
 }
 
 // ---- explanations -------------------------------------------------------------------------------------------------------

@@ -22,6 +22,8 @@
 //                     another tile the whole array is sorted again by a bitonic network.  A key is (score as an ordered
 //                     integer, position in the segment): the positions ascend with the user index, keys are distinct, and the
 //                     sorted prefix is the same whatever order the survivors were staged in.  Status 2: dropped and counted.
+// Items of an item fold-in (stage_e_itemfold.hip; query items >= n_resident of xmap_itemfold_audience_rows): no profile holds them, their
+// holders are the batch's raters -- a second, optional holder CSR that the clear pass of k_au_candidates reads for them.
 // Every output position follows from the scans, so the result does not depend on the grid or on the order of the atomics.
 #include "common.h"
 #include "predict_rows.h"
@@ -81,7 +83,8 @@ __device__ __forceinline__ int au_block_scan(int v, int *total, int *smem) {
 template <bool FILL>
 __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query, const int *query_item, long long U, int I, int keep,
                                                               int keep_holders, const int *nb_cnt, const int *nb_col,
-                                                              const long long *hptr, const int *huser, int *cand_cnt,
+                                                              const long long *hptr, const int *huser, int n_resident,
+                                                              const long long *new_ptr, const int *new_user, int *cand_cnt,
                                                               const long long *cand_ptr, int *cand_user, int *cand_item) {
     extern __shared__ unsigned int au_lds[];    // [AU_WORDS] bitmap of the window, [AU_SUMMARY] touched words (zero between queries),
     unsigned int *bits = au_lds, *summ = au_lds + AU_WORDS;                                      // [AU_THREADS / 64] scan scratch
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
             for (int l = 0; l < cnt; l++) {
                 const int nb = nb_col[(size_t)it * keep + l];
                 if (nb < 0 || nb >= I) continue;        // ignored, as in the prediction
-                const long long r1 = hptr[nb + 1];
+                const long long r1 = hptr[nb + 1];      // (an item of a fold-in batch: no profile holds it, the row is empty)
                 for (long long r = hptr[nb] + tid; r < r1; r += AU_THREADS) {
                     const long long x = (long long)huser[r] - lo;
                     if (x < 0 || x >= AU_WINDOW) continue;
@@ -111,9 +114,11 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
             }
             __syncthreads();
             if (!keep_holders) {                // a user who holds the item is no candidate (the word stays listed as touched)
-                const long long r1 = hptr[it + 1];
-                for (long long r = hptr[it] + tid; r < r1; r += AU_THREADS) {
-                    const long long x = (long long)huser[r] - lo;
+                const bool nw = new_ptr && it >= n_resident;         // a batch item: its holders are its raters
+                const int *hu = nw ? new_user : huser;
+                const long long r1 = nw ? new_ptr[it - n_resident + 1] : hptr[it + 1];
+                for (long long r = (nw ? new_ptr[it - n_resident] : hptr[it]) + tid; r < r1; r += AU_THREADS) {
+                    const long long x = (long long)hu[r] - lo;
                     if (x >= 0 && x < AU_WINDOW) atomicAnd(&bits[x >> 5], ~(1u << (x & 31)));
                 }
                 __syncthreads();
@@ -259,13 +264,14 @@ static void au_select_launch(hipStream_t st, long long n_query, int n_top, int r
 }  // namespace xmap
 using namespace xmap;
 
-extern "C" {
-
-int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+// xmap_audience_rows (new_ptr == NULL) and xmap_itemfold_audience_rows: the items >= n_resident take their holders from the CSR
+// (new_ptr, new_user) -- the raters of a fold-in batch, which no profile holds
+static int audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
                        int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
                        const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
                        const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
-                       int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats) {
+                       int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats, int32_t n_resident,
+                       const int64_t *new_ptr, const int32_t *new_user) {
     XM_SCOPE(stream);
     hipStream_t st = (hipStream_t)stream;
     XM_ARG(n_top >= 1 && n_top <= AU_MAX_TOP);
@@ -313,7 +319,8 @@ int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item,
     XM_HIP(hipFuncSetAttribute((const void *)k_au_candidates<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     XM_HIP(hipFuncSetAttribute((const void *)k_au_candidates<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     k_au_candidates<false><<<dim3(cblocks), dim3(AU_THREADS), lds, st>>>(n_query, query_item, n_users, I, keep, keep_holders, nb_cnt, nb_col,
-                                                                         hptr, huser, cand_cnt, nullptr, nullptr, nullptr);
+                                                                         hptr, huser, n_resident, (const long long *)new_ptr, new_user, cand_cnt, nullptr,
+                                                                         nullptr, nullptr);
     XM_LAUNCH_CHECK();
     rc = xmap_exclusive_scan_i32_to_i64(st, cand_cnt, (int64_t *)cand_ptr, n_query, &n_pairs);
     if (rc) return rc;
@@ -328,7 +335,8 @@ int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item,
         XM_HIP(xm_malloc_async((void **)&decay, sizeof(double) * np, st));
         XM_HIP(xm_malloc_async((void **)&status, sizeof(int) * np, st));
         k_au_candidates<true><<<dim3(cblocks), dim3(AU_THREADS), lds, st>>>(n_query, query_item, n_users, I, keep, keep_holders, nb_cnt,
-                                                                            nb_col, hptr, huser, nullptr, cand_ptr, cand_user, cand_item);
+                                                                            nb_col, hptr, huser, n_resident, (const long long *)new_ptr, new_user, nullptr,
+                                                                            cand_ptr, cand_user, cand_item);
         XM_LAUNCH_CHECK();
         // ---- scores: the pair body of the prediction, unrounded
         rc = predict_rows_run<true>(st, n_pairs, cand_user, cand_item, n_users, I, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
@@ -351,5 +359,29 @@ int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item,
     XM_HIP(hipStreamSynchronize(st));
     if (h_stats) { h_stats[0] = n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = max_now; h_stats[3] = (int64_t)h[1]; }
     return XMAP_OK;
+}
+
+extern "C" {
+
+int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                       int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                       const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                       const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                       int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats) {
+    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
+                         prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_user, out_plain, out_decay, h_stats, n_items,
+                         nullptr, nullptr);
+}
+
+int xmap_itemfold_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                                int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                                const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                                const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                                int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats, int32_t n_resident,
+                                const int64_t *new_ptr, const int32_t *new_user) {
+    XM_ARG(n_resident >= 0 && n_resident <= n_items && (n_resident == n_items || new_ptr));
+    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
+                         prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_user, out_plain, out_decay, h_stats, n_resident,
+                         new_ptr, new_user);
 }
 }

@@ -32,6 +32,17 @@ __host__ __device__ __forceinline__ int class_rank(int cls) {
     return cls == 4 ? 0 : (cls == 0 ? 1 : (cls == 2 ? 2 : (cls == 3 ? 3 : 4)));
 }
 
+// RecommenderSim (core/recommenderSim.py:90-133), shared by the LS variant of the pair kernels (tri_pairs.hip) and the item
+// fold-in (stage_e_itemfold.hip): the significance weighting of a cosine, and a leave-one-out distance as an integer that
+// orders like the number (bit pattern of a non-negative double, NaN above everything: np.max propagates NaN)
+__device__ __forceinline__ double weighted(double cs, int n, int cap) {
+    const int mn = n < cap ? n : cap;
+    return 1.0 * cs * (double)mn / (double)cap;
+}
+__device__ __forceinline__ unsigned long long ls_key(double d) {
+    return (d != d) ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(d);
+}
+
 struct RaterRec { int e0; int pos_ge; float rating; int user; };   // 16 B: one rater of an item
 // fp64 ratings (the RecommenderSim variant, LS: AlterEgo ratings are np.float64 means, core/generator.py:123-138 ->
 // core/recommenderSim.py:64-133): 16-byte profile entries and rater records of their own

@@ -126,14 +126,7 @@ __global__ __launch_bounds__(256) void k_shard_sums(const unsigned long long *sh
 // in one profile), and every pair also gets its leave-one-out local sensitivity, which needs the FINAL inner product
 // and count of the pair: after the accumulation pass the slots are finalised in LDS and the raters are walked a
 // second time, each co-rating looking its slot up and raising the slot's maximum (bit pattern of a non-negative
-// double, NaN above everything: np.max propagates NaN).
-__device__ __forceinline__ double weighted(double cs, int n, int cap) {
-    const int mn = n < cap ? n : cap;
-    return 1.0 * cs * (double)mn / (double)cap;
-}
-__device__ __forceinline__ unsigned long long ls_key(double d) {
-    return (d != d) ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(d);
-}
+// double, NaN above everything: np.max propagates NaN).  (weighted, ls_key: tri.h -- the item fold-in takes the same steps.)
 
 // Per-unit time stamps (round 3, profiles/r03c_pair_trace.txt): a unit of the smallest class lives ~14 us -- 2.0 us
 // until its item / partition / rater range are read, 3.4 us until the first rater records and prefixes are in, 9.7 us

@@ -1504,6 +1504,79 @@ class Engine(object):
         P.sources = (ptr, item, cnt_t, None, R.flags, mp)       # the batch's own raw profiles (explain_sources)
         return P
 
+    def item_foldin(self, P, ptr, user, rating, item_norm, cap, max_records=0):
+        """Item fold-in (xmap_itemfold_count / xmap_itemfold_fill): one row of RecommenderSim per item of a batch of items that are
+        not in the model, against the frozen profiles P (alterego_profiles / union_profiles) and the norms item_norm [I] of
+        rec_sim (S.norm), weighted with its cap.  The batch is a CSR of raters: ptr [B + 1] int64, user int32 (indices of P's
+        users, repeats allowed), rating float64 -- NumPy arrays or tensors; there are no times, and a batch rating is never
+        evidence.  The batch is checked on the device first (a user outside [0, n_users), a ptr that is not a CSR's: XmapError,
+        code ERR_ARG).  max_records: records (rater entry x profile row) per chunk of the sort, 0 = the library's default; the
+        result does not depend on it.  Returns (rows, avg [B], norm [B]) on the device; rows is a SimResult-like object with
+        row_ptr [B + 1], col (resident indices), sim, ls, nij -- rows not sorted -- .avg / .norm, .ptr / .user (the batch's CSR on the device,
+        what audience(batch=) takes) and .counts = (pairs, records, items with a pair).  Nothing resident changes."""
+        st = _stream(self.dev)
+
+        def dev(a, dt):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a, dt))
+            return a.to(device=self.dev, dtype=getattr(torch, np.dtype(dt).name)).contiguous()
+        ptr, user, rating = dev(ptr, np.int64), dev(user, np.int32), dev(rating, np.float64)
+        B, nnz = int(ptr.numel()) - 1, int(user.numel())
+        if B < 0 or rating.numel() != nnz:
+            raise ValueError("item fold-in batch: ptr needs an entry, user / rating one length")
+        norm_in = item_norm.to(device=self.dev, dtype=torch.float64).contiguous()
+        if int(norm_in.numel()) < P.n_items:
+            raise ValueError("item fold-in: item_norm holds %d norms, the profiles' item space has %d" % (norm_in.numel(), P.n_items))
+        cnt = self._empty(max(B, 1), torch.int32)
+        row_ptr = self._empty(B + 1, torch.int64)
+        h = (C.c_int64 * 3)(0, 0, 0)
+        with self.timed("itemfold_count"):
+            check(lib.xmap_itemfold_count(st, i64(B), i64(nnz), vp(ptr), vp(user), i64(P.n_users), i32(P.n_items), vp(P.user_ptr),
+                                          vp(P.user_item), i64(max_records), vp(cnt), vp(row_ptr), h))
+        n = int(h[0])
+        S = SimResult()
+        S.n_items, S.n_kept, S.row_ptr = B, n, row_ptr
+        S.col = self._empty(max(n, 1), torch.int32)
+        S.sim = self._empty(max(n, 1), torch.float64)
+        S.ls = self._empty(max(n, 1), torch.float64)
+        S.nij = self._empty(max(n, 1), torch.int32)
+        avg = self._empty(max(B, 1), torch.float64)
+        norm = self._empty(max(B, 1), torch.float64)
+        with self.timed("itemfold_fill"):
+            check(lib.xmap_itemfold_fill(st, i64(B), i64(nnz), vp(ptr), vp(user), vp(rating), i64(P.n_users), i32(P.n_items),
+                                         vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(norm_in), i32(cap), i64(max_records),
+                                         vp(row_ptr), vp(S.col), vp(S.sim), vp(S.ls), vp(S.nij), vp(avg), vp(norm)))
+        S.col, S.sim, S.ls, S.nij = S.col[:n], S.sim[:n], S.ls[:n], S.nij[:n]
+        S.ptr, S.user, S.cap, S.avg, S.norm = ptr, user, int(cap), avg[:B], norm[:B]
+        S.counts = tuple(int(x) for x in h)
+        return S, avg[:B], norm[:B]
+
+    def item_foldin_tables(self, neighbors, item_avg, rows, keep=None):
+        """The extended tables of I + B items for predict() / topn() / audience(batch=) / explain() (pass n_items = I + B there):
+        rows [0, I) are copies of the resident neighbors = (cnt, col, sim, ls) and item_avg, row I + q is the list of batch item
+        q -- rec_select's rule over its item_foldin rows, keep = the resident lists' width -- and rows.avg[q].  List entries are
+        resident indices; a batch item is nobody's neighbour.  Returns ((cnt, col, sim, ls), avg) on the device."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        I, B = int(cnt.numel()), int(rows.n_items)
+        width = int(col.shape[1]) if col.dim() == 2 else 1
+        keep = width if keep is None else int(keep)
+        if keep != width:
+            raise ValueError("item fold-in tables: keep = %d, the resident lists are %d wide" % (keep, width))
+        ls = neighbors[3].contiguous() if len(neighbors) > 3 and neighbors[3] is not None else torch.zeros_like(sim)
+        x_cnt = self._zeros(max(I + B, 1), torch.int32)
+        x_col = self._zeros((max(I + B, 1), keep), torch.int32)
+        x_sim = self._zeros((max(I + B, 1), keep), torch.float64)
+        x_ls = self._zeros((max(I + B, 1), keep), torch.float64)
+        x_avg = self._zeros(max(I + B, 1), torch.float64)
+        x_cnt[:I], x_col[:I], x_sim[:I], x_ls[:I], x_avg[:I] = cnt, col.view(I, keep), sim.view(I, keep), ls.view(I, keep), item_avg[:I]
+        x_avg[I:I + B] = rows.avg[:B]
+        if rows.n_kept > 0:
+            with self.timed("itemfold_select"):
+                check(lib.xmap_rec_select(st, i32(B), vp(rows.row_ptr), vp(rows.col), vp(rows.sim), vp(rows.ls), i32(keep), vp(x_cnt[I:]),
+                                          vp(x_col[I:]), vp(x_sim[I:]), vp(x_ls[I:])))
+        return (x_cnt[:I + B], x_col[:I + B], x_sim[:I + B], x_ls[:I + B]), x_avg[:I + B]
+
     @staticmethod
     def union_profiles(parts, n_users, n_items, distinct=True, timers=None):
         """The union of the AlterEgo rows of several two-domain problems as ONE set of user-major profiles
@@ -1570,11 +1643,12 @@ class Engine(object):
         P.counts = tuple(int(x) for x in h)
         return P
 
-    def predict(self, P, neighbors, test_user, test_item, item_avg, wtab):
+    def predict(self, P, neighbors, test_user, test_item, item_avg, wtab, n_items=None):
         """RecommenderPrediction.item_based_prediction on the device (xmap_predict_rows, one wave per test pair) over the
         profiles P of alterego_profiles: neighbors = (cnt [I], col [I][keep], sim [I][keep], ...) as rec_select returns
         them (or made by the host), test_user / test_item int32 tensors, item_avg [I] fp64, wtab = exp(-alpha d) fp64.
-        Returns (plain, decayed, status, max_now); a pair with status 2 and max_now > len(wtab) needs a longer table."""
+        Returns (plain, decayed, status, max_now); a pair with status 2 and max_now > len(wtab) needs a longer table.
+        n_items: the items of the tables when they are the extended ones of item_foldin_tables (default: P's item space)."""
         st = _stream(self.dev)
         cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
         T = int(test_user.numel())
@@ -1585,19 +1659,20 @@ class Engine(object):
         h = C.c_int32(0)
         with self.timed("predict_rows"):
             check(lib.xmap_predict_rows(st, i64(T), vp(test_user.contiguous()), vp(test_item.contiguous()), i64(P.n_users),
-                                        i32(P.n_items), i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
+                                        i32(P.n_items if n_items is None else n_items), i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
                                         vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()),
                                         vp(plain), vp(decay), vp(status), C.byref(h)))
         return plain[:T], decay[:T], status[:T], int(h.value)
 
-    def topn(self, P, neighbors, query_user, item_avg, wtab, n_top, rank_by=0, keep_held=False):
+    def topn(self, P, neighbors, query_user, item_avg, wtab, n_top, rank_by=0, keep_held=False, n_items=None):
         """Top-N recommendation on the device (xmap_topn_rows) over the profiles P of alterego_profiles: per query user the
         n_top (1..64) best items its own rows give evidence for, by the unrounded prediction (rank_by 0: plain, 1: decayed;
         score descending, item index ascending); items the user holds are left out unless keep_held.  neighbors, item_avg,
         wtab as predict() takes them; query_user an int32 tensor (any order, repeats allowed; an index outside the users: no
         items).  Returns (cnt [Q], item [Q][n_top] (-1 behind the count), plain, decayed [Q][n_top], stats) with stats =
         (candidates scored, candidates dropped, largest `now`, largest candidate count of a query): candidates were dropped
-        for a short table when stats[2] > len(wtab)."""
+        for a short table when stats[2] > len(wtab).  n_items: as predict() takes it (the extended tables of an item fold-in; a
+        batch item is listed as I + q, also for its own raters: the frozen profiles do not hold it)."""
         st = _stream(self.dev)
         cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
         Q, n_top = int(query_user.numel()), int(n_top)
@@ -1611,19 +1686,21 @@ class Engine(object):
         h = (C.c_int64 * 4)(0, 0, 0, 0)
         with self.timed("topn"):
             check(lib.xmap_topn_rows(st, i64(Q), vp(query_user.contiguous()), i32(n_top), i32(rank_by), i32(abi.TOPN_KEEP_HELD if keep_held else 0),
-                                     i64(P.n_users), i32(P.n_items), i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
-                                     vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()),
-                                     vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
+                                     i64(P.n_users), i32(P.n_items if n_items is None else n_items), i32(keep), vp(cnt), vp(col), vp(sim),
+                                     vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()),
+                                     vp(wtab), i32(wtab.numel()), vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
         return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
 
-    def audience(self, P, neighbors, query_item, item_avg, wtab, n_top, rank_by=0, keep_holders=False):
+    def audience(self, P, neighbors, query_item, item_avg, wtab, n_top, rank_by=0, keep_holders=False, batch=None):
         """The audience of an item on the device (xmap_audience_rows) over the profiles P of alterego_profiles: per query
         item the n_top (1..1024) best users among those whose own rows give evidence for it, by the unrounded prediction
         (rank_by 0: plain, 1: decayed; score descending, user index ascending); users who hold the item are left out unless
         keep_holders.  topn() seen from the item: the same pairs, the same score bits.  neighbors, item_avg, wtab as predict()
         takes them; query_item an int32 tensor (any order, repeats allowed; an index outside the items or an item without a
         list: no users).  Returns (cnt [Q], user [Q][n_top] (-1 behind the count), plain, decayed [Q][n_top], stats) with stats
-        as topn() returns them."""
+        as topn() returns them.  batch = (ptr, user) of an item fold-in (item_foldin's rows.ptr / rows.user, device tensors):
+        neighbors and item_avg are then the extended tables of item_foldin_tables, query items I + q are the batch's, and their
+        raters are their holders (xmap_itemfold_audience_rows)."""
         st = _stream(self.dev)
         cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
         Q, n_top = int(query_item.numel()), int(n_top)
@@ -1635,6 +1712,20 @@ class Engine(object):
         out_plain = self._empty((max(Q, 1), n_top), torch.float64)
         out_decay = self._empty((max(Q, 1), n_top), torch.float64)
         h = (C.c_int64 * 4)(0, 0, 0, 0)
+        if batch is not None:
+            b_ptr, b_user = batch[0].contiguous(), batch[1].contiguous()
+            n_all = int(cnt.numel())
+            n_res = n_all - (int(b_ptr.numel()) - 1)
+            if n_res < 0 or b_ptr.dtype != torch.int64 or b_user.dtype != torch.int32:
+                raise ValueError("audience: batch = (ptr int64 [B + 1], user int32) of at most as many items as the tables hold")
+            with self.timed("audience"):
+                check(lib.xmap_itemfold_audience_rows(st, i64(Q), vp(query_item.contiguous()), i32(n_top), i32(rank_by),
+                                                      i32(abi.AUDIENCE_KEEP_HOLDERS if keep_holders else 0), i64(P.n_users), i32(n_all),
+                                                      i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
+                                                      vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab),
+                                                      i32(wtab.numel()), vp(out_cnt), vp(out_user), vp(out_plain), vp(out_decay), h,
+                                                      i32(n_res), vp(b_ptr), vp(b_user)))
+            return out_cnt[:Q], out_user[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
         with self.timed("audience"):
             check(lib.xmap_audience_rows(st, i64(Q), vp(query_item.contiguous()), i32(n_top), i32(rank_by),
                                          i32(abi.AUDIENCE_KEEP_HOLDERS if keep_holders else 0), i64(P.n_users), i32(P.n_items), i32(keep),

@@ -102,6 +102,8 @@ EXPORTS = [
     "xmap_ctx_rec_neighbors_download", "xmap_ctx_predict", "xmap_ctx_recommend", "xmap_ctx_evaluate_topn",
     "xmap_ctx_foldin", "xmap_ctx_foldin_download", "xmap_ctx_foldin_recommend", "xmap_ctx_foldin_predict", "xmap_ctx_union",
     "xmap_ctx_explain", "xmap_ctx_foldin_explain", "xmap_ctx_audience", "xmap_ctx_foldin_audience",
+    "xmap_itemfold_count", "xmap_itemfold_fill", "xmap_itemfold_audience_rows", "xmap_ctx_item_foldin", "xmap_ctx_item_foldin_download",
+    "xmap_ctx_item_foldin_audience", "xmap_ctx_item_foldin_predict", "xmap_ctx_item_foldin_recommend",
 ]
 
 if not os.path.exists(LIB_PATH):

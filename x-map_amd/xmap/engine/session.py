@@ -426,14 +426,16 @@ def recommend(alterEgoRDD, testRDD, cap, keep, alpha, neighbors=None):
     return res
 
 
-def _predict_records(st, eng2, P, nb, item_avg, uidx, testRDD, alpha):
-    """what recommend and recommend_profiles share: the held-out pairs of testRDD against the profiles P (uidx: uid -> user index
-    of P) -> the LocalRDD of (uid, [(iid, real, plain, decayed) | ()]) with .mae"""
+def _predict_records(st, eng2, P, nb, item_avg, uidx, testRDD, alpha, iidx=None, n_items=None):
+    """what recommend, recommend_profiles and recommend_items share: the held-out pairs of testRDD against the profiles P (uidx:
+    uid -> user index of P; iidx: iid -> item index of the tables, default the train set's; n_items: the items of the tables
+    when they are extended ones) -> the LocalRDD of (uid, [(iid, real, plain, decayed) | ()]) with .mae"""
     import torch
     idt, dev = st.idt, st.engine.dev
+    iidx = idt.iidx if iidx is None else iidx
     recs = records_of(testRDD)
     tu = np.fromiter((uidx.get(uid, -1) for uid, pairs in recs for _ in pairs), np.int32)
-    ti = np.fromiter((idt.iidx.get(pair[0], -1) for _, pairs in recs for pair in pairs), np.int32)
+    ti = np.fromiter((iidx.get(pair[0], -1) for _, pairs in recs for pair in pairs), np.int32)
     try:
         real = np.fromiter((float(pair[1]) for _, pairs in recs for pair in pairs), np.float64)
     except (TypeError, ValueError):
@@ -442,7 +444,7 @@ def _predict_records(st, eng2, P, nb, item_avg, uidx, testRDD, alpha):
     n_w = 66
     while True:
         wtab = _decay_table(alpha, n_w, dev)
-        plain, decay, status, max_now = eng2.predict(P, nb, d_tu, d_ti, item_avg, wtab)
+        plain, decay, status, max_now = eng2.predict(P, nb, d_tu, d_ti, item_avg, wtab, n_items=n_items)
         if max_now <= n_w:
             break
         n_w = max_now
@@ -669,16 +671,18 @@ def recommend_audience(alterEgoRDD, items, cap, keep, alpha, n, decay=False, kee
     return res
 
 
-def _audience_records(st, eng2, P, nb, item_avg, iids, uids, alpha, n, decay, keep_holders, ctx):
-    """what recommend_audience and recommend_audience_profiles share: the audiences of the items `iids` among the users of P,
-    labelled `uids` by index -> the LocalRDD of (iid, [(uid, plain, decayed)*]) with .stats"""
+def _audience_records(st, eng2, P, nb, item_avg, iids, uids, alpha, n, decay, keep_holders, ctx, iidx=None, batch=None):
+    """what recommend_audience, recommend_audience_profiles and recommend_audience_items share: the audiences of the items
+    `iids` among the users of P, labelled `uids` by index -> the LocalRDD of (iid, [(uid, plain, decayed)*]) with .stats.
+    iidx / batch: the item indices and the rater CSR of an item fold-in, whose extended tables nb and item_avg then are"""
     import torch
     idt, dev = st.idt, st.engine.dev
-    d_q = torch.from_numpy(np.fromiter((idt.iidx.get(iid, -1) for iid in iids), np.int32, len(iids))).to(dev)
+    iidx = idt.iidx if iidx is None else iidx
+    d_q = torch.from_numpy(np.fromiter((iidx.get(iid, -1) for iid in iids), np.int32, len(iids))).to(dev)
     n_w = 66
     while True:
         wtab = _decay_table(alpha, n_w, dev)
-        cnt, user, plain, decayed, stats = eng2.audience(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_holders)
+        cnt, user, plain, decayed, stats = eng2.audience(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_holders, batch=batch)
         if stats[2] <= n_w:
             break
         n_w = stats[2]
@@ -702,6 +706,85 @@ def recommend_audience_profiles(alterEgoRDD, profiles, items, cap, keep, alpha, 
                             getattr(items, "ctx", None))
     res.unknown_items, res.counts = unknown, F.counts
     _tail_dicts(res, st, S, nb)
+    return res
+
+
+def _item_fold_in(st, eng2, P, S, nb, item_avg, new_items):
+    """new items [(iid, [(uid, rating)*])*] (an RDD or a list) -> (their RecommenderSim rows: Engine.item_foldin against the
+    profiles P with the norms and the cap of S, the extended tables of Engine.item_foldin_tables, {iid: index in the batch},
+    entries dropped for a uid the train set does not know).  The iids are labels; one the train set knows, or a repeated one,
+    raises ValueError: a resident item has its row already."""
+    idt = st.idt
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    recs = records_of(new_items)
+    index = {}
+    for k, rec in enumerate(recs):
+        if rec[0] in index:
+            raise ValueError("fold-in item %r occurs more than once" % (rec[0],))
+        if rec[0] in idt.iidx:
+            raise ValueError("fold-in item %r is an item of the train set" % (rec[0],))
+        index[rec[0]] = k
+    ptr = np.zeros(len(recs) + 1, np.int64)
+    user, rating, unknown = [], [], 0
+    for k, (_, raters) in enumerate(recs):
+        for entry in raters:
+            u = uidx.get(entry[0])
+            if u is None:
+                unknown += 1
+                continue
+            user.append(u); rating.append(float(entry[1]))
+        ptr[k + 1] = len(user)
+    rows, _, _ = eng2.item_foldin(P, ptr, np.asarray(user, np.int32), np.asarray(rating, np.float64), S.norm, S.cap)
+    x_nb, x_avg = eng2.item_foldin_tables(nb, item_avg, rows)
+    return rows, x_nb, x_avg, index, unknown
+
+
+def _item_dicts(res, st, rows, x_nb, index):
+    """.new_sim_pairs {iid: [(nid, sim)*]} and .new_item_info {iid: (avg, norm, raters)} of the batch of an item fold-in"""
+    I, iids = len(st.idt.iids), st.idt.iids
+    cnt, col, sim = [x[I:].cpu().numpy() for x in x_nb[:3]]
+    avg, norm, n = rows.avg.cpu().numpy(), rows.norm.cpu().numpy(), np.diff(rows.ptr.cpu().numpy())
+    res.new_sim_pairs = {iid: [(iids[col[q, t]], float(sim[q, t])) for t in range(cnt[q])] for iid, q in index.items() if cnt[q] > 0}
+    res.new_item_info = {iid: (float(avg[q]), float(norm[q]), int(n[q])) for iid, q in index.items()}
+
+
+def recommend_audience_items(alterEgoRDD, new_items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None):
+    """recommend_audience for items that are not items of the train set -- a book that enters the catalogue: `new_items` is an
+    RDD or list of (iid, [(uid, rating)*]), the ratings the item has collected so far from users of the train set.  Each item
+    gets one row of RecommenderSim against the frozen AlterEgo profiles (item fold-in: Engine.item_foldin), its neighbour list
+    by the rule of the resident lists, and then the audience of recommend_audience from the model trained on alterEgoRDD's rows,
+    which stays as it is; the item's raters are its holders (left out unless keep_holders).  The iids are labels only: a
+    repeated one, or one the train set knows, raises ValueError; an entry whose uid the train set does not know is dropped and
+    counted in .unknown_users.  Works on a union of AlterEgo rows as well (it reads the tail only).  Returns the LocalRDD of
+    (iid, [(uid, plain, decayed)*]) in the order of `new_items`, with .stats, .sim_pairs, .item_info, .unknown_users, .counts =
+    (pairs, records, items with a pair), .new_sim_pairs {iid: [(nid, sim)*]} and .new_item_info {iid: (avg, norm, raters)}."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_audience_items")
+    rows, x_nb, x_avg, index, unknown = _item_fold_in(st, eng2, P, S, nb, item_avg, new_items)
+    I = len(st.idt.iids)
+    iids = sorted(index, key=index.get)
+    res = _audience_records(st, eng2, P, x_nb, x_avg, iids, st.idt.uids, alpha, n, decay, keep_holders, getattr(new_items, "ctx", None),
+                            iidx={iid: I + q for iid, q in index.items()}, batch=(rows.ptr, rows.user))
+    res.unknown_users, res.counts = unknown, rows.counts
+    _tail_dicts(res, st, S, nb)
+    _item_dicts(res, st, rows, x_nb, index)
+    return res
+
+
+def recommend_items(alterEgoRDD, new_items, testRDD, cap, keep, alpha, neighbors=None):
+    """recommend for items that are not items of the train set: `new_items` as recommend_audience_items takes them and folds
+    them in, testRDD the held-out (uid, [(iid, rating, ...)*]) records whose iids are looked up among the new items' labels
+    first, then in the train set -- one that is neither is an item without a list.  Returns the LocalRDD of recommend (with
+    .mae, .sim_pairs, .item_info) and .unknown_users, .counts, .new_sim_pairs, .new_item_info."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_items")
+    rows, x_nb, x_avg, index, unknown = _item_fold_in(st, eng2, P, S, nb, item_avg, new_items)
+    idt, I = st.idt, len(st.idt.iids)
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    iidx = dict(idt.iidx)
+    iidx.update({iid: I + q for iid, q in index.items()})
+    res = _predict_records(st, eng2, P, x_nb, x_avg, uidx, testRDD, alpha, iidx=iidx, n_items=I + len(index))
+    res.unknown_users, res.counts = unknown, rows.counts
+    _tail_dicts(res, st, S, nb)
+    _item_dicts(res, st, rows, x_nb, index)
     return res
 
 
