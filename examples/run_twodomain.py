@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -19,6 +19,11 @@ three strongest evidence entries of its score with their share, and the user's o
 --audience (with --device-tail): the other direction -- for three target items the ten users to tell about them
 (xmap.engine.session.recommend_audience: the users whose own rows give evidence for the item and who do not hold it yet, by
 the same unrounded prediction).
+
+--eligible (with --device-tail): both directions under eligibility rules -- the top 5 of the same three users over every second
+target item of the catalogue ("in stock") with a score floor, without the item that led their unrestricted list ("shown
+yesterday"); and the audiences of three items among every third user (a segment) above the same floor (the allow_items= /
+allow_users=, exclude= and min_score= options of recommend_topn and recommend_audience: the rules act before scoring).
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -96,6 +101,7 @@ def main(argv=None):
     ap.add_argument("--explain", action="store_true")
     ap.add_argument("--audience", action="store_true")
     ap.add_argument("--new-items", action="store_true")
+    ap.add_argument("--eligible", action="store_true")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -106,9 +112,9 @@ def main(argv=None):
     b, g, rc = para["baseliner"], para["generator"], para["recommender"]
     t = {}
 
-    def timed(name, f, *a):
+    def timed(name, f, *a, **kw):
         t0 = time.time()
-        out = f(*a)
+        out = f(*a, **kw)
         t[name] = time.time() - t0
         return out
     clean_s = BaselinerClean(b["num_atleast_rating"], b["size_subset"], b["date_from"], b["date_to"], domain_label="S:")
@@ -123,6 +129,8 @@ def main(argv=None):
     trainRDD, testRDD = timed("split", assist.baseliner_split_data_pipeline, sc, split, sourceRDD, targetRDD)
     if args.audience and (not args.device_tail or para["recommender"]["private_flag"]):
         ap.error("--audience needs --device-tail and the non-private recommender")
+    if args.eligible and (not args.device_tail or para["recommender"]["private_flag"]):
+        ap.error("--eligible needs --device-tail and the non-private recommender")
     late = []                   # (uid, profile) of the users who arrive after training
     if args.fold_in:
         if not args.device_tail or para["recommender"]["private_flag"]:
@@ -192,6 +200,25 @@ def main(argv=None):
                     rc["mapping_range"], rc["decay_alpha"], 10)
         for iid, lst in aud.collect():
             print("audience of %s:" % iid, ", ".join("%s (%.3f)" % (uid, plain) for uid, plain, _ in lst) or "no evidence")
+    if args.eligible:
+        # the same two calls under eligibility rules: a catalogue subset, yesterday's item, a segment, a floor
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        in_stock = sorted(top.sim_pairs)[::2]
+        shown = {uid: [lst[0][0]] for uid, lst in top.collect() if lst}
+        floor = 3.0
+        el = timed("eligible_topn", session.recommend_topn, alterEgo_profile, [uid for uid, _ in top.collect()], w, k, alpha, 5,
+                   allow_items=in_stock, exclude=shown, min_score=floor)
+        print("eligible: %d of %d listed items in stock, floor %.1f: %d pairs scored, %d removed before scoring, %d below the floor" % (
+            len(in_stock), len(top.sim_pairs), floor, el.stats[0], el.stats[5], el.stats[4]))
+        for uid, lst in el.collect():
+            print("eligible top 5 for %s:" % uid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "nothing eligible")
+        segment = trainRDD.map(lambda rec: rec[0]).collect()[::3]
+        el = timed("eligible_audience", session.recommend_audience, alterEgo_profile, in_stock[:3], w, k, alpha, 10,
+                   allow_users=segment, min_score=floor)
+        print("eligible: a segment of %d users: %d pairs scored, %d removed before scoring, %d below the floor" % (
+            len(segment), el.stats[0], el.stats[5], el.stats[4]))
+        for iid, lst in el.collect():
+            print("eligible audience of %s:" % iid, ", ".join("%s (%.3f)" % (uid, plain) for uid, plain, _ in lst) or "nobody eligible")
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

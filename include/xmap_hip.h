@@ -800,6 +800,49 @@ int xmap_itemfold_audience_rows(void *stream, int64_t n_query, const int32_t *qu
                                 int64_t *h_stats /* host, [4] or NULL, as xmap_audience_rows */,
                                 int32_t n_resident, const int64_t *new_ptr /*[n_new+1]*/, const int32_t *new_user);
 
+/* ---- eligibility rules for xmap_topn_rows and xmap_audience_rows (csrc/rec_filter.h; DESIGN.md 4 "Eligibility"): which ids a
+ * call may return at all.  The rules act inside the candidate pass, BEFORE scoring -- no ineligible pair is scored -- so the n_top
+ * best ELIGIBLE candidates are selected, which no filter over a returned list can do.  n = n_items (top-N) or n_users (audience). */
+typedef struct {
+    const uint32_t *allow;  /* bit (id & 31) of word (id >> 5) set: id is eligible.  (n + 31) / 32 words, n = n_items (top-N)
+                               or n_users (audience).  Bits at or beyond n may hold anything.  NULL: every id is eligible. */
+    const int64_t *ex_ptr;  /* [n_query + 1], ex_ptr[0] = 0, non-decreasing.  NULL: no exclusions. */
+    const int32_t *ex_id;   /* ids never returned for query q: ex_id[ex_ptr[q] .. ex_ptr[q + 1]).  Any order, repeats allowed,
+                               an id outside [0, n) is ignored.  Per QUERY, not per user: a repeated query may carry another list. */
+    double min_score;       /* a scored candidate is kept iff its rank_by score >= min_score (as numbers).  -INFINITY: no floor.
+                               NaN: XMAP_ERR_ARG. */
+} xmap_rec_filter;
+/* The fine-grained calls take DEVICE pointers in the struct (itself in host memory), the coarse calls host pointers.  F == NULL
+ * means {NULL, NULL, NULL, -INFINITY}, and with such a filter the calls return, bit for bit, what the unfiltered calls return.
+ * Order of the rules: (1) the candidates as in the unfiltered call; (2) without the KEEP_* flag the held items / the holders
+ * leave; (3) the ids of the query's exclusion list leave; (4) what remains is intersected with allow; (5) scores; (6) the
+ * status-2 candidates are dropped and counted; (7) the candidates below the floor are dropped and counted; (8) selection --
+ * ranking, ties and padding exactly as in the unfiltered calls.
+ * h_stats (host, [6] or NULL): [0..3] as in the unfiltered calls, taken over the ELIGIBLE candidates; [4] = candidates with status
+ * 0 whose rank_by score is below min_score; [5] = candidate pairs removed by the mask or the exclusion lists = the [0] of the
+ * unfiltered call minus this call's [0] (a held item that is also excluded does not count, a repeated exclusion counts once).
+ * Limit, shared with the unfiltered calls and xmap_predict_rows: the scoring pass launches one wave per pair in ONE grid, which
+ * beyond 6.7e7 pairs has more than 2^32 threads -- keep the candidate pairs of a call (h_stats[0]) below that; the rules are one
+ * way to get there, fewer queries per call the other.
+ * ex_ptr is checked on the device before any candidate work (ex_ptr[0] == 0, non-decreasing; ids listed while ex_id == NULL):
+ * XMAP_ERR_ARG, nothing is read through a table that fails.
+ * xmap_topn_rows_filtered: the arguments of xmap_topn_rows up to out_decay, then F and h_stats [6].
+ * xmap_audience_rows_filtered: the arguments of xmap_itemfold_audience_rows up to out_decay, then n_resident, new_ptr, new_user
+ *   (new_ptr == NULL: resident items only, n_resident is ignored), then F and h_stats [6]: one entry for both audience calls. */
+int xmap_topn_rows_filtered(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                            int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                            const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                            const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
+                            int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
+                            const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
+int xmap_audience_rows_filtered(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                                int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                                const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                                const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
+                                int32_t *out_cnt, int32_t *out_user, double *out_plain, double *out_decay,
+                                int32_t n_resident, const int64_t *new_ptr /*[n_new+1] or NULL*/, const int32_t *new_user,
+                                const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
+
 /* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
  * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
  * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
@@ -972,6 +1015,16 @@ int xmap_union_fill(void *stream, int32_t n_parts, const xmap_union_part *parts 
  *                             (both: an index outside [0, n_new) behaves like an item without a list)
  *   xmap_ctx_item_foldin_recommend : xmap_ctx_recommend over all I + n_new items: a batch item q is returned as I + q.  Limit:
  *                             top-N does not leave a batch item out of its own raters' lists -- the frozen profiles do not hold it
+ * Eligibility (xmap_rec_filter above, HOST pointers inside; F == NULL: no rule): one entry per direction serves all three sources
+ *   xmap_ctx_recommend_filtered : source XMAP_SRC_RESIDENT = xmap_ctx_recommend (also on a union context), XMAP_SRC_FOLDIN =
+ *                             xmap_ctx_foldin_recommend, XMAP_SRC_ITEM_FOLDIN = xmap_ctx_item_foldin_recommend -- each with the
+ *                             preconditions and the index spaces of that call; the mask and the exclusion ids are ITEMS (n = I, or
+ *                             I + n_new for source 2)
+ *   xmap_ctx_audience_filtered : likewise xmap_ctx_audience / xmap_ctx_foldin_audience / xmap_ctx_item_foldin_audience; the mask
+ *                             and the exclusion ids are USERS (the batch's users for source 1)
+ *                             stats [6] (may be NULL) as h_stats of the fine-grained calls.  The host checks min_score (NaN), ex_ptr
+ *                             (ex_ptr[0] == 0, non-decreasing), ex_id (NULL while ids are listed) and source before any device
+ *                             work: XMAP_ERR_ARG, the outputs untouched, the context as it was
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -1068,6 +1121,17 @@ int xmap_ctx_item_foldin_predict(xmap_ctx *ctx, int64_t n_test, const int32_t *t
 int xmap_ctx_item_foldin_recommend(xmap_ctx *ctx, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
                                    int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item,
                                    double *out_plain, double *out_decay, int64_t *stats /* [4] or NULL */);
+#define XMAP_SRC_RESIDENT 0
+#define XMAP_SRC_FOLDIN 1
+#define XMAP_SRC_ITEM_FOLDIN 2
+int xmap_ctx_recommend_filtered(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top,
+                                int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item,
+                                double *out_plain, double *out_decay, const xmap_rec_filter *F /* host pointers inside, or NULL */,
+                                int64_t *stats /* [6] or NULL */);
+int xmap_ctx_audience_filtered(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_item, int32_t n_top,
+                               int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user,
+                               double *out_plain, double *out_decay, const xmap_rec_filter *F /* host pointers inside, or NULL */,
+                               int64_t *stats /* [6] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

@@ -965,16 +965,51 @@ static int predict_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t
     return XMAP_OK;
 }
 
+// The eligibility rules of a coarse call (xmap_rec_filter with HOST pointers), checked on the host before any device work, as
+// xmap_ctx_foldin checks its batch
+static int check_filter(const xmap_rec_filter *F, int64_t n_query) {
+    if (!F) return XMAP_OK;
+    if (F->min_score != F->min_score) { set_error("filter: min_score is NaN"); return XMAP_ERR_ARG; }
+    if (!F->ex_ptr || n_query <= 0) return XMAP_OK;
+    if (F->ex_ptr[0] != 0) { set_error("filter: ex_ptr[0] = %lld, not 0", (long long)F->ex_ptr[0]); return XMAP_ERR_ARG; }
+    for (int64_t q = 0; q < n_query; q++)
+        if (F->ex_ptr[q + 1] < F->ex_ptr[q]) { set_error("filter: ex_ptr[%lld] < ex_ptr[%lld]", (long long)q + 1, (long long)q); return XMAP_ERR_ARG; }
+    if (F->ex_ptr[n_query] > 0 && !F->ex_id) { set_error("filter: ex_ptr lists %lld ids, ex_id is NULL", (long long)F->ex_ptr[n_query]); return XMAP_ERR_ARG; }
+    return XMAP_OK;
+}
+
+// the device copy of a checked host filter over an id space of n ids (n_query > 0)
+static int upload_filter(xmap_ctx *c, ScratchPool &tmp, const xmap_rec_filter *F, int64_t n_query, int64_t n, xmap_rec_filter *D) {
+    D->allow = nullptr; D->ex_ptr = nullptr; D->ex_id = nullptr;
+    D->min_score = F ? F->min_score : -__builtin_inf();
+    if (!F) return XMAP_OK;
+    if (F->allow) {
+        uint32_t *d_allow;
+        XM_TRY(h2d(tmp, &d_allow, F->allow, (size_t)((n + 31) / 32), c->st));
+        D->allow = d_allow;
+    }
+    if (F->ex_ptr) {
+        int64_t *d_ptr;
+        int32_t *d_id;
+        XM_TRY(h2d(tmp, &d_ptr, F->ex_ptr, (size_t)n_query + 1, c->st));
+        XM_TRY(h2d(tmp, &d_id, F->ex_id, (size_t)F->ex_ptr[n_query], c->st));
+        D->ex_ptr = d_ptr; D->ex_id = d_id;
+    }
+    return XMAP_OK;
+}
+
+// n_stats = 4: the unfiltered entry (F is NULL); 6: the filtered one
 static int recommend_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
                           int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain,
-                          double *out_decay, int64_t *stats) {
+                          double *out_decay, int64_t *stats, const xmap_rec_filter *F = nullptr, int n_stats = 4) {
     XM_ARG(n_top >= 1 && n_top <= 64);
     XM_ARG(rank_by == 0 || rank_by == 1);
     XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
     XM_ARG(n_w >= 1 && wtab);
     XM_ARG(n_query >= 0 && (n_query == 0 || (query_user && out_cnt && out_item && out_plain && out_decay)));
+    XM_TRY(check_filter(F, n_query));
     XM_HIP(hipSetDevice(c->device));
-    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (stats) for (int k = 0; k < n_stats; k++) stats[k] = 0;
     if (n_query == 0) return XMAP_OK;
     ScratchPool tmp;
     int32_t *d_user, *d_cnt, *d_item;
@@ -984,8 +1019,14 @@ static int recommend_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64
     XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
     XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
-    XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
-                          P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
+    if (n_stats == 6) {
+        xmap_rec_filter D;
+        XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+        XM_TRY(xmap_topn_rows_filtered(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
+                                       P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, &D, stats));
+    } else
+        XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
+                              P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
@@ -996,14 +1037,15 @@ static int recommend_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64
 
 static int audience_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
                          int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain,
-                         double *out_decay, int64_t *stats) {
+                         double *out_decay, int64_t *stats, const xmap_rec_filter *F = nullptr, int n_stats = 4) {
     XM_ARG(n_top >= 1 && n_top <= 1024);
     XM_ARG(rank_by == 0 || rank_by == 1);
     XM_ARG((flags & ~XMAP_AUDIENCE_KEEP_HOLDERS) == 0);
     XM_ARG(n_w >= 1 && wtab);
     XM_ARG(n_query >= 0 && (n_query == 0 || (query_item && out_cnt && out_user && out_plain && out_decay)));
+    XM_TRY(check_filter(F, n_query));
     XM_HIP(hipSetDevice(c->device));
-    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (stats) for (int k = 0; k < n_stats; k++) stats[k] = 0;
     if (n_query == 0) return XMAP_OK;
     ScratchPool tmp;
     int32_t *d_item, *d_cnt, *d_user;
@@ -1013,7 +1055,13 @@ static int audience_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_
     XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
     XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_user, m, c->st));
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
-    if (T.new_ptr)
+    if (n_stats == 6) {
+        xmap_rec_filter D;
+        XM_TRY(upload_filter(c, tmp, F, n_query, P.n_users, &D));
+        XM_TRY(xmap_audience_rows_filtered(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
+                                           P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay,
+                                           T.n_resident, T.new_ptr, T.new_user, &D, stats));
+    } else if (T.new_ptr)
         XM_TRY(xmap_itemfold_audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
                                            P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay, stats,
                                            T.n_resident, T.new_ptr, T.new_user));
@@ -1255,6 +1303,36 @@ int xmap_ctx_item_foldin_recommend(xmap_ctx *c, int64_t n_query, const int32_t *
     XM_ARG(c && c->have_gen && c->have_rec && c->have_nb && c->have_ifold);
     return recommend_over(c, resident_profiles(c), itemfold_tables(c), n_query, query_user, n_top, rank_by, flags, wtab, n_w, out_cnt,
                           out_item, out_plain, out_decay, stats);
+}
+
+// ---- eligibility: one filtered entry per direction, over the three sources ------------------------------------------------
+
+int xmap_ctx_recommend_filtered(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
+                                int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                                double *out_decay, const xmap_rec_filter *F, int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN || source == XMAP_SRC_ITEM_FOLDIN);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(source != XMAP_SRC_ITEM_FOLDIN || c->have_ifold);
+    return recommend_over(c, source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c),
+                          source == XMAP_SRC_ITEM_FOLDIN ? itemfold_tables(c) : resident_tables(c), n_query, query_user, n_top, rank_by, flags,
+                          wtab, n_w, out_cnt, out_item, out_plain, out_decay, stats, F, 6);
+}
+
+int xmap_ctx_audience_filtered(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by,
+                               int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user, double *out_plain,
+                               double *out_decay, const xmap_rec_filter *F, int64_t *stats) {
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN || source == XMAP_SRC_ITEM_FOLDIN);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(source != XMAP_SRC_ITEM_FOLDIN || (c->have_ifold && n_query >= 0));
+    if (source == XMAP_SRC_ITEM_FOLDIN) {       // query_item = indices into the batch
+        const std::vector<int32_t> q = batch_items(c, n_query, query_item);
+        return audience_over(c, resident_profiles(c), itemfold_tables(c), n_query, query_item ? q.data() : nullptr, n_top, rank_by, flags,
+                             wtab, n_w, out_cnt, out_user, out_plain, out_decay, stats, F, 6);
+    }
+    return audience_over(c, source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c), resident_tables(c), n_query, query_item,
+                         n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain, out_decay, stats, F, 6);
 }
 
 // ---- explanations -------------------------------------------------------------------------------------------------------

@@ -1,0 +1,72 @@
+// rec_filter.h -- the eligibility rules of the filtered top-N and audience calls (xmap_rec_filter; DESIGN.md 4 "Eligibility"):
+// what stage_e_topn.hip and stage_e_audience.hip share.  Both candidate passes hold the candidate set of a query as an LDS
+// bitmap of a window of the id space; the rules act on that bitmap, before anything is scored:
+//   exclusions : the block strides the query's list and clears the ids that fall into the window (their words stay listed as
+//                touched, like the words of held items);
+//   allow      : a touched word is ANDed with its word of the mask where it is emitted -- rf_eligible, the ONE statement of
+//                "the eligible bits of word w" that the count pass and the fill pass both call: if they ever disagreed the fill
+//                pass would write outside buffers of exactly the counted size.
+// The floor acts in the selection kernels, beside the status-2 drop.
+#ifndef XMAP_REC_FILTER_H
+#define XMAP_REC_FILTER_H
+#include "common.h"
+
+namespace xmap {
+
+// bw = the candidate bits of word `word` of the id space (bit b = id 32 word + b, all of them < n: a candidate is an id of the
+// tables); allow has a word for every id < n, so every touched word has one, and garbage bits at or beyond n meet zeros
+template <bool FILT>
+__device__ __forceinline__ unsigned int rf_eligible(unsigned int bw, const unsigned int *allow, long long word) {
+    if constexpr (FILT) {
+        if (allow) bw &= allow[word];
+    }
+    return bw;
+}
+
+// ex_ptr[0 .. n_query]: bad[0] += positions k with ptr[k] < ptr[k - 1] (k = 0: ptr[0] != 0), bad[1] = ptr[n_query].  Bounded by
+// n_query alone: nothing is read through the table before it has passed.
+static __global__ __launch_bounds__(256) void k_rf_check(long long n_query, const long long *ex_ptr, unsigned long long *bad) {
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k <= n_query; k += step) {
+        const bool b = k == 0 ? ex_ptr[0] != 0 : ex_ptr[k] < ex_ptr[k - 1];
+        if (b) atomicAdd(&bad[0], 1ull);        // (bad input only: no need to spare the atomics)
+        if (k == n_query) bad[1] = (unsigned long long)ex_ptr[k];
+    }
+}
+
+// The argument checks of a filtered fine-grained call, before any candidate work.  *filt = the candidate pass needs its FILT
+// instantiation (a mask or an exclusion list is given); *min_score = the floor (-inf without F).  Synchronises iff ex_ptr is given.
+static int rf_prepare(hipStream_t st, int64_t n_query, const xmap_rec_filter *F, bool *filt, double *min_score) {
+    *filt = false;
+    *min_score = -__builtin_inf();
+    if (!F) return XMAP_OK;
+    if (F->min_score != F->min_score) {
+        set_error("xmap_rec_filter: min_score is NaN");
+        return XMAP_ERR_ARG;
+    }
+    *min_score = F->min_score;
+    if (F->ex_ptr && n_query > 0) {
+        unsigned long long *bad = nullptr, h_bad[2] = {0, 0};
+        XM_HIP(xm_malloc_async((void **)&bad, sizeof(h_bad), st));
+        XM_HIP(hipMemsetAsync(bad, 0, sizeof(h_bad), st));
+        const long long total = n_query + 1;
+        const unsigned blocks = (unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+        k_rf_check<<<dim3(blocks), dim3(256), 0, st>>>(n_query, (const long long *)F->ex_ptr, bad);
+        XM_LAUNCH_CHECK();
+        XM_HIP(hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+        XM_HIP(hipStreamSynchronize(st));
+        if (h_bad[0]) {
+            set_error("xmap_rec_filter: ex_ptr has %llu bad entries (ex_ptr[0] = 0, non-decreasing)", h_bad[0]);
+            return XMAP_ERR_ARG;
+        }
+        if (h_bad[1] > 0 && !F->ex_id) {
+            set_error("xmap_rec_filter: ex_ptr lists %llu ids, ex_id is NULL", h_bad[1]);
+            return XMAP_ERR_ARG;
+        }
+    }
+    *filt = F->allow != nullptr || (F->ex_ptr != nullptr && n_query > 0);
+    return XMAP_OK;
+}
+
+}  // namespace xmap
+#endif

@@ -24,13 +24,18 @@
 //                     sorted prefix is the same whatever order the survivors were staged in.  Status 2: dropped and counted.
 // Items of an item fold-in (stage_e_itemfold.hip; query items >= n_resident of xmap_itemfold_audience_rows): no profile holds them, their
 // holders are the batch's raters -- a second, optional holder CSR that the clear pass of k_au_candidates reads for them.
+// xmap_audience_rows_filtered (rec_filter.h; DESIGN.md 4 "Eligibility"): the FILT instantiation of k_au_candidates clears the
+// query's exclusion ids in the bitmap and ANDs every emitted word with the user mask -- before anything is scored -- and
+// k_au_select drops and counts the candidates below the score floor.
 // Every output position follows from the scans, so the result does not depend on the grid or on the order of the atomics.
 #include "common.h"
 #include "predict_rows.h"
+#include "rec_filter.h"
 
 namespace xmap {
 
 constexpr int AU_WINDOW = 1 << 20;              // users per bitmap pass (128 KB of LDS + 4 KB of summary: one block per CU)
+static_assert(AU_WINDOW % 32 == 0, "a window starts at a word of the mask");
 constexpr int AU_WORDS = AU_WINDOW / 32;
 constexpr int AU_SUMMARY = AU_WORDS / 32;       // second level: bit w of word s = bitmap word 32 s + w was touched
 constexpr int AU_THREADS = 1024;                // 16 waves stride a holder row; thread t emits summary word t (thread order = user order)
@@ -80,18 +85,23 @@ __device__ __forceinline__ int au_block_scan(int v, int *total, int *smem) {
     return base + inc - v;
 }
 
-template <bool FILL>
+// FILT (rec_filter.h): the query's exclusion ids are cleared behind the holders, and a touched word meets its word of the mask
+// where it is emitted; the count pass adds what the two removed to *removed.  FILT = false is the unfiltered kernel.
+template <bool FILL, bool FILT>
 __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query, const int *query_item, long long U, int I, int keep,
                                                               int keep_holders, const int *nb_cnt, const int *nb_col,
                                                               const long long *hptr, const int *huser, int n_resident,
                                                               const long long *new_ptr, const int *new_user, int *cand_cnt,
-                                                              const long long *cand_ptr, int *cand_user, int *cand_item) {
+                                                              const long long *cand_ptr, int *cand_user, int *cand_item,
+                                                              const unsigned int *allow, const long long *ex_ptr, const int *ex_id,
+                                                              unsigned long long *removed) {
     extern __shared__ unsigned int au_lds[];    // [AU_WORDS] bitmap of the window, [AU_SUMMARY] touched words (zero between queries),
     unsigned int *bits = au_lds, *summ = au_lds + AU_WORDS;                                      // [AU_THREADS / 64] scan scratch
     int *s_scan = (int *)(au_lds + AU_WORDS + AU_SUMMARY);
     const int tid = threadIdx.x;
     for (int k = tid; k < AU_WORDS + AU_SUMMARY; k += AU_THREADS) au_lds[k] = 0u;
     __syncthreads();
+    [[maybe_unused]] unsigned int gone = 0;     // FILT, count pass: candidates of this thread's words and ids that the rules removed
     for (long long q = blockIdx.x; q < n_query; q += gridDim.x) {
         const int it = query_item[q];
         int cnt = (it >= 0 && it < I) ? nb_cnt[it] : 0;
@@ -123,13 +133,28 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
                 }
                 __syncthreads();
             }
+            if constexpr (FILT) {               // the query's exclusions: a bit that was still set is a candidate removed, once
+                if (ex_ptr) {
+                    const long long e1 = ex_ptr[q + 1];
+                    for (long long e = ex_ptr[q] + tid; e < e1; e += AU_THREADS) {
+                        const long long id = ex_id[e], x = id - lo;
+                        if (id < 0 || id >= U || x < 0 || x >= AU_WINDOW) continue;
+                        const unsigned int bit = 1u << (x & 31);
+                        const unsigned int old = atomicAnd(&bits[x >> 5], ~bit);
+                        if constexpr (!FILL) gone += (old & bit) ? 1u : 0u;
+                    }
+                    __syncthreads();
+                }
+            }
             // emit in ascending index: count per thread, scan over the block, write; the visited words are zeroed on the way
             int c = 0;
             unsigned int sw = summ[tid];
             while (sw) {
-                const int j = __ffs(sw) - 1;
+                const int w = tid * 32 + __ffs(sw) - 1;
                 sw &= sw - 1;
-                c += __popc(bits[tid * 32 + j]);
+                const unsigned int raw = bits[w], bw = rf_eligible<FILT>(raw, allow, (lo >> 5) + w);
+                c += __popc(bw);
+                if constexpr (FILT && !FILL) gone += __popc(raw) - __popc(bw);
             }
             int tot;
             const int ex = au_block_scan(c, &tot, s_scan);
@@ -142,6 +167,7 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
                 unsigned int bw = bits[w];
                 bits[w] = 0u;
                 if constexpr (FILL) {
+                    bw = rf_eligible<FILT>(bw, allow, (lo >> 5) + w);
                     while (bw) {
                         const int bit = __ffs(bw) - 1;
                         bw &= bw - 1;
@@ -157,6 +183,9 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
         if constexpr (!FILL) {
             if (tid == 0) cand_cnt[q] = (int)total;
         }
+    }
+    if constexpr (FILT && !FILL) {
+        if (gone) atomicAdd(removed, (unsigned long long)gone);
     }
 }
 
@@ -185,25 +214,28 @@ __device__ __forceinline__ void au_sort(unsigned long long *K, unsigned *P) {
 }
 
 // K / P [0, CAP): the best keys so far, sorted; [CAP, 2 CAP): the staged survivors of the tiles since the last sort
-template <int CAP>
+// FLOOR: a scored candidate below min_score is dropped and counted; FLOOR = false is the selection of the unfiltered call
+template <int CAP, bool FLOOR>
 __global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query, int n_top, int rank_by, const long long *cand_ptr,
                                                               const int *cand_user, const double *plain, const double *decay,
                                                               const int *status, int *out_cnt, int *out_user, double *out_plain,
                                                               double *out_decay,
-                                                              unsigned long long *stats /*[0] dropped candidates, [1] largest segment*/) {
+                                                              unsigned long long *stats /*[0] dropped candidates, [1] largest segment,
+                                                                                          [2] candidates below the floor*/,
+                                                              double min_score) {
     static_assert(CAP >= AU_SEL_THREADS && (CAP & (CAP - 1)) == 0, "the staging area takes a tile; bitonic sizes");
     __shared__ unsigned long long K[2 * CAP];
     __shared__ unsigned P[2 * CAP];
-    __shared__ int s_staged, s_dropped, s_have;
+    __shared__ int s_staged, s_dropped, s_floored, s_have;
     const int tid = threadIdx.x;
     const long long q = blockIdx.x;
     if (q >= n_query) return;
     const long long a = cand_ptr[q], b = cand_ptr[q + 1];
     const double *score = rank_by ? decay : plain;
     for (int k = tid; k < 2 * CAP; k += AU_SEL_THREADS) { K[k] = AU_NO_KEY; P[k] = AU_NO_POS; }
-    if (tid == 0) { s_staged = 0; s_dropped = 0; s_have = 0; }
+    if (tid == 0) { s_staged = 0; s_dropped = 0; s_floored = 0; s_have = 0; }
     __syncthreads();
-    int dropped = 0;
+    int dropped = 0, floored = 0;
     long long p = a;
     while (p < b) {
         const int staged = s_staged;
@@ -223,7 +255,11 @@ __global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query,
             const long long x = p + tid;
             if (x >= b) continue;
             if (status[x] != 0) { dropped++; continue; }
-            const unsigned long long xk = au_key(score[x]);
+            const double xs = score[x];
+            if constexpr (FLOOR) {
+                if (xs < min_score) { floored++; continue; }    // the floor: kept iff score >= min_score
+            }
+            const unsigned long long xk = au_key(xs);
             const unsigned xp = (unsigned)(x - a);
             if (xk < wk || (xk == wk && xp < wp)) {
                 const int at = CAP + atomicAdd(&s_staged, 1);
@@ -244,11 +280,17 @@ __global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query,
         out_decay[o] = v ? decay[a + pos] : 0.0;
     }
     if (dropped) atomicAdd(&s_dropped, dropped);
+    if constexpr (FLOOR) {
+        if (floored) atomicAdd(&s_floored, floored);
+    }
     if (have) atomicAdd(&s_have, have);
     __syncthreads();
     if (tid == 0) {
         out_cnt[q] = s_have;
         if (s_dropped) atomicAdd(&stats[0], (unsigned long long)s_dropped);
+        if constexpr (FLOOR) {
+            if (s_floored) atomicAdd(&stats[2], (unsigned long long)s_floored);
+        }
         atomicMax(&stats[1], (unsigned long long)(b - a));
     }
 }
@@ -256,22 +298,38 @@ __global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query,
 template <int CAP>
 static void au_select_launch(hipStream_t st, long long n_query, int n_top, int rank_by, const long long *cand_ptr, const int *cand_user,
                              const double *plain, const double *decay, const int *status, int *out_cnt, int *out_user,
-                             double *out_plain, double *out_decay, unsigned long long *stats) {
-    k_au_select<CAP><<<dim3((unsigned)n_query), dim3(AU_SEL_THREADS), 0, st>>>(n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay,
-                                                                               status, out_cnt, out_user, out_plain, out_decay, stats);
+                             double *out_plain, double *out_decay, unsigned long long *stats, double min_score) {
+    const bool floor = min_score > -__builtin_inf();   // no floor: the selection of the unfiltered call
+    (floor ? k_au_select<CAP, true> : k_au_select<CAP, false>)<<<dim3((unsigned)n_query), dim3(AU_SEL_THREADS), 0, st>>>(
+        n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay, status, out_cnt, out_user, out_plain, out_decay, stats, min_score);
+}
+
+// the two passes of the candidate kernel, by the rules a call carries: one statement per launch
+template <bool FILL, bool FILT, class... A>
+static void au_candidates_launch(hipStream_t st, unsigned blocks, size_t lds, A... a) {
+    k_au_candidates<FILL, FILT><<<dim3(blocks), dim3(AU_THREADS), lds, st>>>(a...);
+}
+template <bool FILL, class... A>
+static hipError_t au_candidates(bool filt, hipStream_t st, unsigned blocks, size_t lds, A... a) {
+    const void *f = filt ? (const void *)k_au_candidates<FILL, true> : (const void *)k_au_candidates<FILL, false>;
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (filt) au_candidates_launch<FILL, true>(st, blocks, lds, a...);
+    else au_candidates_launch<FILL, false>(st, blocks, lds, a...);
+    return hipGetLastError();
 }
 
 }  // namespace xmap
 using namespace xmap;
 
-// xmap_audience_rows (new_ptr == NULL) and xmap_itemfold_audience_rows: the items >= n_resident take their holders from the CSR
-// (new_ptr, new_user) -- the raters of a fold-in batch, which no profile holds
+// xmap_audience_rows (new_ptr == NULL), xmap_itemfold_audience_rows and xmap_audience_rows_filtered (n_stats = 6): the items >=
+// n_resident take their holders from the CSR (new_ptr, new_user) -- the raters of a fold-in batch, which no profile holds
 static int audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
                        int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
                        const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
                        const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
                        int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats, int32_t n_resident,
-                       const int64_t *new_ptr, const int32_t *new_user) {
+                       const int64_t *new_ptr, const int32_t *new_user, const xmap_rec_filter *F = nullptr, int n_stats = 4) {
     XM_SCOPE(stream);
     hipStream_t st = (hipStream_t)stream;
     XM_ARG(n_top >= 1 && n_top <= AU_MAX_TOP);
@@ -283,7 +341,11 @@ static int audience_rows(void *stream, int64_t n_query, const int32_t *query_ite
     XM_ARG(n_query == 0 || (query_item && out_cnt && out_user && out_plain && out_decay));
     XM_ARG(n_items == 0 || (nb_cnt && nb_col && nb_sim && item_avg));
     XM_ARG(n_users == 0 || (prof_item && prof_rating && prof_time));
-    if (h_stats) h_stats[0] = h_stats[1] = h_stats[2] = h_stats[3] = 0;
+    if (h_stats) for (int k = 0; k < n_stats; k++) h_stats[k] = 0;
+    bool filt = false;
+    double min_score = 0.0;
+    int rc = rf_prepare(st, n_query, F, &filt, &min_score);     // before any candidate work
+    if (rc) return rc;
     if (n_query == 0) return XMAP_OK;
     const int I = n_items;
     const size_t i1 = (size_t)(I ? I : 1);
@@ -299,7 +361,7 @@ static int audience_rows(void *stream, int64_t n_query, const int32_t *query_ite
                                                                        nullptr);
         XM_LAUNCH_CHECK();
     }
-    int rc = xmap_exclusive_scan_i32_to_i64(st, hcnt, (int64_t *)hptr, I, &n_hold);
+    rc = xmap_exclusive_scan_i32_to_i64(st, hcnt, (int64_t *)hptr, I, &n_hold);
     if (rc) return rc;
     XM_HIP(xm_malloc_async((void **)&huser, sizeof(int) * (size_t)(n_hold ? n_hold : 1), st));
     if (n_hold > 0) {
@@ -316,12 +378,16 @@ static int audience_rows(void *stream, int64_t n_query, const int32_t *query_ite
     const size_t lds = sizeof(unsigned int) * (AU_WORDS + AU_SUMMARY + AU_THREADS / 64);
     const unsigned cblocks = (unsigned)(n_query < AU_MAX_BLOCKS ? n_query : AU_MAX_BLOCKS);
     const int keep_holders = flags & XMAP_AUDIENCE_KEEP_HOLDERS;
-    XM_HIP(hipFuncSetAttribute((const void *)k_au_candidates<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    XM_HIP(hipFuncSetAttribute((const void *)k_au_candidates<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_au_candidates<false><<<dim3(cblocks), dim3(AU_THREADS), lds, st>>>(n_query, query_item, n_users, I, keep, keep_holders, nb_cnt, nb_col,
-                                                                         hptr, huser, n_resident, (const long long *)new_ptr, new_user, cand_cnt, nullptr,
-                                                                         nullptr, nullptr);
-    XM_LAUNCH_CHECK();
+    // [0] dropped candidates, [1] largest segment, [2] below the floor, [3] removed by the mask or the exclusion lists
+    unsigned long long *stats = nullptr;
+    XM_HIP(xm_malloc_async((void **)&stats, sizeof(unsigned long long) * 4, st));
+    XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 4, st));
+    const unsigned int *allow = filt ? (const unsigned int *)F->allow : nullptr;
+    const long long *ex_ptr = filt ? (const long long *)F->ex_ptr : nullptr;
+    const int *ex_id = filt ? F->ex_id : nullptr;
+    XM_HIP(au_candidates<false>(filt, st, cblocks, lds, (long long)n_query, query_item, (long long)n_users, I, keep, keep_holders, nb_cnt, nb_col,
+                                (const long long *)hptr, (const int *)huser, n_resident, (const long long *)new_ptr, new_user, cand_cnt,
+                                (const long long *)nullptr, (int *)nullptr, (int *)nullptr, allow, ex_ptr, ex_id, stats + 3));
     rc = xmap_exclusive_scan_i32_to_i64(st, cand_cnt, (int64_t *)cand_ptr, n_query, &n_pairs);
     if (rc) return rc;
     double *plain = nullptr, *decay = nullptr;
@@ -334,30 +400,30 @@ static int audience_rows(void *stream, int64_t n_query, const int32_t *query_ite
         XM_HIP(xm_malloc_async((void **)&plain, sizeof(double) * np, st));
         XM_HIP(xm_malloc_async((void **)&decay, sizeof(double) * np, st));
         XM_HIP(xm_malloc_async((void **)&status, sizeof(int) * np, st));
-        k_au_candidates<true><<<dim3(cblocks), dim3(AU_THREADS), lds, st>>>(n_query, query_item, n_users, I, keep, keep_holders, nb_cnt,
-                                                                            nb_col, hptr, huser, n_resident, (const long long *)new_ptr, new_user, nullptr,
-                                                                            cand_ptr, cand_user, cand_item);
-        XM_LAUNCH_CHECK();
+        XM_HIP(au_candidates<true>(filt, st, cblocks, lds, (long long)n_query, query_item, (long long)n_users, I, keep, keep_holders, nb_cnt,
+                                   nb_col, (const long long *)hptr, (const int *)huser, n_resident, (const long long *)new_ptr, new_user,
+                                   (int *)nullptr, (const long long *)cand_ptr, cand_user, cand_item, allow, ex_ptr, ex_id,
+                                   (unsigned long long *)nullptr));
         // ---- scores: the pair body of the prediction, unrounded
         rc = predict_rows_run<true>(st, n_pairs, cand_user, cand_item, n_users, I, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
                                     prof_rating, prof_time, item_avg, wtab, n_w, plain, decay, status, &max_now);
         if (rc) return rc;
     }
-    // ---- selection
-    unsigned long long *stats = nullptr;
-    XM_HIP(xm_malloc_async((void **)&stats, sizeof(unsigned long long) * 2, st));
-    XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 2, st));
+    // ---- selection (n_pairs == 0: every segment is empty, the counts and the padding are still written)
     if (n_top <= 256)
         au_select_launch<256>(st, n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay, status, out_cnt, out_user, out_plain, out_decay,
-                              stats);
+                              stats, min_score);
     else
         au_select_launch<1024>(st, n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay, status, out_cnt, out_user, out_plain,
-                               out_decay, stats);
+                               out_decay, stats, min_score);
     XM_LAUNCH_CHECK();
-    unsigned long long h[2] = {0, 0};
+    unsigned long long h[4] = {0, 0, 0, 0};
     XM_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    if (h_stats) { h_stats[0] = n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = max_now; h_stats[3] = (int64_t)h[1]; }
+    if (h_stats) {
+        h_stats[0] = n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = max_now; h_stats[3] = (int64_t)h[1];
+        if (n_stats == 6) { h_stats[4] = (int64_t)h[2]; h_stats[5] = (int64_t)h[3]; }
+    }
     return XMAP_OK;
 }
 
@@ -383,5 +449,18 @@ int xmap_itemfold_audience_rows(void *stream, int64_t n_query, const int32_t *qu
     return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
                          prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_user, out_plain, out_decay, h_stats, n_resident,
                          new_ptr, new_user);
+}
+
+int xmap_audience_rows_filtered(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
+                                int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                                const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                                const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                                int32_t *out_user, double *out_plain, double *out_decay, int32_t n_resident, const int64_t *new_ptr,
+                                const int32_t *new_user, const xmap_rec_filter *F, int64_t *h_stats) {
+    if (!new_ptr) n_resident = n_items;         // resident items only
+    XM_ARG(n_resident >= 0 && n_resident <= n_items);
+    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
+                         prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_user, out_plain, out_decay, h_stats, n_resident,
+                         new_ptr, new_user, F, 6);
 }
 }

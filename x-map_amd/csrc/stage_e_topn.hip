@@ -17,13 +17,18 @@
 //   k_tn_select     : segmented top-N, one wave per query: lane j holds the j-th best (score desc, item asc) seen so far; the
 //                     segment streams through 64 candidates at a time, a candidate that beats the current N-th is inserted by
 //                     a ballot count and a one-lane shift.  Candidates with status 2 are dropped and counted.
+// xmap_topn_rows_filtered (rec_filter.h; DESIGN.md 4 "Eligibility"): the FILT instantiation of k_tn_candidates clears the query's
+// exclusion ids in the bitmap and ANDs every emitted word with the item mask -- before anything is scored -- and k_tn_select
+// drops and counts the candidates below the score floor.
 // Every output position follows from the scans, so the result does not depend on the grid or on the order of the atomics.
 #include "common.h"
 #include "predict_rows.h"
+#include "rec_filter.h"
 
 namespace xmap {
 
 constexpr int TN_WINDOW = 1 << 19;              // items per bitmap pass (64 KB of LDS; two blocks per CU)
+static_assert(TN_WINDOW % 32 == 0, "a window starts at a word of the mask");
 constexpr int TN_WORDS = TN_WINDOW / 32;
 constexpr int TN_SUMMARY = TN_WORDS / 32;       // second level: bit w of word s = bitmap word 32 s + w was touched
 constexpr int TN_THREADS = 256;
@@ -68,17 +73,21 @@ __device__ __forceinline__ int tn_block_scan(int v, int *total, int *smem) {
     return base + inc - v;
 }
 
-template <bool FILL>
+// FILT (rec_filter.h): the query's exclusion ids are cleared behind the held items, and a touched word meets its word of the
+// mask where it is emitted; the count pass adds what the two removed to *removed.  FILT = false is the unfiltered kernel.
+template <bool FILL, bool FILT>
 __global__ __launch_bounds__(TN_THREADS) void k_tn_candidates(long long n_query, const int *query_user, long long U, int I, int keep_held,
                                                               const long long *rptr, const int *ritem, const long long *pptr,
                                                               const int *pitem, int *cand_cnt, const long long *cand_ptr,
-                                                              int *cand_user, int *cand_item) {
+                                                              int *cand_user, int *cand_item, const unsigned int *allow,
+                                                              const long long *ex_ptr, const int *ex_id, unsigned long long *removed) {
     extern __shared__ unsigned int tn_lds[];    // [TN_WORDS] bitmap of the window, [TN_SUMMARY] touched words (zero between users),
     unsigned int *bits = tn_lds, *summ = tn_lds + TN_WORDS;                                      // [TN_THREADS / 64] scan scratch
     int *s_scan = (int *)(tn_lds + TN_WORDS + TN_SUMMARY);
     const int tid = threadIdx.x;
     for (int k = tid; k < TN_WORDS + TN_SUMMARY; k += TN_THREADS) tn_lds[k] = 0u;
     __syncthreads();
+    [[maybe_unused]] unsigned int gone = 0;     // FILT, count pass: candidates of this thread's words and ids that the rules removed
     for (long long q = blockIdx.x; q < n_query; q += gridDim.x) {
         const int u = query_user[q];
         long long a = 0, b = 0;
@@ -107,15 +116,30 @@ __global__ __launch_bounds__(TN_THREADS) void k_tn_candidates(long long n_query,
                 }
                 __syncthreads();
             }
+            if constexpr (FILT) {               // the query's exclusions: a bit that was still set is a candidate removed, once
+                if (ex_ptr) {
+                    const long long e1 = ex_ptr[q + 1];
+                    for (long long e = ex_ptr[q] + tid; e < e1; e += TN_THREADS) {
+                        const long long id = ex_id[e], x = id - lo;
+                        if (id < 0 || id >= I || x < 0 || x >= TN_WINDOW) continue;
+                        const unsigned int bit = 1u << (x & 31);
+                        const unsigned int old = atomicAnd(&bits[x >> 5], ~bit);
+                        if constexpr (!FILL) gone += (old & bit) ? 1u : 0u;
+                    }
+                    __syncthreads();
+                }
+            }
             // emit in ascending index: count per thread, scan over the block, write; the visited words are zeroed on the way
             int c = 0;
 #pragma unroll
             for (int k = 0; k < TN_PER; k++) {
                 unsigned int sw = summ[tid * TN_PER + k];
                 while (sw) {
-                    const int j = __ffs(sw) - 1;
+                    const int w = (tid * TN_PER + k) * 32 + __ffs(sw) - 1;
                     sw &= sw - 1;
-                    c += __popc(bits[(tid * TN_PER + k) * 32 + j]);
+                    const unsigned int raw = bits[w], bw = rf_eligible<FILT>(raw, allow, (lo >> 5) + w);
+                    c += __popc(bw);
+                    if constexpr (FILT && !FILL) gone += __popc(raw) - __popc(bw);
                 }
             }
             int tot;
@@ -133,6 +157,7 @@ __global__ __launch_bounds__(TN_THREADS) void k_tn_candidates(long long n_query,
                     unsigned int bw = bits[w];
                     bits[w] = 0u;
                     if constexpr (FILL) {
+                        bw = rf_eligible<FILT>(bw, allow, (lo >> 5) + w);
                         while (bw) {
                             const int bit = __ffs(bw) - 1;
                             bw &= bw - 1;
@@ -150,26 +175,38 @@ __global__ __launch_bounds__(TN_THREADS) void k_tn_candidates(long long n_query,
             if (tid == 0) cand_cnt[q] = (int)total;
         }
     }
+    if constexpr (FILT && !FILL) {
+        if (gone) atomicAdd(removed, (unsigned long long)gone);
+    }
 }
 
-// lane j < have holds the j-th best candidate so far; keys are distinct (a segment holds an item once)
+// lane j < have holds the j-th best candidate so far; keys are distinct (a segment holds an item once).  FLOOR: a scored candidate
+// below min_score is dropped and counted; FLOOR = false is the selection of the unfiltered call (min_score is not read)
+template <bool FLOOR>
 __global__ __launch_bounds__(256) void k_tn_select(long long n_query, int n_top, int rank_by, const long long *cand_ptr, const int *cand_item,
                                                    const double *plain, const double *decay, const int *status, int *out_cnt,
                                                    int *out_item, double *out_plain, double *out_decay,
-                                                   unsigned long long *stats /*[0] dropped candidates, [1] largest segment*/) {
+                                                   unsigned long long *stats /*[0] dropped candidates, [1] largest segment,
+                                                                               [2] candidates below the floor*/,
+                                                   double min_score) {
     const int lane = lane_id();
     const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= n_query) return;
     const long long a = cand_ptr[q], b = cand_ptr[q + 1];
     double ks = 0.0, kp = 0.0, kd = 0.0;
-    int ki = -1, have = 0, dropped = 0;
+    int ki = -1, have = 0, dropped = 0, floored = 0;
     for (long long p = a; p < b; p += 64) {
         const bool in = p + lane < b;
-        const bool ok = in && status[p + lane] == 0;
-        dropped += __popcll(__ballot(in && !ok));
-        const int xi = ok ? cand_item[p + lane] : 0;
-        const double xp = ok ? plain[p + lane] : 0.0, xd = ok ? decay[p + lane] : 0.0;
+        const bool scored = in && status[p + lane] == 0;
+        dropped += __popcll(__ballot(in && !scored));
+        const int xi = scored ? cand_item[p + lane] : 0;
+        const double xp = scored ? plain[p + lane] : 0.0, xd = scored ? decay[p + lane] : 0.0;
         const double xs = rank_by ? xd : xp;
+        bool ok = scored;
+        if constexpr (FLOOR) {                          // the floor: kept iff score >= min_score
+            ok = scored && !(xs < min_score);
+            floored += __popcll(__ballot(scored && !ok));
+        }
         const double ws = rld(ks, n_top - 1);
         const int wi = rl32(ki, n_top - 1);
         unsigned long long m = __ballot(ok && (have < n_top || xs > ws || (xs == ws && xi < wi)));
@@ -197,20 +234,37 @@ __global__ __launch_bounds__(256) void k_tn_select(long long n_query, int n_top,
     if (lane == 0) {
         out_cnt[q] = have;
         if (dropped) atomicAdd(&stats[0], (unsigned long long)dropped);
+        if constexpr (FLOOR) {
+            if (floored) atomicAdd(&stats[2], (unsigned long long)floored);
+        }
         atomicMax(&stats[1], (unsigned long long)(b - a));
     }
+}
+
+// the two passes of the candidate kernel and the selection, by the rules a call carries: one statement per launch
+template <bool FILL, bool FILT, class... A>
+static void tn_candidates_launch(hipStream_t st, unsigned blocks, size_t lds, A... a) {
+    k_tn_candidates<FILL, FILT><<<dim3(blocks), dim3(TN_THREADS), lds, st>>>(a...);
+}
+template <bool FILL, class... A>
+static hipError_t tn_candidates(bool filt, hipStream_t st, unsigned blocks, size_t lds, A... a) {
+    const void *f = filt ? (const void *)k_tn_candidates<FILL, true> : (const void *)k_tn_candidates<FILL, false>;
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (filt) tn_candidates_launch<FILL, true>(st, blocks, lds, a...);
+    else tn_candidates_launch<FILL, false>(st, blocks, lds, a...);
+    return hipGetLastError();
 }
 
 }  // namespace xmap
 using namespace xmap;
 
-extern "C" {
-
-int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
-                   int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
-                   const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
-                   const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
-                   int32_t *out_item, double *out_plain, double *out_decay, int64_t *h_stats) {
+// xmap_topn_rows (F == NULL, n_stats = 4) and xmap_topn_rows_filtered (n_stats = 6)
+static int topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                     int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                     const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                     const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                     int32_t *out_item, double *out_plain, double *out_decay, const xmap_rec_filter *F, int64_t *h_stats, int n_stats) {
     XM_SCOPE(stream);
     hipStream_t st = (hipStream_t)stream;
     XM_ARG(n_top >= 1 && n_top <= TN_MAX_TOP);
@@ -221,7 +275,11 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
     XM_ARG(n_query == 0 || (query_user && out_cnt && out_item && out_plain && out_decay));
     XM_ARG(n_items == 0 || (nb_cnt && nb_col && nb_sim && item_avg));
     XM_ARG(n_users == 0 || (prof_item && prof_rating && prof_time));
-    if (h_stats) h_stats[0] = h_stats[1] = h_stats[2] = h_stats[3] = 0;
+    if (h_stats) for (int k = 0; k < n_stats; k++) h_stats[k] = 0;
+    bool filt = false;
+    double min_score = 0.0;
+    int rc = rf_prepare(st, n_query, F, &filt, &min_score);     // before any candidate work
+    if (rc) return rc;
     if (n_query == 0) return XMAP_OK;
     const int I = n_items;
     const size_t i1 = (size_t)(I ? I : 1);
@@ -237,7 +295,7 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
         k_tn_rev<false><<<dim3(rev_blocks), dim3(256), 0, st>>>(I, keep, nb_cnt, nb_col, rcnt, nullptr, nullptr);
         XM_LAUNCH_CHECK();
     }
-    int rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rptr, I, &n_rev);
+    rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rptr, I, &n_rev);
     if (rc) return rc;
     XM_HIP(xm_malloc_async((void **)&ritem, sizeof(int) * (size_t)(n_rev ? n_rev : 1), st));
     if (n_rev > 0) {
@@ -253,12 +311,16 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
     XM_HIP(xm_malloc_async((void **)&cand_ptr, sizeof(long long) * ((size_t)n_query + 1), st));
     const size_t lds = sizeof(unsigned int) * (TN_WORDS + TN_SUMMARY + TN_THREADS / 64);
     const unsigned cblocks = (unsigned)(n_query < TN_MAX_BLOCKS ? n_query : TN_MAX_BLOCKS);
-    XM_HIP(hipFuncSetAttribute((const void *)k_tn_candidates<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    XM_HIP(hipFuncSetAttribute((const void *)k_tn_candidates<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_tn_candidates<false><<<dim3(cblocks), dim3(TN_THREADS), lds, st>>>(n_query, query_user, n_users, I, flags & XMAP_TOPN_KEEP_HELD, rptr,
-                                                                         ritem, (const long long *)prof_ptr, prof_item, cand_cnt, nullptr,
-                                                                         nullptr, nullptr);
-    XM_LAUNCH_CHECK();
+    // [0] dropped candidates, [1] largest segment, [2] below the floor, [3] removed by the mask or the exclusion lists
+    unsigned long long *stats = nullptr;
+    XM_HIP(xm_malloc_async((void **)&stats, sizeof(unsigned long long) * 4, st));
+    XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 4, st));
+    const unsigned int *allow = filt ? (const unsigned int *)F->allow : nullptr;
+    const long long *ex_ptr = filt ? (const long long *)F->ex_ptr : nullptr;
+    const int *ex_id = filt ? F->ex_id : nullptr;
+    XM_HIP(tn_candidates<false>(filt, st, cblocks, lds, (long long)n_query, query_user, (long long)n_users, I, flags & XMAP_TOPN_KEEP_HELD,
+                                (const long long *)rptr, (const int *)ritem, (const long long *)prof_ptr, prof_item, cand_cnt,
+                                (const long long *)nullptr, (int *)nullptr, (int *)nullptr, allow, ex_ptr, ex_id, stats + 3));
     rc = xmap_exclusive_scan_i32_to_i64(st, cand_cnt, (int64_t *)cand_ptr, n_query, &n_pairs);
     if (rc) return rc;
     double *plain = nullptr, *decay = nullptr;
@@ -271,26 +333,46 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
         XM_HIP(xm_malloc_async((void **)&plain, sizeof(double) * np, st));
         XM_HIP(xm_malloc_async((void **)&decay, sizeof(double) * np, st));
         XM_HIP(xm_malloc_async((void **)&status, sizeof(int) * np, st));
-        k_tn_candidates<true><<<dim3(cblocks), dim3(TN_THREADS), lds, st>>>(n_query, query_user, n_users, I, flags & XMAP_TOPN_KEEP_HELD, rptr,
-                                                                            ritem, (const long long *)prof_ptr, prof_item, nullptr, cand_ptr,
-                                                                            cand_user, cand_item);
-        XM_LAUNCH_CHECK();
+        XM_HIP(tn_candidates<true>(filt, st, cblocks, lds, (long long)n_query, query_user, (long long)n_users, I, flags & XMAP_TOPN_KEEP_HELD,
+                                   (const long long *)rptr, (const int *)ritem, (const long long *)prof_ptr, prof_item, (int *)nullptr,
+                                   (const long long *)cand_ptr, cand_user, cand_item, allow, ex_ptr, ex_id, (unsigned long long *)nullptr));
         // ---- scores: the pair body of the prediction, unrounded
         rc = predict_rows_run<true>(st, n_pairs, cand_user, cand_item, n_users, I, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
                                     prof_rating, prof_time, item_avg, wtab, n_w, plain, decay, status, &max_now);
         if (rc) return rc;
     }
-    // ---- selection
-    unsigned long long *stats = nullptr;
-    XM_HIP(xm_malloc_async((void **)&stats, sizeof(unsigned long long) * 2, st));
-    XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 2, st));
-    k_tn_select<<<dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st>>>(n_query, n_top, rank_by, cand_ptr, cand_item, plain, decay, status,
-                                                                           out_cnt, out_item, out_plain, out_decay, stats);
+    // ---- selection (n_pairs == 0: every segment is empty, the counts and the padding are still written)
+    const bool floor = min_score > -__builtin_inf();   // no floor: the selection of the unfiltered call
+    (floor ? k_tn_select<true> : k_tn_select<false>)<<<dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st>>>(
+        n_query, n_top, rank_by, cand_ptr, cand_item, plain, decay, status, out_cnt, out_item, out_plain, out_decay, stats, min_score);
     XM_LAUNCH_CHECK();
-    unsigned long long h[2] = {0, 0};
+    unsigned long long h[4] = {0, 0, 0, 0};
     XM_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    if (h_stats) { h_stats[0] = n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = max_now; h_stats[3] = (int64_t)h[1]; }
+    if (h_stats) {
+        h_stats[0] = n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = max_now; h_stats[3] = (int64_t)h[1];
+        if (n_stats == 6) { h_stats[4] = (int64_t)h[2]; h_stats[5] = (int64_t)h[3]; }
+    }
     return XMAP_OK;
+}
+
+extern "C" {
+
+int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                   int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                   const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                   const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                   int32_t *out_item, double *out_plain, double *out_decay, int64_t *h_stats) {
+    return topn_rows(stream, n_query, query_user, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
+                     prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_item, out_plain, out_decay, nullptr, h_stats, 4);
+}
+
+int xmap_topn_rows_filtered(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                            int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                            const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                            const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                            int32_t *out_item, double *out_plain, double *out_decay, const xmap_rec_filter *F, int64_t *h_stats) {
+    return topn_rows(stream, n_query, query_user, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
+                     prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_item, out_plain, out_decay, F, h_stats, 6);
 }
 }

@@ -1664,7 +1664,36 @@ class Engine(object):
                                         vp(plain), vp(decay), vp(status), C.byref(h)))
         return plain[:T], decay[:T], status[:T], int(h.value)
 
-    def topn(self, P, neighbors, query_user, item_avg, wtab, n_top, rank_by=0, keep_held=False, n_items=None):
+    def _rec_filter(self, n, n_query, allow, exclude, min_score):
+        """the xmap_rec_filter of topn() / audience() over an id space of n ids + the tensors it points into (kept by the caller
+        for the call).  allow: a bool tensor [n] (packed here, on the device) or the packed words [(n + 31) // 32] (int32 /
+        uint32, filters.pack_mask); exclude: (ptr int64 [Q + 1], ids int32), filters.exclusion_csr; all on the device."""
+        words = ptr = ids = None
+        if allow is not None:
+            n_words = (int(n) + 31) // 32
+            if allow.dtype == torch.bool:
+                if tuple(allow.shape) != (int(n),):
+                    raise ValueError("allow: a bool mask of %d ids, not %s" % (n, tuple(allow.shape)))
+                bits = torch.zeros(n_words * 32, dtype=torch.int64, device=self.dev)
+                bits[:int(n)] = allow.to(self.dev)
+                w = (bits.view(n_words, 32) << torch.arange(32, dtype=torch.int64, device=self.dev)).sum(dim=1)
+                words = (w - ((w >> 31) << 32)).to(torch.int32)
+            else:
+                words = allow.contiguous()
+                if words.element_size() != 4 or words.dtype.is_floating_point or int(words.numel()) != n_words:
+                    raise ValueError("allow: %d packed 32-bit words for %d ids, not %s %s" % (n_words, n, words.dtype, tuple(words.shape)))
+            words = words if words.numel() else torch.zeros(1, dtype=torch.int32, device=self.dev)
+        if exclude is not None:
+            ptr, ids = exclude[0].contiguous(), exclude[1].contiguous()
+            if ptr.dtype != torch.int64 or ids.dtype != torch.int32 or int(ptr.numel()) != int(n_query) + 1:
+                raise ValueError("exclude = (ptr int64 [%d], ids int32): one list per query" % (int(n_query) + 1))
+            ids = ids if ids.numel() else torch.zeros(1, dtype=torch.int32, device=self.dev)
+        if min_score is not None and min_score != min_score:
+            raise ValueError("min_score is NaN")
+        return abi.rec_filter(words, ptr, ids, min_score), (words, ptr, ids)
+
+    def topn(self, P, neighbors, query_user, item_avg, wtab, n_top, rank_by=0, keep_held=False, n_items=None, allow=None,
+             exclude=None, min_score=None):
         """Top-N recommendation on the device (xmap_topn_rows) over the profiles P of alterego_profiles: per query user the
         n_top (1..64) best items its own rows give evidence for, by the unrounded prediction (rank_by 0: plain, 1: decayed;
         score descending, item index ascending); items the user holds are left out unless keep_held.  neighbors, item_avg,
@@ -1672,7 +1701,11 @@ class Engine(object):
         items).  Returns (cnt [Q], item [Q][n_top] (-1 behind the count), plain, decayed [Q][n_top], stats) with stats =
         (candidates scored, candidates dropped, largest `now`, largest candidate count of a query): candidates were dropped
         for a short table when stats[2] > len(wtab).  n_items: as predict() takes it (the extended tables of an item fold-in; a
-        batch item is listed as I + q, also for its own raters: the frozen profiles do not hold it)."""
+        batch item is listed as I + q, also for its own raters: the frozen profiles do not hold it).
+        Eligibility (xmap_topn_rows_filtered; the rules act before scoring, so the n_top best ELIGIBLE items are selected):
+        allow = the items that may be returned (bool tensor [items] or packed words), exclude = (ptr, ids) of items never returned
+        per QUERY, min_score = floor on the rank_by score.  With any of the three the stats are 6: the four above over the
+        eligible candidates, candidates below the floor, candidate pairs the mask or the lists removed."""
         st = _stream(self.dev)
         cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
         Q, n_top = int(query_user.numel()), int(n_top)
@@ -1683,6 +1716,18 @@ class Engine(object):
         out_item = self._empty((max(Q, 1), n_top), torch.int32)
         out_plain = self._empty((max(Q, 1), n_top), torch.float64)
         out_decay = self._empty((max(Q, 1), n_top), torch.float64)
+        if allow is not None or exclude is not None or min_score is not None:
+            F, alive = self._rec_filter(P.n_items if n_items is None else n_items, Q, allow, exclude, min_score)
+            h = (C.c_int64 * 6)()
+            with self.timed("topn"):
+                check(lib.xmap_topn_rows_filtered(st, i64(Q), vp(query_user.contiguous()), i32(n_top), i32(rank_by),
+                                                  i32(abi.TOPN_KEEP_HELD if keep_held else 0), i64(P.n_users),
+                                                  i32(P.n_items if n_items is None else n_items), i32(keep), vp(cnt), vp(col), vp(sim),
+                                                  vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(P.user_time),
+                                                  vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()), vp(out_cnt), vp(out_item),
+                                                  vp(out_plain), vp(out_decay), C.byref(F), h))
+            del alive
+            return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
         h = (C.c_int64 * 4)(0, 0, 0, 0)
         with self.timed("topn"):
             check(lib.xmap_topn_rows(st, i64(Q), vp(query_user.contiguous()), i32(n_top), i32(rank_by), i32(abi.TOPN_KEEP_HELD if keep_held else 0),
@@ -1691,7 +1736,8 @@ class Engine(object):
                                      vp(wtab), i32(wtab.numel()), vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
         return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
 
-    def audience(self, P, neighbors, query_item, item_avg, wtab, n_top, rank_by=0, keep_holders=False, batch=None):
+    def audience(self, P, neighbors, query_item, item_avg, wtab, n_top, rank_by=0, keep_holders=False, batch=None, allow=None,
+                 exclude=None, min_score=None):
         """The audience of an item on the device (xmap_audience_rows) over the profiles P of alterego_profiles: per query
         item the n_top (1..1024) best users among those whose own rows give evidence for it, by the unrounded prediction
         (rank_by 0: plain, 1: decayed; score descending, user index ascending); users who hold the item are left out unless
@@ -1700,7 +1746,9 @@ class Engine(object):
         list: no users).  Returns (cnt [Q], user [Q][n_top] (-1 behind the count), plain, decayed [Q][n_top], stats) with stats
         as topn() returns them.  batch = (ptr, user) of an item fold-in (item_foldin's rows.ptr / rows.user, device tensors):
         neighbors and item_avg are then the extended tables of item_foldin_tables, query items I + q are the batch's, and their
-        raters are their holders (xmap_itemfold_audience_rows)."""
+        raters are their holders (xmap_itemfold_audience_rows).
+        Eligibility (xmap_audience_rows_filtered), as topn() takes it with users for items: allow = the users who may be returned,
+        exclude = (ptr, ids) of users never returned per QUERY, min_score = floor on the rank_by score; then 6 stats."""
         st = _stream(self.dev)
         cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
         Q, n_top = int(query_item.numel()), int(n_top)
@@ -1712,12 +1760,27 @@ class Engine(object):
         out_plain = self._empty((max(Q, 1), n_top), torch.float64)
         out_decay = self._empty((max(Q, 1), n_top), torch.float64)
         h = (C.c_int64 * 4)(0, 0, 0, 0)
+        b_ptr = b_user = None
+        n_all = n_res = int(P.n_items)
         if batch is not None:
             b_ptr, b_user = batch[0].contiguous(), batch[1].contiguous()
             n_all = int(cnt.numel())
             n_res = n_all - (int(b_ptr.numel()) - 1)
             if n_res < 0 or b_ptr.dtype != torch.int64 or b_user.dtype != torch.int32:
                 raise ValueError("audience: batch = (ptr int64 [B + 1], user int32) of at most as many items as the tables hold")
+        if allow is not None or exclude is not None or min_score is not None:
+            F, alive = self._rec_filter(P.n_users, Q, allow, exclude, min_score)
+            h = (C.c_int64 * 6)()
+            with self.timed("audience"):
+                check(lib.xmap_audience_rows_filtered(st, i64(Q), vp(query_item.contiguous()), i32(n_top), i32(rank_by),
+                                                      i32(abi.AUDIENCE_KEEP_HOLDERS if keep_holders else 0), i64(P.n_users), i32(n_all),
+                                                      i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
+                                                      vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab),
+                                                      i32(wtab.numel()), vp(out_cnt), vp(out_user), vp(out_plain), vp(out_decay),
+                                                      i32(n_res), vp(b_ptr), vp(b_user), C.byref(F), h))
+            del alive
+            return out_cnt[:Q], out_user[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
+        if batch is not None:
             with self.timed("audience"):
                 check(lib.xmap_itemfold_audience_rows(st, i64(Q), vp(query_item.contiguous()), i32(n_top), i32(rank_by),
                                                       i32(abi.AUDIENCE_KEEP_HOLDERS if keep_holders else 0), i64(P.n_users), i32(n_all),

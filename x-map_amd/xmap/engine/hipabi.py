@@ -20,6 +20,7 @@ MID_ROWS_SPAN = 36864     # XMAP_MID_ROWS_SPAN: columns of a middle-list row per
 ERR_HIP, ERR_ARG, ERR_OVERFLOW, ERR_CAPACITY = -1, -2, -3, -4     # XMAP_ERR_* of include/xmap_hip.h
 TOPN_KEEP_HELD = 1        # XMAP_TOPN_KEEP_HELD: flag of xmap_topn_rows / xmap_ctx_recommend
 AUDIENCE_KEEP_HOLDERS = 1 # XMAP_AUDIENCE_KEEP_HOLDERS: flag of xmap_audience_rows / xmap_ctx_audience
+SRC_RESIDENT, SRC_FOLDIN, SRC_ITEM_FOLDIN = 0, 1, 2      # XMAP_SRC_*: source of xmap_ctx_recommend_filtered / xmap_ctx_audience_filtered
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
 EXPLAIN_MAX_EV, EXPLAIN_MAX_SRC = 16, 8      # evidence entries per pair / source positions per entry of xmap_explain_*
@@ -87,6 +88,12 @@ class PathOut(C.Structure):
                 ("xs_off", C.c_void_p), ("xs_end", C.c_void_p), ("xs_val", C.c_void_p)]
 
 
+class RecFilter(C.Structure):
+    """xmap_rec_filter: the eligibility rules of a filtered top-N / audience call (device pointers for the fine-grained calls,
+    host pointers for the coarse ones); rec_filter() fills one"""
+    _fields_ = [("allow", C.c_void_p), ("ex_ptr", C.c_void_p), ("ex_id", C.c_void_p), ("min_score", C.c_double)]
+
+
 EXPORTS = [
     "xmap_last_error", "xmap_version", "xmap_trim", "xmap_debug_arena", "xmap_debug_arena_call", "xmap_exclusive_scan_i64", "xmap_exclusive_scan_i32_to_i64",
     "xmap_build_csc", "xmap_user_stats", "xmap_item_stats", 
@@ -104,6 +111,7 @@ EXPORTS = [
     "xmap_ctx_explain", "xmap_ctx_foldin_explain", "xmap_ctx_audience", "xmap_ctx_foldin_audience",
     "xmap_itemfold_count", "xmap_itemfold_fill", "xmap_itemfold_audience_rows", "xmap_ctx_item_foldin", "xmap_ctx_item_foldin_download",
     "xmap_ctx_item_foldin_audience", "xmap_ctx_item_foldin_predict", "xmap_ctx_item_foldin_recommend",
+    "xmap_topn_rows_filtered", "xmap_audience_rows_filtered", "xmap_ctx_recommend_filtered", "xmap_ctx_audience_filtered",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -220,6 +228,13 @@ def vp(t):
     if t is None:
         return C.c_void_p(0)
     return C.c_void_p(t.data_ptr())
+
+
+def rec_filter(allow=None, ex_ptr=None, ex_id=None, min_score=None):
+    """an xmap_rec_filter over torch tensors (device, for the fine-grained calls) or None; min_score None = no floor.  The
+    caller keeps the tensors alive for the call."""
+    return RecFilter(None if allow is None else allow.data_ptr(), None if ex_ptr is None else ex_ptr.data_ptr(),
+                     None if ex_id is None else ex_id.data_ptr(), float("-inf") if min_score is None else float(min_score))
 
 
 def i64(v):

@@ -470,7 +470,29 @@ def _predict_records(st, eng2, P, nb, item_avg, uidx, testRDD, alpha, iidx=None,
     return res
 
 
-def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None):
+def _eligibility(dev, labels, index, n_ids, allow, exclude, min_score):
+    """The eligibility rules of a top-N / audience call as the keyword arguments of Engine.topn / Engine.audience: allow = the ids
+    (id strings) that may be returned, exclude = {query label: ids never returned for it}, min_score = floor on the ranking score;
+    index = {id string: index below n_ids}, labels = the query labels in query order.  Ids the dictionary does not know are
+    ignored.  All three None: {} -- the unfiltered call."""
+    if allow is None and exclude is None and min_score is None:
+        return {}
+    import torch
+    from . import filters
+    kw = {}
+    if allow is not None:
+        ids = [index[x] for x in (allow.collect() if hasattr(allow, "collect") else allow) if x in index]
+        kw["allow"] = torch.from_numpy(filters.pack_mask(np.asarray(ids, np.int64), n_ids).view(np.int32)).to(dev)
+    if exclude is not None:
+        ptr, ids = filters.exclusion_csr([[index[x] for x in exclude.get(lab, ()) if x in index] for lab in labels])
+        kw["exclude"] = (torch.from_numpy(ptr).to(dev), torch.from_numpy(ids).to(dev))
+    if min_score is not None:
+        kw["min_score"] = float(min_score)
+    return kw
+
+
+def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None,
+                   allow_items=None, exclude=None, min_score=None):
     """Top-N recommendation on the device from an AlterEgoRDD handle: the set-up of recommend (profiles -> RecommenderSim ->
     neighbour lists, or `neighbors`), then for every uid of `users` the n (1..64) best items its own rows give evidence for,
     ranked by the unrounded prediction -- without temporal decay, or with (decay=True, alpha) -- score descending, item id
@@ -479,29 +501,35 @@ def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_he
     .sim_pairs and .item_info like recommend, and .stats = (candidates scored, candidates dropped, largest `now`, largest
     candidate count of a user).  explain = n_ev or (n_ev, n_src) (n_src defaults to 4): the result also carries .explanations
     = [(uid, [(iid, [entry*])*])*], the explanation of exactly the (user, item) pairs of the returned lists in their order,
-    entries as explain() gives them; without it the call returns what it always returned."""
+    entries as explain() gives them; without it the call returns what it always returned.
+    Eligibility (the rules act before scoring: the n best ELIGIBLE items are returned): allow_items = the iids that may be
+    returned at all (in stock, a category, the new releases), exclude = {uid: iids never returned for that user} (shown yesterday,
+    bought elsewhere), min_score = floor on the ranking score (plain, or decayed with decay=True); iids the train set does not know
+    are ignored.  With any of them .stats has six entries: the four above over the eligible candidates, the candidates below the
+    floor, the candidate pairs the rules removed before scoring."""
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn")
     idt = st.idt
     uids = list(users.collect()) if hasattr(users, "collect") else list(users)
     uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
     query = [uidx.get(uid, -1) for uid in uids]
-    res = _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, getattr(users, "ctx", None))
+    res = _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, getattr(users, "ctx", None),
+                        _eligibility(st.engine.dev, uids, idt.iidx, len(idt.iids), allow_items, exclude, min_score))
     _tail_dicts(res, st, S, nb)
     if explain is not None:
         _explain_lists(res, st, eng2, P, nb, item_avg, query, alpha, decay, explain, (st.ratings, st.times) if hasattr(st, "ratings") else None)
     return res
 
 
-def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, ctx):
+def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, ctx, rules=None):
     """what recommend_topn and recommend_topn_profiles share: the lists of the user indices `query` of P, labelled `uids` -> the
-    LocalRDD of (uid, [(iid, plain, decayed)*]) with .stats"""
+    LocalRDD of (uid, [(iid, plain, decayed)*]) with .stats; rules = _eligibility(...)"""
     import torch
     idt, dev = st.idt, st.engine.dev
     d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
     n_w = 66
     while True:
         wtab = _decay_table(alpha, n_w, dev)
-        cnt, item, plain, decayed, stats = eng2.topn(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_held)
+        cnt, item, plain, decayed, stats = eng2.topn(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_held, **(rules or {}))
         if stats[2] <= n_w:
             break
         n_w = stats[2]
@@ -634,7 +662,8 @@ def _fold_in(st, G, profiles):
     return F, index, unknown
 
 
-def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None):
+def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None,
+                            allow_items=None, exclude=None, min_score=None):
     """recommend_topn for users that are not rows of the train set -- a user who arrived after training, a trained user whose
     profile changed: `profiles` is an RDD or list of (uid, [(iid, rating, time)*]) raw profiles, source and target items mixed.
     Each gets its AlterEgo profile with the replacement map behind alterEgoRDD (fold-in: Engine.foldin_profiles) and then the
@@ -643,12 +672,14 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     rating float32 does not hold raises as the train set's does; times are any mutually comparable objects.  Returns the LocalRDD of
     recommend_topn in the order of `profiles`, with .stats, .sim_pairs, .item_info, .unknown_items and .counts = (AlterEgo rows,
     pass-through rows, profiles with a row).  explain as recommend_topn takes it: the sources are then entries of the profile
-    passed in (its iid, rating and time objects)."""
+    passed in (its iid, rating and time objects).  allow_items, exclude = {uid of a profile: iids}, min_score: the eligibility
+    rules of recommend_topn."""
     _no_fold_in(alterEgoRDD, "recommend_topn_profiles")
     st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn_profiles")
     F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
     uids = sorted(index, key=index.get)
-    res = _topn_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, n, decay, keep_held, getattr(profiles, "ctx", None))
+    res = _topn_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, n, decay, keep_held, getattr(profiles, "ctx", None),
+                        _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
     res.unknown_items, res.counts = unknown, F.counts
     _tail_dicts(res, st, S, nb)
     if explain is not None:
@@ -656,25 +687,36 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     return res
 
 
-def recommend_audience(alterEgoRDD, items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None):
+def recommend_audience(alterEgoRDD, items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None, allow_users=None,
+                       exclude=None, min_score=None):
     """The audience of an item on the device from an AlterEgoRDD handle -- recommend_topn the other way round: the set-up of
     recommend_topn, then for every iid of `items` the n (1..1024) best users among those whose own rows give evidence for it,
     ranked by the unrounded prediction -- without temporal decay, or with (decay=True, alpha) -- score descending, user INDEX
     (the order of the train set's users) ascending on equal scores; users who already hold the item are left out unless
     keep_holders (Engine.audience).  Returns a LocalRDD of (iid, [(uid, plain, decayed)*]) in the order of `items`; an iid the
     train set does not know gives (iid, []).  It carries .sim_pairs, .item_info and .stats like recommend_topn (.stats[3]: the
-    largest candidate count of an item).  The scores of a (uid, iid) pair are the bits recommend_topn gives it."""
+    largest candidate count of an item).  The scores of a (uid, iid) pair are the bits recommend_topn gives it.
+    Eligibility, as recommend_topn takes it with users for items: allow_users = the uids that may be returned at all (a segment,
+    those who did not opt out), exclude = {iid: uids never returned for that item} (already contacted), min_score = floor; uids
+    the train set does not know are ignored; .stats then has six entries.  Only eligible pairs are scored: a campaign over a 1 %
+    segment scores 1 % of the pairs."""
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_audience")
     iids = list(items.collect()) if hasattr(items, "collect") else list(items)
-    res = _audience_records(st, eng2, P, nb, item_avg, iids, st.idt.uids, alpha, n, decay, keep_holders, getattr(items, "ctx", None))
+    res = _audience_records(st, eng2, P, nb, item_avg, iids, st.idt.uids, alpha, n, decay, keep_holders, getattr(items, "ctx", None),
+                            rules=_eligibility(st.engine.dev, iids, _user_index(st.idt), len(st.idt.uids), allow_users, exclude, min_score))
     _tail_dicts(res, st, S, nb)
     return res
 
 
-def _audience_records(st, eng2, P, nb, item_avg, iids, uids, alpha, n, decay, keep_holders, ctx, iidx=None, batch=None):
+def _user_index(idt):
+    return getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+
+
+def _audience_records(st, eng2, P, nb, item_avg, iids, uids, alpha, n, decay, keep_holders, ctx, iidx=None, batch=None, rules=None):
     """what recommend_audience, recommend_audience_profiles and recommend_audience_items share: the audiences of the items
     `iids` among the users of P, labelled `uids` by index -> the LocalRDD of (iid, [(uid, plain, decayed)*]) with .stats.
-    iidx / batch: the item indices and the rater CSR of an item fold-in, whose extended tables nb and item_avg then are"""
+    iidx / batch: the item indices and the rater CSR of an item fold-in, whose extended tables nb and item_avg then are;
+    rules = _eligibility(...) over the users of P"""
     import torch
     idt, dev = st.idt, st.engine.dev
     iidx = idt.iidx if iidx is None else iidx
@@ -682,7 +724,8 @@ def _audience_records(st, eng2, P, nb, item_avg, iids, uids, alpha, n, decay, ke
     n_w = 66
     while True:
         wtab = _decay_table(alpha, n_w, dev)
-        cnt, user, plain, decayed, stats = eng2.audience(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_holders, batch=batch)
+        cnt, user, plain, decayed, stats = eng2.audience(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_holders, batch=batch,
+                                                                **(rules or {}))
         if stats[2] <= n_w:
             break
         n_w = stats[2]
@@ -693,17 +736,20 @@ def _audience_records(st, eng2, P, nb, item_avg, iids, uids, alpha, n, decay, ke
     return res
 
 
-def recommend_audience_profiles(alterEgoRDD, profiles, items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None):
+def recommend_audience_profiles(alterEgoRDD, profiles, items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None,
+                                allow_users=None, exclude=None, min_score=None):
     """recommend_audience among users that are not rows of the train set ("which of the users who arrived today"): `profiles`
     as recommend_topn_profiles takes them and folds them in; the audiences of `items` are chosen among these profiles only,
     from the model trained on alterEgoRDD's rows, which stays as it is.  Equal scores are ordered by the position in `profiles`.
-    Returns the LocalRDD of recommend_audience with .unknown_items and .counts as recommend_topn_profiles."""
+    Returns the LocalRDD of recommend_audience with .unknown_items and .counts as recommend_topn_profiles.  allow_users (uids of
+    `profiles`), exclude = {iid: uids}, min_score: the eligibility rules of recommend_audience."""
     _no_fold_in(alterEgoRDD, "recommend_audience_profiles")
     st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_audience_profiles")
     F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
     iids = list(items.collect()) if hasattr(items, "collect") else list(items)
     res = _audience_records(st, eng2, F, nb, item_avg, iids, sorted(index, key=index.get), alpha, n, decay, keep_holders,
-                            getattr(items, "ctx", None))
+                            getattr(items, "ctx", None),
+                            rules=_eligibility(st.engine.dev, iids, index, len(index), allow_users, exclude, min_score))
     res.unknown_items, res.counts = unknown, F.counts
     _tail_dicts(res, st, S, nb)
     return res
@@ -748,7 +794,8 @@ def _item_dicts(res, st, rows, x_nb, index):
     res.new_item_info = {iid: (float(avg[q]), float(norm[q]), int(n[q])) for iid, q in index.items()}
 
 
-def recommend_audience_items(alterEgoRDD, new_items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None):
+def recommend_audience_items(alterEgoRDD, new_items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None,
+                             allow_users=None, exclude=None, min_score=None):
     """recommend_audience for items that are not items of the train set -- a book that enters the catalogue: `new_items` is an
     RDD or list of (iid, [(uid, rating)*]), the ratings the item has collected so far from users of the train set.  Each item
     gets one row of RecommenderSim against the frozen AlterEgo profiles (item fold-in: Engine.item_foldin), its neighbour list
@@ -757,13 +804,15 @@ def recommend_audience_items(alterEgoRDD, new_items, cap, keep, alpha, n, decay=
     repeated one, or one the train set knows, raises ValueError; an entry whose uid the train set does not know is dropped and
     counted in .unknown_users.  Works on a union of AlterEgo rows as well (it reads the tail only).  Returns the LocalRDD of
     (iid, [(uid, plain, decayed)*]) in the order of `new_items`, with .stats, .sim_pairs, .item_info, .unknown_users, .counts =
-    (pairs, records, items with a pair), .new_sim_pairs {iid: [(nid, sim)*]} and .new_item_info {iid: (avg, norm, raters)}."""
+    (pairs, records, items with a pair), .new_sim_pairs {iid: [(nid, sim)*]} and .new_item_info {iid: (avg, norm, raters)}.
+    allow_users, exclude = {iid of a new item: uids}, min_score: the eligibility rules of recommend_audience."""
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_audience_items")
     rows, x_nb, x_avg, index, unknown = _item_fold_in(st, eng2, P, S, nb, item_avg, new_items)
     I = len(st.idt.iids)
     iids = sorted(index, key=index.get)
     res = _audience_records(st, eng2, P, x_nb, x_avg, iids, st.idt.uids, alpha, n, decay, keep_holders, getattr(new_items, "ctx", None),
-                            iidx={iid: I + q for iid, q in index.items()}, batch=(rows.ptr, rows.user))
+                            iidx={iid: I + q for iid, q in index.items()}, batch=(rows.ptr, rows.user),
+                            rules=_eligibility(st.engine.dev, iids, _user_index(st.idt), len(st.idt.uids), allow_users, exclude, min_score))
     res.unknown_users, res.counts = unknown, rows.counts
     _tail_dicts(res, st, S, nb)
     _item_dicts(res, st, rows, x_nb, index)
