@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -24,6 +24,10 @@ the same unrounded prediction).
 target item of the catalogue ("in stock") with a score floor, without the item that led their unrestricted list ("shown
 yesterday"); and the audiences of three items among every third user (a segment) above the same floor (the allow_items= /
 allow_users=, exclude= and min_score= options of recommend_topn and recommend_audience: the rules act before scoring).
+
+--diverse W (with --device-tail): the top-10 lists of the evaluated users re-ranked out of their 40 best items by greedy maximal
+marginal relevance at weight W (the diversify= / pool= options of evaluate_topn and recommend_topn): NDCG@10 and the mean intra-list
+similarity at weight 0 -- the plain lists -- and at W, then the re-ranked top 5 of the same three users.
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -102,6 +106,7 @@ def main(argv=None):
     ap.add_argument("--audience", action="store_true")
     ap.add_argument("--new-items", action="store_true")
     ap.add_argument("--eligible", action="store_true")
+    ap.add_argument("--diverse", type=float, default=None, metavar="W")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -131,6 +136,8 @@ def main(argv=None):
         ap.error("--audience needs --device-tail and the non-private recommender")
     if args.eligible and (not args.device_tail or para["recommender"]["private_flag"]):
         ap.error("--eligible needs --device-tail and the non-private recommender")
+    if args.diverse is not None and (not args.device_tail or para["recommender"]["private_flag"]):
+        ap.error("--diverse needs --device-tail and the non-private recommender")
     late = []                   # (uid, profile) of the users who arrive after training
     if args.fold_in:
         if not args.device_tail or para["recommender"]["private_flag"]:
@@ -219,6 +226,19 @@ def main(argv=None):
             len(segment), el.stats[0], el.stats[5], el.stats[4]))
         for iid, lst in el.collect():
             print("eligible audience of %s:" % iid, ", ".join("%s (%.3f)" % (uid, plain) for uid, plain, _ in lst) or "nobody eligible")
+    if args.diverse is not None:
+        # score against redundancy: the same evaluation over lists re-ranked out of a pool of 40, at weight 0 and at W
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        for weight in (0.0, args.diverse):
+            ev = timed("diverse_eval_w%g" % weight, session.evaluate_topn, alterEgo_profile, testRDD, w, k, alpha, 10, cutoffs=(10,),
+                       rel_min=4.0, diversify=weight, pool=40)
+            print("diversify %g: NDCG@10 %.4f, mean intra-list similarity %.4f, %d items covered, over %d users" % (
+                weight, ev.at[10]["ndcg"], ev.ils, ev.at[10]["coverage"], ev.at[10]["users"]))
+        dv = timed("diverse_topn", session.recommend_topn, alterEgo_profile, [uid for uid, _ in top.collect()], w, k, alpha, 5,
+                   diversify=args.diverse, pool=40)
+        for (uid, lst), ils in zip(dv.collect(), dv.ils):
+            print("diversified top 5 for %s (intra-list similarity %.3f):" % (uid, ils),
+                  ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "no evidence")
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

@@ -596,6 +596,38 @@ int xmap_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                    int64_t *h_stats /* host, [4] or NULL: candidates scored, candidates dropped (status 2),
                                        largest `now`, largest candidate count of one query */);
 
+/* ---- diversified top-N (csrc/stage_e_diverse.hip; DESIGN.md 4 "Diversified lists"): a greedy maximal-marginal-relevance
+ * re-ranking of a top-M pool into a top-N list by item similarity, and the intra-list similarity (ILS) of every returned list.
+ * xmap_div_index: the diversity index of a RecommenderSim CSR (row_ptr [I+1], col / sim [nnz], as xmap_ctx_rec_sim and
+ *   Engine.rec_sim leave it; any order inside a row): dv_col [nnz] = every row's columns ascending, dv_abs [nnz] = fabs(sim)
+ *   beside them; row_ptr is shared.  A pure function of the CSR as a set of entries per row.  A row holds a column at most once:
+ *   the repeated (row, column) entries are counted into *h_dups (host, may be NULL) and, if there are any, the call returns
+ *   XMAP_ERR_ARG (as for a column outside [0, I)).  nnz < 2^31.  Temporaries (24 B per entry) from the stream's arena.  Syncs.
+ * xmap_diversify_rows: per query q the pool in_cnt[q], in_item / in_plain / in_decay [q][n_pool] as xmap_topn_rows writes it with
+ *   n_top = n_pool (pool position = rank; entries behind the count are ignored), 1 <= n_top <= n_pool <= 64, weight finite and
+ *   >= 0 (else XMAP_ERR_ARG before any device work):
+ *     n = min(in_cnt, n_top); live = positions 0 .. in_cnt-1; pen[j] = sum[j] = 0.0; pairsum = 0.0
+ *     for r = 0 .. n-1:
+ *       obj[j] = score[j] - weight * pen[j]      (score by rank_by; one fp64 multiply, one fp64 subtract)
+ *       j* = the live position with the largest obj (as numbers), the smallest position on equal obj
+ *       out_item / out_plain / out_decay [q][r] = the pool's at j*, out_pos[q][r] = j*, out_pen[q][r] = pen[j*]
+ *       pairsum += sum[j*]; j* leaves live
+ *       if r + 1 < n and 0 <= in_item[j*] < n_items: for every live c whose item is a column of row in_item[j*], with v = dv_abs
+ *         there: pen[c] = v if v > pen[c] (a NaN never raises a penalty); sum[c] += v
+ *     out_cnt[q] = n; out_ils[q] = pairsum / (n (n - 1) / 2), 0.0 for n < 2
+ *   Behind the count: item -1, position -1, 0.0.  Sums in fp64 in pick order.  weight = 0 returns the pool's prefix bit for bit,
+ *   with its ILS.  The similarities are finite (an infinite one makes obj a NaN at weight 0: no order is promised then).  Outputs
+ *   may not alias inputs.  h_stats (host, [2] or NULL): queries whose list differs from the pool's prefix, sum of out_cnt; the
+ *   call syncs only when it is given.  One wave per query; a pure function of the inputs. */
+int xmap_div_index(void *stream, int32_t n_items, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const double *sim,
+                   int32_t *dv_col, double *dv_abs, int64_t *h_dups /* host, may be NULL */);
+int xmap_diversify_rows(void *stream, int64_t n_query, int32_t n_pool, const int32_t *in_cnt, const int32_t *in_item,
+                        const double *in_plain, const double *in_decay, int32_t rank_by, double weight, int32_t n_top,
+                        int32_t n_items, const int64_t *row_ptr, const int32_t *dv_col, const double *dv_abs,
+                        int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_pos,
+                        double *out_pen, double *out_ils,
+                        int64_t *h_stats /* host [2] or NULL: queries whose list differs from the pool prefix, sum of out_cnt */);
+
 /* ---- audience of an item (csrc/stage_e_audience.hip): per query item the n_top best USERS among those whose own rows give
  * evidence for it, ranked by the UNROUNDED prediction -- xmap_topn_rows seen from the item.  Same arrays as xmap_topn_rows, in its
  * order; query_item replaces query_user and out_user replaces out_item.
@@ -1132,6 +1164,20 @@ int xmap_ctx_audience_filtered(xmap_ctx *ctx, int32_t source, int64_t n_query, c
                                int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t *out_cnt, int32_t *out_user,
                                double *out_plain, double *out_decay, const xmap_rec_filter *F /* host pointers inside, or NULL */,
                                int64_t *stats /* [6] or NULL */);
+/* Diversified top-N: xmap_ctx_recommend_filtered with n_top = n_pool into device temporaries, then xmap_diversify_rows over the
+ * context's diversity index of the resident RecommenderSim -- so the rules of F act before the pool is cut, and the floor before
+ * the re-ranking.  Sources: XMAP_SRC_RESIDENT (also on a union context) and XMAP_SRC_FOLDIN; XMAP_SRC_ITEM_FOLDIN is XMAP_ERR_ARG
+ * (the rows of batch items are not part of the index).  weight finite and >= 0, 1 <= n_top <= n_pool <= 64 and the source are
+ * checked on the host before any device work: on XMAP_ERR_ARG the outputs are untouched and the context is as it was.  The index
+ * is built on first use, dropped with the RecommenderSim result (any earlier stage run again) and kept by
+ * xmap_ctx_rec_set_neighbors / xmap_ctx_rec_select: it belongs to the matrix, not to the lists.  Host outputs: out_cnt [n_query],
+ * out_item / out_plain / out_decay / out_pen [n_query][n_top], out_ils [n_query]. */
+int xmap_ctx_recommend_diverse(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_pool,
+                               int32_t n_top, int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, double weight,
+                               const xmap_rec_filter *F /* host pointers inside, or NULL */, int32_t *out_cnt, int32_t *out_item,
+                               double *out_plain, double *out_decay, double *out_pen, double *out_ils,
+                               int64_t *stats /* [8] or NULL: the six of xmap_ctx_recommend_filtered, then the two of
+                                                 xmap_diversify_rows */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

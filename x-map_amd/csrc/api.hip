@@ -90,6 +90,12 @@ struct xmap_ctx {
     int rec_cap = 0;                // the num_atleast of the resident RecommenderSim (an item fold-in weights with the same)
     int32_t *nb_cnt = nullptr, *nb_col = nullptr;
     double *nb_sim = nullptr, *nb_ls = nullptr;
+    // the diversity index of the RecommenderSim CSR (xmap_div_index; rs_row_ptr is shared): built by the first
+    // xmap_ctx_recommend_diverse, dropped with the matrix, kept when the neighbour lists change
+    Pool p_div;
+    bool have_div = false;
+    int32_t *dv_col = nullptr;
+    double *dv_abs = nullptr;
     // item fold-in: the RecommenderSim rows of the last batch of new items (if_*), the batch's rater CSR, and the EXTENDED tables
     // of I + if_new items (x_*: rows [0, I) copies of nb_* / rs_avg, row I + q the list and the average of batch item q); hangs
     // on the tail and the neighbour lists: dropped with them
@@ -157,8 +163,8 @@ static void drop_ifold(xmap_ctx *c) {
 
 static void drop_tail(xmap_ctx *c) {
     drop_ifold(c);
-    c->p_nb.release(); c->p_rec.release();
-    c->have_rec = c->have_nb = false;
+    c->p_nb.release(); c->p_rec.release(); c->p_div.release();
+    c->have_rec = c->have_nb = c->have_div = false;
 }
 
 // the fold-in batch hangs on the replacement map: upload, item_sim, extend and generate drop it; the tail calls leave it
@@ -1333,6 +1339,66 @@ int xmap_ctx_audience_filtered(xmap_ctx *c, int32_t source, int64_t n_query, con
     }
     return audience_over(c, source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c), resident_tables(c), n_query, query_item,
                          n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain, out_decay, stats, F, 6);
+}
+
+// ---- diversified lists: the filtered top-N with n_top = n_pool into device temporaries, then the re-ranking ----------------------
+
+int xmap_ctx_recommend_diverse(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top,
+                               int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, double weight, const xmap_rec_filter *F,
+                               int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, double *out_pen,
+                               double *out_ils, int64_t *stats) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(weight >= 0.0 && weight <= 1.7976931348623157e308);      // finite and >= 0 (a NaN fails both)
+    XM_ARG(n_pool >= 1 && n_pool <= 64);
+    XM_ARG(n_top >= 1 && n_top <= n_pool);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN);       // the rows of batch items are not part of the index
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query >= 0 && (n_query == 0 || (query_user && out_cnt && out_item && out_plain && out_decay && out_pen && out_ils)));
+    XM_TRY(check_filter(F, n_query));
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 8; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    const int32_t I = c->R.n_items;
+    if (!c->have_div) {
+        c->p_div.release();
+        XM_ALLOC(c->p_div, c->dv_col, c->rec_pairs); XM_ALLOC(c->p_div, c->dv_abs, c->rec_pairs);
+        int64_t dups = 0;
+        XM_TRY(xmap_div_index(c->st, I, c->rec_pairs, c->rs_row_ptr, c->rs_col, c->rs_sim, c->dv_col, c->dv_abs, &dups));
+        c->have_div = true;
+    }
+    const Profiles P = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const Tables T = resident_tables(c);
+    ScratchPool tmp;
+    int32_t *d_user, *p_cnt, *p_item, *d_cnt, *d_item, *d_pos;
+    double *d_w, *p_plain, *p_decay, *d_plain, *d_decay, *d_pen, *d_ils;
+    const size_t n = (size_t)n_query, mp = n * (size_t)n_pool, m = n * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_user, query_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &p_cnt, n, c->st)); XM_TRY(dalloc(tmp, &p_item, mp, c->st));
+    XM_TRY(dalloc(tmp, &p_plain, mp, c->st)); XM_TRY(dalloc(tmp, &p_decay, mp, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st)); XM_TRY(dalloc(tmp, &d_pos, m, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
+    XM_TRY(dalloc(tmp, &d_pen, m, c->st)); XM_TRY(dalloc(tmp, &d_ils, n, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+    int64_t h6[6] = {0, 0, 0, 0, 0, 0}, h2[2] = {0, 0};
+    XM_TRY(xmap_topn_rows_filtered(c->st, n_query, d_user, n_pool, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
+                                   P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, p_cnt, p_item, p_plain, p_decay, &D, h6));
+    XM_TRY(xmap_diversify_rows(c->st, n_query, n_pool, p_cnt, p_item, p_plain, p_decay, rank_by, weight, n_top, I, c->rs_row_ptr,
+                               c->dv_col, c->dv_abs, d_cnt, d_item, d_plain, d_decay, d_pos, d_pen, d_ils, h2));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_TRY(d2h(out_pen, (const double *)d_pen, m, c->st));
+    XM_TRY(d2h(out_ils, (const double *)d_ils, n, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    if (stats) { for (int k = 0; k < 6; k++) stats[k] = h6[k]; stats[6] = h2[0]; stats[7] = h2[1]; }
+    return XMAP_OK;
 }
 
 // ---- explanations -------------------------------------------------------------------------------------------------------

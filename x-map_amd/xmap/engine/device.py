@@ -99,6 +99,11 @@ class ExtResult(object):
     pass
 
 
+class DivIndex(object):
+    """what Engine.div_index returns: the diversity index of a rec_sim result"""
+    pass
+
+
 class GenResult(object):
     pass
 
@@ -1735,6 +1740,48 @@ class Engine(object):
                                      vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()),
                                      vp(wtab), i32(wtab.numel()), vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
         return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
+
+    def div_index(self, S):
+        """The diversity index of a rec_sim result (xmap_div_index): every row's columns ascending with |sim| beside them, what
+        diversify() searches.  Returns a handle (n_items, row_ptr -- S's own --, dv_col, dv_abs, nnz) on the device; it belongs to
+        the matrix, whatever neighbour lists are selected from it.  A row that holds a column twice raises XmapError."""
+        I, nnz = int(S.row_ptr.numel()) - 1, int(S.col.numel())
+        X = DivIndex()
+        X.n_items, X.nnz, X.row_ptr = I, nnz, S.row_ptr.contiguous()
+        X.dv_col, X.dv_abs = self._empty(max(nnz, 1), torch.int32), self._empty(max(nnz, 1), torch.float64)
+        dups = C.c_int64(0)
+        with self.timed("div_index"):
+            check(lib.xmap_div_index(_stream(self.dev), i32(I), i64(nnz), vp(X.row_ptr), vp(S.col.contiguous()), vp(S.sim.contiguous()),
+                                     vp(X.dv_col), vp(X.dv_abs), C.byref(dups)))
+        return X
+
+    def diversify(self, lists, index, weight, n_top, rank_by=0):
+        """Greedy maximal-marginal-relevance re-ranking on the device (xmap_diversify_rows) of the pools `lists` = what topn()
+        returned with n_top = the pool's width (1..64; the stats are ignored), over a div_index() handle: the next item is the one
+        with the largest score - weight * (its largest |sim| to an item picked so far), the earlier pool position on equal
+        values.  weight finite and >= 0; weight 0 returns the pool's prefix.  Returns (cnt [Q], item [Q][n_top] (-1 behind the
+        count), plain, decayed [Q][n_top], pos [Q][n_top] = the pool position of each pick (-1 behind the count), pen [Q][n_top] =
+        the penalty it was picked at, ils [Q] = the mean pairwise |sim| of the returned items (0.0 below two), stats = (lists that
+        differ from the pool's prefix, items returned))."""
+        in_cnt, in_item, in_plain, in_decay = [x.contiguous() for x in lists[:4]]
+        Q, n_top = int(in_cnt.numel()), int(n_top)
+        n_pool = int(in_item.shape[1]) if in_item.dim() == 2 else 1
+        weight = float(weight)
+        if not (0.0 <= weight < float("inf")):
+            raise ValueError("weight = %r: finite and >= 0" % weight)
+        if not 1 <= n_top <= n_pool <= 64:
+            raise ValueError("n_top = %d of a pool of %d: 1 <= n_top <= pool <= 64" % (n_top, n_pool))
+        cnt = self._empty(max(Q, 1), torch.int32)
+        item, pos = self._empty((max(Q, 1), n_top), torch.int32), self._empty((max(Q, 1), n_top), torch.int32)
+        plain, decay, pen = [self._empty((max(Q, 1), n_top), torch.float64) for _ in range(3)]
+        ils = self._empty(max(Q, 1), torch.float64)
+        h = (C.c_int64 * 2)(0, 0)
+        with self.timed("diversify"):
+            check(lib.xmap_diversify_rows(_stream(self.dev), i64(Q), i32(n_pool), vp(in_cnt), vp(in_item), vp(in_plain), vp(in_decay),
+                                          i32(rank_by), C.c_double(weight), i32(n_top), i32(index.n_items), vp(index.row_ptr),
+                                          vp(index.dv_col), vp(index.dv_abs), vp(cnt), vp(item), vp(plain), vp(decay), vp(pos), vp(pen),
+                                          vp(ils), h))
+        return cnt[:Q], item[:Q], plain[:Q], decay[:Q], pos[:Q], pen[:Q], ils[:Q], (int(h[0]), int(h[1]))
 
     def audience(self, P, neighbors, query_item, item_avg, wtab, n_top, rank_by=0, keep_holders=False, batch=None, allow=None,
                  exclude=None, min_score=None):

@@ -112,6 +112,7 @@ EXPORTS = [
     "xmap_itemfold_count", "xmap_itemfold_fill", "xmap_itemfold_audience_rows", "xmap_ctx_item_foldin", "xmap_ctx_item_foldin_download",
     "xmap_ctx_item_foldin_audience", "xmap_ctx_item_foldin_predict", "xmap_ctx_item_foldin_recommend",
     "xmap_topn_rows_filtered", "xmap_audience_rows_filtered", "xmap_ctx_recommend_filtered", "xmap_ctx_audience_filtered",
+    "xmap_div_index", "xmap_diversify_rows", "xmap_ctx_recommend_diverse",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -8,6 +8,7 @@
 The id dictionary built from a trainRDD is shared by the three stages; engines are
 cached per trainRDD object so that generator_pipeline reuses the one stage A uploaded.
 """
+import math
 import weakref
 
 import numpy as np
@@ -492,7 +493,7 @@ def _eligibility(dev, labels, index, n_ids, allow, exclude, min_score):
 
 
 def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None,
-                   allow_items=None, exclude=None, min_score=None):
+                   allow_items=None, exclude=None, min_score=None, diversify=None, pool=None):
     """Top-N recommendation on the device from an AlterEgoRDD handle: the set-up of recommend (profiles -> RecommenderSim ->
     neighbour lists, or `neighbors`), then for every uid of `users` the n (1..64) best items its own rows give evidence for,
     ranked by the unrounded prediction -- without temporal decay, or with (decay=True, alpha) -- score descending, item id
@@ -506,38 +507,79 @@ def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_he
     returned at all (in stock, a category, the new releases), exclude = {uid: iids never returned for that user} (shown yesterday,
     bought elsewhere), min_score = floor on the ranking score (plain, or decayed with decay=True); iids the train set does not know
     are ignored.  With any of them .stats has six entries: the four above over the eligible candidates, the candidates below the
-    floor, the candidate pairs the rules removed before scoring."""
+    floor, the candidate pairs the rules removed before scoring.
+    Diversified lists: diversify = a weight w >= 0 re-ranks the `pool` best items (default min(64, 4 n); n <= pool <= 64) of every
+    user into the n returned ones by greedy maximal marginal relevance (Engine.diversify): the next item is the one with the largest
+    score - w * (its largest |sim| in the RecommenderSim matrix to an item picked so far).  The records are the existing ones in the
+    new order, the rules act before the pool is cut, and the result carries .ils = the mean pairwise |sim| of every user's list, in
+    the order of `users`, and .div_stats = (lists that differ from the pool's prefix, items returned).  diversify = 0 returns the
+    lists of the plain call with their .ils; diversify = None takes the plain path untouched."""
+    _diverse(n, diversify, pool)
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn")
     idt = st.idt
     uids = list(users.collect()) if hasattr(users, "collect") else list(users)
     uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
     query = [uidx.get(uid, -1) for uid in uids]
     res = _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, getattr(users, "ctx", None),
-                        _eligibility(st.engine.dev, uids, idt.iidx, len(idt.iids), allow_items, exclude, min_score))
+                        _eligibility(st.engine.dev, uids, idt.iidx, len(idt.iids), allow_items, exclude, min_score),
+                        _diverse(n, diversify, pool, eng2, S))
     _tail_dicts(res, st, S, nb)
     if explain is not None:
         _explain_lists(res, st, eng2, P, nb, item_avg, query, alpha, decay, explain, (st.ratings, st.times) if hasattr(st, "ratings") else None)
     return res
 
 
-def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, ctx, rules=None):
-    """what recommend_topn and recommend_topn_profiles share: the lists of the user indices `query` of P, labelled `uids` -> the
-    LocalRDD of (uid, [(iid, plain, decayed)*]) with .stats; rules = _eligibility(...)"""
-    import torch
-    idt, dev = st.idt, st.engine.dev
-    d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
+def _diverse(n, diversify, pool, eng2=None, S=None):
+    """the diversify= / pool= keywords of a top-N call, checked (before any device work, without eng2) -> None (the plain path) or
+    (weight, pool width, the diversity index of S: built once per RecommenderSim result and kept on it, next to what the neighbour
+    lists are selected from)"""
+    if diversify is None:
+        if pool is not None:
+            raise ValueError("pool = %r without diversify" % (pool,))
+        return None
+    weight = float(diversify)
+    if not (0.0 <= weight < float("inf")):
+        raise ValueError("diversify = %r: a finite weight >= 0" % (diversify,))
+    m = min(64, 4 * int(n)) if pool is None else int(pool)
+    if not 1 <= int(n) <= m <= 64:
+        raise ValueError("n = %d of a pool of %d: 1 <= n <= pool <= 64" % (int(n), m))
+    if eng2 is None:
+        return weight, m, None
+    if getattr(S, "div_index", None) is None:
+        S.div_index = eng2.div_index(S)
+    return weight, m, S.div_index
+
+
+def _topn_lists(eng2, P, nb, d_q, item_avg, alpha, n, decay, keep_held, dev, rules, diverse):
+    """Engine.topn with a decay table long enough (and Engine.diversify over its pool): (cnt, item, plain, decayed, stats, ils,
+    div_stats), the last two None on the plain path"""
     n_w = 66
     while True:
         wtab = _decay_table(alpha, n_w, dev)
-        cnt, item, plain, decayed, stats = eng2.topn(P, nb, d_q, item_avg, wtab, int(n), 1 if decay else 0, keep_held, **(rules or {}))
-        if stats[2] <= n_w:
+        out = eng2.topn(P, nb, d_q, item_avg, wtab, int(diverse[1] if diverse else n), 1 if decay else 0, keep_held, **(rules or {}))
+        if out[4][2] <= n_w:
             break
-        n_w = stats[2]
+        n_w = out[4][2]
+    if not diverse:
+        return out + (None, None)
+    cnt, item, plain, decayed, _, _, ils, div_stats = eng2.diversify(out, diverse[2], diverse[0], int(n), 1 if decay else 0)
+    return cnt, item, plain, decayed, out[4], ils, div_stats
+
+
+def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, ctx, rules=None, diverse=None):
+    """what recommend_topn and recommend_topn_profiles share: the lists of the user indices `query` of P, labelled `uids` -> the
+    LocalRDD of (uid, [(iid, plain, decayed)*]) with .stats; rules = _eligibility(...), diverse = _diverse(...)"""
+    import torch
+    idt, dev = st.idt, st.engine.dev
+    d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
+    cnt, item, plain, decayed, stats, ils, div_stats = _topn_lists(eng2, P, nb, d_q, item_avg, alpha, n, decay, keep_held, dev, rules, diverse)
     cnt, item, plain, decayed = cnt.cpu().numpy(), item.cpu().numpy(), plain.cpu().numpy(), decayed.cpu().numpy()
     iids = idt.iids
     out = [(uid, [(iids[item[q, t]], float(plain[q, t]), float(decayed[q, t])) for t in range(cnt[q])]) for q, uid in enumerate(uids)]
     res = LocalRDD(out, ctx)
     res.stats = stats
+    if diverse:
+        res.ils, res.div_stats = [float(x) for x in ils.cpu().numpy()], div_stats
     return res
 
 
@@ -663,7 +705,7 @@ def _fold_in(st, G, profiles):
 
 
 def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None,
-                            allow_items=None, exclude=None, min_score=None):
+                            allow_items=None, exclude=None, min_score=None, diversify=None, pool=None):
     """recommend_topn for users that are not rows of the train set -- a user who arrived after training, a trained user whose
     profile changed: `profiles` is an RDD or list of (uid, [(iid, rating, time)*]) raw profiles, source and target items mixed.
     Each gets its AlterEgo profile with the replacement map behind alterEgoRDD (fold-in: Engine.foldin_profiles) and then the
@@ -673,13 +715,15 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     recommend_topn in the order of `profiles`, with .stats, .sim_pairs, .item_info, .unknown_items and .counts = (AlterEgo rows,
     pass-through rows, profiles with a row).  explain as recommend_topn takes it: the sources are then entries of the profile
     passed in (its iid, rating and time objects).  allow_items, exclude = {uid of a profile: iids}, min_score: the eligibility
-    rules of recommend_topn."""
+    rules of recommend_topn.  diversify, pool: the diversified lists of recommend_topn, with .ils and .div_stats."""
     _no_fold_in(alterEgoRDD, "recommend_topn_profiles")
+    _diverse(n, diversify, pool)
     st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn_profiles")
     F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
     uids = sorted(index, key=index.get)
     res = _topn_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, n, decay, keep_held, getattr(profiles, "ctx", None),
-                        _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
+                        _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score),
+                        _diverse(n, diversify, pool, eng2, S))
     res.unknown_items, res.counts = unknown, F.counts
     _tail_dicts(res, st, S, nb)
     if explain is not None:
@@ -853,14 +897,15 @@ def recommend_profiles(alterEgoRDD, profiles, testRDD, cap, keep, alpha, neighbo
 
 class TopnEvaluation(object):
     """what evaluate_topn returns: .at {cutoff: dict(users, hit_rate, precision, recall, ndcg, map, mrr, coverage)}, .stats,
-    .masks {uid: hit mask}, .sim_pairs, .item_info"""
+    .masks {uid: hit mask}, .sim_pairs, .item_info, .ils (mean intra-list similarity over the evaluated users; None unless the lists
+    were diversified)"""
 
     def __init__(self):
-        self.at, self.stats, self.masks = {}, (0,) * 8, {}
+        self.at, self.stats, self.masks, self.ils = {}, (0,) * 8, {}, None
 
 
 def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20), rel_min=4.0, decay=False, keep_held=False,
-                  neighbors=None):
+                  neighbors=None, diversify=None, pool=None):
     """Hold-out evaluation of the top-N recommendation on the device: the set-up of recommend, then the held-out pairs of
     testRDD ((uid, [(iid, rating, ...)*]) records as recommend takes them, every (uid, iid) once) pick the users with a rating
     >= rel_min (Engine.eval_users), those users get their n best items (Engine.topn: recommend_topn's lists), and the lists
@@ -870,11 +915,15 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     distinct items within c over their lists); .stats = (evaluated users, relevant pairs, ignored pairs, pairs below rel_min,
     candidates scored, candidates dropped, largest `now`, largest candidate count); .masks {uid: int} for the evaluated users
     (bit r = the item at rank r is a relevant held-out item); .sim_pairs / .item_info like recommend.  ValueError on a
-    repeated (uid, iid) or a rating that is not a number."""
+    repeated (uid, iid) or a rating that is not a number.
+    diversify, pool as recommend_topn takes them: the lists that are scored are the re-ranked ones, and .ils is the mean intra-list
+    similarity over the evaluated users (summed on the host from the per-user values; 0.0 without users), so one call per weight
+    gives the accuracy / redundancy curve -- diversify = 0 the redundancy of the plain lists."""
     import torch
     if not isinstance(alterEgoRDD, (AlterEgoRDD, AlterEgoUnion)):
         raise TypeError("evaluate_topn() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device) or the "
                         "AlterEgoUnion of union_alterego")
+    _diverse(n, diversify, pool)
     recs = records_of(testRDD)
     seen = set()
     for uid, pairs in recs:
@@ -897,13 +946,8 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     d_tu, d_ti, d_tr = torch.from_numpy(tu).to(dev), torch.from_numpy(ti).to(dev), torch.from_numpy(real).to(dev)
     U, I = len(idt.uids), len(idt.iids)
     n_rel, users, counts = eng2.eval_users(d_tu, d_ti, d_tr, float(rel_min), U, I)
-    n_w = 66
-    while True:
-        wtab = _decay_table(alpha, n_w, dev)
-        cnt, item, _, _, stats = eng2.topn(P, nb, users, item_avg, wtab, int(n), 1 if decay else 0, keep_held)
-        if stats[2] <= n_w:
-            break
-        n_w = stats[2]
+    cnt, item, _, _, stats, ils, _ = _topn_lists(eng2, P, nb, users, item_avg, alpha, n, decay, keep_held, dev, None,
+                                                 _diverse(n, diversify, pool, eng2, S))
     mask, _, agg, cover = eng2.topn_eval(d_tu, d_ti, d_tr, float(rel_min), n_rel, users, cnt, item, cuts, I)
     res = TopnEvaluation()
     agg, cover = agg.cpu().numpy(), cover.cpu().numpy()
@@ -914,6 +958,9 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
                          recall=mean(float(agg[k, 4])), ndcg=mean(float(agg[k, 5])), map=mean(float(agg[k, 6])),
                          mrr=mean(float(agg[k, 7])), coverage=int(cover[k]))
     res.stats = tuple(counts) + tuple(stats)
+    if ils is not None:
+        v = ils.cpu().numpy()
+        res.ils = math.fsum(v.tolist()) / len(v) if len(v) else 0.0
     res.masks = {idt.uids[u]: int(b) & 0xffffffffffffffff for u, b in zip(users.cpu().tolist(), mask.cpu().tolist())}
     _tail_dicts(res, st, S, nb)
     return res
