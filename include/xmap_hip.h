@@ -853,9 +853,9 @@ typedef struct {
  * h_stats (host, [6] or NULL): [0..3] as in the unfiltered calls, taken over the ELIGIBLE candidates; [4] = candidates with status
  * 0 whose rank_by score is below min_score; [5] = candidate pairs removed by the mask or the exclusion lists = the [0] of the
  * unfiltered call minus this call's [0] (a held item that is also excluded does not count, a repeated exclusion counts once).
- * Limit, shared with the unfiltered calls and xmap_predict_rows: the scoring pass launches one wave per pair in ONE grid, which
- * beyond 6.7e7 pairs has more than 2^32 threads -- keep the candidate pairs of a call (h_stats[0]) below that; the rules are one
- * way to get there, fewer queries per call the other.
+ * The scoring pass, shared with the unfiltered calls and xmap_predict_rows, starts one wave per pair; it is launched in ranges of
+ * 15 * 2^22 (6.3e7) pairs, so the pair count of a call (h_stats[0]) is bounded by the memory per pair only (28 B of temporaries per candidate
+ * pair, 16 B per pair in xmap_predict_rows), not by the 2^32 threads of a grid.
  * ex_ptr is checked on the device before any candidate work (ex_ptr[0] == 0, non-decreasing; ids listed while ex_id == NULL):
  * XMAP_ERR_ARG, nothing is read through a table that fails.
  * xmap_topn_rows_filtered: the arguments of xmap_topn_rows up to out_decay, then F and h_stats [6].

@@ -1,8 +1,8 @@
 """Timing of diversified top-N (Engine.div_index, Engine.diversify) on the AlterEgo rows of a synthetic workload, with the protocol
 of filter_timing.py: HIP events, warm, median of --reps, the calls alternated rep by rep.  The first --users users with rows are
 the queries; their pools are the unfiltered xmap_topn_rows lists with n_top = --pool, and that call is timed too: it is what the
-re-ranking is an addition to.  One top-N call must stay below MAX_PAIRS scored pairs (as in filter_timing.py: beyond 6.7e7 the
-scoring launch has more than 2^32 threads), so the queries are cut into equal chunks, halved until the first chunk's call scores
+re-ranking is an addition to.  One top-N call stays below MAX_PAIRS scored pairs (as in filter_timing.py: once the limit of a single
+scoring grid, kept so that the numbers compare), so the queries are cut into equal chunks, halved until the first chunk's call scores
 at most MAX_PAIRS pairs; top-N runs chunk by chunk and its time is the sum over the chunks, the re-ranking runs over all pools at
 once.
 
@@ -24,7 +24,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "x-map_amd"))
 
-MAX_PAIRS = 60000000            # below the 2^32 threads of one scoring launch (64 threads per pair)
+MAX_PAIRS = 60000000            # pairs of one call: what the recorded runs used (once the limit of a single scoring grid)
 
 
 def main():

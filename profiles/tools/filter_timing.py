@@ -1,9 +1,9 @@
 """Timing of top-N and audience under eligibility rules (Engine.topn / Engine.audience with allow= / exclude= / min_score=) on the
 AlterEgo rows of a synthetic workload, with the protocol of audience_timing.py: HIP events, warm, median of --reps; the --items
 most-held listed items for audience, the first --users users with rows for top-N.  The query sets are halved until the
-unfiltered call scores at most MAX_PAIRS pairs: the scoring pass launches one wave per pair in one grid, and beyond 6.7e7
-pairs that grid has more than 2^32 threads -- a time taken there is not the time of complete scoring.  One
-call times, alternated rep by rep (each rep starts one variant further on):
+unfiltered call scores at most MAX_PAIRS pairs: when the tool was written the scoring pass was one grid, which from 6.7e7
+pairs on has 2^32 threads; the pass is launched in ranges since and the bound stays so that the numbers
+compare with the recorded ones.  One call times, alternated rep by rep (each rep starts one variant further on):
 
     unfiltered      the unfiltered entry (xmap_topn_rows / xmap_audience_rows)
     empty           the _filtered entry with an empty filter {NULL, NULL, NULL, -inf}
@@ -33,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, os.path.join(ROOT, "x-map_amd"))
 
 
-MAX_PAIRS = 60000000            # below the 2^32 threads of one scoring launch (64 threads per pair)
+MAX_PAIRS = 60000000            # pairs of one call: what the recorded runs used (once the limit of a single scoring grid)
 
 
 def main():

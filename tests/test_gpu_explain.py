@@ -290,10 +290,11 @@ def test_hand_case_through_the_engine(n_ev, rank_by):
 
 
 # ------------------------------------------------------------------------------------------- 2. beyond the LDS staging
-def test_evidence_beyond_the_lds_staging():
+def _staging_case():
+    """test_gpu_topn._hand_case (a user holding one neighbour 300 times) + two more users holding ONE neighbour 129 and 128 times:
+    the boundary of the staging.  (arrays, users, items, keep, the 300-row user, the item whose list holds that one neighbour)"""
     arrays, U, I, keep, dup_user = _hand_case(copies=300)
     ptr, pit, pra, pti, cnt, col, sim, avg = arrays[:8]
-    # two more users holding ONE neighbour 129 and 128 times: the boundary of the staging, both launches in one call
     star = next(i for i in range(I) if cnt[i] >= 1 and 0 <= col[i, 0] < I and (col[i, :min(cnt[i], keep)] == col[i, 0]).sum() == 1)
     x = int(col[star, 0])
     extra = [129, 128]
@@ -301,8 +302,13 @@ def test_evidence_beyond_the_lds_staging():
     pit = np.concatenate([pit, np.full(sum(extra), x, pit.dtype)])
     pra = np.concatenate([pra, 1.0 + (np.arange(sum(extra)) % 7) / 2.0])
     pti = np.concatenate([pti, (np.arange(sum(extra)) % 50).astype(np.int64) * 3600])
-    arrays = [ptr, pit, pra, pti, cnt, col, sim, avg]
-    U2 = U + 2
+    return [ptr, pit, pra, pti, cnt, col, sim, avg], U + 2, I, keep, dup_user, star
+
+
+def test_evidence_beyond_the_lds_staging():
+    # both launches in one call
+    arrays, U2, I, keep, dup_user, star = _staging_case()
+    U = U2 - 2
     pu = [dup_user] * I + [U, U + 1, 3, 4, 5]
     pi = list(range(I)) + [star, star, 5, 5, 5]
     assert len(pu) % 4 != 0                             # a last block with idle waves

@@ -377,12 +377,10 @@ def _predict_rows(arrays, n_users, n_items, keep, alpha, n_w):
     return plain.cpu().numpy(), decay.cpu().numpy(), status.cpu().numpy(), h.value
 
 
-@pytest.mark.parametrize("copies", [70, 300])
-def test_evidence_beyond_64_entries(copies):
-    """a user holding one neighbour item 70 times with distinct times (the construction xmap_predict hands back to the host
-    with status 2), and 300 times: more than the LDS staging of a wave holds, the arena launch"""
-    from xmap.core.recommenderPrediction import RecommenderPrediction
-    n_users, n_items, keep, alpha, dup_user = 80, 60, 10, 1.5, 7
+def _long_evidence_case(copies):
+    """the dictionaries of _prediction_case with a user holding one neighbour item `copies` times at distinct times, and a test
+    line for that user over an item whose list holds the neighbour: (ratings, sims, info, test, the line, sizes)"""
+    n_users, n_items, keep, dup_user = 80, 60, 10, 7
     ratings, sims, info, test = _prediction_case(3, n_users, n_items, dup_user=dup_user)
     held = "B%04dT:" % 1
     if copies > 70:
@@ -392,17 +390,32 @@ def test_evidence_beyond_64_entries(copies):
         info[held] = (float(np.mean([x[1] for x in ratings[held]])), 1.0, len(ratings[held]))
     owners = [i for i, lst in sims.items() if any(n == held for n, _ in lst)]
     assert owners
-    test = test + [("U%05d" % dup_user, [(owners[0], 4.0)])]
+    return ratings, sims, info, test, ("U%05d" % dup_user, [(owners[0], 4.0)]), (n_users, n_items, keep)
+
+
+def _long_evidence_statement(ratings, sims, info, test, alpha):
+    """the Python statement over the test lines; per pair the `now` (distinct times of its evidence + 1) and its evidence entries"""
+    from xmap.core.recommenderPrediction import RecommenderPrediction
     tool = RecommenderPrediction(alpha, "cosine_item")
     rb, sb, ib = _B(ratings), _B(sims), _B(info)
     want = [t for line in test for t in tool.item_based_prediction(line, rb, sb, ib)[1]]
-    # the `now` of every pair from the Python side: distinct times of its evidence + 1
     nows = []
     for u, pairs in test:
         for p in pairs:
             times = {when for n, _ in sims.get(p[0], []) for who, _, when in ratings[n] if who == u}
             nows.append(len(times) + 1 if times else 0)
     n_ev = [sum(1 for n, _ in sims.get(p[0], []) for who, _, _ in ratings[n] if who == u) for u, pairs in test for p in pairs]
+    return want, nows, n_ev
+
+
+@pytest.mark.parametrize("copies", [70, 300])
+def test_evidence_beyond_64_entries(copies):
+    """a user holding one neighbour item 70 times with distinct times (the construction xmap_predict hands back to the host
+    with status 2), and 300 times: more than the LDS staging of a wave holds, the arena launch"""
+    alpha = 1.5
+    ratings, sims, info, test, line, (n_users, n_items, keep) = _long_evidence_case(copies)
+    test = test + [line]
+    want, nows, n_ev = _long_evidence_statement(ratings, sims, info, test, alpha)
     assert max(n_ev) >= copies and n_ev[-1] == max(n_ev) and max(nows) > 66
     arrays = _case_arrays(ratings, sims, info, test, n_users, n_items, keep)
     real = [p[1] for _, pairs in test for p in pairs]

@@ -2,6 +2,7 @@
 // predictions of item_based_prediction) and the scoring pass of the top-N recommendation (stage_e_topn.hip: the same two
 // values before bound_rating).  One body with a compile-time switch: the two kernels are the same code.
 #pragma once
+#include <stdlib.h>
 #include "common.h"
 
 namespace xmap {
@@ -10,6 +11,32 @@ constexpr int PR_CAP = 128;        // evidence entries of a pair staged in LDS (
 constexpr int PR_WAVES = 4;
 constexpr int EX_MAX_EV = 16;      // evidence entries an explanation reports per pair
 constexpr int EX_MAX_SRC = 8;      // source positions it reports per entry
+
+// Work items (one wave each) of one launch of a wave-per-item kernel.  A grid holds fewer than 2^32 threads, that is fewer than
+// 2^26 waves: a call with more items than PAIR_RANGE is launched range by range, the kernel taking the first item of its range
+// as a base for the wave index; a call with fewer is the one launch it always was.  15 / 16 of the 2^26: as large as a grid
+// may be, less a margin -- the waves of two ranges do not overlap, so every cut costs the tail of one launch (about 1 ms in
+// 600 at 5.5e7 pairs when the range was 2^25), and the calls that were one launch before ranges existed stay one.
+constexpr long long PAIR_RANGE = 15ll << 22;
+static_assert(PAIR_RANGE * 64 < (1ll << 32), "the grid of a range stays below 2^32 threads");
+
+// launch(first item of the range, one past its last item, grid) for the ranges of n_work items, in ascending order;
+// `waves` = work items per block; every launch is checked.  XMAP_PAIR_RANGE (tests: several ranges on small inputs) lowers the
+// range, read once per call.
+template <class Launch>
+static int for_pair_ranges(long long n_work, int waves, Launch launch) {
+    long long span = PAIR_RANGE;
+    if (const char *e = getenv("XMAP_PAIR_RANGE")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v < span) span = v;
+    }
+    for (long long base = 0; base < n_work; base += span) {
+        const long long end = n_work - base < span ? n_work : base + span;
+        launch(base, end, dim3((unsigned)((end - base + waves - 1) / waves)));
+        XM_LAUNCH_CHECK();
+    }
+    return XMAP_OK;
+}
 
 // The explain mode's outputs (xmap_explain_rows, stage_e_explain.hip); unused -- and compiled out -- in the other modes.
 struct ExplainOut {
@@ -55,14 +82,14 @@ __device__ __forceinline__ void wave_sync() {
 // an entry is 8 doubles instead of 6.  The other instantiations compile none of this.
 template <bool ARENA, bool RAW, bool EXPLAIN = false>
 __device__ __forceinline__ void predict_pair(
-    long long n_work, const int *tu, const int *ti, long long U, int I, int keep, const int *nb_cnt, const int *nb_col,
+    long long w_base, long long n_work, const int *tu, const int *ti, long long U, int I, int keep, const int *nb_cnt, const int *nb_col,
     const double *nb_sim, const long long *pptr, const int *pitem, const double *prating, const long long *ptime,
     const double *avg, const double *wtab, int n_w, double *out_plain, double *out_decay, int *status, int *max_now,
     unsigned long long *ovf, long long *ovf_list, double *arena, const ExplainOut X = ExplainOut()) {
     static_assert(!EXPLAIN || RAW, "the explanation reports the unrounded score");
     constexpr int COLS = EXPLAIN ? 8 : 6;       // doubles of an arena slice per evidence entry
     const int wv = threadIdx.x >> 6, lane = lane_id();
-    const long long w = (long long)blockIdx.x * PR_WAVES + wv;
+    const long long w = w_base + (long long)blockIdx.x * PR_WAVES + wv;      // the launch covers the work items [w_base, n_work)
     if (w >= n_work) return;
     const long long t = ARENA ? ovf_list[2 * w] : w;
     const int u = tu[t], it = ti[t];
@@ -253,18 +280,21 @@ __device__ __forceinline__ void predict_pair(
 
 template <bool ARENA, bool RAW>
 __global__ __launch_bounds__(64 * PR_WAVES) void k_predict_rows(
-    long long n_work, const int *tu, const int *ti, long long U, int I, int keep, const int *nb_cnt, const int *nb_col,
+    long long w_base, long long n_work, const int *tu, const int *ti, long long U, int I, int keep, const int *nb_cnt, const int *nb_col,
     const double *nb_sim, const long long *pptr, const int *pitem, const double *prating, const long long *ptime,
     const double *avg, const double *wtab, int n_w, double *out_plain, double *out_decay, int *status, int *max_now,
     unsigned long long *ovf, long long *ovf_list, double *arena) {
-    predict_pair<ARENA, RAW>(n_work, tu, ti, U, I, keep, nb_cnt, nb_col, nb_sim, pptr, pitem, prating, ptime, avg, wtab, n_w, out_plain,
+    predict_pair<ARENA, RAW>(w_base, n_work, tu, ti, U, I, keep, nb_cnt, nb_col, nb_sim, pptr, pitem, prating, ptime, avg, wtab, n_w, out_plain,
                              out_decay, status, max_now, ovf, ovf_list, arena);
 }
 
 // The two launches of a pair kernel over n_test pairs: the wave-per-pair launch, then -- for the pairs whose evidence does not
 // fit the LDS staging -- the same kernel over an arena of exactly the entries the first launch counted (arena_cols doubles per
-// entry).  launch(arena launch?, grid, pairs of the launch, max_now, ctl, ovf_list, arena) starts the kernel; one host wait per
-// launch.  *h_max_now (may be NULL) = the largest `now` met.  Shared by the prediction, the top-N scores and the explanation.
+// entry).  Either launch is cut into ranges of PAIR_RANGE work items (for_pair_ranges): launch(arena launch?, grid, first work
+// item, one past the last, max_now, ctl, ovf_list, arena) starts the kernel on one range.  The counters, max_now, ovf_list and
+// the arena belong to the whole call: every range adds to the same ctl and appends to the same ovf_list, and the arena launch
+// reads the list that all ranges wrote.  One host wait per launch (not per range).  *h_max_now (may be NULL) = the largest
+// `now` met.  Shared by the prediction, the top-N scores and the explanation.
 template <class Launch>
 static int pair_rows_run(hipStream_t st, int64_t n_test, int arena_cols, int32_t *h_max_now, Launch launch) {
     XM_SCOPE(st);
@@ -276,16 +306,20 @@ static int pair_rows_run(hipStream_t st, int64_t n_test, int arena_cols, int32_t
     XM_HIP(xm_malloc_async((void **)&ovf_list, sizeof(long long) * 2 * (size_t)n_test, st));
     XM_HIP(hipMemsetAsync(ctl, 0, sizeof(unsigned long long) * 3, st));
     int *max_now = (int *)(ctl + 2);
-    launch(false, dim3((unsigned)((n_test + PR_WAVES - 1) / PR_WAVES)), (long long)n_test, max_now, ctl, ovf_list, (double *)nullptr);
-    XM_LAUNCH_CHECK();
+    int rc = for_pair_ranges((long long)n_test, PR_WAVES, [&](long long base, long long end, dim3 grid) {
+        launch(false, grid, base, end, max_now, ctl, ovf_list, (double *)nullptr);
+    });
+    if (rc) return rc;
     unsigned long long h[3] = {0, 0, 0};
     XM_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
     if (h[0] > 0) {       // pairs whose evidence does not fit the LDS staging: the same kernel over an arena of exactly h[1] entries
         double *arena = nullptr;
         XM_HIP(xm_malloc_async((void **)&arena, sizeof(double) * arena_cols * (size_t)h[1], st));
-        launch(true, dim3((unsigned)((h[0] + PR_WAVES - 1) / PR_WAVES)), (long long)h[0], max_now, ctl, ovf_list, arena);
-        XM_LAUNCH_CHECK();
+        rc = for_pair_ranges((long long)h[0], PR_WAVES, [&](long long base, long long end, dim3 grid) {
+            launch(true, grid, base, end, max_now, ctl, ovf_list, arena);
+        });
+        if (rc) return rc;
         XM_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
         XM_HIP(hipStreamSynchronize(st));
     }
@@ -299,10 +333,10 @@ static int predict_rows_run(hipStream_t st, int64_t n_test, const int32_t *test_
                             const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time,
                             const double *item_avg, const double *wtab, int32_t n_w, double *out_plain, double *out_decay,
                             int32_t *status, int32_t *h_max_now) {
-    return pair_rows_run(st, n_test, 6, h_max_now, [&](bool in_arena, dim3 grid, long long n_work, int *max_now, unsigned long long *ctl,
-                                                       long long *ovf_list, double *arena) {
+    return pair_rows_run(st, n_test, 6, h_max_now, [&](bool in_arena, dim3 grid, long long w_base, long long n_work, int *max_now,
+                                                       unsigned long long *ctl, long long *ovf_list, double *arena) {
         auto k = in_arena ? k_predict_rows<true, RAW> : k_predict_rows<false, RAW>;
-        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(n_work, test_user, test_item, n_users, n_items, keep, nb_cnt, nb_col, nb_sim,
+        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(w_base, n_work, test_user, test_item, n_users, n_items, keep, nb_cnt, nb_col, nb_sim,
                                                 (const long long *)prof_ptr, prof_item, prof_rating, (const long long *)prof_time, item_avg,
                                                 wtab, n_w, out_plain, out_decay, status, max_now, ctl, ovf_list, arena);
     });

@@ -21,22 +21,22 @@ namespace xmap {
 
 template <bool ARENA>
 __global__ __launch_bounds__(64 * PR_WAVES) void k_explain_rows(
-    long long n_work, const int *tu, const int *ti, long long U, int I, int keep, const int *nb_cnt, const int *nb_col,
+    long long w_base, long long n_work, const int *tu, const int *ti, long long U, int I, int keep, const int *nb_cnt, const int *nb_col,
     const double *nb_sim, const long long *pptr, const int *pitem, const double *prating, const long long *ptime,
     const double *avg, const double *wtab, int n_w, int *status, int *max_now, unsigned long long *ovf, long long *ovf_list,
     double *arena, ExplainOut X) {
-    predict_pair<ARENA, true, true>(n_work, tu, ti, U, I, keep, nb_cnt, nb_col, nb_sim, pptr, pitem, prating, ptime, avg, wtab, n_w,
+    predict_pair<ARENA, true, true>(w_base, n_work, tu, ti, U, I, keep, nb_cnt, nb_col, nb_sim, pptr, pitem, prating, ptime, avg, wtab, n_w,
                                     nullptr, nullptr, status, max_now, ovf, ovf_list, arena, X);
 }
 
 constexpr int XS_WAVES = 4;
 
 __global__ __launch_bounds__(64 * XS_WAVES) void k_explain_sources(
-    long long n_work, const int *pair_user, int n_ev, const int *ex_cnt, const long long *ex_row, long long U, int I,
+    long long w_base, long long n_work, const int *pair_user, int n_ev, const int *ex_cnt, const long long *ex_row, long long U, int I,
     const long long *pptr, const int *pitem, const int *cnt_t, const long long *off_t, const long long *rptr, const int *ritem,
     const uint8_t *flags, const int *map, int n_src, int *src_total, long long *src_pos) {
     const int lane = lane_id();
-    const long long w = (long long)blockIdx.x * XS_WAVES + (threadIdx.x >> 6);
+    const long long w = w_base + (long long)blockIdx.x * XS_WAVES + (threadIdx.x >> 6);     // the launch covers [w_base, n_work)
     if (w >= n_work) return;
     const long long t = w / n_ev;
     const int e = (int)(w - t * n_ev);
@@ -97,10 +97,10 @@ int xmap_explain_rows(void *stream, int64_t n_pairs, const int32_t *pair_user, c
     ExplainOut X;
     X.rank_by = rank_by; X.n_ev = n_ev; X.total = ex_total; X.cnt = ex_cnt; X.score = ex_score; X.row = (long long *)ex_row;
     X.slot = ex_slot; X.share = ex_share;
-    return pair_rows_run(st, n_pairs, 8, h_max_now, [&](bool in_arena, dim3 grid, long long n_work, int *max_now, unsigned long long *ctl,
-                                                        long long *ovf_list, double *arena) {
+    return pair_rows_run(st, n_pairs, 8, h_max_now, [&](bool in_arena, dim3 grid, long long w_base, long long n_work, int *max_now,
+                                                        unsigned long long *ctl, long long *ovf_list, double *arena) {
         auto k = in_arena ? k_explain_rows<true> : k_explain_rows<false>;
-        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(n_work, pair_user, pair_item, n_users, n_items, keep, nb_cnt, nb_col, nb_sim,
+        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(w_base, n_work, pair_user, pair_item, n_users, n_items, keep, nb_cnt, nb_col, nb_sim,
                                                 (const long long *)prof_ptr, prof_item, prof_rating, (const long long *)prof_time, item_avg,
                                                 wtab, n_w, ex_status, max_now, ctl, ovf_list, arena, X);
     });
@@ -118,11 +118,10 @@ int xmap_explain_sources(void *stream, int64_t n_pairs, const int32_t *pair_user
     XM_ARG(n_users == 0 || n_pairs == 0 || (prof_item && raw_item && flags && map_src2tgt));
     if (n_pairs == 0) return XMAP_OK;
     const long long n_work = (long long)n_pairs * n_ev;
-    XM_ARG((n_work + XS_WAVES - 1) / XS_WAVES < 2147483647ll);
-    k_explain_sources<<<dim3((unsigned)((n_work + XS_WAVES - 1) / XS_WAVES)), dim3(64 * XS_WAVES), 0, (hipStream_t)stream>>>(
-        n_work, pair_user, n_ev, ex_cnt, (const long long *)ex_row, n_users, n_items, (const long long *)prof_ptr, prof_item, cnt_t,
-        (const long long *)off_t, (const long long *)raw_ptr, raw_item, flags, map_src2tgt, n_src, src_total, (long long *)src_pos);
-    XM_LAUNCH_CHECK();
-    return XMAP_OK;
+    return for_pair_ranges(n_work, XS_WAVES, [&](long long base, long long end, dim3 grid) {      // one wave per (pair, entry): in ranges
+        k_explain_sources<<<grid, dim3(64 * XS_WAVES), 0, (hipStream_t)stream>>>(
+            base, end, pair_user, n_ev, ex_cnt, (const long long *)ex_row, n_users, n_items, (const long long *)prof_ptr, prof_item, cnt_t,
+            (const long long *)off_t, (const long long *)raw_ptr, raw_item, flags, map_src2tgt, n_src, src_total, (long long *)src_pos);
+    });
 }
 }
