@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -28,6 +28,11 @@ allow_users=, exclude= and min_score= options of recommend_topn and recommend_au
 --diverse W (with --device-tail): the top-10 lists of the evaluated users re-ranked out of their 40 best items by greedy maximal
 marginal relevance at weight W (the diversify= / pool= options of evaluate_topn and recommend_topn): NDCG@10 and the mean intra-list
 similarity at weight 0 -- the plain lists -- and at W, then the re-ranked top 5 of the same three users.
+
+--groups K (with --device-tail): one list for several users -- three groups of K members are drawn from the test users, and the top 5
+of the first group are printed side by side under the three aggregates (mean, least misery, most pleasure) with the member who
+likes each item least (xmap.engine.session.recommend_group: the members' unrounded predictions are aggregated on the device; a
+member without evidence for an item predicts its average).
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -107,6 +112,7 @@ def main(argv=None):
     ap.add_argument("--new-items", action="store_true")
     ap.add_argument("--eligible", action="store_true")
     ap.add_argument("--diverse", type=float, default=None, metavar="W")
+    ap.add_argument("--groups", type=int, default=None, metavar="K")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -138,6 +144,8 @@ def main(argv=None):
         ap.error("--eligible needs --device-tail and the non-private recommender")
     if args.diverse is not None and (not args.device_tail or para["recommender"]["private_flag"]):
         ap.error("--diverse needs --device-tail and the non-private recommender")
+    if args.groups is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.groups <= 64):
+        ap.error("--groups K needs --device-tail, the non-private recommender and 1 <= K <= 64")
     late = []                   # (uid, profile) of the users who arrive after training
     if args.fold_in:
         if not args.device_tail or para["recommender"]["private_flag"]:
@@ -239,6 +247,23 @@ def main(argv=None):
         for (uid, lst), ils in zip(dv.collect(), dv.ils):
             print("diversified top 5 for %s (intra-list similarity %.3f):" % (uid, ils),
                   ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _ in lst) or "no evidence")
+    if args.groups is not None:
+        # one list for several users: K-member groups of test users under the three aggregates
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        pool = [uid for uid, _ in testRDD.take(3 * args.groups)]
+        parties = [("group %d" % (g + 1), pool[g * args.groups:(g + 1) * args.groups]) for g in range(3) if pool[g * args.groups:(g + 1) * args.groups]]
+        by_how = {}
+        for how in ("mean", "min", "max"):
+            by_how[how] = timed("group_topn_" + how, session.recommend_group, alterEgo_profile, parties, w, k, alpha, 5, how=how)
+        st = by_how["mean"].stats
+        print("groups: %d of %d members: %d member pairs scored, %d group candidates (largest group %d)" % (
+            len(parties), args.groups, st[0], st[7], st[3]))
+        gid, members = parties[0]
+        print("%s = %s" % (gid, ", ".join(members)))
+        print("  %-44s | %-44s | %-44s" % ("mean", "least misery", "most pleasure"))
+        cols = [by_how[how].collect()[0][1] for how in ("mean", "min", "max")]
+        for pos in range(max(len(c) for c in cols)):
+            print("  " + " | ".join("%-44s" % ("%s %.3f (least: %s)" % (c[pos][0], c[pos][1], c[pos][3]) if pos < len(c) else "") for c in cols))
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

@@ -875,6 +875,65 @@ int xmap_audience_rows_filtered(void *stream, int64_t n_query, const int32_t *qu
                                 int32_t n_resident, const int64_t *new_ptr /*[n_new+1] or NULL*/, const int32_t *new_user,
                                 const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
 
+/* ---- group lists (csrc/stage_e_group.hip; DESIGN.md 4 "Group lists"): ONE top-N list for several users -- a household, a party
+ * of four, a shared account -- by aggregating the members' UNROUNDED predictions.  Combining per-member lists of xmap_topn_rows on
+ * the host cannot do this: the cut is inside the kernel (an item that is tenth for every member is first for the group and in
+ * nobody's list), and a member without evidence for an item still predicts it -- the item average -- which no list carries.
+ * Inputs: the arrays of xmap_topn_rows (profiles, nb_cnt / nb_col / nb_sim [I][keep], item_avg, wtab / n_w), and
+ *   groups as a CSR: grp_ptr [G + 1] (grp_ptr[0] = 0, non-decreasing), grp_user [grp_ptr[G]]; how = XMAP_GROUP_MEAN (average),
+ *   XMAP_GROUP_MIN (least misery) or XMAP_GROUP_MAX (most pleasure); veto; flags (XMAP_TOPN_KEEP_HELD only); F or NULL.
+ * Members: group g has the members u_0 .. u_{m-1} in list order, 0 <= m <= XMAP_GROUP_MAX_MEMBERS.  A repeated member counts as
+ *   often as it is listed (a weight).  A member outside [0, n_users) or without rows is still a member: it holds nothing and has
+ *   no evidence for anything, as in xmap_predict_rows.
+ * Candidates of g: (1) the items i that are a candidate of at least one member in the sense of xmap_topn_rows with KEEP_HELD
+ *   (nb_cnt[i] > 0 and the member's profile holds one of the first min(nb_cnt[i], keep) neighbours; an entry outside [0, I) is
+ *   ignored); (2) without XMAP_TOPN_KEEP_HELD every item that ANY member holds leaves; (3) the ids of the group's exclusion list
+ *   leave (F->ex_ptr is indexed by group); (4) the rest is intersected with F->allow.  In ascending item index, each once.
+ * Member scores: s_j = the unrounded `plain` (and, separately, `decayed`) of the pair (u_j, i), exactly as xmap_topn_rows gives
+ *   it; if u_j has no evidence for i, s_j = item_avg[i], the same bits (the prediction's own answer for such a pair).  A
+ *   candidate is dropped and counted in stats[1] if some member's pair has status 2 (zero weight sum, non-finite value, now > n_w)
+ *   or some member lacks evidence while item_avg[i] is not finite.  stats[2] = the largest `now` met; beyond n_w: call again with
+ *   a table of that length, as with xmap_topn_rows.
+ * Aggregate, for plain and for decayed by the same rule: MEAN = (((s_0 + s_1) + ...) + s_{m-1}) / (double)m -- fp64 sums left to
+ *   right starting from s_0 (not from 0.0 + s_0), one division; MIN / MAX: compared as numbers, on equal values the earliest member
+ *   in list order supplies the bits.
+ * Veto ("average without misery"): a candidate leaves and is counted in stats[6] if some member's rank_by score is < veto, as
+ *   numbers, under every `how`.  veto = -INFINITY: no veto.  NaN: XMAP_ERR_ARG.
+ * Floor: F->min_score acts on the AGGREGATE rank_by score; counted in stats[4].  Order of the drops: status 2, veto, floor.
+ * Ranking: by the aggregate rank_by score descending, item index ascending on equal scores (scores compare as numbers).
+ * Outputs (device): out_cnt [G]; out_item / out_plain / out_decay [G][n_top] with -1 / 0.0 / 0.0 behind the count, exactly as
+ *   xmap_topn_rows writes them -- so xmap_diversify_rows takes them as a pool unchanged; out_low [G][n_top] = the position j in the
+ *   group's list of the member with the smallest rank_by score for that item, the smallest such j on ties, -1 behind the count
+ *   ("who likes this least").  1 <= n_top <= 64.  A group with m = 0 gets count 0.  A pure function of the inputs: it depends on
+ *   neither the grid nor the order of the atomics.
+ * h_stats (host, [8] or NULL): [0] member pairs scored (pairs with evidence only), [1] group candidates dropped for status 2,
+ *   [2] largest `now`, [3] largest candidate count of one group, [4] group candidates below the floor, [5] group candidates
+ *   removed by the exclusion lists (a bit still set after step 2; a repeated exclusion counts once; an item F->allow leaves out
+ *   is never marked, so it is not counted here), [6] group candidates vetoed, [7] group candidates after steps 1-4, summed over
+ *   the groups.  [0] and [2] are taken over the pairs the member pass scores: per listing of a member, the items its rows give
+ *   evidence for that F->allow admits and -- without XMAP_TOPN_KEEP_HELD -- that the member does not hold itself.
+ * A group of one member under any `how`, veto = -INFINITY, returns the list of xmap_topn_rows_filtered for that user bit for bit,
+ *   out_low = 0, stats[0..4] equal.
+ * Passes: grp_ptr is checked on the device before any other work (XMAP_ERR_ARG with a message; nothing is read through a table
+ *   that fails, the outputs are untouched) -> member pass: the candidate-and-scoring half of xmap_topn_rows over the flattened
+ *   member list, under F->allow and the call's flags (an item a member holds leaves the group without KEEP_HELD whoever has
+ *   evidence for it, so that member's pair is never needed): per member a segment of (item ascending, plain, decayed, status),
+ *   pairs with evidence only -- a pair without evidence predicts item_avg and costs no wave.  A masked item is never scored; an
+ *   excluded one may be (the exclusion lists belong to groups, and are short) -> the groups' candidates through the LDS bitmap
+ *   (count, scan, fill) -> aggregate and select, one wave per group, a member's score found by bisection in its segment.
+ *   Temporaries from the stream's arena; every offset is int64.  Syncs. */
+#define XMAP_GROUP_MEAN 0
+#define XMAP_GROUP_MIN 1
+#define XMAP_GROUP_MAX 2
+#define XMAP_GROUP_MAX_MEMBERS 64
+int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr, const int32_t *grp_user, int32_t n_top, int32_t rank_by,
+                         int32_t flags, int32_t how, double veto,
+                         int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
+                         const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
+                         const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
+                         int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_low,
+                         const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [8] or NULL */);
+
 /* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
  * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
  * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
@@ -1057,6 +1116,7 @@ int xmap_union_fill(void *stream, int32_t n_parts, const xmap_union_part *parts 
  *                             stats [6] (may be NULL) as h_stats of the fine-grained calls.  The host checks min_score (NaN), ex_ptr
  *                             (ex_ptr[0] == 0, non-decreasing), ex_id (NULL while ids are listed) and source before any device
  *                             work: XMAP_ERR_ARG, the outputs untouched, the context as it was
+ *   xmap_ctx_recommend_group : group lists (xmap_group_topn_rows) over the same three sources; stats [8] as its h_stats
  * Errors: negative return code, text in xmap_last_error(). */
 typedef struct xmap_ctx xmap_ctx;
 
@@ -1178,6 +1238,16 @@ int xmap_ctx_recommend_diverse(xmap_ctx *ctx, int32_t source, int64_t n_query, c
                                double *out_plain, double *out_decay, double *out_pen, double *out_ils,
                                int64_t *stats /* [8] or NULL: the six of xmap_ctx_recommend_filtered, then the two of
                                                  xmap_diversify_rows */);
+/* Group lists: xmap_group_topn_rows over the resident tables, host arrays in and out.  Sources as xmap_ctx_recommend_filtered; with
+ * XMAP_SRC_FOLDIN the members index the fold-in batch (a party of guests nobody trained on), with XMAP_SRC_ITEM_FOLDIN a batch
+ * item q is returned as I + q.  The mask and the exclusion ids are ITEMS; F->ex_ptr has one list per GROUP.  how, veto (NaN),
+ * n_top, rank_by, flags, grp_ptr (grp_ptr[0] == 0, non-decreasing, sizes <= XMAP_GROUP_MAX_MEMBERS), the filter and the source
+ * are checked on the host before any device work: on XMAP_ERR_ARG the outputs are untouched and the context is as it was.  Host
+ * outputs: out_cnt [n_groups], out_item / out_plain / out_decay / out_low [n_groups][n_top]. */
+int xmap_ctx_recommend_group(xmap_ctx *ctx, int32_t source, int64_t n_groups, const int64_t *grp_ptr, const int32_t *grp_user,
+                             int32_t n_top, int32_t rank_by, int32_t flags, int32_t how, double veto, const double *wtab, int32_t n_w,
+                             int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_low,
+                             const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [8] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

@@ -1341,6 +1341,64 @@ int xmap_ctx_audience_filtered(xmap_ctx *c, int32_t source, int64_t n_query, con
                          n_top, rank_by, flags, wtab, n_w, out_cnt, out_user, out_plain, out_decay, stats, F, 6);
 }
 
+// ---- group lists: one list for several users, over the three sources --------------------------------------------------------------
+
+int xmap_ctx_recommend_group(xmap_ctx *c, int32_t source, int64_t n_groups, const int64_t *grp_ptr, const int32_t *grp_user, int32_t n_top,
+                             int32_t rank_by, int32_t flags, int32_t how, double veto, const double *wtab, int32_t n_w, int32_t *out_cnt,
+                             int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_low, const xmap_rec_filter *F,
+                             int64_t *stats) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(how == XMAP_GROUP_MEAN || how == XMAP_GROUP_MIN || how == XMAP_GROUP_MAX);
+    XM_ARG(veto == veto);                       // NaN
+    XM_ARG(n_top >= 1 && n_top <= 64);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_groups >= 0 && (n_groups == 0 || (grp_ptr && out_cnt && out_item && out_plain && out_decay && out_low)));
+    if (n_groups > 0 && grp_ptr[0] != 0) { set_error("groups: grp_ptr[0] = %lld, not 0", (long long)grp_ptr[0]); return XMAP_ERR_ARG; }
+    for (int64_t g = 0; g < n_groups; g++) {
+        const int64_t m = grp_ptr[g + 1] - grp_ptr[g];
+        if (m < 0) { set_error("groups: grp_ptr[%lld] < grp_ptr[%lld]", (long long)g + 1, (long long)g); return XMAP_ERR_ARG; }
+        if (m > XMAP_GROUP_MAX_MEMBERS) {
+            set_error("groups: group %lld has %lld members, more than %d", (long long)g, (long long)m, XMAP_GROUP_MAX_MEMBERS);
+            return XMAP_ERR_ARG;
+        }
+    }
+    const int64_t n_mem = n_groups > 0 ? grp_ptr[n_groups] : 0;
+    if (n_mem > 0 && !grp_user) { set_error("groups: grp_ptr lists %lld members, grp_user is NULL", (long long)n_mem); return XMAP_ERR_ARG; }
+    XM_TRY(check_filter(F, n_groups));
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN || source == XMAP_SRC_ITEM_FOLDIN);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(source != XMAP_SRC_ITEM_FOLDIN || c->have_ifold);
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 8; k++) stats[k] = 0;
+    if (n_groups == 0) return XMAP_OK;
+    const Profiles P = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const Tables T = source == XMAP_SRC_ITEM_FOLDIN ? itemfold_tables(c) : resident_tables(c);
+    ScratchPool tmp;
+    int64_t *d_ptr;
+    int32_t *d_user = nullptr, *d_cnt, *d_item, *d_low;
+    double *d_w, *d_plain, *d_decay;
+    const size_t n = (size_t)n_groups, m = n * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_ptr, grp_ptr, n + 1, c->st));
+    if (n_mem > 0) XM_TRY(h2d(tmp, &d_user, grp_user, (size_t)n_mem, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st)); XM_TRY(dalloc(tmp, &d_low, m, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_groups, T.n_items, &D));
+    XM_TRY(xmap_group_topn_rows(c->st, n_groups, d_ptr, d_user, n_top, rank_by, flags, how, veto, P.n_users, T.n_items, T.keep, T.cnt, T.col,
+                                T.sim, P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, d_low, &D, stats));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_TRY(d2h(out_low, (const int32_t *)d_low, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
 // ---- diversified lists: the filtered top-N with n_top = n_pool into device temporaries, then the re-ranking ----------------------
 
 int xmap_ctx_recommend_diverse(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top,

@@ -2,7 +2,7 @@
 // evidence for, ranked by the unrounded prediction (DESIGN.md 4 "Top-N").  Everything it reads is what the tail leaves
 // resident: user-major profiles, neighbour lists [I][keep], item averages.
 //
-//   k_tn_rev<count | fill> : the reverse of the neighbour lists -- for neighbour n the items whose first
+//   k_tn_rev<count | fill> : (topn_pass.h) the reverse of the neighbour lists -- for neighbour n the items whose first
 //                     min(cnt, keep) entries hold n -- by count -> xmap_exclusive_scan -> fill.  One entry per list position
 //                     (a repeated neighbour repeats its owner); the order inside a row is whatever the atomics give: the
 //                     candidate pass de-duplicates through a bitmap and emits in index order.
@@ -20,58 +20,20 @@
 // xmap_topn_rows_filtered (rec_filter.h; DESIGN.md 4 "Eligibility"): the FILT instantiation of k_tn_candidates clears the query's
 // exclusion ids in the bitmap and ANDs every emitted word with the item mask -- before anything is scored -- and k_tn_select
 // drops and counts the candidates below the score floor.
+// The call is two halves: tn_score_candidates (reverse lists, candidates, scores; declared in topn_pass.h, which also holds k_tn_rev,
+// tn_block_scan and the window geometry) and the selection.  The group lists (stage_e_group.hip) run the first half over their
+// flattened member list.
 // Every output position follows from the scans, so the result does not depend on the grid or on the order of the atomics.
 #include "common.h"
 #include "predict_rows.h"
 #include "rec_filter.h"
+#include "topn_pass.h"
 
 namespace xmap {
 
 constexpr int TN_WINDOW = 1 << 19;              // items per bitmap pass (64 KB of LDS; two blocks per CU)
+static_assert(TN_WINDOW == 1 << TN_WINDOW_LOG2, "the window of topn_pass.h, which stage_e_group.hip shares");
 static_assert(TN_WINDOW % 32 == 0, "a window starts at a word of the mask");
-constexpr int TN_WORDS = TN_WINDOW / 32;
-constexpr int TN_SUMMARY = TN_WORDS / 32;       // second level: bit w of word s = bitmap word 32 s + w was touched
-constexpr int TN_THREADS = 256;
-constexpr int TN_PER = TN_SUMMARY / TN_THREADS; // summary words a thread emits (consecutive: thread order = item order)
-constexpr int TN_MAX_TOP = 64;
-constexpr int TN_MAX_BLOCKS = 2048;         // blocks of the candidate pass (grid-stride over the queries: the window is zeroed once per block)
-
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_tn_rev(int I, int keep, const int *nb_cnt, const int *nb_col, int *rcnt, const long long *rptr,
-                                                int *ritem) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long i = t / keep;
-    const int p = (int)(t - i * keep);
-    if (i >= I) return;
-    int cnt = nb_cnt[i];
-    cnt = cnt < keep ? cnt : keep;
-    if (p >= cnt) return;
-    const int nb = nb_col[(size_t)i * keep + p];
-    if (nb < 0 || nb >= I) return;              // ignored, as in the prediction
-    const int at = atomicAdd(&rcnt[nb], 1);
-    if constexpr (FILL) ritem[rptr[nb] + at] = (int)i;
-}
-
-__device__ __forceinline__ int tn_block_scan(int v, int *total, int *smem) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) smem[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < TN_THREADS / 64; k++) {
-        const int s = smem[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
 
 // FILT (rec_filter.h): the query's exclusion ids are cleared behind the held items, and a touched word meets its word of the
 // mask where it is emitted; the count pass adds what the two removed to *removed.  FILT = false is the unfiltered kernel.
@@ -256,6 +218,64 @@ static hipError_t tn_candidates(bool filt, hipStream_t st, unsigned blocks, size
     return hipGetLastError();
 }
 
+// topn_pass.h: the candidate-and-scoring half, shared with the member pass of the group lists (stage_e_group.hip)
+int tn_score_candidates(hipStream_t st, int64_t n_query, const int32_t *query_user, int32_t flags, int64_t n_users, int32_t n_items,
+                        int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col, const double *nb_sim, const int64_t *prof_ptr,
+                        const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time, const double *item_avg,
+                        const double *wtab, int32_t n_w, bool filt, const unsigned int *allow, const long long *ex_ptr, const int *ex_id,
+                        unsigned long long *removed, TnScored *out) {
+    const int I = n_items;
+    const size_t i1 = (size_t)(I ? I : 1);
+    // ---- reverse neighbour lists
+    int *rcnt = nullptr, *ritem = nullptr;
+    long long *rptr = nullptr;
+    int64_t n_rev = 0;
+    XM_HIP(xm_malloc_async((void **)&rcnt, sizeof(int) * i1, st));
+    XM_HIP(xm_malloc_async((void **)&rptr, sizeof(long long) * (i1 + 1), st));
+    XM_HIP(hipMemsetAsync(rcnt, 0, sizeof(int) * i1, st));
+    const unsigned rev_blocks = (unsigned)(((long long)I * keep + 255) / 256);
+    if (I > 0) {
+        k_tn_rev<false><<<dim3(rev_blocks), dim3(256), 0, st>>>(I, keep, nb_cnt, nb_col, rcnt, nullptr, nullptr);
+        XM_LAUNCH_CHECK();
+    }
+    int rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rptr, I, &n_rev);
+    if (rc) return rc;
+    XM_HIP(xm_malloc_async((void **)&ritem, sizeof(int) * (size_t)(n_rev ? n_rev : 1), st));
+    if (n_rev > 0) {
+        XM_HIP(hipMemsetAsync(rcnt, 0, sizeof(int) * i1, st));
+        k_tn_rev<true><<<dim3(rev_blocks), dim3(256), 0, st>>>(I, keep, nb_cnt, nb_col, rcnt, rptr, ritem);
+        XM_LAUNCH_CHECK();
+    }
+    // ---- candidates: count, scan, fill
+    int *cand_cnt = nullptr, *cand_user = nullptr;
+    XM_HIP(xm_malloc_async((void **)&cand_cnt, sizeof(int) * (size_t)n_query, st));
+    XM_HIP(xm_malloc_async((void **)&out->cand_ptr, sizeof(long long) * ((size_t)n_query + 1), st));
+    const size_t lds = TN_LDS_BYTES;
+    const unsigned cblocks = (unsigned)(n_query < TN_MAX_BLOCKS ? n_query : TN_MAX_BLOCKS);
+    XM_HIP(tn_candidates<false>(filt, st, cblocks, lds, (long long)n_query, query_user, (long long)n_users, I, flags & XMAP_TOPN_KEEP_HELD,
+                                (const long long *)rptr, (const int *)ritem, (const long long *)prof_ptr, prof_item, cand_cnt,
+                                (const long long *)nullptr, (int *)nullptr, (int *)nullptr, allow, ex_ptr, ex_id, removed));
+    rc = xmap_exclusive_scan_i32_to_i64(st, cand_cnt, (int64_t *)out->cand_ptr, n_query, &out->n_pairs);
+    if (rc) return rc;
+    if (out->n_pairs > 0) {
+        const size_t np = (size_t)out->n_pairs;
+        XM_HIP(xm_malloc_async((void **)&cand_user, sizeof(int) * np, st));
+        XM_HIP(xm_malloc_async((void **)&out->cand_item, sizeof(int) * np, st));
+        XM_HIP(xm_malloc_async((void **)&out->plain, sizeof(double) * np, st));
+        XM_HIP(xm_malloc_async((void **)&out->decay, sizeof(double) * np, st));
+        XM_HIP(xm_malloc_async((void **)&out->status, sizeof(int) * np, st));
+        XM_HIP(tn_candidates<true>(filt, st, cblocks, lds, (long long)n_query, query_user, (long long)n_users, I, flags & XMAP_TOPN_KEEP_HELD,
+                                   (const long long *)rptr, (const int *)ritem, (const long long *)prof_ptr, prof_item, (int *)nullptr,
+                                   (const long long *)out->cand_ptr, cand_user, out->cand_item, allow, ex_ptr, ex_id,
+                                   (unsigned long long *)nullptr));
+        // ---- scores: the pair body of the prediction, unrounded
+        rc = predict_rows_run<true>(st, out->n_pairs, cand_user, out->cand_item, n_users, I, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
+                                    prof_rating, prof_time, item_avg, wtab, n_w, out->plain, out->decay, out->status, &out->max_now);
+        if (rc) return rc;
+    }
+    return XMAP_OK;
+}
+
 }  // namespace xmap
 using namespace xmap;
 
@@ -281,76 +301,25 @@ static int topn_rows(void *stream, int64_t n_query, const int32_t *query_user, i
     int rc = rf_prepare(st, n_query, F, &filt, &min_score);     // before any candidate work
     if (rc) return rc;
     if (n_query == 0) return XMAP_OK;
-    const int I = n_items;
-    const size_t i1 = (size_t)(I ? I : 1);
-    // ---- reverse neighbour lists
-    int *rcnt = nullptr, *ritem = nullptr;
-    long long *rptr = nullptr;
-    int64_t n_rev = 0;
-    XM_HIP(xm_malloc_async((void **)&rcnt, sizeof(int) * i1, st));
-    XM_HIP(xm_malloc_async((void **)&rptr, sizeof(long long) * (i1 + 1), st));
-    XM_HIP(hipMemsetAsync(rcnt, 0, sizeof(int) * i1, st));
-    const unsigned rev_blocks = (unsigned)(((long long)I * keep + 255) / 256);
-    if (I > 0) {
-        k_tn_rev<false><<<dim3(rev_blocks), dim3(256), 0, st>>>(I, keep, nb_cnt, nb_col, rcnt, nullptr, nullptr);
-        XM_LAUNCH_CHECK();
-    }
-    rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rptr, I, &n_rev);
-    if (rc) return rc;
-    XM_HIP(xm_malloc_async((void **)&ritem, sizeof(int) * (size_t)(n_rev ? n_rev : 1), st));
-    if (n_rev > 0) {
-        XM_HIP(hipMemsetAsync(rcnt, 0, sizeof(int) * i1, st));
-        k_tn_rev<true><<<dim3(rev_blocks), dim3(256), 0, st>>>(I, keep, nb_cnt, nb_col, rcnt, rptr, ritem);
-        XM_LAUNCH_CHECK();
-    }
-    // ---- candidates: count, scan, fill
-    int *cand_cnt = nullptr, *cand_user = nullptr, *cand_item = nullptr;
-    long long *cand_ptr = nullptr;
-    int64_t n_pairs = 0;
-    XM_HIP(xm_malloc_async((void **)&cand_cnt, sizeof(int) * (size_t)n_query, st));
-    XM_HIP(xm_malloc_async((void **)&cand_ptr, sizeof(long long) * ((size_t)n_query + 1), st));
-    const size_t lds = sizeof(unsigned int) * (TN_WORDS + TN_SUMMARY + TN_THREADS / 64);
-    const unsigned cblocks = (unsigned)(n_query < TN_MAX_BLOCKS ? n_query : TN_MAX_BLOCKS);
     // [0] dropped candidates, [1] largest segment, [2] below the floor, [3] removed by the mask or the exclusion lists
     unsigned long long *stats = nullptr;
     XM_HIP(xm_malloc_async((void **)&stats, sizeof(unsigned long long) * 4, st));
     XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 4, st));
-    const unsigned int *allow = filt ? (const unsigned int *)F->allow : nullptr;
-    const long long *ex_ptr = filt ? (const long long *)F->ex_ptr : nullptr;
-    const int *ex_id = filt ? F->ex_id : nullptr;
-    XM_HIP(tn_candidates<false>(filt, st, cblocks, lds, (long long)n_query, query_user, (long long)n_users, I, flags & XMAP_TOPN_KEEP_HELD,
-                                (const long long *)rptr, (const int *)ritem, (const long long *)prof_ptr, prof_item, cand_cnt,
-                                (const long long *)nullptr, (int *)nullptr, (int *)nullptr, allow, ex_ptr, ex_id, stats + 3));
-    rc = xmap_exclusive_scan_i32_to_i64(st, cand_cnt, (int64_t *)cand_ptr, n_query, &n_pairs);
+    TnScored S;
+    rc = tn_score_candidates(st, n_query, query_user, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating,
+                             prof_time, item_avg, wtab, n_w, filt, filt ? (const unsigned int *)F->allow : nullptr,
+                             filt ? (const long long *)F->ex_ptr : nullptr, filt ? F->ex_id : nullptr, stats + 3, &S);
     if (rc) return rc;
-    double *plain = nullptr, *decay = nullptr;
-    int *status = nullptr;
-    int32_t max_now = 0;
-    if (n_pairs > 0) {
-        const size_t np = (size_t)n_pairs;
-        XM_HIP(xm_malloc_async((void **)&cand_user, sizeof(int) * np, st));
-        XM_HIP(xm_malloc_async((void **)&cand_item, sizeof(int) * np, st));
-        XM_HIP(xm_malloc_async((void **)&plain, sizeof(double) * np, st));
-        XM_HIP(xm_malloc_async((void **)&decay, sizeof(double) * np, st));
-        XM_HIP(xm_malloc_async((void **)&status, sizeof(int) * np, st));
-        XM_HIP(tn_candidates<true>(filt, st, cblocks, lds, (long long)n_query, query_user, (long long)n_users, I, flags & XMAP_TOPN_KEEP_HELD,
-                                   (const long long *)rptr, (const int *)ritem, (const long long *)prof_ptr, prof_item, (int *)nullptr,
-                                   (const long long *)cand_ptr, cand_user, cand_item, allow, ex_ptr, ex_id, (unsigned long long *)nullptr));
-        // ---- scores: the pair body of the prediction, unrounded
-        rc = predict_rows_run<true>(st, n_pairs, cand_user, cand_item, n_users, I, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
-                                    prof_rating, prof_time, item_avg, wtab, n_w, plain, decay, status, &max_now);
-        if (rc) return rc;
-    }
     // ---- selection (n_pairs == 0: every segment is empty, the counts and the padding are still written)
     const bool floor = min_score > -__builtin_inf();   // no floor: the selection of the unfiltered call
     (floor ? k_tn_select<true> : k_tn_select<false>)<<<dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st>>>(
-        n_query, n_top, rank_by, cand_ptr, cand_item, plain, decay, status, out_cnt, out_item, out_plain, out_decay, stats, min_score);
+        n_query, n_top, rank_by, S.cand_ptr, S.cand_item, S.plain, S.decay, S.status, out_cnt, out_item, out_plain, out_decay, stats, min_score);
     XM_LAUNCH_CHECK();
     unsigned long long h[4] = {0, 0, 0, 0};
     XM_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
     if (h_stats) {
-        h_stats[0] = n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = max_now; h_stats[3] = (int64_t)h[1];
+        h_stats[0] = S.n_pairs; h_stats[1] = (int64_t)h[0]; h_stats[2] = S.max_now; h_stats[3] = (int64_t)h[1];
         if (n_stats == 6) { h_stats[4] = (int64_t)h[2]; h_stats[5] = (int64_t)h[3]; }
     }
     return XMAP_OK;

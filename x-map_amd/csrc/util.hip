@@ -205,7 +205,7 @@ static int exclusive_scan(hipStream_t st, const TIn *in, int64_t *out, int64_t n
 
 extern "C" {
 const char *xmap_last_error(void) { return xmap::g_err; }
-int xmap_version(void) { return 112; }
+int xmap_version(void) { return 113; }
 
 /* The library's temporaries: give every idle arena's memory of the calling thread back to the driver (arenas with live
  * temporaries are left alone).  Synchronises the device. */

@@ -1741,6 +1741,55 @@ class Engine(object):
                                      vp(wtab), i32(wtab.numel()), vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), h))
         return out_cnt[:Q], out_item[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
 
+    def group_topn(self, P, neighbors, grp_ptr, grp_user, item_avg, wtab, n_top, how="mean", veto=None, rank_by=0, keep_held=False,
+                   n_items=None, allow=None, exclude=None, min_score=None):
+        """Group lists on the device (xmap_group_topn_rows): ONE list of n_top (1..64) items per group of users, by aggregating
+        the members' unrounded predictions.  Groups are a CSR: grp_ptr int64 [G + 1] (grp_ptr[0] = 0, non-decreasing, at most 64
+        members each), grp_user int32 -- indices into P's users in list order; a repeated member counts as often as listed, an
+        index outside the users is a member without rows.  Candidates: the items at least one member's rows give evidence for;
+        unless keep_held every item ANY member holds leaves.  A member without evidence for a candidate predicts the item
+        average.  how = "mean" (left-to-right fp64 sum, one division), "min" (least misery) or "max" (most pleasure); veto: a
+        candidate leaves if some member's rank_by score is below it (None: no veto).  allow / exclude / min_score as topn()
+        takes them, with one exclusion list per GROUP and the floor on the aggregate score.  Returns (cnt [G], item [G][n_top]
+        (-1 behind the count), plain, decayed [G][n_top], low [G][n_top] = the list position of the least-happy member (-1
+        behind the count), stats) with stats = [member pairs scored, candidates dropped (status 2), largest `now`, largest
+        candidate count of a group, below the floor, removed by the exclusion lists, vetoed, group candidates]: candidates were
+        dropped for a short table when stats[2] > len(wtab).  The first four tensors have the layout of topn(): diversify() takes
+        them as a pool."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        grp_ptr, grp_user = grp_ptr.contiguous(), grp_user.contiguous()
+        G, n_top = int(grp_ptr.numel()) - 1, int(n_top)
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        if not 1 <= n_top <= 64:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 64" % n_top)
+        if isinstance(how, str):
+            if how not in abi.GROUP_HOW:
+                raise ValueError("how = %r: one of %s" % (how, sorted(abi.GROUP_HOW)))
+            how = abi.GROUP_HOW[how]
+        if how not in (abi.GROUP_MEAN, abi.GROUP_MIN, abi.GROUP_MAX):
+            raise ValueError("how = %r: XMAP_GROUP_MEAN / _MIN / _MAX" % (how,))
+        veto = float("-inf") if veto is None else float(veto)
+        if veto != veto:
+            raise ValueError("veto is NaN")
+        if G < 0 or grp_ptr.dtype != torch.int64 or grp_user.dtype != torch.int32:
+            raise ValueError("groups = (grp_ptr int64 [G + 1], grp_user int32)")
+        n_ids = P.n_items if n_items is None else n_items
+        F, alive = self._rec_filter(n_ids, G, allow, exclude, min_score)
+        grp_user = grp_user if grp_user.numel() else torch.zeros(1, dtype=torch.int32, device=self.dev)
+        out_cnt = self._empty(max(G, 1), torch.int32)
+        out_item, out_low = self._empty((max(G, 1), n_top), torch.int32), self._empty((max(G, 1), n_top), torch.int32)
+        out_plain, out_decay = self._empty((max(G, 1), n_top), torch.float64), self._empty((max(G, 1), n_top), torch.float64)
+        h = (C.c_int64 * 8)()
+        with self.timed("group_topn"):
+            check(lib.xmap_group_topn_rows(st, i64(G), vp(grp_ptr), vp(grp_user), i32(n_top), i32(rank_by),
+                                           i32(abi.TOPN_KEEP_HELD if keep_held else 0), i32(how), C.c_double(veto), i64(P.n_users),
+                                           i32(n_ids), i32(keep), vp(cnt), vp(col), vp(sim), vp(P.user_ptr), vp(P.user_item),
+                                           vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()),
+                                           vp(out_cnt), vp(out_item), vp(out_plain), vp(out_decay), vp(out_low), C.byref(F), h))
+        del alive
+        return out_cnt[:G], out_item[:G], out_plain[:G], out_decay[:G], out_low[:G], [int(x) for x in h]
+
     def div_index(self, S):
         """The diversity index of a rec_sim result (xmap_div_index): every row's columns ascending with |sim| beside them, what
         diversify() searches.  Returns a handle (n_items, row_ptr -- S's own --, dv_col, dv_abs, nnz) on the device; it belongs to

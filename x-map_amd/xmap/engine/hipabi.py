@@ -21,6 +21,9 @@ ERR_HIP, ERR_ARG, ERR_OVERFLOW, ERR_CAPACITY = -1, -2, -3, -4     # XMAP_ERR_* o
 TOPN_KEEP_HELD = 1        # XMAP_TOPN_KEEP_HELD: flag of xmap_topn_rows / xmap_ctx_recommend
 AUDIENCE_KEEP_HOLDERS = 1 # XMAP_AUDIENCE_KEEP_HOLDERS: flag of xmap_audience_rows / xmap_ctx_audience
 SRC_RESIDENT, SRC_FOLDIN, SRC_ITEM_FOLDIN = 0, 1, 2      # XMAP_SRC_*: source of xmap_ctx_recommend_filtered / xmap_ctx_audience_filtered
+GROUP_MEAN, GROUP_MIN, GROUP_MAX = 0, 1, 2      # XMAP_GROUP_*: `how` of xmap_group_topn_rows / xmap_ctx_recommend_group
+GROUP_MAX_MEMBERS = 64    # XMAP_GROUP_MAX_MEMBERS: members of one group
+GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
 EXPLAIN_MAX_EV, EXPLAIN_MAX_SRC = 16, 8      # evidence entries per pair / source positions per entry of xmap_explain_*
@@ -113,6 +116,7 @@ EXPORTS = [
     "xmap_ctx_item_foldin_audience", "xmap_ctx_item_foldin_predict", "xmap_ctx_item_foldin_recommend",
     "xmap_topn_rows_filtered", "xmap_audience_rows_filtered", "xmap_ctx_recommend_filtered", "xmap_ctx_audience_filtered",
     "xmap_div_index", "xmap_diversify_rows", "xmap_ctx_recommend_diverse",
+    "xmap_group_topn_rows", "xmap_ctx_recommend_group",
 ]
 
 if not os.path.exists(LIB_PATH):

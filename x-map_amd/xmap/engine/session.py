@@ -731,6 +731,74 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     return res
 
 
+def _group_records(st, eng2, P, nb, item_avg, uidx, groups, alpha, n, how, veto, decay, keep_held, ctx, allow_items, exclude, min_score):
+    """what recommend_group and recommend_group_profiles share: groups = [(gid, [uid*])*] over the users of P (uidx: uid -> user
+    index of P; an unknown uid stays a member without rows) -> the LocalRDD of (gid, [(iid, plain, decayed, low_uid)*]) with .stats;
+    the decay table grows by the stats[2] loop of _topn_lists"""
+    import torch
+    from . import hipabi
+    idt, dev = st.idt, st.engine.dev
+    groups = [(gid, list(members)) for gid, members in (groups.collect() if hasattr(groups, "collect") else groups)]
+    for gid, members in groups:
+        if len(members) > hipabi.GROUP_MAX_MEMBERS:
+            raise ValueError("group %r has %d members; the device aggregation takes up to %d" % (gid, len(members), hipabi.GROUP_MAX_MEMBERS))
+    gids = [gid for gid, _ in groups]
+    ptr = np.zeros(len(groups) + 1, np.int64)
+    np.cumsum([len(m) for _, m in groups], out=ptr[1:])
+    users = np.fromiter((uidx.get(uid, -1) for _, m in groups for uid in m), np.int32, int(ptr[-1]))
+    d_ptr, d_user = torch.from_numpy(ptr).to(dev), torch.from_numpy(users).to(dev)
+    rules = _eligibility(dev, gids, idt.iidx, len(idt.iids), allow_items, exclude, min_score)
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        out = eng2.group_topn(P, nb, d_ptr, d_user, item_avg, wtab, int(n), how, veto, 1 if decay else 0, keep_held, **rules)
+        if out[5][2] <= n_w:
+            break
+        n_w = out[5][2]
+    cnt, item, plain, decayed, low = [x.cpu().numpy() for x in out[:5]]
+    iids = idt.iids
+    res = LocalRDD([(gid, [(iids[item[g, t]], float(plain[g, t]), float(decayed[g, t]), members[low[g, t]]) for t in range(cnt[g])])
+                    for g, (gid, members) in enumerate(groups)], ctx)
+    res.stats = out[5]
+    return res
+
+
+def recommend_group(alterEgoRDD, groups, cap, keep, alpha, n, how="mean", veto=None, decay=False, keep_held=False, neighbors=None,
+                    allow_items=None, exclude=None, min_score=None):
+    """ONE list for several users -- a household, a party, a shared account -- on the device (Engine.group_topn): the set-up of
+    recommend_topn, then for every (gid, [uid*]) of `groups` the n (1..64) best items by the aggregate of the members' unrounded
+    predictions: how = "mean", "min" (least misery) or "max" (most pleasure).  Candidates are the items at least one member's rows
+    give evidence for; a member without evidence for one predicts the item average (as the prediction itself does); items ANY member
+    holds are left out unless keep_held.  veto: an item leaves if some member's score is below it ("average without misery").  A
+    member listed twice counts twice; a uid the train set does not know stays a member without rows; at most 64 members.  Returns a
+    LocalRDD of (gid, [(iid, plain, decayed, low_uid)*]) in the order of `groups` -- low_uid = the member who likes the item least,
+    the first such in list order -- with .stats (the eight of Engine.group_topn), .sim_pairs and .item_info.  allow_items, exclude =
+    {gid: iids}, min_score (on the aggregate): the eligibility rules of recommend_topn."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_group")
+    idt = st.idt
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    res = _group_records(st, eng2, P, nb, item_avg, uidx, groups, alpha, n, how, veto, decay, keep_held, getattr(groups, "ctx", None),
+                         allow_items, exclude, min_score)
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
+def recommend_group_profiles(alterEgoRDD, profiles, groups, cap, keep, alpha, n, how="mean", veto=None, decay=False, keep_held=False,
+                             neighbors=None, allow_items=None, exclude=None, min_score=None):
+    """recommend_group for members that are not rows of the train set -- a party of guests nobody trained on: `profiles` as
+    recommend_topn_profiles takes them (folded in with the replacement map behind alterEgoRDD), and the uids of `groups` name
+    profiles of that batch; a uid without a profile stays a member without rows.  Returns the LocalRDD of recommend_group, with
+    .unknown_items and .counts as recommend_topn_profiles."""
+    _no_fold_in(alterEgoRDD, "recommend_group_profiles")
+    st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_group_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    res = _group_records(st, eng2, F, nb, item_avg, index, groups, alpha, n, how, veto, decay, keep_held, getattr(groups, "ctx", None),
+                         allow_items, exclude, min_score)
+    res.unknown_items, res.counts = unknown, F.counts
+    _tail_dicts(res, st, S, nb)
+    return res
+
+
 def recommend_audience(alterEgoRDD, items, cap, keep, alpha, n, decay=False, keep_holders=False, neighbors=None, allow_users=None,
                        exclude=None, min_score=None):
     """The audience of an item on the device from an AlterEgoRDD handle -- recommend_topn the other way round: the set-up of
