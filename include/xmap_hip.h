@@ -75,6 +75,13 @@ int xmap_debug_arena_call(void *stream, int64_t bytes, int fail);
 /* exclusive prefix sum of n int64 values; out[n] receives the total; *h_total (may be NULL) too (syncs). */
 int xmap_exclusive_scan_i64(void *stream, const int64_t *in, int64_t *out, int64_t n, int64_t *h_total);
 int xmap_exclusive_scan_i32_to_i64(void *stream, const int32_t *in, int64_t *out, int64_t n, int64_t *h_total);
+/* Two int32 arrays of one length scanned in the same launches: out_a = exclusive scan of in_a (a_plus_b != 0: of in_a + in_b,
+ * added up in 64 bits), out_b = exclusive scan of in_b; out_a[n] / out_b[n] the totals, h_totals [2] (host, may be NULL) too
+ * (syncs).  The scans take two launches while the array has at most xmap_scan_self_tiles() tiles of 2048 values (every block
+ * of the second launch adds up the tile sums in front of it), three beyond that; no block ever waits for another. */
+int xmap_exclusive_scan2_i32_to_i64(void *stream, const int32_t *in_a, const int32_t *in_b, int32_t a_plus_b, int64_t *out_a,
+                                    int64_t *out_b, int64_t n, int64_t *h_totals);
+int xmap_scan_self_tiles(void);
 
 /* ---- stage A: baseliner_calculate_sim_pipeline (utils/assist.py:66-77) ------------------- */
 
@@ -244,6 +251,20 @@ int xmap_sim3_plan(void *stream, const xmap_ratings *R, int32_t slot_target, con
                    const int32_t *ctl, int32_t *Q, int32_t *C, uint8_t *small, uint64_t *Wp, int32_t *Qcat /*[5 I]*/,
                    int64_t *uq_ptr /*[5 I + 1]*/, int64_t *uc_ptr /*[I + 1]*/, int32_t dups, int32_t *uq_item, int32_t *uq_q /*[4 cap_light]*/,
                    int32_t *uc_item, int32_t *uc_c, int64_t cap_light, int64_t cap_heavy, int64_t *h_out /*[10], host*/);
+/* The same in two halves, for a caller that has work for the device while the host waits: xmap_sim3_plan_begin queues the plan
+ * kernels, the copy of the ten counts into a pinned block (one per thread and device, reused) and an event behind it;
+ * xmap_sim3_plan_wait waits for that event only -- not for what was queued on the stream since -- and returns the counts
+ * and the checks of xmap_sim3_plan.  One begin, then its wait, per thread and device: a begin whose wait never came is dropped
+ * by the next begin (after its copy has landed); a wait without a begin is refused. */
+int xmap_sim3_plan_begin(void *stream, const xmap_ratings *R, int32_t slot_target, const int64_t *pre, const int32_t *hid,
+                         const int32_t *ctl, int32_t *Q, int32_t *C, uint8_t *small, uint64_t *Wp, int32_t *Qcat /*[5 I]*/,
+                         int64_t *uq_ptr /*[5 I + 1]*/, int64_t *uc_ptr /*[I + 1]*/, int32_t dups, int32_t *uq_item, int32_t *uq_q /*[4 cap_light]*/,
+                         int32_t *uc_item, int32_t *uc_c, int64_t cap_light, int64_t cap_heavy);
+int xmap_sim3_plan_wait(int64_t cap_light, int64_t cap_heavy, int64_t *h_out /*[10], host*/);
+/* The read of xmap_sim2_pairs' d_counters [6] (flags, kept / evaluated pairs) the same way: begin after the pair kernels, then
+ * whatever does not need the counts (xmap_sim3_mircount), then wait. */
+int xmap_sim3_counters_begin(void *stream, const int64_t *d_counters /*[6]*/);
+int xmap_sim3_counters_wait(int64_t *h_out /*[6], host*/);
 /* mir[j] = entries of a half COO whose second index is j, i.e. the mirrored entries row j gets (skip_self: an entry pairing a
  * row with itself has none).  Three coalesced passes over the partner column (bucket histogram, scatter, LDS windows) instead
  * of the device atomic per kept pair the pair kernels used to issue: those 2.65e7 atomics per pass were what the class

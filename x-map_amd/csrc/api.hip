@@ -269,6 +269,8 @@ struct TriResult {
 
 // layout -> plan(slot_target) -> pairs (again with smaller partitions after a table overflow, with more slack after a COO
 // overflow; one host wait per attempt) -> mirrored counts -> mirror.  tmp: the pass's scratch, the caller's to release.
+// The two host waits do not drain the stream (the order of Engine.item_sim_tri, xmap/engine/device.py): the profile copy's flag
+// pass is queued behind the first plan's read-back, the mirrored counts behind the read-back of the pair kernels' counters.
 static int tri_pass(hipStream_t st, const TriPass &J, Pool &tmp, TriResult &O) {
 #define T_ALLOC(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), st))
 #define T_ALLOCZ(ptr, n) XM_TRY(dalloc(tmp, &(ptr), (size_t)(n), st, true))
@@ -291,7 +293,7 @@ static int tri_pass(hipStream_t st, const TriPass &J, Pool &tmp, TriResult &O) {
     T_ALLOC(hist, U + 2); T_ALLOC(pre, U + 3); T_ALLOC(ctl, 4); T_ALLOC(hid, i1); T_ALLOCZ(hlist, 1024);
     T_ALLOC(ub_key, n1); T_ALLOC(ub, (wide ? 2 : 1) * n1); T_ALLOC(rcrec, 2 * n1); T_ALLOC(Wp, i1);
     T_ALLOC(srec, rw * n1); T_ALLOC(buf_a, rw * n1); T_ALLOC(buf_b, rw * n1);
-    XM_TRY(xmap_sim3_layout(st, &R, (int64_t *)R.item_ptr, J.rating64, J.ch_min, XMAP_LAYOUT_RECORDS | XMAP_LAYOUT_STATS | XMAP_LAYOUT_UB_FLAGS,
+    XM_TRY(xmap_sim3_layout(st, &R, (int64_t *)R.item_ptr, J.rating64, J.ch_min, XMAP_LAYOUT_RECORDS | XMAP_LAYOUT_STATS,
                             0, I, cnt, O.u_avg, O.u_norm, hist, pre, ctl, hid, hlist, ub_key, ub, srec, buf_a, buf_b, rcrec, Wp, O.info,
                             O.norms, nullptr));
     int32_t *Q, *Cc, *Qcat, *uq_item = nullptr, *uq_q = nullptr, *uc_item = nullptr, *uc_c = nullptr;
@@ -302,13 +304,18 @@ static int tri_pass(hipStream_t st, const TriPass &J, Pool &tmp, TriResult &O) {
     int slot_target = 768;          // (75 % load of the 1024-slot tables; device.py: SLOT_TARGET / CH_MIN)
     double coo_slack = 1.0;
     int64_t hc[10];
-    auto plan = [&](int target) -> int {
+    auto plan = [&](int target, bool ub_flags) -> int {
         const int64_t cap_light = J.half_contrib / target + I + 1, cap_heavy = nnz / J.ch_min + 1025;
         T_ALLOC(uq_item, cap_light); T_ALLOC(uq_q, 4 * cap_light); T_ALLOC(uc_item, cap_heavy); T_ALLOC(uc_c, cap_heavy);
-        return xmap_sim3_plan(st, &R, target, pre, hid, ctl, Q, Cc, small, Wp, Qcat, uq_ptr, uc_ptr, J.dups, uq_item, uq_q, uc_item, uc_c,
-                              cap_light, cap_heavy, hc);
+        XM_TRY(xmap_sim3_plan_begin(st, &R, target, pre, hid, ctl, Q, Cc, small, Wp, Qcat, uq_ptr, uc_ptr, J.dups, uq_item, uq_q, uc_item, uc_c,
+                                    cap_light, cap_heavy));
+        // the profile copy's flags (the plan reads none of them): once, under the first plan's wait
+        if (ub_flags && !wide)
+            XM_TRY(xmap_sim3_layout(st, &R, (int64_t *)R.item_ptr, J.rating64, J.ch_min, XMAP_LAYOUT_UB_FLAGS, 0, I, cnt, O.u_avg, O.u_norm, hist,
+                                    pre, ctl, hid, hlist, ub_key, ub, srec, buf_a, buf_b, rcrec, Wp, O.info, O.norms, nullptr));
+        return xmap_sim3_plan_wait(cap_light, cap_heavy, hc);
     };
-    XM_TRY(plan(slot_target));
+    XM_TRY(plan(slot_target, true));
     // all phases in one call: the heavy rows run on a side stream next to the class launches of the light rows; own and
     // mirrored row counts apart (mir), kept / evaluated pairs summed on the device
     const int phases = XMAP_PAIRS_RESET | XMAP_PAIRS_LIGHT | XMAP_PAIRS_MIRCOUNT | XMAP_PAIRS_SHARD_SUMS | XMAP_PAIRS_NO_MARKS |
@@ -333,12 +340,15 @@ static int tri_pass(hipStream_t st, const TriPass &J, Pool &tmp, TriResult &O) {
                                ctl, Cc, uc_ptr, uc_item, uc_c, (int32_t)n_hu, (int32_t)n_heavy, phases, hp_hi, hp_lo, hp_cnt, hp_mut, cap_coo, coo_i,
                                coo_j, coo_sim, coo_mutu, coo_nij, coo_aux, own, d_shards, d_cnt, mir));
         int64_t h_cnt[6];
-        XM_TRY(d2h(h_cnt, d_cnt, 6, st));
-        XM_HIP(hipStreamSynchronize(st));
+        int32_t *mir_part;
+        T_ALLOC(mir_part, cap_coo);
+        XM_TRY(xmap_sim3_counters_begin(st, d_cnt));
+        XM_TRY(xmap_sim3_mircount(st, I, cap_coo, coo_i, coo_j, d_shards, cap_coo, J.skip_self ? 1 : 0, mir_part, mir));
+        XM_TRY(xmap_sim3_counters_wait(h_cnt));
         if (h_cnt[2]) {                 // an LDS pair table overflowed: smaller partitions
             if (slot_target <= 32) { set_error("pair-table overflow"); return XMAP_ERR_OVERFLOW; }
             slot_target /= 2;
-            XM_TRY(plan(slot_target));
+            XM_TRY(plan(slot_target, false));
             continue;
         }
         if (h_cnt[3]) {                 // a half-COO shard overflowed: more slack
@@ -361,7 +371,6 @@ static int tri_pass(hipStream_t st, const TriPass &J, Pool &tmp, TriResult &O) {
     XM_TRY(dalloc(*J.mutu_pool, &O.mutu, (size_t)O.kept, st)); XM_TRY(dalloc(*J.csr_pool, &O.nij, (size_t)O.kept, st));
     if (J.aux) XM_TRY(dalloc(*J.csr_pool, &O.aux, (size_t)O.kept, st));
     T_ALLOC(fill, i1); T_ALLOC(tot, i1); T_ALLOC(mir_a, (J.aux ? 4 : 3) * nn); T_ALLOC(mir_b, (J.aux ? 4 : 3) * nn);
-    XM_TRY(xmap_sim3_mircount(st, I, cap_coo, coo_i, coo_j, d_shards, n, J.skip_self ? 1 : 0, mir_a, mir));
     return xmap_sim3_mirror(st, I, cap_coo, coo_i, coo_j, coo_sim, coo_mutu, coo_nij, d_shards, n, own, mir, tot, J.row_ptr, mptr, fill, mir_a,
                             mir_b, O.col, O.sim, O.mutu, O.nij, coo_aux, O.aux, 0, I);
 #undef T_ALLOC

@@ -49,6 +49,25 @@ struct XmScope {
     XmScope &operator=(const XmScope &) = delete;
 };
 #define XM_SCOPE(stream) xmap::XmScope xm_scope_((hipStream_t)(stream))
+// Read-backs that do not drain the stream (util.hip): post = copy `words` int64 from the device into the slot's pinned block
+// and record the slot's event behind it; take = wait for that event, *h = the block.  One post, then one take, per slot.
+constexpr int HW_SLOTS = 2, HW_WORDS = 16;
+constexpr int HW_PLAN = 0, HW_PAIRS = 1;        // the plan's counts (tri_layout.hip), the pair kernels' counters (tri_pairs.hip)
+struct HostWait { int dev; int64_t *h; hipEvent_t ev[HW_SLOTS]; bool pending[HW_SLOTS]; };
+HostWait *host_wait();
+int host_wait_post(hipStream_t st, int slot, const void *d_src, int words);
+int host_wait_take(int slot, const int64_t **h);
+// the small fills of one phase in one launch (util.hip): range y = words[y] 32-bit words at p[y] set to val[y]
+struct FillList {
+    enum { MAX = 8 };
+    void *p[MAX]; unsigned long long words[MAX]; unsigned val[MAX]; int n;
+    FillList() : n(0) {}
+    void add(void *ptr, size_t bytes, unsigned v = 0u) {
+        if (n >= MAX) { n = MAX + 1; return; }          // (fill_multi refuses the list)
+        p[n] = ptr; words[n] = bytes / 4; val[n] = v; n++;
+    }
+};
+int fill_multi(hipStream_t st, const FillList &F);
 // plan.hip: stable LSD radix sort of (key, value) pairs by the low `bits` bits of the key; tmp buffers of n entries
 int radix_sort_pairs(hipStream_t st, unsigned long long *keys, int *vals, unsigned long long *keys_tmp, int *vals_tmp, long long n,
                      int bits);

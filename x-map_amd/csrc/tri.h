@@ -57,12 +57,14 @@ constexpr int COO_SHARDS = 4096;
 // (skip_self) have none.  n_ranges ranges of range_cap slots, the first cur[r] of range r valid (cur == NULL: all of them).
 // part: range_cap * n_ranges ints of scratch.  Three passes (k_cbs_hist, k_cbs_scatter, k_cb_count), no atomic per entry.
 // (The layout counts the raters per item with it: the item column as one range.)
+// fills (or NULL): fills of the caller's that are due before the first kernel; they leave in one launch with the bucket counters'
 int mirror_counts(hipStream_t st, int n_items, long long range_cap, int n_ranges, const unsigned long long *cur, const int *coo_i,
-                  const int *coo_j, bool skip_self, int *part, int *counts);
+                  const int *coo_j, bool skip_self, int *part, int *counts, FillList *fills = nullptr);
 // tile sort, host side: geometry for K keys and M records (tilesort.h): tile measure 2^ts_log, key weight KW, T = NA * NB tiles
 void ts_geometry(int K, long long M, int ch, ts::Geo &G);
 // tables of one sort (arena temporaries of the calling entry point) + plan and chunk kernels
-int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr);
+// (fills: as for mirror_counts)
+int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr, FillList *fills = nullptr);
 // level B over 24-byte records: run by the layout (fp64 sort records) and the mirror (no sixth column), instantiated there
 extern template __global__ void ts::k_ts_bin<3, true, ts::RecLoader<3>>(ts::Geo, ts::RecLoader<3>, long long, unsigned long long *__restrict__);
 

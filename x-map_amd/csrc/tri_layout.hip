@@ -240,8 +240,10 @@ __device__ __forceinline__ void plan_item(int i, long long w, int I, const long 
     small[i] = (uint8_t)cls;
     Wp[i] = (unsigned long long)w;
     // the light units are listed class-major (largest tables first: their units run longest), so that each table
-    // class is one contiguous range of units: Qcat[rank][i] (zero-initialised) is what the unit scan runs over
-    Qcat[(size_t)class_rank(cls) * I + i] = q;
+    // class is one contiguous range of units: Qcat[rank][i] (zero in the other classes) is what the unit scan runs over
+    const int rank = class_rank(cls);
+#pragma unroll
+    for (int r = 0; r < N_CLASSES; r++) Qcat[(size_t)r * I + i] = (r == rank) ? q : 0;
 }
 
 __global__ __launch_bounds__(256) void k_plan2(int I, const long long *iptr, const RaterRec *rc, const long long *pre,
@@ -256,8 +258,17 @@ __global__ __launch_bounds__(256) void k_plan2(int I, const long long *iptr, con
 // what k_pair_tri needs to start, in one round trip
 __global__ __launch_bounds__(256) void k_fill_units2(int I, const long long *iptr, const int *Qcat, const long long *uq_ptr,
                                                      int *uq_item, int *uq_q, const int *C, const long long *uc_ptr, int *uc_item,
-                                                     int *uc_c, long long cap_light, long long cap_heavy) {
+                                                     int *uc_c, long long cap_light, long long cap_heavy, const int *ctl,
+                                                     long long *counts) {
     const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    // what the host reads back, in one block: {light units, heavy units, first unit of class rank 0..4, light units, CH, |H|}
+    // (both scans are complete: they ran in earlier launches)
+    if (counts && x == 0) {
+        for (int c = 0; c <= N_CLASSES; c++) counts[2 + c] = uq_ptr[(long long)c * I];
+        counts[0] = uq_ptr[(long long)N_CLASSES * I];
+        counts[1] = uc_ptr[I];
+        counts[8] = ctl[0]; counts[9] = ctl[1];
+    }
     if (x >= (long long)N_CLASSES * I) return;
     const int i = (int)(x % I);
     long long b = uq_ptr[x];
@@ -670,13 +681,22 @@ using namespace xmap;
 namespace {
 
 // rater-count histogram -> pre[v] = #items with fewer than v raters (partner bounds), ctl = {CH, |H|, -, -}, the heavy set hid / hlist
+void heavy_set_fills(FillList &F, int64_t n_users, int32_t *hist, int32_t *ctl) {
+    F.add(hist, sizeof(int32_t) * (size_t)(n_users + 2));
+    F.add(ctl, sizeof(int32_t), 0x7f7f7f7fu);                       // CH = 0x7f7f7f7f: "no heavy rows"
+    F.add(ctl + 1, 3 * sizeof(int32_t));
+}
+// filled: the caller has cleared hist and ctl already (heavy_set_fills in a launch of its own)
 int heavy_set(void *stream, int I, int64_t n_users, const int64_t *item_ptr, int32_t ch_min, int32_t *hist, int64_t *pre, int32_t *ctl,
-              int32_t *hid, int32_t *hlist) {
+              int32_t *hid, int32_t *hlist, bool filled = false) {
     hipStream_t st = (hipStream_t)stream;
     const int HB = (int)n_users + 2;
-    XM_HIP(hipMemsetAsync(hist, 0, sizeof(int32_t) * (size_t)HB, st));
-    XM_HIP(hipMemsetAsync(ctl, 0x7f, sizeof(int32_t), st));          // CH = 0x7f7f7f7f: "no heavy rows"
-    XM_HIP(hipMemsetAsync(ctl + 1, 0, 3 * sizeof(int32_t), st));
+    if (!filled) {
+        FillList F;
+        heavy_set_fills(F, n_users, hist, ctl);
+        int rc = fill_multi(st, F);
+        if (rc) return rc;
+    }
     if (I > 0) {
         k_hist<<<dim3((unsigned)((I + 256 * HIST_PER - 1) / (256 * HIST_PER))), dim3(256), 0, st>>>(I, (const long long *)item_ptr, HB, hist);
         XM_LAUNCH_CHECK();
@@ -713,8 +733,7 @@ int plan_rows(void *stream, const xmap_ratings *R, int32_t slot_target, const vo
     XM_ARG(slot_target > 0 && slot_target <= T_SLOTS);
     hipStream_t st = (hipStream_t)stream;
     const int I = R->n_items;
-    XM_HIP(hipMemsetAsync(Qcat, 0, sizeof(int32_t) * (size_t)N_CLASSES * (size_t)(I > 0 ? I : 1), st));
-    if (I > 0) {
+    if (I > 0) {            // (k_plan2 writes every class slot of every item: no fill of Qcat)
         k_plan2<<<dim3((unsigned)((I + 255) / 256)), dim3(256), 0, st>>>(
             I, (const long long *)R->item_ptr, (const RaterRec *)rc, (const long long *)pre, (int)R->n_users + 2, hid, ctl, slot_target, dups,
             Q, C, small, (unsigned long long *)Wp, Qcat);
@@ -823,45 +842,64 @@ int xmap_sim2_units(void *stream, int32_t n_items, const int64_t *item_ptr, cons
     if (n_items == 0) return XMAP_OK;
     k_fill_units2<<<dim3((unsigned)(((long long)N_CLASSES * n_items + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
         n_items, (const long long *)item_ptr, Qcat, (const long long *)uq_ptr, uq_item, uq_q, C, (const long long *)uc_ptr, uc_item, uc_c, 0x7fffffffffffffffLL,
-        0x7fffffffffffffffLL);
+        0x7fffffffffffffffLL, nullptr, nullptr);
     XM_LAUNCH_CHECK();
     return XMAP_OK;
 }
 
-/* xmap_sim2_plan + xmap_sim2_units with ONE synchronisation (include/xmap_hip.h): the scans leave their totals on the device */
-int xmap_sim3_plan(void *stream, const xmap_ratings *R, int32_t slot_target, const int64_t *pre, const int32_t *hid,
-                   const int32_t *ctl, int32_t *Q, int32_t *C, uint8_t *small, uint64_t *Wp, int32_t *Qcat, int64_t *uq_ptr,
-                   int64_t *uc_ptr, int32_t dups, int32_t *uq_item, int32_t *uq_q, int32_t *uc_item, int32_t *uc_c,
-                   int64_t cap_light, int64_t cap_heavy, int64_t *h_out) {
+/* xmap_sim2_plan + xmap_sim2_units with ONE host wait (include/xmap_hip.h): the scans leave their totals on the device, the unit
+ * kernel gathers everything the host reads into one block, and that block travels to pinned memory with an event behind it.
+ * begin queues all of it; wait takes the event.  What the caller queues in between runs while the host waits and reads. */
+int xmap_sim3_plan_begin(void *stream, const xmap_ratings *R, int32_t slot_target, const int64_t *pre, const int32_t *hid,
+                         const int32_t *ctl, int32_t *Q, int32_t *C, uint8_t *small, uint64_t *Wp, int32_t *Qcat, int64_t *uq_ptr,
+                         int64_t *uc_ptr, int32_t dups, int32_t *uq_item, int32_t *uq_q, int32_t *uc_item, int32_t *uc_c,
+                         int64_t cap_light, int64_t cap_heavy) {
     XM_SCOPE(stream);
-    XM_ARG(R && Wp && pre && hid && ctl && Q && C && small && Qcat && uq_ptr && uc_ptr && h_out);
+    XM_ARG(R && Wp && pre && hid && ctl && Q && C && small && Qcat && uq_ptr && uc_ptr);
     XM_ARG(uq_item && uq_q && uc_item && uc_c && cap_light >= 0 && cap_heavy >= 0);
     hipStream_t st = (hipStream_t)stream;
     const int I = R->n_items;
-    for (int c = 0; c < 10; c++) h_out[c] = 0;
     int rcode = plan_rows(stream, R, slot_target, nullptr, pre, hid, ctl, Q, C, small, Wp, Qcat, uq_ptr, uc_ptr, dups, nullptr, nullptr);
     if (rcode) return rcode;
-    if (I > 0) {
-        k_fill_units2<<<dim3((unsigned)(((long long)N_CLASSES * I + 255) / 256)), dim3(256), 0, st>>>(
-            I, (const long long *)R->item_ptr, Qcat, (const long long *)uq_ptr, uq_item, uq_q, C, (const long long *)uc_ptr, uc_item, uc_c,
-            cap_light, cap_heavy);
-        XM_LAUNCH_CHECK();
-        // class boundaries uq_ptr[c I], c = 0..5 (the last one is the total), the heavy units' total, {CH, |H|}
-        XM_HIP(hipMemcpy2DAsync(&h_out[2], sizeof(int64_t), uq_ptr, sizeof(int64_t) * (size_t)I, sizeof(int64_t), N_CLASSES + 1,
-                                hipMemcpyDeviceToHost, st));
-        XM_HIP(hipMemcpyAsync(&h_out[1], uc_ptr + I, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    }
-    int32_t h_ctl[2] = {0, 0};
-    rcode = read_heavy_ctl(st, ctl, h_ctl);
-    h_out[0] = h_out[2 + N_CLASSES];
-    h_out[8] = h_ctl[0]; h_out[9] = h_ctl[1];
+    long long *counts = nullptr;
+    XM_HIP(xm_malloc_async((void **)&counts, sizeof(long long) * 10, st));
+    // (no items: one block that only gathers the counts -- both scans have left their zero totals)
+    const long long threads = (long long)N_CLASSES * I > 0 ? (long long)N_CLASSES * I : 1;
+    k_fill_units2<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
+        I, (const long long *)R->item_ptr, Qcat, (const long long *)uq_ptr, uq_item, uq_q, C, (const long long *)uc_ptr, uc_item, uc_c,
+        cap_light, cap_heavy, ctl, counts);
+    XM_LAUNCH_CHECK();
+    return host_wait_post(st, HW_PLAN, counts, 10);
+}
+
+int xmap_sim3_plan_wait(int64_t cap_light, int64_t cap_heavy, int64_t *h_out) {
+    XM_ARG(h_out);
+    const int64_t *h = nullptr;
+    int rcode = host_wait_take(HW_PLAN, &h);
     if (rcode) return rcode;
+    for (int c = 0; c < 10; c++) h_out[c] = h[c];
+    if (h_out[9] > HMAX) {
+        set_error("heavy set larger than %d", HMAX);
+        return XMAP_ERR_OVERFLOW;
+    }
     if (h_out[0] > cap_light || h_out[1] > cap_heavy) {
         set_error("unit arrays too small: %lld light / %lld heavy units, room for %lld / %lld", (long long)h_out[0], (long long)h_out[1],
                   (long long)cap_light, (long long)cap_heavy);
         return XMAP_ERR_CAPACITY;
     }
     return XMAP_OK;
+}
+
+int xmap_sim3_plan(void *stream, const xmap_ratings *R, int32_t slot_target, const int64_t *pre, const int32_t *hid,
+                   const int32_t *ctl, int32_t *Q, int32_t *C, uint8_t *small, uint64_t *Wp, int32_t *Qcat, int64_t *uq_ptr,
+                   int64_t *uc_ptr, int32_t dups, int32_t *uq_item, int32_t *uq_q, int32_t *uc_item, int32_t *uc_c,
+                   int64_t cap_light, int64_t cap_heavy, int64_t *h_out) {
+    XM_ARG(h_out);
+    for (int c = 0; c < 10; c++) h_out[c] = 0;
+    int rcode = xmap_sim3_plan_begin(stream, R, slot_target, pre, hid, ctl, Q, C, small, Wp, Qcat, uq_ptr, uc_ptr, dups, uq_item, uq_q, uc_item,
+                                     uc_c, cap_light, cap_heavy);
+    if (rcode) return rcode;
+    return xmap_sim3_plan_wait(cap_light, cap_heavy, h_out);
 }
 
 /* Round-3 layout of stage A (one transposition per pass): see the declarations in include/xmap_hip.h. */
@@ -881,17 +919,39 @@ int xmap_sim3_layout(void *stream, const xmap_ratings *R, int64_t *item_ptr, con
     const bool wide = rating64 != nullptr;
     const size_t In = (size_t)(I > 0 ? I : 1);
     int rcode = XMAP_OK;
+    // the big items' lists (STATS); taken here so that their counters are cleared with the other fills of the pass
+    const bool stats = (phases & XMAP_LAYOUT_STATS) && stats_hi > stats_lo;
+    BigList B;
+    bool b_cleared = false;
+    if (stats) {
+        B.chunk_cap = nnz / STAT_CHK + nnz / STAT_BIG + 2;
+        B.item_cap = nnz / STAT_BIG + 2;
+        XM_HIP(xm_malloc_async((void **)&B.counters, 2 * sizeof(unsigned), st));
+        XM_HIP(xm_malloc_async((void **)&B.chunks, sizeof(int2) * (size_t)B.chunk_cap, st));
+        XM_HIP(xm_malloc_async((void **)&B.items, sizeof(int4) * (size_t)B.item_cap, st));
+        XM_HIP(xm_malloc_async((void **)&B.part, sizeof(double) * ITEM_PART * (size_t)B.chunk_cap, st));
+    }
     if (phases & XMAP_LAYOUT_RECORDS) {
+        // every small fill of the pass in one launch: the rater counts, the histogram and ctl of the heavy set, W+ (summed by the
+        // tile sort's last level), the big items' counters (+ the bucket counters of the partitioned count)
+        FillList F;
+        F.add(cnt, sizeof(int32_t) * In);
+        heavy_set_fills(F, R->n_users, hist, ctl);
+        F.add(Wp, sizeof(uint64_t) * In);
+        if (stats) { F.add(B.counters, 2 * sizeof(unsigned)); b_cleared = true; }
         // raters per item -> item_ptr
-        XM_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * In, st));
         const char *cb_env = getenv("XMAP_COUNT_PART_MIN");          // (tests force the partitioned count on small inputs)
         const long long cb_min = cb_env ? atoll(cb_env) : 2000000ll;
         if (nnz >= cb_min && I > 0) {         // partitioned count (k_cbs_*, k_cb_count): the item column as one range, through bufA
-            rcode = mirror_counts(st, I, nnz, 1, nullptr, nullptr, R->user_item, false, (int *)bufA, cnt);        // (free until the tile sort)
+            rcode = mirror_counts(st, I, nnz, 1, nullptr, nullptr, R->user_item, false, (int *)bufA, cnt, &F);        // (free until the tile sort)
             if (rcode) return rcode;
-        } else if (nnz > 0) {
-            k_count3<<<dim3((unsigned)((nnz + CNT_CHUNK - 1) / CNT_CHUNK)), dim3(256), 0, st>>>(nnz, R->user_item, cnt);
-            XM_LAUNCH_CHECK();
+        } else {
+            rcode = fill_multi(st, F);
+            if (rcode) return rcode;
+            if (nnz > 0) {
+                k_count3<<<dim3((unsigned)((nnz + CNT_CHUNK - 1) / CNT_CHUNK)), dim3(256), 0, st>>>(nnz, R->user_item, cnt);
+                XM_LAUNCH_CHECK();
+            }
         }
         rcode = xmap_exclusive_scan_i32_to_i64(stream, cnt, item_ptr, I, nullptr);
         if (rcode) return rcode;
@@ -900,7 +960,7 @@ int xmap_sim3_layout(void *stream, const xmap_ratings *R, int64_t *item_ptr, con
             if (rcode) return rcode;
         }
         // rater-count histogram -> partner bounds, heavy set (as xmap_sim2_layout)
-        rcode = heavy_set(stream, I, R->n_users, item_ptr, ch_min, hist, pre, ctl, hid, hlist);
+        rcode = heavy_set(stream, I, R->n_users, item_ptr, ch_min, hist, pre, ctl, hid, hlist, true);
         if (rcode) return rcode;
         // sorted profiles + sort records (no mutuality flags yet)
         if (R->n_users > 0 && nnz > 0) {
@@ -910,8 +970,7 @@ int xmap_sim3_layout(void *stream, const xmap_ratings *R, int64_t *item_ptr, con
                 (unsigned long long *)ub_key, ub, (unsigned long long *)srec);
             XM_LAUNCH_CHECK();
         }
-        // sort records -> rater records in item order, W+
-        XM_HIP(hipMemsetAsync(Wp, 0, sizeof(uint64_t) * In, st));
+        // sort records -> rater records in item order, W+ (cleared above)
         if (nnz > 0 && I > 0) {
             ts::Geo G;
             ts_geometry(I, nnz, wide ? ts::Chunk<3>::CH : ts::Chunk<2>::CH, G);
@@ -923,15 +982,8 @@ int xmap_sim3_layout(void *stream, const xmap_ratings *R, int64_t *item_ptr, con
         }
     }
     // item statistics of [stats_lo, stats_hi) from the rater records (+ those records' mutuality flags), big items in chunks
-    if ((phases & XMAP_LAYOUT_STATS) && stats_hi > stats_lo) {
-        BigList B;
-        B.chunk_cap = nnz / STAT_CHK + nnz / STAT_BIG + 2;
-        B.item_cap = nnz / STAT_BIG + 2;
-        XM_HIP(xm_malloc_async((void **)&B.counters, 2 * sizeof(unsigned), st));
-        XM_HIP(xm_malloc_async((void **)&B.chunks, sizeof(int2) * (size_t)B.chunk_cap, st));
-        XM_HIP(xm_malloc_async((void **)&B.items, sizeof(int4) * (size_t)B.item_cap, st));
-        XM_HIP(xm_malloc_async((void **)&B.part, sizeof(double) * ITEM_PART * (size_t)B.chunk_cap, st));
-        XM_HIP(hipMemsetAsync(B.counters, 0, 2 * sizeof(unsigned), st));
+    if (stats) {
+        if (!b_cleared) XM_HIP(hipMemsetAsync(B.counters, 0, 2 * sizeof(unsigned), st));
         rcode = wide ? item_stats3(st, I, stats_lo, stats_hi, item_ptr, RcWideSrc{(const RaterRecWide *)rc}, info, norms, B)
                      : item_stats3(st, I, stats_lo, stats_hi, item_ptr, RcSrc{(RaterRec *)rc, u_avg}, info, norms, B);
         if (rcode) return rcode;

@@ -244,11 +244,8 @@ __global__ __launch_bounds__(CB_T) void k_cbs_scatter(long long range_cap, int n
 }
 
 // ---- the mirror (round 3): own half written in runs, mirrored half through the tile sort --------------------------------------
-// Row i of the CSR = [the pairs row i computed itself (own[i]) | the pairs computed in lighter rows (mir[i])].
-__global__ __launch_bounds__(256) void k_row_totals(int I, const int *own, const int *mir, int *tot) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < I) tot[i] = own[i] + mir[i];
-}
+// Row i of the CSR = [the pairs row i computed itself (own[i]) | the pairs computed in lighter rows (mir[i])]; the row totals
+// own + mir are added up inside the scan that makes row_ptr (xmap_exclusive_scan2_i32_to_i64).
 
 // level-A loader of the mirror: the half COO (SoA, cut into shards that are filled from their start) as 24-byte records
 // keyed by the heavier item; its chunks are listed from the shard cursors (k_coo_chunks), so every slot of a chunk is a
@@ -479,7 +476,7 @@ void ts_geometry(int K, long long M, int ch, ts::Geo &G) {
     }
 }
 
-int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr) {
+int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr, FillList *fills) {
     G.ptr = ptr;
     G.clist_cap = G.M / G.ch + G.NA + 1;
     G.slist_cap = G.M / ts::SL + (G.M >> G.ts_log) + 2;
@@ -493,8 +490,12 @@ int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr) {
     G.curA = z; G.curB = z + G.NA; G.counters = (unsigned *)(z + G.NA + 2 * (size_t)G.T);
     XM_HIP(xm_malloc_async((void **)&G.clist, sizeof(int2) * (size_t)G.clist_cap, st));
     XM_HIP(xm_malloc_async((void **)&G.slist, sizeof(int2) * (size_t)G.slist_cap, st));
-    XM_HIP(hipMemsetAsync(z, 0, sizeof(unsigned long long) * nz, st));
-    XM_HIP(hipMemsetAsync(G.tile_large, 0xff, sizeof(int) * (size_t)G.T, st));
+    FillList own;
+    FillList &F = fills ? *fills : own;
+    F.add(z, sizeof(unsigned long long) * nz);
+    F.add(G.tile_large, sizeof(int) * (size_t)G.T, 0xffffffffu);
+    int rcode = fill_multi(st, F);
+    if (rcode) return rcode;
     ts::k_ts_plan<<<dim3((unsigned)((G.K + 255) / 256)), dim3(256), 0, st>>>(G);
     XM_LAUNCH_CHECK();
     ts::k_ts_chunks<<<dim3((unsigned)((G.NA + 255) / 256)), dim3(256), 0, st>>>(G);
@@ -527,8 +528,10 @@ int mirror_levels(hipStream_t st, const ts::Geo &G, int64_t coo_cap, const int32
 }  // namespace
 
 int mirror_counts(hipStream_t st, int n_items, long long range_cap, int n_ranges, const unsigned long long *cur, const int *coo_i,
-                  const int *coo_j, bool skip_self, int *part, int *counts) {
-    if (n_items <= 0 || range_cap <= 0 || n_ranges <= 0) return XMAP_OK;
+                  const int *coo_j, bool skip_self, int *part, int *counts, FillList *fills) {
+    FillList own;
+    FillList &F = fills ? *fills : own;
+    if (n_items <= 0 || range_cap <= 0 || n_ranges <= 0) return fill_multi(st, F);
     int sh = 0;
     while (((long long)(n_items - 1) >> sh) >= CB_MAX) sh++;
     unsigned *bcnt = nullptr, *bcur = nullptr;
@@ -536,7 +539,9 @@ int mirror_counts(hipStream_t st, int n_items, long long range_cap, int n_ranges
     XM_HIP(xm_malloc_async((void **)&bcnt, sizeof(unsigned) * CB_MAX, st));
     XM_HIP(xm_malloc_async((void **)&bcur, sizeof(unsigned) * CB_MAX, st));
     XM_HIP(xm_malloc_async((void **)&bptr, sizeof(long long) * (CB_MAX + 1), st));
-    XM_HIP(hipMemsetAsync(bcnt, 0, sizeof(unsigned) * CB_MAX, st));
+    F.add(bcnt, sizeof(unsigned) * CB_MAX);
+    int rcode = fill_multi(st, F);
+    if (rcode) return rcode;
     const long long segs = (long long)n_ranges * ((range_cap + CB_CHUNK - 1) / CB_CHUNK);
     const dim3 g((unsigned)((segs + CB_SPB - 1) / CB_SPB));
     (skip_self ? k_cbs_hist<true> : k_cbs_hist<false>)<<<g, dim3(CB_T), 0, st>>>(range_cap, n_ranges, cur, coo_i, coo_j, sh, bcnt);
@@ -585,10 +590,11 @@ int xmap_sim3_mircount(void *stream, int32_t n_items, int64_t coo_cap, const int
     XM_ARG(d_shards ? (coo_cap >= COO_SHARDS) : (n_pairs <= coo_cap));
     hipStream_t st = (hipStream_t)stream;
     if (n_items == 0) return XMAP_OK;
-    XM_HIP(hipMemsetAsync(mir, 0, sizeof(int32_t) * (size_t)n_items, st));
-    if (n_pairs == 0 || coo_cap == 0) return XMAP_OK;
+    FillList F;            // the counts and the bucket counters are cleared in one launch
+    F.add(mir, sizeof(int32_t) * (size_t)n_items);
+    if (n_pairs == 0 || coo_cap == 0) return fill_multi(st, F);
     return mirror_counts(st, n_items, d_shards ? coo_cap / COO_SHARDS : n_pairs, d_shards ? COO_SHARDS : 1,
-                         (const unsigned long long *)d_shards, coo_i, coo_j, skip_self != 0, (int *)scratch, mir);
+                         (const unsigned long long *)d_shards, coo_i, coo_j, skip_self != 0, (int *)scratch, mir, &F);
 }
 
 int xmap_sim3_mirror(void *stream, int32_t n_items, int64_t coo_cap, const int32_t *coo_i, const int32_t *coo_j,
@@ -604,20 +610,12 @@ int xmap_sim3_mirror(void *stream, int32_t n_items, int64_t coo_cap, const int32
     XM_ARG((coo_aux != nullptr) == (aux != nullptr));
     hipStream_t st = (hipStream_t)stream;
     const int I = n_items;
-    if (I > 0) {
-        k_row_totals<<<dim3((unsigned)((I + 255) / 256)), dim3(256), 0, st>>>(I, own, mir, tot);
-        XM_LAUNCH_CHECK();
-    }
-    int rcode = xmap_exclusive_scan_i32_to_i64(stream, tot, row_ptr, I, nullptr);
-    if (rcode) return rcode;
-    rcode = xmap_exclusive_scan_i32_to_i64(stream, mir, mptr, I, nullptr);
+    // row_ptr = scan of own + mir (the row totals are added up inside the scan: tot stays unused), mptr = scan of mir: one pass
+    int rcode = xmap_exclusive_scan2_i32_to_i64(stream, own, mir, 1, row_ptr, mptr, I, nullptr);
     if (rcode) return rcode;
     if (n_pairs == 0 || I == 0 || coo_cap == 0) return XMAP_OK;
-    XM_HIP(hipMemsetAsync(fill, 0, sizeof(int32_t) * (size_t)I, st));
     ts::Geo G;
     ts_geometry(I, n_pairs, coo_aux ? ts::Chunk<4>::CH : ts::Chunk<3>::CH, G);      // (n_pairs bounds the mirrored records: a self pair has none)
-    rcode = ts_prepare(st, G, (const long long *)mptr);
-    if (rcode) return rcode;
     // the COO's chunks: from the shard cursors of the pair kernels, or one range of n_pairs records
     static_assert(ts::Chunk<3>::CH <= ts::Chunk<4>::CH && ts::Chunk<4>::CH % ts::Chunk<3>::CH == 0, "chunk lists by the narrow record width");
     const int n_shards = d_shards ? COO_SHARDS : 1;
@@ -627,7 +625,11 @@ int xmap_sim3_mirror(void *stream, int32_t n_items, int64_t coo_cap, const int32
     unsigned *n_chunks = nullptr;
     XM_HIP(xm_malloc_async((void **)&chunks, sizeof(longlong2) * (size_t)chunk_cap, st));
     XM_HIP(xm_malloc_async((void **)&n_chunks, sizeof(unsigned), st));
-    XM_HIP(hipMemsetAsync(n_chunks, 0, sizeof(unsigned), st));
+    FillList F;            // the row cursors, the chunk counter and the sort's tables are cleared in one launch
+    F.add(fill, sizeof(int32_t) * (size_t)I);
+    F.add(n_chunks, sizeof(unsigned));
+    rcode = ts_prepare(st, G, (const long long *)mptr, &F);
+    if (rcode) return rcode;
     k_coo_chunks<<<dim3((unsigned)((n_shards + 255) / 256)), dim3(256), 0, st>>>(n_shards, shard_cap, (const unsigned long long *)d_shards,
                                                                                  n_pairs, chunks, n_chunks, chunk_cap);
     XM_LAUNCH_CHECK();

@@ -678,11 +678,12 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
     // exact cosine: the adjusted-cosine kernels (double-double dot product) with a zero user average and the plain norms
     const bool exact_cos = method == XMAP_COSINE_EXACT;
     const double *nrm = norms + (method == XMAP_ADJUST_COSINE ? (size_t)R->n_items : 0);
+    FillList F;             // the small fills of the call leave in one launch
     if (exact_cos) {
         double *zero_avg = nullptr;
         const size_t ub = sizeof(double) * (size_t)(R->n_users > 0 ? R->n_users : 1);
         XM_HIP(xm_malloc_async((void **)&zero_avg, ub, st));
-        XM_HIP(hipMemsetAsync(zero_avg, 0, ub, st));
+        F.add(zero_avg, ub);
         u_avg = zero_avg;
         method = XMAP_ADJUST_COSINE;
     }
@@ -692,13 +693,19 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
     XM_ARG(!coo_ls || ((raw || method == XMAP_ADJUST_COSINE) && n_heavy_units == 0));
     XM_ARG(!raw || (coo_ls && n_heavy_units == 0 && n_heavy == 0));
     const size_t In = (size_t)(R->n_items > 0 ? R->n_items : 1);
+    // with RESET the shard sums' two words are cleared along with the counters; without, in front of k_shard_sums
+    const bool sums_cleared = (phases & XMAP_PAIRS_RESET) && (phases & XMAP_PAIRS_SHARD_SUMS);
     if (phases & XMAP_PAIRS_RESET) {   // reset the COO cursor / counters / row counts
-        XM_HIP(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
-        XM_HIP(hipMemsetAsync(d_shards, 0, 2 * COO_SHARDS * sizeof(int64_t), st));
+        F.add(d_counters, (sums_cleared ? 6 : 4) * sizeof(int64_t));
+        F.add(d_shards, 2 * COO_SHARDS * sizeof(int64_t));
         // -1 = unused entry (NO_MARKS: the caller reads the COO through the shard cursors only: 0.4 GB less to write)
         if (!(phases & XMAP_PAIRS_NO_MARKS)) XM_HIP(hipMemsetAsync(coo_i, 0xff, sizeof(int32_t) * (size_t)coo_cap, st));
-        XM_HIP(hipMemsetAsync(rowcnt, 0, sizeof(int32_t) * In, st));
-        if (mircnt) XM_HIP(hipMemsetAsync(mircnt, 0, sizeof(int32_t) * In, st));
+        F.add(rowcnt, sizeof(int32_t) * In);
+        if (mircnt) F.add(mircnt, sizeof(int32_t) * In);
+    }
+    {
+        int rc_fill = fill_multi(st, F);
+        if (rc_fill) return rc_fill;
     }
     TriArgs A;
     memset(&A, 0, sizeof(A));
@@ -762,7 +769,7 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
         if (rcode) return rcode;
     }
     if (phases & XMAP_PAIRS_SHARD_SUMS) {      // d_counters is [6]: [4] = kept pairs, [5] = unordered pairs evaluated (sums over the shards)
-        XM_HIP(hipMemsetAsync(d_counters + 4, 0, 2 * sizeof(int64_t), st));
+        if (!sums_cleared) XM_HIP(hipMemsetAsync(d_counters + 4, 0, 2 * sizeof(int64_t), st));
         k_shard_sums<<<dim3(1), dim3(256), 0, st>>>((const unsigned long long *)d_shards, (unsigned long long *)d_counters);
         XM_LAUNCH_CHECK();
     }
@@ -774,6 +781,21 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
         return mirror_counts(st, R->n_items, coo_cap / COO_SHARDS, COO_SHARDS, (const unsigned long long *)d_shards, coo_i, coo_j,
                              coo_ls != nullptr, part, rowcnt);
     }
+    return XMAP_OK;
+}
+
+/* The host's read of the pair kernels' counters without draining the stream (include/xmap_hip.h): begin queues the copy into
+ * pinned memory and an event behind it, wait takes the event. */
+int xmap_sim3_counters_begin(void *stream, const int64_t *d_counters) {
+    XM_ARG(d_counters);
+    return host_wait_post((hipStream_t)stream, HW_PAIRS, d_counters, 6);
+}
+int xmap_sim3_counters_wait(int64_t *h_out) {
+    XM_ARG(h_out);
+    const int64_t *h = nullptr;
+    int rcode = host_wait_take(HW_PAIRS, &h);
+    if (rcode) return rcode;
+    for (int c = 0; c < 6; c++) h_out[c] = h[c];
     return XMAP_OK;
 }
 }

@@ -26,6 +26,9 @@ def _stream(dev):
 # 1.28 ms at 640 / 1024, 1.20 ms at 768 / 2048)
 SLOT_TARGET = 768
 CH_MIN = 2048
+# Test-only switch, read once: the stage-A sequence (layout3 .. tri_mirror) with a stream synchronisation after every
+# fine-grained call, i.e. nothing runs under a host wait.  tests/test_gpu_stage_a_waits.py holds the overlapped sequence to it.
+STEPWISE = os.environ.get("XMAP_STAGE_A_STEPWISE") == "1"
 
 
 class DeviceRatings(object):
@@ -166,6 +169,11 @@ class Engine(object):
 
     def _empty(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.dev)
+
+    def _step(self):
+        """STEPWISE: drain the stream after a fine-grained call of stage A"""
+        if STEPWISE:
+            torch.cuda.current_stream(self.dev).synchronize()
 
     def _out(self, shape, dtype, written):
         """buffer a kernel is about to fill completely (`written`: it will run, i.e. the input is not empty): no
@@ -451,9 +459,12 @@ class Engine(object):
                                       vp(L.C), vp(L.uc_ptr), vp(L.uc_item), vp(L.uc_c)))
         L.slot_target = slot_target
 
-    def _tri_plan3(self, L, slot_target):
-        """_tri_plan with one synchronisation (xmap_sim3_plan): unit arrays sized from host-known bounds, the counts the
-        launches need and the heavy set's {CH, |H|} in one copy"""
+    def _tri_plan3(self, L, slot_target, under_wait=None):
+        """_tri_plan with one host wait (xmap_sim3_plan_begin / _wait): unit arrays sized from host-known bounds, the counts the
+        launches need and the heavy set's {CH, |H|} in one copy into pinned memory with an event behind it.  under_wait():
+        launches that do not depend on the counts (the profile copy's flag pass); they are queued behind the copy and run while
+        the host waits for the event, reads the counts and launches the pair kernels.  L.pairs_hint (set by the caller that will
+        run tri_pairs next): the pair kernels' buffers are allocated before the wait as well."""
         R = self.R
         st = _stream(self.dev)
         I = R.n_items
@@ -466,10 +477,18 @@ class Engine(object):
         L.uc_c = self._empty(cap_heavy, torch.int32)
         h = (C.c_int64 * 10)()
         with self.timed("tri_plan"):
-            check(lib.xmap_sim3_plan(st, C.byref(R.c), i32(slot_target), vp(L.pre), vp(L.hid), vp(L.ctl), vp(L.Q), vp(L.C),
-                                     vp(L.small), vp(L.Wp), vp(L.Qcat), vp(L.uq_ptr), vp(L.uc_ptr),
-                                     i32(1 if getattr(L, "dups", False) else 0), vp(L.uq_item), vp(L.uq_q), vp(L.uc_item),
-                                     vp(L.uc_c), i64(cap_light), i64(cap_heavy), h))
+            check(lib.xmap_sim3_plan_begin(st, C.byref(R.c), i32(slot_target), vp(L.pre), vp(L.hid), vp(L.ctl), vp(L.Q), vp(L.C),
+                                           vp(L.small), vp(L.Wp), vp(L.Qcat), vp(L.uq_ptr), vp(L.uc_ptr),
+                                           i32(1 if getattr(L, "dups", False) else 0), vp(L.uq_item), vp(L.uq_q), vp(L.uc_item),
+                                           vp(L.uc_c), i64(cap_light), i64(cap_heavy)))
+            self._step()
+            if under_wait is not None:
+                under_wait()
+                self._step()
+            hint = getattr(L, "pairs_hint", None)
+            if hint is not None and getattr(L, "_pairs_pre", None) is None:
+                L._pairs_pre = self._pairs_buffers(L, 1.0, **hint)
+            check(lib.xmap_sim3_plan_wait(i64(cap_light), i64(cap_heavy), h))
         L.n_light, L.n_heavy_units = int(h[0]), int(h[1])
         L.cls_ptr = (C.c_int64 * 6)(*[int(h[2 + c]) for c in range(6)])
         L.CH, L.n_heavy = int(h[8]), int(h[9])
@@ -501,23 +520,18 @@ class Engine(object):
         coo_slack = 1.0
         while True:
             lo, hi = (0, L.n_light) if unit_range is None else (int(unit_range[0]), int(unit_range[1]))
-            # per-shard capacity >= one full table (1024 kept pairs) + the expected share with slack
-            cap_coo = (max(int(L.half_contrib * coo_slack), 1) // 4096 + 1100) * 4096
-            coo_i = self._empty(cap_coo, torch.int32)
-            coo_j = self._empty(cap_coo, torch.int32)
-            coo_sim = self._empty(cap_coo, torch.float64)
-            coo_mutu = self._empty(cap_coo, torch.int32)
-            coo_nij = self._empty(cap_coo, torch.int32)
-            coo_ls = self._empty(cap_coo, torch.float64) if (rec or raw) else None    # raw: the error column of the dot
-            rowcnt = self._empty(max(I, 1), torch.int32)
-            mircnt = self._empty(max(I, 1), torch.int32) if split else None
+            # (taken under the plan's wait when the caller announced this call: _tri_plan3; else, and on a retry, here)
+            pre = L.__dict__.pop("_pairs_pre", None)
+            if pre is None or pre["key"] != self._pairs_key(L, coo_slack, rec or raw, split, count_mir and split and not raw):
+                pre = self._pairs_buffers(L, coo_slack, rec or raw, split, count_mir and split and not raw)
+            cap_coo = pre["cap_coo"]
+            coo_i, coo_j, coo_sim, coo_mutu, coo_nij, coo_ls = pre["coo"]
+            rowcnt, mircnt, d_cnt, d_shards = pre["rowcnt"], pre["mircnt"], pre["d_cnt"], pre["d_shards"]
             nh = L.n_heavy_units if do_heavy else 0
             hp_hi = self._empty(max(nh, 1) * 1024, torch.float64)
             hp_lo = self._empty(max(nh, 1) * 1024, torch.float64)
             hp_cnt = self._empty(max(nh, 1) * 1024, torch.int32)
             hp_mut = self._empty(max(nh, 1) * 1024, torch.int32)
-            d_cnt = self._zeros(6, torch.int64)       # [4], [5]: the shard sums (PAIRS_SHARD_SUMS)
-            d_shards = self._empty(2 * 4096, torch.int64)
 
             deal = 0 if heavy_deal is None else abi.pairs_deal(heavy_deal[1], heavy_deal[0])
             heavy, merge = (abi.PAIRS_HEAVY, abi.PAIRS_HEAVY_MERGE) if do_heavy else (0, 0)
@@ -532,6 +546,7 @@ class Engine(object):
                     vp(L.uc_item), vp(L.uc_c), i32(nh), i32(L.n_heavy), phases,
                     vp(hp_hi), vp(hp_lo), vp(hp_cnt), vp(hp_mut), i64(cap_coo), vp(coo_i), vp(coo_j), vp(coo_sim),
                     vp(coo_mutu), vp(coo_nij), vp(coo_ls), vp(rowcnt), vp(d_shards), vp(d_cnt), vp(mircnt)))
+                self._step()
             if os.environ.get("XMAP_SPLIT_PHASES") == "1":        # one timer per phase (analysis)
                 with self.timed("pair_heavy"):
                     run(abi.PAIRS_RESET | heavy)
@@ -542,12 +557,20 @@ class Engine(object):
             else:       # the heavy rows (chunk partials + merge) on a side stream next to the class launches of the light rows
                 with self.timed("pair_tri"):
                     run(abi.PAIRS_RESET | heavy | light | merge | abi.PAIRS_MIRCOUNT | abi.PAIRS_SHARD_SUMS)
+            # the one host wait of the pair kernels (flags + kept / evaluated pairs): the copy into pinned memory and its event
+            # are queued here, the mirrored counts behind them; the host waits for the event alone, so the counts arrive while
+            # the 0.2 ms of the count kernels still run, and the mirror's allocations and launches fall under them
+            check(lib.xmap_sim3_counters_begin(st, vp(d_cnt)))
+            self._step()
             if count_mir and split and not raw:
                 with self.timed("mir_count"):
-                    scratch = self._empty(cap_coo, torch.int32)
                     check(lib.xmap_sim3_mircount(st, i32(I), i64(cap_coo), vp(coo_i), vp(coo_j), vp(d_shards), i64(cap_coo),
-                                                 i32(1 if rec else 0), vp(scratch), vp(mircnt)))
-            h = d_cnt.tolist()          # the one synchronisation of the pair kernels: flags + kept / evaluated pairs
+                                                 i32(1 if rec else 0), vp(pre["mir_scratch"]), vp(mircnt)))
+                    self._step()
+                L._mirror_pre = self._mirror_buffers(cap_coo, 4 if rec else 3)
+            hc = (C.c_int64 * 6)()
+            check(lib.xmap_sim3_counters_wait(hc))
+            h = [int(x) for x in hc]
             if h[2]:
                 if L.slot_target <= 32:
                     raise abi.XmapError(abi.ERR_OVERFLOW, "pair-table overflow")
@@ -569,6 +592,34 @@ class Engine(object):
         if split:
             return out + (mircnt, d_shards) + (() if retry else (0,))
         return out if retry else out + (0,)
+
+    def _pairs_key(self, L, coo_slack, has_ls, split, count_mir):
+        # per-shard capacity >= one full table (1024 kept pairs) + the expected share with slack
+        cap_coo = (max(int(L.half_contrib * coo_slack), 1) // 4096 + 1100) * 4096
+        return (cap_coo, bool(has_ls), bool(split), bool(count_mir))
+
+    def _pairs_buffers(self, L, coo_slack, has_ls, split, count_mir):
+        """what tri_pairs needs that does not depend on the plan's counts: half COO, row counts, counters, shard cursors"""
+        I = self.R.n_items
+        key = self._pairs_key(L, coo_slack, has_ls, split, count_mir)
+        cap_coo = key[0]
+        coo = (self._empty(cap_coo, torch.int32), self._empty(cap_coo, torch.int32), self._empty(cap_coo, torch.float64),
+               self._empty(cap_coo, torch.int32), self._empty(cap_coo, torch.int32),
+               self._empty(cap_coo, torch.float64) if has_ls else None)            # raw: the error column of the dot
+        return {"key": key, "cap_coo": cap_coo, "coo": coo,
+                "rowcnt": self._empty(max(I, 1), torch.int32),
+                "mircnt": self._empty(max(I, 1), torch.int32) if split else None,
+                "d_cnt": self._empty(6, torch.int64),       # (cleared by PAIRS_RESET) [4], [5]: the shard sums (PAIRS_SHARD_SUMS)
+                "d_shards": self._empty(2 * 4096, torch.int64),
+                "mir_scratch": self._empty(cap_coo, torch.int32) if count_mir else None}
+
+    def _mirror_buffers(self, n_rec, rw):
+        """what tri_mirror needs apart from the CSR columns, for at most n_rec records of rw words"""
+        I = self.R.n_items
+        return {"n_rec": int(n_rec), "rw": rw,
+                "row_ptr": self._out(I + 1, torch.int64, I > 0), "mptr": self._empty(I + 1, torch.int64),
+                "tot": self._empty(max(I, 1), torch.int32), "fill": self._empty(max(I, 1), torch.int32),
+                "buf_a": self._empty(max(int(n_rec), 1) * rw, torch.int64), "buf_b": self._empty(max(int(n_rec), 1) * rw, torch.int64)}
 
     def tri_scatter(self, coo, rowcnt, info, n=None, L=None):
         """mirror a (complete) half COO (n valid entries; unused ones have coo_i = -1) into the CSR"""
@@ -606,7 +657,8 @@ class Engine(object):
         pair machinery as stage A: exact (double-double) sums with a zero user average, no heavy set."""
         R = self.R
         with self.timed("rec_stats"):
-            stats, L = self.layout3(slot_target, ch_min=max(64, R.n_users + 2), wide=True)      # no heavy set
+            stats, L = self.layout3(slot_target, ch_min=max(64, R.n_users + 2), wide=True,      # no heavy set
+                                    pairs_hint=dict(has_ls=True, split=True, count_mir=True))
         S, n_unordered = self._pairs_to_csr("adjust_cosine", cap, stats, L, rec=True)
         S.cap, S.n_unordered, S.layout = int(cap), n_unordered, L
         S.norm = self.norms[R.n_items:2 * R.n_items]
@@ -626,13 +678,17 @@ class Engine(object):
                                       vp(col), vp(sim), vp(ls)))
         return cnt[:I], col[:I], sim[:I], ls[:I]
 
-    def layout3(self, slot_target=SLOT_TARGET, ch_min=CH_MIN, wide=False, item_range=None):
+    def layout3(self, slot_target=SLOT_TARGET, ch_min=CH_MIN, wide=False, item_range=None, pairs_hint=None):
         """Round-3 layout of the "tri" formulation, one transposition per pass (xmap_sim3_layout): item counts, user and
         item info, weight-sorted profiles, rater records through the tile sort, heavy set, work units.  Returns (stats, L)
         like stats() + tri_layout().  wide: fp64 ratings (R.user_rating64) with zero user averages -- the RecommenderSim
         variant.  item_range (item-sharded ranks): the item statistics of that share of the items only; the caller then
         completes stats[2] (info) and self.norms on every rank -- the all-gather of per-item norms -- and calls L.finish(),
-        which sets the mutuality flags from them and plans the work units."""
+        which sets the mutuality flags from them and plans the work units.  Without item_range the profile copy's flag pass
+        (k_ub_flags) is queued behind the plan's read-back instead of in front of the plan: neither the plan nor the unit kernel
+        reads those flags, and the pass then runs while the host waits for the plan's counts (its time moves from the
+        "layout3" bracket into "tri_plan").  pairs_hint = {has_ls, split, count_mir} of the tri_pairs call that follows: its
+        buffers are allocated under that wait too."""
         R = self.R
         st = _stream(self.dev)
         I, U, nnz = R.n_items, R.n_users, R.nnz
@@ -661,15 +717,20 @@ class Engine(object):
         L.half_contrib = R.half_contrib          # = sum of W+ over the items (the host knows it from the profile lengths)
         if item_range is None:
             with self.timed("layout3"):
-                call(abi.LAYOUT_RECORDS | abi.LAYOUT_STATS | abi.LAYOUT_UB_FLAGS, 0, I)
-            self._tri_plan3(L, slot_target)
+                call(abi.LAYOUT_RECORDS | abi.LAYOUT_STATS, 0, I)
+                self._step()
+            L.pairs_hint = pairs_hint
+            # (fp64 ratings: no mutuality, no flag pass)
+            self._tri_plan3(L, slot_target, under_wait=None if wide else (lambda: call(abi.LAYOUT_UB_FLAGS, 0, I)))
         else:
             with self.timed("layout3"):
                 call(abi.LAYOUT_RECORDS | abi.LAYOUT_STATS, int(item_range[0]), int(item_range[1]))
+                self._step()
 
             def finish():
                 with self.timed("layout3_flags"):
                     call(abi.LAYOUT_UB_FLAGS | abi.LAYOUT_RC_FLAGS, 0, I)
+                    self._step()
                 self._tri_plan3(L, slot_target)
             L.finish = finish
         return (u_avg, u_norm, info, None, None), L
@@ -682,12 +743,13 @@ class Engine(object):
                                      vp(shards), i64(n), i32(1 if skip_self else 0), vp(scratch), vp(mir)))
         return mir
 
-    def tri_mirror(self, coo, own, mir, info, n, shards=None, rows=None, counted=False):
+    def tri_mirror(self, coo, own, mir, info, n, shards=None, rows=None, counted=False, pre=None):
         """round-3 mirror (xmap_sim3_mirror): a complete half COO with n valid entries, own[i] = pairs row i computed,
         mir[j] = pairs computed in lighter rows -> CSR, row = [own | mirrored].  shards: the cursors tri_pairs left (the
         COO is cut into 4096 shards filled from their start); None: the COO is one range of n records.  rows = (lo, hi):
         only these rows are built (the others stay empty) -- an item-sharded rank's share of the matrix, which is all its
-        knn and reverse-list shares read.  mir is filled here from the COO unless counted=True (mir_counts ran already)."""
+        knn and reverse-list shares read.  mir is filled here from the COO unless counted=True (mir_counts ran already).
+        pre: _mirror_buffers taken before the kept count was known (room for the whole COO); the CSR columns are sized here."""
         R = self.R
         st = _stream(self.dev)
         I = R.n_items
@@ -704,12 +766,9 @@ class Engine(object):
                 mir[:lo].zero_(); mir[hi:].zero_()
                 kept = int((own[lo:hi].long().sum() + mir[lo:hi].long().sum()).item())
         rw = 4 if coo_ls is not None else 3
-        row_ptr = self._out(I + 1, torch.int64, I > 0)
-        mptr = self._empty(I + 1, torch.int64)
-        tot = self._empty(max(I, 1), torch.int32)
-        fill = self._empty(max(I, 1), torch.int32)
-        buf_a = self._empty(max(int(n), 1) * rw, torch.int64)
-        buf_b = self._empty(max(int(n), 1) * rw, torch.int64)
+        if pre is None or pre["rw"] != rw or pre["n_rec"] < int(n):
+            pre = self._mirror_buffers(n, rw)
+        row_ptr, mptr, tot, fill, buf_a, buf_b = [pre[k] for k in ("row_ptr", "mptr", "tot", "fill", "buf_a", "buf_b")]
         col = self._empty(max(kept, 1), torch.int32)
         sim = self._empty(max(kept, 1), torch.float64)
         mutu = self._empty(max(kept, 1), torch.int32)
@@ -725,6 +784,7 @@ class Engine(object):
             check(lib.xmap_sim3_mirror(st, i32(I), i64(cap), vp(coo_i), vp(coo_j), vp(coo_sim), vp(coo_mutu), vp(coo_nij), vp(shards), i64(n),
                                        vp(own), vp(mir), vp(tot), vp(row_ptr), vp(mptr), vp(fill), vp(buf_a), vp(buf_b), vp(col),
                                        vp(sim), vp(mutu), vp(nij), vp(coo_ls), vp(ls), i32(lo), i32(hi)))
+            self._step()
         if coo_ls is not None:
             kept = int(row_ptr[I].item()) if I > 0 else 0
         S = self.sim_from_device(row_ptr, col[:kept], sim[:kept], mutu[:kept], nij[:kept], info)
@@ -740,7 +800,7 @@ class Engine(object):
             return self.tri_scatter(coo, rowcnt, stats[2], n, L), n_unordered
         coo, own, n, n_unordered, mir, shards = self.tri_pairs(method, cap, stats, L, do_heavy=not rec, rec=rec, split=True,
                                                                marks=False, count_mir=True)
-        return self.tri_mirror(coo, own, mir, stats[2], n, shards, counted=True), n_unordered
+        return self.tri_mirror(coo, own, mir, stats[2], n, shards, counted=True, pre=L.__dict__.pop("_mirror_pre", None)), n_unordered
 
     def item_sim_tri(self, method, cap, slot_target=SLOT_TARGET, ch_min=CH_MIN):
         """baseliner_calculate_sim_pipeline, second formulation (all rows, one GPU).  XMAP_A_V2=1: the round-2 sequence
@@ -750,7 +810,7 @@ class Engine(object):
                 stats = self.stats()
             L = self.tri_layout(stats, slot_target, ch_min)
         else:
-            stats, L = self.layout3(slot_target, ch_min)
+            stats, L = self.layout3(slot_target, ch_min, pairs_hint=dict(has_ls=False, split=True, count_mir=True))
         S, n_unordered = self._pairs_to_csr(method, cap, stats, L)
         S.method = abi.METHODS[method] if isinstance(method, str) else int(method)
         S.cap = int(cap)

@@ -99,6 +99,7 @@ class RecFilter(C.Structure):
 
 EXPORTS = [
     "xmap_last_error", "xmap_version", "xmap_trim", "xmap_debug_arena", "xmap_debug_arena_call", "xmap_exclusive_scan_i64", "xmap_exclusive_scan_i32_to_i64",
+    "xmap_exclusive_scan2_i32_to_i64", "xmap_scan_self_tiles", "xmap_sim3_plan_begin", "xmap_sim3_plan_wait", "xmap_sim3_counters_begin", "xmap_sim3_counters_wait",
     "xmap_build_csc", "xmap_user_stats", "xmap_item_stats", 
     "xmap_sim2_layout", "xmap_sim2_plan", "xmap_sim2_units",
     "xmap_sim2_pairs", "xmap_sim2_scatter", "xmap_sim3_layout", "xmap_sim3_plan", "xmap_sim3_mircount", "xmap_sim3_mirror", "xmap_item_partials", "xmap_item_merge", "xmap_sim2_pack_partials",
