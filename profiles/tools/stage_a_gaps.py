@@ -14,9 +14,11 @@ for f in files:
 rows.sort()
 print("kernels in trace:", len(rows))
 COUNT = ("k_count3", "k_cbs", "k_cb_count")
-ends = [x for x, r in enumerate(rows) if "k_mir_large" in r[2]]
+# the last kernel of the mirror: k_mir_tiles, or k_mir_large in a trace from before level B finished the large keys
+LAST = "k_mir_large" if any("k_mir_large" in r[2] for r in rows) else "k_mir_tiles"
+ends = [x for x, r in enumerate(rows) if LAST in r[2]]
 sorts = [x for x, r in enumerate(rows) if "k_sort_profiles3" in r[2]]
-print("k_mir_large:", len(ends), "k_sort_profiles3:", len(sorts))
+print(LAST + ":", len(ends), "k_sort_profiles3:", len(sorts))
 res = []
 for s in sorts:
     e = next((x for x in ends if x > s), None)

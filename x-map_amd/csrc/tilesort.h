@@ -11,16 +11,18 @@
 //                                                      the records and the keys it holds)
 //   tile of key k      m[k] >> ts_log                  (T tiles, a level-A bucket = 2^NB_LOG consecutive tiles)
 //   large key          count >= tile measure: always the last key of its tile, at most one per tile; its records are
-//                      routed straight to its own position range at level B and converted in slices (k_*_large)
+//                      routed straight to its own position range at level B, which writes them in their final form
+//                      (the level's finisher: they sit in LDS in final order when the chunk leaves)
 //   level A / B        a workgroup bins a chunk of CH records: the records are loaded whole (coalesced) into registers,
 //                      bucket histogram and ranks by LDS atomics, one returning global atomic per occupied bucket for the
 //                      fragment's place in the bucket's range, the records staged in LDS in bucket order and copied out
-//                      as flat words (consecutive lanes write consecutive words of a fragment)
+//                      as flat words (consecutive lanes write consecutive words of a fragment); level B's large keys:
+//                      a lane per record, consecutive lanes consecutive positions of the key's range
 //   level C            one workgroup per tile: the small keys' records get their rank from LDS cursors, are laid out in
 //                      final order in LDS and leave as whole rows
 //
 // Any order inside a key is a correct result (every consumer sums exactly or re-sorts), which is what makes ranks by
-// atomics admissible.  No host synchronisation: chunk and slice lists are built on the device, grids are upper bounds.
+// atomics admissible.  No host synchronisation: the chunk list is built on the device, grids are upper bounds.
 #pragma once
 #include "common.h"
 
@@ -37,8 +39,6 @@ constexpr int NA_MAX = 256;       // level-A buckets (LDS histogram; two staged 
 constexpr int CAP = 3072;         // records of a tile's small part that are laid out in LDS (more: placed directly)
 constexpr int CT = 512;           // threads of a level-C workgroup
 constexpr int NK_MAX = 520;       // keys of a tile's small part (the host chooses KW so that tile measure / KW + 1 fits)
-constexpr int SL = 2048;          // records per slice of a large key
-constexpr int LT = 256;           // threads of a slice workgroup
 
 struct Geo {
     int K;                        // keys
@@ -51,10 +51,9 @@ struct Geo {
     int *tile_large;              // [T] the tile's large key, or -1
     unsigned long long *curA;     // [NA] fragment cursors of the level-A buckets
     unsigned long long *curB;     // [2 T] ... of the tiles' small parts, then of their large keys
-    unsigned *counters;           // [0] level-B chunks listed, [1] slices of large keys listed
+    unsigned *counters;           // [0] level-B chunks listed
     int2 *clist;                  // level-B chunks (bucket, chunk)
-    int2 *slist;                  // slices (large key, slice)
-    long long clist_cap, slist_cap;
+    long long clist_cap;
 };
 
 __device__ __forceinline__ long long measure(const Geo &G, int k, long long p) { return p + (long long)k * G.KW; }
@@ -98,11 +97,27 @@ struct RecLoader {
     __device__ __forceinline__ void extra(long long, const unsigned long long (&)[Chunk<RW>::EPT][RW], const bool (&)[Chunk<RW>::EPT]) const {}
 };
 
+// What level B does with the records of the large keys (the finisher of k_ts_bin): they are staged in final order, so they
+// leave in their final form instead of going through `out`.
+//   STATE / state(G, k)   a 64-bit value per occupied large bucket, computed once by the thread that reserves its fragment
+//   gather(w)             what a record's final form needs from memory: issued for FU records of a lane before any is stored
+//   store(state, p, w, g) record w at position p of the sort's position space; returns its share of the key's sum (WSUM)
+//   WSUM / flush(k, sum)  the sum over the workgroup's records of large key k: one call per (workgroup, occupied bucket)
+// NoFin: level A, which has no large buckets.
+struct NoFin {
+    static constexpr bool STATE = false, WSUM = false;
+    __device__ __forceinline__ long long state(const Geo &, int) const { return 0; }
+    template <int RW> __device__ __forceinline__ unsigned gather(const unsigned long long (&)[RW]) const { return 0u; }
+    template <int RW> __device__ __forceinline__ unsigned long long store(long long, long long, const unsigned long long (&)[RW], unsigned) const { return 0ull; }
+    __device__ __forceinline__ void flush(int, unsigned long long) const {}
+};
+constexpr int FU = 4;             // records of a large key per lane whose gathers are in flight together
+
 // One binning level.  LEVEL_B = false: a chunk of the loader's index space (L.chunk), buckets = level-A buckets.
 // LEVEL_B = true: a listed chunk of a level-A bucket's range in the input (position space), buckets = the bucket's fine
-// tiles (small part) + their large keys.
-template <int RW, bool LEVEL_B, typename Loader>
-__global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, unsigned long long *__restrict__ out) {
+// tiles (small part, to `out`) + their large keys (to their final place through the finisher F).
+template <int RW, bool LEVEL_B, typename Loader, typename Fin>
+__global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, unsigned long long *__restrict__ out, Fin F) {
     constexpr int CH = Chunk<RW>::CH, EPT = Chunk<RW>::EPT;
     constexpr int NBK = LEVEL_B ? 2 * NB : NA_MAX;
     __shared__ unsigned hist[NBK];
@@ -113,6 +128,8 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
     __shared__ unsigned short sbk[CH];
     constexpr int NKB = LEVEL_B ? NB : NA_MAX;      // buckets by key: level B's large keys share their tile's
     __shared__ int bkey0[NKB], blarge[LEVEL_B ? NB : 1];
+    __shared__ long long fstate[LEVEL_B && Fin::STATE ? NB : 1];             // the finisher's: per large bucket
+    __shared__ unsigned long long fsum[LEVEL_B && Fin::WSUM ? NB : 1];
     const int tid = threadIdx.x;
     long long i0, i1;
     int a = 0;
@@ -128,6 +145,8 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
     }
     const int nbk = LEVEL_B ? 2 * NB : G.NA;
     for (int b = tid; b < nbk; b += BT) hist[b] = 0u;
+    if (LEVEL_B && Fin::WSUM)
+        for (int b = tid; b < NB; b += BT) fsum[b] = 0ull;
     // the first key of every bucket: level A (no key reaches the buckets past NA), level B (the tiles of bucket a and
     // their large keys)
     if (LEVEL_B) {
@@ -182,8 +201,15 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
             start = G.tile_pos0[b << NB_LOG];
             cur = &G.curA[b];
         }
-        // word 0 of the staged chunk -> its word of `out`, as if the whole chunk went where this fragment goes
-        gbase[b] = (start + (long long)atomicAdd(cur, (unsigned long long)c) - (long long)off[b]) * RW;
+        // word 0 of the staged chunk -> its word of `out`, as if the whole chunk went where this fragment goes (a large
+        // key's fragment: slot 0 -> its position, for the finisher)
+        const long long pos = start + (long long)atomicAdd(cur, (unsigned long long)c) - (long long)off[b];
+        if (LEVEL_B && b >= NB) {
+            gbase[b] = pos;
+            if (Fin::STATE) fstate[b - NB] = F.state(G, blarge[b - NB]);
+        } else {
+            gbase[b] = pos * RW;
+        }
     }
 #pragma unroll
     for (int r = 0; r < EPT; r++) {
@@ -198,13 +224,55 @@ __global__ __launch_bounds__(BT) void k_ts_bin(Geo G, Loader L, long long n_in, 
     // the staged chunk leaves as flat words, VW per lane (16 bytes where a record is a whole number of them): consecutive
     // lanes write consecutive words of a fragment, so a store instruction covers every line it touches and no line of a
     // fragment is stored twice (a lane per 24-byte record touched each of its lines with both of its stores)
+    // (level B: the small parts, slots [0, off[NB]); the large keys' records are the tail of the staging area)
     constexpr int VW = RW % 2 == 0 ? 2 : 1;
-    const int nw = (int)off[nbk] * RW;
+    const int nw = (int)off[LEVEL_B ? NB : nbk] * RW;
 #pragma unroll 4
     for (int q = tid * VW; q < nw; q += BT * VW) {
         unsigned long long *o = out + (gbase[sbk[q / RW]] + q);
 #pragma unroll
         for (int x = 0; x < VW; x++) o[x] = stage[q + x];
+    }
+    if (!LEVEL_B) return;
+    // the large keys' records in their final form: a lane per record, consecutive lanes take consecutive slots = consecutive
+    // positions of a fragment, so every column store of a wave covers runs of whole lines (but for the fragment's ends).
+    // No chunk without such records enters the loop or meets the barrier behind it.
+    const int s0 = (int)off[NB], s1 = (int)off[2 * NB];
+    for (int sw = s0 + (tid & ~63); sw < s1; sw += BT * FU) {        // (wave-uniform: the sums below run over whole waves)
+        const int sb = sw + (tid & 63);
+        unsigned long long v[FU][RW];
+        unsigned g[FU];
+        int bk[FU];
+#pragma unroll
+        for (int t = 0; t < FU; t++) {      // (past the end: the last record again, not stored)
+            const int s = min(sb + t * BT, s1 - 1);
+            bk[t] = sbk[s];
+#pragma unroll
+            for (int x = 0; x < RW; x++) v[t][x] = stage[s * RW + x];
+        }
+#pragma unroll
+        for (int t = 0; t < FU; t++) g[t] = F.gather(v[t]);
+#pragma unroll
+        for (int t = 0; t < FU; t++) {
+            if (sw + t * BT >= s1) break;
+            const int s = sb + t * BT;
+            unsigned long long add = 0ull;
+            if (s < s1) add = F.store(Fin::STATE ? fstate[bk[t] - NB] : 0ll, gbase[bk[t]] + s, v[t], g[t]);
+            if (Fin::WSUM) {
+                // the lanes of a wave hold consecutive slots: one bucket as a rule, and then one LDS atomic for all of them
+                if (__all(bk[t] == __builtin_amdgcn_readfirstlane(bk[t]))) {
+                    add = (unsigned long long)wave_sum_ll((long long)add);
+                    if (lane_id() == 0 && add) atomicAdd(&fsum[bk[t] - NB], add);
+                } else if (add) {
+                    atomicAdd(&fsum[bk[t] - NB], add);
+                }
+            }
+        }
+    }
+    if (Fin::WSUM && s1 > s0) {
+        __syncthreads();
+        for (int b = tid; b < NB; b += BT)
+            if (hist[NB + b]) F.flush(blarge[b], fsum[b]);
     }
 }
 

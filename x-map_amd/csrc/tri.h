@@ -65,7 +65,5 @@ void ts_geometry(int K, long long M, int ch, ts::Geo &G);
 // tables of one sort (arena temporaries of the calling entry point) + plan and chunk kernels
 // (fills: as for mirror_counts)
 int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr, FillList *fills = nullptr);
-// level B over 24-byte records: run by the layout (fp64 sort records) and the mirror (no sixth column), instantiated there
-extern template __global__ void ts::k_ts_bin<3, true, ts::RecLoader<3>>(ts::Geo, ts::RecLoader<3>, long long, unsigned long long *__restrict__);
 
 }  // namespace xmap

@@ -6,7 +6,7 @@
 //   k_rater_records : the rater records of every item; W+_i = number of contributions of row i (k_plan2)
 //   k_plan2 / k_fill_units2 : light units (item, hash partition) listed by LDS table class, heavy units (item in H,
 //                     chunk of CH raters)
-//   round 3 (one transposition per pass, below): k_count3, k_sort_profiles3, k_rc_tiles / k_rc_large through the tile sort,
+//   round 3 (one transposition per pass, below): k_count3, k_sort_profiles3, k_rc_tiles / RcFin through the tile sort,
 //                     k_item_stats3 .. k_item_big_flags, k_rc_flags / k_ub_flags
 #include "tri.h"
 #include "item_stats.h"
@@ -439,13 +439,17 @@ __global__ __launch_bounds__(256) void k_sort_profiles3(long long U, const long 
 
 // final form of a rater record from its sort record: e0 = first entry of the user's profile
 template <bool WIDE>
-__device__ __forceinline__ ulonglong2 rater_record(const unsigned long long *w, const long long *uptr) {
-    const unsigned user = WIDE ? (unsigned)w[2] : (unsigned)(w[1] >> 32);
-    const unsigned e0 = (unsigned)uptr[user];
+__device__ __forceinline__ unsigned rater_user(const unsigned long long *w) { return WIDE ? (unsigned)w[2] : (unsigned)(w[1] >> 32); }
+template <bool WIDE>
+__device__ __forceinline__ ulonglong2 rater_record_at(const unsigned long long *w, unsigned e0) {
     ulonglong2 o;
     o.x = (unsigned long long)e0 | (w[0] & 0xffffffff00000000ull);     // {e0, pos | flag}
     o.y = w[1];                                                        // narrow: {rating bits, user}; wide: the fp64 rating
     return o;
+}
+template <bool WIDE>
+__device__ __forceinline__ ulonglong2 rater_record(const unsigned long long *w, const long long *uptr) {
+    return rater_record_at<WIDE>(w, (unsigned)uptr[rater_user<WIDE>(w)]);
 }
 
 // level C of the rater records: one workgroup per tile.  The small keys' records are ranked by LDS cursors, converted,
@@ -494,26 +498,21 @@ __global__ __launch_bounds__(ts::CT) void k_rc_tiles(ts::Geo G, const unsigned l
     for (int x = threadIdx.x; x < h.nk; x += ts::CT) Wp[h.k0 + x] = wsum[x];
 }
 
-// the slices of the large keys: their records sit in their final range already (any order inside a key is a result)
+// the large keys' rater records, written by level B (tilesort.h: the finisher) at their final position; W+ of a large key is
+// summed per workgroup in LDS and added once (Wp is cleared before the sort, k_rc_tiles stores the small keys' only)
 template <bool WIDE>
-__global__ __launch_bounds__(ts::LT) void k_rc_large(ts::Geo G, const unsigned long long *bufB, const long long *uptr,
-                                                     ulonglong2 *rc, unsigned long long *Wp) {
-    constexpr int RW = WIDE ? 3 : 2;
-    if (blockIdx.x >= G.counters[1]) return;
-    const int2 sl = G.slist[blockIdx.x];
-    const long long lo = G.ptr[sl.x] + (long long)sl.y * ts::SL;
-    const long long hi = min(G.ptr[sl.x + 1], lo + ts::SL);
-    unsigned long long sum = 0ull;
-    for (long long p = lo + threadIdx.x; p < hi; p += ts::LT) {
-        unsigned long long w[RW];
-#pragma unroll
-        for (int x = 0; x < RW; x++) w[x] = bufB[(size_t)p * RW + x];
-        sum += (unsigned long long)((unsigned)(w[0] >> 32) & 0x7fffffffu);
-        rc[p] = rater_record<WIDE>(w, uptr);
+struct RcFin {
+    static constexpr int RW = WIDE ? 3 : 2;
+    static constexpr bool STATE = false, WSUM = true;
+    const long long *__restrict__ uptr; ulonglong2 *__restrict__ rc; unsigned long long *Wp;
+    __device__ __forceinline__ long long state(const ts::Geo &, int) const { return 0; }
+    __device__ __forceinline__ unsigned gather(const unsigned long long (&w)[RW]) const { return (unsigned)uptr[rater_user<WIDE>(w)]; }
+    __device__ __forceinline__ unsigned long long store(long long, long long p, const unsigned long long (&w)[RW], unsigned e0) const {
+        rc[p] = rater_record_at<WIDE>(w, e0);
+        return (unsigned long long)((unsigned)(w[0] >> 32) & 0x7fffffffu);
     }
-    sum = (unsigned long long)wave_sum_ll((long long)sum);
-    if (lane_id() == 0 && sum) atomicAdd(&Wp[sl.x], sum);
-}
+    __device__ __forceinline__ void flush(int k, unsigned long long sum) const { if (sum) atomicAdd(&Wp[k], sum); }
+};
 
 // item statistics from the rater records (item_stats.h); the records' mutuality flags are set once the average is known
 struct RcSrc {
@@ -749,17 +748,16 @@ template <int RW>
 int sort_rater_records(hipStream_t st, const ts::Geo &G, long long nnz, const void *srec, void *bufA, void *bufB, const int64_t *user_ptr,
                        void *rc, uint64_t *Wp) {
     constexpr bool WIDE = RW == 3;
-    const dim3 gridA((unsigned)((nnz + G.ch - 1) / G.ch)), gridB((unsigned)G.clist_cap), gridL((unsigned)G.slist_cap);
+    const dim3 gridA((unsigned)((nnz + G.ch - 1) / G.ch)), gridB((unsigned)G.clist_cap);
     ts::RecLoader<RW> LA{(const unsigned long long *)srec}, LB{(const unsigned long long *)bufA};
-    ts::k_ts_bin<RW, false, ts::RecLoader<RW>><<<gridA, dim3(ts::BT), 0, st>>>(G, LA, nnz, (unsigned long long *)bufA);
+    RcFin<WIDE> FB{(const long long *)user_ptr, (ulonglong2 *)rc, (unsigned long long *)Wp};
+    ts::k_ts_bin<RW, false, ts::RecLoader<RW>, ts::NoFin><<<gridA, dim3(ts::BT), 0, st>>>(G, LA, nnz, (unsigned long long *)bufA, ts::NoFin{});
     XM_LAUNCH_CHECK();
-    ts::k_ts_bin<RW, true, ts::RecLoader<RW>><<<gridB, dim3(ts::BT), 0, st>>>(G, LB, nnz, (unsigned long long *)bufB);
+    // level B: the tiles' small parts to bufB, the large keys' records to rc (+ their W+)
+    ts::k_ts_bin<RW, true, ts::RecLoader<RW>, RcFin<WIDE>><<<gridB, dim3(ts::BT), 0, st>>>(G, LB, nnz, (unsigned long long *)bufB, FB);
     XM_LAUNCH_CHECK();
     k_rc_tiles<WIDE><<<dim3((unsigned)G.T), dim3(ts::CT), 0, st>>>(G, (const unsigned long long *)bufB, (const long long *)user_ptr,
                                                                   (ulonglong2 *)rc, (unsigned long long *)Wp);
-    XM_LAUNCH_CHECK();
-    k_rc_large<WIDE><<<gridL, dim3(ts::LT), 0, st>>>(G, (const unsigned long long *)bufB, (const long long *)user_ptr, (ulonglong2 *)rc,
-                                                     (unsigned long long *)Wp);
     XM_LAUNCH_CHECK();
     return XMAP_OK;
 }

@@ -3,7 +3,7 @@
 //   k_scatter       : round 2 (xmap_sim2_scatter: the user-sharded step, cross-checks) -- atomic row cursors
 //   k_cbs_hist / k_cb_scan / k_cbs_scatter / k_cb_count : mirror_counts -- occurrences of every item in a column with no
 //                     atomic per entry (xmap_sim3_mircount; the layout's raters per item)
-//   k_coo_chunks, CooLoaderT, k_mir_tiles / k_mir_large : round 3 (xmap_sim3_mirror) -- row = [own | mirrored]: the own half
+//   k_coo_chunks, CooLoaderT, MirFin, k_mir_tiles : round 3 (xmap_sim3_mirror) -- row = [own | mirrored]: the own half
 //                     written in runs from the COO, the mirrored half routed by the tile sort keyed by the heavier item
 //   k_ts_plan / k_ts_chunks, ts_geometry, ts_prepare : the host side of the tile sort (tilesort.h), shared with the layout
 #include "tri.h"
@@ -395,28 +395,29 @@ __global__ __launch_bounds__(ts::CT) void k_mir_tiles(ts::Geo G, const unsigned 
     }
 }
 
+// the large keys' mirrored halves, written by level B (tilesort.h: the finisher): record w at position p of the sort goes to
+// the CSR columns at p + row_ptr[k] + own[k] - ptr[k]
 template <bool AUX>
-__global__ __launch_bounds__(ts::LT) void k_mir_large(ts::Geo G, const unsigned long long *bufB, const long long *row_ptr,
-                                                      const int *own, int *col, double *sim, int *mutu, int *nij, double *aux) {
-    constexpr int RW = AUX ? 4 : 3;
-    if (blockIdx.x >= G.counters[1]) return;
-    const int2 sl = G.slist[blockIdx.x];
-    const int k = sl.x;
-    const long long lo = G.ptr[k] + (long long)sl.y * ts::SL;
-    const long long hi = min(G.ptr[k + 1], lo + ts::SL);
-    const long long sh = row_ptr[k] + own[k] - G.ptr[k];
-    for (long long p = lo + threadIdx.x; p < hi; p += ts::LT) {
-        const unsigned long long w0 = bufB[(size_t)p * RW], w1 = bufB[(size_t)p * RW + 1], w2 = bufB[(size_t)p * RW + 2];
+struct MirFin {
+    static constexpr int RW = AUX ? 4 : 3;
+    static constexpr bool STATE = true, WSUM = false;
+    const long long *__restrict__ row_ptr; const int *__restrict__ own;
+    int *__restrict__ col; double *__restrict__ sim; int *__restrict__ mutu; int *__restrict__ nij; double *__restrict__ aux;
+    __device__ __forceinline__ long long state(const ts::Geo &G, int k) const { return row_ptr[k] + (long long)own[k] - G.ptr[k]; }
+    __device__ __forceinline__ unsigned gather(const unsigned long long (&)[RW]) const { return 0u; }
+    __device__ __forceinline__ unsigned long long store(long long sh, long long p, const unsigned long long (&w)[RW], unsigned) const {
         const long long P = p + sh;
-        col[P] = (int)(w0 >> 32); sim[P] = __longlong_as_double((long long)w1);
-        mutu[P] = (int)(unsigned)w2; nij[P] = (int)(w2 >> 32);
-        if (AUX) aux[P] = __longlong_as_double((long long)bufB[(size_t)p * RW + 3]);
+        col[P] = (int)(w[0] >> 32); sim[P] = __longlong_as_double((long long)w[1]);
+        mutu[P] = (int)(unsigned)w[2]; nij[P] = (int)(w[2] >> 32);
+        if (AUX) aux[P] = __longlong_as_double((long long)w[RW - 1]);
+        return 0ull;
     }
-}
+    __device__ __forceinline__ void flush(int, unsigned long long) const {}
+};
 
 namespace ts {
 
-// one thread per key: tile, tile boundaries, large keys and their slices
+// one thread per key: tile, tile boundaries, large keys
 __global__ __launch_bounds__(256) void k_ts_plan(Geo G) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= G.K) return;
@@ -427,13 +428,7 @@ __global__ __launch_bounds__(256) void k_ts_plan(Geo G) {
     for (int x = tp + 1; x <= t; x++) { G.tile_key0[x] = k; G.tile_pos0[x] = p; }
     if (k == G.K - 1)
         for (int x = t + 1; x <= G.T; x++) { G.tile_key0[x] = G.K; G.tile_pos0[x] = G.ptr[G.K]; }
-    if (large) {
-        G.tile_large[t] = k;
-        const int nsl = (int)((cnt + SL - 1) / SL);
-        const unsigned base = atomicAdd(&G.counters[1], (unsigned)nsl);
-        for (int x = 0; x < nsl; x++)
-            if ((long long)base + x < G.slist_cap) G.slist[base + x] = make_int2(k, x);
-    }
+    if (large) G.tile_large[t] = k;
 }
 
 // one thread per level-A bucket: its chunks of CH records for level B
@@ -450,8 +445,6 @@ __global__ __launch_bounds__(256) void k_ts_chunks(Geo G) {
 }
 
 }  // namespace ts
-
-template __global__ void ts::k_ts_bin<3, true, ts::RecLoader<3>>(ts::Geo, ts::RecLoader<3>, long long, unsigned long long *__restrict__);      // (tri.h)
 
 // ---- tile sort: host side (tri.h) ----
 void ts_geometry(int K, long long M, int ch, ts::Geo &G) {
@@ -479,17 +472,15 @@ void ts_geometry(int K, long long M, int ch, ts::Geo &G) {
 int ts_prepare(hipStream_t st, ts::Geo &G, const long long *ptr, FillList *fills) {
     G.ptr = ptr;
     G.clist_cap = G.M / G.ch + G.NA + 1;
-    G.slist_cap = G.M / ts::SL + (G.M >> G.ts_log) + 2;
     XM_HIP(xm_malloc_async((void **)&G.tile_key0, sizeof(int) * ((size_t)G.T + 1), st));
     XM_HIP(xm_malloc_async((void **)&G.tile_pos0, sizeof(long long) * ((size_t)G.T + 1), st));
     XM_HIP(xm_malloc_async((void **)&G.tile_large, sizeof(int) * (size_t)G.T, st));
-    // cursors and counters in one zeroed block: curA [NA], curB [2 T], counters [2 x 4 B]
+    // cursors and the chunk counter in one zeroed block: curA [NA], curB [2 T], counters [8 B]
     unsigned long long *z = nullptr;
     const size_t nz = (size_t)G.NA + 2 * (size_t)G.T + 1;
     XM_HIP(xm_malloc_async((void **)&z, sizeof(unsigned long long) * nz, st));
     G.curA = z; G.curB = z + G.NA; G.counters = (unsigned *)(z + G.NA + 2 * (size_t)G.T);
     XM_HIP(xm_malloc_async((void **)&G.clist, sizeof(int2) * (size_t)G.clist_cap, st));
-    XM_HIP(xm_malloc_async((void **)&G.slist, sizeof(int2) * (size_t)G.slist_cap, st));
     FillList own;
     FillList &F = fills ? *fills : own;
     F.add(z, sizeof(unsigned long long) * nz);
@@ -513,15 +504,16 @@ int mirror_levels(hipStream_t st, const ts::Geo &G, int64_t coo_cap, const int32
     CooLoaderT<AUX, SHARE> LA{coo_i, coo_j, coo_sim, coo_mutu, coo_nij, coo_aux, chunks, n_chunks, (const long long *)row_ptr, fill,
                               col, sim, mutu, nij, aux, row_lo, row_hi};
     ts::RecLoader<RW> LB{(const unsigned long long *)bufA};
-    ts::k_ts_bin<RW, false, CooLoaderT<AUX, SHARE>><<<dim3((unsigned)chunk_cap), dim3(ts::BT), 0, st>>>(G, LA, coo_cap, (unsigned long long *)bufA);
+    MirFin<AUX> FB{(const long long *)row_ptr, own, col, sim, mutu, nij, aux};
+    ts::k_ts_bin<RW, false, CooLoaderT<AUX, SHARE>, ts::NoFin><<<dim3((unsigned)chunk_cap), dim3(ts::BT), 0, st>>>(
+        G, LA, coo_cap, (unsigned long long *)bufA, ts::NoFin{});
     XM_LAUNCH_CHECK();
-    ts::k_ts_bin<RW, true, ts::RecLoader<RW>><<<dim3((unsigned)G.clist_cap), dim3(ts::BT), 0, st>>>(G, LB, n_pairs, (unsigned long long *)bufB);
+    // level B: the tiles' small parts to bufB, the large keys' records to the CSR
+    ts::k_ts_bin<RW, true, ts::RecLoader<RW>, MirFin<AUX>><<<dim3((unsigned)G.clist_cap), dim3(ts::BT), 0, st>>>(
+        G, LB, n_pairs, (unsigned long long *)bufB, FB);
     XM_LAUNCH_CHECK();
     k_mir_tiles<AUX><<<dim3((unsigned)G.T), dim3(ts::CT), 0, st>>>(G, (const unsigned long long *)bufB, (const long long *)row_ptr, own, col,
                                                                    sim, mutu, nij, aux);
-    XM_LAUNCH_CHECK();
-    k_mir_large<AUX><<<dim3((unsigned)G.slist_cap), dim3(ts::LT), 0, st>>>(G, (const unsigned long long *)bufB, (const long long *)row_ptr, own,
-                                                                            col, sim, mutu, nij, aux);
     XM_LAUNCH_CHECK();
     return XMAP_OK;
 }
