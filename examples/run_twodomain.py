@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -33,6 +33,10 @@ similarity at weight 0 -- the plain lists -- and at W, then the re-ranked top 5 
 of the first group are printed side by side under the three aggregates (mean, least misery, most pleasure) with the member who
 likes each item least (xmap.engine.session.recommend_group: the members' unrounded predictions are aggregated on the device; a
 member without evidence for an item predicts its average).
+
+--peers N (with --device-tail): "who is this user like?" -- for three test users the N users of the train set with the most similar
+AlterEgo profiles (xmap.engine.session.similar_users: centred cosine weighted by the number of common records), and each user plus
+their peers as one group of recommend_group: "people like you also liked".
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -113,6 +117,7 @@ def main(argv=None):
     ap.add_argument("--eligible", action="store_true")
     ap.add_argument("--diverse", type=float, default=None, metavar="W")
     ap.add_argument("--groups", type=int, default=None, metavar="K")
+    ap.add_argument("--peers", type=int, default=None, metavar="N")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -146,6 +151,8 @@ def main(argv=None):
         ap.error("--diverse needs --device-tail and the non-private recommender")
     if args.groups is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.groups <= 64):
         ap.error("--groups K needs --device-tail, the non-private recommender and 1 <= K <= 64")
+    if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
+        ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
     if args.fold_in:
         if not args.device_tail or para["recommender"]["private_flag"]:
@@ -264,6 +271,20 @@ def main(argv=None):
         cols = [by_how[how].collect()[0][1] for how in ("mean", "min", "max")]
         for pos in range(max(len(c) for c in cols)):
             print("  " + " | ".join("%-44s" % ("%s %.3f (least: %s)" % (c[pos][0], c[pos][1], c[pos][3]) if pos < len(c) else "") for c in cols))
+    if args.peers is not None:
+        # who is this user like?  The N nearest profiles of a few test users, then each user and their peers as ONE group:
+        # "people like you also liked"
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        some = [uid for uid, _ in testRDD.take(3)]
+        peers = timed("similar_users", session.similar_users, alterEgo_profile, some, args.peers, cap=5, min_common=2)
+        print("peers: %d candidates of %d users, %d records expanded (largest candidate count %d)" % (
+            peers.stats[0], len(some), peers.stats[5], peers.stats[4]))
+        for uid, lst in peers.collect():
+            print("peers of %s:" % uid, ", ".join("%s (%.3f, %d in common)" % e for e in lst) or "nobody shares an item")
+        circles = [("%s and peers" % uid, [uid] + [u2 for u2, _, _ in lst]) for uid, lst in peers.collect()]
+        liked = timed("peers_group_topn", session.recommend_group, alterEgo_profile, circles, w, k, alpha, 5, how="mean")
+        for gid, lst in liked.collect():
+            print("people like you also liked (%s):" % gid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _, _ in lst) or "no evidence")
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

@@ -71,6 +71,9 @@ int xmap_version(void);
 int xmap_trim(void);
 int xmap_debug_arena(void *stream, int64_t *live, int64_t *reserved);
 int xmap_debug_arena_call(void *stream, int64_t bytes, int fail);
+/* Measurement hook: the library's stable LSD radix sort of n (key, value) pairs by the low `bits` bits of the key, in place, alone
+ * -- the yardstick of the calls built around it (item fold-in, peers; profiles/tools/peers_timing.py).  1 <= bits <= 64, n < 2^31. */
+int xmap_debug_sort_pairs(void *stream, uint64_t *keys, int32_t *vals, int64_t n, int32_t bits);
 
 /* exclusive prefix sum of n int64 values; out[n] receives the total; *h_total (may be NULL) too (syncs). */
 int xmap_exclusive_scan_i64(void *stream, const int64_t *in, int64_t *out, int64_t n, int64_t *h_total);
@@ -955,6 +958,61 @@ int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr,
                          int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_low,
                          const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [8] or NULL */);
 
+/* ---- peers (csrc/stage_e_peers.hip; DESIGN.md 4 "Peers"): "who is this user like?" -- for every query user the n_top resident
+ * users with the most similar profiles, by the significance-weighted cosine of RecommenderSim taken between USERS.  All
+ * arithmetic is fp64, one rounded operation per step, no fused multiply-add.
+ * A profile row p is VALID iff 0 <= prof_item[p] < n_items; invalid rows are ignored everywhere.  x of a row = prof_rating[p] -
+ *   centre[prof_item[p]]; centre == NULL: the rating itself.  HOLDER ORDER of item n: the valid resident rows that hold n by
+ *   ascending row index (user ascending, then profile order); a user who holds an item twice appears twice.
+ * Records of query q with query user a: for each valid row p of a in profile order, for each holder row h of its item in holder
+ *   order, the record (v = user of h, t = x of p times x of h).  A user holding an item twice on either side multiplies out.
+ * Candidates of q: the users v with at least one record; n = the records of v; dot = the high word of the double-double sum of
+ *   t in record order; norm2 of a user = the same form of the user with itself (p over its valid rows, r over its valid rows with
+ *   the same item, both in profile order), nrm = sqrt of it (a negative or NaN argument: NaN); the query's nrm by the same code
+ *   over the query CSR.  np = nrm of a * nrm of v; cs = np != 0 ? dot / np : 0.0; sim = 1.0 * cs * min(n, cap) / cap.
+ * Rules, in this order: (1) the candidates; (2) with XMAP_PEERS_SAME (the query CSR is the resident CSR) v == query_user[q]
+ *   leaves unless XMAP_PEERS_KEEP_SELF; (3) the ids of the query's exclusion list leave; (4) the rest is intersected with
+ *   F->allow -- the mask and the ids are USERS, one exclusion list per query, and the mask acts in the expansion: no record of an
+ *   ineligible user is written; (5) n < min_common: dropped, counted; (6) sim; non-finite: dropped, counted; (7) sim < F->min_score:
+ *   dropped, counted; (8) selection by sim descending as numbers, user index ascending on equal sim.  F == NULL: no rules.
+ * Outputs (device): out_cnt [n_query]; out_user / out_sim / out_common [n_query][n_top] with -1 / 0.0 / 0 behind the count;
+ *   out_common = n of the entry.  1 <= n_top <= 1024, cap >= 1 (cap = 1 returns cs), min_common >= 1, n_users < 2^31.  A query
+ *   user outside the query CSR or without valid rows gets count 0; queries may repeat.  A pure function of the inputs: it depends
+ *   on neither the grid, nor the order of any atomic, nor max_records.
+ * h_stats (host, [6] or NULL): [0] candidates after rules 2-4, [1] dropped by min_common, [2] dropped as non-finite, [3] dropped
+ *   below the floor, [4] the largest candidate count (after rules 2-4) of one query, [5] records expanded.
+ * xmap_peer_index: hd_ptr [n_items + 1], hd_user / hd_x [n_rows] (n_rows = prof_ptr[n_users] < 2^31; the entries behind
+ *   hd_ptr[n_items] are not part of the index), nrm [n_users]; *h_rows = rows indexed = hd_ptr[n_items].  The transposition is a
+ *   stable sort of the row indices by item.  Temporaries: 24 B per profile row.  Syncs.
+ * xmap_peer_rows: the queries index the CSR q_ptr / q_item / q_rating of n_q_users users (the resident profiles, or a fold-in
+ *   batch); centre must be the one the index was built with.  The queries are cut into chunks of consecutive queries whose records
+ *   number at most max_records (0: the library's default, 2^22); a single query above that is a chunk of its own and its records
+ *   must stay below 2^31 (XMAP_ERR_CAPACITY).  Per chunk: record counts per query row -> scan -> expansion (one thread per record)
+ *   -> stable radix sort on (q - q0) << user_bits | v -> run heads -> scan -> one lane per run -> segmented selection.
+ *   Temporaries from the stream's arena: 64 B per record of the largest chunk (48 B per record + 16 B per run, sized for as many runs as records).  n_top, cap, min_common, flags and
+ *   a NaN floor are checked on the host before any device work, the pointers too; ex_ptr and the row count of the queries on the
+ *   device, before an output is written.  max_records above 2^31 - 2 counts as 2^31 - 2.  Syncs.
+ * xmap_peer_centre: centre[i] = the average of hd_x over the holders of item i (0.0 without holders) of an index built with
+ *   centre == NULL -- the double-double sum (exact to 2^-104) rounded once, divided by the entries, as RecommenderSim takes its item averages
+ *   (xmap_ctx_rec_download's item_avg) -- so a caller centres without a RecommenderSim pass: index without centre, this call,
+ *   index with it.  hd_x may be NULL iff no row is indexed.  One wave per item.  Does not sync.
+ * Launches: every kernel that takes one wave or one block per user, query, query row or item is launched in ranges below 2^32
+ *   threads, so the sizes are bounded as stated -- n_users < 2^31, profile rows < 2^31, n_query <= 2^28, query rows of
+ *   one call < 2^31, records of one query < 2^31 - 1 -- and by memory, not by a grid. */
+#define XMAP_PEERS_SAME 1
+#define XMAP_PEERS_KEEP_SELF 2
+#define XMAP_PEERS_CENTRED 4    /* xmap_ctx_peers only: centre by the context's item averages */
+int xmap_peer_index(void *stream, int64_t n_users, int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item,
+                    const double *prof_rating, const double *centre /*[I] or NULL*/, int64_t *hd_ptr /*[I+1]*/, int32_t *hd_user,
+                    double *hd_x /*[n_rows]*/, double *nrm /*[n_users]*/, int64_t *h_rows /*host, may be NULL*/);
+int xmap_peer_centre(void *stream, int32_t n_items, const int64_t *hd_ptr, const double *hd_x, double *centre /*[I]*/);
+int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int64_t n_q_users, const int64_t *q_ptr,
+                   const int32_t *q_item, const double *q_rating, int32_t flags, int32_t n_top, int32_t cap, int32_t min_common,
+                   int64_t n_users, int32_t n_items, const double *centre, const int64_t *hd_ptr, const int32_t *hd_user,
+                   const double *hd_x, const double *nrm, int64_t max_records /*0: library default*/, int32_t *out_cnt,
+                   int32_t *out_user, double *out_sim, int32_t *out_common,
+                   const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
+
 /* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
  * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
  * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
@@ -1269,6 +1327,17 @@ int xmap_ctx_recommend_group(xmap_ctx *ctx, int32_t source, int64_t n_groups, co
                              int32_t n_top, int32_t rank_by, int32_t flags, int32_t how, double veto, const double *wtab, int32_t n_w,
                              int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_low,
                              const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [8] or NULL */);
+/* Peers: xmap_peer_rows over the context's profiles, host arrays in and out.  XMAP_SRC_RESIDENT: the queries are resident users
+ * and the library sets XMAP_PEERS_SAME (also on a union context); XMAP_SRC_FOLDIN: the queries index the fold-in batch, the
+ * candidates are the resident users, no self rule; XMAP_SRC_ITEM_FOLDIN is XMAP_ERR_ARG.  flags: XMAP_PEERS_KEEP_SELF,
+ * XMAP_PEERS_CENTRED (centre by the context's item averages).  Needs the result of xmap_ctx_rec_sim: have_rec, the profiles and the averages.
+ * The index is cached in the context per centring: built on first use, dropped by whatever drops the profiles or the averages.
+ * The mask and the exclusion ids are USERS.  n_top, cap, min_common, flags, the source and the filter are checked on the host
+ * before any device work: on XMAP_ERR_ARG the outputs keep every byte.  Host outputs: out_cnt [n_query], out_user / out_sim /
+ * out_common [n_query][n_top]. */
+int xmap_ctx_peers(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
+                   int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common,
+                   const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

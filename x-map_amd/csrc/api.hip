@@ -96,6 +96,13 @@ struct xmap_ctx {
     bool have_div = false;
     int32_t *dv_col = nullptr;
     double *dv_abs = nullptr;
+    // the peer index of the resident profiles (xmap_peer_index), one per centring ([0] raw ratings, [1] centred by rs_avg): built
+    // by the first xmap_ctx_peers that needs it, dropped with the profiles and the averages (drop_tail)
+    Pool p_peer[2];
+    bool have_peer[2] = {false, false};
+    int64_t *pr_hd_ptr[2] = {nullptr, nullptr};
+    int32_t *pr_hd_user[2] = {nullptr, nullptr};
+    double *pr_hd_x[2] = {nullptr, nullptr}, *pr_nrm[2] = {nullptr, nullptr};
     // item fold-in: the RecommenderSim rows of the last batch of new items (if_*), the batch's rater CSR, and the EXTENDED tables
     // of I + if_new items (x_*: rows [0, I) copies of nb_* / rs_avg, row I + q the list and the average of batch item q); hangs
     // on the tail and the neighbour lists: dropped with them
@@ -165,6 +172,7 @@ static void drop_tail(xmap_ctx *c) {
     drop_ifold(c);
     c->p_nb.release(); c->p_rec.release(); c->p_div.release();
     c->have_rec = c->have_nb = c->have_div = false;
+    for (int k = 0; k < 2; k++) { c->p_peer[k].release(); c->have_peer[k] = false; }
 }
 
 // the fold-in batch hangs on the replacement map: upload, item_sim, extend and generate drop it; the tail calls leave it
@@ -1465,6 +1473,57 @@ int xmap_ctx_recommend_diverse(xmap_ctx *c, int32_t source, int64_t n_query, con
     XM_TRY(d2h(out_ils, (const double *)d_ils, n, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
     if (stats) { for (int k = 0; k < 6; k++) stats[k] = h6[k]; stats[6] = h2[0]; stats[7] = h2[1]; }
+    return XMAP_OK;
+}
+
+// ---- peers: the users most like a query user, over the resident profiles or a fold-in batch ---------------------------------------
+
+int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
+                   int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, const xmap_rec_filter *F,
+                   int64_t *stats) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(n_top >= 1 && n_top <= 1024);
+    XM_ARG(cap >= 1);
+    XM_ARG(min_common >= 1);
+    XM_ARG((flags & ~(XMAP_PEERS_KEEP_SELF | XMAP_PEERS_CENTRED)) == 0);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN);       // an item fold-in adds items, not users
+    XM_ARG(n_query >= 0 && (n_query == 0 || (query_user && out_cnt && out_user && out_sim && out_common)));
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_gen && c->have_rec);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 6; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    const int32_t I = c->R.n_items;
+    const int64_t U = c->R.n_users;
+    const int z = (flags & XMAP_PEERS_CENTRED) ? 1 : 0;
+    const double *centre = z ? c->rs_avg : nullptr;
+    if (!c->have_peer[z]) {
+        c->p_peer[z].release();
+        XM_ALLOC(c->p_peer[z], c->pr_hd_ptr[z], I + 1); XM_ALLOC(c->p_peer[z], c->pr_hd_user[z], c->n_rows);
+        XM_ALLOC(c->p_peer[z], c->pr_hd_x[z], c->n_rows); XM_ALLOC(c->p_peer[z], c->pr_nrm[z], U);
+        XM_TRY(xmap_peer_index(c->st, U, I, c->pf_ptr, c->pf_item, c->pf_rating, centre, c->pr_hd_ptr[z], c->pr_hd_user[z], c->pr_hd_x[z],
+                               c->pr_nrm[z], nullptr));
+        c->have_peer[z] = true;
+    }
+    const Profiles Q = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const int32_t fl = (flags & XMAP_PEERS_KEEP_SELF) | (source == XMAP_SRC_RESIDENT ? XMAP_PEERS_SAME : 0);
+    ScratchPool tmp;
+    int32_t *d_query, *d_cnt, *d_user, *d_common;
+    double *d_sim;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_query, query_user, n, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_user, m, c->st));
+    XM_TRY(dalloc(tmp, &d_sim, m, c->st)); XM_TRY(dalloc(tmp, &d_common, m, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, U, &D));
+    XM_TRY(xmap_peer_rows(c->st, n_query, d_query, Q.n_users, Q.ptr, Q.item, Q.rating, fl, n_top, cap, min_common, U, I, centre,
+                          c->pr_hd_ptr[z], c->pr_hd_user[z], c->pr_hd_x[z], c->pr_nrm[z], 0, d_cnt, d_user, d_sim, d_common, &D, stats));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_user, (const int32_t *)d_user, m, c->st));
+    XM_TRY(d2h(out_sim, (const double *)d_sim, m, c->st));
+    XM_TRY(d2h(out_common, (const int32_t *)d_common, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
     return XMAP_OK;
 }
 

@@ -182,6 +182,18 @@ using namespace xmap;
 
 extern "C" {
 
+int xmap_debug_sort_pairs(void *stream, uint64_t *keys, int32_t *vals, int64_t n, int32_t bits) {
+    XM_ARG(n >= 0 && n < 2147483647ll && bits >= 1 && bits <= 64 && (n == 0 || (keys && vals)));
+    hipStream_t st = (hipStream_t)stream;
+    XM_SCOPE(st);
+    if (n == 0) return XMAP_OK;
+    unsigned long long *kt = nullptr;
+    int *vt = nullptr;
+    XM_HIP(xm_malloc_async((void **)&kt, sizeof(unsigned long long) * (size_t)n, st));
+    XM_HIP(xm_malloc_async((void **)&vt, sizeof(int) * (size_t)n, st));
+    return radix_sort_pairs(st, (unsigned long long *)keys, vals, kt, vt, n, bits);
+}
+
 int xmap_nb_index(void *stream, int32_t n_items, const uint8_t *cls, int32_t *nb_list, int32_t *nb_id, int64_t *h_n_nb) {
     XM_SCOPE(stream);
     XM_ARG(cls && nb_list && nb_id && h_n_nb);

@@ -16,12 +16,12 @@
 //                     second-level bitmap of stage_e_topn.hip (one bit per bitmap word that was touched) is all the emit pass
 //                     scans, and it zeroes exactly the words it visits: the window is cleared once per block, never per query.
 //   scoring         : k_predict_rows<., RAW = true> (predict_rows.h) over the (user, item) candidate list, unchanged.
-//   k_au_select     : segmented top-N, one block per query, for segments of up to a million candidates and N up to 1024.  The
-//                     block keeps the best CAP >= n_top keys seen so far sorted in LDS; the segment streams through in tiles,
-//                     a candidate that beats the current N-th key is staged behind them, and when the staging area cannot take
-//                     another tile the whole array is sorted again by a bitonic network.  A key is (score as an ordered
-//                     integer, position in the segment): the positions ascend with the user index, keys are distinct, and the
-//                     sorted prefix is the same whatever order the survivors were staged in.  Status 2: dropped and counted.
+//   k_au_select     : segmented top-N, one block per query, for segments of up to a million candidates and N up to 1024:
+//                     au_select_segment of au_select.h (shared with stage_e_peers.hip) -- the best CAP >= n_top keys sorted in
+//                     LDS, the segment streamed through in tiles, survivors staged and re-sorted by a bitonic network.  A key is
+//                     (score as an ordered integer, position in the segment): the positions ascend with the user index, keys
+//                     are distinct, and the sorted prefix is the same whatever order the survivors were staged in.  Status 2:
+//                     dropped and counted.
 // Items of an item fold-in (stage_e_itemfold.hip; query items >= n_resident of xmap_itemfold_audience_rows): no profile holds them, their
 // holders are the batch's raters -- a second, optional holder CSR that the clear pass of k_au_candidates reads for them.
 // xmap_audience_rows_filtered (rec_filter.h; DESIGN.md 4 "Eligibility"): the FILT instantiation of k_au_candidates clears the
@@ -29,6 +29,7 @@
 // k_au_select drops and counts the candidates below the score floor.
 // Every output position follows from the scans, so the result does not depend on the grid or on the order of the atomics.
 #include "common.h"
+#include "au_select.h"
 #include "predict_rows.h"
 #include "rec_filter.h"
 
@@ -41,11 +42,7 @@ constexpr int AU_SUMMARY = AU_WORDS / 32;       // second level: bit w of word s
 constexpr int AU_THREADS = 1024;                // 16 waves stride a holder row; thread t emits summary word t (thread order = user order)
 static_assert(AU_SUMMARY == AU_THREADS, "one summary word per thread");
 constexpr int AU_MAX_BLOCKS = 512;              // blocks of the candidate pass (grid-stride over the queries: the window is zeroed once per block)
-constexpr int AU_MAX_TOP = 1024;
 constexpr int AU_ROW_BLOCKS = 2048;             // blocks of the holders pass (grid-stride over the profile rows)
-constexpr int AU_SEL_THREADS = 256;             // threads of a selection block = candidates of a tile
-constexpr unsigned long long AU_NO_KEY = ~0ull; // behind every key of a finite score
-constexpr unsigned AU_NO_POS = 0xffffffffu;
 
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_au_holders(long long U, int I, const long long *pptr, const int *pitem, int *hcnt,
@@ -189,31 +186,7 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
     }
 }
 
-// a finite score as an integer that ascends where the score DEscends; -0.0 and 0.0 get one key (scores compare as numbers)
-__device__ __forceinline__ unsigned long long au_key(double s) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(s + 0.0);        // -0.0 + 0.0 = 0.0
-    return (b >> 63) ? b : ~(b | (1ull << 63));         // negative: larger magnitude = later; positive: larger = earlier, before every negative
-}
-
-// ascending bitonic sort of (K, P)[0 .. 2 CAP), all threads of the block; keys (K, P) are distinct except among the blanks
-template <int CAP>
-__device__ __forceinline__ void au_sort(unsigned long long *K, unsigned *P) {
-    constexpr int N = 2 * CAP;
-    for (int k = 2; k <= N; k <<= 1) {
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            for (int t = threadIdx.x; t < N / 2; t += AU_SEL_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const unsigned long long ki = K[i], kl = K[l];
-                const unsigned pi = P[i], pl = P[l];
-                const bool gt = ki > kl || (ki == kl && pi > pl);
-                if (gt == ((i & k) == 0)) { K[i] = kl; K[l] = ki; P[i] = pl; P[l] = pi; }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// K / P [0, CAP): the best keys so far, sorted; [CAP, 2 CAP): the staged survivors of the tiles since the last sort
+// the selection itself is au_select_segment (au_select.h, shared with stage_e_peers.hip); this kernel writes the audience's outputs
 // FLOOR: a scored candidate below min_score is dropped and counted; FLOOR = false is the selection of the unfiltered call
 template <int CAP, bool FLOOR>
 __global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query, int n_top, int rank_by, const long long *cand_ptr,
@@ -223,7 +196,6 @@ __global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query,
                                                               unsigned long long *stats /*[0] dropped candidates, [1] largest segment,
                                                                                           [2] candidates below the floor*/,
                                                               double min_score) {
-    static_assert(CAP >= AU_SEL_THREADS && (CAP & (CAP - 1)) == 0, "the staging area takes a tile; bitonic sizes");
     __shared__ unsigned long long K[2 * CAP];
     __shared__ unsigned P[2 * CAP];
     __shared__ int s_staged, s_dropped, s_floored, s_have;
@@ -231,44 +203,9 @@ __global__ __launch_bounds__(AU_SEL_THREADS) void k_au_select(long long n_query,
     const long long q = blockIdx.x;
     if (q >= n_query) return;
     const long long a = cand_ptr[q], b = cand_ptr[q + 1];
-    const double *score = rank_by ? decay : plain;
-    for (int k = tid; k < 2 * CAP; k += AU_SEL_THREADS) { K[k] = AU_NO_KEY; P[k] = AU_NO_POS; }
-    if (tid == 0) { s_staged = 0; s_dropped = 0; s_floored = 0; s_have = 0; }
-    __syncthreads();
+    if (tid == 0) { s_dropped = 0; s_floored = 0; s_have = 0; }
     int dropped = 0, floored = 0;
-    long long p = a;
-    while (p < b) {
-        const int staged = s_staged;
-        __syncthreads();                        // every thread has read the count before a tile adds to it
-        const int tiles = (CAP - staged) / AU_SEL_THREADS;
-        if (tiles == 0) {                       // no room for another tile: sort, the best CAP stay, the staging area is blank again
-            au_sort<CAP>(K, P);
-            for (int k = CAP + tid; k < 2 * CAP; k += AU_SEL_THREADS) { K[k] = AU_NO_KEY; P[k] = AU_NO_POS; }
-            if (tid == 0) s_staged = 0;
-            __syncthreads();
-            continue;
-        }
-        // as many tiles as the staging area has room for, against one N-th key
-        const unsigned long long wk = K[n_top - 1];
-        const unsigned wp = P[n_top - 1];
-        for (int t = 0; t < tiles && p < b; t++, p += AU_SEL_THREADS) {
-            const long long x = p + tid;
-            if (x >= b) continue;
-            if (status[x] != 0) { dropped++; continue; }
-            const double xs = score[x];
-            if constexpr (FLOOR) {
-                if (xs < min_score) { floored++; continue; }    // the floor: kept iff score >= min_score
-            }
-            const unsigned long long xk = au_key(xs);
-            const unsigned xp = (unsigned)(x - a);
-            if (xk < wk || (xk == wk && xp < wp)) {
-                const int at = CAP + atomicAdd(&s_staged, 1);
-                K[at] = xk; P[at] = xp;
-            }
-        }
-        __syncthreads();
-    }
-    if (s_staged > 0) au_sort<CAP>(K, P);
+    au_select_segment<CAP, FLOOR>(a, b, n_top, rank_by ? decay : plain, status, min_score, K, P, &s_staged, dropped, floored);
     int have = 0;
     for (int j = tid; j < n_top; j += AU_SEL_THREADS) {
         const size_t o = (size_t)q * n_top + j;

@@ -1,0 +1,559 @@
+// stage_e_peers.hip -- similar users on the device: for every query user the N resident users whose profiles are most alike
+// (DESIGN.md 4 "Peers").  The transpose of the item fold-in (stage_e_itemfold.hip): there one new item against the items of its
+// raters' profiles, here one user against the holders of the items of its own profile; the same "sort, don't hash" -- expand
+// records, stable radix_sort_pairs, run heads, one lane per run -- and no floating-point atomic, so the bits depend on neither
+// the grid nor the chunking.
+//
+// x(p) = prof_rating[p] - centre[prof_item[p]] (centre == NULL: the rating itself); a row is VALID iff 0 <= prof_item[p] < I.
+// The index (xmap_peer_index): the item-major transposition of the valid resident rows in HOLDER ORDER (ascending row index = user
+// ascending, then profile order), x beside the user, and nrm(u) = sqrt(the bilinear form of u with itself) of every user.
+//   k_pr_item_keys : key = the row's item (invalid: I, sorted behind everything), value = the row -> radix_sort_pairs (stable)
+//   k_pr_hd_ptr    : hd_ptr[i] = the first sorted position whose key is >= i (bisection), i <= I
+//   k_pr_hd_fill   : hd_user (bisection of prof_ptr) and hd_x per sorted position
+//   k_pr_norm      : one wave per user; the wave finds the rows r with the item of row p by ballot, every lane runs the same
+//                    double-double chain in record order (p in profile order, r in profile order)
+// The rows (xmap_peer_rows): the queries are cut into chunks of consecutive queries whose records number at most max_records.
+//   k_pr_qlen / k_pr_count : rows per query -> scan; records per query row = holders of its item (under a mask: the ELIGIBLE
+//                    holders, one wave per row counting ballots) -> scan = rec_off
+//   k_pr_expand    : one thread per record (its row and query by bisection): key = (q - q0) << user_bits | v, value = the record's
+//                    index, t = fl(x(p) x(h)).  k_pr_expand_masked: one wave per query row walks the holders and compacts the
+//                    eligible ones in holder order -- no record of an ineligible user is written
+//   radix_sort_pairs : stable, so the records of one (q, v) stay in expansion order
+//   k_pr_heads -> scan -> k_pr_starts, k_pr_first : runs, and per query of the chunk its first run
+//   k_pr_reduce    : one lane per run: self rule, exclusion list, min_common, dot = the double-double chain, sim, the floor
+//   k_pr_select    : au_select_segment (au_select.h) over the runs of a query; position in the segment ascends with the user
+#include <vector>
+
+#include "common.h"
+#include "au_select.h"
+#include "predict_rows.h"
+#include "rec_filter.h"
+#include "tri.h"
+
+namespace xmap {
+
+constexpr long long PR_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (64 B each: 270 MB of temporaries)
+constexpr int PR_NOT_CANDIDATE = 1, PR_DROPPED = 2;     // status of a run (0: scored and kept)
+
+__device__ __forceinline__ double pr_x(const int *item, const double *rating, const double *centre, long long p) {
+    return centre ? rating[p] - centre[item[p]] : rating[p];
+}
+
+// the last k in [lo, hi) with a[k] <= x (a non-decreasing, a[lo] <= x)
+__device__ __forceinline__ long long pr_last_le(const long long *a, long long lo, long long hi, long long x) {
+    while (hi - lo > 1) {
+        const long long mid = (lo + hi) >> 1;
+        if (a[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_pr_item_keys(long long n_rows, int I, const int *pitem, unsigned long long *keys, int *vals) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const int it = pitem[r];
+    keys[r] = (it < 0 || it >= I) ? (unsigned long long)I : (unsigned long long)it;
+    vals[r] = (int)r;
+}
+
+__global__ __launch_bounds__(256) void k_pr_hd_ptr(int I, long long n_rows, const unsigned long long *keys, long long *hd_ptr) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > I) return;
+    long long lo = 0, hi = n_rows;              // first position in [0, n_rows] with key >= i
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (keys[mid] >= (unsigned long long)i) hi = mid; else lo = mid + 1;
+    }
+    hd_ptr[i] = lo;
+}
+
+__global__ __launch_bounds__(256) void k_pr_hd_fill(long long n_rows, long long U, int I, const unsigned long long *keys, const int *vals,
+                                                    const long long *pptr, const int *pitem, const double *prating, const double *centre,
+                                                    int *hd_user, double *hd_x) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_rows) return;
+    if (keys[t] >= (unsigned long long)I) { hd_user[t] = -1; hd_x[t] = 0.0; return; }   // behind hd_ptr[I]: never read
+    const long long r = vals[t];
+    hd_user[t] = (int)pr_last_le(pptr, 0, U, r);        // users without rows are passed over
+    hd_x[t] = pr_x(pitem, prating, centre, r);
+}
+
+// one wave per entry k of the list: user u = sel ? sel[k] : k; out[k] = nrm(u), 0.0 for a user outside [0, U)
+// (base: the first entry of this launch -- for_pair_ranges of predict_rows.h keeps every grid below 2^32 threads)
+__global__ __launch_bounds__(256) void k_pr_norm(long long base, long long n, const int *sel, long long U, int I, const long long *pptr, const int *pitem,
+                                                 const double *prating, const double *centre, double *out) {
+    const long long k = base + (long long)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
+    if (k >= n) return;                         // (wave-uniform)
+    const int lane = lane_id();
+    const long long u = sel ? (long long)sel[k] : k;
+    long long p0 = 0, p1 = 0;
+    if (u >= 0 && u < U) { p0 = pptr[u]; p1 = pptr[u + 1]; }
+    double hi = 0.0, lo = 0.0;
+    for (long long p = p0; p < p1; p++) {
+        const int ip = pitem[p];
+        if (ip < 0 || ip >= I) continue;        // (wave-uniform)
+        const double xp = pr_x(pitem, prating, centre, p);
+        for (long long base = p0; base < p1; base += WAVE) {
+            const long long r = base + lane;
+            const bool m = r < p1 && pitem[r] == ip;
+            const double xr = m ? pr_x(pitem, prating, centre, r) : 0.0;
+            unsigned long long mask = __ballot(m);
+            while (mask) {                      // every lane runs the same chain
+                const int l = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                dd_add(hi, lo, xp * __shfl(xr, l, WAVE));
+            }
+        }
+    }
+    if (lane == 0) out[k] = sqrt(hi);           // a negative or NaN sum: NaN
+}
+
+// rows of query q in the query CSR: 0 for a query user outside it
+__global__ __launch_bounds__(256) void k_pr_qlen(long long n_query, const int *query_user, long long n_q_users, const long long *qptr, int *qlen) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_query) return;
+    const long long a = query_user[q];
+    qlen[q] = (a >= 0 && a < n_q_users) ? (int)(qptr[a + 1] - qptr[a]) : 0;
+}
+
+__device__ __forceinline__ bool pr_allowed(const unsigned int *allow, int v) { return (allow[v >> 5] >> (v & 31)) & 1u; }
+
+// records of flattened query row e (one wave per row): the holders of its item, under a mask the eligible ones
+__global__ __launch_bounds__(256) void k_pr_count(long long base, long long n_qrows, long long n_query, const long long *qrow_off, const int *query_user,
+                                                  const long long *qptr, const int *qitem, int I, const long long *hd_ptr, const int *hd_user,
+                                                  const unsigned int *allow, int *cnt) {
+    const long long e = base + (long long)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
+    if (e >= n_qrows) return;
+    const int lane = lane_id();
+    const long long q = pr_last_le(qrow_off, 0, n_query, e);
+    const long long p = qptr[query_user[q]] + (e - qrow_off[q]);
+    const int it = qitem[p];
+    int c = 0;
+    if (it >= 0 && it < I) {
+        const long long h0 = hd_ptr[it], h1 = hd_ptr[it + 1];
+        if (!allow) c = (int)(h1 - h0);
+        else
+            for (long long base = h0; base < h1; base += WAVE) {
+                const long long h = base + lane;
+                c += __popcll(__ballot(h < h1 && pr_allowed(allow, hd_user[h])));
+            }
+    }
+    if (lane == 0) cnt[e] = c;
+}
+
+// qrec[q] = records in front of query q = rec_off[qrow_off[q]], q <= n_query
+__global__ __launch_bounds__(256) void k_pr_qrec(long long n_query, const long long *qrow_off, const long long *rec_off, long long *qrec) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q <= n_query) qrec[q] = rec_off[qrow_off[q]];
+}
+
+__global__ __launch_bounds__(256) void k_pr_expand(long long n, long long rec0, long long e0, long long e1, long long q0, long long q1,
+                                                   const long long *qrow_off, const long long *rec_off, const int *query_user,
+                                                   const long long *qptr, const int *qitem, const double *qrating, const double *centre,
+                                                   const long long *hd_ptr, const int *hd_user, const double *hd_x, int user_bits,
+                                                   unsigned long long *keys, int *vals, double *tv) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const long long g = rec0 + t;
+    const long long e = pr_last_le(rec_off, e0, e1, g);         // rows without records are passed over
+    const long long q = pr_last_le(qrow_off, q0, q1, e);        // queries without rows too
+    const long long p = qptr[query_user[q]] + (e - qrow_off[q]);
+    const long long h = hd_ptr[qitem[p]] + (g - rec_off[e]);    // (a row with records has a valid item)
+    keys[t] = ((unsigned long long)(q - q0) << user_bits) | (unsigned long long)(unsigned)hd_user[h];
+    vals[t] = (int)t;
+    tv[t] = pr_x(qitem, qrating, centre, p) * hd_x[h];
+}
+
+// under a mask: one wave per query row of the chunk, the eligible holders compacted in holder order at rec_off[e] - rec0
+__global__ __launch_bounds__(256) void k_pr_expand_masked(long long rec0, long long e0, long long e1, long long q0, long long q1,
+                                                          const long long *qrow_off, const long long *rec_off, const int *query_user,
+                                                          const long long *qptr, const int *qitem, const double *qrating,
+                                                          const double *centre, int I, const long long *hd_ptr, const int *hd_user,
+                                                          const double *hd_x, const unsigned int *allow, int user_bits,
+                                                          unsigned long long *keys, int *vals, double *tv) {
+    const long long e = e0 + (long long)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
+    if (e >= e1) return;
+    const int lane = lane_id();
+    const long long end = rec_off[e + 1] - rec0;
+    long long o = rec_off[e] - rec0;
+    if (o == end) return;                       // no eligible holder (or an invalid item)
+    const long long q = pr_last_le(qrow_off, q0, q1, e);
+    const long long p = qptr[query_user[q]] + (e - qrow_off[q]);
+    const int it = qitem[p];
+    if (it < 0 || it >= I) return;
+    const double xp = pr_x(qitem, qrating, centre, p);
+    const long long h1 = hd_ptr[it + 1];
+    for (long long base = hd_ptr[it]; base < h1; base += WAVE) {
+        const long long h = base + lane;
+        const int v = h < h1 ? hd_user[h] : 0;
+        const bool m = h < h1 && pr_allowed(allow, v);
+        const unsigned long long mask = __ballot(m);
+        const long long at = o + __popcll(mask & lanemask_lt());
+        if (m && at < end) {                    // (at < end: the count pass saw the same mask)
+            keys[at] = ((unsigned long long)(q - q0) << user_bits) | (unsigned long long)(unsigned)v;
+            vals[at] = (int)at;
+            tv[at] = xp * hd_x[h];
+        }
+        o += __popcll(mask);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pr_heads(long long n, const unsigned long long *keys, int *head) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) head[t] = (t == 0 || keys[t] != keys[t - 1]) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_pr_starts(long long n, const int *head, const long long *run_idx, int *run_start) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    if (head[t]) run_start[run_idx[t]] = (int)t;
+    if (t == 0) run_start[run_idx[n]] = (int)n;
+}
+
+// first[x] = index of the first run of local query x, x <= nq: run_idx at the first sorted position whose query is >= x
+__global__ __launch_bounds__(256) void k_pr_first(long long nq, long long n, const unsigned long long *keys, int user_bits,
+                                                  const long long *run_idx, long long *first) {
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x > nq) return;
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if ((keys[mid] >> user_bits) >= (unsigned long long)x) hi = mid; else lo = mid + 1;
+    }
+    first[x] = run_idx[lo];
+}
+
+// one lane per run, records in sorted (= expansion) order.  cnt: [0] dropped by min_common, [1] non-finite, [2] below the floor
+__global__ __launch_bounds__(256) void k_pr_reduce(long long n, const unsigned long long *keys, const int *vals, const double *tv,
+                                                   const long long *run_idx, const int *run_start, int user_bits, long long q0,
+                                                   const int *query_user, int same, int keep_self, const long long *ex_ptr,
+                                                   const int *ex_id, int min_common, int cap, double min_score, const double *qnrm,
+                                                   const double *nrm, int *r_status, double *r_sim, int *r_common,
+                                                   unsigned long long *cnt) {
+    const long long n_runs = run_idx[n];
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < n_runs; r += step) {
+        const int s = run_start[r], e = run_start[r + 1];
+        const unsigned long long key = keys[s];
+        const long long q = q0 + (long long)(key >> user_bits);
+        const int v = (int)(key & ((1ull << user_bits) - 1ull));
+        const int nc = e - s;
+        r_common[r] = nc;
+        r_sim[r] = 0.0;
+        bool out = same && !keep_self && v == query_user[q];
+        if (!out && ex_ptr) {
+            const long long x1 = ex_ptr[q + 1];
+            for (long long x = ex_ptr[q]; x < x1 && !out; x++) out = ex_id[x] == v;
+        }
+        if (out) { r_status[r] = PR_NOT_CANDIDATE; continue; }
+        if (nc < min_common) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[0], 1ull); continue; }
+        double dot = 0.0, lo = 0.0;
+        for (int t = s; t < e; t++) dd_add(dot, lo, tv[vals[t]]);
+        const double np = qnrm[q] * nrm[v];
+        const double sim = weighted((np != 0.0) ? dot / np : 0.0, nc, cap);     // NaN != 0: divides
+        if (!(fabs(sim) <= 1.7976931348623157e308)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
+        if (sim < min_score) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[2], 1ull); continue; }
+        r_sim[r] = sim;
+        r_status[r] = 0;
+    }
+}
+
+// one block per query of the chunk: its runs are the segment [first[x], first[x + 1]), in ascending user index
+// cnt: [3] candidates after the self rule, the exclusions and the mask, [4] the largest such count of one query
+template <int CAP>
+__global__ __launch_bounds__(AU_SEL_THREADS) void k_pr_select(long long nq, long long q0, int n_top, const long long *first,
+                                                              const unsigned long long *keys, const int *run_start, int user_bits,
+                                                              const int *r_status, const double *r_sim, const int *r_common,
+                                                              int *out_cnt, int *out_user, double *out_sim, int *out_common,
+                                                              unsigned long long *cnt) {
+    __shared__ unsigned long long K[2 * CAP];
+    __shared__ unsigned P[2 * CAP];
+    __shared__ int s_staged, s_have, s_cand;
+    const int tid = threadIdx.x;
+    const long long x = blockIdx.x;
+    if (x >= nq) return;
+    const long long a = first[x], b = first[x + 1];
+    if (tid == 0) { s_have = 0; s_cand = 0; }
+    int dropped = 0, floored = 0, cand = 0;
+    for (long long r = a + tid; r < b; r += AU_SEL_THREADS) cand += r_status[r] != PR_NOT_CANDIDATE ? 1 : 0;
+    au_select_segment<CAP, false>(a, b, n_top, r_sim, r_status, 0.0, K, P, &s_staged, dropped, floored);
+    int have = 0;
+    for (int j = tid; j < n_top; j += AU_SEL_THREADS) {
+        const size_t o = (size_t)(q0 + x) * n_top + j;
+        const unsigned pos = P[j];
+        const bool v = pos != AU_NO_POS;
+        have += v ? 1 : 0;
+        out_user[o] = v ? (int)(keys[run_start[a + pos]] & ((1ull << user_bits) - 1ull)) : -1;
+        out_sim[o] = v ? r_sim[a + pos] : 0.0;
+        out_common[o] = v ? r_common[a + pos] : 0;
+    }
+    if (have) atomicAdd(&s_have, have);
+    if (cand) atomicAdd(&s_cand, cand);
+    __syncthreads();
+    if (tid == 0) {
+        out_cnt[q0 + x] = s_have;
+        if (s_cand) { atomicAdd(&cnt[3], (unsigned long long)s_cand); atomicMax(&cnt[4], (unsigned long long)s_cand); }
+    }
+}
+
+// the outputs of a query without records: count 0 and the padding
+__global__ __launch_bounds__(256) void k_pr_blank(long long n_query, int n_top, int *out_cnt, int *out_user, double *out_sim, int *out_common) {
+    const long long total = n_query * n_top, step = (long long)gridDim.x * blockDim.x;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += step) {
+        if (k < n_query) out_cnt[k] = 0;
+        out_user[k] = -1; out_sim[k] = 0.0; out_common[k] = 0;
+    }
+}
+
+// avg[i] of the x of item i's holders: the exact double-double sum rounded once, divided by the entries -- what item_stats.h
+// computes for an item of RecommenderSim (lane-strided sums, the fixed butterfly of dd_reduce); one wave per item
+__global__ __launch_bounds__(256) void k_pr_centre(long long base, long long I, const long long *hd_ptr, const double *hd_x, double *avg) {
+    const long long i = base + (long long)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
+    const bool on = i < I;
+    const int lane = lane_id();
+    long long p0 = 0, p1 = 0;
+    if (on) { p0 = hd_ptr[i]; p1 = hd_ptr[i + 1]; }
+    double s = 0.0, slo = 0.0;
+    for (long long p = p0 + lane; p < p1; p += WAVE) dd_add(s, slo, hd_x[p]);
+    dd_reduce<WAVE>(s, slo);
+    if (on && lane == 0) avg[i] = (p1 > p0) ? 1.0 * s / (double)(p1 - p0) : 0.0;
+}
+
+static int pr_bits_for(long long v) {   // bits that hold 0 .. v - 1, at least one
+    int b = 1;
+    while (b < 62 && (1ll << b) < v) b++;
+    return b;
+}
+
+static unsigned pr_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+
+constexpr long long PR_SELECT_RANGE = 1ll << 23;        // queries (one block of 256 threads each) per launch of the selection
+static_assert(PR_SELECT_RANGE * AU_SEL_THREADS < (1ll << 32), "the grid of a range stays below 2^32 threads");
+constexpr unsigned PR_BLANK_BLOCKS = 1u << 20;          // blocks of the grid-stride fill of the outputs
+
+template <int CAP, class... A>
+static int pr_select_ranges(hipStream_t st, long long nq, long long q0, int n_top, const long long *first, A... a) {
+    for (long long x0 = 0; x0 < nq; x0 += PR_SELECT_RANGE) {       // the queries of a range: first + x0, outputs from q0 + x0
+        const long long m = nq - x0 < PR_SELECT_RANGE ? nq - x0 : PR_SELECT_RANGE;
+        k_pr_select<CAP><<<dim3((unsigned)m), dim3(AU_SEL_THREADS), 0, st>>>(m, q0 + x0, n_top, first + x0, a...);
+        XM_LAUNCH_CHECK();
+    }
+    return XMAP_OK;
+}
+
+static int pr_norms(hipStream_t st, long long n, const int *sel, long long U, int I, const long long *pptr, const int *pitem,
+                    const double *prating, const double *centre, double *out) {
+    return for_pair_ranges(n, 4, [&](long long base, long long end, dim3 grid) {
+        k_pr_norm<<<grid, dim3(256), 0, st>>>(base, end, sel, U, I, pptr, pitem, prating, centre, out);
+    });
+}
+
+}  // namespace xmap
+
+using namespace xmap;
+
+extern "C" {
+
+int xmap_peer_index(void *stream, int64_t n_users, int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item,
+                    const double *prof_rating, const double *centre, int64_t *hd_ptr, int32_t *hd_user, double *hd_x, double *nrm,
+                    int64_t *h_rows) {
+    XM_ARG(n_users >= 0 && n_users < 2147483647ll && n_items >= 0 && prof_ptr && hd_ptr && (n_users == 0 || nrm));
+    hipStream_t st = (hipStream_t)stream;
+    XM_SCOPE(st);
+    if (h_rows) *h_rows = 0;
+    const int I = n_items;
+    long long n_rows = 0;
+    XM_HIP(hipMemcpyAsync(&n_rows, prof_ptr + n_users, sizeof(long long), hipMemcpyDeviceToHost, st));
+    XM_HIP(hipStreamSynchronize(st));
+    XM_ARG(n_rows >= 0 && n_rows < 2147483647ll);
+    XM_ARG(n_rows == 0 || (prof_item && prof_rating && hd_user && hd_x));
+    if (n_rows == 0) {
+        XM_HIP(hipMemsetAsync(hd_ptr, 0, sizeof(int64_t) * ((size_t)I + 1), st));
+    } else {
+        const size_t nr = (size_t)n_rows;
+        unsigned long long *keys = nullptr;
+        int *vals = nullptr;
+        XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nr, st));
+        XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nr, st));
+        const unsigned nb = pr_blocks(n_rows, 256);
+        k_pr_item_keys<<<dim3(nb), dim3(256), 0, st>>>(n_rows, I, prof_item, keys, vals);
+        XM_LAUNCH_CHECK();
+        int rc = radix_sort_pairs(st, keys, vals, keys + nr, vals + nr, n_rows, pr_bits_for((long long)I + 1));
+        if (rc) return rc;
+        k_pr_hd_ptr<<<dim3(pr_blocks((long long)I + 1, 256)), dim3(256), 0, st>>>(I, n_rows, keys, (long long *)hd_ptr);
+        XM_LAUNCH_CHECK();
+        k_pr_hd_fill<<<dim3(nb), dim3(256), 0, st>>>(n_rows, n_users, I, keys, vals, (const long long *)prof_ptr, prof_item, prof_rating,
+                                                     centre, hd_user, hd_x);
+        XM_LAUNCH_CHECK();
+    }
+    if (n_users > 0) {
+        const int rc = pr_norms(st, n_users, nullptr, n_users, I, (const long long *)prof_ptr, prof_item, prof_rating, centre, nrm);
+        if (rc) return rc;
+    }
+    long long rows = 0;
+    XM_HIP(hipMemcpyAsync(&rows, hd_ptr + I, sizeof(long long), hipMemcpyDeviceToHost, st));
+    XM_HIP(hipStreamSynchronize(st));
+    if (h_rows) *h_rows = rows;
+    return XMAP_OK;
+}
+
+int xmap_peer_centre(void *stream, int32_t n_items, const int64_t *hd_ptr, const double *hd_x, double *centre) {
+    XM_ARG(n_items >= 0 && (n_items == 0 || (hd_ptr && centre)));
+    hipStream_t st = (hipStream_t)stream;
+    return for_pair_ranges(n_items, 4, [&](long long base, long long, dim3 grid) {
+        k_pr_centre<<<grid, dim3(256), 0, st>>>(base, n_items, (const long long *)hd_ptr, hd_x, centre);
+    });
+}
+
+int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int64_t n_q_users, const int64_t *q_ptr, const int32_t *q_item,
+                   const double *q_rating, int32_t flags, int32_t n_top, int32_t cap, int32_t min_common, int64_t n_users, int32_t n_items,
+                   const double *centre, const int64_t *hd_ptr, const int32_t *hd_user, const double *hd_x, const double *nrm,
+                   int64_t max_records, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, const xmap_rec_filter *F,
+                   int64_t *h_stats) {
+    // the host checks: before any device work
+    XM_ARG(n_top >= 1 && n_top <= AU_MAX_TOP);
+    XM_ARG(cap >= 1);
+    XM_ARG(min_common >= 1);
+    XM_ARG((flags & ~(XMAP_PEERS_SAME | XMAP_PEERS_KEEP_SELF)) == 0);
+    XM_ARG(n_query >= 0 && n_query <= (1ll << 28) && n_q_users >= 0 && n_users >= 0 && n_users < 2147483647ll && n_items >= 0 &&
+           max_records >= 0);
+    XM_ARG(n_query == 0 || (query_user && q_ptr && hd_ptr && out_cnt && out_user && out_sim && out_common));
+    XM_ARG(n_query == 0 || n_users == 0 || n_items == 0 || (q_item && q_rating && hd_user && hd_x && nrm));
+    hipStream_t st = (hipStream_t)stream;
+    XM_SCOPE(st);
+    if (h_stats) for (int k = 0; k < 6; k++) h_stats[k] = 0;
+    bool filt = false;
+    double min_score = 0.0;
+    int rc = rf_prepare(st, n_query, F, &filt, &min_score);     // a NaN floor; ex_ptr, on the device
+    if (rc) return rc;
+    if (n_query == 0) return XMAP_OK;
+    const unsigned int *allow = filt ? (const unsigned int *)F->allow : nullptr;
+    const long long *ex_ptr = filt ? (const long long *)F->ex_ptr : nullptr;
+    const int *ex_id = filt ? F->ex_id : nullptr;
+    const int I = n_items;
+    const size_t nq1 = (size_t)n_query + 1;
+    // ---- rows per query, records per row (the outputs are first written once the row count has passed)
+    int *qlen = nullptr;
+    long long *qrow_off = nullptr;
+    int64_t n_qrows = 0;
+    XM_HIP(xm_malloc_async((void **)&qlen, sizeof(int) * (size_t)n_query, st));
+    XM_HIP(xm_malloc_async((void **)&qrow_off, sizeof(long long) * nq1, st));
+    k_pr_qlen<<<dim3(pr_blocks(n_query, 256)), dim3(256), 0, st>>>(n_query, query_user, n_q_users, (const long long *)q_ptr, qlen);
+    XM_LAUNCH_CHECK();
+    if ((rc = xmap_exclusive_scan_i32_to_i64(st, qlen, (int64_t *)qrow_off, n_query, &n_qrows))) return rc;
+    XM_ARG(n_qrows < 2147483647ll);
+    {
+        const long long cells = (long long)n_query * n_top;
+        const unsigned bb = pr_blocks(cells, 256);
+        k_pr_blank<<<dim3(bb < PR_BLANK_BLOCKS ? bb : PR_BLANK_BLOCKS), dim3(256), 0, st>>>(n_query, n_top, out_cnt, out_user, out_sim, out_common);
+        XM_LAUNCH_CHECK();
+    }
+    if (n_qrows == 0 || n_users == 0 || I == 0) { XM_HIP(hipStreamSynchronize(st)); return XMAP_OK; }
+    const size_t ne = (size_t)n_qrows;
+    int *rcnt = nullptr;
+    long long *rec_off = nullptr, *qrec = nullptr;
+    double *qnrm = nullptr;
+    XM_HIP(xm_malloc_async((void **)&rcnt, sizeof(int) * ne, st));
+    XM_HIP(xm_malloc_async((void **)&rec_off, sizeof(long long) * (ne + 1), st));
+    XM_HIP(xm_malloc_async((void **)&qrec, sizeof(long long) * nq1, st));
+    XM_HIP(xm_malloc_async((void **)&qnrm, sizeof(double) * (size_t)n_query, st));
+    rc = for_pair_ranges(n_qrows, 4, [&](long long base, long long end, dim3 grid) {
+        k_pr_count<<<grid, dim3(256), 0, st>>>(base, end, n_query, qrow_off, query_user, (const long long *)q_ptr, q_item, I,
+                                               (const long long *)hd_ptr, hd_user, allow, rcnt);
+    });
+    if (rc) return rc;
+    if ((rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rec_off, n_qrows, nullptr))) return rc;
+    k_pr_qrec<<<dim3(pr_blocks(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, qrow_off, rec_off, qrec);
+    XM_LAUNCH_CHECK();
+    if ((rc = pr_norms(st, n_query, query_user, n_q_users, I, (const long long *)q_ptr, q_item, q_rating, centre, qnrm))) return rc;
+    std::vector<long long> h_row(nq1), h_rec(nq1);
+    XM_HIP(hipMemcpyAsync(h_row.data(), qrow_off, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    XM_HIP(hipMemcpyAsync(h_rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    XM_HIP(hipStreamSynchronize(st));
+    // ---- chunks of consecutive queries: [q0, q1) with at most max_records records, or one query
+    if (max_records <= 0) max_records = PR_MAX_RECORDS;
+    if (max_records > 2147483646ll) max_records = 2147483646ll;    // a chunk of several queries stays below 2^31 - 1 records: only a
+                                                                   // single query can reach the capacity error below
+    std::vector<long long> cut;
+    cut.push_back(0);
+    long long n_max = 0, nq_max = 0;
+    for (long long q0 = 0; q0 < n_query;) {
+        long long q1 = q0 + 1;
+        while (q1 < n_query && h_rec[q1 + 1] - h_rec[q0] <= max_records) q1++;
+        const long long n = h_rec[q1] - h_rec[q0];
+        if (n >= 2147483647ll) {
+            set_error("peers: query %lld expands to %lld records, a chunk holds fewer than 2^31", q0, n);
+            return XMAP_ERR_CAPACITY;
+        }
+        n_max = n > n_max ? n : n_max;
+        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
+        cut.push_back(q1);
+        q0 = q1;
+    }
+    unsigned long long *cnt = nullptr, h[5] = {0, 0, 0, 0, 0};
+    XM_HIP(xm_malloc_async((void **)&cnt, sizeof(h), st));
+    XM_HIP(hipMemsetAsync(cnt, 0, sizeof(h), st));
+    if (n_max > 0) {
+        const int user_bits = pr_bits_for(n_users);
+        XM_ARG(user_bits + pr_bits_for(nq_max) <= 62);
+        const size_t nm = (size_t)n_max;
+        unsigned long long *keys = nullptr;
+        int *vals = nullptr, *head = nullptr, *run_start = nullptr, *r_status = nullptr, *r_common = nullptr;
+        long long *run_idx = nullptr, *first = nullptr;
+        double *tv = nullptr, *r_sim = nullptr;
+        XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
+        XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
+        XM_HIP(xm_malloc_async((void **)&tv, sizeof(double) * nm, st));
+        XM_HIP(xm_malloc_async((void **)&head, sizeof(int) * nm, st));
+        XM_HIP(xm_malloc_async((void **)&run_idx, sizeof(long long) * (nm + 1), st));
+        XM_HIP(xm_malloc_async((void **)&run_start, sizeof(int) * (nm + 1), st));
+        XM_HIP(xm_malloc_async((void **)&first, sizeof(long long) * ((size_t)nq_max + 1), st));
+        XM_HIP(xm_malloc_async((void **)&r_status, sizeof(int) * nm, st));
+        XM_HIP(xm_malloc_async((void **)&r_common, sizeof(int) * nm, st));
+        XM_HIP(xm_malloc_async((void **)&r_sim, sizeof(double) * nm, st));
+        const int same = (flags & XMAP_PEERS_SAME) ? 1 : 0, keep_self = (flags & XMAP_PEERS_KEEP_SELF) ? 1 : 0;
+        for (size_t k = 0; k + 1 < cut.size(); k++) {
+            const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
+            const long long n = h_rec[q1] - h_rec[q0];
+            if (n == 0) continue;               // (the blank outputs stand)
+            const unsigned nb = pr_blocks(n, 256);
+            if (allow) {
+                rc = for_pair_ranges(h_row[q1] - h_row[q0], 4, [&](long long base, long long end, dim3 grid) {      // rows [base, end) of the chunk
+                    k_pr_expand_masked<<<grid, dim3(256), 0, st>>>(h_rec[q0], h_row[q0] + base, h_row[q0] + end, q0, q1, qrow_off, rec_off,
+                                                                   query_user, (const long long *)q_ptr, q_item, q_rating, centre, I,
+                                                                   (const long long *)hd_ptr, hd_user, hd_x, allow, user_bits, keys, vals, tv);
+                });
+                if (rc) return rc;
+            } else
+                k_pr_expand<<<dim3(nb), dim3(256), 0, st>>>(n, h_rec[q0], h_row[q0], h_row[q1], q0, q1, qrow_off, rec_off, query_user,
+                                                            (const long long *)q_ptr, q_item, q_rating, centre, (const long long *)hd_ptr,
+                                                            hd_user, hd_x, user_bits, keys, vals, tv);
+            XM_LAUNCH_CHECK();
+            if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, user_bits + pr_bits_for(nq)))) return rc;
+            k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
+            XM_LAUNCH_CHECK();
+            if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
+            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
+            XM_LAUNCH_CHECK();
+            k_pr_first<<<dim3(pr_blocks(nq + 1, 256)), dim3(256), 0, st>>>(nq, n, keys, user_bits, run_idx, first);
+            XM_LAUNCH_CHECK();
+            k_pr_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, keys, vals, tv, run_idx, run_start, user_bits, q0, query_user,
+                                                                            same, keep_self, ex_ptr, ex_id, min_common, cap, min_score, qnrm,
+                                                                            nrm, r_status, r_sim, r_common, cnt);
+            XM_LAUNCH_CHECK();
+            rc = n_top <= 256 ? pr_select_ranges<256>(st, nq, q0, n_top, first, keys, run_start, user_bits, r_status, r_sim, r_common, out_cnt,
+                                                      out_user, out_sim, out_common, cnt)
+                              : pr_select_ranges<1024>(st, nq, q0, n_top, first, keys, run_start, user_bits, r_status, r_sim, r_common, out_cnt,
+                                                       out_user, out_sim, out_common, cnt);
+            if (rc) return rc;
+        }
+    }
+    XM_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    XM_HIP(hipStreamSynchronize(st));
+    if (h_stats) {
+        h_stats[0] = (int64_t)h[3]; h_stats[1] = (int64_t)h[0]; h_stats[2] = (int64_t)h[1]; h_stats[3] = (int64_t)h[2];
+        h_stats[4] = (int64_t)h[4]; h_stats[5] = h_rec[(size_t)n_query];
+    }
+    return XMAP_OK;
+}
+}

@@ -107,6 +107,11 @@ class DivIndex(object):
     pass
 
 
+class PeerIndex(object):
+    """what Engine.peer_index returns: the item-major transposition of a set of profiles and every user's norm"""
+    pass
+
+
 class GenResult(object):
     pass
 
@@ -1952,6 +1957,69 @@ class Engine(object):
                                          vp(item_avg.contiguous()), vp(wtab), i32(wtab.numel()), vp(out_cnt), vp(out_user), vp(out_plain),
                                          vp(out_decay), h))
         return out_cnt[:Q], out_user[:Q], out_plain[:Q], out_decay[:Q], tuple(int(x) for x in h)
+
+    def peer_index(self, P, centre=None):
+        """The peer index of the profiles P (xmap_peer_index): the item-major transposition of P's valid rows in holder order
+        (ascending row index) with x = rating - centre[item] beside the user (centre None: the rating itself), and nrm [users].
+        Returns a handle (n_users, n_items, centre, hd_ptr, hd_user, hd_x, nrm, n_rows = rows indexed) on the device; it belongs
+        to the profiles and the centring, whatever is asked of it."""
+        X = PeerIndex()
+        X.n_users, X.n_items = int(P.n_users), int(P.n_items)
+        X.centre = None if centre is None else centre.contiguous()
+        n = int(P.user_item.numel())
+        X.hd_ptr = self._empty(X.n_items + 1, torch.int64)
+        X.hd_user, X.hd_x = self._empty(max(n, 1), torch.int32), self._empty(max(n, 1), torch.float64)
+        X.nrm = self._empty(max(X.n_users, 1), torch.float64)
+        rows = C.c_int64(0)
+        with self.timed("peer_index"):
+            check(lib.xmap_peer_index(_stream(self.dev), i64(X.n_users), i32(X.n_items), vp(P.user_ptr), vp(P.user_item),
+                                      vp(P.user_rating64), vp(X.centre), vp(X.hd_ptr), vp(X.hd_user), vp(X.hd_x), vp(X.nrm),
+                                      C.byref(rows)))
+        X.n_rows = int(rows.value)
+        return X
+
+    def peer_centre(self, index):
+        """The item averages of the profiles behind an UNCENTRED peer_index() handle (xmap_peer_centre): per item the exact sum of
+        its holders' ratings rounded once, divided by the entries -- the averages RecommenderSim computes, without its pair pass.
+        Returns a float64 tensor [items]: pass it to peer_index(P, centre) for the centred index."""
+        if index.centre is not None:
+            raise ValueError("peer_centre: the averages are taken over an index built without a centre")
+        avg = self._empty(max(index.n_items, 1), torch.float64)
+        with self.timed("peer_centre"):
+            check(lib.xmap_peer_centre(_stream(self.dev), i32(index.n_items), vp(index.hd_ptr), vp(index.hd_x), vp(avg)))
+        return avg[:index.n_items]
+
+    def peers(self, index, Q, query_user, n_top, cap=1, min_common=1, same=False, keep_self=False, allow=None, exclude=None,
+              min_sim=None, max_records=0):
+        """Similar users on the device (xmap_peer_rows): per query user -- an index into the profiles Q, the resident ones (same
+        = True: the user itself leaves unless keep_self) or a fold-in batch -- the n_top (1..1024) users of the peer_index() handle
+        with the largest sim = cosine of the centred profiles * min(common, cap) / cap; sim descending, user index ascending.
+        allow = the users who may be returned (bool tensor [users] or packed words; it acts in the expansion), exclude = (ptr, ids)
+        of users never returned per QUERY, min_sim = floor.  Returns (cnt [Q], user [Q][n_top] (-1 behind the count), sim
+        [Q][n_top], common [Q][n_top], stats) with stats = (candidates, dropped by min_common, dropped as non-finite, dropped below
+        the floor, largest candidate count of a query, records expanded).  max_records: the chunk bound (0: the library's)."""
+        st = _stream(self.dev)
+        n_q, n_top = int(query_user.numel()), int(n_top)
+        if not 1 <= n_top <= 1024:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 1024" % n_top)
+        if int(cap) < 1 or int(min_common) < 1:
+            raise ValueError("cap = %r, min_common = %r: both >= 1" % (cap, min_common))
+        out_cnt = self._empty(max(n_q, 1), torch.int32)
+        out_user, out_common = self._empty((max(n_q, 1), n_top), torch.int32), self._empty((max(n_q, 1), n_top), torch.int32)
+        out_sim = self._empty((max(n_q, 1), n_top), torch.float64)
+        F = alive = None
+        if allow is not None or exclude is not None or min_sim is not None:
+            F, alive = self._rec_filter(index.n_users, n_q, allow, exclude, min_sim)
+        flags = (abi.PEERS_SAME if same else 0) | (abi.PEERS_KEEP_SELF if keep_self else 0)
+        h = (C.c_int64 * 6)()
+        with self.timed("peers"):
+            check(lib.xmap_peer_rows(st, i64(n_q), vp(query_user.contiguous()), i64(Q.n_users), vp(Q.user_ptr), vp(Q.user_item),
+                                     vp(Q.user_rating64), i32(flags), i32(n_top), i32(cap), i32(min_common), i64(index.n_users),
+                                     i32(index.n_items), vp(index.centre), vp(index.hd_ptr), vp(index.hd_user), vp(index.hd_x),
+                                     vp(index.nrm), i64(max_records), vp(out_cnt), vp(out_user), vp(out_sim), vp(out_common),
+                                     None if F is None else C.byref(F), h))
+        del alive
+        return out_cnt[:n_q], out_user[:n_q], out_sim[:n_q], out_common[:n_q], tuple(int(x) for x in h)
 
     def explain(self, P, neighbors, pair_user, pair_item, item_avg, wtab, n_ev, rank_by=0):
         """Why a pair scores what it scores (xmap_explain_rows, the pair body of predict() in its explain mode): for the (user,

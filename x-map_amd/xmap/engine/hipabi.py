@@ -23,6 +23,7 @@ AUDIENCE_KEEP_HOLDERS = 1 # XMAP_AUDIENCE_KEEP_HOLDERS: flag of xmap_audience_ro
 SRC_RESIDENT, SRC_FOLDIN, SRC_ITEM_FOLDIN = 0, 1, 2      # XMAP_SRC_*: source of xmap_ctx_recommend_filtered / xmap_ctx_audience_filtered
 GROUP_MEAN, GROUP_MIN, GROUP_MAX = 0, 1, 2      # XMAP_GROUP_*: `how` of xmap_group_topn_rows / xmap_ctx_recommend_group
 GROUP_MAX_MEMBERS = 64    # XMAP_GROUP_MAX_MEMBERS: members of one group
+PEERS_SAME, PEERS_KEEP_SELF, PEERS_CENTRED = 1, 2, 4      # XMAP_PEERS_*: flags of xmap_peer_rows / xmap_ctx_peers
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -98,7 +99,7 @@ class RecFilter(C.Structure):
 
 
 EXPORTS = [
-    "xmap_last_error", "xmap_version", "xmap_trim", "xmap_debug_arena", "xmap_debug_arena_call", "xmap_exclusive_scan_i64", "xmap_exclusive_scan_i32_to_i64",
+    "xmap_last_error", "xmap_version", "xmap_trim", "xmap_debug_arena", "xmap_debug_arena_call", "xmap_debug_sort_pairs", "xmap_exclusive_scan_i64", "xmap_exclusive_scan_i32_to_i64",
     "xmap_exclusive_scan2_i32_to_i64", "xmap_scan_self_tiles", "xmap_sim3_plan_begin", "xmap_sim3_plan_wait", "xmap_sim3_counters_begin", "xmap_sim3_counters_wait",
     "xmap_build_csc", "xmap_user_stats", "xmap_item_stats", 
     "xmap_sim2_layout", "xmap_sim2_plan", "xmap_sim2_units",
@@ -118,6 +119,7 @@ EXPORTS = [
     "xmap_topn_rows_filtered", "xmap_audience_rows_filtered", "xmap_ctx_recommend_filtered", "xmap_ctx_audience_filtered",
     "xmap_div_index", "xmap_diversify_rows", "xmap_ctx_recommend_diverse",
     "xmap_group_topn_rows", "xmap_ctx_recommend_group",
+    "xmap_peer_index", "xmap_peer_centre", "xmap_peer_rows", "xmap_ctx_peers",
 ]
 
 if not os.path.exists(LIB_PATH):

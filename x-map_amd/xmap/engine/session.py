@@ -867,6 +867,86 @@ def recommend_audience_profiles(alterEgoRDD, profiles, items, cap, keep, alpha, 
     return res
 
 
+def _peer_setup(alterEgoRDD, centred, who):
+    """what similar_users and similar_users_profiles share: the profiles of the AlterEgo rows and their peer index -> (state,
+    engine over the profiles, P, index).  centred: x = rating - the item average of the profiles (Engine.peer_centre over the
+    uncentred index: the exact sum rounded once / entries, RecommenderSim's averages without its pair pass).  The set-up -- the
+    profiles, one or two index builds (a stable sort of the profile rows each) and the averages -- is kept on the handle per
+    centring, so only the first call on a handle pays it; a call then costs Engine.peers alone."""
+    from . import device
+    if not isinstance(alterEgoRDD, (AlterEgoUnion, AlterEgoRDD)):
+        raise TypeError("%s() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device) or the "
+                        "AlterEgoUnion of union_alterego" % who)
+    st = alterEgoRDD.state
+    kept = alterEgoRDD.__dict__.setdefault("_peer_setup", {})      # {"P": (engine, profiles), False / True: index}; goes with the handle
+    if "P" not in kept:
+        if isinstance(alterEgoRDD, AlterEgoUnion):
+            P = alterEgoRDD.profiles()
+        else:
+            G = alterEgoRDD.G
+            P = st.engine.alterego_profiles(G, time_key=time_rank(st)[G.time] if G.n_rows else G.time)
+        eng2 = device.Engine(P)
+        eng2.timers = st.engine.timers
+        kept["P"] = (eng2, P)
+    eng2, P = kept["P"]
+    if False not in kept:
+        kept[False] = eng2.peer_index(P)
+    if centred and True not in kept:
+        kept[True] = eng2.peer_index(P, eng2.peer_centre(kept[False]))
+    return st, eng2, P, kept[bool(centred)]
+
+
+def _peer_records(st, eng2, X, Q, query, labels, uids, n, cap, min_common, same, keep_self, ctx, rules):
+    """the peers of the users `query` (indices into the profiles Q, labelled `labels`) among the resident users `uids` -> the
+    LocalRDD of (label, [(uid, sim, common)*]) with .stats (the six of Engine.peers)"""
+    import torch
+    d_q = torch.from_numpy(np.fromiter(query, np.int32, len(labels))).to(st.engine.dev)
+    rules = dict(rules)
+    if "min_score" in rules:
+        rules["min_sim"] = rules.pop("min_score")
+    cnt, user, sim, common, stats = eng2.peers(X, Q, d_q, int(n), int(cap), int(min_common), same, keep_self, **rules)
+    cnt, user, sim, common = cnt.cpu().numpy(), user.cpu().numpy(), sim.cpu().numpy(), common.cpu().numpy()
+    res = LocalRDD([(lab, [(uids[user[q, t]], float(sim[q, t]), int(common[q, t])) for t in range(cnt[q])])
+                    for q, lab in enumerate(labels)], ctx)
+    res.stats = stats
+    return res
+
+
+def similar_users(alterEgoRDD, users, n, cap=1, centred=True, min_common=1, keep_self=False, allow_users=None, exclude=None,
+                  min_sim=None):
+    """"Who is this user like?" on the device (Engine.peer_index / Engine.peers): for every uid of `users` the n (1..1024) users of
+    the train set whose AlterEgo profiles are most alike -- sim = the cosine of the two profiles over the items both hold (centred:
+    ratings minus the item average) times min(common, cap) / cap, the significance weighting of RecommenderSim; sim descending, user
+    INDEX ascending on equal sim; the user itself is left out unless keep_self.  min_common: peers with fewer common records are
+    dropped.  Returns a LocalRDD of (uid, [(uid2, sim, common)*]) in the order of `users`; a uid the train set does not know gives
+    (uid, []).  It carries .stats = (candidates, dropped by min_common, dropped as non-finite, dropped below min_sim, largest
+    candidate count of a user, records expanded).  Cost: the first call on a handle builds the peer index (and with centred the
+    item averages) and keeps it on the handle; later calls run the expansion, sort and selection only.  Eligibility as
+    recommend_audience takes it: allow_users = the uids that may be
+    returned (a segment: only their records are expanded), exclude = {uid: uids never returned for it}, min_sim = floor."""
+    st, eng2, P, X = _peer_setup(alterEgoRDD, centred, "similar_users")
+    uids = list(users.collect()) if hasattr(users, "collect") else list(users)
+    uidx = _user_index(st.idt)
+    return _peer_records(st, eng2, X, P, (uidx.get(u, -1) for u in uids), uids, st.idt.uids, n, cap, min_common, True, keep_self,
+                         getattr(users, "ctx", None), _eligibility(st.engine.dev, uids, uidx, len(st.idt.uids), allow_users, exclude, min_sim))
+
+
+def similar_users_profiles(alterEgoRDD, profiles, n, cap=1, centred=True, min_common=1, allow_users=None, exclude=None, min_sim=None):
+    """similar_users for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them and folds them
+    in; their peers are chosen among the users of the train set (no self rule: a profile is nobody's row).  Returns the LocalRDD of
+    similar_users in the order of `profiles`, with .unknown_items and .counts as recommend_topn_profiles.  exclude = {uid of a
+    profile: uids of the train set}."""
+    _no_fold_in(alterEgoRDD, "similar_users_profiles")
+    st, eng2, _, X = _peer_setup(alterEgoRDD, centred, "similar_users_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    labels = sorted(index, key=index.get)
+    res = _peer_records(st, eng2, X, F, range(len(labels)), labels, st.idt.uids, n, cap, min_common, False, False,
+                        getattr(profiles, "ctx", None),
+                        _eligibility(st.engine.dev, labels, _user_index(st.idt), len(st.idt.uids), allow_users, exclude, min_sim))
+    res.unknown_items, res.counts = unknown, F.counts
+    return res
+
+
 def _item_fold_in(st, eng2, P, S, nb, item_avg, new_items):
     """new items [(iid, [(uid, rating)*])*] (an RDD or a list) -> (their RecommenderSim rows: Engine.item_foldin against the
     profiles P with the norms and the cap of S, the extended tables of Engine.item_foldin_tables, {iid: index in the batch},
