@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K]]
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -37,6 +37,11 @@ member without evidence for an item predicts its average).
 --peers N (with --device-tail): "who is this user like?" -- for three test users the N users of the train set with the most similar
 AlterEgo profiles (xmap.engine.session.similar_users: centred cosine weighted by the number of common records), and each user plus
 their peers as one group of recommend_group: "people like you also liked".
+
+--user-knn K (with --device-tail): the user-based recommender beside the item-based one -- every test user's K nearest train users
+(as --peers finds them), the MAE of the held-out ratings predicted from those neighbours' ratings (the reference's
+user_based_prediction: xmap.engine.session.predict_user_knn), and for three test users the five items their neighbours rate highest
+(recommend_user_knn; Resnick's formula, at least two neighbour ratings per item).
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -118,6 +123,7 @@ def main(argv=None):
     ap.add_argument("--diverse", type=float, default=None, metavar="W")
     ap.add_argument("--groups", type=int, default=None, metavar="K")
     ap.add_argument("--peers", type=int, default=None, metavar="N")
+    ap.add_argument("--user-knn", type=int, default=None, metavar="K")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -151,6 +157,8 @@ def main(argv=None):
         ap.error("--diverse needs --device-tail and the non-private recommender")
     if args.groups is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.groups <= 64):
         ap.error("--groups K needs --device-tail, the non-private recommender and 1 <= K <= 64")
+    if args.user_knn is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.user_knn <= 1024):
+        ap.error("--user-knn K needs --device-tail, the non-private recommender and 1 <= K <= 1024")
     if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
         ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
@@ -285,6 +293,17 @@ def main(argv=None):
         liked = timed("peers_group_topn", session.recommend_group, alterEgo_profile, circles, w, k, alpha, 5, how="mean")
         for gid, lst in liked.collect():
             print("people like you also liked (%s):" % gid, ", ".join("%s (%.3f)" % (iid, plain) for iid, plain, _, _ in lst) or "no evidence")
+    if args.user_knn is not None:
+        # the user-based recommender: predictions and lists from the ratings of the K nearest users
+        ub, ub_mae = timed("user_knn_predict", session.predict_user_knn, alterEgo_profile, testRDD, args.user_knn, cap=5, min_common=2)
+        print("user-kNN (K = %d): MAE %s over %d of %d held-out pairs" % (
+            args.user_knn, ub_mae, int(ub.mae[0]) if ub.mae else 0, sum(len(p) for _, p in testRDD.collect())))
+        some = [uid for uid, _ in testRDD.take(3)]
+        lists = timed("user_knn_topn", session.recommend_user_knn, alterEgo_profile, some, args.user_knn, 5, cap=5, min_common=2,
+                      own_mean=True, min_support=2)
+        print("user-kNN lists: %d candidates of %d users, %d records expanded" % (lists.stats[0], len(some), lists.stats[5]))
+        for uid, lst in lists.collect():
+            print("people like %s rated highly:" % uid, ", ".join("%s (%.3f, %d ratings)" % e for e in lst) or "no neighbour rated anything new")
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

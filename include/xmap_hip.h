@@ -1013,6 +1013,69 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                    int32_t *out_user, double *out_sim, int32_t *out_common,
                    const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
 
+/* ---- user-kNN (csrc/stage_e_uknn.hip; DESIGN.md 4 "User-kNN"): "people like you rated this highly" -- predictions and top-N
+ * lists from the peer lists of xmap_peer_rows.  The reference's user_based_prediction restated.  All arithmetic is fp64, one
+ * rounded operation per step, no fused multiply-add.
+ * A profile row p is VALID iff 0 <= prof_item[p] < n_items; invalid rows are ignored everywhere.
+ * Lists: n_query lists in the layout xmap_peer_rows writes -- nb_cnt [n_query] (<= 0: the query has no list), nb_user / nb_sim
+ *   [n_query][n_nb], 1 <= n_nb <= 1024; the list of q is its first min(nb_cnt[q], n_nb) entries (v_j, s_j), j in list order.  An
+ *   entry whose v_j is outside [0, n_users) is a neighbour without rows.  query_avg [n_query] = the mean of the QUERY user, given
+ *   beside the lists so that a folded-in query (not a resident user) works; user_avg [n_users] = the resident means (read with
+ *   XMAP_UKNN_OWN_MEAN only, may be NULL without it).
+ * Evidence of (q, i): for each neighbour j in list order, each row p of v_j's profile with prof_item[p] == i in profile order
+ *   is the entry (s_j, d), d = prof_rating[p] - query_avg[q]; with XMAP_UKNN_OWN_MEAN d = prof_rating[p] - user_avg[v_j]
+ *   (Resnick's formula; flags 0 is the reference's, which subtracts the QUERY's mean).  A neighbour that holds i twice gives two
+ *   entries; there is no cap.  num = the sum of fl(s_j * d), den = the sum of |s_j|, both from 0.0 left to right in entry order.
+ *   score = query_avg[q] + num / den; without evidence score = query_avg[q].  No temporal decay.
+ * xmap_uknn_means: user_avg[u] = the mean over the valid rows of user u: the double-double sum (exact to 2^-104) rounded once,
+ *   divided by the count, as RecommenderSim takes its item averages and xmap_peer_centre its centre (lane l of 64 sums the rows
+ *   l, l + 64, .. of the profile, the fixed butterfly of dd_reduce folds the lanes); user_cnt[u] = the valid rows.  A user
+ *   without valid rows gets 0.0 and 0.  One wave per user, launched in ranges below 2^32 threads.  n_users < 2^31.  Does not sync.
+ * xmap_uknn_predict_rows: one wave per test pair t = (test_q[t], test_item[t]); test_q indexes the lists.  status[t]: 3 = test_q
+ *   outside [0, n_query) or test_item outside [0, n_items); else 1 = nb_cnt[q] <= 0 (the reference skips the user's pairs, and
+ *   calculate_mae does not count them); else 2 = the Python statement raises here (evidence with den == 0.0, or a score that is
+ *   not finite); else 0 = predicted, with or without evidence.  out_score[t] = the score, out_bound[t] = bound_rating of it
+ *   (round half up, clamp to [0, 5]), both 0.0 unless status is 0; out_n[t] = the evidence entries (0 for status 1 and 3).
+ *   The sums do not depend on the grid.  The MAE of the call is xmap_mae(status, real, out_bound, out_bound).  Launched in ranges
+ *   below 2^32 threads; no temporaries.  Does not sync.
+ * xmap_uknn_topn_rows: per query q the n_top (1..1024) items its neighbours hold, ranked by the unrounded score.  Records of q:
+ *   for each neighbour j in list order, each valid row of v_j in profile order, the record (item, s_j, d).  Rules, in this
+ *   order: (1) the candidates are the items with at least one record; (2) the items query_user[q] holds in the query CSR q_ptr /
+ *   q_item of n_q_users users (any row with that item; a query user outside the CSR holds nothing) leave unless
+ *   XMAP_UKNN_KEEP_HELD; (3) the ids of the query's exclusion list leave, and the rest is intersected with F->allow -- the mask
+ *   and the ids are ITEMS, one exclusion list per query, and the mask acts in the expansion: no record of an ineligible item is
+ *   written; (4) support = the records of the item; support < min_support (>= 1): dropped, counted; (5) the score as above over
+ *   the item's records in record order; not finite (den == 0.0 among them): dropped, counted; (6) score < F->min_score: dropped,
+ *   counted; (7) selection by score descending as numbers, item index ascending on equal scores.  F == NULL: no rules.
+ *   Outputs (device): out_cnt [n_query]; out_item / out_score / out_support [n_query][n_top] with -1 / 0.0 / 0 behind the count.
+ *   Queries may repeat.  A pure function of the inputs: it depends on neither the grid, nor the order of any atomic, nor
+ *   max_records.  h_stats (host, [6] or NULL): [0] candidates after rules 2-3, [1] dropped by min_support, [2] dropped as
+ *   non-finite, [3] dropped below the floor, [4] the largest candidate count (after rules 2-3) of one query, [5] records expanded.
+ *   The queries are cut into chunks of consecutive queries whose records number at most max_records (0: the library's default,
+ *   2^22); a single query above that is a chunk of its own and its records must stay below 2^31 (XMAP_ERR_CAPACITY).  Per chunk:
+ *   record counts per (query, list position) -> scan -> expansion (one wave per position compacts its rows) -> stable radix sort
+ *   on (q - q0) << item_bits | item -> run heads -> scan -> one lane per run -> segmented selection.  Temporaries from the
+ *   stream's arena: 72 B per record of the largest chunk (56 B per record + 16 B per run, sized for as many runs as records) and
+ *   12 B per (query, list position); n_query * n_nb < 2^31, n_query <= 2^28.  n_top, n_nb, min_support, flags, a NaN floor and
+ *   the pointers are checked on the host before any device work; ex_ptr and the record counts on the device, before an output is
+ *   written.  max_records above 2^31 - 2 counts as 2^31 - 2.  Syncs. */
+#define XMAP_UKNN_OWN_MEAN 1
+#define XMAP_UKNN_KEEP_HELD 2   /* xmap_uknn_topn_rows / xmap_ctx_uknn_recommend only */
+int xmap_uknn_means(void *stream, int64_t n_users, int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item,
+                    const double *prof_rating, double *user_avg /*[U]*/, int32_t *user_cnt /*[U]*/);
+int xmap_uknn_predict_rows(void *stream, int64_t n_test, const int32_t *test_q, const int32_t *test_item, int64_t n_query,
+                           const double *query_avg, int32_t n_nb, const int32_t *nb_cnt, const int32_t *nb_user, const double *nb_sim,
+                           int64_t n_users, int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item,
+                           const double *prof_rating, const double *user_avg /*[U] or NULL*/, int32_t flags, double *out_score,
+                           double *out_bound, int32_t *out_n, int32_t *status);
+int xmap_uknn_topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int64_t n_q_users, const int64_t *q_ptr,
+                        const int32_t *q_item, const double *query_avg, int32_t n_nb, const int32_t *nb_cnt, const int32_t *nb_user,
+                        const double *nb_sim, int64_t n_users, int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item,
+                        const double *prof_rating, const double *user_avg /*[U] or NULL*/, int32_t flags, int32_t n_top,
+                        int32_t min_support, int64_t max_records /*0: library default*/, int32_t *out_cnt, int32_t *out_item,
+                        double *out_score, int32_t *out_support,
+                        const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
+
 /* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
  * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
  * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
@@ -1338,6 +1401,27 @@ int xmap_ctx_recommend_group(xmap_ctx *ctx, int32_t source, int64_t n_groups, co
 int xmap_ctx_peers(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
                    int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common,
                    const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
+/* User-kNN: the peers of the users in question by xmap_peer_rows exactly as xmap_ctx_peers runs it (source, n_nb as its n_top,
+ * peer_flags = XMAP_PEERS_KEEP_SELF | XMAP_PEERS_CENTRED, cap, min_common; no rules on the peers), the means by xmap_uknn_means
+ * (the resident users'; with XMAP_SRC_FOLDIN the queries' own means over the batch's profiles), then xmap_uknn_predict_rows /
+ * xmap_uknn_topn_rows over the resident profiles.  Host arrays in and out.  XMAP_SRC_ITEM_FOLDIN is XMAP_ERR_ARG.  Needs what
+ * xmap_ctx_peers needs.  n_nb, n_top, min_support, cap, min_common, both flag words, the source and the filter are checked on the
+ * host before the context is read or any device work is done: on XMAP_ERR_ARG the outputs keep every byte.
+ * xmap_ctx_uknn_predict: test_user indexes the resident users or the batch; the distinct users of the pairs are the queries.
+ *   flags: XMAP_UKNN_OWN_MEAN.  Host outputs out_score / out_bound / out_n / status [n_test] as xmap_uknn_predict_rows writes
+ *   them (status 3 cannot occur for a user: a user outside the source has no list, status 1).  mae ([2] or NULL; needs
+ *   test_rating) = {pairs with status 0, sum |test_rating - out_bound| over them} by xmap_mae.
+ * xmap_ctx_uknn_recommend: query_user indexes the resident users or the batch; the held items are the query's own rows there.
+ *   flags: XMAP_UKNN_OWN_MEAN | XMAP_UKNN_KEEP_HELD.  The mask and the exclusion ids of F are ITEMS.  Host outputs: out_cnt
+ *   [n_query], out_item / out_score / out_support [n_query][n_top]; stats as the h_stats of xmap_uknn_topn_rows. */
+int xmap_ctx_uknn_predict(xmap_ctx *ctx, int32_t source, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
+                          const double *test_rating /* or NULL */, int32_t n_nb, int32_t peer_flags, int32_t cap, int32_t min_common,
+                          int32_t flags, double *out_score, double *out_bound, int32_t *out_n, int32_t *status,
+                          double *mae /* [2] or NULL */);
+int xmap_ctx_uknn_recommend(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_nb,
+                            int32_t peer_flags, int32_t cap, int32_t min_common, int32_t flags, int32_t n_top, int32_t min_support,
+                            int32_t *out_cnt, int32_t *out_item, double *out_score, int32_t *out_support,
+                            const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

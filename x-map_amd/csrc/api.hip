@@ -20,6 +20,7 @@
 // overflow retries and unit planning that xmap/engine/device.py does for the Python host.  No torch, no other library.
 #include <math.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
@@ -1478,6 +1479,20 @@ int xmap_ctx_recommend_diverse(xmap_ctx *c, int32_t source, int64_t n_query, con
 
 // ---- peers: the users most like a query user, over the resident profiles or a fold-in batch ---------------------------------------
 
+// the context's peer index of centring z (0 raw ratings, 1 centred by rs_avg): built on first use
+static int peer_index_of(xmap_ctx *c, int z) {
+    if (c->have_peer[z]) return XMAP_OK;
+    const int32_t I = c->R.n_items;
+    const int64_t U = c->R.n_users;
+    c->p_peer[z].release();
+    XM_ALLOC(c->p_peer[z], c->pr_hd_ptr[z], I + 1); XM_ALLOC(c->p_peer[z], c->pr_hd_user[z], c->n_rows);
+    XM_ALLOC(c->p_peer[z], c->pr_hd_x[z], c->n_rows); XM_ALLOC(c->p_peer[z], c->pr_nrm[z], U);
+    XM_TRY(xmap_peer_index(c->st, U, I, c->pf_ptr, c->pf_item, c->pf_rating, z ? c->rs_avg : nullptr, c->pr_hd_ptr[z], c->pr_hd_user[z],
+                           c->pr_hd_x[z], c->pr_nrm[z], nullptr));
+    c->have_peer[z] = true;
+    return XMAP_OK;
+}
+
 int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
                    int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, const xmap_rec_filter *F,
                    int64_t *stats) {
@@ -1498,14 +1513,7 @@ int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *
     const int64_t U = c->R.n_users;
     const int z = (flags & XMAP_PEERS_CENTRED) ? 1 : 0;
     const double *centre = z ? c->rs_avg : nullptr;
-    if (!c->have_peer[z]) {
-        c->p_peer[z].release();
-        XM_ALLOC(c->p_peer[z], c->pr_hd_ptr[z], I + 1); XM_ALLOC(c->p_peer[z], c->pr_hd_user[z], c->n_rows);
-        XM_ALLOC(c->p_peer[z], c->pr_hd_x[z], c->n_rows); XM_ALLOC(c->p_peer[z], c->pr_nrm[z], U);
-        XM_TRY(xmap_peer_index(c->st, U, I, c->pf_ptr, c->pf_item, c->pf_rating, centre, c->pr_hd_ptr[z], c->pr_hd_user[z], c->pr_hd_x[z],
-                               c->pr_nrm[z], nullptr));
-        c->have_peer[z] = true;
-    }
+    XM_TRY(peer_index_of(c, z));
     const Profiles Q = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
     const int32_t fl = (flags & XMAP_PEERS_KEEP_SELF) | (source == XMAP_SRC_RESIDENT ? XMAP_PEERS_SAME : 0);
     ScratchPool tmp;
@@ -1523,6 +1531,137 @@ int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *
     XM_TRY(d2h(out_user, (const int32_t *)d_user, m, c->st));
     XM_TRY(d2h(out_sim, (const double *)d_sim, m, c->st));
     XM_TRY(d2h(out_common, (const int32_t *)d_common, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+// ---- user-kNN: predictions and top-N from the peer lists ----------------------------------------------------------------------------
+
+// what the two user-kNN calls share, on the device: the n_nb peers of the queries (xmap_peer_rows without rules), the resident
+// means and the queries' own means
+struct UknnLists {
+    int32_t *query, *cnt, *user;
+    double *sim, *user_avg, *query_avg;
+    Profiles Q;
+};
+
+static int uknn_lists(xmap_ctx *c, ScratchPool &tmp, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_nb,
+                      int32_t peer_flags, int32_t cap, int32_t min_common, UknnLists *L) {
+    const int32_t I = c->R.n_items;
+    const int64_t U = c->R.n_users;
+    const int z = (peer_flags & XMAP_PEERS_CENTRED) ? 1 : 0;
+    XM_TRY(peer_index_of(c, z));
+    L->Q = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const int32_t fl = (peer_flags & XMAP_PEERS_KEEP_SELF) | (source == XMAP_SRC_RESIDENT ? XMAP_PEERS_SAME : 0);
+    const size_t n = (size_t)n_query, m = n * (size_t)n_nb;
+    int32_t *d_common, *d_ucnt, *d_qcnt;
+    XM_TRY(h2d(tmp, &L->query, query_user, n, c->st));
+    XM_TRY(dalloc(tmp, &L->cnt, n, c->st)); XM_TRY(dalloc(tmp, &L->user, m, c->st));
+    XM_TRY(dalloc(tmp, &L->sim, m, c->st)); XM_TRY(dalloc(tmp, &d_common, m, c->st));
+    XM_TRY(xmap_peer_rows(c->st, n_query, L->query, L->Q.n_users, L->Q.ptr, L->Q.item, L->Q.rating, fl, n_nb, cap, min_common, U, I,
+                          z ? c->rs_avg : nullptr, c->pr_hd_ptr[z], c->pr_hd_user[z], c->pr_hd_x[z], c->pr_nrm[z], 0, L->cnt, L->user,
+                          L->sim, d_common, nullptr, nullptr));
+    XM_TRY(dalloc(tmp, &L->user_avg, (size_t)U, c->st)); XM_TRY(dalloc(tmp, &d_ucnt, (size_t)U, c->st));
+    XM_TRY(xmap_uknn_means(c->st, U, I, c->pf_ptr, c->pf_item, c->pf_rating, L->user_avg, d_ucnt));
+    const double *src = L->user_avg;
+    if (source == XMAP_SRC_FOLDIN) {
+        double *d_qavg;
+        XM_TRY(dalloc(tmp, &d_qavg, (size_t)L->Q.n_users, c->st)); XM_TRY(dalloc(tmp, &d_qcnt, (size_t)L->Q.n_users, c->st));
+        XM_TRY(xmap_uknn_means(c->st, L->Q.n_users, I, L->Q.ptr, L->Q.item, L->Q.rating, d_qavg, d_qcnt));
+        src = d_qavg;
+    }
+    XM_TRY(dalloc(tmp, &L->query_avg, n, c->st));
+    XM_TRY(uknn_gather(c->st, n_query, L->query, L->Q.n_users, src, L->query_avg));
+    return XMAP_OK;
+}
+
+int xmap_ctx_uknn_predict(xmap_ctx *c, int32_t source, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
+                          const double *test_rating, int32_t n_nb, int32_t peer_flags, int32_t cap, int32_t min_common, int32_t flags,
+                          double *out_score, double *out_bound, int32_t *out_n, int32_t *status, double *mae) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(n_nb >= 1 && n_nb <= 1024);
+    XM_ARG(cap >= 1);
+    XM_ARG(min_common >= 1);
+    XM_ARG((peer_flags & ~(XMAP_PEERS_KEEP_SELF | XMAP_PEERS_CENTRED)) == 0);
+    XM_ARG((flags & ~XMAP_UKNN_OWN_MEAN) == 0);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN);       // an item fold-in adds items, not users
+    XM_ARG(n_test >= 0 && (n_test == 0 || (test_user && test_item && out_score && out_bound && out_n && status)));
+    XM_ARG(!mae || test_rating || n_test == 0);
+    XM_ARG(c && c->have_gen && c->have_rec);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_HIP(hipSetDevice(c->device));
+    if (mae) mae[0] = mae[1] = 0.0;
+    if (n_test == 0) return XMAP_OK;
+    // the distinct users of the pairs are the queries (ascending); test_q = the pair's position among them
+    std::vector<int32_t> users(test_user, test_user + n_test);
+    std::sort(users.begin(), users.end());
+    users.erase(std::unique(users.begin(), users.end()), users.end());
+    std::vector<int32_t> tq((size_t)n_test);
+    for (int64_t t = 0; t < n_test; t++) tq[(size_t)t] = (int32_t)(std::lower_bound(users.begin(), users.end(), test_user[t]) - users.begin());
+    ScratchPool tmp;
+    UknnLists L;
+    XM_TRY(uknn_lists(c, tmp, source, (int64_t)users.size(), users.data(), n_nb, peer_flags, cap, min_common, &L));
+    int32_t *d_q, *d_item, *d_n, *d_status;
+    double *d_real = nullptr, *d_score, *d_bound, *d_mae;
+    const size_t n = (size_t)n_test;
+    XM_TRY(h2d(tmp, &d_q, (const int32_t *)tq.data(), n, c->st));
+    XM_TRY(h2d(tmp, &d_item, test_item, n, c->st));
+    if (test_rating) XM_TRY(h2d(tmp, &d_real, test_rating, n, c->st));
+    XM_TRY(dalloc(tmp, &d_score, n, c->st)); XM_TRY(dalloc(tmp, &d_bound, n, c->st));
+    XM_TRY(dalloc(tmp, &d_n, n, c->st)); XM_TRY(dalloc(tmp, &d_status, n, c->st)); XM_TRY(dalloc(tmp, &d_mae, 3, c->st, true));
+    XM_TRY(xmap_uknn_predict_rows(c->st, n_test, d_q, d_item, (int64_t)users.size(), L.query_avg, n_nb, L.cnt, L.user, L.sim, c->R.n_users,
+                                  c->R.n_items, c->pf_ptr, c->pf_item, c->pf_rating, L.user_avg, flags, d_score, d_bound, d_n, d_status));
+    double h_mae[3] = {0.0, 0.0, 0.0};
+    if (mae) {
+        XM_TRY(xmap_mae(c->st, n_test, d_status, d_real, d_bound, d_bound, d_mae));
+        XM_TRY(d2h(h_mae, (const double *)d_mae, 3, c->st));
+    }
+    XM_TRY(d2h(out_score, (const double *)d_score, n, c->st));
+    XM_TRY(d2h(out_bound, (const double *)d_bound, n, c->st));
+    XM_TRY(d2h(out_n, (const int32_t *)d_n, n, c->st));
+    XM_TRY(d2h(status, (const int32_t *)d_status, n, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    if (mae) { mae[0] = h_mae[0]; mae[1] = h_mae[1]; }
+    return XMAP_OK;
+}
+
+int xmap_ctx_uknn_recommend(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_nb, int32_t peer_flags,
+                            int32_t cap, int32_t min_common, int32_t flags, int32_t n_top, int32_t min_support, int32_t *out_cnt,
+                            int32_t *out_item, double *out_score, int32_t *out_support, const xmap_rec_filter *F, int64_t *stats) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(n_nb >= 1 && n_nb <= 1024);
+    XM_ARG(n_top >= 1 && n_top <= 1024);
+    XM_ARG(min_support >= 1);
+    XM_ARG(cap >= 1);
+    XM_ARG(min_common >= 1);
+    XM_ARG((peer_flags & ~(XMAP_PEERS_KEEP_SELF | XMAP_PEERS_CENTRED)) == 0);
+    XM_ARG((flags & ~(XMAP_UKNN_OWN_MEAN | XMAP_UKNN_KEEP_HELD)) == 0);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN);       // an item fold-in adds items, not users
+    XM_ARG(n_query >= 0 && (n_query == 0 || (query_user && out_cnt && out_item && out_score && out_support)));
+    XM_ARG(n_query * (int64_t)n_nb < 2147483647ll);
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_gen && c->have_rec);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 6; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    ScratchPool tmp;
+    UknnLists L;
+    XM_TRY(uknn_lists(c, tmp, source, n_query, query_user, n_nb, peer_flags, cap, min_common, &L));
+    int32_t *d_cnt, *d_item, *d_support;
+    double *d_score;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top;
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
+    XM_TRY(dalloc(tmp, &d_score, m, c->st)); XM_TRY(dalloc(tmp, &d_support, m, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, c->R.n_items, &D));
+    XM_TRY(xmap_uknn_topn_rows(c->st, n_query, L.query, L.Q.n_users, L.Q.ptr, L.Q.item, L.query_avg, n_nb, L.cnt, L.user, L.sim, c->R.n_users,
+                               c->R.n_items, c->pf_ptr, c->pf_item, c->pf_rating, L.user_avg, flags, n_top, min_support, 0, d_cnt, d_item,
+                               d_score, d_support, &D, stats));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_score, (const double *)d_score, m, c->st));
+    XM_TRY(d2h(out_support, (const int32_t *)d_support, m, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
     return XMAP_OK;
 }

@@ -71,6 +71,8 @@ int fill_multi(hipStream_t st, const FillList &F);
 // plan.hip: stable LSD radix sort of (key, value) pairs by the low `bits` bits of the key; tmp buffers of n entries
 int radix_sort_pairs(hipStream_t st, unsigned long long *keys, int *vals, unsigned long long *keys_tmp, int *vals_tmp, long long n,
                      int bits);
+// stage_e_uknn.hip: out[k] = src[sel[k]], 0.0 for an index outside [0, n_src) -- the query means of the coarse user-kNN calls
+int uknn_gather(hipStream_t st, long long n, const int *sel, long long n_src, const double *src, double *out);
 
 constexpr int WAVE = 64;
 

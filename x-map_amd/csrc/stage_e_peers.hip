@@ -28,24 +28,15 @@
 #include "au_select.h"
 #include "predict_rows.h"
 #include "rec_filter.h"
+#include "sorted_runs.h"
 #include "tri.h"
 
 namespace xmap {
 
 constexpr long long PR_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (64 B each: 270 MB of temporaries)
-constexpr int PR_NOT_CANDIDATE = 1, PR_DROPPED = 2;     // status of a run (0: scored and kept)
 
 __device__ __forceinline__ double pr_x(const int *item, const double *rating, const double *centre, long long p) {
     return centre ? rating[p] - centre[item[p]] : rating[p];
-}
-
-// the last k in [lo, hi) with a[k] <= x (a non-decreasing, a[lo] <= x)
-__device__ __forceinline__ long long pr_last_le(const long long *a, long long lo, long long hi, long long x) {
-    while (hi - lo > 1) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(256) void k_pr_item_keys(long long n_rows, int I, const int *pitem, unsigned long long *keys, int *vals) {
@@ -198,30 +189,7 @@ __global__ __launch_bounds__(256) void k_pr_expand_masked(long long rec0, long l
     }
 }
 
-__global__ __launch_bounds__(256) void k_pr_heads(long long n, const unsigned long long *keys, int *head) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) head[t] = (t == 0 || keys[t] != keys[t - 1]) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void k_pr_starts(long long n, const int *head, const long long *run_idx, int *run_start) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    if (head[t]) run_start[run_idx[t]] = (int)t;
-    if (t == 0) run_start[run_idx[n]] = (int)n;
-}
-
-// first[x] = index of the first run of local query x, x <= nq: run_idx at the first sorted position whose query is >= x
-__global__ __launch_bounds__(256) void k_pr_first(long long nq, long long n, const unsigned long long *keys, int user_bits,
-                                                  const long long *run_idx, long long *first) {
-    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x > nq) return;
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((keys[mid] >> user_bits) >= (unsigned long long)x) hi = mid; else lo = mid + 1;
-    }
-    first[x] = run_idx[lo];
-}
+// k_pr_heads, k_pr_starts, k_pr_first: sorted_runs.h
 
 // one lane per run, records in sorted (= expansion) order.  cnt: [0] dropped by min_common, [1] non-finite, [2] below the floor
 __global__ __launch_bounds__(256) void k_pr_reduce(long long n, const unsigned long long *keys, const int *vals, const double *tv,
@@ -258,52 +226,8 @@ __global__ __launch_bounds__(256) void k_pr_reduce(long long n, const unsigned l
     }
 }
 
-// one block per query of the chunk: its runs are the segment [first[x], first[x + 1]), in ascending user index
-// cnt: [3] candidates after the self rule, the exclusions and the mask, [4] the largest such count of one query
-template <int CAP>
-__global__ __launch_bounds__(AU_SEL_THREADS) void k_pr_select(long long nq, long long q0, int n_top, const long long *first,
-                                                              const unsigned long long *keys, const int *run_start, int user_bits,
-                                                              const int *r_status, const double *r_sim, const int *r_common,
-                                                              int *out_cnt, int *out_user, double *out_sim, int *out_common,
-                                                              unsigned long long *cnt) {
-    __shared__ unsigned long long K[2 * CAP];
-    __shared__ unsigned P[2 * CAP];
-    __shared__ int s_staged, s_have, s_cand;
-    const int tid = threadIdx.x;
-    const long long x = blockIdx.x;
-    if (x >= nq) return;
-    const long long a = first[x], b = first[x + 1];
-    if (tid == 0) { s_have = 0; s_cand = 0; }
-    int dropped = 0, floored = 0, cand = 0;
-    for (long long r = a + tid; r < b; r += AU_SEL_THREADS) cand += r_status[r] != PR_NOT_CANDIDATE ? 1 : 0;
-    au_select_segment<CAP, false>(a, b, n_top, r_sim, r_status, 0.0, K, P, &s_staged, dropped, floored);
-    int have = 0;
-    for (int j = tid; j < n_top; j += AU_SEL_THREADS) {
-        const size_t o = (size_t)(q0 + x) * n_top + j;
-        const unsigned pos = P[j];
-        const bool v = pos != AU_NO_POS;
-        have += v ? 1 : 0;
-        out_user[o] = v ? (int)(keys[run_start[a + pos]] & ((1ull << user_bits) - 1ull)) : -1;
-        out_sim[o] = v ? r_sim[a + pos] : 0.0;
-        out_common[o] = v ? r_common[a + pos] : 0;
-    }
-    if (have) atomicAdd(&s_have, have);
-    if (cand) atomicAdd(&s_cand, cand);
-    __syncthreads();
-    if (tid == 0) {
-        out_cnt[q0 + x] = s_have;
-        if (s_cand) { atomicAdd(&cnt[3], (unsigned long long)s_cand); atomicMax(&cnt[4], (unsigned long long)s_cand); }
-    }
-}
-
-// the outputs of a query without records: count 0 and the padding
-__global__ __launch_bounds__(256) void k_pr_blank(long long n_query, int n_top, int *out_cnt, int *out_user, double *out_sim, int *out_common) {
-    const long long total = n_query * n_top, step = (long long)gridDim.x * blockDim.x;
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += step) {
-        if (k < n_query) out_cnt[k] = 0;
-        out_user[k] = -1; out_sim[k] = 0.0; out_common[k] = 0;
-    }
-}
+// k_pr_select (cnt [3] candidates after the self rule, the exclusions and the mask, [4] the largest such count of one query)
+// and k_pr_blank: sorted_runs.h
 
 // avg[i] of the x of item i's holders: the exact double-double sum rounded once, divided by the entries -- what item_stats.h
 // computes for an item of RecommenderSim (lane-strided sums, the fixed butterfly of dd_reduce); one wave per item
@@ -317,28 +241,6 @@ __global__ __launch_bounds__(256) void k_pr_centre(long long base, long long I, 
     for (long long p = p0 + lane; p < p1; p += WAVE) dd_add(s, slo, hd_x[p]);
     dd_reduce<WAVE>(s, slo);
     if (on && lane == 0) avg[i] = (p1 > p0) ? 1.0 * s / (double)(p1 - p0) : 0.0;
-}
-
-static int pr_bits_for(long long v) {   // bits that hold 0 .. v - 1, at least one
-    int b = 1;
-    while (b < 62 && (1ll << b) < v) b++;
-    return b;
-}
-
-static unsigned pr_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
-constexpr long long PR_SELECT_RANGE = 1ll << 23;        // queries (one block of 256 threads each) per launch of the selection
-static_assert(PR_SELECT_RANGE * AU_SEL_THREADS < (1ll << 32), "the grid of a range stays below 2^32 threads");
-constexpr unsigned PR_BLANK_BLOCKS = 1u << 20;          // blocks of the grid-stride fill of the outputs
-
-template <int CAP, class... A>
-static int pr_select_ranges(hipStream_t st, long long nq, long long q0, int n_top, const long long *first, A... a) {
-    for (long long x0 = 0; x0 < nq; x0 += PR_SELECT_RANGE) {       // the queries of a range: first + x0, outputs from q0 + x0
-        const long long m = nq - x0 < PR_SELECT_RANGE ? nq - x0 : PR_SELECT_RANGE;
-        k_pr_select<CAP><<<dim3((unsigned)m), dim3(AU_SEL_THREADS), 0, st>>>(m, q0 + x0, n_top, first + x0, a...);
-        XM_LAUNCH_CHECK();
-    }
-    return XMAP_OK;
 }
 
 static int pr_norms(hipStream_t st, long long n, const int *sel, long long U, int I, const long long *pptr, const int *pitem,

@@ -2021,6 +2021,90 @@ class Engine(object):
         del alive
         return out_cnt[:n_q], out_user[:n_q], out_sim[:n_q], out_common[:n_q], tuple(int(x) for x in h)
 
+    def user_means(self, P):
+        """The mean rating of every user of the profiles P over its valid rows (xmap_uknn_means): the exact sum rounded once,
+        divided by the count, as the item averages are taken.  Returns (avg float64 [users] -- 0.0 without valid rows --, cnt int32
+        [users])."""
+        U = int(P.n_users)
+        avg, cnt = self._empty(max(U, 1), torch.float64), self._empty(max(U, 1), torch.int32)
+        with self.timed("user_means"):
+            check(lib.xmap_uknn_means(_stream(self.dev), i64(U), i32(P.n_items), vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64),
+                                      vp(avg), vp(cnt)))
+        return avg[:U], cnt[:U]
+
+    @staticmethod
+    def _uknn_lists(lists):
+        cnt, user, sim = [x.contiguous() for x in lists[:3]]
+        if user.dim() != 2 or tuple(sim.shape) != tuple(user.shape) or int(cnt.numel()) != int(user.shape[0]):
+            raise ValueError("lists = (cnt [Q], user [Q][n_nb], sim [Q][n_nb]) as peers() returns them")
+        if cnt.dtype != torch.int32 or user.dtype != torch.int32 or sim.dtype != torch.float64:
+            raise ValueError("lists = (cnt int32, user int32, sim float64)")
+        n_nb = int(user.shape[1])
+        if not 1 <= n_nb <= 1024:
+            raise ValueError("n_nb = %d: the lists hold 1 .. 1024 neighbours" % n_nb)
+        return cnt, user, sim, n_nb
+
+    def uknn_predict(self, P, lists, query_avg, test_q, test_item, user_avg=None, own_mean=False):
+        """User-kNN prediction on the device (xmap_uknn_predict_rows, one wave per test pair): lists = what peers() returned for
+        the queries (cnt, user, sim, ...), query_avg float64 [Q] = the queries' own means (user_means() of the profiles the
+        queries index, gathered), test_q int32 = the pair's index into the lists, test_item int32.  P: the resident profiles the
+        neighbours index.  pred = query mean + sum(sim * (rating - query mean)) / sum(|sim|) over the neighbours' rows that hold
+        the item, in list order then profile order; own_mean: rating - the NEIGHBOUR's mean (Resnick; needs user_avg =
+        user_means(P)[0]).  Returns (score, bound, n, status): the unrounded prediction, bound_rating of it, the evidence entries,
+        and status 0 predicted / 1 no list / 2 the reference raises here / 3 pair out of range."""
+        cnt, user, sim, n_nb = self._uknn_lists(lists)
+        T, n_q = int(test_q.numel()), int(cnt.numel())
+        if own_mean and user_avg is None:
+            raise ValueError("own_mean needs user_avg = user_means(P)[0]")
+        if int(query_avg.numel()) != n_q:
+            raise ValueError("query_avg: one mean per list (%d), not %d" % (n_q, int(query_avg.numel())))
+        score, bound = self._empty(max(T, 1), torch.float64), self._empty(max(T, 1), torch.float64)
+        n, status = self._empty(max(T, 1), torch.int32), self._empty(max(T, 1), torch.int32)
+        with self.timed("uknn_predict"):
+            check(lib.xmap_uknn_predict_rows(_stream(self.dev), i64(T), vp(test_q.contiguous()), vp(test_item.contiguous()), i64(n_q),
+                                             vp(query_avg.contiguous()), i32(n_nb), vp(cnt), vp(user), vp(sim), i64(P.n_users),
+                                             i32(P.n_items), vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64),
+                                             vp(None if user_avg is None else user_avg.contiguous()),
+                                             i32(abi.UKNN_OWN_MEAN if own_mean else 0), vp(score), vp(bound), vp(n), vp(status)))
+        return score[:T], bound[:T], n[:T], status[:T]
+
+    def uknn_topn(self, P, Q, query_user, lists, query_avg, n_top, user_avg=None, own_mean=False, keep_held=False, min_support=1,
+                  allow=None, exclude=None, min_score=None, max_records=0):
+        """User-kNN top-N on the device (xmap_uknn_topn_rows): per query -- lists / query_avg as uknn_predict() takes them,
+        query_user int32 = its index into the profiles Q (the resident ones or a fold-in batch), whose items it holds -- the n_top
+        (1..1024) items its neighbours hold with the largest unrounded prediction; score descending, item index ascending.  Held
+        items leave unless keep_held; an item with fewer than min_support records is dropped.  allow / exclude / min_score as
+        topn() takes them (items; the mask acts in the expansion).  Returns (cnt [Q], item [Q][n_top] (-1 behind the count), score,
+        support [Q][n_top], stats) with stats = (candidates, dropped by min_support, dropped as non-finite, dropped below the
+        floor, largest candidate count of a query, records expanded).  max_records: the chunk bound (0: the library's)."""
+        cnt, user, sim, n_nb = self._uknn_lists(lists)
+        n_q, n_top = int(query_user.numel()), int(n_top)
+        if not 1 <= n_top <= 1024:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 1024" % n_top)
+        if int(min_support) < 1:
+            raise ValueError("min_support = %r: >= 1" % (min_support,))
+        if own_mean and user_avg is None:
+            raise ValueError("own_mean needs user_avg = user_means(P)[0]")
+        if int(cnt.numel()) != n_q or int(query_avg.numel()) != n_q:
+            raise ValueError("one list and one mean per query (%d)" % n_q)
+        out_cnt = self._empty(max(n_q, 1), torch.int32)
+        out_item, out_support = self._empty((max(n_q, 1), n_top), torch.int32), self._empty((max(n_q, 1), n_top), torch.int32)
+        out_score = self._empty((max(n_q, 1), n_top), torch.float64)
+        F = alive = None
+        if allow is not None or exclude is not None or min_score is not None:
+            F, alive = self._rec_filter(P.n_items, n_q, allow, exclude, min_score)
+        flags = (abi.UKNN_OWN_MEAN if own_mean else 0) | (abi.UKNN_KEEP_HELD if keep_held else 0)
+        h = (C.c_int64 * 6)()
+        with self.timed("uknn_topn"):
+            check(lib.xmap_uknn_topn_rows(_stream(self.dev), i64(n_q), vp(query_user.contiguous()), i64(Q.n_users), vp(Q.user_ptr),
+                                          vp(Q.user_item), vp(query_avg.contiguous()), i32(n_nb), vp(cnt), vp(user), vp(sim),
+                                          i64(P.n_users), i32(P.n_items), vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64),
+                                          vp(None if user_avg is None else user_avg.contiguous()), i32(flags), i32(n_top),
+                                          i32(min_support), i64(max_records), vp(out_cnt), vp(out_item), vp(out_score), vp(out_support),
+                                          None if F is None else C.byref(F), h))
+        del alive
+        return out_cnt[:n_q], out_item[:n_q], out_score[:n_q], out_support[:n_q], tuple(int(x) for x in h)
+
     def explain(self, P, neighbors, pair_user, pair_item, item_avg, wtab, n_ev, rank_by=0):
         """Why a pair scores what it scores (xmap_explain_rows, the pair body of predict() in its explain mode): for the (user,
         item) pairs -- int32 tensors, typically the lists of topn() -- the n_ev (1..16) strongest evidence entries of the

@@ -24,6 +24,7 @@ SRC_RESIDENT, SRC_FOLDIN, SRC_ITEM_FOLDIN = 0, 1, 2      # XMAP_SRC_*: source of
 GROUP_MEAN, GROUP_MIN, GROUP_MAX = 0, 1, 2      # XMAP_GROUP_*: `how` of xmap_group_topn_rows / xmap_ctx_recommend_group
 GROUP_MAX_MEMBERS = 64    # XMAP_GROUP_MAX_MEMBERS: members of one group
 PEERS_SAME, PEERS_KEEP_SELF, PEERS_CENTRED = 1, 2, 4      # XMAP_PEERS_*: flags of xmap_peer_rows / xmap_ctx_peers
+UKNN_OWN_MEAN, UKNN_KEEP_HELD = 1, 2      # XMAP_UKNN_*: flags of xmap_uknn_predict_rows / xmap_uknn_topn_rows and the coarse calls
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -120,6 +121,7 @@ EXPORTS = [
     "xmap_div_index", "xmap_diversify_rows", "xmap_ctx_recommend_diverse",
     "xmap_group_topn_rows", "xmap_ctx_recommend_group",
     "xmap_peer_index", "xmap_peer_centre", "xmap_peer_rows", "xmap_ctx_peers",
+    "xmap_uknn_means", "xmap_uknn_predict_rows", "xmap_uknn_topn_rows", "xmap_ctx_uknn_predict", "xmap_ctx_uknn_recommend",
 ]
 
 if not os.path.exists(LIB_PATH):

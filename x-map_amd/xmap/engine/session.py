@@ -947,6 +947,121 @@ def similar_users_profiles(alterEgoRDD, profiles, n, cap=1, centred=True, min_co
     return res
 
 
+def _uknn_setup(alterEgoRDD, centred, who):
+    """_peer_setup + the resident users' means (Engine.user_means), kept on the handle like the index"""
+    st, eng2, P, X = _peer_setup(alterEgoRDD, centred, who)
+    kept = alterEgoRDD.__dict__["_peer_setup"]
+    if "means" not in kept:
+        kept["means"] = eng2.user_means(P)[0]
+    return st, eng2, P, X, kept["means"]
+
+
+def _uknn_lists(st, eng2, X, Q, means, query, n_nb, cap, min_common, same):
+    """the peer lists of the users `query` (indices into the profiles Q whose means are `means`) and their own means (0.0 for an
+    index outside Q: such a query has no list either) -> (query tensor, lists, query_avg)"""
+    import torch
+    d_q = torch.from_numpy(np.asarray(list(query), np.int32).reshape(-1)).to(st.engine.dev)
+    lists = eng2.peers(X, Q, d_q, int(n_nb), int(cap), int(min_common), same, False)
+    if int(means.numel()):
+        inside = (d_q >= 0) & (d_q < int(means.numel()))
+        q_avg = torch.where(inside, means[d_q.clamp(0, int(means.numel()) - 1).long()], torch.zeros((), dtype=means.dtype, device=means.device))
+    else:
+        q_avg = torch.zeros(int(d_q.numel()), dtype=torch.float64, device=st.engine.dev)
+    return d_q, lists, q_avg
+
+
+def predict_user_knn(alterEgoRDD, testRDD, n_nb, cap=1, centred=True, min_common=1, own_mean=False):
+    """User-based kNN prediction on the device, the reference's user_based_prediction over the AlterEgo profiles: for every uid of
+    testRDD its n_nb (1..1024) nearest users (similar_users: cap, centred, min_common; the user itself left out), then for every
+    held-out (iid, real) pred = the user's mean + sum(sim * (rating - the user's mean)) / sum(|sim|) over the neighbours' ratings
+    of the item, in list order -- the QUERY user's mean is subtracted, as the reference does; own_mean=True subtracts each
+    neighbour's own mean (Resnick's formula) -- bounded by bound_rating; without evidence the user's mean; no temporal decay.
+    Returns (records, mae): records = a LocalRDD of (uid, [(iid, real, predicted) | ()]) in testRDD order, () for a user without
+    neighbours (or unknown to the train set) and for an iid the train set does not know; mae = the single string calculate_mae
+    gives for a "user" method (None without a predicted pair or when a real rating is not a number).  records.mae = (count, sum
+    |real - predicted|) from the device (Engine.mae)."""
+    import torch
+    st, eng2, P, X, means = _uknn_setup(alterEgoRDD, centred, "predict_user_knn")
+    idt, dev = st.idt, st.engine.dev
+    uidx = _user_index(idt)
+    recs = records_of(testRDD)
+    order = {}
+    for uid, _ in recs:
+        order.setdefault(uid, len(order))
+    _, lists, q_avg = _uknn_lists(st, eng2, X, P, means, (uidx.get(u, -1) for u in sorted(order, key=order.get)), n_nb, cap, min_common, True)
+    tq = np.fromiter((order[uid] for uid, pairs in recs for _ in pairs), np.int32)
+    ti = np.fromiter((idt.iidx.get(pair[0], -1) for _, pairs in recs for pair in pairs), np.int32)
+    try:
+        real = np.fromiter((float(pair[1]) for _, pairs in recs for pair in pairs), np.float64)
+    except (TypeError, ValueError):
+        real = None
+    score, bound, n, status = eng2.uknn_predict(P, lists, q_avg, torch.from_numpy(tq).to(dev), torch.from_numpy(ti).to(dev), means, own_mean)
+    mae = None
+    if real is not None and len(tq):
+        mae = tuple(eng2.mae(status, torch.from_numpy(real).to(dev), bound, bound).tolist()[:2])
+    bound, status = bound.cpu().numpy(), status.cpu().numpy()
+    out, q = [], 0
+    for uid, pairs in recs:
+        line = []
+        for pair in pairs:
+            if status[q] == 0:
+                line.append((pair[0], pair[1], float(bound[q])))
+            elif status[q] == 2:
+                raise ZeroDivisionError("prediction of (%r, %r): zero weight sum or non-finite value (the reference raises here)"
+                                        % (uid, pair[0]))
+            else:
+                line.append(())
+            q += 1
+        out.append((uid, line))
+    res = LocalRDD(out, getattr(testRDD, "ctx", None))
+    res.mae = mae
+    return res, (str(np.float64(mae[1]) / np.float64(mae[0])) if mae and mae[0] > 0 else None)
+
+
+def _uknn_records(st, eng2, P, Q, d_q, lists, q_avg, means, labels, n, own_mean, keep_held, min_support, ctx, rules):
+    cnt, item, score, support, stats = eng2.uknn_topn(P, Q, d_q, lists, q_avg, int(n), means, own_mean, keep_held, int(min_support), **rules)
+    cnt, item, score, support = cnt.cpu().numpy(), item.cpu().numpy(), score.cpu().numpy(), support.cpu().numpy()
+    iids = st.idt.iids
+    res = LocalRDD([(lab, [(iids[item[q, t]], float(score[q, t]), int(support[q, t])) for t in range(cnt[q])])
+                    for q, lab in enumerate(labels)], ctx)
+    res.stats = stats
+    return res
+
+
+def recommend_user_knn(alterEgoRDD, users, n_nb, n, cap=1, centred=True, min_common=1, own_mean=False, keep_held=False, min_support=1,
+                       allow_items=None, exclude=None, min_score=None):
+    """User-based top-N on the device ("people like you rated this highly"): for every uid of `users` its n_nb nearest users as
+    predict_user_knn takes them, then the n (1..1024) items those neighbours hold with the largest unrounded prediction of
+    predict_user_knn; score descending, item INDEX ascending on equal scores.  Items the user holds are left out unless keep_held;
+    an item fewer than min_support neighbour ratings speak for is dropped.  Returns a LocalRDD of (uid, [(iid, score, support)*])
+    in the order of `users`; a uid the train set does not know gives (uid, []).  .stats = (candidates, dropped by min_support,
+    dropped as non-finite, dropped below min_score, largest candidate count of a user, records expanded).  Eligibility as
+    recommend_topn takes it: allow_items, exclude = {uid: iids}, min_score."""
+    st, eng2, P, X, means = _uknn_setup(alterEgoRDD, centred, "recommend_user_knn")
+    uids = list(users.collect()) if hasattr(users, "collect") else list(users)
+    uidx = _user_index(st.idt)
+    d_q, lists, q_avg = _uknn_lists(st, eng2, X, P, means, (uidx.get(u, -1) for u in uids), n_nb, cap, min_common, True)
+    return _uknn_records(st, eng2, P, P, d_q, lists, q_avg, means, uids, n, own_mean, keep_held, min_support, getattr(users, "ctx", None),
+                         _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
+
+
+def recommend_user_knn_profiles(alterEgoRDD, profiles, n_nb, n, cap=1, centred=True, min_common=1, own_mean=False, keep_held=False,
+                                min_support=1, allow_items=None, exclude=None, min_score=None):
+    """recommend_user_knn for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them and
+    folds them in; their neighbours are users of the train set, their mean and their held items come from the folded-in profile.
+    Returns the LocalRDD of recommend_user_knn in the order of `profiles`, with .unknown_items and .counts as
+    recommend_topn_profiles.  exclude = {uid of a profile: iids}."""
+    _no_fold_in(alterEgoRDD, "recommend_user_knn_profiles")
+    st, eng2, P, X, means = _uknn_setup(alterEgoRDD, centred, "recommend_user_knn_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    labels = sorted(index, key=index.get)
+    d_q, lists, q_avg = _uknn_lists(st, eng2, X, F, eng2.user_means(F)[0], range(len(labels)), n_nb, cap, min_common, False)
+    res = _uknn_records(st, eng2, P, F, d_q, lists, q_avg, means, labels, n, own_mean, keep_held, min_support, getattr(profiles, "ctx", None),
+                        _eligibility(st.engine.dev, labels, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
+    res.unknown_items, res.counts = unknown, F.counts
+    return res
+
+
 def _item_fold_in(st, eng2, P, S, nb, item_avg, new_items):
     """new items [(iid, [(uid, rating)*])*] (an RDD or a list) -> (their RecommenderSim rows: Engine.item_foldin against the
     profiles P with the norms and the cap of S, the extended tables of Engine.item_foldin_tables, {iid: index in the batch},
