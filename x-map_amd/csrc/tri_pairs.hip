@@ -4,6 +4,8 @@
 //                     hop, prefix-only profile reads; appends kept pairs to a half-COO.  LS = true is the
 //                     RecommenderSim variant (core/recommenderSim.py:65-133): no filter, self pairs, second walk for
 //                     the leave-one-out local sensitivity
+//   k_pair_pack     : the light rows of the 128- and 256-slot classes, G consecutive units per wave: 8-byte slots, the
+//                     double-double sums by rank within the slot (no claim, no turn), finalised by the co-rating of rank 0
 //   k_pair_heavy    : rows of H, raters in chunks (one rater per lane), DENSE LDS table over H, partial tables to HBM
 //   k_heavy_merge   : double-double merge of the chunk partials (4 waves per row), finalise, append
 //   k_shard_sums    : kept / evaluated pairs summed over the shard cursors, for the host's single read-back
@@ -470,6 +472,338 @@ __global__ __launch_bounds__(64 * NW, (LOG_SLOTS == 7 && !LS) ? 8 : 1) void k_pa
     }
 }
 
+// Packed light rows: the 128- and 256-slot classes (one partition per row by construction: plan_item files a row there only
+// with q == 1).  A row of the smallest class has 6 raters and 63 co-ratings on average -- a single round of 64 lanes -- and
+// k_pair_tri holds a wave and a table for five dependent round trips to do it.  Here one wave takes G consecutive units of
+// its class range and computes them in ONE pass: the G unit records in one round trip, the members' raters as one list (the
+// table of a co-rating is its member's region of the wave's LDS), all rounds of the flat list in flight together, one
+// finalisation, one returning atomic on the shard cursor.
+// The sums take no lock and no turn: the returning atomicAdd on a slot's count word gives every co-rating its RANK within
+// its slot; a lane keeps (slot, rank, term) of its co-ratings in registers; after the walk a wave scan of the slot counts
+// gives every slot an offset, the terms go to an LDS buffer at offset + rank, and the lane whose co-rating has rank 0 sums
+// its slot with dd_add in registers (exact, hence order-independent) and finalises the pair there: it knows the partner, and
+// the partner's norm has been in flight since the walk.  So the finalisation runs over the rounds of the walk (two for the
+// average pack of the 128-slot class), not over the slots of G tables at half load, and in the order of the flat list,
+// which is member by member.  LDS per slot: key + count word, 8 B (k_pair_tri: 26 B), + 8 B per co-rating.
+// A pack the wave cannot hold that way -- more than 64 raters, or more than 64 E co-ratings (the partner bound of a row
+// is min(W+, heavier items): on a small catalogue a 128-slot row may have thousands of co-ratings) -- runs its members one
+// after the other through one table with the per-slot serialised sum of k_pair_tri (the same LDS bytes, laid out anew) and
+// append_pairs.  Correct for any row of the class; not what the class launches spend their time in.
+// E: the rounds of 64 co-ratings a wave holds in registers.  G and E per class: launch_pack.
+constexpr int pack_lds(int log_slots, int g, int e) {
+    return 8 * (g << log_slots) + 512 * e > (26 << log_slots) ? 8 * (g << log_slots) + 512 * e : (26 << log_slots);
+}
+constexpr int pack_waves(int lds) { return 160 * 1024 / lds / 4 > 8 ? 8 : 160 * 1024 / lds / 4; }    // per SIMD, as the LDS admits
+template <int METHOD, int LOG_SLOTS, int G, int PACK_E>
+__global__ __launch_bounds__(64, pack_waves(pack_lds(LOG_SLOTS, G, PACK_E))) void k_pair_pack(TriArgs A) {
+    constexpr int S = 1 << LOG_SLOTS, GS = G * S;
+    constexpr int NIT = GS / 64;            // rounds of 64 slots
+    constexpr bool ADJ = METHOD == XMAP_ADJUST_COSINE;
+    constexpr int CAP = 64 * PACK_E;
+    static_assert(GS % 256 == 0 && GS <= 65536 && CAP <= 32768, "16-byte fills; (slot, rank) in one word");
+    __shared__ __align__(16) unsigned char lds[pack_lds(LOG_SLOTS, G, PACK_E)];
+    // the pack: key[GS] | count word[GS] (n_ij low half, mutuality high half: n_ij < WIDE_MIN) | terms[CAP]
+    uint32_t *key = (uint32_t *)lds;
+    uint32_t *cm = key + GS;
+    double *terms = (double *)(cm + GS);
+    // one member at a time: key[S] | count word[S] | sum[S] | error[S] | claim[S]
+    uint32_t *key1 = (uint32_t *)lds;
+    uint32_t *cm1 = key1 + S;
+    double *dot1 = (double *)(cm1 + S);
+    double *dlo1 = dot1 + S;
+    unsigned short *claim1 = (unsigned short *)(dlo1 + S);
+
+    const int lane = lane_id();
+    const long long u0 = A.unit_lo + (long long)blockIdx.x * G;
+    if (u0 >= A.unit_hi) return;
+    const int nm = (A.unit_hi - u0 < G) ? (int)(A.unit_hi - u0) : G;     // members of this pack
+    // the unit records of the pack in one round trip (lane m: member m)
+    const long long um = u0 + (lane < nm ? lane : 0);
+    const int it_l = A.uq_item[um];
+    const int4 ud = ((const int4 *)A.uq_q)[um];
+    const int nr_l = lane < nm ? ud.z - ud.y : 0;
+    int im[G], pm[G], ro[G + 1];          // item, first rater, position in the pack's rater list (scalars)
+    ro[0] = 0;
+#pragma unroll
+    for (int m = 0; m < G; m++) {
+        im[m] = rl32(it_l, m); pm[m] = rl32(ud.y, m);
+        ro[m + 1] = ro[m] + rl32(nr_l, m);
+    }
+    const int R = ro[G];
+
+    // the pack's raters, one per lane
+    bool packed = R <= 64;
+    int eoff = 0, usrf = 0, end = 0, total = 0;
+    float r = 0.f;
+    if (packed) {
+        int p = pm[0] + lane;
+#pragma unroll
+        for (int m = 1; m < G; m++)
+            if (lane >= ro[m]) p = pm[m] + (lane - ro[m]);
+        const bool ok = lane < R;
+        const RaterRec rr = A.rc[ok ? p : pm[0]];
+        {
+            const uint4 e4 = make_uint4(T_EMPTY, T_EMPTY, T_EMPTY, T_EMPTY), z4 = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+            for (int x = 0; x < GS / 256; x++) { ((uint4 *)key)[x * 64 + lane] = e4; ((uint4 *)cm)[x * 64 + lane] = z4; }
+        }
+        r = rr.rating;
+        usrf = rr.user | (rr.pos_ge & (int)0x80000000);   // the rater's side of its item's average travels with the user
+        const int len = ok ? (rr.pos_ge & 0x7fffffff) : 0;       // the rater's prefix: entries [e0, e0 + len) of its profile
+        end = len;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(end, d, 64); if (lane >= d) end += v; }
+        total = rl32(end, 63);
+        eoff = rr.e0 - (end - len);           // co-rating f of the flat list is entry eoff + f
+        packed = total <= CAP;
+    }
+    if (!packed) {
+        for (int m = 0; m < nm; m++) {
+            const int i = rl32(it_l, m), p0 = rl32(ud.y, m), p1 = rl32(ud.z, m);
+            int ovf = 0;
+            __syncthreads();          // (one wave: orders the LDS phases)
+            for (int s = lane; s < S; s += 64) { key1[s] = T_EMPTY; cm1[s] = 0u; dot1[s] = 0.0; dlo1[s] = 0.0; }
+            __syncthreads();
+            // the walk of k_pair_tri in blocks of 64 raters, one round at a time
+            for (int base = p0; base < p1; base += 64) {
+                const bool ok = base + lane < p1;
+                const RaterRec rr = A.rc[ok ? base + lane : p0];
+                const int len = ok ? (rr.pos_ge & 0x7fffffff) : 0;
+                int en = len;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(en, d, 64); if (lane >= d) en += v; }
+                const int tot = rl32(en, 63);
+                const int st = en - len;
+                for (int f0 = 0; f0 < tot; f0 += 64) {
+                    const int f = f0 + lane;
+                    bool act = f < tot;
+                    int t = 0;
+#pragma unroll
+                    for (int step = 32; step >= 1; step >>= 1) { const int v = __shfl(en, t + step - 1, 64); if (v <= f) t += step; }
+                    const int eb = __shfl(rr.e0, t, 64), sb = __shfl(st, t, 64), ut = __shfl(rr.user, t, 64);
+                    const int pwt = __shfl(rr.pos_ge, t, 64);
+                    const double ri = (double)__shfl(rr.rating, t, 64);
+                    const int2 v = A.ub[act ? eb + (f - sb) : 0];
+                    const double a = ADJ ? A.u_avg[act ? ut : 0] : 0.0;
+                    const int j = v.x & 0x7fffffff;
+                    const double rjd = (double)__int_as_float(v.y);
+                    uint32_t h = 0;
+                    if (act) {
+                        h = ((uint32_t)j * 0x9E3779B1u) >> (32 - LOG_SLOTS);
+                        int probes = 0;
+                        for (;;) {
+                            const uint32_t prev = atomicCAS(&key1[h], T_EMPTY, (uint32_t)j);
+                            if (prev == T_EMPTY || prev == (uint32_t)j) break;
+                            h = (h + 1) & (S - 1);
+                            if (++probes >= S) { act = false; ovf = 1; break; }
+                        }
+                    }
+                    if (act) atomicAdd(&cm1[h], 1u | (((((unsigned)v.x) >> 31) == (((unsigned)pwt) >> 31)) ? (1u << 16) : 0u));
+                    const double tm = ADJ ? (ri - a) * (rjd - a) : (1.0 * ri) * rjd;
+                    // (LDS-qualified volatile accesses, as in k_pair_tri)
+                    typedef __attribute__((address_space(3))) volatile double lds_vf64;
+                    typedef __attribute__((address_space(3))) volatile unsigned short lds_vu16;
+                    lds_vf64 *vhi = (lds_vf64 *)dot1, *vlo = (lds_vf64 *)dlo1;
+                    lds_vu16 *vclaim = (lds_vu16 *)claim1;
+                    bool pending = act;
+                    while (__ballot(pending)) {       // lanes that share a slot take turns
+                        if (pending) vclaim[h] = (unsigned short)lane;
+                        if (pending && vclaim[h] == (unsigned short)lane) {
+                            double hi = vhi[h], lo = vlo[h];
+                            dd_add(hi, lo, tm);
+                            vhi[h] = hi; vlo[h] = lo;
+                            pending = false;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (__ballot(ovf)) {
+                if (lane == 0) atomicOr(&A.counters[2], 1ull);
+                return;
+            }
+            append_pairs(A, i, 0, S,
+                [&](int s, int &j, int &n, int &mu, double &sv, bool &o) {
+                    const uint32_t kj = key1[s];
+                    o = kj != T_EMPTY;
+                    if (!o) return false;
+                    j = (int)kj; n = (int)(cm1[s] & 0xffffu); mu = (int)(cm1[s] >> 16);
+                    return finish_pair<METHOD>(A, i, j, n, mu, dot1[s], sv);
+                },
+                [&](int s, bool o, bool keep, double sv) {
+                    if (o) { if (keep) dot1[s] = sv; else key1[s] = T_EMPTY; }
+                },
+                [&](int s, int &j, int &n, int &mu, double &sv) {
+                    const uint32_t kj = key1[s];
+                    if (kj == T_EMPTY) return false;
+                    j = (int)kj; n = (int)(cm1[s] & 0xffffu); mu = (int)(cm1[s] >> 16); sv = dot1[s];
+                    return true;
+                },
+                [&](int s) { return 0.0; });
+        }
+        return;
+    }
+    double nxm[G];                        // (for the finalisation: in flight during the walk)
+#pragma unroll
+    for (int m = 0; m < G; m++) nxm[m] = A.nrm[im[m]];
+    // the walk: co-rating f = 64 u + lane of the pack's flat list, all rounds' loads in flight together (k_pair_tri: walk)
+    int jw[PACK_E], tt[PACK_E], ee[PACK_E], uu[PACK_E], sr[PACK_E];
+    float rj[PACK_E];
+    double term[PACK_E], ny[PACK_E];
+    int ovf = 0;
+#pragma unroll
+    for (int u = 0; u < PACK_E; u++) {
+        if (u * 64 >= total) break;           // (uniform)
+        const int f = u * 64 + lane;
+        const bool act = f < total;
+        int t = 0;                            // the rater of co-rating f: #{k : end[k] <= f}
+#pragma unroll
+        for (int step = 32; step >= 1; step >>= 1) { const int v = __shfl(end, t + step - 1, 64); if (v <= f) t += step; }
+        const int eo = __shfl(eoff, t, 64), uf = __shfl(usrf, t, 64);
+        tt[u] = t;
+        ee[u] = act ? eo + f : 0;
+        uu[u] = act ? uf : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < PACK_E; u++) {
+        if (u * 64 >= total) break;
+        const int2 v = A.ub[ee[u]];
+        jw[u] = v.x; rj[u] = __int_as_float(v.y);
+        term[u] = ADJ ? A.u_avg[uu[u] & 0x7fffffff] : 0.0;       // (the rater's average, until the term is formed)
+    }
+#pragma unroll
+    for (int u = 0; u < PACK_E; u++) {
+        sr[u] = -1;
+        if (u * 64 >= total) continue;
+        const double ri = (double)__shfl(r, tt[u], 64);
+        int mt = 0;                           // the member of the rater
+#pragma unroll
+        for (int m = 1; m < G; m++) mt += (tt[u] >= ro[m]) ? 1 : 0;
+        const int j = jw[u] & 0x7fffffff;
+        bool act = u * 64 + lane < total;
+        ny[u] = act ? A.nrm[j] : 0.0;         // (for the finalisation)
+        uint32_t h = 0;
+        if (act) {
+            const uint32_t tb = (uint32_t)mt << LOG_SLOTS;
+            h = ((uint32_t)j * 0x9E3779B1u) >> (32 - LOG_SLOTS);
+            int probes = 0;
+            for (;;) {
+                const uint32_t prev = atomicCAS(&key[tb + h], T_EMPTY, (uint32_t)j);
+                if (prev == T_EMPTY || prev == (uint32_t)j) break;
+                h = (h + 1) & (S - 1);
+                if (++probes >= S) { act = false; ovf = 1; break; }
+            }
+            h += tb;
+        }
+        if (act) {
+            const uint32_t inc = 1u | (((((unsigned)jw[u]) >> 31) == (((unsigned)uu[u]) >> 31)) ? (1u << 16) : 0u);
+            const uint32_t rank = atomicAdd(&cm[h], inc) & 0xffffu;
+            sr[u] = (int)(h | (rank << 16));
+            const double a = term[u];
+            term[u] = ADJ ? (ri - a) * ((double)rj[u] - a) : (1.0 * ri) * (double)rj[u];
+        }
+    }
+    if (__ballot(ovf)) {
+        if (lane == 0) atomicOr(&A.counters[2], 1ull);
+        return;
+    }
+    __syncthreads();          // (one wave: orders the LDS phases)
+    // offsets of the slots' terms (lane-major: the slots 64 k + lane of a lane follow one another); they replace the keys
+    {
+        int cnt[NIT], mine = 0;
+#pragma unroll
+        for (int k = 0; k < NIT; k++) { cnt[k] = (int)(cm[k * 64 + lane] & 0xffffu); mine += cnt[k]; }
+        int off = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(off, d, 64); if (lane >= d) off += v; }
+        off -= mine;
+#pragma unroll
+        for (int k = 0; k < NIT; k++) { key[k * 64 + lane] = (uint32_t)off; off += cnt[k]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < PACK_E; u++)
+        if (sr[u] >= 0) terms[key[sr[u] & 0xffff] + (uint32_t)(sr[u] >> 16)] = term[u];
+    __syncthreads();
+    // finalisation (k_pair_tri's, for G rows, by the lanes of rank 0): one returning atomic on the shard cursor for the pack's
+    // kept pairs, the appends in the order of the flat list -- a row's records stay contiguous in its shard --, a row-count
+    // add per member
+    const auto k_coo_i = KARG(coo_i);
+    const auto k_coo_j = KARG(coo_j);
+    const auto k_coo_sim = KARG(coo_sim);
+    const auto k_coo_mutu = KARG(coo_mutu);
+    const auto k_coo_nij = KARG(coo_nij);
+    const auto k_rowcnt = KARG(rowcnt);
+    const auto k_shard_cur = KARG(shard_cur);
+    const auto k_shard_occ = KARG(shard_occ);
+    const auto k_shard_cap = KARG(shard_cap);
+    const auto k_cap = KARG(cap);
+    const auto k_counters = KARG(counters);
+    unsigned long long fk[PACK_E];        // ballots of the kept pairs
+    uint32_t fc[PACK_E];
+    int kept = 0, occ = 0, mkept = 0;     // mkept: lane m holds member m's kept pairs
+#pragma unroll
+    for (int u = 0; u < PACK_E; u++) {
+        fk[u] = 0ull;
+        if (u * 64 >= total) continue;
+        const bool own = sr[u] >= 0 && (sr[u] >> 16) == 0;
+        const int slot = own ? (sr[u] & 0xffff) : 0;
+        const int mt = slot >> LOG_SLOTS;
+        const uint32_t c = cm[slot];
+        const int n = own ? (int)(c & 0xffffu) : 0, mu = (int)(c >> 16);
+        const int off = (int)key[slot];
+        double hi = 0.0, lo = 0.0;
+        for (int x = 0; __ballot(x < n); x++)
+            if (x < n) dd_add(hi, lo, terms[off + x]);
+        bool keep = own;
+        if (own) {                        // cosine (:91-95), significance weighting (:84-89), zero filter (:198,:207): finish_pair
+            double nx = nxm[0];
+#pragma unroll
+            for (int m = 1; m < G; m++) nx = (mt == m) ? nxm[m] : nx;
+            const double np = nx * ny[u];
+            const double cs = (np != 0.0) ? 1.0 * hi / np : 0.0;
+            const int mn = n < k_cap ? n : k_cap;
+            hi = 1.0 * cs * (double)mn / (double)k_cap;
+            keep = (hi != 0.0) && (mu != 0);
+        }
+        term[u] = hi;
+        fc[u] = c;
+        fk[u] = __ballot(keep);
+        kept += __popcll(fk[u]);
+        occ += __popcll(__ballot(own));
+#pragma unroll
+        for (int m = 0; m < G; m++) {
+            const int cm_ = __popcll(__ballot(keep && mt == m));
+            if (lane == m) mkept += cm_;
+        }
+    }
+    const int shard = blockIdx.x & (COO_SHARDS - 1);
+    if (lane == 0 && occ) atomicAdd(&k_shard_occ[shard], (unsigned long long)occ);
+    if (!kept) return;
+    unsigned long long cbase = 0;
+    if (lane == 0) cbase = atomicAdd(&k_shard_cur[shard], (unsigned long long)kept);
+    if (mkept) atomicAdd(&k_rowcnt[it_l], mkept);
+    cbase = ((unsigned long long)(unsigned)rl32((int)(cbase >> 32), 0) << 32) | (unsigned)rl32((int)(cbase & 0xffffffffull), 0);
+    if ((long long)(cbase + kept) > k_shard_cap) {
+        if (lane == 0) atomicOr(&k_counters[3], 1ull);
+        return;
+    }
+    cbase += (unsigned long long)shard * (unsigned long long)k_shard_cap;
+#pragma unroll
+    for (int u = 0; u < PACK_E; u++) {
+        if ((fk[u] >> lane) & 1ull) {
+            const long long pp = (long long)cbase + __popcll(fk[u] & lanemask_lt());
+            const int mt = (sr[u] & 0xffff) >> LOG_SLOTS;
+            int i = im[0];
+#pragma unroll
+            for (int m = 1; m < G; m++) i = (mt == m) ? im[m] : i;
+            k_coo_i[pp] = i; k_coo_j[pp] = jw[u] & 0x7fffffff;
+            k_coo_sim[pp] = term[u]; k_coo_mutu[pp] = (int)(fc[u] >> 16); k_coo_nij[pp] = (int)(fc[u] & 0xffffu);
+        }
+        cbase += __popcll(fk[u]);
+    }
+}
+
 // rows of H: chunk c of the raters, dense table over H (partners of a heavy row are heavier, hence in H)
 // HEAVY_WAVES waves share the unit's dense table (each takes every HEAVY_WAVES-th block of 64 raters): a unit is a chain
 // of dependent gathers (rater record -> prefix entry -> heavy id) and one wave per 26 KB table left 6 waves on a CU.
@@ -641,6 +975,23 @@ int launch_tri(int c, dim3 grid, hipStream_t st, const TriArgs &A) {
     return XMAP_OK;
 }
 
+// rows per wave (G) and rounds of co-ratings held (E) of the packed classes (profiles/r10_pair_packs.txt: the sweep).  Two
+// rows: at BASELINE configs[1] two rows of the 128-slot class have at most 192 co-ratings, two of the 256-slot class at most
+// 383; four rows per wave (E = 6) ran 8 % longer in the 128-slot class, eight 70 % longer: what a wave does for its rows it does
+// one round after the other, and a pack lives as long as that takes
+constexpr int PACK_G128 = 2, PACK_E128 = 3, PACK_G256 = 2, PACK_E256 = 6;
+// the packed classes (k_pair_pack): rank 4 = the 128-slot class, rank 3 = the 256-slot class -> the units of a pack
+int pack_units(int c) { return c == 4 ? PACK_G128 : (c == 3 ? PACK_G256 : 0); }
+template <int METHOD>
+int launch_pack(int c, long long n_units, hipStream_t st, const TriArgs &A) {
+    const int g = pack_units(c);
+    const dim3 grid((unsigned)((n_units + g - 1) / g));
+    if (c == 4) k_pair_pack<METHOD, 7, PACK_G128, PACK_E128><<<grid, dim3(64), 0, st>>>(A);
+    else k_pair_pack<METHOD, 8, PACK_G256, PACK_E256><<<grid, dim3(64), 0, st>>>(A);
+    XM_LAUNCH_CHECK();
+    return XMAP_OK;
+}
+
 // the rows of H: chunk partials of n_units heavy units (0: none), then the merge of n_heavy rows (0: none)
 int launch_heavy(int method, hipStream_t st, const TriArgs &A, int n_units, int n_heavy) {
     const bool cos = method == XMAP_COSINE;         // (else the double-double kernels; exact cosine arrives as adjusted cosine)
@@ -747,6 +1098,10 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
         // one launch per table class: the class's units within [unit_lo, unit_hi).  The classes are independent (they
         // only share the COO cursors, which are atomic) and each ends in a tail of long rows at low occupancy: they
         // run side by side on forked streams and the caller's stream joins them.
+        // the 128- and 256-slot classes go through k_pair_pack, several rows per wave; the raw step and RecommenderSim keep
+        // k_pair_tri there.  XMAP_PAIR_PACKS=0 (tests, A/B runs): every class through k_pair_tri
+        const char *pk_env = getenv("XMAP_PAIR_PACKS");
+        const bool packs = !raw && !coo_ls && !(pk_env && atoi(pk_env) == 0);
         for (int c = 0; c < N_CLASSES; c++) {
             const long long lo = unit_lo > cls_ptr[c] ? unit_lo : cls_ptr[c];
             const long long hi = unit_hi < cls_ptr[c + 1] ? unit_hi : cls_ptr[c + 1];
@@ -755,7 +1110,9 @@ int xmap_sim2_pairs(void *stream, const xmap_ratings *R, int method, int cap, co
             const dim3 grid((unsigned)(hi - lo));
             hipStream_t cs = side->s[c];
             XM_HIP(hipStreamWaitEvent(cs, side->fork, 0));
-            if (coo_ls && !raw) rcode = launch_tri<XMAP_ADJUST_COSINE, true>(c, grid, cs, A);
+            if (packs && pack_units(c))
+                rcode = method == XMAP_COSINE ? launch_pack<XMAP_COSINE>(c, hi - lo, cs, A) : launch_pack<XMAP_ADJUST_COSINE>(c, hi - lo, cs, A);
+            else if (coo_ls && !raw) rcode = launch_tri<XMAP_ADJUST_COSINE, true>(c, grid, cs, A);
             else if (method == XMAP_COSINE) rcode = launch_tri<XMAP_COSINE, false>(c, grid, cs, A);
             else rcode = launch_tri<XMAP_ADJUST_COSINE, false>(c, grid, cs, A);
             if (rcode) return rcode;
