@@ -126,5 +126,55 @@ __device__ __forceinline__ void item_stats_group(bool on, int i, int gl, int I, 
     }
 }
 
+// The same statistics for an item of at most G * UN raters [p0, p1) whose source hands out whole rater records (Src::Rec:
+// tri_layout.hip), with every load in flight before the first is used: a lane asks for its UN records, then for their UN user
+// averages, and only then adds -- in the order of item_stats_group's walk (iteration t of lane gl is rater p0 + gl + t G), one
+// accumulator set per lane, so every sum has that walk's bits.  The flags are set from the records in the registers: one
+// 4-byte store where the flag is raised, no second load.
+template <int G, int UN, typename Src>
+__device__ __forceinline__ void item_stats_records(bool on, int i, int gl, int I, long long p0, long long p1, const Src src,
+                                                   double *info, double *norms) {
+    typename Src::Rec x[UN];
+    double av[UN];
+    bool v[UN];
+#pragma unroll
+    for (int t = 0; t < UN; t++) {
+        v[t] = on && p0 + gl + t * G < p1;
+        if (v[t]) x[t] = src.rec(p0 + gl + t * G);
+    }
+#pragma unroll
+    for (int t = 0; t < UN; t++) av[t] = v[t] ? src.uavg(Src::user(x[t])) : 0.0;
+    double s = 0.0, slo = 0.0, q = 0.0, qlo = 0.0, a2 = 0.0, a2lo = 0.0;
+#pragma unroll
+    for (int t = 0; t < UN; t++) {
+        if (!v[t]) continue;
+        const double r = Src::rating(x[t]);
+        const double d = r - av[t];
+        dd_add(s, slo, r);
+        dd_add(q, qlo, r * r);
+        dd_add(a2, a2lo, d * d);
+    }
+    dd_reduce<G>(s, slo);
+    dd_reduce<G>(q, qlo);
+    dd_reduce<G>(a2, a2lo);
+    s = __shfl(s, 0, G);
+    q = __shfl(q, 0, G);
+    a2 = __shfl(a2, 0, G);
+    const double n = on ? (double)(p1 - p0) : 0.0;
+    const double avg = (on && p1 > p0) ? 1.0 * s / n : 0.0;
+    if (on && gl == 0) {
+        info[(size_t)i * 4 + 0] = avg;
+        info[(size_t)i * 4 + 1] = sqrt(q);
+        info[(size_t)i * 4 + 2] = sqrt(a2);
+        info[(size_t)i * 4 + 3] = 1.0 * n;
+        norms[i] = sqrt(q);
+        norms[(size_t)I + i] = sqrt(a2);
+    }
+    if (Src::has_flags)
+#pragma unroll
+        for (int t = 0; t < UN; t++)
+            if (v[t] && Src::rating(x[t]) >= avg) src.raise_flag(p0 + gl + t * G, x[t]);
+}
+
 
 }  // namespace xmap

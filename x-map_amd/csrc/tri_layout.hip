@@ -334,22 +334,46 @@ __device__ __forceinline__ void sort_entry3(const int *uitem, const float *ur32,
     py = WIDE ? __double_as_longlong(ur64[e]) : (long long)(unsigned)__float_as_int(ur32[e]);
 }
 
-template <bool WIDE>
-__device__ __forceinline__ void bitonic_desc3(int width, int pos, unsigned long long &key, int &px, long long &py) {
-#pragma unroll
-    for (int k2 = 2; k2 <= 64; k2 <<= 1) {
-        if (k2 <= width)
-#pragma unroll
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            const unsigned long long ok = __shfl_xor(key, j, 64);
-            const int ox = __shfl_xor(px, j, 64);
-            long long oy;
-            if (WIDE) oy = __shfl_xor(py, j, 64); else oy = (long long)(unsigned)__shfl_xor((int)py, j, 64);
-            const bool desc = (pos & k2) == 0;
-            const bool lower = (pos & j) == 0;
-            const bool take_other = (lower == desc) ? (ok > key) : (ok < key);
-            if (take_other) { key = ok; px = ox; py = oy; }
-        }
+// v of lane ^ J.  Partners inside a row of 16 lanes come through the data-parallel lane selects of the vector unit, which
+// cost no LDS turn and no wait: quad permutations for 1 and 2, half-row mirror then quad reversal for 4 (7 ^ 3), a row
+// rotation by 8 for 8.  All 64 lanes are active wherever the networks run.
+template <int J>
+__device__ __forceinline__ int xor_lane(int v) {
+    if constexpr (J == 1) return __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, true);            // quad_perm:[1,0,3,2]
+    else if constexpr (J == 2) return __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, true);       // quad_perm:[2,3,0,1]
+    else if constexpr (J == 4) {
+        const int h = __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, true);                     // row_half_mirror
+        return __builtin_amdgcn_update_dpp(h, h, 0x1B, 0xF, 0xF, true);                             // quad_perm:[3,2,1,0]
+    } else if constexpr (J == 8) return __builtin_amdgcn_update_dpp(v, v, 0x128, 0xF, 0xF, true);    // row_ror:8
+    else return __shfl_xor(v, J, 64);
+}
+
+// the compare-exchange steps J, J / 2 .. 1 of merge level K2: the lane keeps the larger of the two keys where the network wants
+// the larger one, the smaller where it wants the smaller one, its own on a tie.  The key's low word is the item, so the rating is
+// all that travels with it.
+template <bool WIDE, int K2, int J>
+__device__ __forceinline__ void bitonic_steps3(int pos, unsigned long long &key, long long &py) {
+    if constexpr (J > 0) {
+        const unsigned long long ok = (unsigned long long)(unsigned)xor_lane<J>((int)(unsigned)key) |
+                                      ((unsigned long long)(unsigned)xor_lane<J>((int)(key >> 32)) << 32);
+        long long oy = (long long)(unsigned)xor_lane<J>((int)(unsigned long long)py);
+        if (WIDE) oy |= (long long)((unsigned long long)(unsigned)xor_lane<J>((int)((unsigned long long)py >> 32)) << 32);
+        const bool desc = (pos & K2) == 0;
+        const bool lower = (pos & J) == 0;
+        const bool take_other = (lower == desc) ? (ok > key) : (ok < key);
+        key = take_other ? ok : key;
+        py = take_other ? oy : py;
+        bitonic_steps3<WIDE, K2, J / 2>(pos, key, py);
+    }
+}
+
+// descending bitonic network over groups of `width` lanes (width a power of two <= 64, uniform); pos = lane in group
+template <bool WIDE, int K2 = 2>
+__device__ __forceinline__ void bitonic_desc3(int width, int pos, unsigned long long &key, long long &py) {
+    if constexpr (K2 <= 64) {
+        if (K2 > width) return;
+        bitonic_steps3<WIDE, K2, K2 / 2>(pos, key, py);
+        bitonic_desc3<WIDE, K2 * 2>(width, pos, key, py);
     }
 }
 
@@ -372,51 +396,124 @@ __device__ __forceinline__ void emit_entry3(long long a, int d, int rank, long l
     }
 }
 
-// k_sort_profiles with the item's rater count as the only gather and the sort records as second output
+// The round-3 sort.  A wave takes SORT_NB consecutive users and asks for everything it will need before it uses any of
+// it: the SORT_NB + 1 profile starts in one load; the entries of its short profiles (up to 16 ratings; SORT_NB / 4 rounds of
+// four, one profile per 16-lane group) and of the first SORT_MB profiles of 17..64 ratings (one per wave) with clamped,
+// unconditional loads; then every rater-count gather; then the networks, which are independent chains; then the stores.
+// The network of a round is cut off at the round's longest profile, that of a whole-wave profile at its length, as in
+// k_sort_profiles; profiles above 64 ratings follow one by one, ranked by counting.
+constexpr int SORT_NB = 16;
+constexpr int SORT_MB = 4;
+
+template <bool WIDE>
+__device__ __forceinline__ void entry_load3(const int *uitem, const float *ur32, const double *ur64, long long e, int &it,
+                                            long long &py) {
+    it = uitem[e];
+    py = WIDE ? __double_as_longlong(ur64[e]) : (long long)(unsigned)__float_as_int(ur32[e]);
+}
+
+// up to SORT_MB profiles of 17..64 ratings, one per wave-wide network: k[m] = the user's place in the batch or -1
+struct MidGroup {
+    int k[SORT_MB], a[SORT_MB], d[SORT_MB];     // uniform
+    int it[SORT_MB], c[SORT_MB];
+    long long py[SORT_MB];
+};
+
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_sort_profiles3(long long U, const long long *uptr, const int *uitem, const float *ur32,
                                                         const double *ur64, const int *cnt, unsigned long long *ub_key,
                                                         void *ub, unsigned long long *srec) {
     __shared__ unsigned long long lkeys[4][SORT_LDS];
-    const long long u0 = ((long long)blockIdx.x * 4 + uniform((int)(threadIdx.x >> 6))) * 4;
+    constexpr int ROUNDS = SORT_NB / 4;
+    const int wv = uniform((int)(threadIdx.x >> 6));
+    const long long u0 = ((long long)blockIdx.x * 4 + wv) * SORT_NB;
     if (u0 >= U) return;
     const int lane = lane_id();
     const int g = lane >> 4, gl = lane & 15;
-    {   // the short profiles, one per 16-lane group
-        const long long u = u0 + g;
-        long long a = 0;
-        int d = 0;
-        if (u < U) { a = uptr[u]; d = (int)(uptr[u + 1] - a); }
-        const bool small = d <= 16;
-        int wmax = small ? d : 0;
+    // lane k: start and length of user u0 + k (an empty profile past the last user).  nnz < 2^31 (xmap_sim3_layout)
+    const long long ul = u0 + lane;
+    const int pa = (int)uptr[ul < U ? ul : U];
+    const int dl = __shfl_down(pa, 1, 64) - pa;
+    unsigned midm = (unsigned)__ballot(lane < SORT_NB && dl > 16 && dl <= 64);
+    const unsigned longm = (unsigned)__ballot(lane < SORT_NB && dl > 64);
+
+    MidGroup M;
+    auto mid_request = [&]() {
 #pragma unroll
-        for (int m = 32; m >= 16; m >>= 1) wmax = max(wmax, __shfl_xor(wmax, m, 64));
-        wmax = rl32(wmax, 0);
+        for (int m = 0; m < SORT_MB; m++) {
+            M.k[m] = midm ? __ffs(midm) - 1 : -1;
+            midm &= midm - 1;
+            const int k = M.k[m] >= 0 ? M.k[m] : 0;
+            M.a[m] = rl32(pa, k);
+            M.d[m] = M.k[m] >= 0 ? rl32(dl, k) : 0;
+            entry_load3<WIDE>(uitem, ur32, ur64, lane < M.d[m] ? (long long)M.a[m] + lane : 0ll, M.it[m], M.py[m]);
+        }
+    };
+    auto mid_gather = [&]() {
+#pragma unroll
+        for (int m = 0; m < SORT_MB; m++) M.c[m] = cnt[M.it[m]];
+    };
+    auto mid_finish = [&]() {
+#pragma unroll
+        for (int m = 0; m < SORT_MB; m++) {
+            if (M.k[m] < 0) continue;
+            const int d = M.d[m];
+            const long long a = M.a[m], u = u0 + M.k[m];
+            const bool on = lane < d;
+            unsigned long long key = on ? wkey(M.c[m], M.it[m]) : 0ull;   // pads sort last
+            long long py = on ? M.py[m] : 0ll;
+            bitonic_desc3<WIDE>(pow2_at_least(d), lane, key, py);
+            if (on) emit_entry3<WIDE>(a, d, lane, u, (int)(unsigned)key, py, ub, srec);
+        }
+    };
+
+    // requests: the short profiles' entries, the first whole-wave profiles' entries
+    int sa[ROUNDS], sd[ROUNDS], sit[ROUNDS], sc[ROUNDS];
+    long long spy[ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ROUNDS; r++) {
+        sa[r] = __shfl(pa, r * 4 + g, 64);
+        sd[r] = __shfl(dl, r * 4 + g, 64);
+        const bool on = sd[r] <= 16 && gl < sd[r];
+        entry_load3<WIDE>(uitem, ur32, ur64, on ? (long long)sa[r] + gl : 0ll, sit[r], spy[r]);
+    }
+    mid_request();
+#pragma unroll
+    for (int r = 0; r < ROUNDS; r++) sc[r] = cnt[sit[r]];
+    mid_gather();
+
+#pragma unroll
+    for (int r = 0; r < ROUNDS; r++) {
+        const long long u = u0 + r * 4 + g;
+        const int d = sd[r];
+        const bool small = d <= 16, on = small && gl < d;
+        int wmax = 0;                       // the longest short profile of the round (uniform)
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+            const int dx = rl32(dl, r * 4 + x);
+            wmax = max(wmax, dx <= 16 ? dx : 0);
+        }
         if (wmax > 0) {
-            unsigned long long key = 0ull;   // pads sort last
-            int px = 0;
-            long long py = 0;
-            if (small && gl < d) sort_entry3<WIDE>(uitem, ur32, ur64, cnt, a + gl, key, px, py);
-            bitonic_desc3<WIDE>(pow2_at_least(wmax), gl, key, px, py);
-            if (small && gl < d) emit_entry3<WIDE>(a, d, gl, u, px, py, ub, srec);
+            unsigned long long key = on ? wkey(sc[r], sit[r]) : 0ull;   // pads sort last
+            long long py = on ? spy[r] : 0ll;
+            bitonic_desc3<WIDE>(pow2_at_least(wmax), gl, key, py);
+            if (on) emit_entry3<WIDE>(sa[r], d, gl, u, (int)(unsigned)key, py, ub, srec);
         }
     }
-    for (int q = 0; q < 4; q++) {   // the longer ones on the whole wave
-        const long long u = u0 + q;
-        if (u >= U) break;
-        const long long a = uptr[u];
-        const int d = (int)(uptr[u + 1] - a);
-        if (d <= 16) continue;
-        if (d <= 64) {
-            unsigned long long key = 0ull;
-            int px = 0;
-            long long py = 0;
-            if (lane < d) sort_entry3<WIDE>(uitem, ur32, ur64, cnt, a + lane, key, px, py);
-            bitonic_desc3<WIDE>(pow2_at_least(d), lane, key, px, py);
-            if (lane < d) emit_entry3<WIDE>(a, d, lane, u, px, py, ub, srec);
-            continue;
-        }
-        unsigned long long *keys = d <= SORT_LDS ? lkeys[uniform((int)(threadIdx.x >> 6))] : ub_key + a;
+    for (;;) {
+        mid_finish();
+        if (!midm) break;
+        mid_request();
+        mid_gather();
+    }
+
+    // longer than a wave: rank by counting.  The keys are staged in LDS (or, past SORT_LDS of them, in the ub_key scratch) and
+    // every entry counts the heavier ones.
+    for (unsigned lm = longm; lm; lm &= lm - 1) {
+        const int k = __ffs(lm) - 1;
+        const long long a = rl32(pa, k), u = u0 + k;
+        const int d = rl32(dl, k);
+        unsigned long long *keys = d <= SORT_LDS ? lkeys[wv] : ub_key + a;
         for (int p = lane; p < d; p += 64) {
             unsigned long long key;
             int px;
@@ -521,6 +618,12 @@ struct RcSrc {
     __device__ __forceinline__ void load(long long p, double &r, int &u) const { const RaterRec x = rc[p]; r = (double)x.rating; u = x.user; }
     __device__ __forceinline__ double uavg(int u) const { return u_avg[u]; }
     __device__ __forceinline__ void set_flag(long long p, bool ge) const { if (ge) rc[p].pos_ge |= (int)0x80000000u; }
+    // whole records (item_stats_records): one 16-byte load holds the rating, the user and the flag word
+    typedef RaterRec Rec;
+    __device__ __forceinline__ Rec rec(long long p) const { return rc[p]; }
+    static __device__ __forceinline__ double rating(const Rec &x) { return (double)x.rating; }
+    static __device__ __forceinline__ int user(const Rec &x) { return x.user; }
+    __device__ __forceinline__ void raise_flag(long long p, const Rec &x) const { rc[p].pos_ge = (int)((unsigned)x.pos_ge | 0x80000000u); }
 };
 struct RcWideSrc {
     const RaterRecWide *rc;
@@ -528,6 +631,11 @@ struct RcWideSrc {
     __device__ __forceinline__ void load(long long p, double &r, int &u) const { r = rc[p].rating; u = 0; }
     __device__ __forceinline__ double uavg(int) const { return 0.0; }
     __device__ __forceinline__ void set_flag(long long, bool) const {}
+    typedef RaterRecWide Rec;
+    __device__ __forceinline__ Rec rec(long long p) const { return rc[p]; }
+    static __device__ __forceinline__ double rating(const Rec &x) { return x.rating; }
+    static __device__ __forceinline__ int user(const Rec &) { return 0; }
+    __device__ __forceinline__ void raise_flag(long long, const Rec &) const {}
 };
 
 // Items with more than STAT_BIG raters (up to 1e5 at BASELINE configs[1]: one wave walking them was the kernel's tail, and
@@ -551,15 +659,18 @@ __global__ __launch_bounds__(256) void k_item_stats3(int I, int lo, int hi, cons
     const int i0 = lo + (blockIdx.x * 4 + uniform((int)(threadIdx.x >> 6))) * 4;
     if (i0 >= hi) return;
     const int lane = lane_id();
-    {
+    // lane k: where the records of item i0 + k start and how many there are (none past the range); one load for the wave
+    const long long pl = iptr[min(i0 + lane, hi)];
+    const long long nl = __shfl_down(pl, 1, 64) - pl;
+    {   // up to 64 raters: four items at a time, one per 16-lane group, four records a lane
         const int i = i0 + (lane >> 4);
-        const bool on = i < hi && iptr[i + 1] - iptr[i] <= 64;
-        item_stats_group<16, Src, false>(on, i, lane & 15, I, iptr, src, info, norms, nullptr, nullptr);
+        const long long p0 = __shfl(pl, lane >> 4, 64), n = __shfl(nl, lane >> 4, 64);
+        item_stats_records<16, 4, Src>(i < hi && n <= 64, i, lane & 15, I, p0, p0 + n, src, info, norms);
     }
     for (int t = 0; t < 4; t++) {
         const int i = i0 + t;
         if (i >= hi) break;
-        const long long n = iptr[i + 1] - iptr[i];
+        const long long n = rl64(nl, t);
         if (n <= 64) continue;
         if (n > STAT_BIG) {
             if (lane == 0) {
@@ -572,7 +683,7 @@ __global__ __launch_bounds__(256) void k_item_stats3(int I, int lo, int hi, cons
             }
             continue;
         }
-        item_stats_group<64, Src, false>(true, i, lane, I, iptr, src, info, norms, nullptr, nullptr);
+        item_stats_group<64, Src, false>(true, i, lane, I, iptr, src, info, norms, nullptr, nullptr);     // 65 .. STAT_BIG: the whole wave walks
     }
 }
 
@@ -962,7 +1073,7 @@ int xmap_sim3_layout(void *stream, const xmap_ratings *R, int64_t *item_ptr, con
         if (rcode) return rcode;
         // sorted profiles + sort records (no mutuality flags yet)
         if (R->n_users > 0 && nnz > 0) {
-            const dim3 grid((unsigned)((R->n_users + 15) / 16));
+            const dim3 grid((unsigned)((R->n_users + 4 * SORT_NB - 1) / (4 * SORT_NB)));
             (wide ? k_sort_profiles3<true> : k_sort_profiles3<false>)<<<grid, dim3(256), 0, st>>>(
                 R->n_users, (const long long *)R->user_ptr, R->user_item, wide ? nullptr : R->user_rating, rating64, cnt,
                 (unsigned long long *)ub_key, ub, (unsigned long long *)srec);
