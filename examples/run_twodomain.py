@@ -6,7 +6,13 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K]]
+
+--user-based: the recommender stages with the user method of the reference's egg (calculate_xmap_sim_method = cosine_user): the
+similarity between the users' AlterEgo profiles with its local sensitivity on the device (xmap.engine.session.UserSimRDD), the
+neighbour selection, the user-based prediction; prints the single MAE of a user method.  The AlterEgo rows of a user who rated a
+target item AND holds it through the map carry that item twice; cosine_user on the device takes profiles without repeated items,
+so such rows are merged first as the reference's avoid_duplicate_ratings merges mapped ratings (the mean, the first time).
 
 --device-tail: the recommender stages run from the AlterEgo rows in HBM to the predictions without a host conversion
 (xmap.engine.session.recommend; non-private neighbour selection) and print the same MAE line.  After the MAE line: the ranking
@@ -107,6 +113,15 @@ def write_inputs(workdir, users, items, seed):
     return path
 
 
+def merge_repeated_items(sc, alterEgo_profile):
+    """(uid, iid, rating, time) rows with one row per (uid, iid): the mean rating and the first time of the rows that meet"""
+    import numpy as np
+    merged = {}
+    for uid, iid, rating, when in alterEgo_profile.collect():
+        merged.setdefault((uid, iid), []).append((rating, when))
+    return sc.parallelize([(uid, iid, float(np.mean([r for r, _ in v])), v[0][1]) for (uid, iid), v in merged.items()])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=3000)
@@ -114,6 +129,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=31)
     ap.add_argument("--workdir", default="/tmp/xmap_demo")
     ap.add_argument("--private", action="store_true")
+    ap.add_argument("--user-based", action="store_true")
     ap.add_argument("--device-tail", action="store_true")
     ap.add_argument("--fold-in", action="store_true")
     ap.add_argument("--explain", action="store_true")
@@ -129,6 +145,10 @@ def main(argv=None):
     if args.private:
         para["generator"]["private_flag"] = True
         para["recommender"]["private_flag"] = True
+    if args.user_based:
+        if args.device_tail:
+            ap.error("--user-based runs the reference pipeline; --device-tail is the item-based tail")
+        para["recommender"]["calculate_xmap_sim_method"] = "cosine_user"
     sc = SparkContext(conf=SparkConf().setAppName("xmap two-domain on MI355X"))
     sqlContext = SQLContext(sc)
     b, g, rc = para["baseliner"], para["generator"], para["recommender"]
@@ -194,8 +214,9 @@ def main(argv=None):
                           rc["mapping_range"], rc["decay_alpha"])
         mae = rpred.calculate_mae(predicted)
     else:
+        profile = merge_repeated_items(sc, alterEgo_profile) if args.user_based else alterEgo_profile
         _, _, ubd, ibd, uinfo, iinfo, alterEgo_sim = timed(
-            "recommender_sim", assist.recommender_calculate_sim_pipeline, sc, rsim, alterEgo_profile)
+            "recommender_sim", assist.recommender_calculate_sim_pipeline, sc, rsim, profile)
         kept = timed("recommender_privacy", assist.recommender_privacy_pipeline, rpriv, alterEgo_sim, rc["private_flag"])
         simpair_bd = sc.broadcast(kept.collectAsMap())
         mae = timed("recommender_prediction", assist.recommender_prediction_pipeline, rpred, rsim, testRDD, simpair_bd,
@@ -204,6 +225,9 @@ def main(argv=None):
     sc.stop()
     print("train users %d, test users %d, sim pairs %d, AlterEgo rows %d" % (
         trainRDD.count(), testRDD.count(), item2item_simRDD.count(), alterEgo_profile.count()))
+    if args.user_based:
+        print("MAE (user-based):", mae)
+        return mae
     print("MAE (no decay; decay):", mae)
     from xmap.engine import session
     if isinstance(alterEgo_profile, session.AlterEgoRDD) and not rc["private_flag"]:

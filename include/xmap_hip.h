@@ -1012,6 +1012,26 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                    const double *hd_x, const double *nrm, int64_t max_records /*0: library default*/, int32_t *out_cnt,
                    int32_t *out_user, double *out_sim, int32_t *out_common,
                    const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
+/* xmap_peer_rows_ls: xmap_peer_rows plus the LOCAL SENSITIVITY of every returned entry -- the second half of the reference's
+ * ((id1, id2), [sim, LS]) record of a user method (cosine_user), by which the private perturbation scales its noise.  out_cnt /
+ * out_user / out_sim / out_common and h_stats are the bytes xmap_peer_rows writes for the same inputs; rules, chunking, masks,
+ * exclusions, floor, fold-in queries and flags are unchanged.  For a returned entry (q, v) with its n records in record order,
+ * record t made of a_t = the x of the query's row and b_t = the x of the holder's row, inner = the entry's dot, nx = the query's
+ * nrm, ny = nrm[v]; per record, one rounded fp64 operation per step, no fused multiply-add:
+ *   rest = inner - a_t * b_t;  m1 = sqrt((nx * nx - a_t * a_t) * (ny * ny));  m2 = sqrt((nx * nx) * (ny * ny - b_t * b_t));
+ *   d1 = |w(m1 != 0 ? 1.0 * rest / m1 : 0.0) - sim|, d2 likewise with m2, w(c) = 1.0 * c * min(n - 1, cap) / cap
+ * out_ls [n_query][n_top] = the largest d over the records, a NaN above everything (a maximum of bit patterns: no order of
+ * evaluation enters); 0.0 behind the count.  An entry of one record has ls = |sim|.  It depends on neither the grid, nor the
+ * chunking, nor max_records.  The expansion writes the two factors instead of their product and the reduce multiplies them (the
+ * same bits); the sensitivity is taken for the returned entries only, one wave per entry, which finds its run by bisection.
+ * Temporaries: 80 B per record of the largest chunk instead of 64 B (the second factor, and the dot of every run).  The host
+ * checks of xmap_peer_rows; out_ls == NULL is XMAP_ERR_ARG before any device work.  Syncs. */
+int xmap_peer_rows_ls(void *stream, int64_t n_query, const int32_t *query_user, int64_t n_q_users, const int64_t *q_ptr,
+                      const int32_t *q_item, const double *q_rating, int32_t flags, int32_t n_top, int32_t cap, int32_t min_common,
+                      int64_t n_users, int32_t n_items, const double *centre, const int64_t *hd_ptr, const int32_t *hd_user,
+                      const double *hd_x, const double *nrm, int64_t max_records /*0: library default*/, int32_t *out_cnt,
+                      int32_t *out_user, double *out_sim, int32_t *out_common, double *out_ls /*[n_query][n_top], 0.0 behind the count*/,
+                      const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
 
 /* ---- user-kNN (csrc/stage_e_uknn.hip; DESIGN.md 4 "User-kNN"): "people like you rated this highly" -- predictions and top-N
  * lists from the peer lists of xmap_peer_rows.  The reference's user_based_prediction restated.  All arithmetic is fp64, one
@@ -1401,6 +1421,11 @@ int xmap_ctx_recommend_group(xmap_ctx *ctx, int32_t source, int64_t n_groups, co
 int xmap_ctx_peers(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
                    int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common,
                    const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
+/* xmap_ctx_peers plus the local sensitivity of every returned entry (xmap_peer_rows_ls): the same sources, flags, index cache
+ * and host checks -- on XMAP_ERR_ARG (out_ls == NULL included) the outputs keep every byte.  Host out_ls [n_query][n_top]. */
+int xmap_ctx_peers_ls(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags,
+                      int32_t cap, int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common,
+                      double *out_ls, const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
 /* User-kNN: the peers of the users in question by xmap_peer_rows exactly as xmap_ctx_peers runs it (source, n_nb as its n_top,
  * peer_flags = XMAP_PEERS_KEEP_SELF | XMAP_PEERS_CENTRED, cap, min_common; no rules on the peers), the means by xmap_uknn_means
  * (the resident users'; with XMAP_SRC_FOLDIN the queries' own means over the batch's profiles), then xmap_uknn_predict_rows /

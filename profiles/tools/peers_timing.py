@@ -10,6 +10,11 @@ construction and the protocol of group_timing.py: HIP events, a warm-up of every
                 the call cannot be faster than its sort.  What stays inside the clock beyond the call's own sort: the hook's two
                 arena temporaries per chunk (the call takes its sort buffers once)
 
+    <list>_rows, <list>_ls, <list>_parent    with --ls / --parent-lib: xmap_peer_rows and xmap_peer_rows_ls of this build and
+                xmap_peer_rows of ANOTHER build of the library (the parent commit's libxmap_hip.so), all three through one path
+                -- ctypes on output tensors made once -- and in turn within every repetition, so that a pair of medians is a pair of
+                alternating runs on one box.  Reported: <list>_ls_over_rows and <list>_rows_over_parent
+
 and records the medians, the records per call, the chunks, the key widths and the stats of both calls.  --no-sort leaves the
 sort_* variants out and --lists picks the calls: for a kernel trace of the calls alone
 (rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python profiles/tools/peers_timing.py --no-sort --reps 2).
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--no-sort", action="store_true")
     ap.add_argument("--lists", default="random,heavy")
+    ap.add_argument("--ls", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -96,6 +103,27 @@ def main():
     with_rows = torch.nonzero(P.user_ptr[1:] > P.user_ptr[:-1]).flatten().cpu().numpy()
     q_random = torch.from_numpy(with_rows[rng.integers(0, len(with_rows), args.queries)].astype(np.int32)).to(dev)
     q_heavy = torch.topk(per_user, args.queries).indices.to(torch.int32)
+    parent = C.CDLL(os.path.abspath(args.parent_lib)) if args.parent_lib else None
+    if parent:
+        res["parent_version"] = int(parent.xmap_version())
+
+    def raw(L, q, ls):
+        """xmap_peer_rows (ls: xmap_peer_rows_ls) of the library L on outputs made once"""
+        n_q = int(q.numel())
+        o_cnt = torch.empty(n_q, dtype=torch.int32, device=dev)
+        o_user, o_common = [torch.empty((n_q, args.n_top), dtype=torch.int32, device=dev) for _ in range(2)]
+        o_sim, o_ls = [torch.empty((n_q, args.n_top), dtype=torch.float64, device=dev) for _ in range(2)]
+        f = L.xmap_peer_rows_ls if ls else L.xmap_peer_rows
+
+        def call():
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            a = [st, abi.i64(n_q), abi.vp(q), abi.i64(P.n_users), abi.vp(P.user_ptr), abi.vp(P.user_item), abi.vp(P.user_rating64),
+                 abi.i32(abi.PEERS_SAME), abi.i32(args.n_top), abi.i32(args.cap), abi.i32(1), abi.i64(X.n_users), abi.i32(X.n_items),
+                 abi.vp(X.centre), abi.vp(X.hd_ptr), abi.vp(X.hd_user), abi.vp(X.hd_x), abi.vp(X.nrm), abi.i64(0), abi.vp(o_cnt),
+                 abi.vp(o_user), abi.vp(o_sim), abi.vp(o_common)] + ([abi.vp(o_ls)] if ls else []) + [None, None]
+            rc = f(*a)
+            assert rc == 0, rc
+        return call
     calls = []
     for name, q in [c for c in (("random", q_random), ("heavy", q_heavy)) if c[0] in args.lists.split(",")]:      # at most --max-records records per call: fewer queries if need be
         fits = int((torch.cumsum(per_user[q.long()], 0) <= args.max_records).sum().item())
@@ -109,6 +137,12 @@ def main():
         n_rec = int(out[4][5])
         res["records"][name] = n_rec
         variants.append((name, lambda q=q: e2.peers(X, P, q, args.n_top, cap=args.cap, same=True)))
+        if args.ls or parent:
+            variants.append((name + "_rows", raw(abi.lib, q, False)))
+        if args.ls:
+            variants.append((name + "_ls", raw(abi.lib, q, True)))
+        if parent:
+            variants.append((name + "_parent", raw(parent, q, False)))
         if args.no_sort:
             continue
         # the sort alone, chunk by chunk as the call cuts the queries: consecutive queries with at most 2^22 records, or one query
@@ -150,6 +184,11 @@ def main():
     res["ms_all"] = {v: [float(x) for x in t] for v, t in times.items()}
     for name, _ in ([] if args.no_sort else calls):
         res[name + "_over_sort"] = res["ms"][name] / max(res["ms"]["sort_" + name], 1e-9)
+    for name, _ in calls:
+        if args.ls:
+            res[name + "_ls_over_rows"] = res["ms"][name + "_ls"] / max(res["ms"][name + "_rows"], 1e-9)
+        if parent:
+            res[name + "_rows_over_parent"] = res["ms"][name + "_rows"] / max(res["ms"][name + "_parent"], 1e-9)
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:

@@ -1493,9 +1493,10 @@ static int peer_index_of(xmap_ctx *c, int z) {
     return XMAP_OK;
 }
 
-int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
-                   int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, const xmap_rec_filter *F,
-                   int64_t *stats) {
+// xmap_ctx_peers (with_ls = false, out_ls unused) and xmap_ctx_peers_ls
+static int ctx_peers_run(xmap_ctx *c, bool with_ls, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags,
+                         int32_t cap, int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common,
+                         double *out_ls, const xmap_rec_filter *F, int64_t *stats) {
     // the host checks: before any device work, the outputs untouched, the context as it was
     XM_ARG(n_top >= 1 && n_top <= 1024);
     XM_ARG(cap >= 1);
@@ -1503,6 +1504,7 @@ int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *
     XM_ARG((flags & ~(XMAP_PEERS_KEEP_SELF | XMAP_PEERS_CENTRED)) == 0);
     XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN);       // an item fold-in adds items, not users
     XM_ARG(n_query >= 0 && (n_query == 0 || (query_user && out_cnt && out_user && out_sim && out_common)));
+    XM_ARG(!with_ls || out_ls);
     XM_TRY(check_filter(F, n_query));
     XM_ARG(c && c->have_gen && c->have_rec);
     XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
@@ -1525,14 +1527,36 @@ int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *
     XM_TRY(dalloc(tmp, &d_sim, m, c->st)); XM_TRY(dalloc(tmp, &d_common, m, c->st));
     xmap_rec_filter D;
     XM_TRY(upload_filter(c, tmp, F, n_query, U, &D));
-    XM_TRY(xmap_peer_rows(c->st, n_query, d_query, Q.n_users, Q.ptr, Q.item, Q.rating, fl, n_top, cap, min_common, U, I, centre,
-                          c->pr_hd_ptr[z], c->pr_hd_user[z], c->pr_hd_x[z], c->pr_nrm[z], 0, d_cnt, d_user, d_sim, d_common, &D, stats));
+    double *d_ls = nullptr;
+    if (with_ls) {
+        XM_TRY(dalloc(tmp, &d_ls, m, c->st));
+        XM_TRY(xmap_peer_rows_ls(c->st, n_query, d_query, Q.n_users, Q.ptr, Q.item, Q.rating, fl, n_top, cap, min_common, U, I, centre,
+                                 c->pr_hd_ptr[z], c->pr_hd_user[z], c->pr_hd_x[z], c->pr_nrm[z], 0, d_cnt, d_user, d_sim, d_common, d_ls,
+                                 &D, stats));
+    } else
+        XM_TRY(xmap_peer_rows(c->st, n_query, d_query, Q.n_users, Q.ptr, Q.item, Q.rating, fl, n_top, cap, min_common, U, I, centre,
+                              c->pr_hd_ptr[z], c->pr_hd_user[z], c->pr_hd_x[z], c->pr_nrm[z], 0, d_cnt, d_user, d_sim, d_common, &D, stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_user, (const int32_t *)d_user, m, c->st));
     XM_TRY(d2h(out_sim, (const double *)d_sim, m, c->st));
     XM_TRY(d2h(out_common, (const int32_t *)d_common, m, c->st));
+    if (with_ls) XM_TRY(d2h(out_ls, (const double *)d_ls, m, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
     return XMAP_OK;
+}
+
+int xmap_ctx_peers(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
+                   int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, const xmap_rec_filter *F,
+                   int64_t *stats) {
+    return ctx_peers_run(c, false, source, n_query, query_user, n_top, flags, cap, min_common, out_cnt, out_user, out_sim, out_common,
+                         nullptr, F, stats);
+}
+
+int xmap_ctx_peers_ls(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int32_t cap,
+                      int32_t min_common, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, double *out_ls,
+                      const xmap_rec_filter *F, int64_t *stats) {
+    return ctx_peers_run(c, true, source, n_query, query_user, n_top, flags, cap, min_common, out_cnt, out_user, out_sim, out_common,
+                         out_ls, F, stats);
 }
 
 // ---- user-kNN: predictions and top-N from the peer lists ----------------------------------------------------------------------------

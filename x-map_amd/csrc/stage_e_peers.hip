@@ -22,6 +22,12 @@
 //   k_pr_heads -> scan -> k_pr_starts, k_pr_first : runs, and per query of the chunk its first run
 //   k_pr_reduce    : one lane per run: self rule, exclusion list, min_common, dot = the double-double chain, sim, the floor
 //   k_pr_select    : au_select_segment (au_select.h) over the runs of a query; position in the segment ascends with the user
+// With the local sensitivity (xmap_peer_rows_ls; LS = true of the templates below -- xmap_peer_rows is the LS = false code): the
+// expansion writes the two factors of a record instead of their product, the reduce multiplies them (the same bits) and keeps the
+// dot of every run, and after the selection
+//   k_pr_ls        : one wave per returned entry: its run by bisection among the runs of the query (they ascend with the user),
+//                    the leave-one-out distances of the records lane-strided, the largest as an integer (ls_key of tri.h: a
+//                    maximum of integers, so the order of the lanes does not matter)
 #include <vector>
 
 #include "common.h"
@@ -33,7 +39,7 @@
 
 namespace xmap {
 
-constexpr long long PR_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (64 B each: 270 MB of temporaries)
+constexpr long long PR_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (64 B each: 270 MB of temporaries; 80 B with the local sensitivity)
 
 __device__ __forceinline__ double pr_x(const int *item, const double *rating, const double *centre, long long p) {
     return centre ? rating[p] - centre[item[p]] : rating[p];
@@ -138,11 +144,12 @@ __global__ __launch_bounds__(256) void k_pr_qrec(long long n_query, const long l
     if (q <= n_query) qrec[q] = rec_off[qrow_off[q]];
 }
 
+template <bool LS>
 __global__ __launch_bounds__(256) void k_pr_expand(long long n, long long rec0, long long e0, long long e1, long long q0, long long q1,
                                                    const long long *qrow_off, const long long *rec_off, const int *query_user,
                                                    const long long *qptr, const int *qitem, const double *qrating, const double *centre,
                                                    const long long *hd_ptr, const int *hd_user, const double *hd_x, int user_bits,
-                                                   unsigned long long *keys, int *vals, double *tv) {
+                                                   unsigned long long *keys, int *vals, double *tv, double *tb) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     const long long g = rec0 + t;
@@ -152,16 +159,18 @@ __global__ __launch_bounds__(256) void k_pr_expand(long long n, long long rec0, 
     const long long h = hd_ptr[qitem[p]] + (g - rec_off[e]);    // (a row with records has a valid item)
     keys[t] = ((unsigned long long)(q - q0) << user_bits) | (unsigned long long)(unsigned)hd_user[h];
     vals[t] = (int)t;
-    tv[t] = pr_x(qitem, qrating, centre, p) * hd_x[h];
+    if constexpr (LS) { tv[t] = pr_x(qitem, qrating, centre, p); tb[t] = hd_x[h]; }     // the factors: the query's x, the holder's x
+    else tv[t] = pr_x(qitem, qrating, centre, p) * hd_x[h];
 }
 
 // under a mask: one wave per query row of the chunk, the eligible holders compacted in holder order at rec_off[e] - rec0
+template <bool LS>
 __global__ __launch_bounds__(256) void k_pr_expand_masked(long long rec0, long long e0, long long e1, long long q0, long long q1,
                                                           const long long *qrow_off, const long long *rec_off, const int *query_user,
                                                           const long long *qptr, const int *qitem, const double *qrating,
                                                           const double *centre, int I, const long long *hd_ptr, const int *hd_user,
                                                           const double *hd_x, const unsigned int *allow, int user_bits,
-                                                          unsigned long long *keys, int *vals, double *tv) {
+                                                          unsigned long long *keys, int *vals, double *tv, double *tb) {
     const long long e = e0 + (long long)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
     if (e >= e1) return;
     const int lane = lane_id();
@@ -183,7 +192,8 @@ __global__ __launch_bounds__(256) void k_pr_expand_masked(long long rec0, long l
         if (m && at < end) {                    // (at < end: the count pass saw the same mask)
             keys[at] = ((unsigned long long)(q - q0) << user_bits) | (unsigned long long)(unsigned)v;
             vals[at] = (int)at;
-            tv[at] = xp * hd_x[h];
+            if constexpr (LS) { tv[at] = xp; tb[at] = hd_x[h]; }
+            else tv[at] = xp * hd_x[h];
         }
         o += __popcll(mask);
     }
@@ -192,9 +202,11 @@ __global__ __launch_bounds__(256) void k_pr_expand_masked(long long rec0, long l
 // k_pr_heads, k_pr_starts, k_pr_first: sorted_runs.h
 
 // one lane per run, records in sorted (= expansion) order.  cnt: [0] dropped by min_common, [1] non-finite, [2] below the floor
+// LS: tv / tb are the factors, r_dot[r] = the dot of a kept run
+template <bool LS>
 __global__ __launch_bounds__(256) void k_pr_reduce(long long n, const unsigned long long *keys, const int *vals, const double *tv,
-                                                   const long long *run_idx, const int *run_start, int user_bits, long long q0,
-                                                   const int *query_user, int same, int keep_self, const long long *ex_ptr,
+                                                   const double *tb, double *r_dot, const long long *run_idx, const int *run_start,
+                                                   int user_bits, long long q0, const int *query_user, int same, int keep_self, const long long *ex_ptr,
                                                    const int *ex_id, int min_common, int cap, double min_score, const double *qnrm,
                                                    const double *nrm, int *r_status, double *r_sim, int *r_common,
                                                    unsigned long long *cnt) {
@@ -216,7 +228,11 @@ __global__ __launch_bounds__(256) void k_pr_reduce(long long n, const unsigned l
         if (out) { r_status[r] = PR_NOT_CANDIDATE; continue; }
         if (nc < min_common) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[0], 1ull); continue; }
         double dot = 0.0, lo = 0.0;
-        for (int t = s; t < e; t++) dd_add(dot, lo, tv[vals[t]]);
+        if constexpr (LS) {
+            for (int t = s; t < e; t++) { const int i = vals[t]; dd_add(dot, lo, tv[i] * tb[i]); }
+            r_dot[r] = dot;
+        } else
+            for (int t = s; t < e; t++) dd_add(dot, lo, tv[vals[t]]);
         const double np = qnrm[q] * nrm[v];
         const double sim = weighted((np != 0.0) ? dot / np : 0.0, nc, cap);     // NaN != 0: divides
         if (!(fabs(sim) <= 1.7976931348623157e308)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
@@ -228,6 +244,56 @@ __global__ __launch_bounds__(256) void k_pr_reduce(long long n, const unsigned l
 
 // k_pr_select (cnt [3] candidates after the self rule, the exclusions and the mask, [4] the largest such count of one query)
 // and k_pr_blank: sorted_runs.h
+
+// The local sensitivity of the returned entries of a chunk, one wave per cell c = x * n_top + j of its nq queries (base: the first
+// cell of this launch).  Entry j of query q0 + x is user v; its run is the one of v among the runs [first[x], first[x + 1]) of the
+// query, which ascend with the user.  Per record, with a / b the query's and the holder's x (recommenderSim.py:98-116 between
+// users, as k_if_reduce takes it between items): rest = inner - a b; the two norms with the record left out of one side;
+// d = |weighted(rest / m, n - 1, cap) - sim|.  ls = the largest d, NaN above everything.
+__global__ __launch_bounds__(256) void k_pr_ls(long long base, long long n_cells, long long q0, int n_top, const long long *first,
+                                               const unsigned long long *keys, const int *vals, const double *ta, const double *tb,
+                                               const int *run_start, int user_bits, const double *r_dot, int cap, const double *qnrm,
+                                               const double *nrm, const int *out_cnt, const int *out_user, const double *out_sim,
+                                               double *out_ls) {
+    const long long c = base + (long long)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
+    if (c >= n_cells) return;                   // (wave-uniform)
+    const long long x = c / n_top;
+    const int j = (int)(c - x * n_top);
+    const long long q = q0 + x;
+    if (j >= out_cnt[q]) return;                // behind the count: the blank 0.0 stands
+    const size_t o = (size_t)q * n_top + j;
+    const int v = out_user[o];
+    const unsigned long long umask = (1ull << user_bits) - 1ull;
+    long long lo = first[x], hi = first[x + 1];         // the first run of the query whose user is >= v
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if ((long long)(keys[run_start[mid]] & umask) >= (long long)v) hi = mid; else lo = mid + 1;
+    }
+    if (lo >= first[x + 1] || (int)(keys[run_start[lo]] & umask) != v) return;      // (every returned entry has its run)
+    const int s = run_start[lo], e = run_start[lo + 1];
+    const int nc = e - s;
+    const double inner = r_dot[lo], sim = out_sim[o];
+    const double nx = qnrm[q], ny = nrm[v];
+    long long best = 0ll;                       // ls_key: the bits of a non-negative double, below 2^63
+    for (int t = s + lane_id(); t < e; t += WAVE) {
+        const int i = vals[t];
+        const double a = ta[i], b = tb[i];
+        const double rest = inner - a * b;
+        const double m1 = sqrt((nx * nx - a * a) * (ny * ny));
+        const double m2 = sqrt((nx * nx) * (ny * ny - b * b));
+        const double d1 = fabs(weighted((m1 != 0.0) ? 1.0 * rest / m1 : 0.0, nc - 1, cap) - sim);
+        const double d2 = fabs(weighted((m2 != 0.0) ? 1.0 * rest / m2 : 0.0, nc - 1, cap) - sim);
+        const long long k1 = (long long)ls_key(d1), k2 = (long long)ls_key(d2);
+        const long long k = k1 > k2 ? k1 : k2;
+        best = k > best ? k : best;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const long long other = __shfl_xor(best, m, WAVE);
+        best = other > best ? other : best;
+    }
+    if (lane_id() == 0) out_ls[o] = __longlong_as_double(best);
+}
 
 // avg[i] of the x of item i's holders: the exact double-double sum rounded once, divided by the entries -- what item_stats.h
 // computes for an item of RecommenderSim (lane-strided sums, the fixed butterfly of dd_reduce); one wave per item
@@ -253,6 +319,14 @@ static int pr_norms(hipStream_t st, long long n, const int *sel, long long U, in
 }  // namespace xmap
 
 using namespace xmap;
+
+// xmap_peer_rows (LS = false, out_ls unused) and xmap_peer_rows_ls (LS = true)
+template <bool LS>
+static int peer_rows_run(void *stream, int64_t n_query, const int32_t *query_user, int64_t n_q_users, const int64_t *q_ptr, const int32_t *q_item,
+                         const double *q_rating, int32_t flags, int32_t n_top, int32_t cap, int32_t min_common, int64_t n_users, int32_t n_items,
+                         const double *centre, const int64_t *hd_ptr, const int32_t *hd_user, const double *hd_x, const double *nrm,
+                         int64_t max_records, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, double *out_ls,
+                         const xmap_rec_filter *F, int64_t *h_stats);
 
 extern "C" {
 
@@ -312,6 +386,29 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                    const double *centre, const int64_t *hd_ptr, const int32_t *hd_user, const double *hd_x, const double *nrm,
                    int64_t max_records, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, const xmap_rec_filter *F,
                    int64_t *h_stats) {
+    return peer_rows_run<false>(stream, n_query, query_user, n_q_users, q_ptr, q_item, q_rating, flags, n_top, cap, min_common, n_users,
+                                n_items, centre, hd_ptr, hd_user, hd_x, nrm, max_records, out_cnt, out_user, out_sim, out_common, nullptr,
+                                F, h_stats);
+}
+
+int xmap_peer_rows_ls(void *stream, int64_t n_query, const int32_t *query_user, int64_t n_q_users, const int64_t *q_ptr,
+                      const int32_t *q_item, const double *q_rating, int32_t flags, int32_t n_top, int32_t cap, int32_t min_common,
+                      int64_t n_users, int32_t n_items, const double *centre, const int64_t *hd_ptr, const int32_t *hd_user,
+                      const double *hd_x, const double *nrm, int64_t max_records, int32_t *out_cnt, int32_t *out_user, double *out_sim,
+                      int32_t *out_common, double *out_ls, const xmap_rec_filter *F, int64_t *h_stats) {
+    XM_ARG(out_ls);                             // also with n_query == 0
+    return peer_rows_run<true>(stream, n_query, query_user, n_q_users, q_ptr, q_item, q_rating, flags, n_top, cap, min_common, n_users,
+                               n_items, centre, hd_ptr, hd_user, hd_x, nrm, max_records, out_cnt, out_user, out_sim, out_common, out_ls, F,
+                               h_stats);
+}
+}
+
+template <bool LS>
+static int peer_rows_run(void *stream, int64_t n_query, const int32_t *query_user, int64_t n_q_users, const int64_t *q_ptr, const int32_t *q_item,
+                         const double *q_rating, int32_t flags, int32_t n_top, int32_t cap, int32_t min_common, int64_t n_users, int32_t n_items,
+                         const double *centre, const int64_t *hd_ptr, const int32_t *hd_user, const double *hd_x, const double *nrm,
+                         int64_t max_records, int32_t *out_cnt, int32_t *out_user, double *out_sim, int32_t *out_common, double *out_ls,
+                         const xmap_rec_filter *F, int64_t *h_stats) {
     // the host checks: before any device work
     XM_ARG(n_top >= 1 && n_top <= AU_MAX_TOP);
     XM_ARG(cap >= 1);
@@ -349,6 +446,7 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
         const unsigned bb = pr_blocks(cells, 256);
         k_pr_blank<<<dim3(bb < PR_BLANK_BLOCKS ? bb : PR_BLANK_BLOCKS), dim3(256), 0, st>>>(n_query, n_top, out_cnt, out_user, out_sim, out_common);
         XM_LAUNCH_CHECK();
+        if constexpr (LS) XM_HIP(hipMemsetAsync(out_ls, 0, sizeof(double) * (size_t)cells, st));        // 0.0 behind the count
     }
     if (n_qrows == 0 || n_users == 0 || I == 0) { XM_HIP(hipStreamSynchronize(st)); return XMAP_OK; }
     const size_t ne = (size_t)n_qrows;
@@ -402,7 +500,7 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
         unsigned long long *keys = nullptr;
         int *vals = nullptr, *head = nullptr, *run_start = nullptr, *r_status = nullptr, *r_common = nullptr;
         long long *run_idx = nullptr, *first = nullptr;
-        double *tv = nullptr, *r_sim = nullptr;
+        double *tv = nullptr, *r_sim = nullptr, *tb = nullptr, *r_dot = nullptr;
         XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
         XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
         XM_HIP(xm_malloc_async((void **)&tv, sizeof(double) * nm, st));
@@ -413,6 +511,10 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
         XM_HIP(xm_malloc_async((void **)&r_status, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_common, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_sim, sizeof(double) * nm, st));
+        if constexpr (LS) {
+            XM_HIP(xm_malloc_async((void **)&tb, sizeof(double) * nm, st));
+            XM_HIP(xm_malloc_async((void **)&r_dot, sizeof(double) * nm, st));
+        }
         const int same = (flags & XMAP_PEERS_SAME) ? 1 : 0, keep_self = (flags & XMAP_PEERS_KEEP_SELF) ? 1 : 0;
         for (size_t k = 0; k + 1 < cut.size(); k++) {
             const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
@@ -421,15 +523,15 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
             const unsigned nb = pr_blocks(n, 256);
             if (allow) {
                 rc = for_pair_ranges(h_row[q1] - h_row[q0], 4, [&](long long base, long long end, dim3 grid) {      // rows [base, end) of the chunk
-                    k_pr_expand_masked<<<grid, dim3(256), 0, st>>>(h_rec[q0], h_row[q0] + base, h_row[q0] + end, q0, q1, qrow_off, rec_off,
+                    k_pr_expand_masked<LS><<<grid, dim3(256), 0, st>>>(h_rec[q0], h_row[q0] + base, h_row[q0] + end, q0, q1, qrow_off, rec_off,
                                                                    query_user, (const long long *)q_ptr, q_item, q_rating, centre, I,
-                                                                   (const long long *)hd_ptr, hd_user, hd_x, allow, user_bits, keys, vals, tv);
+                                                                   (const long long *)hd_ptr, hd_user, hd_x, allow, user_bits, keys, vals, tv, tb);
                 });
                 if (rc) return rc;
             } else
-                k_pr_expand<<<dim3(nb), dim3(256), 0, st>>>(n, h_rec[q0], h_row[q0], h_row[q1], q0, q1, qrow_off, rec_off, query_user,
+                k_pr_expand<LS><<<dim3(nb), dim3(256), 0, st>>>(n, h_rec[q0], h_row[q0], h_row[q1], q0, q1, qrow_off, rec_off, query_user,
                                                             (const long long *)q_ptr, q_item, q_rating, centre, (const long long *)hd_ptr,
-                                                            hd_user, hd_x, user_bits, keys, vals, tv);
+                                                            hd_user, hd_x, user_bits, keys, vals, tv, tb);
             XM_LAUNCH_CHECK();
             if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, user_bits + pr_bits_for(nq)))) return rc;
             k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
@@ -439,7 +541,7 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
             XM_LAUNCH_CHECK();
             k_pr_first<<<dim3(pr_blocks(nq + 1, 256)), dim3(256), 0, st>>>(nq, n, keys, user_bits, run_idx, first);
             XM_LAUNCH_CHECK();
-            k_pr_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, keys, vals, tv, run_idx, run_start, user_bits, q0, query_user,
+            k_pr_reduce<LS><<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, keys, vals, tv, tb, r_dot, run_idx, run_start, user_bits, q0, query_user,
                                                                             same, keep_self, ex_ptr, ex_id, min_common, cap, min_score, qnrm,
                                                                             nrm, r_status, r_sim, r_common, cnt);
             XM_LAUNCH_CHECK();
@@ -448,6 +550,13 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
                               : pr_select_ranges<1024>(st, nq, q0, n_top, first, keys, run_start, user_bits, r_status, r_sim, r_common, out_cnt,
                                                        out_user, out_sim, out_common, cnt);
             if (rc) return rc;
+            if constexpr (LS) {
+                rc = for_pair_ranges(nq * n_top, 4, [&](long long base, long long end, dim3 grid) {
+                    k_pr_ls<<<grid, dim3(256), 0, st>>>(base, end, q0, n_top, first, keys, vals, tv, tb, run_start, user_bits, r_dot, cap,
+                                                        qnrm, nrm, out_cnt, out_user, out_sim, out_ls);
+                });
+                if (rc) return rc;
+            }
         }
     }
     XM_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -457,5 +566,4 @@ int xmap_peer_rows(void *stream, int64_t n_query, const int32_t *query_user, int
         h_stats[4] = (int64_t)h[4]; h_stats[5] = h_rec[(size_t)n_query];
     }
     return XMAP_OK;
-}
 }

@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
 """RecommenderPrediction: item-based kNN prediction with temporal decay + MAE (mirror of reference
-core/recommenderPrediction.py:5-139).  Evaluation stage downstream of the hot path."""
+core/recommenderPrediction.py:5-139), and the user-based prediction of the reference's prebuilt egg.  Evaluation stage
+downstream of the hot path."""
 import numpy as np
 
 
@@ -69,14 +70,132 @@ class RecommenderPrediction:
         return test_dataRDD.map(lambda line: self.item_based_prediction(
             line, item_based_dict_bd, itembased_sim_pair_dict_bd, item_info_bd))
 
+    def _predict_user_pair(self, uid, pair, neighbours, user_bd):
+        """one (iid, real, time) pair of a test user with a neighbour list: the QUERY's mean is subtracted from the neighbours'
+        ratings, evidence in list order, then profile order"""
+        iid, real, _ = pair
+        base = user_bd.value[uid][0]
+        evidence = []
+        for _, nsim, ratings in neighbours:
+            evidence += [(nsim, rating[1] - base) for rating in ratings if iid in rating[0]]
+        if evidence:
+            predicted = base + sum(s * d for s, d in evidence) / sum(abs(s) for s, _ in evidence)
+        else:
+            predicted = base
+        return iid, real, self.bound_rating(predicted)
+
+    def user_based_prediction(self, line, rating_bd, sim_bd, user_bd):
+        """(uid, [(iid, real, predicted)*]), or (uid, [()]) for a uid without a neighbour list -- what the reference's egg
+        computes.  rating_bd: {uid: [(iid, rating, time)*]}, sim_bd: {uid: [(uid2, sim)*]}, user_bd: {uid: (avg, norm, n)}.
+        As there, a neighbour's rating counts when `iid in rated_iid` (substring test), a neighbour without ratings is a
+        KeyError, and evidence whose sims are all 0.0 a ZeroDivisionError."""
+        uid, pairs = line
+        if uid not in sim_bd.value.keys():
+            return uid, [()]
+        neighbours = [(nb[0], nb[1], rating_bd.value[nb[0]]) for nb in sim_bd.value[uid]]
+        return uid, [self._predict_user_pair(uid, pair, neighbours, user_bd) for pair in pairs]
+
     def user_based_recommendation(self, test_dataRDD, user_based_dict_bd, userbased_sim_pair_dict_bd, user_info_bd):
-        """`recommender_prediction_pipeline` takes this branch when "user" is in the similarity method
-        (reference utils/assist.py:199-202), but the reference's source tree has no such method -- it shipped in the
-        project's prebuilt egg only (core/recommenderPrediction.py defines the item-based pair alone) -- so a caller of the
-        reference gets an AttributeError at this point, and so does a caller of this package."""
-        raise AttributeError("'RecommenderPrediction' object has no attribute 'user_based_recommendation' "
-                             "(absent from the reference's sources as well: reference utils/assist.py:199-202 calls a method "
-                             "that only its prebuilt egg had)")
+        """`recommender_prediction_pipeline` takes this branch when "user" is in the similarity method (reference
+        utils/assist.py:199-202; the method shipped in the reference's prebuilt egg).  No temporal decay.  On a machine with the
+        HIP library and a GPU the pairs are predicted by `xmap_uknn_predict_rows` (csrc/stage_e_uknn.hip: one wave per test pair,
+        the same operations in the same order) whenever the substring test `iid in rated_iid` is an equality test, i.e. all item
+        ids have one length; a pair the kernel flags (an item no profile holds, evidence the statement raises on) and every
+        other input go through the Python statement above.  Both give the same tuples (tests/test_gpu_user_sim.py)."""
+        out = self._device_user_recommendation(test_dataRDD, user_based_dict_bd, userbased_sim_pair_dict_bd, user_info_bd)
+        if out is not None:
+            return out
+        return test_dataRDD.map(lambda line: self.user_based_prediction(
+            line, user_based_dict_bd, userbased_sim_pair_dict_bd, user_info_bd))
+
+    def _device_user_recommendation(self, test_dataRDD, rating_bd, sim_bd, user_bd):
+        try:
+            import torch
+            if not torch.cuda.is_available():
+                return None
+            from ..engine import hipabi as abi
+            from ..engine.localrdd import LocalRDD, records_of
+        except ImportError:
+            return None
+        import ctypes as C
+        recs = records_of(test_dataRDD)
+        ratings, sims, info = rating_bd.value, sim_bd.value, user_bd.value
+        items = {r[0] for lst in ratings.values() for r in lst}
+        ids = items | {pair[0] for _, pairs in recs for pair in pairs if pair}
+        if not ids or not all(isinstance(x, str) for x in ids) or len({len(x) for x in ids}) != 1:
+            return None                     # `iid in rated_iid` is a genuine substring test here
+        try:
+            users = sorted(ratings)
+            uidx = {u: k for k, u in enumerate(users)}
+            iidx = {i: k for k, i in enumerate(sorted(items))}
+            U, I = len(users), len(iidx)
+            ptr = np.zeros(U + 1, np.int64)
+            for u, lst in ratings.items():
+                ptr[uidx[u] + 1] = len(lst)
+            np.cumsum(ptr, out=ptr)
+            n = int(ptr[-1])
+            p_item, p_rating = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64)
+            for u, lst in ratings.items():
+                a = int(ptr[uidx[u]])
+                p_item[a:a + len(lst)] = [iidx[r[0]] for r in lst]
+                p_rating[a:a + len(lst)] = [float(r[1]) for r in lst]
+            listed = [uid in sims and len(sims[uid]) > 0 for uid, _ in recs]
+            n_nb = max([len(sims[uid]) for (uid, _), on in zip(recs, listed) if on] or [1])
+            if n_nb > 1024 or len(recs) * n_nb >= 2 ** 31:
+                return None
+            Q = len(recs)
+            nb_cnt, q_avg = np.zeros(max(Q, 1), np.int32), np.zeros(max(Q, 1), np.float64)
+            nb_user, nb_sim = np.full((max(Q, 1), n_nb), -1, np.int32), np.zeros((max(Q, 1), n_nb), np.float64)
+            for q, ((uid, pairs), on) in enumerate(zip(recs, listed)):
+                if not on:
+                    continue
+                lst = sims[uid]
+                nb_cnt[q] = len(lst)
+                nb_user[q, :len(lst)] = [uidx[v] for v, _ in lst]       # a neighbour without ratings: KeyError, as in the reference
+                nb_sim[q, :len(lst)] = [float(sv) for _, sv in lst]
+                if pairs:
+                    q_avg[q] = float(info[uid][0])
+        except (KeyError, TypeError, ValueError):
+            return None                     # let the Python statement raise what the reference raises
+        tq, ti, where = [], [], []
+        for q, ((uid, pairs), on) in enumerate(zip(recs, listed)):
+            if on:
+                for rp, pair in enumerate(pairs):
+                    tq.append(q)
+                    ti.append(iidx.get(pair[0], -1))
+                    where.append((q, rp))
+        T = len(tq)
+        dev = "cuda:%d" % torch.cuda.current_device()
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_tq, d_ti = to(np.asarray(tq, np.int32).reshape(-1)), to(np.asarray(ti, np.int32).reshape(-1))
+        d = [to(q_avg), to(nb_cnt), to(nb_user), to(nb_sim), to(ptr), to(p_item), to(p_rating)]
+        score = torch.zeros(max(T, 1), dtype=torch.float64, device=dev)
+        bound = torch.zeros(max(T, 1), dtype=torch.float64, device=dev)
+        n_ev = torch.zeros(max(T, 1), dtype=torch.int32, device=dev)
+        status = torch.zeros(max(T, 1), dtype=torch.int32, device=dev)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if T:
+            abi.check(abi.lib.xmap_uknn_predict_rows(st, C.c_int64(T), vp(d_tq), vp(d_ti), C.c_int64(Q), vp(d[0]), C.c_int32(n_nb), vp(d[1]),
+                                                     vp(d[2]), vp(d[3]), C.c_int64(U), C.c_int32(I), vp(d[4]), vp(d[5]), vp(d[6]), None,
+                                                     C.c_int32(0), vp(score), vp(bound), vp(n_ev), vp(status)))
+        bound, status = bound.cpu().numpy(), status.cpu().numpy()
+        out = []
+        for (uid, pairs), on in zip(recs, listed):
+            if on:
+                out.append((uid, [None] * len(pairs)))
+            else:                           # no list: [()]; an empty one: the statement (the user's mean for every pair)
+                out.append(self.user_based_prediction((uid, pairs), rating_bd, sim_bd, user_bd))
+        neighbours = {}
+        for t, (q, rp) in enumerate(where):
+            uid, pairs = recs[q]
+            if status[t] == 0:
+                out[q][1][rp] = (pairs[rp][0], pairs[rp][1], float(bound[t]))
+            else:                           # an item outside the profiles, or evidence the statement raises on
+                if q not in neighbours:
+                    neighbours[q] = [(nb[0], nb[1], ratings[nb[0]]) for nb in sims[uid]]
+                out[q][1][rp] = self._predict_user_pair(uid, pairs[rp], neighbours[q], user_bd)
+        return LocalRDD(out, getattr(test_dataRDD, "ctx", None))
 
     @staticmethod
     def _time_key(when):

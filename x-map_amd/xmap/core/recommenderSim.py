@@ -3,7 +3,9 @@
 (mirror of reference core/recommenderSim.py:9-195).  calculate_sim runs on the GPU
 (Engine.rec_sim: the stage-A pair machinery with a second walk for the leave-one-out local sensitivity); the
 profile / info helpers around it are host-side Python over RDD-like objects, as in the reference.  cosine_sim and
-adjusted_cosine_sim are kept as the readable per-pair statement of what the kernel computes (used by the CPU tests)."""
+adjusted_cosine_sim are kept as the readable per-pair statement of what the kernel computes (used by the CPU tests).
+The user method cosine_user (the reference shipped it in its prebuilt egg) runs on the GPU too: the similar-users
+machinery with the local sensitivity of every pair (Engine.peers_ls), behind session.UserSimRDD."""
 from itertools import combinations
 
 import numpy as np
@@ -89,9 +91,19 @@ class RecommenderSim:
         if "cosine_item" in self.method:
             from ..engine import session      # raises if libxmap_hip.so is missing: no CPU fallback
             return session.rec_sim_from_profiles(user_profile, self.num_atleast, getattr(user_profile, "ctx", None))
+        elif "cosine_user" in self.method:
+            # the user methods of the reference's egg; "adjust_cosine_user" lands here too, as it does there.  On the device:
+            # the peers machinery with the per-pair local sensitivity (Engine.peers_ls), behind a lazy handle
+            from ..engine import session
+            return session.user_sim_from_profiles(user_profile, self.num_atleast, getattr(user_profile, "ctx", None))
         elif "adjust_cosine_item" in self.method:
             return self.produce_pairwise(user_profile).map(lambda line: self.adjusted_cosine_sim(line, user_info))
 
     def calculate_sim_host(self, item_profile, user_profile, item_info, user_info):
         """the per-pair Python statement of calculate_sim (reference :188-195), for tests without a GPU"""
         return self.produce_pairwise(user_profile).map(lambda line: self.cosine_sim(line, item_info))
+
+    def calculate_user_sim_host(self, item_profile, user_profile, item_info, user_info):
+        """the per-pair Python statement of the cosine_user branch of calculate_sim: the pairs of users over the item profile,
+        the norms of the users; for tests without a GPU"""
+        return self.produce_pairwise(item_profile).map(lambda line: self.cosine_sim(line, user_info))

@@ -2021,6 +2021,35 @@ class Engine(object):
         del alive
         return out_cnt[:n_q], out_user[:n_q], out_sim[:n_q], out_common[:n_q], tuple(int(x) for x in h)
 
+    def peers_ls(self, index, Q, query_user, n_top, cap=1, min_common=1, same=False, keep_self=False, allow=None, exclude=None,
+                 min_sim=None, max_records=0):
+        """peers() plus the local sensitivity of every returned entry (xmap_peer_rows_ls): the largest leave-one-out distance of
+        the entry's sim over the records the two users share, the second half of the reference's ((id1, id2), [sim, LS]) record of
+        a user method.  The arguments of peers(); cnt, user, sim, common and stats are the bytes peers() returns.  Returns (cnt,
+        user, sim, common, ls [Q][n_top] (0.0 behind the count), stats)."""
+        st = _stream(self.dev)
+        n_q, n_top = int(query_user.numel()), int(n_top)
+        if not 1 <= n_top <= 1024:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 1024" % n_top)
+        if int(cap) < 1 or int(min_common) < 1:
+            raise ValueError("cap = %r, min_common = %r: both >= 1" % (cap, min_common))
+        out_cnt = self._empty(max(n_q, 1), torch.int32)
+        out_user, out_common = self._empty((max(n_q, 1), n_top), torch.int32), self._empty((max(n_q, 1), n_top), torch.int32)
+        out_sim, out_ls = self._empty((max(n_q, 1), n_top), torch.float64), self._empty((max(n_q, 1), n_top), torch.float64)
+        F = alive = None
+        if allow is not None or exclude is not None or min_sim is not None:
+            F, alive = self._rec_filter(index.n_users, n_q, allow, exclude, min_sim)
+        flags = (abi.PEERS_SAME if same else 0) | (abi.PEERS_KEEP_SELF if keep_self else 0)
+        h = (C.c_int64 * 6)()
+        with self.timed("peers_ls"):
+            check(lib.xmap_peer_rows_ls(st, i64(n_q), vp(query_user.contiguous()), i64(Q.n_users), vp(Q.user_ptr), vp(Q.user_item),
+                                        vp(Q.user_rating64), i32(flags), i32(n_top), i32(cap), i32(min_common), i64(index.n_users),
+                                        i32(index.n_items), vp(index.centre), vp(index.hd_ptr), vp(index.hd_user), vp(index.hd_x),
+                                        vp(index.nrm), i64(max_records), vp(out_cnt), vp(out_user), vp(out_sim), vp(out_common),
+                                        vp(out_ls), None if F is None else C.byref(F), h))
+        del alive
+        return out_cnt[:n_q], out_user[:n_q], out_sim[:n_q], out_common[:n_q], out_ls[:n_q], tuple(int(x) for x in h)
+
     def user_means(self, P):
         """The mean rating of every user of the profiles P over its valid rows (xmap_uknn_means): the exact sum rounded once,
         divided by the count, as the item averages are taken.  Returns (avg float64 [users] -- 0.0 without valid rows --, cnt int32

@@ -120,7 +120,7 @@ EXPORTS = [
     "xmap_topn_rows_filtered", "xmap_audience_rows_filtered", "xmap_ctx_recommend_filtered", "xmap_ctx_audience_filtered",
     "xmap_div_index", "xmap_diversify_rows", "xmap_ctx_recommend_diverse",
     "xmap_group_topn_rows", "xmap_ctx_recommend_group",
-    "xmap_peer_index", "xmap_peer_centre", "xmap_peer_rows", "xmap_ctx_peers",
+    "xmap_peer_index", "xmap_peer_centre", "xmap_peer_rows", "xmap_ctx_peers", "xmap_peer_rows_ls", "xmap_ctx_peers_ls",
     "xmap_uknn_means", "xmap_uknn_predict_rows", "xmap_uknn_topn_rows", "xmap_ctx_uknn_predict", "xmap_ctx_uknn_recommend",
 ]
 

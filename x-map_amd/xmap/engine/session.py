@@ -947,6 +947,106 @@ def similar_users_profiles(alterEgoRDD, profiles, n, cap=1, centred=True, min_co
     return res
 
 
+class UserSimRDD(LocalRDD):
+    """alterEgo_sim of a user method (cosine_user): ((uid1, uid2), [sim, local sensitivity]) for both directions of every pair
+    of users with a common item, the user itself left out.  Nothing is materialised until the rows are asked for: the handle
+    keeps the profiles and their uncentred peer index on the device, and Engine.peers_ls (xmap_peer_rows_ls) gives the lists --
+    every user a query, same, uncentred, cap = num_atleast, min_common 1.  Peers orders by sim, the reference's selection by
+    |sim|; they agree when no rating is negative, which is checked once at upload (by_abs: the host sorts the full rows)."""
+
+    max_keep = 1024             # the widest list the device selection returns
+    GROUP = 2048                # queries per Engine.peers_ls call: the outputs stay at 48 MB
+
+    def __init__(self, engine, P, X, uids, cap, by_abs, ctx=None):
+        LocalRDD.__init__(self, None, ctx)
+        self.engine, self.P, self.X, self.uids, self.cap, self.by_abs = engine, P, X, uids, int(cap), bool(by_abs)
+
+    def _lists(self, n_top):
+        """-> ([(user index, neighbour indices, sims, sensitivities)*] for every user with a neighbour, in rank order; the
+        largest candidate count of a user)"""
+        import torch
+        U, out, widest = len(self.uids), [], 0
+        for a in range(0, U, self.GROUP):
+            d_q = torch.arange(a, min(a + self.GROUP, U), dtype=torch.int32, device=self.engine.dev)
+            cnt, user, sim, _, ls, stats = self.engine.peers_ls(self.X, self.P, d_q, n_top, self.cap, 1, True, False)
+            widest = max(widest, stats[4])
+            cnt, user, sim, ls = cnt.cpu().numpy(), user.cpu().numpy(), sim.cpu().numpy(), ls.cpu().numpy()
+            out.extend((a + k, user[k, :cnt[k]], sim[k, :cnt[k]], ls[k, :cnt[k]]) for k in range(len(cnt)) if cnt[k])
+        return out, widest
+
+    def select_neighbors(self, keep):
+        """nonprivate_neighbor_selection on the device: [(uid, [(uid2, [sim, ls])*])*] for every user with a neighbour, in uid
+        order; per user the `keep` largest |sim|, user index ascending on equal sim"""
+        keep = int(keep)
+        if not 1 <= keep <= self.max_keep:
+            raise ValueError("select_neighbors(%d): the device selection takes 1 .. %d" % (keep, self.max_keep))
+        uids = self.uids
+        if self.by_abs:
+            pos = {u: k for k, u in enumerate(uids)}
+            by = {}
+            for (u1, u2), info in self._data:
+                by.setdefault(u1, []).append((u2, info))
+            res = [(u, sorted(lst, key=lambda e: (-abs(e[1][0]), pos[e[0]]))[:keep]) for u, lst in by.items()]
+        else:
+            res = [(uids[q], [(uids[v], [float(s), float(l)]) for v, s, l in zip(user, sim, ls)])
+                   for q, user, sim, ls in self._lists(keep)[0]]
+        res.sort(key=lambda e: e[0])
+        return res
+
+    def _rows(self):
+        lists, widest = self._lists(self.max_keep)
+        if widest > self.max_keep:
+            raise ValueError("a user has %d neighbours, the rows are materialised through lists of %d: take the neighbours with "
+                             "select_neighbors(keep) instead of the full rows" % (widest, self.max_keep))
+        uids = self.uids
+        rows = []
+        for q, user, sim, ls in lists:
+            o = np.argsort(user, kind="stable")         # canonical order: (uid1, uid2) by index
+            rows.extend(((uids[q], uids[v]), [float(s), float(l)]) for v, s, l in zip(user[o], sim[o], ls[o]))
+        return rows
+
+
+def user_sim_from_profiles(user_profiles, cap, ctx=None):
+    """user_profiles: [(uid, [(iid, rating, time)*])*] (the user-based AlterEgo profile) -> the UserSimRDD of the cosine_user
+    similarity.  uids and iids go in lexicographic order, so "index ascending on equal sim" is "uid ascending".  A profile that
+    holds an item twice is refused: the peer index gives such a user a bilinear norm, the reference sqrt(sum r^2)."""
+    import torch
+    from types import SimpleNamespace
+    from . import device
+    recs = sorted(records_of(user_profiles), key=lambda r: r[0])
+    uids = [u for u, _ in recs]
+    if len(set(uids)) != len(uids):
+        raise ValueError("user_sim_from_profiles: a uid appears in two profiles")
+    iids = sorted({t[0] for _, prof in recs for t in prof})
+    iidx = {s: k for k, s in enumerate(iids)}
+    ptr = np.zeros(len(recs) + 1, np.int64)
+    item, rating = [], []
+    for k, (uid, prof) in enumerate(recs):
+        held = [iidx[t[0]] for t in prof]
+        if len(set(held)) != len(held):
+            raise ValueError("user_sim_from_profiles: the profile of %r holds an item twice; cosine_user on the device takes "
+                             "profiles without repeated items (the reference pipeline removes them: avoid_duplicate_ratings)" % (uid,))
+        ptr[k + 1] = ptr[k] + len(prof)
+        item.extend(held)
+        rating.extend(float(t[1]) for t in prof)
+    dev = torch.device("cuda:%d" % torch.cuda.current_device())
+    rating = np.asarray(rating, np.float64)
+    to = lambda a: torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(dev)
+    P = SimpleNamespace(device=dev, n_users=len(uids), n_items=len(iids), user_ptr=to(ptr), user_item=to(np.asarray(item, np.int32)),
+                        user_rating64=to(rating))
+    eng = device.Engine(P)
+    return UserSimRDD(eng, P, eng.peer_index(P), uids, cap, bool((rating < 0).any()), ctx)
+
+
+def user_sim(alterEgoRDD, cap):
+    """user_sim_from_profiles over the handle's resident profiles (_peer_setup: no host round trip) -> UserSimRDD; the users
+    are indexed as the train set has them"""
+    st, eng2, P, X = _peer_setup(alterEgoRDD, False, "user_sim")
+    n = int(P.user_ptr[-1].item())
+    return UserSimRDD(eng2, P, X, st.idt.uids, cap, bool((P.user_rating64[:n] < 0).any().item()) if n else False,
+                      getattr(alterEgoRDD, "ctx", None))
+
+
 def _uknn_setup(alterEgoRDD, centred, who):
     """_peer_setup + the resident users' means (Engine.user_means), kept on the handle like the index"""
     st, eng2, P, X = _peer_setup(alterEgoRDD, centred, who)
