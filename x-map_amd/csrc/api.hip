@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.h"
+#include "rec_model.h"
 
 namespace xmap {
 
@@ -956,6 +957,10 @@ static Tables resident_tables(const xmap_ctx *c) {
 static Tables itemfold_tables(const xmap_ctx *c) {
     return Tables{(int32_t)(c->R.n_items + c->if_new), c->keep, c->x_cnt, c->x_col, c->x_sim, c->x_avg, c->R.n_items, c->if_ptr, c->if_user};
 }
+// the model of one coarse call (rec_model.h): profiles, tables and the call's decay table on the device
+static RecModel rec_model(const Profiles &P, const Tables &T, const double *d_w, int32_t n_w) {
+    return RecModel{P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim, P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w};
+}
 
 static int predict_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t n_test, const int32_t *test_user, const int32_t *test_item,
                         const double *test_rating, const double *wtab, int32_t n_w, double *out_plain, double *out_decay,
@@ -976,8 +981,7 @@ static int predict_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_t
     if (test_rating) XM_TRY(h2d(tmp, &d_real, test_rating, n, c->st));
     XM_TRY(dalloc(tmp, &d_plain, n, c->st, true)); XM_TRY(dalloc(tmp, &d_decay, n, c->st, true));
     XM_TRY(dalloc(tmp, &d_status, n, c->st, true)); XM_TRY(dalloc(tmp, &d_mae, 3, c->st, true));
-    XM_TRY(xmap_predict_rows(c->st, n_test, d_user, d_item, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim, P.ptr,
-                             P.item, P.rating, P.time, T.avg, d_w, n_w, d_plain, d_decay, d_status, max_now));
+    XM_TRY(predict_rows(c->st, n_test, d_user, d_item, rec_model(P, T, d_w, n_w), d_plain, d_decay, d_status, max_now));
     if (mae) {
         XM_TRY(xmap_mae(c->st, n_test, d_status, d_real, d_plain, d_decay, d_mae));
         XM_TRY(d2h(mae, (const double *)d_mae, 3, c->st));
@@ -1043,14 +1047,10 @@ static int recommend_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64
     XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
     XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
-    if (n_stats == 6) {
-        xmap_rec_filter D;
-        XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
-        XM_TRY(xmap_topn_rows_filtered(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
-                                       P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, &D, stats));
-    } else
-        XM_TRY(xmap_topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
-                              P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, stats));
+    xmap_rec_filter D;
+    if (n_stats == 6) XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+    XM_TRY(topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, rec_model(P, T, d_w, n_w), d_cnt, d_item, d_plain, d_decay,
+                     n_stats == 6 ? &D : nullptr, stats, n_stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
@@ -1079,19 +1079,10 @@ static int audience_over(xmap_ctx *c, const Profiles &P, const Tables &T, int64_
     XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
     XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_user, m, c->st));
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
-    if (n_stats == 6) {
-        xmap_rec_filter D;
-        XM_TRY(upload_filter(c, tmp, F, n_query, P.n_users, &D));
-        XM_TRY(xmap_audience_rows_filtered(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
-                                           P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay,
-                                           T.n_resident, T.new_ptr, T.new_user, &D, stats));
-    } else if (T.new_ptr)
-        XM_TRY(xmap_itemfold_audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
-                                           P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay, stats,
-                                           T.n_resident, T.new_ptr, T.new_user));
-    else
-        XM_TRY(xmap_audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
-                                  P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_user, d_plain, d_decay, stats));
+    xmap_rec_filter D;
+    if (n_stats == 6) XM_TRY(upload_filter(c, tmp, F, n_query, P.n_users, &D));
+    XM_TRY(audience_rows(c->st, n_query, d_item, n_top, rank_by, flags, rec_model(P, T, d_w, n_w), d_cnt, d_user, d_plain, d_decay, stats,
+                         T.n_resident, T.new_ptr, T.new_user, n_stats == 6 ? &D : nullptr, n_stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_user, (const int32_t *)d_user, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
@@ -1406,8 +1397,8 @@ int xmap_ctx_recommend_group(xmap_ctx *c, int32_t source, int64_t n_groups, cons
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
     xmap_rec_filter D;
     XM_TRY(upload_filter(c, tmp, F, n_groups, T.n_items, &D));
-    XM_TRY(xmap_group_topn_rows(c->st, n_groups, d_ptr, d_user, n_top, rank_by, flags, how, veto, P.n_users, T.n_items, T.keep, T.cnt, T.col,
-                                T.sim, P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay, d_low, &D, stats));
+    XM_TRY(group_topn_rows(c->st, n_groups, d_ptr, d_user, n_top, rank_by, flags, how, veto, rec_model(P, T, d_w, n_w), d_cnt, d_item, d_plain,
+                           d_decay, d_low, &D, stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
     XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
@@ -1462,8 +1453,7 @@ int xmap_ctx_recommend_diverse(xmap_ctx *c, int32_t source, int64_t n_query, con
     xmap_rec_filter D;
     XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
     int64_t h6[6] = {0, 0, 0, 0, 0, 0}, h2[2] = {0, 0};
-    XM_TRY(xmap_topn_rows_filtered(c->st, n_query, d_user, n_pool, rank_by, flags, P.n_users, T.n_items, T.keep, T.cnt, T.col, T.sim,
-                                   P.ptr, P.item, P.rating, P.time, T.avg, d_w, n_w, p_cnt, p_item, p_plain, p_decay, &D, h6));
+    XM_TRY(topn_rows(c->st, n_query, d_user, n_pool, rank_by, flags, rec_model(P, T, d_w, n_w), p_cnt, p_item, p_plain, p_decay, &D, h6, 6));
     XM_TRY(xmap_diversify_rows(c->st, n_query, n_pool, p_cnt, p_item, p_plain, p_decay, rank_by, weight, n_top, I, c->rs_row_ptr,
                                c->dv_col, c->dv_abs, d_cnt, d_item, d_plain, d_decay, d_pos, d_pen, d_ils, h2));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
@@ -1729,9 +1719,8 @@ static int explain_over(xmap_ctx *c, const Profiles &P, const RawProfiles &W, in
     XM_TRY(dalloc(tmp, &d_status, n, c->st)); XM_TRY(dalloc(tmp, &d_total, n, c->st)); XM_TRY(dalloc(tmp, &d_cnt, n, c->st));
     XM_TRY(dalloc(tmp, &d_score, n, c->st));
     XM_TRY(dalloc(tmp, &d_row, m, c->st)); XM_TRY(dalloc(tmp, &d_slot, m, c->st)); XM_TRY(dalloc(tmp, &d_share, m, c->st));
-    XM_TRY(xmap_explain_rows(c->st, n_pairs, d_user, d_item, rank_by, n_ev, P.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col,
-                             c->nb_sim, P.ptr, P.item, P.rating, P.time, c->rs_avg, d_w, n_w, d_status, d_total, d_cnt, d_score, d_row,
-                             d_slot, d_share, max_now));
+    XM_TRY(explain_rows(c->st, n_pairs, d_user, d_item, rank_by, n_ev, rec_model(P, resident_tables(c), d_w, n_w), d_status, d_total, d_cnt,
+                        d_score, d_row, d_slot, d_share, max_now));
     if (n_src > 0) {
         XM_TRY(dalloc(tmp, &d_stotal, m, c->st)); XM_TRY(dalloc(tmp, &d_spos, m * (size_t)n_src, c->st));
         XM_TRY(xmap_explain_sources(c->st, n_pairs, d_user, n_ev, d_cnt, d_row, P.n_users, c->R.n_items, P.ptr, P.item, W.cnt_t, W.off_t,
@@ -1883,9 +1872,8 @@ int xmap_ctx_evaluate_topn(xmap_ctx *c, int64_t n_test, const int32_t *test_user
     XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
     XM_TRY(dalloc(tmp, &d_mask, Q, c->st)); XM_TRY(dalloc(tmp, &d_agg, (size_t)n_cut * 8, c->st));
     XM_TRY(dalloc(tmp, &d_cover, (size_t)n_cut, c->st));
-    XM_TRY(xmap_topn_rows(c->st, (int64_t)Q, d_eval, n_top, rank_by, flags, c->R.n_users, c->R.n_items, c->keep, c->nb_cnt, c->nb_col,
-                          c->nb_sim, c->pf_ptr, c->pf_item, c->pf_rating, c->pf_time, c->rs_avg, d_w, n_w, d_cnt, d_item, d_plain, d_decay,
-                          stats ? stats + 4 : nullptr));
+    XM_TRY(topn_rows(c->st, (int64_t)Q, d_eval, n_top, rank_by, flags, rec_model(resident_profiles(c), resident_tables(c), d_w, n_w), d_cnt,
+                     d_item, d_plain, d_decay, nullptr, stats ? stats + 4 : nullptr, 4));
     XM_TRY(xmap_topn_eval(c->st, n_test, d_tu, d_ti, d_tr, rel_min, c->R.n_users, c->R.n_items, d_nrel, (int64_t)Q, d_eval, n_top, d_cnt,
                           d_item, n_cut, cut, d_dtab, d_mask, nullptr, d_agg, d_cover));
     XM_TRY(d2h(agg, (const double *)d_agg, (size_t)n_cut * 8, c->st));

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdlib.h>
 #include "common.h"
+#include "rec_model.h"
 
 namespace xmap {
 
@@ -328,17 +329,15 @@ static int pair_rows_run(hipStream_t st, int64_t n_test, int arena_cols, int32_t
 }
 
 template <bool RAW>
-static int predict_rows_run(hipStream_t st, int64_t n_test, const int32_t *test_user, const int32_t *test_item, int64_t n_users,
-                            int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col, const double *nb_sim,
-                            const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time,
-                            const double *item_avg, const double *wtab, int32_t n_w, double *out_plain, double *out_decay,
-                            int32_t *status, int32_t *h_max_now) {
+static int predict_rows_run(hipStream_t st, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const RecModel &M,
+                            double *out_plain, double *out_decay, int32_t *status, int32_t *h_max_now) {
     return pair_rows_run(st, n_test, 6, h_max_now, [&](bool in_arena, dim3 grid, long long w_base, long long n_work, int *max_now,
                                                        unsigned long long *ctl, long long *ovf_list, double *arena) {
         auto k = in_arena ? k_predict_rows<true, RAW> : k_predict_rows<false, RAW>;
-        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(w_base, n_work, test_user, test_item, n_users, n_items, keep, nb_cnt, nb_col, nb_sim,
-                                                (const long long *)prof_ptr, prof_item, prof_rating, (const long long *)prof_time, item_avg,
-                                                wtab, n_w, out_plain, out_decay, status, max_now, ctl, ovf_list, arena);
+        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(w_base, n_work, test_user, test_item, M.n_users, M.n_items, M.keep, M.nb_cnt, M.nb_col,
+                                                M.nb_sim, (const long long *)M.prof_ptr, M.prof_item, M.prof_rating,
+                                                (const long long *)M.prof_time, M.item_avg, M.wtab, M.n_w, out_plain, out_decay, status,
+                                                max_now, ctl, ovf_list, arena);
     });
 }
 

@@ -1,12 +1,14 @@
 // rec_filter.h -- the eligibility rules of the filtered top-N and audience calls (xmap_rec_filter; DESIGN.md 4 "Eligibility"):
-// what stage_e_topn.hip and stage_e_audience.hip share.  Both candidate passes hold the candidate set of a query as an LDS
-// bitmap of a window of the id space; the rules act on that bitmap, before anything is scored:
+// what stage_e_topn.hip, stage_e_audience.hip and stage_e_group.hip share.  The candidate passes hold the candidate set of a
+// query as an LDS bitmap of a window of the id space (IdBitmap, id_bitmap.h); the rules act on that bitmap, before anything is
+// scored:
 //   exclusions : the block strides the query's list and clears the ids that fall into the window (their words stay listed as
-//                touched, like the words of held items);
+//                touched, like the words of held items) -- IdBitmap::exclude;
 //   allow      : a touched word is ANDed with its word of the mask where it is emitted -- rf_eligible, the ONE statement of
 //                "the eligible bits of word w" that the count pass and the fill pass both call: if they ever disagreed the fill
-//                pass would write outside buffers of exactly the counted size.
-// The floor acts in the selection kernels, beside the status-2 drop.
+//                pass would write outside buffers of exactly the counted size.  Its one caller is IdBitmap::emit, of which
+//                the two passes are two instantiations.
+// The floor acts in the selection kernels, beside the status-2 drop.  This file holds rf_eligible and the argument checks.
 #ifndef XMAP_REC_FILTER_H
 #define XMAP_REC_FILTER_H
 #include "common.h"

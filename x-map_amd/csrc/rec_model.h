@@ -1,0 +1,60 @@
+// rec_model.h -- the model the recommender tail reads, as ONE value inside the library: user-major profiles, neighbour lists
+// [n_items][keep], item averages and the decay table.  The fine-grained extern "C" entries (include/xmap_hip.h) take these as
+// 13 separate arguments; each builds a RecModel from them on its first line -- the fields stand in the order of those
+// arguments -- and everything below an entry takes the struct, as do the coarse calls of api.hip, which build it once per call
+// from their profiles and tables.  Host code only: the kernels keep their parameter lists.
+#ifndef XMAP_REC_MODEL_H
+#define XMAP_REC_MODEL_H
+#include "common.h"
+
+namespace xmap {
+
+struct RecModel {
+    int64_t n_users;
+    int32_t n_items, keep;
+    const int32_t *nb_cnt, *nb_col;     // [n_items], [n_items][keep]
+    const double *nb_sim;               // [n_items][keep]
+    const int64_t *prof_ptr;            // [n_users + 1]
+    const int32_t *prof_item;
+    const double *prof_rating;
+    const int64_t *prof_time;
+    const double *item_avg;             // [n_items]
+    const double *wtab;                 // [n_w]
+    int32_t n_w;
+};
+
+// what the ranking calls (top-N, audience, group lists) ask of a model before any device work
+static inline int rec_model_check(const RecModel &M) {
+    XM_ARG(M.n_w >= 1 && M.wtab);
+    XM_ARG(M.n_users >= 0 && M.n_items >= 0 && M.keep >= 1 && M.keep <= 64 && M.prof_ptr);
+    XM_ARG(M.n_items == 0 || (M.nb_cnt && M.nb_col && M.nb_sim && M.item_avg));
+    XM_ARG(M.n_users == 0 || (M.prof_item && M.prof_rating && M.prof_time));
+    return XMAP_OK;
+}
+
+// The bodies of the fine-grained entries, which the coarse calls of api.hip share.  Pointers are device pointers; the
+// arguments, outputs, h_stats and sync points are those of the entry of the same name in include/xmap_hip.h.
+// stage_e_rows.hip: xmap_predict_rows
+int predict_rows(void *stream, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const RecModel &M, double *out_plain,
+                 double *out_decay, int32_t *status, int32_t *h_max_now);
+// stage_e_topn.hip: xmap_topn_rows (F == NULL, n_stats = 4) and xmap_topn_rows_filtered (n_stats = 6)
+int topn_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags, const RecModel &M,
+              int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, const xmap_rec_filter *F, int64_t *h_stats,
+              int n_stats);
+// stage_e_audience.hip: xmap_audience_rows (new_ptr == NULL, n_resident = n_items), xmap_itemfold_audience_rows and
+// xmap_audience_rows_filtered (n_stats = 6): the items >= n_resident take their holders from the CSR (new_ptr, new_user) -- the
+// raters of a fold-in batch, which no profile holds
+int audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags, const RecModel &M,
+                  int32_t *out_cnt, int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats, int32_t n_resident,
+                  const int64_t *new_ptr, const int32_t *new_user, const xmap_rec_filter *F, int n_stats);
+// stage_e_group.hip: xmap_group_topn_rows
+int group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr, const int32_t *grp_user, int32_t n_top, int32_t rank_by,
+                    int32_t flags, int32_t how, double veto, const RecModel &M, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                    double *out_decay, int32_t *out_low, const xmap_rec_filter *F, int64_t *h_stats);
+// stage_e_explain.hip: xmap_explain_rows
+int explain_rows(void *stream, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by, int32_t n_ev,
+                 const RecModel &M, int32_t *ex_status, int32_t *ex_total, int32_t *ex_cnt, double *ex_score, int64_t *ex_row,
+                 int32_t *ex_slot, double *ex_share, int32_t *h_max_now);
+
+}  // namespace xmap
+#endif

@@ -1,7 +1,8 @@
-// sorted_runs.h -- the back half of "sort, don't hash" that the peers (stage_e_peers.hip) and the user-kNN top-N (stage_e_uknn.hip)
-// share: over the records of a chunk of queries, stably sorted on (q - q0) << id_bits | id, the run heads, the run starts, the
-// first run of every query, and the segmented selection (au_select.h) over the runs of a query with its outputs
-// (count, id, score, size of the run).  What a run is worth -- its status and score -- is the caller's own reduce kernel.
+// sorted_runs.h -- the back half of "sort, don't hash" that the peers (stage_e_peers.hip), the user-kNN top-N (stage_e_uknn.hip) and
+// the item fold-in (stage_e_itemfold.hip) share: over the records of a chunk of queries, stably sorted on
+// (q - q0) << id_bits | id, the run heads, the run starts, the first run of every query, and -- for the first two -- the segmented
+// selection (au_select.h) over the runs of a query with its outputs (count, id, score, size of the run).  What a run is worth --
+// its status and score -- is the caller's own reduce kernel.
 #ifndef XMAP_SORTED_RUNS_H
 #define XMAP_SORTED_RUNS_H
 #include "common.h"
@@ -32,17 +33,23 @@ static __global__ __launch_bounds__(256) void k_pr_starts(long long n, const int
     if (t == 0) run_start[run_idx[n]] = (int)n;
 }
 
-// first[x] = index of the first run of local query x, x <= nq: run_idx at the first sorted position whose query is >= x
+// index of the first run of local query x: run_idx at the first sorted position in [0, n] whose query is >= x (run_idx[n] = all runs)
+__device__ __forceinline__ long long pr_first_run(long long n, const unsigned long long *keys, int id_bits, const long long *run_idx,
+                                                  unsigned long long x) {
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if ((keys[mid] >> id_bits) >= x) hi = mid; else lo = mid + 1;
+    }
+    return run_idx[lo];
+}
+
+// first[x] = index of the first run of local query x, x <= nq
 static __global__ __launch_bounds__(256) void k_pr_first(long long nq, long long n, const unsigned long long *keys, int id_bits,
                                                          const long long *run_idx, long long *first) {
     const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (x > nq) return;
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((keys[mid] >> id_bits) >= (unsigned long long)x) hi = mid; else lo = mid + 1;
-    }
-    first[x] = run_idx[lo];
+    first[x] = pr_first_run(n, keys, id_bits, run_idx, (unsigned long long)x);
 }
 
 // one block per query of the chunk: its runs are the segment [first[x], first[x + 1]), in ascending id

@@ -13,8 +13,8 @@
 //                     the item's first min(cnt, keep) neighbours n -- at most 64 rows, each as long as the neighbour is popular,
 //                     so the whole block strides one row after the other, coalesced -- the holders of the item itself are
 //                     cleared again unless XMAP_AUDIENCE_KEEP_HOLDERS, and the marked users leave in ascending index.  The
-//                     second-level bitmap of stage_e_topn.hip (one bit per bitmap word that was touched) is all the emit pass
-//                     scans, and it zeroes exactly the words it visits: the window is cleared once per block, never per query.
+//                     bitmap, its summary level, the exclusion clear and the two-pass emit are IdBitmap (id_bitmap.h), shared
+//                     with the top-N and the group lists, here with 1024 threads over 2^20 ids: one summary word per thread.
 //   scoring         : k_predict_rows<., RAW = true> (predict_rows.h) over the (user, item) candidate list, unchanged.
 //   k_au_select     : segmented top-N, one block per query, for segments of up to a million candidates and N up to 1024:
 //                     au_select_segment of au_select.h (shared with stage_e_peers.hip) -- the best CAP >= n_top keys sorted in
@@ -30,17 +30,18 @@
 // Every output position follows from the scans, so the result does not depend on the grid or on the order of the atomics.
 #include "common.h"
 #include "au_select.h"
+#include "id_bitmap.h"
 #include "predict_rows.h"
 #include "rec_filter.h"
+#include "two_pass.h"
 
 namespace xmap {
 
 constexpr int AU_WINDOW = 1 << 20;              // users per bitmap pass (128 KB of LDS + 4 KB of summary: one block per CU)
 static_assert(AU_WINDOW % 32 == 0, "a window starts at a word of the mask");
-constexpr int AU_WORDS = AU_WINDOW / 32;
-constexpr int AU_SUMMARY = AU_WORDS / 32;       // second level: bit w of word s = bitmap word 32 s + w was touched
 constexpr int AU_THREADS = 1024;                // 16 waves stride a holder row; thread t emits summary word t (thread order = user order)
-static_assert(AU_SUMMARY == AU_THREADS, "one summary word per thread");
+using AuBitmap = IdBitmap<AU_THREADS, 20>;
+static_assert(AuBitmap::WINDOW == AU_WINDOW && AuBitmap::PER == 1, "one summary word per thread");
 constexpr int AU_MAX_BLOCKS = 512;              // blocks of the candidate pass (grid-stride over the queries: the window is zeroed once per block)
 constexpr int AU_ROW_BLOCKS = 2048;             // blocks of the holders pass (grid-stride over the profile rows)
 
@@ -61,29 +62,9 @@ __global__ __launch_bounds__(256) void k_au_holders(long long U, int I, const lo
     }
 }
 
-__device__ __forceinline__ int au_block_scan(int v, int *total, int *smem) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) smem[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < AU_THREADS / 64; k++) {
-        const int s = smem[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // FILT (rec_filter.h): the query's exclusion ids are cleared behind the holders, and a touched word meets its word of the mask
-// where it is emitted; the count pass adds what the two removed to *removed.  FILT = false is the unfiltered kernel.
+// where it is emitted; the count pass adds what the two removed to *removed.  FILT = false is the unfiltered kernel: it reads
+// none of allow, ex_ptr, ex_id.
 template <bool FILL, bool FILT>
 __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query, const int *query_item, long long U, int I, int keep,
                                                               int keep_holders, const int *nb_cnt, const int *nb_col,
@@ -92,13 +73,9 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
                                                               const long long *cand_ptr, int *cand_user, int *cand_item,
                                                               const unsigned int *allow, const long long *ex_ptr, const int *ex_id,
                                                               unsigned long long *removed) {
-    extern __shared__ unsigned int au_lds[];    // [AU_WORDS] bitmap of the window, [AU_SUMMARY] touched words (zero between queries),
-    unsigned int *bits = au_lds, *summ = au_lds + AU_WORDS;                                      // [AU_THREADS / 64] scan scratch
-    int *s_scan = (int *)(au_lds + AU_WORDS + AU_SUMMARY);
+    extern __shared__ unsigned int au_lds[];
+    AuBitmap bm(au_lds);
     const int tid = threadIdx.x;
-    for (int k = tid; k < AU_WORDS + AU_SUMMARY; k += AU_THREADS) au_lds[k] = 0u;
-    __syncthreads();
-    [[maybe_unused]] unsigned int gone = 0;     // FILT, count pass: candidates of this thread's words and ids that the rules removed
     for (long long q = blockIdx.x; q < n_query; q += gridDim.x) {
         const int it = query_item[q];
         int cnt = (it >= 0 && it < I) ? nb_cnt[it] : 0;
@@ -111,79 +88,27 @@ __global__ __launch_bounds__(AU_THREADS) void k_au_candidates(long long n_query,
                 const int nb = nb_col[(size_t)it * keep + l];
                 if (nb < 0 || nb >= I) continue;        // ignored, as in the prediction
                 const long long r1 = hptr[nb + 1];      // (an item of a fold-in batch: no profile holds it, the row is empty)
-                for (long long r = hptr[nb] + tid; r < r1; r += AU_THREADS) {
-                    const long long x = (long long)huser[r] - lo;
-                    if (x < 0 || x >= AU_WINDOW) continue;
-                    const int w = (int)(x >> 5);
-                    const unsigned int old = atomicOr(&bits[w], 1u << (x & 31));
-                    if (old == 0u) atomicOr(&summ[w >> 5], 1u << (w & 31));
-                }
+                for (long long r = hptr[nb] + tid; r < r1; r += AU_THREADS) bm.mark((long long)huser[r] - lo);
             }
             __syncthreads();
-            if (!keep_holders) {                // a user who holds the item is no candidate (the word stays listed as touched)
+            if (!keep_holders) {                // a user who holds the item is no candidate
                 const bool nw = new_ptr && it >= n_resident;         // a batch item: its holders are its raters
                 const int *hu = nw ? new_user : huser;
                 const long long r1 = nw ? new_ptr[it - n_resident + 1] : hptr[it + 1];
-                for (long long r = (nw ? new_ptr[it - n_resident] : hptr[it]) + tid; r < r1; r += AU_THREADS) {
-                    const long long x = (long long)hu[r] - lo;
-                    if (x >= 0 && x < AU_WINDOW) atomicAnd(&bits[x >> 5], ~(1u << (x & 31)));
-                }
+                for (long long r = (nw ? new_ptr[it - n_resident] : hptr[it]) + tid; r < r1; r += AU_THREADS) bm.unmark((long long)hu[r] - lo);
                 __syncthreads();
             }
-            if constexpr (FILT) {               // the query's exclusions: a bit that was still set is a candidate removed, once
-                if (ex_ptr) {
-                    const long long e1 = ex_ptr[q + 1];
-                    for (long long e = ex_ptr[q] + tid; e < e1; e += AU_THREADS) {
-                        const long long id = ex_id[e], x = id - lo;
-                        if (id < 0 || id >= U || x < 0 || x >= AU_WINDOW) continue;
-                        const unsigned int bit = 1u << (x & 31);
-                        const unsigned int old = atomicAnd(&bits[x >> 5], ~bit);
-                        if constexpr (!FILL) gone += (old & bit) ? 1u : 0u;
-                    }
-                    __syncthreads();
-                }
-            }
-            // emit in ascending index: count per thread, scan over the block, write; the visited words are zeroed on the way
-            int c = 0;
-            unsigned int sw = summ[tid];
-            while (sw) {
-                const int w = tid * 32 + __ffs(sw) - 1;
-                sw &= sw - 1;
-                const unsigned int raw = bits[w], bw = rf_eligible<FILT>(raw, allow, (lo >> 5) + w);
-                c += __popc(bw);
-                if constexpr (FILT && !FILL) gone += __popc(raw) - __popc(bw);
-            }
-            int tot;
-            const int ex = au_block_scan(c, &tot, s_scan);
-            long long o = out0 + total + ex;
-            sw = summ[tid];
-            summ[tid] = 0u;
-            while (sw) {
-                const int w = tid * 32 + __ffs(sw) - 1;
-                sw &= sw - 1;
-                unsigned int bw = bits[w];
-                bits[w] = 0u;
-                if constexpr (FILL) {
-                    bw = rf_eligible<FILT>(bw, allow, (lo >> 5) + w);
-                    while (bw) {
-                        const int bit = __ffs(bw) - 1;
-                        bw &= bw - 1;
-                        cand_user[o] = (int)(lo + (long long)w * 32 + bit);
-                        cand_item[o] = it;
-                        o++;
-                    }
-                }
-            }
-            total += tot;
-            __syncthreads();
+            if constexpr (FILT) bm.template exclude<!FILL>(ex_ptr, ex_id, q, U, lo);
+            total += bm.template emit<FILL, FILT, FILT>(lo, allow, out0 + total, [&](long long o, long long user) {
+                cand_user[o] = (int)user;
+                cand_item[o] = it;
+            });
         }
         if constexpr (!FILL) {
             if (tid == 0) cand_cnt[q] = (int)total;
         }
     }
-    if constexpr (FILT && !FILL) {
-        if (gone) atomicAdd(removed, (unsigned long long)gone);
-    }
+    if constexpr (FILT && !FILL) bm.add_gone(removed);
 }
 
 // the selection itself is au_select_segment (au_select.h, shared with stage_e_peers.hip); this kernel writes the audience's outputs
@@ -241,111 +166,81 @@ static void au_select_launch(hipStream_t st, long long n_query, int n_top, int r
         n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay, status, out_cnt, out_user, out_plain, out_decay, stats, min_score);
 }
 
-// the two passes of the candidate kernel, by the rules a call carries: one statement per launch
-template <bool FILL, bool FILT, class... A>
-static void au_candidates_launch(hipStream_t st, unsigned blocks, size_t lds, A... a) {
-    k_au_candidates<FILL, FILT><<<dim3(blocks), dim3(AU_THREADS), lds, st>>>(a...);
-}
-template <bool FILL, class... A>
-static hipError_t au_candidates(bool filt, hipStream_t st, unsigned blocks, size_t lds, A... a) {
-    const void *f = filt ? (const void *)k_au_candidates<FILL, true> : (const void *)k_au_candidates<FILL, false>;
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (filt) au_candidates_launch<FILL, true>(st, blocks, lds, a...);
-    else au_candidates_launch<FILL, false>(st, blocks, lds, a...);
-    return hipGetLastError();
-}
-
-}  // namespace xmap
-using namespace xmap;
-
-// xmap_audience_rows (new_ptr == NULL), xmap_itemfold_audience_rows and xmap_audience_rows_filtered (n_stats = 6): the items >=
-// n_resident take their holders from the CSR (new_ptr, new_user) -- the raters of a fold-in batch, which no profile holds
-static int audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
-                       int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col,
-                       const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
-                       const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
-                       int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats, int32_t n_resident,
-                       const int64_t *new_ptr, const int32_t *new_user, const xmap_rec_filter *F = nullptr, int n_stats = 4) {
+// rec_model.h: xmap_audience_rows (new_ptr == NULL), xmap_itemfold_audience_rows and xmap_audience_rows_filtered (n_stats = 6): the
+// items >= n_resident take their holders from the CSR (new_ptr, new_user) -- the raters of a fold-in batch, which no profile holds
+int audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags, const RecModel &M,
+                  int32_t *out_cnt, int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats, int32_t n_resident,
+                  const int64_t *new_ptr, const int32_t *new_user, const xmap_rec_filter *F, int n_stats) {
     XM_SCOPE(stream);
     hipStream_t st = (hipStream_t)stream;
     XM_ARG(n_top >= 1 && n_top <= AU_MAX_TOP);
     XM_ARG(rank_by == 0 || rank_by == 1);
     XM_ARG((flags & ~XMAP_AUDIENCE_KEEP_HOLDERS) == 0);
-    XM_ARG(n_w >= 1 && wtab);
-    XM_ARG(n_query >= 0 && n_query <= 2147483647ll && n_users >= 0 && n_users <= 2147483647ll && n_items >= 0 && keep >= 1 && keep <= 64 &&
-           prof_ptr);
+    int rc = rec_model_check(M);
+    if (rc) return rc;
+    XM_ARG(n_query >= 0 && n_query <= 2147483647ll && M.n_users <= 2147483647ll);
     XM_ARG(n_query == 0 || (query_item && out_cnt && out_user && out_plain && out_decay));
-    XM_ARG(n_items == 0 || (nb_cnt && nb_col && nb_sim && item_avg));
-    XM_ARG(n_users == 0 || (prof_item && prof_rating && prof_time));
     if (h_stats) for (int k = 0; k < n_stats; k++) h_stats[k] = 0;
     bool filt = false;
     double min_score = 0.0;
-    int rc = rf_prepare(st, n_query, F, &filt, &min_score);     // before any candidate work
+    rc = rf_prepare(st, n_query, F, &filt, &min_score);         // before any candidate work
     if (rc) return rc;
     if (n_query == 0) return XMAP_OK;
-    const int I = n_items;
-    const size_t i1 = (size_t)(I ? I : 1);
+    const int I = M.n_items;
+    const long long *pptr = (const long long *)M.prof_ptr;
     // ---- holders: the profiles by item
-    int *hcnt = nullptr, *huser = nullptr;
+    int *huser = nullptr;
     long long *hptr = nullptr;
     int64_t n_hold = 0;
-    XM_HIP(xm_malloc_async((void **)&hcnt, sizeof(int) * i1, st));
-    XM_HIP(xm_malloc_async((void **)&hptr, sizeof(long long) * (i1 + 1), st));
-    XM_HIP(hipMemsetAsync(hcnt, 0, sizeof(int) * i1, st));
-    if (I > 0 && n_users > 0) {
-        k_au_holders<false><<<dim3(AU_ROW_BLOCKS), dim3(256), 0, st>>>(n_users, I, (const long long *)prof_ptr, prof_item, hcnt, nullptr,
-                                                                       nullptr);
-        XM_LAUNCH_CHECK();
-    }
-    rc = xmap_exclusive_scan_i32_to_i64(st, hcnt, (int64_t *)hptr, I, &n_hold);
+    rc = count_scan_fill<true>(
+        st, I, &hptr, &n_hold,
+        [&](bool fill, int *hcnt, const long long *ptr) {
+            if (I > 0 && M.n_users > 0)
+                (fill ? k_au_holders<true> : k_au_holders<false>)<<<dim3(AU_ROW_BLOCKS), dim3(256), 0, st>>>(M.n_users, I, pptr, M.prof_item, hcnt,
+                                                                                                           ptr, huser);
+            return hipGetLastError();
+        },
+        [&](int64_t n) -> int {
+            XM_HIP(xm_malloc_async((void **)&huser, sizeof(int) * (size_t)(n ? n : 1), st));
+            return XMAP_OK;
+        });
     if (rc) return rc;
-    XM_HIP(xm_malloc_async((void **)&huser, sizeof(int) * (size_t)(n_hold ? n_hold : 1), st));
-    if (n_hold > 0) {
-        XM_HIP(hipMemsetAsync(hcnt, 0, sizeof(int) * i1, st));
-        k_au_holders<true><<<dim3(AU_ROW_BLOCKS), dim3(256), 0, st>>>(n_users, I, (const long long *)prof_ptr, prof_item, hcnt, hptr, huser);
-        XM_LAUNCH_CHECK();
-    }
-    // ---- candidates: count, scan, fill
-    int *cand_cnt = nullptr, *cand_user = nullptr, *cand_item = nullptr;
-    long long *cand_ptr = nullptr;
-    int64_t n_pairs = 0;
-    XM_HIP(xm_malloc_async((void **)&cand_cnt, sizeof(int) * (size_t)n_query, st));
-    XM_HIP(xm_malloc_async((void **)&cand_ptr, sizeof(long long) * ((size_t)n_query + 1), st));
-    const size_t lds = sizeof(unsigned int) * (AU_WORDS + AU_SUMMARY + AU_THREADS / 64);
-    const unsigned cblocks = (unsigned)(n_query < AU_MAX_BLOCKS ? n_query : AU_MAX_BLOCKS);
-    const int keep_holders = flags & XMAP_AUDIENCE_KEEP_HOLDERS;
     // [0] dropped candidates, [1] largest segment, [2] below the floor, [3] removed by the mask or the exclusion lists
     unsigned long long *stats = nullptr;
     XM_HIP(xm_malloc_async((void **)&stats, sizeof(unsigned long long) * 4, st));
     XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 4, st));
+    // ---- candidates: count, scan, fill
+    int *cand_user = nullptr, *cand_item = nullptr, *status = nullptr;
+    long long *cand_ptr = nullptr;
+    double *plain = nullptr, *decay = nullptr;
+    int64_t n_pairs = 0;
+    const unsigned cblocks = (unsigned)(n_query < AU_MAX_BLOCKS ? n_query : AU_MAX_BLOCKS);
     const unsigned int *allow = filt ? (const unsigned int *)F->allow : nullptr;
     const long long *ex_ptr = filt ? (const long long *)F->ex_ptr : nullptr;
     const int *ex_id = filt ? F->ex_id : nullptr;
-    XM_HIP(au_candidates<false>(filt, st, cblocks, lds, (long long)n_query, query_item, (long long)n_users, I, keep, keep_holders, nb_cnt, nb_col,
-                                (const long long *)hptr, (const int *)huser, n_resident, (const long long *)new_ptr, new_user, cand_cnt,
-                                (const long long *)nullptr, (int *)nullptr, (int *)nullptr, allow, ex_ptr, ex_id, stats + 3));
-    rc = xmap_exclusive_scan_i32_to_i64(st, cand_cnt, (int64_t *)cand_ptr, n_query, &n_pairs);
+    rc = count_scan_fill<false>(
+        st, n_query, &cand_ptr, &n_pairs,
+        [&](bool fill, int *cand_cnt, const long long *ptr) {
+            const auto k = fill ? (filt ? k_au_candidates<true, true> : k_au_candidates<true, false>)
+                                : (filt ? k_au_candidates<false, true> : k_au_candidates<false, false>);
+            return launch_dyn_lds(k, cblocks, AU_THREADS, AuBitmap::LDS_BYTES, st, n_query, query_item, M.n_users, I, M.keep,
+                                  flags & XMAP_AUDIENCE_KEEP_HOLDERS, M.nb_cnt, M.nb_col, hptr, huser, n_resident, (const long long *)new_ptr,
+                                  new_user, cand_cnt, ptr, cand_user, cand_item, allow, ex_ptr, ex_id, stats + 3);
+        },
+        [&](int64_t n) -> int {
+            if (n == 0) return XMAP_OK;
+            const size_t np = (size_t)n;
+            XM_HIP(xm_malloc_async((void **)&cand_user, sizeof(int) * np, st));
+            XM_HIP(xm_malloc_async((void **)&cand_item, sizeof(int) * np, st));
+            XM_HIP(xm_malloc_async((void **)&plain, sizeof(double) * np, st));
+            XM_HIP(xm_malloc_async((void **)&decay, sizeof(double) * np, st));
+            XM_HIP(xm_malloc_async((void **)&status, sizeof(int) * np, st));
+            return XMAP_OK;
+        });
     if (rc) return rc;
-    double *plain = nullptr, *decay = nullptr;
-    int *status = nullptr;
+    // ---- scores: the pair body of the prediction, unrounded
     int32_t max_now = 0;
-    if (n_pairs > 0) {
-        const size_t np = (size_t)n_pairs;
-        XM_HIP(xm_malloc_async((void **)&cand_user, sizeof(int) * np, st));
-        XM_HIP(xm_malloc_async((void **)&cand_item, sizeof(int) * np, st));
-        XM_HIP(xm_malloc_async((void **)&plain, sizeof(double) * np, st));
-        XM_HIP(xm_malloc_async((void **)&decay, sizeof(double) * np, st));
-        XM_HIP(xm_malloc_async((void **)&status, sizeof(int) * np, st));
-        XM_HIP(au_candidates<true>(filt, st, cblocks, lds, (long long)n_query, query_item, (long long)n_users, I, keep, keep_holders, nb_cnt,
-                                   nb_col, (const long long *)hptr, (const int *)huser, n_resident, (const long long *)new_ptr, new_user,
-                                   (int *)nullptr, (const long long *)cand_ptr, cand_user, cand_item, allow, ex_ptr, ex_id,
-                                   (unsigned long long *)nullptr));
-        // ---- scores: the pair body of the prediction, unrounded
-        rc = predict_rows_run<true>(st, n_pairs, cand_user, cand_item, n_users, I, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item,
-                                    prof_rating, prof_time, item_avg, wtab, n_w, plain, decay, status, &max_now);
-        if (rc) return rc;
-    }
+    if (n_pairs > 0 && (rc = predict_rows_run<true>(st, n_pairs, cand_user, cand_item, M, plain, decay, status, &max_now))) return rc;
     // ---- selection (n_pairs == 0: every segment is empty, the counts and the padding are still written)
     if (n_top <= 256)
         au_select_launch<256>(st, n_query, n_top, rank_by, cand_ptr, cand_user, plain, decay, status, out_cnt, out_user, out_plain, out_decay,
@@ -364,6 +259,9 @@ static int audience_rows(void *stream, int64_t n_query, const int32_t *query_ite
     return XMAP_OK;
 }
 
+}  // namespace xmap
+using namespace xmap;
+
 extern "C" {
 
 int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
@@ -371,9 +269,9 @@ int xmap_audience_rows(void *stream, int64_t n_query, const int32_t *query_item,
                        const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating,
                        const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
                        int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats) {
-    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
-                         prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_user, out_plain, out_decay, h_stats, n_items,
-                         nullptr, nullptr);
+    const RecModel M{n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating, prof_time, item_avg, wtab, n_w};
+    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, M, out_cnt, out_user, out_plain, out_decay, h_stats, n_items,
+                         nullptr, nullptr, nullptr, 4);
 }
 
 int xmap_itemfold_audience_rows(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
@@ -382,10 +280,10 @@ int xmap_itemfold_audience_rows(void *stream, int64_t n_query, const int32_t *qu
                                 const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
                                 int32_t *out_user, double *out_plain, double *out_decay, int64_t *h_stats, int32_t n_resident,
                                 const int64_t *new_ptr, const int32_t *new_user) {
+    const RecModel M{n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating, prof_time, item_avg, wtab, n_w};
     XM_ARG(n_resident >= 0 && n_resident <= n_items && (n_resident == n_items || new_ptr));
-    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
-                         prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_user, out_plain, out_decay, h_stats, n_resident,
-                         new_ptr, new_user);
+    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, M, out_cnt, out_user, out_plain, out_decay, h_stats, n_resident,
+                         new_ptr, new_user, nullptr, 4);
 }
 
 int xmap_audience_rows_filtered(void *stream, int64_t n_query, const int32_t *query_item, int32_t n_top, int32_t rank_by, int32_t flags,
@@ -394,10 +292,10 @@ int xmap_audience_rows_filtered(void *stream, int64_t n_query, const int32_t *qu
                                 const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *out_cnt,
                                 int32_t *out_user, double *out_plain, double *out_decay, int32_t n_resident, const int64_t *new_ptr,
                                 const int32_t *new_user, const xmap_rec_filter *F, int64_t *h_stats) {
+    const RecModel M{n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating, prof_time, item_avg, wtab, n_w};
     if (!new_ptr) n_resident = n_items;         // resident items only
     XM_ARG(n_resident >= 0 && n_resident <= n_items);
-    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
-                         prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_cnt, out_user, out_plain, out_decay, h_stats, n_resident,
+    return audience_rows(stream, n_query, query_item, n_top, rank_by, flags, M, out_cnt, out_user, out_plain, out_decay, h_stats, n_resident,
                          new_ptr, new_user, F, 6);
 }
 }

@@ -76,6 +76,30 @@ __global__ __launch_bounds__(64 * XS_WAVES) void k_explain_sources(
     if (lane >= written && lane < n_src) pos[lane] = -1;
 }
 
+// rec_model.h: the body of xmap_explain_rows.  The tables are asked for only when there is a pair to explain.
+int explain_rows(void *stream, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by, int32_t n_ev,
+                 const RecModel &M, int32_t *ex_status, int32_t *ex_total, int32_t *ex_cnt, double *ex_score, int64_t *ex_row,
+                 int32_t *ex_slot, double *ex_share, int32_t *h_max_now) {
+    XM_ARG(n_ev >= 1 && n_ev <= EX_MAX_EV);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG(n_pairs >= 0 && M.n_users >= 0 && M.n_items >= 0 && M.keep >= 1 && M.keep <= 64 && M.n_w >= 1 && M.wtab && M.prof_ptr);
+    XM_ARG(n_pairs == 0 || (pair_user && pair_item && M.nb_cnt && M.nb_col && M.nb_sim && M.item_avg));
+    XM_ARG(n_pairs == 0 || (ex_status && ex_total && ex_cnt && ex_score && ex_row && ex_slot && ex_share));
+    XM_ARG(M.n_users == 0 || (M.prof_item && M.prof_rating && M.prof_time));
+    hipStream_t st = (hipStream_t)stream;
+    ExplainOut X;
+    X.rank_by = rank_by; X.n_ev = n_ev; X.total = ex_total; X.cnt = ex_cnt; X.score = ex_score; X.row = (long long *)ex_row;
+    X.slot = ex_slot; X.share = ex_share;
+    return pair_rows_run(st, n_pairs, 8, h_max_now, [&](bool in_arena, dim3 grid, long long w_base, long long n_work, int *max_now,
+                                                        unsigned long long *ctl, long long *ovf_list, double *arena) {
+        auto k = in_arena ? k_explain_rows<true> : k_explain_rows<false>;
+        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(w_base, n_work, pair_user, pair_item, M.n_users, M.n_items, M.keep, M.nb_cnt, M.nb_col,
+                                                M.nb_sim, (const long long *)M.prof_ptr, M.prof_item, M.prof_rating,
+                                                (const long long *)M.prof_time, M.item_avg, M.wtab, M.n_w, ex_status, max_now, ctl,
+                                                ovf_list, arena, X);
+    });
+}
+
 }  // namespace xmap
 using namespace xmap;
 
@@ -87,23 +111,9 @@ int xmap_explain_rows(void *stream, int64_t n_pairs, const int32_t *pair_user, c
                       const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w, int32_t *ex_status,
                       int32_t *ex_total, int32_t *ex_cnt, double *ex_score, int64_t *ex_row, int32_t *ex_slot, double *ex_share,
                       int32_t *h_max_now) {
-    XM_ARG(n_ev >= 1 && n_ev <= EX_MAX_EV);
-    XM_ARG(rank_by == 0 || rank_by == 1);
-    XM_ARG(n_pairs >= 0 && n_users >= 0 && n_items >= 0 && keep >= 1 && keep <= 64 && n_w >= 1 && wtab && prof_ptr);
-    XM_ARG(n_pairs == 0 || (pair_user && pair_item && nb_cnt && nb_col && nb_sim && item_avg));
-    XM_ARG(n_pairs == 0 || (ex_status && ex_total && ex_cnt && ex_score && ex_row && ex_slot && ex_share));
-    XM_ARG(n_users == 0 || (prof_item && prof_rating && prof_time));
-    hipStream_t st = (hipStream_t)stream;
-    ExplainOut X;
-    X.rank_by = rank_by; X.n_ev = n_ev; X.total = ex_total; X.cnt = ex_cnt; X.score = ex_score; X.row = (long long *)ex_row;
-    X.slot = ex_slot; X.share = ex_share;
-    return pair_rows_run(st, n_pairs, 8, h_max_now, [&](bool in_arena, dim3 grid, long long w_base, long long n_work, int *max_now,
-                                                        unsigned long long *ctl, long long *ovf_list, double *arena) {
-        auto k = in_arena ? k_explain_rows<true> : k_explain_rows<false>;
-        k<<<grid, dim3(64 * PR_WAVES), 0, st>>>(w_base, n_work, pair_user, pair_item, n_users, n_items, keep, nb_cnt, nb_col, nb_sim,
-                                                (const long long *)prof_ptr, prof_item, prof_rating, (const long long *)prof_time, item_avg,
-                                                wtab, n_w, ex_status, max_now, ctl, ovf_list, arena, X);
-    });
+    const RecModel M{n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating, prof_time, item_avg, wtab, n_w};
+    return explain_rows(stream, n_pairs, pair_user, pair_item, rank_by, n_ev, M, ex_status, ex_total, ex_cnt, ex_score, ex_row, ex_slot,
+                        ex_share, h_max_now);
 }
 
 int xmap_explain_sources(void *stream, int64_t n_pairs, const int32_t *pair_user, int32_t n_ev, const int32_t *ex_cnt,

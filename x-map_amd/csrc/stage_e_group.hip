@@ -12,11 +12,10 @@
 //                     item a member holds leaves the group's candidates without XMAP_TOPN_KEEP_HELD whoever else has evidence
 //                     for it, so that member's pair is never needed -- and a group of one scores exactly what xmap_topn_rows scores.
 //   k_gr_candidates : one block per group (grid-stride), run twice (count, then fill into a buffer of exactly the counted size).
-//                     The windowed LDS bitmap and its summary level as in k_tn_candidates, zeroing exactly the words it visits:
-//                     the union of the members' segments is marked, every member's held items are cleared unless KEEP_HELD, the
-//                     group's exclusion ids are cleared (a bit that was still set is counted, once), and the marked items leave
-//                     in ascending index through rf_eligible -- the one statement of "the eligible bits of a word" for both
-//                     passes (rec_filter.h).
+//                     The windowed LDS bitmap of k_tn_candidates (IdBitmap, id_bitmap.h; the geometry of topn_pass.h): the union
+//                     of the members' segments is marked, every member's held items are cleared unless KEEP_HELD, the group's
+//                     exclusion ids are cleared (a bit that was still set is counted, once), and the marked items leave in
+//                     ascending index through the shared emit, which applies the mask without counting what it removes.
 //   k_gr_select     : one wave per group, four per block.  The group's candidates stream through 64 at a time; a lane owns one
 //                     candidate and walks the members in list order: the item is found in the member's segment by bisection
 //                     (one entry or none: a segment holds an item once) and gives that entry's scores and status, or the item
@@ -26,6 +25,7 @@
 #include "common.h"
 #include "rec_filter.h"
 #include "topn_pass.h"
+#include "two_pass.h"
 
 namespace xmap {
 
@@ -45,20 +45,18 @@ static __global__ __launch_bounds__(256) void k_gr_check(long long n_groups, con
     }
 }
 
-// mem_ptr / mem_item: the members' candidate segments (member pass), indexed by the position in grp_user
+// mem_ptr / mem_item: the members' candidate segments (member pass), indexed by the position in grp_user.  The mask is always
+// applied (allow may be NULL), ex_ptr is tested at run time, and *excluded counts the bits the exclusion lists cleared -- not
+// what the mask removed, which the member pass has counted.
 template <bool FILL>
 __global__ __launch_bounds__(TN_THREADS) void k_gr_candidates(long long n_groups, const long long *grp_ptr, const int *grp_user, long long U, int I,
                                                               int keep_held, const long long *mem_ptr, const int *mem_item,
                                                               const long long *pptr, const int *pitem, int *gc_cnt, const long long *gc_ptr,
                                                               int *gc_item, const unsigned int *allow, const long long *ex_ptr,
                                                               const int *ex_id, unsigned long long *excluded) {
-    extern __shared__ unsigned int gr_lds[];    // [TN_WORDS] bitmap of the window, [TN_SUMMARY] touched words (zero between groups),
-    unsigned int *bits = gr_lds, *summ = gr_lds + TN_WORDS;                                      // [TN_THREADS / 64] scan scratch
-    int *s_scan = (int *)(gr_lds + TN_WORDS + TN_SUMMARY);
+    extern __shared__ unsigned int gr_lds[];
+    TnBitmap bm(gr_lds);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int k = tid; k < TN_WORDS + TN_SUMMARY; k += TN_THREADS) gr_lds[k] = 0u;
-    __syncthreads();
-    [[maybe_unused]] unsigned int gone = 0;     // count pass: bits this thread's exclusion ids cleared
     for (long long g = blockIdx.x; g < n_groups; g += gridDim.x) {
         const long long a = grp_ptr[g], b = grp_ptr[g + 1];
         long long total = 0;
@@ -67,83 +65,26 @@ __global__ __launch_bounds__(TN_THREADS) void k_gr_candidates(long long n_groups
             // mark: one wave per member walks the member's segment
             for (long long p = a + wv; p < b; p += TN_THREADS / 64) {
                 const long long r1 = mem_ptr[p + 1];
-                for (long long r = mem_ptr[p] + lane; r < r1; r += 64) {
-                    const long long x = (long long)mem_item[r] - lo;
-                    if (x < 0 || x >= GR_WINDOW) continue;
-                    const int w = (int)(x >> 5);
-                    const unsigned int old = atomicOr(&bits[w], 1u << (x & 31));
-                    if (old == 0u) atomicOr(&summ[w >> 5], 1u << (w & 31));
-                }
+                for (long long r = mem_ptr[p] + lane; r < r1; r += 64) bm.mark((long long)mem_item[r] - lo);
             }
             __syncthreads();
-            if (!keep_held) {                   // an item any member holds is no candidate (its word stays listed as touched)
+            if (!keep_held) {                   // an item any member holds is no candidate
                 for (long long p = a + wv; p < b; p += TN_THREADS / 64) {
                     const int u = grp_user[p];
                     if (u < 0 || u >= U) continue;
                     const long long r1 = pptr[u + 1];
-                    for (long long r = pptr[u] + lane; r < r1; r += 64) {
-                        const long long x = (long long)pitem[r] - lo;
-                        if (x >= 0 && x < GR_WINDOW) atomicAnd(&bits[x >> 5], ~(1u << (x & 31)));
-                    }
+                    for (long long r = pptr[u] + lane; r < r1; r += 64) bm.unmark((long long)pitem[r] - lo);
                 }
                 __syncthreads();
             }
-            if (ex_ptr) {                       // the group's exclusions: a bit that was still set is a candidate removed, once
-                const long long e1 = ex_ptr[g + 1];
-                for (long long e = ex_ptr[g] + tid; e < e1; e += TN_THREADS) {
-                    const long long id = ex_id[e], x = id - lo;
-                    if (id < 0 || id >= I || x < 0 || x >= GR_WINDOW) continue;
-                    const unsigned int bit = 1u << (x & 31);
-                    const unsigned int old = atomicAnd(&bits[x >> 5], ~bit);
-                    if constexpr (!FILL) gone += (old & bit) ? 1u : 0u;
-                }
-                __syncthreads();
-            }
-            // emit in ascending index: count per thread, scan over the block, write; the visited words are zeroed on the way
-            int c = 0;
-#pragma unroll
-            for (int k = 0; k < TN_PER; k++) {
-                unsigned int sw = summ[tid * TN_PER + k];
-                while (sw) {
-                    const int w = (tid * TN_PER + k) * 32 + __ffs(sw) - 1;
-                    sw &= sw - 1;
-                    c += __popc(rf_eligible<true>(bits[w], allow, (lo >> 5) + w));
-                }
-            }
-            int tot;
-            const int ex = tn_block_scan(c, &tot, s_scan);
-            [[maybe_unused]] long long o = out0 + total + ex;
-#pragma unroll
-            for (int k = 0; k < TN_PER; k++) {
-                const int s = tid * TN_PER + k;
-                unsigned int sw = summ[s];
-                if (sw == 0u) continue;
-                summ[s] = 0u;
-                while (sw) {
-                    const int w = s * 32 + __ffs(sw) - 1;
-                    sw &= sw - 1;
-                    [[maybe_unused]] unsigned int bw = bits[w];
-                    bits[w] = 0u;
-                    if constexpr (FILL) {
-                        bw = rf_eligible<true>(bw, allow, (lo >> 5) + w);
-                        while (bw) {
-                            const int bit = __ffs(bw) - 1;
-                            bw &= bw - 1;
-                            gc_item[o++] = (int)(lo + (long long)w * 32 + bit);
-                        }
-                    }
-                }
-            }
-            total += tot;
-            __syncthreads();
+            bm.template exclude<!FILL>(ex_ptr, ex_id, g, I, lo);
+            total += bm.template emit<FILL, true, false>(lo, allow, out0 + total, [&](long long o, long long item) { gc_item[o] = (int)item; });
         }
         if constexpr (!FILL) {
             if (tid == 0) gc_cnt[g] = (int)total;
         }
     }
-    if constexpr (!FILL) {
-        if (gone) atomicAdd(excluded, (unsigned long long)gone);
-    }
+    if constexpr (!FILL) bm.add_gone(excluded);
 }
 
 // lane j < have holds the j-th best candidate so far; keys are distinct (the candidate list holds an item once).
@@ -239,25 +180,10 @@ __global__ __launch_bounds__(256) void k_gr_select(long long n_groups, int n_top
     }
 }
 
-template <bool FILL, class... A>
-static hipError_t gr_candidates(hipStream_t st, unsigned blocks, A... a) {
-    const hipError_t e = hipFuncSetAttribute((const void *)k_gr_candidates<FILL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    k_gr_candidates<FILL><<<dim3(blocks), dim3(TN_THREADS), TN_LDS_BYTES, st>>>(a...);
-    return hipGetLastError();
-}
-
-}  // namespace xmap
-using namespace xmap;
-
-extern "C" {
-
-int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr, const int32_t *grp_user, int32_t n_top, int32_t rank_by,
-                         int32_t flags, int32_t how, double veto, int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt,
-                         const int32_t *nb_col, const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item,
-                         const double *prof_rating, const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
-                         int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_low,
-                         const xmap_rec_filter *F, int64_t *h_stats) {
+// rec_model.h: the body of xmap_group_topn_rows
+int group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr, const int32_t *grp_user, int32_t n_top, int32_t rank_by,
+                    int32_t flags, int32_t how, double veto, const RecModel &M, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                    double *out_decay, int32_t *out_low, const xmap_rec_filter *F, int64_t *h_stats) {
     XM_SCOPE(stream);
     hipStream_t st = (hipStream_t)stream;
     XM_ARG(how == XMAP_GROUP_MEAN || how == XMAP_GROUP_MIN || how == XMAP_GROUP_MAX);
@@ -265,11 +191,9 @@ int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr,
     XM_ARG(n_top >= 1 && n_top <= TN_MAX_TOP);
     XM_ARG(rank_by == 0 || rank_by == 1);
     XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
-    XM_ARG(n_w >= 1 && wtab);
-    XM_ARG(n_groups >= 0 && n_users >= 0 && n_items >= 0 && keep >= 1 && keep <= 64 && prof_ptr);
-    XM_ARG(n_groups == 0 || (grp_ptr && out_cnt && out_item && out_plain && out_decay && out_low));
-    XM_ARG(n_items == 0 || (nb_cnt && nb_col && nb_sim && item_avg));
-    XM_ARG(n_users == 0 || (prof_item && prof_rating && prof_time));
+    int rc = rec_model_check(M);
+    if (rc) return rc;
+    XM_ARG(n_groups >= 0 && (n_groups == 0 || (grp_ptr && out_cnt && out_item && out_plain && out_decay && out_low)));
     if (h_stats) for (int k = 0; k < 8; k++) h_stats[k] = 0;
     if (n_groups == 0) {
         bool f0 = false;
@@ -303,7 +227,7 @@ int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr,
     }
     bool filt = false;
     double min_score = 0.0;
-    int rc = rf_prepare(st, n_groups, F, &filt, &min_score);
+    rc = rf_prepare(st, n_groups, F, &filt, &min_score);
     if (rc) return rc;
     const unsigned int *allow = F ? (const unsigned int *)F->allow : nullptr;
     const long long *ex_ptr = F ? (const long long *)F->ex_ptr : nullptr;
@@ -315,36 +239,29 @@ int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr,
     XM_HIP(hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 6, st));
     // ---- member pass: the flattened members as the queries of a top-N call; the mask, not the exclusions
     TnScored S;
-    if (n_mem > 0) {
-        rc = tn_score_candidates(st, n_mem, grp_user, flags, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating,
-                                 prof_time, item_avg, wtab, n_w, allow != nullptr, allow, nullptr, nullptr, stats + 5, &S);
-        if (rc) return rc;
-    }
+    if (n_mem > 0 && (rc = tn_score_candidates(st, n_mem, grp_user, flags, M, allow != nullptr, allow, nullptr, nullptr, stats + 5, &S))) return rc;
     // ---- the groups' candidates: count, scan, fill
-    int *gc_cnt = nullptr, *gc_item = nullptr;
+    int *gc_item = nullptr;
     long long *gc_ptr = nullptr;
     int64_t n_gc = 0;
-    XM_HIP(xm_malloc_async((void **)&gc_cnt, sizeof(int) * (size_t)n_groups, st));
-    XM_HIP(xm_malloc_async((void **)&gc_ptr, sizeof(long long) * ((size_t)n_groups + 1), st));
     const unsigned cblocks = (unsigned)(n_groups < TN_MAX_BLOCKS ? n_groups : TN_MAX_BLOCKS);
-    XM_HIP(gr_candidates<false>(st, cblocks, (long long)n_groups, (const long long *)grp_ptr, grp_user, (long long)n_users, (int)n_items,
-                                (int)(flags & XMAP_TOPN_KEEP_HELD), (const long long *)S.cand_ptr, (const int *)S.cand_item,
-                                (const long long *)prof_ptr, prof_item, gc_cnt, (const long long *)nullptr, (int *)nullptr, allow, ex_ptr,
-                                ex_id, stats + 3));
-    rc = xmap_exclusive_scan_i32_to_i64(st, gc_cnt, (int64_t *)gc_ptr, n_groups, &n_gc);
+    rc = count_scan_fill<false>(
+        st, n_groups, &gc_ptr, &n_gc,
+        [&](bool fill, int *gc_cnt, const long long *ptr) {
+            return launch_dyn_lds(fill ? k_gr_candidates<true> : k_gr_candidates<false>, cblocks, TN_THREADS, TnBitmap::LDS_BYTES, st, n_groups,
+                                  (const long long *)grp_ptr, grp_user, M.n_users, M.n_items, flags & XMAP_TOPN_KEEP_HELD, S.cand_ptr,
+                                  S.cand_item, (const long long *)M.prof_ptr, M.prof_item, gc_cnt, ptr, gc_item, allow, ex_ptr, ex_id, stats + 3);
+        },
+        [&](int64_t n) -> int {
+            if (n > 0) XM_HIP(xm_malloc_async((void **)&gc_item, sizeof(int) * (size_t)n, st));
+            return XMAP_OK;
+        });
     if (rc) return rc;
-    if (n_gc > 0) {
-        XM_HIP(xm_malloc_async((void **)&gc_item, sizeof(int) * (size_t)n_gc, st));
-        XM_HIP(gr_candidates<true>(st, cblocks, (long long)n_groups, (const long long *)grp_ptr, grp_user, (long long)n_users, (int)n_items,
-                                   (int)(flags & XMAP_TOPN_KEEP_HELD), (const long long *)S.cand_ptr, (const int *)S.cand_item,
-                                   (const long long *)prof_ptr, prof_item, (int *)nullptr, (const long long *)gc_ptr, gc_item, allow, ex_ptr,
-                                   ex_id, (unsigned long long *)nullptr));
-    }
     // ---- aggregate and select (n_gc == 0: every list is empty, the counts and the padding are still written)
     auto sel = how == XMAP_GROUP_MEAN ? k_gr_select<XMAP_GROUP_MEAN> : how == XMAP_GROUP_MIN ? k_gr_select<XMAP_GROUP_MIN> : k_gr_select<XMAP_GROUP_MAX>;
     sel<<<dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, st>>>(
         (long long)n_groups, n_top, rank_by, (const long long *)grp_ptr, (const long long *)S.cand_ptr, (const int *)S.cand_item,
-        (const double *)S.plain, (const double *)S.decay, (const int *)S.status, (const long long *)gc_ptr, (const int *)gc_item, item_avg, veto,
+        (const double *)S.plain, (const double *)S.decay, (const int *)S.status, (const long long *)gc_ptr, (const int *)gc_item, M.item_avg, veto,
         min_score, out_cnt, out_item, out_plain, out_decay, out_low, stats);
     XM_LAUNCH_CHECK();
     unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
@@ -355,5 +272,21 @@ int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr,
         h_stats[4] = (int64_t)h[2]; h_stats[5] = (int64_t)h[3]; h_stats[6] = (int64_t)h[4]; h_stats[7] = n_gc;
     }
     return XMAP_OK;
+}
+
+}  // namespace xmap
+using namespace xmap;
+
+extern "C" {
+
+int xmap_group_topn_rows(void *stream, int64_t n_groups, const int64_t *grp_ptr, const int32_t *grp_user, int32_t n_top, int32_t rank_by,
+                         int32_t flags, int32_t how, double veto, int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt,
+                         const int32_t *nb_col, const double *nb_sim, const int64_t *prof_ptr, const int32_t *prof_item,
+                         const double *prof_rating, const int64_t *prof_time, const double *item_avg, const double *wtab, int32_t n_w,
+                         int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_low,
+                         const xmap_rec_filter *F, int64_t *h_stats) {
+    const RecModel M{n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating, prof_time, item_avg, wtab, n_w};
+    return group_topn_rows(stream, n_groups, grp_ptr, grp_user, n_top, rank_by, flags, how, veto, M, out_cnt, out_item, out_plain, out_decay,
+                           out_low, F, h_stats);
 }
 }

@@ -17,9 +17,10 @@
 //   k_if_expand  : one thread per record of the chunk (its entry and item by bisection): key = (q - q0) << item_bits | j,
 //                  value = the record's index in the chunk; the fill pass also keeps (r0, r1) per record
 //   radix_sort_pairs (plan.hip): stable, so the records of one (q, j) stay in expansion order
-//   k_if_heads   : 1 where a run of equal keys starts -> scan = the run's index
-//   k_if_rows    : per item of the chunk the index of its first run (bisection of the sorted keys) -> its row count
-//   k_if_starts / k_if_reduce (fill only): one lane per run walks its records twice -- the double-double sum and sim, then the
+//   k_pr_heads   : (sorted_runs.h, shared with the peers and the user-kNN top-N, as are k_pr_starts and the two bisections)
+//                  1 where a run of equal keys starts -> scan = the run's index
+//   k_if_rows    : per item of the chunk the index of its first run (pr_first_run: bisection of the sorted keys) -> its row count
+//   k_pr_starts / k_if_reduce (fill only): one lane per run walks its records twice -- the double-double sum and sim, then the
 //                  leave-one-out maximum -- and writes the entry at row_ptr[q] + (run - first run of q)
 //   k_if_stats   : avg and norm of a new item, one wave per item: the lane-strided double-double sums and dd_reduce of
 //                  item_stats.h
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "sorted_runs.h"
 #include "tri.h"
 
 namespace xmap {
@@ -68,15 +70,6 @@ __global__ __launch_bounds__(256) void k_if_item_rec(long long n_new, const long
     if (q <= n_new) item_rec[q] = rec_off[ptr[q]];
 }
 
-// the last k in [lo, hi) with a[k] <= x (a non-decreasing, a[lo] <= x)
-__device__ __forceinline__ long long if_last_le(const long long *a, long long lo, long long hi, long long x) {
-    while (hi - lo > 1) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_if_expand(long long n, long long rec0, long long e0, long long e1, long long q0, long long q1,
                                                    const long long *ptr, const int *user, const double *rating, const long long *pptr,
                                                    const int *pitem, const double *prating, const long long *rec_off, int item_bits,
@@ -84,8 +77,8 @@ __global__ __launch_bounds__(256) void k_if_expand(long long n, long long rec0, 
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     const long long g = rec0 + t;
-    const long long e = if_last_le(rec_off, e0, e1, g);         // entries without records are passed over
-    const long long q = if_last_le(ptr, q0, q1, e);             // items without entries too
+    const long long e = pr_last_le(rec_off, e0, e1, g);         // entries without records are passed over
+    const long long q = pr_last_le(ptr, q0, q1, e);             // items without entries too
     const long long p = pptr[user[e]] + (g - rec_off[e]);
     const unsigned long long j = (unsigned long long)(unsigned)pitem[p] & ((1ull << item_bits) - 1ull);
     keys[t] = ((unsigned long long)(q - q0) << item_bits) | j;
@@ -93,37 +86,15 @@ __global__ __launch_bounds__(256) void k_if_expand(long long n, long long rec0, 
     if (r0) { r0[t] = rating[e]; r1[t] = prating[p]; }
 }
 
-__global__ __launch_bounds__(256) void k_if_heads(long long n, const unsigned long long *keys, int *head) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) head[t] = (t == 0 || keys[t] != keys[t - 1]) ? 1 : 0;
-}
-
-// index of the first run of local item x: run_idx at the first sorted position whose item is >= x (run_idx[n] = all runs)
-__device__ __forceinline__ long long if_first_run(long long n, const unsigned long long *keys, int item_bits, const long long *run_idx,
-                                                  unsigned long long x) {
-    long long lo = 0, hi = n;           // first position in [0, n] with (key >> item_bits) >= x
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((keys[mid] >> item_bits) >= x) hi = mid; else lo = mid + 1;
-    }
-    return run_idx[lo];
-}
-
+// first run and row count of every item of the chunk (sorted_runs.h: the bisection of k_pr_first)
 __global__ __launch_bounds__(256) void k_if_rows(long long nq, long long n, const unsigned long long *keys, int item_bits,
                                                  const long long *run_idx, long long *first, int *cnt) {
     const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= nq) return;
-    const long long a = if_first_run(n, keys, item_bits, run_idx, (unsigned long long)x);
-    const long long b = if_first_run(n, keys, item_bits, run_idx, (unsigned long long)x + 1ull);
+    const long long a = pr_first_run(n, keys, item_bits, run_idx, (unsigned long long)x);
+    const long long b = pr_first_run(n, keys, item_bits, run_idx, (unsigned long long)x + 1ull);
     first[x] = a;
     if (cnt) cnt[x] = (int)(b - a);
-}
-
-__global__ __launch_bounds__(256) void k_if_starts(long long n, const int *head, const long long *run_idx, int *run_start) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    if (head[t]) run_start[run_idx[t]] = (int)t;
-    if (t == 0) run_start[run_idx[n]] = (int)n;
 }
 
 // one lane per run, records in sorted (= expansion) order
@@ -191,12 +162,6 @@ __global__ __launch_bounds__(256) void k_if_stats(long long n_new, const long lo
     }
 }
 
-static int bits_for(long long v) {      // bits that hold 0 .. v - 1, at least one
-    int b = 1;
-    while (b < 62 && (1ll << b) < v) b++;
-    return b;
-}
-
 struct IfBatch {
     long long n_new, nnz;
     const long long *ptr; const int *user; const double *rating;
@@ -249,8 +214,8 @@ static int itemfold_pass(hipStream_t st, const IfBatch &B, long long max_records
         q0 = q1;
     }
     if (n_max == 0) return XMAP_OK;             // no rater has a row: every count is 0
-    const int item_bits = bits_for(B.n_items);
-    XM_ARG(item_bits + bits_for(nq_max) <= 62);
+    const int item_bits = pr_bits_for(B.n_items);
+    XM_ARG(item_bits + pr_bits_for(nq_max) <= 62);
     const size_t nm = (size_t)n_max;
     unsigned long long *keys = nullptr;
     int *vals = nullptr, *head = nullptr, *run_start = nullptr;
@@ -274,14 +239,14 @@ static int itemfold_pass(hipStream_t st, const IfBatch &B, long long max_records
         k_if_expand<<<dim3(nb), dim3(256), 0, st>>>(n, h_rec[q0], h_ptr[q0], h_ptr[q1], q0, q1, B.ptr, B.user, B.rating, B.pptr, B.pitem,
                                                     B.prating, rec_off, item_bits, keys, vals, r0, r1);
         XM_LAUNCH_CHECK();
-        if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, item_bits + bits_for(nq)))) return rc;
-        k_if_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
+        if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, item_bits + pr_bits_for(nq)))) return rc;
+        k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
         XM_LAUNCH_CHECK();
         if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
         k_if_rows<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(nq, n, keys, item_bits, run_idx, first, fill ? nullptr : cnt + q0);
         XM_LAUNCH_CHECK();
         if (fill) {
-            k_if_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
+            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
             XM_LAUNCH_CHECK();
             k_if_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, keys, vals, r0, r1, run_idx, run_start, first, item_bits, q0,
                                                                             B.n_items, item_norm, new_norm, cap, row_ptr, col, sim, ls, nij);

@@ -76,6 +76,15 @@ __global__ __launch_bounds__(64) void k_mae_final(int n_part, const double *part
     out[0] = c; out[1] = a; out[2] = b;
 }
 
+// rec_model.h: the body of xmap_predict_rows.  The tables are asked for only when there is a pair to predict.
+int predict_rows(void *stream, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const RecModel &M, double *out_plain,
+                 double *out_decay, int32_t *status, int32_t *h_max_now) {
+    XM_ARG(n_test >= 0 && M.n_users >= 0 && M.n_items >= 0 && M.keep >= 1 && M.keep <= 64 && M.n_w >= 1 && M.wtab && M.prof_ptr);
+    XM_ARG(n_test == 0 || (test_user && test_item && M.nb_cnt && M.nb_col && M.nb_sim && M.item_avg && out_plain && out_decay && status));
+    XM_ARG(M.n_users == 0 || (M.prof_item && M.prof_rating && M.prof_time));
+    return predict_rows_run<false>((hipStream_t)stream, n_test, test_user, test_item, M, out_plain, out_decay, status, h_max_now);
+}
+
 }  // namespace xmap
 using namespace xmap;
 
@@ -99,11 +108,8 @@ int xmap_predict_rows(void *stream, int64_t n_test, const int32_t *test_user, co
                       const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time,
                       const double *item_avg, const double *wtab, int32_t n_w, double *out_plain, double *out_decay,
                       int32_t *status, int32_t *h_max_now) {
-    XM_ARG(n_test >= 0 && n_users >= 0 && n_items >= 0 && keep >= 1 && keep <= 64 && n_w >= 1 && wtab && prof_ptr);
-    XM_ARG(n_test == 0 || (test_user && test_item && nb_cnt && nb_col && nb_sim && item_avg && out_plain && out_decay && status));
-    XM_ARG(prof_ptr && (n_users == 0 || (prof_item && prof_rating && prof_time)));
-    return predict_rows_run<false>((hipStream_t)stream, n_test, test_user, test_item, n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr,
-                                   prof_item, prof_rating, prof_time, item_avg, wtab, n_w, out_plain, out_decay, status, h_max_now);
+    const RecModel M{n_users, n_items, keep, nb_cnt, nb_col, nb_sim, prof_ptr, prof_item, prof_rating, prof_time, item_avg, wtab, n_w};
+    return predict_rows(stream, n_test, test_user, test_item, M, out_plain, out_decay, status, h_max_now);
 }
 
 int xmap_mae(void *stream, int64_t n_test, const int32_t *status, const double *real, const double *out_plain, const double *out_decay,
