@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N]]
 
 --user-based: the recommender stages with the user method of the reference's egg (calculate_xmap_sim_method = cosine_user): the
 similarity between the users' AlterEgo profiles with its local sensitivity on the device (xmap.engine.session.UserSimRDD), the
@@ -48,6 +48,10 @@ their peers as one group of recommend_group: "people like you also liked".
 (as --peers finds them), the MAE of the held-out ratings predicted from those neighbours' ratings (the reference's
 user_based_prediction: xmap.engine.session.predict_user_knn), and for three test users the five items their neighbours rate highest
 (recommend_user_knn; Resnick's formula, at least two neighbour ratings per item).
+--related N (with --device-tail): "what goes with these items?" -- the product-page and cart query, with no user and no rating: for
+three baskets drawn from held-out users' items the N items most related to the basket as a whole over the RecommenderSim rows
+(xmap.engine.session.related_items: the sum of the members' similarities, the members themselves left out), and for the first
+basket the list under "mean" and "max" beside it.
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -140,6 +144,7 @@ def main(argv=None):
     ap.add_argument("--groups", type=int, default=None, metavar="K")
     ap.add_argument("--peers", type=int, default=None, metavar="N")
     ap.add_argument("--user-knn", type=int, default=None, metavar="K")
+    ap.add_argument("--related", type=int, default=None, metavar="N")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -179,6 +184,8 @@ def main(argv=None):
         ap.error("--groups K needs --device-tail, the non-private recommender and 1 <= K <= 64")
     if args.user_knn is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.user_knn <= 1024):
         ap.error("--user-knn K needs --device-tail, the non-private recommender and 1 <= K <= 1024")
+    if args.related is not None and (not args.device_tail or not 1 <= args.related <= 1024):
+        ap.error("--related N needs --device-tail and 1 <= N <= 1024")
     if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
         ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
@@ -328,6 +335,21 @@ def main(argv=None):
         print("user-kNN lists: %d candidates of %d users, %d records expanded" % (lists.stats[0], len(some), lists.stats[5]))
         for uid, lst in lists.collect():
             print("people like %s rated highly:" % uid, ", ".join("%s (%.3f, %d ratings)" % e for e in lst) or "no neighbour rated anything new")
+    if args.related is not None:
+        # what goes with these items?  Baskets of a few held-out items each: no user, no rating
+        carts = [("basket of %s" % uid, [e[0] for e in pairs[:3]]) for uid, pairs in testRDD.take(3)]
+        by_how = {}
+        for how in ("sum", "mean", "max"):
+            by_how[how] = timed("related_" + how, session.related_items, alterEgo_profile, carts, rc["calculate_xmap_weighting"], args.related,
+                                how=how)
+        rel = by_how["sum"]
+        print("related: %d candidates of %d baskets, %d records expanded (largest candidate count %d), %d unknown members" % (
+            rel.stats[0], len(carts), rel.stats[5], rel.stats[4], rel.unknown_items))
+        for (label, members), (_, lst) in zip(carts, rel.collect()):
+            print("%s = %s" % (label, ", ".join(members)))
+            print("  goes with:", ", ".join("%s (%.3f, %d of %d)" % (iid, s, n, len(members)) for iid, s, n in lst) or "nothing related")
+        for how in ("mean", "max"):
+            print("  first basket by %s:" % how, ", ".join("%s (%.3f)" % (iid, s) for iid, s, _ in by_how[how].collect()[0][1]) or "nothing related")
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

@@ -1096,6 +1096,55 @@ int xmap_uknn_topn_rows(void *stream, int64_t n_query, const int32_t *query_user
                         double *out_score, int32_t *out_support,
                         const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
 
+/* ---- related items (csrc/stage_e_related.hip; DESIGN.md 4 "Related items"): "what goes with these items" -- the n_top items most
+ * related to a SET of items (a cart, an anonymous session, "more like this"), read off the rows of the RecommenderSim CSR.  No
+ * user and no rating takes part.  Merging per-member neighbour lists on the host cannot do this: the cut is per member (an item
+ * that is eleventh for every member and first for the basket is in nobody's list).  All arithmetic is fp64, one rounded operation
+ * per step, no fused multiply-add.
+ * The matrix: the RecommenderSim CSR as xmap_sim2_scatter leaves it (row_ptr [n_items + 1], col / sim): rows in storage order,
+ *   not sorted; a row may hold a column twice and may hold its own index; resident, trusted, read only; a row holds fewer than
+ *   2^31 - 1 entries.  An entry whose column is outside [0, n_items) is ignored.
+ * The baskets: a CSR of n_query baskets, b_ptr [n_query + 1] (b_ptr[0] = 0, non-decreasing), b_item [b_ptr[n_query]], b_weight
+ *   beside it or NULL.  A member outside [0, n_items) is a member without a row; a repeated member counts once per occurrence;
+ *   an empty basket is valid.
+ * Records of query q: for each basket position p in order whose member b is valid, each entry e of row b in storage order, the
+ *   record (item = col[e], v = fl(b_weight[p] * sim[e])); b_weight == NULL: v = sim[e], nothing is multiplied.
+ * Rules, in this order: (1) the candidates are the items with at least one record; (2) the basket's own valid members leave
+ *   unless XMAP_RELATED_KEEP_MEMBERS; (3) the ids of the query's exclusion list leave, and the rest is intersected with F->allow
+ *   -- the mask and the ids are ITEMS, one exclusion list per query, and both act in the expansion: no record of an ineligible
+ *   item is written; (4) support = the records of the item; support < min_support (>= 1): dropped, counted; (5) the score over
+ *   the item's records in record order -- XMAP_RELATED_SUM: from 0.0 left to right; XMAP_RELATED_MEAN: that sum / (double)support;
+ *   XMAP_RELATED_MAX: the largest v as numbers, the first occurrence's bits among equals, NaN if any v is NaN; (6) a score that
+ *   is not finite: dropped, counted; (7) score < F->min_score: dropped, counted; (8) selection by score descending as numbers,
+ *   item index ascending on equal scores.  F == NULL: no rules.
+ * Outputs (device): out_cnt [n_query]; out_item / out_score / out_support [n_query][n_top] with -1 / 0.0 / 0 behind the count;
+ *   1 <= n_top <= 1024.  Queries may repeat.  A pure function of the inputs: it depends on neither the grid, nor the order of
+ *   any atomic, nor max_records.  h_stats (host, [6] or NULL): [0] candidates after rules 2-3, [1] dropped by min_support, [2]
+ *   dropped as non-finite, [3] dropped below the floor, [4] the largest candidate count (after rules 2-3) of one query, [5]
+ *   records expanded (the records of the items rule 3 lets through, members' included; the markers below are not counted).
+ * The queries are cut into chunks of consecutive queries whose records number at most max_records (0: the library's default,
+ *   2^22); a single query above that is a chunk of its own and its records must stay below 2^31 (XMAP_ERR_CAPACITY).  Per chunk:
+ *   record counts per basket position -> scan -> expansion (one wave per position compacts the member's row under the mask and
+ *   the exclusion list) -> stable radix sort on (q - q0) << item_bits | item -> run heads -> scan -> one lane per run ->
+ *   segmented selection.  Rule 2 takes no second walk: every valid position also emits one MARKER record for its own item, which
+ *   sorts into that item's run and makes the run no candidate; markers count towards a chunk's size only.  Temporaries from the
+ *   stream's arena: 64 B per record of the largest chunk (48 B per record + 16 B per run, sized for as many runs as records),
+ *   12 B per basket position and 8 B per query; n_query <= 2^28.  n_top, how, flags, min_support, a NaN floor and the pointers
+ *   are checked on the host before any device work; b_ptr, ex_ptr (the error names the first bad position) and the record
+ *   counts on the device, before anything is indexed through the tables or an output is written.  max_records above 2^31 - 2
+ *   counts as 2^31 - 2.  The exclusion list of a query is walked whole for every row entry of its members, in the count pass
+ *   and in the expansion (row length * list length steps per basket position): meant for short lists.  Syncs. */
+#define XMAP_RELATED_SUM 0
+#define XMAP_RELATED_MEAN 1
+#define XMAP_RELATED_MAX 2
+#define XMAP_RELATED_KEEP_MEMBERS 1
+int xmap_related_rows(void *stream, int64_t n_query, const int64_t *b_ptr /*[n_query+1]*/, const int32_t *b_item,
+                      const double *b_weight /* or NULL: every weight 1.0, and no multiplication is performed */,
+                      int32_t n_items, const int64_t *row_ptr /*[I+1]*/, const int32_t *col, const double *sim,
+                      int32_t how, int32_t flags, int32_t n_top, int32_t min_support, int64_t max_records /*0: library default*/,
+                      int32_t *out_cnt, int32_t *out_item, double *out_score, int32_t *out_support,
+                      const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
+
 /* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
  * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
  * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
@@ -1447,6 +1496,16 @@ int xmap_ctx_uknn_recommend(xmap_ctx *ctx, int32_t source, int64_t n_query, cons
                             int32_t peer_flags, int32_t cap, int32_t min_common, int32_t flags, int32_t n_top, int32_t min_support,
                             int32_t *out_cnt, int32_t *out_item, double *out_score, int32_t *out_support,
                             const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
+/* Related items for a basket: xmap_related_rows over the context's RecommenderSim CSR.  Host arrays in (b_ptr / b_item / b_weight,
+ * F with host pointers), host arrays out, as xmap_related_rows defines them; stats as its h_stats.  Needs the result of
+ * xmap_ctx_rec_sim only (have_rec) -- no neighbour lists -- so it works right after xmap_ctx_rec_sim and on a union context, and
+ * goes with whatever drops the RecommenderSim rows.  n_top, how, flags, min_support, max_records, the pointers, b_ptr and the
+ * filter are checked on the host before the context is read or any device work is done: on XMAP_ERR_ARG the outputs keep every
+ * byte. */
+int xmap_ctx_related(xmap_ctx *ctx, int64_t n_query, const int64_t *b_ptr /*[n_query+1]*/, const int32_t *b_item,
+                     const double *b_weight /* or NULL */, int32_t how, int32_t flags, int32_t n_top, int32_t min_support,
+                     int64_t max_records /*0: library default*/, int32_t *out_cnt, int32_t *out_item, double *out_score,
+                     int32_t *out_support, const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

@@ -13,6 +13,7 @@
 //                     -> [rec_sim -> rec_select] -> xmap_ctx_foldin_predict | xmap_ctx_foldin_recommend (the same kernels, the batch's rows)
 //   item fold-in, for items that were not in the upload:  rec_sim -> rec_select -> xmap_ctx_item_foldin (rows, lists, extended tables)
 //                     -> xmap_ctx_item_foldin_audience | _predict | _recommend (the same kernels, tables of I + n_new items)
+//   related items for a basket:  rec_sim -> xmap_ctx_related (the top-N over the RecommenderSim rows of the basket's members; no lists)
 //   explanations of (user, item) pairs: xmap_ctx_explain | xmap_ctx_foldin_explain, wherever xmap_ctx_predict | xmap_ctx_foldin_predict work
 //   xmap_ctx_*_download copy results into caller-allocated host buffers whose sizes the stage call reported.
 //
@@ -1672,6 +1673,51 @@ int xmap_ctx_uknn_recommend(xmap_ctx *c, int32_t source, int64_t n_query, const 
     XM_TRY(xmap_uknn_topn_rows(c->st, n_query, L.query, L.Q.n_users, L.Q.ptr, L.Q.item, L.query_avg, n_nb, L.cnt, L.user, L.sim, c->R.n_users,
                                c->R.n_items, c->pf_ptr, c->pf_item, c->pf_rating, L.user_avg, flags, n_top, min_support, 0, d_cnt, d_item,
                                d_score, d_support, &D, stats));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_score, (const double *)d_score, m, c->st));
+    XM_TRY(d2h(out_support, (const int32_t *)d_support, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+// ---- related items: the top-N over the RecommenderSim rows of a basket's members -----------------------------------------------------
+
+int xmap_ctx_related(xmap_ctx *c, int64_t n_query, const int64_t *b_ptr, const int32_t *b_item, const double *b_weight, int32_t how,
+                     int32_t flags, int32_t n_top, int32_t min_support, int64_t max_records, int32_t *out_cnt, int32_t *out_item,
+                     double *out_score, int32_t *out_support, const xmap_rec_filter *F, int64_t *stats) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(n_top >= 1 && n_top <= 1024);
+    XM_ARG(how == XMAP_RELATED_SUM || how == XMAP_RELATED_MEAN || how == XMAP_RELATED_MAX);
+    XM_ARG((flags & ~XMAP_RELATED_KEEP_MEMBERS) == 0);
+    XM_ARG(min_support >= 1);
+    XM_ARG(max_records >= 0);
+    XM_ARG(n_query >= 0 && n_query <= (1ll << 28) && (n_query == 0 || (b_ptr && out_cnt && out_item && out_score && out_support)));
+    if (n_query > 0) {
+        if (b_ptr[0] != 0) { set_error("related: b_ptr[0] = %lld, not 0", (long long)b_ptr[0]); return XMAP_ERR_ARG; }
+        for (int64_t q = 0; q < n_query; q++)
+            if (b_ptr[q + 1] < b_ptr[q]) { set_error("related: b_ptr[%lld] < b_ptr[%lld]", (long long)q + 1, (long long)q); return XMAP_ERR_ARG; }
+        if (b_ptr[n_query] > 0 && !b_item) { set_error("related: b_ptr lists %lld members, b_item is NULL", (long long)b_ptr[n_query]); return XMAP_ERR_ARG; }
+    }
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_rec);
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 6; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    ScratchPool tmp;
+    int64_t *d_ptr;
+    int32_t *d_member, *d_cnt, *d_item, *d_support;
+    double *d_weight = nullptr, *d_score;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top, nb = (size_t)b_ptr[n_query];
+    XM_TRY(h2d(tmp, &d_ptr, b_ptr, n + 1, c->st));
+    XM_TRY(h2d(tmp, &d_member, b_item, nb, c->st));
+    if (b_weight) XM_TRY(h2d(tmp, &d_weight, b_weight, nb, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
+    XM_TRY(dalloc(tmp, &d_score, m, c->st)); XM_TRY(dalloc(tmp, &d_support, m, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, c->R.n_items, &D));
+    XM_TRY(xmap_related_rows(c->st, n_query, d_ptr, d_member, d_weight, c->R.n_items, c->rs_row_ptr, c->rs_col, c->rs_sim, how, flags, n_top,
+                             min_support, max_records, d_cnt, d_item, d_score, d_support, &D, stats));
     XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
     XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
     XM_TRY(d2h(out_score, (const double *)d_score, m, c->st));

@@ -25,15 +25,39 @@ __device__ __forceinline__ unsigned int rf_eligible(unsigned int bw, const unsig
     return bw;
 }
 
-// ex_ptr[0 .. n_query]: bad[0] += positions k with ptr[k] < ptr[k - 1] (k = 0: ptr[0] != 0), bad[1] = ptr[n_query].  Bounded by
-// n_query alone: nothing is read through the table before it has passed.
-static __global__ __launch_bounds__(256) void k_rf_check(long long n_query, const long long *ex_ptr, unsigned long long *bad) {
+// A CSR pointer table ptr[0 .. n]: bad[0] += positions k with ptr[k] < ptr[k - 1] (k = 0: ptr[0] != 0), bad[1] = ptr[n], bad[2] = the
+// first such position (the caller sets it to RF_NO_POS).  Bounded by n alone: nothing is read through the table before it has passed.
+constexpr unsigned long long RF_NO_POS = ~0ull;
+static __global__ __launch_bounds__(256) void k_rf_check(long long n, const long long *ptr, unsigned long long *bad) {
     const long long step = (long long)gridDim.x * blockDim.x;
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k <= n_query; k += step) {
-        const bool b = k == 0 ? ex_ptr[0] != 0 : ex_ptr[k] < ex_ptr[k - 1];
-        if (b) atomicAdd(&bad[0], 1ull);        // (bad input only: no need to spare the atomics)
-        if (k == n_query) bad[1] = (unsigned long long)ex_ptr[k];
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k <= n; k += step) {
+        const bool b = k == 0 ? ptr[0] != 0 : ptr[k] < ptr[k - 1];
+        if (b) {                                // (bad input only: no need to spare the atomics; a minimum does not depend on their order)
+            atomicAdd(&bad[0], 1ull);
+            atomicMin(&bad[2], (unsigned long long)k);
+        }
+        if (k == n) bad[1] = (unsigned long long)ptr[k];
     }
+}
+
+// The device check of the pointer table `name` of n lists, for the call `who`: XMAP_ERR_ARG with the count of bad entries and the
+// first bad position; *total = ptr[n].  Synchronises.
+static int rf_check_ptr(hipStream_t st, int64_t n, const long long *ptr, const char *who, const char *name, long long *total) {
+    unsigned long long *bad = nullptr, h_bad[3] = {0, 0, RF_NO_POS};
+    XM_HIP(xm_malloc_async((void **)&bad, sizeof(h_bad), st));
+    XM_HIP(hipMemcpyAsync(bad, h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st));
+    const long long entries = n + 1;
+    const unsigned blocks = (unsigned)((entries + 255) / 256 < 1024 ? (entries + 255) / 256 : 1024);
+    k_rf_check<<<dim3(blocks), dim3(256), 0, st>>>(n, ptr, bad);
+    XM_LAUNCH_CHECK();
+    XM_HIP(hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+    XM_HIP(hipStreamSynchronize(st));
+    if (h_bad[0]) {
+        set_error("%s: %s has %llu bad entries, the first at %s[%llu] (%s[0] = 0, non-decreasing)", who, name, h_bad[0], name, h_bad[2], name);
+        return XMAP_ERR_ARG;
+    }
+    *total = (long long)h_bad[1];
+    return XMAP_OK;
 }
 
 // The argument checks of a filtered fine-grained call, before any candidate work.  *filt = the candidate pass needs its FILT
@@ -48,21 +72,11 @@ static int rf_prepare(hipStream_t st, int64_t n_query, const xmap_rec_filter *F,
     }
     *min_score = F->min_score;
     if (F->ex_ptr && n_query > 0) {
-        unsigned long long *bad = nullptr, h_bad[2] = {0, 0};
-        XM_HIP(xm_malloc_async((void **)&bad, sizeof(h_bad), st));
-        XM_HIP(hipMemsetAsync(bad, 0, sizeof(h_bad), st));
-        const long long total = n_query + 1;
-        const unsigned blocks = (unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-        k_rf_check<<<dim3(blocks), dim3(256), 0, st>>>(n_query, (const long long *)F->ex_ptr, bad);
-        XM_LAUNCH_CHECK();
-        XM_HIP(hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
-        XM_HIP(hipStreamSynchronize(st));
-        if (h_bad[0]) {
-            set_error("xmap_rec_filter: ex_ptr has %llu bad entries (ex_ptr[0] = 0, non-decreasing)", h_bad[0]);
-            return XMAP_ERR_ARG;
-        }
-        if (h_bad[1] > 0 && !F->ex_id) {
-            set_error("xmap_rec_filter: ex_ptr lists %llu ids, ex_id is NULL", h_bad[1]);
+        long long n_ex = 0;
+        const int rc = rf_check_ptr(st, n_query, (const long long *)F->ex_ptr, "xmap_rec_filter", "ex_ptr", &n_ex);
+        if (rc) return rc;
+        if (n_ex > 0 && !F->ex_id) {
+            set_error("xmap_rec_filter: ex_ptr lists %lld ids, ex_id is NULL", n_ex);
             return XMAP_ERR_ARG;
         }
     }

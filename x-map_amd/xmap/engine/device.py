@@ -2134,6 +2134,50 @@ class Engine(object):
         del alive
         return out_cnt[:n_q], out_item[:n_q], out_score[:n_q], out_support[:n_q], tuple(int(x) for x in h)
 
+    def related(self, S, b_ptr, b_item, n_top, how="sum", weights=None, keep_members=False, min_support=1, allow=None, exclude=None,
+                min_score=None, max_records=0):
+        """Related items for a basket on the device (xmap_related_rows): per basket -- a CSR, b_ptr int64 [Q + 1], b_item int32 --
+        the n_top (1..1024) items most related to its members over the rows of the RecommenderSim CSR S (a rec_sim() result, or
+        any (row_ptr int64 [I + 1], col int32, sim float64) on the device).  An item's records are the entries that name it in the
+        members' rows, position by position, each row in storage order; its score is their sum ("sum"), their mean ("mean") or the
+        largest ("max"), with weights (float64, one per basket position) multiplied into the similarities first; score descending,
+        item index ascending.  No user and no rating takes part.  The basket's own members leave unless keep_members; a member
+        outside the items has no row; an item with fewer than min_support records is dropped.  allow / exclude / min_score as
+        topn() takes them (items; the mask and the lists act in the expansion).  Returns (cnt [Q], item [Q][n_top] (-1 behind the
+        count), score, support [Q][n_top], stats) with stats = (candidates, dropped by min_support, dropped as non-finite, dropped
+        below the floor, largest candidate count of a query, records expanded).  max_records: the chunk bound (0: the library's)."""
+        row_ptr, col, sim = (S.row_ptr, S.col, S.sim) if hasattr(S, "row_ptr") else S
+        n_items = int(row_ptr.numel()) - 1
+        n_q, n_top = int(b_ptr.numel()) - 1, int(n_top)
+        if how not in abi.RELATED_HOW:
+            raise ValueError("how = %r: one of %s" % (how, sorted(abi.RELATED_HOW)))
+        if not 1 <= n_top <= 1024:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 1024" % n_top)
+        if int(min_support) < 1:
+            raise ValueError("min_support = %r: >= 1" % (min_support,))
+        if n_q < 0 or b_ptr.dtype != torch.int64 or b_item.dtype != torch.int32:
+            raise ValueError("baskets = (b_ptr int64 [Q + 1], b_item int32)")
+        if row_ptr.dtype != torch.int64 or col.dtype != torch.int32 or sim.dtype != torch.float64 or n_items < 0:
+            raise ValueError("S = (row_ptr int64 [I + 1], col int32, sim float64)")
+        if weights is not None and (weights.dtype != torch.float64 or int(weights.numel()) != int(b_item.numel())):
+            raise ValueError("weights: float64, one per basket position (%d)" % int(b_item.numel()))
+        out_cnt = self._empty(max(n_q, 1), torch.int32)
+        out_item, out_support = self._empty((max(n_q, 1), n_top), torch.int32), self._empty((max(n_q, 1), n_top), torch.int32)
+        out_score = self._empty((max(n_q, 1), n_top), torch.float64)
+        F = alive = None
+        if allow is not None or exclude is not None or min_score is not None:
+            F, alive = self._rec_filter(n_items, n_q, allow, exclude, min_score)
+        h = (C.c_int64 * 6)()
+        with self.timed("related"):
+            check(lib.xmap_related_rows(_stream(self.dev), i64(n_q), vp(b_ptr.contiguous()), vp(b_item.contiguous()),
+                                        vp(None if weights is None else weights.contiguous()), i32(n_items), vp(row_ptr.contiguous()),
+                                        vp(col.contiguous()), vp(sim.contiguous()), i32(abi.RELATED_HOW[how]),
+                                        i32(abi.RELATED_KEEP_MEMBERS if keep_members else 0), i32(n_top), i32(min_support),
+                                        i64(max_records), vp(out_cnt), vp(out_item), vp(out_score), vp(out_support),
+                                        None if F is None else C.byref(F), h))
+        del alive
+        return out_cnt[:n_q], out_item[:n_q], out_score[:n_q], out_support[:n_q], tuple(int(x) for x in h)
+
     def explain(self, P, neighbors, pair_user, pair_item, item_avg, wtab, n_ev, rank_by=0):
         """Why a pair scores what it scores (xmap_explain_rows, the pair body of predict() in its explain mode): for the (user,
         item) pairs -- int32 tensors, typically the lists of topn() -- the n_ev (1..16) strongest evidence entries of the

@@ -25,6 +25,9 @@ GROUP_MEAN, GROUP_MIN, GROUP_MAX = 0, 1, 2      # XMAP_GROUP_*: `how` of xmap_gr
 GROUP_MAX_MEMBERS = 64    # XMAP_GROUP_MAX_MEMBERS: members of one group
 PEERS_SAME, PEERS_KEEP_SELF, PEERS_CENTRED = 1, 2, 4      # XMAP_PEERS_*: flags of xmap_peer_rows / xmap_ctx_peers
 UKNN_OWN_MEAN, UKNN_KEEP_HELD = 1, 2      # XMAP_UKNN_*: flags of xmap_uknn_predict_rows / xmap_uknn_topn_rows and the coarse calls
+RELATED_SUM, RELATED_MEAN, RELATED_MAX = 0, 1, 2      # XMAP_RELATED_*: `how` of xmap_related_rows / xmap_ctx_related
+RELATED_KEEP_MEMBERS = 1  # XMAP_RELATED_KEEP_MEMBERS: flag of the same
+RELATED_HOW = {"sum": RELATED_SUM, "mean": RELATED_MEAN, "max": RELATED_MAX}
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -122,6 +125,7 @@ EXPORTS = [
     "xmap_group_topn_rows", "xmap_ctx_recommend_group",
     "xmap_peer_index", "xmap_peer_centre", "xmap_peer_rows", "xmap_ctx_peers", "xmap_peer_rows_ls", "xmap_ctx_peers_ls",
     "xmap_uknn_means", "xmap_uknn_predict_rows", "xmap_uknn_topn_rows", "xmap_ctx_uknn_predict", "xmap_ctx_uknn_recommend",
+    "xmap_related_rows", "xmap_ctx_related",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -353,28 +353,36 @@ def _no_fold_in(alterEgoRDD, who):
                         "profiles in against one part's AlterEgoRDD" % who)
 
 
-def _tail_setup(alterEgoRDD, cap, keep, neighbors, who):
-    """what recommend and recommend_topn share: profiles of the AlterEgo rows -> RecommenderSim -> neighbour lists (selected on
-    the device, or the caller's lists as arrays).  Returns (state, engine over the profiles, P, S, (cnt, col, sim), item_avg)."""
-    import torch
+def _tail_matrix(alterEgoRDD, cap, who):
+    """the front of every tail call: profiles of the AlterEgo rows -> RecommenderSim.  Returns (state, engine over the profiles, P,
+    S); no neighbour list is selected."""
     from . import device
     if isinstance(alterEgoRDD, AlterEgoUnion):
         st = alterEgoRDD.state
-        eng, idt = st.engine, st.idt
+        eng = st.engine
         P = alterEgoRDD.profiles()
     elif isinstance(alterEgoRDD, AlterEgoRDD):
         st, G = alterEgoRDD.state, alterEgoRDD.G
-        eng, idt = st.engine, st.idt
+        eng = st.engine
         key = time_rank(st)[G.time] if G.n_rows else G.time
         P = eng.alterego_profiles(G, time_key=key)
     else:
         raise TypeError("%s() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device) or the "
                         "AlterEgoUnion of union_alterego" % who)
-    dev = eng.dev
-    I = len(idt.iids)
     eng2 = device.Engine(P)
     eng2.timers = eng.timers
     S = eng2.rec_sim(int(cap))
+    return st, eng2, P, S
+
+
+def _tail_setup(alterEgoRDD, cap, keep, neighbors, who):
+    """what recommend and recommend_topn share: profiles of the AlterEgo rows -> RecommenderSim -> neighbour lists (selected on
+    the device, or the caller's lists as arrays).  Returns (state, engine over the profiles, P, S, (cnt, col, sim), item_avg)."""
+    import torch
+    st, eng2, P, S = _tail_matrix(alterEgoRDD, cap, who)
+    idt = st.idt
+    dev = st.engine.dev
+    I = len(idt.iids)
     item_avg = S.info[:I, 0].contiguous()
     if neighbors is None:
         nb = eng2.rec_select(S, int(keep))[:3]
@@ -1159,6 +1167,68 @@ def recommend_user_knn_profiles(alterEgoRDD, profiles, n_nb, n, cap=1, centred=T
     res = _uknn_records(st, eng2, P, F, d_q, lists, q_avg, means, labels, n, own_mean, keep_held, min_support, getattr(profiles, "ctx", None),
                         _eligibility(st.engine.dev, labels, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
     res.unknown_items, res.counts = unknown, F.counts
+    return res
+
+
+def related_items(alterEgoRDD, baskets, cap, n, how="sum", keep_members=False, min_support=1, allow_items=None, exclude=None,
+                  min_score=None, map_sources=False):
+    """Related items for a basket, on the device: "what goes with these items" -- the product page, the cart, an anonymous
+    session; no user and no rating takes part.  The front of recommend (profiles of the AlterEgo rows -> RecommenderSim, cap; no
+    neighbour list is selected), then for every basket the n (1..1024) items most related to its members over the rows of the
+    RecommenderSim matrix (Engine.related): an item's records are the entries that name it in the members' rows, its score their
+    sum (how="sum"), mean ("mean") or largest ("max"); score descending, item index ascending on equal scores.  `baskets` is an
+    RDD or list of (label, [iid*]) or (label, [(iid, weight)*]) -- weights multiply the member's similarities; a repeated member
+    counts once per occurrence; a repeated label raises ValueError.  The members themselves are left out unless keep_members; an
+    item with fewer than min_support records is dropped.  allow_items, exclude = {label: iids}, min_score: the eligibility rules of
+    recommend_topn, applied before the cut.  Takes an AlterEgoRDD or an AlterEgoUnion.
+    map_sources=True (an AlterEgoRDD only) is the cross-domain query -- a basket of movies gives related books: a member that is
+    a source item is replaced by its target under the handle's replacement map before the call (looked up on the host; the map is
+    downloaded once per call), and a source member without a replacement counts as unknown.  A union has one map per part: TypeError.
+    Returns a LocalRDD of (label, [(iid, score, support)*]) in basket order with .stats = (candidates, dropped by min_support,
+    dropped as non-finite, dropped below the floor, largest candidate count of a basket, records expanded) and .unknown_items =
+    the members dropped because the id table does not know their iid (or, with map_sources, the map has no target for them)."""
+    import torch
+    if map_sources and isinstance(alterEgoRDD, AlterEgoUnion):
+        raise TypeError("related_items(map_sources=True): a union of AlterEgo rows has one replacement map per part; map the "
+                        "basket against one part's AlterEgoRDD")
+    st, eng2, _, S = _tail_matrix(alterEgoRDD, cap, "related_items")
+    idt, dev = st.idt, st.engine.dev
+    recs = [(rec[0], list(rec[1])) for rec in (baskets.collect() if hasattr(baskets, "collect") else baskets)]
+    labels = [lab for lab, _ in recs]
+    if len(set(labels)) != len(labels):
+        seen = set()
+        raise ValueError("related_items(): basket label %r occurs more than once" % ([x for x in labels if x in seen or seen.add(x)][0],))
+    mp = flags = None
+    if map_sources:
+        G = alterEgoRDD.G
+        if getattr(G, "map", None) is None:
+            raise ValueError("map_sources needs the replacement map of the generate pass (Engine.alterego keeps it on its result)")
+        mp, flags = G.map.cpu().numpy(), st.engine.R.flags.cpu().numpy()
+    ptr = np.zeros(len(recs) + 1, np.int64)
+    item, weight, weighted, unknown = [], [], False, 0
+    for k, (_, members) in enumerate(recs):
+        for m in members:
+            iid, w = (m[0], float(m[1])) if isinstance(m, (tuple, list)) else (m, 1.0)
+            weighted = weighted or isinstance(m, (tuple, list))
+            i = idt.iidx.get(iid)
+            if i is not None and mp is not None and not (int(flags[i]) & 2):      # a source item: its target, if it has one
+                i = int(mp[i]) if int(mp[i]) >= 0 else None
+            if i is None:
+                unknown += 1
+                continue
+            item.append(i); weight.append(w)
+        ptr[k + 1] = len(item)
+    d_ptr = torch.from_numpy(ptr).to(dev)
+    d_item = torch.from_numpy(np.asarray(item, np.int32)).to(dev)
+    d_w = torch.from_numpy(np.asarray(weight, np.float64)).to(dev) if weighted else None
+    rules = _eligibility(dev, labels, idt.iidx, len(idt.iids), allow_items, exclude, min_score)
+    cnt, it, score, support, stats = eng2.related(S, d_ptr, d_item, int(n), how=how, weights=d_w, keep_members=keep_members,
+                                                  min_support=min_support, **rules)
+    cnt, it, score, support = cnt.cpu().numpy(), it.cpu().numpy(), score.cpu().numpy(), support.cpu().numpy()
+    iids = idt.iids
+    out = [(lab, [(iids[it[q, t]], float(score[q, t]), int(support[q, t])) for t in range(cnt[q])]) for q, lab in enumerate(labels)]
+    res = LocalRDD(out, getattr(baskets, "ctx", None))
+    res.stats, res.unknown_items = stats, unknown
     return res
 
 
