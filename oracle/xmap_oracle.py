@@ -307,6 +307,26 @@ def rec_select(R, keep):
     return cnt, col, sim, ls
 
 
+def rec_select_rows(row_ptr, col, sim, ls, keep):
+    """rec_select on rows fed by the caller (CSR: row_ptr [I + 1], col / sim / ls per entry, the entries of a row in any order):
+    xo_rec_select reads I, row_ptr, col, sim and ls of the struct and nothing else, so the struct is built here over NumPy
+    arrays and never handed to xo_rec_free.  -> (cnt [I], col [I][keep], sim, ls)"""
+    R = Rec()
+    R.row_ptr = np.ascontiguousarray(row_ptr, np.int64)
+    I = len(R.row_ptr) - 1
+    assert I >= 0 and R.row_ptr[0] == 0 and np.all(np.diff(R.row_ptr) >= 0) and 1 <= int(keep)
+    D = int(R.row_ptr[-1])
+    pad = lambda a, dt: np.ascontiguousarray(a if D else np.zeros(1), dt)      # (never a null pointer)
+    R.col, R.sim, R.ls = pad(col, np.int32), pad(sim, np.float64), pad(ls, np.float64)
+    assert all(len(a) == max(D, 1) for a in (R.col, R.sim, R.ls))
+    R._own = _XoRec(I=I, row_ptr=_p(R.row_ptr, C.c_int64), col=_p(R.col, C.c_int32), sim=_p(R.sim, C.c_double),
+                    ls=_p(R.ls, C.c_double), nij=None, norm=None)
+    R._h = C.pointer(R._own)
+    out = rec_select(R, int(keep))
+    R._h = None                  # the arrays are NumPy's: never free()d by the library
+    return out
+
+
 def rec_free(R):
     if getattr(R, "_h", None) is not None:
         lib().xo_rec_free(R._h)
