@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW]]
 
 --user-based: the recommender stages with the user method of the reference's egg (calculate_xmap_sim_method = cosine_user): the
 similarity between the users' AlterEgo profiles with its local sensitivity on the device (xmap.engine.session.UserSimRDD), the
@@ -52,6 +52,11 @@ user_based_prediction: xmap.engine.session.predict_user_knn), and for three test
 three baskets drawn from held-out users' items the N items most related to the basket as a whole over the RecommenderSim rows
 (xmap.engine.session.related_items: the sum of the members' similarities, the members themselves left out), and for the first
 basket the list under "mean" and "max" beside it.
+--fill HOW (with --device-tail; HOW = count or mean): the popularity fill -- every list is cut from candidates with evidence, so a
+test user with few AlterEgo rows gets a short list and one without any an empty one.  The run prints, without and with the fill
+(xmap.engine.session.recommend_topn / evaluate_topn with fill=HOW: short lists completed with the most held / best rated items
+the user does not hold), the share of short lists, the share of empty lists, recall@10 and the items covered, and the head of the
+ranking itself (popular_items).
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -145,6 +150,7 @@ def main(argv=None):
     ap.add_argument("--peers", type=int, default=None, metavar="N")
     ap.add_argument("--user-knn", type=int, default=None, metavar="K")
     ap.add_argument("--related", type=int, default=None, metavar="N")
+    ap.add_argument("--fill", default=None, choices=["count", "mean"], metavar="HOW")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -186,6 +192,8 @@ def main(argv=None):
         ap.error("--user-knn K needs --device-tail, the non-private recommender and 1 <= K <= 1024")
     if args.related is not None and (not args.device_tail or not 1 <= args.related <= 1024):
         ap.error("--related N needs --device-tail and 1 <= N <= 1024")
+    if args.fill is not None and (not args.device_tail or para["recommender"]["private_flag"]):
+        ap.error("--fill HOW needs --device-tail and the non-private recommender")
     if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
         ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
@@ -350,6 +358,21 @@ def main(argv=None):
             print("  goes with:", ", ".join("%s (%.3f, %d of %d)" % (iid, s, n, len(members)) for iid, s, n in lst) or "nothing related")
         for how in ("mean", "max"):
             print("  first basket by %s:" % how, ", ".join("%s (%.3f)" % (iid, s) for iid, s, _ in by_how[how].collect()[0][1]) or "nothing related")
+    if args.fill is not None:
+        # what the fill buys: the lists of every test user without and with it, scored against the held-out ratings
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        spec = args.fill if args.fill == "count" else dict(how="mean", damping=25.0, min_count=2)
+        everyone = [uid for uid, _ in testRDD.collect()]
+        print("fill = %s: %d test users, lists of 10" % (args.fill, len(everyone)))
+        print("  %-8s %12s %12s %10s %10s" % ("", "short lists", "empty lists", "recall@10", "coverage"))
+        for name, fill in (("without", None), ("with", spec)):
+            lists = timed("topn_fill_" + name, session.recommend_topn, alterEgo_profile, everyone, w, k, alpha, 10, fill=fill).collect()
+            ev = session.evaluate_topn(alterEgo_profile, testRDD, w, k, alpha, 10, cutoffs=(10,), rel_min=4.0, fill=fill)
+            print("  %-8s %11.1f%% %11.1f%% %10.4f %10d" % (
+                name, 100.0 * sum(len(l) < 10 for _, l in lists) / max(len(lists), 1),
+                100.0 * sum(not l for _, l in lists) / max(len(lists), 1), ev.at[10]["recall"], ev.at[10]["coverage"]))
+        shelf = session.popular_items(alterEgo_profile, w, 5, **(dict(how="count") if args.fill == "count" else spec))
+        print("  the shelf of an anonymous visitor:", ", ".join("%s (%.3f)" % e for e in shelf))
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

@@ -1145,6 +1145,55 @@ int xmap_related_rows(void *stream, int64_t n_query, const int64_t *b_ptr /*[n_q
                       int32_t *out_cnt, int32_t *out_item, double *out_score, int32_t *out_support,
                       const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
 
+/* ---- popularity fill (csrc/stage_e_fill.hip; DESIGN.md 4 "Popularity fill"): a ranking of the items by popularity, and the
+ * completion of short top-N lists with its head.  Every other list of the tail is cut from candidates with evidence; these two
+ * calls answer when there is none (a user without rows, a one-rating fold-in, a 1 % mask, the anonymous visitor).
+ * xmap_pop_index: the ranking over an index xmap_peer_index built with centre == NULL (hd_x = raw ratings).  Per item i:
+ *   n_i = hd_ptr[i + 1] - hd_ptr[i] (a user holding an item twice counts twice, as in the peers); S_i = the double-double sum of
+ *   hd_x over the item's holders rounded once (what xmap_peer_centre divides); T = hd_ptr[n_items]; G = the double-double sum of
+ *   all indexed hd_x rounded once, taken over the per-item (hi, lo) partials in a fixed shape (one block: thread t of 1024 adds the
+ *   items t, t + 1024, ..., then a fixed tree), so its bits depend on no grid; mu = T > 0 ? G / T : 0.0.  Scores, fp64, one rounded
+ *   operation per step, no fused multiply-add: XMAP_POP_COUNT: (double)n_i; XMAP_POP_MEAN: (S_i + damping * mu) / ((double)n_i +
+ *   damping).  Item i is ranked iff n_i >= min_count and its score is finite; the others are counted into h_counts[1] (below
+ *   min_count) and h_counts[2] (non-finite; a non-finite G makes every MEAN score non-finite).  Order: score descending as numbers
+ *   (-0.0 equals 0.0), item index ascending on equal scores.  pop_item / pop_score [0 .. ranked) hold the ranking (the score's own
+ *   bits), -1 / 0.0 behind it; pop_pos[i] = i's position or -1; h_counts[0] = ranked.  A pure function of the index.  damping
+ *   (finite, >= 0), min_count (>= 1) and how are checked before any device work.  One stable radix sort of n_items 64-bit keys
+ *   and one pass over the indexed rows; temporaries (48 B per item) from the stream's arena.  Syncs.
+ * xmap_topn_fill_rows: completes, in place, lists in the layout xmap_topn_rows, xmap_topn_rows_filtered, xmap_diversify_rows and
+ *   xmap_group_topn_rows write (cnt [Q], item / plain / decay [Q][n_top], 1 <= n_top <= 64; cnt outside [0, n_top] counts as the
+ *   nearer bound).  The profiles are the CSR the queries index (the resident profiles or a fold-in batch; prof_item only).
+ *   n_pop_items = the size of the ranked id space (pop_pos has that many entries); ids in [n_pop_items, n_items) -- the batch items
+ *   of an item fold-in -- have no position and are never filled.  Per query q, u = query_user[q], c = cnt[q], L = item[q][0 .. c):
+ *     for r in 0 .. n_ranked - 1 while c < n_top:  i = pop_item[r]
+ *       skip if i in L (or appended by this loop); skip if not (flags & XMAP_TOPN_KEEP_HELD) and u in [0, n_users) and a row of u
+ *       holds i; skip if F and i in ex_id[ex_ptr[q] .. ex_ptr[q + 1]) (ids outside [0, n_items) ignored, repeats allowed); skip if
+ *       F and F->allow and bit i of allow is clear;
+ *       item[q][c] = i; plain[q][c] = decay[q][c] = item_avg[i]; out_src[q][c] = 1; c += 1
+ *     cnt[q] = c; out_src[q][t] = 0 for t < the count on entry, -1 behind the final count.
+ *   item_avg[i] is what the model predicts for a pair without evidence.  A list that is full on entry keeps every byte.
+ *   F->min_score is a floor on PREDICTIONS: it does not apply to a fill (a NaN floor is still XMAP_ERR_ARG).  The fill knows the
+ *   lists, not the scores: an item the scoring pass dropped (status 2, or below the floor) may return as a fill.  A user outside
+ *   [0, n_users) holds nothing: such a query is the anonymous visitor, whose list is the eligible head of the ranking.  Queries may
+ *   repeat, each with its own exclusion list.  ex_ptr is checked on the device before any output is written, as in the filtered
+ *   calls: XMAP_ERR_ARG, the outputs untouched.  A pure function of the inputs.  h_stats (host, [4] or NULL): queries short on
+ *   entry, of those filled to n_top, fill entries written, queries still short.
+ *   One wave per query walks the ranking XMAP_FILL_WINDOW positions at a time: every skip id is looked up once per window in
+ *   pop_pos and marked in an LDS bitmap of the window; a query re-walks only when its skip ids cover a whole window of the head
+ *   (at most ceil((need + skip ids) / XMAP_FILL_WINDOW) windows).  With F->allow the ranking is compacted once per call to its
+ *   allowed positions (16 B per ranked item + 4 B per item of temporaries), so a sparse mask costs one pass over the items.  Syncs. */
+#define XMAP_POP_COUNT 0
+#define XMAP_POP_MEAN 1
+#define XMAP_FILL_WINDOW 4096
+int xmap_pop_index(void *stream, int32_t n_items, const int64_t *hd_ptr /*[I+1]*/, const double *hd_x, int32_t how, double damping,
+                   int32_t min_count, int32_t *pop_item /*[I]*/, double *pop_score /*[I]*/, int32_t *pop_pos /*[I]*/,
+                   int64_t *h_counts /* host, [3] or NULL: ranked, below min_count, non-finite score */);
+int xmap_topn_fill_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t flags, int64_t n_users,
+                        int32_t n_items, const int64_t *prof_ptr, const int32_t *prof_item, const double *item_avg, int32_t n_ranked,
+                        const int32_t *pop_item, const int32_t *pop_pos, int32_t n_pop_items, int32_t *cnt, int32_t *item,
+                        double *plain, double *decay /* in place, [Q] / [Q][n_top] */, int32_t *out_src /*[Q][n_top]*/,
+                        const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [4] or NULL */);
+
 /* ---- union of AlterEgo rows (csrc/stage_c_union.hip): the rows of D independent two-domain problems -> ONE set of user-major
  * profiles, the reference's alterEgo_profile1.union(alterEgo_profile2) [.distinct()] (code/multidomain_demo.py:128), in the
  * layout xmap_rec_profiles writes -- xmap_sim3_layout (RecommenderSim), xmap_rec_select, xmap_predict_rows, xmap_topn_rows,
@@ -1506,6 +1555,25 @@ int xmap_ctx_related(xmap_ctx *ctx, int64_t n_query, const int64_t *b_ptr /*[n_q
                      const double *b_weight /* or NULL */, int32_t how, int32_t flags, int32_t n_top, int32_t min_support,
                      int64_t max_records /*0: library default*/, int32_t *out_cnt, int32_t *out_item, double *out_score,
                      int32_t *out_support, const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [6] or NULL */);
+/* Popularity fill: the ranking (xmap_pop_index) over the context's peer index of the raw ratings, built on first use and kept
+ * beside it with the (how, damping, min_count) it was built for: rebuilt when those differ, dropped with the tail.  One ranking
+ * per context.
+ *   xmap_ctx_popular        : the head of the ranking: out_item / out_score [n_max] (host; -1 / 0.0 behind the ranking's end).  ALL
+ *                             n_max entries of both are written, also where n_max exceeds the number of items: the caller's
+ *                             buffers hold n_max entries, not min(n_max, n_items).  *n_ranked = the whole ranking's length.  Needs the resident profiles (have_rec), also on a union context.
+ *   xmap_ctx_recommend_filled : xmap_ctx_recommend_filtered into device temporaries, then xmap_topn_fill_rows; out_src [n_query][n_top]
+ *                             as it writes it.  Sources as the filtered call: XMAP_SRC_FOLDIN: held is the batch's rows, popularity
+ *                             is the resident users'; XMAP_SRC_ITEM_FOLDIN: the batch items are never filled.  stats [10]: the six of
+ *                             xmap_ctx_recommend_filtered, then the four of xmap_topn_fill_rows.
+ * n_top, rank_by, how, damping, min_count, source, flags, a NaN floor and n_max are checked on the host before the context is
+ * read, each check naming its argument: on XMAP_ERR_ARG the outputs keep every byte. */
+int xmap_ctx_popular(xmap_ctx *ctx, int32_t how, double damping, int32_t min_count, int64_t n_max, int32_t *out_item,
+                     double *out_score /* host [n_max] */, int64_t *n_ranked /* host, the whole ranking's length */);
+int xmap_ctx_recommend_filled(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top,
+                              int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t how, double damping,
+                              int32_t min_count, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
+                              int32_t *out_src, const xmap_rec_filter *F /* host pointers inside, or NULL */,
+                              int64_t *stats /* [10] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

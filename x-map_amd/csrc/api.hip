@@ -106,6 +106,15 @@ struct xmap_ctx {
     int64_t *pr_hd_ptr[2] = {nullptr, nullptr};
     int32_t *pr_hd_user[2] = {nullptr, nullptr};
     double *pr_hd_x[2] = {nullptr, nullptr}, *pr_nrm[2] = {nullptr, nullptr};
+    // the popularity ranking over the peer index [0] (xmap_pop_index), with what it was built for: built by the first
+    // xmap_ctx_popular / xmap_ctx_recommend_filled, rebuilt when (how, damping, min_count) differ, dropped with the tail
+    Pool p_pop;
+    bool have_pop = false;
+    int32_t pop_how = 0, pop_min = 0;
+    double pop_damping = 0.0;
+    int64_t pop_ranked = 0;
+    int32_t *pp_item = nullptr, *pp_pos = nullptr;
+    double *pp_score = nullptr;
     // item fold-in: the RecommenderSim rows of the last batch of new items (if_*), the batch's rater CSR, and the EXTENDED tables
     // of I + if_new items (x_*: rows [0, I) copies of nb_* / rs_avg, row I + q the list and the average of batch item q); hangs
     // on the tail and the neighbour lists: dropped with them
@@ -176,6 +185,7 @@ static void drop_tail(xmap_ctx *c) {
     c->p_nb.release(); c->p_rec.release(); c->p_div.release();
     c->have_rec = c->have_nb = c->have_div = false;
     for (int k = 0; k < 2; k++) { c->p_peer[k].release(); c->have_peer[k] = false; }
+    c->p_pop.release(); c->have_pop = false;
 }
 
 // the fold-in batch hangs on the replacement map: upload, item_sim, extend and generate drop it; the tail calls leave it
@@ -1723,6 +1733,90 @@ int xmap_ctx_related(xmap_ctx *c, int64_t n_query, const int64_t *b_ptr, const i
     XM_TRY(d2h(out_score, (const double *)d_score, m, c->st));
     XM_TRY(d2h(out_support, (const int32_t *)d_support, m, c->st));
     XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+// ---- popularity fill: the ranking over the peer index of the raw ratings, and short lists completed with its head ------------------
+
+// the context's ranking for (how, damping, min_count): built on first use, rebuilt when the three differ (one ranking per context)
+static int pop_index_of(xmap_ctx *c, int32_t how, double damping, int32_t min_count) {
+    if (c->have_pop && c->pop_how == how && c->pop_damping == damping && c->pop_min == min_count) return XMAP_OK;
+    XM_TRY(peer_index_of(c, 0));
+    const int32_t I = c->R.n_items;
+    c->p_pop.release();
+    c->have_pop = false;
+    XM_ALLOC(c->p_pop, c->pp_item, I); XM_ALLOC(c->p_pop, c->pp_pos, I); XM_ALLOC(c->p_pop, c->pp_score, I);
+    int64_t h[3] = {0, 0, 0};
+    XM_TRY(xmap_pop_index(c->st, I, c->pr_hd_ptr[0], c->pr_hd_x[0], how, damping, min_count, c->pp_item, c->pp_score, c->pp_pos, h));
+    c->pop_how = how; c->pop_damping = damping; c->pop_min = min_count; c->pop_ranked = h[0];
+    c->have_pop = true;
+    return XMAP_OK;
+}
+
+int xmap_ctx_popular(xmap_ctx *c, int32_t how, double damping, int32_t min_count, int64_t n_max, int32_t *out_item, double *out_score,
+                     int64_t *n_ranked) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(how == XMAP_POP_COUNT || how == XMAP_POP_MEAN);
+    XM_ARG(damping >= 0.0 && damping <= 1.7976931348623157e308);      // finite and >= 0 (a NaN fails both)
+    XM_ARG(min_count >= 1);
+    XM_ARG(n_max >= 0 && (n_max == 0 || (out_item && out_score)));
+    XM_ARG(c && c->have_gen && c->have_rec);
+    XM_HIP(hipSetDevice(c->device));
+    XM_TRY(pop_index_of(c, how, damping, min_count));
+    const int64_t I = c->R.n_items, n = n_max < I ? n_max : I;
+    XM_TRY(d2h(out_item, (const int32_t *)c->pp_item, (size_t)n, c->st));
+    XM_TRY(d2h(out_score, (const double *)c->pp_score, (size_t)n, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    for (int64_t k = n; k < n_max; k++) { out_item[k] = -1; out_score[k] = 0.0; }
+    if (n_ranked) *n_ranked = c->pop_ranked;
+    return XMAP_OK;
+}
+
+int xmap_ctx_recommend_filled(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by,
+                              int32_t flags, const double *wtab, int32_t n_w, int32_t how, double damping, int32_t min_count,
+                              int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_src,
+                              const xmap_rec_filter *F, int64_t *stats) {
+    // the host checks: before any device work, the outputs untouched, the context as it was
+    XM_ARG(n_top >= 1 && n_top <= 64);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((flags & ~XMAP_TOPN_KEEP_HELD) == 0);
+    XM_ARG(how == XMAP_POP_COUNT || how == XMAP_POP_MEAN);
+    XM_ARG(damping >= 0.0 && damping <= 1.7976931348623157e308);      // finite and >= 0 (a NaN fails both)
+    XM_ARG(min_count >= 1);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN || source == XMAP_SRC_ITEM_FOLDIN);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query >= 0 && (n_query == 0 || (query_user && out_cnt && out_item && out_plain && out_decay && out_src)));
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(source != XMAP_SRC_ITEM_FOLDIN || c->have_ifold);
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 10; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    XM_TRY(pop_index_of(c, how, damping, min_count));
+    const Profiles P = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const Tables T = source == XMAP_SRC_ITEM_FOLDIN ? itemfold_tables(c) : resident_tables(c);
+    ScratchPool tmp;
+    int32_t *d_user, *d_cnt, *d_item, *d_src;
+    double *d_w, *d_plain, *d_decay;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_user, query_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st)); XM_TRY(dalloc(tmp, &d_src, m, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+    int64_t h6[6] = {0, 0, 0, 0, 0, 0}, h4[4] = {0, 0, 0, 0};
+    XM_TRY(topn_rows(c->st, n_query, d_user, n_top, rank_by, flags, rec_model(P, T, d_w, n_w), d_cnt, d_item, d_plain, d_decay, &D, h6, 6));
+    XM_TRY(xmap_topn_fill_rows(c->st, n_query, d_user, n_top, flags, P.n_users, T.n_items, P.ptr, P.item, T.avg, (int32_t)c->pop_ranked,
+                               c->pp_item, c->pp_pos, c->R.n_items, d_cnt, d_item, d_plain, d_decay, d_src, &D, h4));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_TRY(d2h(out_src, (const int32_t *)d_src, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    if (stats) { for (int k = 0; k < 6; k++) stats[k] = h6[k]; for (int k = 0; k < 4; k++) stats[6 + k] = h4[k]; }
     return XMAP_OK;
 }
 

@@ -112,6 +112,11 @@ class PeerIndex(object):
     pass
 
 
+class PopIndex(object):
+    """what Engine.pop_index returns: the popularity ranking of the items of a peer index"""
+    pass
+
+
 class GenResult(object):
     pass
 
@@ -1988,6 +1993,64 @@ class Engine(object):
         with self.timed("peer_centre"):
             check(lib.xmap_peer_centre(_stream(self.dev), i32(index.n_items), vp(index.hd_ptr), vp(index.hd_x), vp(avg)))
         return avg[:index.n_items]
+
+    def pop_index(self, index, how="count", damping=0.0, min_count=1):
+        """The popularity ranking of the items (xmap_pop_index) over an UNCENTRED peer_index() handle: how "count" ranks by the
+        holders of an item, "mean" by (sum of its ratings + damping * the mean of all ratings) / (holders + damping); an item with
+        fewer than min_count holders or a non-finite score is not ranked.  Score descending, item index ascending on equal scores.
+        Returns a handle (n_items, item [I] (-1 behind the ranking), score [I], pos [I] (-1: not ranked), n_ranked, counts =
+        (ranked, below min_count, non-finite), how, damping, min_count) on the device."""
+        if index.centre is not None:
+            raise ValueError("pop_index: the ranking is taken over an index built without a centre")
+        if how not in abi.POP_HOW:
+            raise ValueError("how = %r: one of %s" % (how, sorted(abi.POP_HOW)))
+        damping, min_count = float(damping), int(min_count)
+        if not (0.0 <= damping < float("inf")):
+            raise ValueError("damping = %r: finite and >= 0" % damping)
+        if min_count < 1:
+            raise ValueError("min_count = %d: at least 1" % min_count)
+        X = PopIndex()
+        X.n_items, X.how, X.damping, X.min_count = int(index.n_items), how, damping, min_count
+        X.item, X.pos = self._empty(max(X.n_items, 1), torch.int32), self._empty(max(X.n_items, 1), torch.int32)
+        X.score = self._empty(max(X.n_items, 1), torch.float64)
+        h = (C.c_int64 * 3)(0, 0, 0)
+        with self.timed("pop_index"):
+            check(lib.xmap_pop_index(_stream(self.dev), i32(X.n_items), vp(index.hd_ptr), vp(index.hd_x), i32(abi.POP_HOW[how]),
+                                     C.c_double(damping), i32(min_count), vp(X.item), vp(X.score), vp(X.pos), h))
+        X.counts = tuple(int(x) for x in h)
+        X.n_ranked = X.counts[0]
+        return X
+
+    def fill(self, lists, pop, P, query_user, item_avg, keep_held=False, allow=None, exclude=None, n_items=None):
+        """Completes short lists with the head of a popularity ranking (xmap_topn_fill_rows).  `lists` = what topn() / diversify()
+        returned (cnt, item, plain, decayed, ...), for the queries query_user over the profiles P; pop a
+        pop_index() handle.  A fill is the next ranked item the list does not contain, the user does not hold (unless keep_held),
+        the query's exclusion list does not name and the mask allows; its plain and decayed value is item_avg[item], the
+        prediction of a pair without evidence.  n_items: the size of the id space of item_avg and the mask when it exceeds the
+        ranking's (the extended tables of an item fold-in: batch items are never filled).  The inputs are left as they are.
+        Returns (cnt, item, plain, decayed, src [Q][n_top] (0: the model's, 1: a fill, -1 behind the count), stats = (queries
+        short on entry, of those filled to n_top, fill entries written, queries still short))."""
+        cnt, item, plain, decay = [x.clone().contiguous() for x in lists[:4]]
+        Q = int(cnt.numel())
+        n_top = int(item.shape[1]) if item.dim() == 2 else 1
+        if not 1 <= n_top <= 64:
+            raise ValueError("n_top = %d: the fill takes lists of 1 .. 64" % n_top)
+        if int(query_user.numel()) != Q:
+            raise ValueError("fill: %d lists for %d queries" % (Q, int(query_user.numel())))
+        n_items = int(pop.n_items if n_items is None else n_items)
+        src = self._empty((max(Q, 1), n_top), torch.int32)
+        F = alive = None
+        if allow is not None or exclude is not None:
+            F, alive = self._rec_filter(n_items, Q, allow, exclude, None)
+        h = (C.c_int64 * 4)(0, 0, 0, 0)
+        with self.timed("fill"):
+            check(lib.xmap_topn_fill_rows(_stream(self.dev), i64(Q), vp(query_user.contiguous()), i32(n_top),
+                                          i32(abi.TOPN_KEEP_HELD if keep_held else 0), i64(P.n_users), i32(n_items), vp(P.user_ptr),
+                                          vp(P.user_item), vp(item_avg.contiguous()), i32(pop.n_ranked), vp(pop.item), vp(pop.pos),
+                                          i32(pop.n_items), vp(cnt), vp(item), vp(plain), vp(decay), vp(src),
+                                          None if F is None else C.byref(F), h))
+        del alive
+        return cnt, item, plain, decay, src[:Q], tuple(int(x) for x in h)
 
     def peers(self, index, Q, query_user, n_top, cap=1, min_common=1, same=False, keep_self=False, allow=None, exclude=None,
               min_sim=None, max_records=0):

@@ -28,6 +28,9 @@ UKNN_OWN_MEAN, UKNN_KEEP_HELD = 1, 2      # XMAP_UKNN_*: flags of xmap_uknn_pred
 RELATED_SUM, RELATED_MEAN, RELATED_MAX = 0, 1, 2      # XMAP_RELATED_*: `how` of xmap_related_rows / xmap_ctx_related
 RELATED_KEEP_MEMBERS = 1  # XMAP_RELATED_KEEP_MEMBERS: flag of the same
 RELATED_HOW = {"sum": RELATED_SUM, "mean": RELATED_MEAN, "max": RELATED_MAX}
+POP_COUNT, POP_MEAN = 0, 1      # XMAP_POP_*: `how` of xmap_pop_index / xmap_ctx_popular / xmap_ctx_recommend_filled
+FILL_WINDOW = 4096        # XMAP_FILL_WINDOW: rank positions one wave of xmap_topn_fill_rows marks at a time
+POP_HOW = {"count": POP_COUNT, "mean": POP_MEAN}
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -126,6 +129,7 @@ EXPORTS = [
     "xmap_peer_index", "xmap_peer_centre", "xmap_peer_rows", "xmap_ctx_peers", "xmap_peer_rows_ls", "xmap_ctx_peers_ls",
     "xmap_uknn_means", "xmap_uknn_predict_rows", "xmap_uknn_topn_rows", "xmap_ctx_uknn_predict", "xmap_ctx_uknn_recommend",
     "xmap_related_rows", "xmap_ctx_related",
+    "xmap_pop_index", "xmap_topn_fill_rows", "xmap_ctx_popular", "xmap_ctx_recommend_filled",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -353,9 +353,8 @@ def _no_fold_in(alterEgoRDD, who):
                         "profiles in against one part's AlterEgoRDD" % who)
 
 
-def _tail_matrix(alterEgoRDD, cap, who):
-    """the front of every tail call: profiles of the AlterEgo rows -> RecommenderSim.  Returns (state, engine over the profiles, P,
-    S); no neighbour list is selected."""
+def _tail_profiles(alterEgoRDD, who):
+    """the profiles of the AlterEgo rows.  Returns (state, engine over the profiles, P)."""
     from . import device
     if isinstance(alterEgoRDD, AlterEgoUnion):
         st = alterEgoRDD.state
@@ -371,6 +370,13 @@ def _tail_matrix(alterEgoRDD, cap, who):
                         "AlterEgoUnion of union_alterego" % who)
     eng2 = device.Engine(P)
     eng2.timers = eng.timers
+    return st, eng2, P
+
+
+def _tail_matrix(alterEgoRDD, cap, who):
+    """the front of every tail call: profiles of the AlterEgo rows -> RecommenderSim.  Returns (state, engine over the profiles, P,
+    S); no neighbour list is selected."""
+    st, eng2, P = _tail_profiles(alterEgoRDD, who)
     S = eng2.rec_sim(int(cap))
     return st, eng2, P, S
 
@@ -501,7 +507,7 @@ def _eligibility(dev, labels, index, n_ids, allow, exclude, min_score):
 
 
 def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None,
-                   allow_items=None, exclude=None, min_score=None, diversify=None, pool=None):
+                   allow_items=None, exclude=None, min_score=None, diversify=None, pool=None, fill=None):
     """Top-N recommendation on the device from an AlterEgoRDD handle: the set-up of recommend (profiles -> RecommenderSim ->
     neighbour lists, or `neighbors`), then for every uid of `users` the n (1..64) best items its own rows give evidence for,
     ranked by the unrounded prediction -- without temporal decay, or with (decay=True, alpha) -- score descending, item id
@@ -521,8 +527,19 @@ def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_he
     score - w * (its largest |sim| in the RecommenderSim matrix to an item picked so far).  The records are the existing ones in the
     new order, the rules act before the pool is cut, and the result carries .ils = the mean pairwise |sim| of every user's list, in
     the order of `users`, and .div_stats = (lists that differ from the pool's prefix, items returned).  diversify = 0 returns the
-    lists of the plain call with their .ils; diversify = None takes the plain path untouched."""
+    lists of the plain call with their .ils; diversify = None takes the plain path untouched.
+    Popularity fill: fill = "count", "mean" or dict(how=, damping=, min_count=) completes every list shorter than n -- a user
+    without rows, a uid the train set does not know, a narrow allow_items -- with the most popular items of the resident profiles
+    (Engine.pop_index: by holders, or by the damped mean rating) that the list does not contain, the user does not hold (unless
+    keep_held), exclude does not name and allow_items admits; min_score is a floor on predictions and does not apply.  A filled
+    record is (iid, item average, item average): what the model predicts without evidence.  The stages run rules -> pool ->
+    diversify -> fill: fills never enter the re-ranking and .ils stays that of the model's part.  The result carries .sources (per
+    user a list of 0 = the model's / 1 = a fill) and .fill_stats = (lists short before the fill, of those filled to n, fill
+    entries, lists still short); with explain a filled pair is explained as any pair without evidence is.  fill = None takes the
+    path as it is without it.  Every call with fill builds the peer index and the ranking anew (as it builds RecommenderSim anew);
+    a caller that fills many batches keeps them with Engine.peer_index / pop_index / fill, or in a coarse context."""
     _diverse(n, diversify, pool)
+    spec = _fill_spec(fill)
     st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn")
     idt = st.idt
     uids = list(users.collect()) if hasattr(users, "collect") else list(users)
@@ -530,7 +547,7 @@ def recommend_topn(alterEgoRDD, users, cap, keep, alpha, n, decay=False, keep_he
     query = [uidx.get(uid, -1) for uid in uids]
     res = _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, getattr(users, "ctx", None),
                         _eligibility(st.engine.dev, uids, idt.iidx, len(idt.iids), allow_items, exclude, min_score),
-                        _diverse(n, diversify, pool, eng2, S))
+                        _diverse(n, diversify, pool, eng2, S), (spec, P) if spec else None)
     _tail_dicts(res, st, S, nb)
     if explain is not None:
         _explain_lists(res, st, eng2, P, nb, item_avg, query, alpha, decay, explain, (st.ratings, st.times) if hasattr(st, "ratings") else None)
@@ -574,13 +591,47 @@ def _topn_lists(eng2, P, nb, d_q, item_avg, alpha, n, decay, keep_held, dev, rul
     return cnt, item, plain, decayed, out[4], ils, div_stats
 
 
-def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, ctx, rules=None, diverse=None):
+def _fill_spec(fill):
+    """the fill= keyword of a top-N call, checked before any device work -> None (the path as it is without it) or (how, damping,
+    min_count): "count" / "mean", or a dict with how / damping / min_count"""
+    if fill is None:
+        return None
+    spec = dict(how=fill) if isinstance(fill, str) else dict(fill)
+    if set(spec) - {"how", "damping", "min_count"}:
+        raise ValueError("fill = %r: a dict of how / damping / min_count" % (fill,))
+    how, damping, min_count = spec.get("how", "count"), float(spec.get("damping", 0.0)), int(spec.get("min_count", 1))
+    if how not in ("count", "mean"):
+        raise ValueError("fill: how = %r, not \"count\" or \"mean\"" % (how,))
+    if not (0.0 <= damping < float("inf")):
+        raise ValueError("fill: damping = %r: finite and >= 0" % damping)
+    if min_count < 1:
+        raise ValueError("fill: min_count = %d: at least 1" % min_count)
+    return how, damping, min_count
+
+
+def _fill_lists(eng2, resident, P, d_q, item_avg, lists, spec, keep_held, rules):
+    """Engine.fill of `lists` (cnt, item, plain, decayed of the queries d_q over the profiles P) with the popularity ranking of the
+    RESIDENT profiles for spec = _fill_spec(...); of the rules the mask and the exclusion lists apply, the floor is one on
+    predictions.  Returns (cnt, item, plain, decayed, src, fill_stats).  Like the rest of the session layer, which rebuilds its
+    model per call, this builds the peer index and the ranking on every call (3.4 ms together at BASELINE configs[1], beside the
+    0.1 ms of the fill itself); only the coarse context (xmap_ctx_recommend_filled) keeps them between calls."""
+    pop = eng2.pop_index(eng2.peer_index(resident), *spec)
+    kw = {k: v for k, v in (rules or {}).items() if k in ("allow", "exclude")}
+    return eng2.fill(lists, pop, P, d_q, item_avg, keep_held=keep_held, **kw)
+
+
+def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_held, ctx, rules=None, diverse=None, fill=None):
     """what recommend_topn and recommend_topn_profiles share: the lists of the user indices `query` of P, labelled `uids` -> the
-    LocalRDD of (uid, [(iid, plain, decayed)*]) with .stats; rules = _eligibility(...), diverse = _diverse(...)"""
+    LocalRDD of (uid, [(iid, plain, decayed)*]) with .stats; rules = _eligibility(...), diverse = _diverse(...), fill = None or
+    (_fill_spec(...), the resident profiles): the stages run rules -> pool -> diversify -> fill"""
     import torch
     idt, dev = st.idt, st.engine.dev
     d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
     cnt, item, plain, decayed, stats, ils, div_stats = _topn_lists(eng2, P, nb, d_q, item_avg, alpha, n, decay, keep_held, dev, rules, diverse)
+    src = fill_stats = None
+    if fill:
+        cnt, item, plain, decayed, src, fill_stats = _fill_lists(eng2, fill[1], P, d_q, item_avg, (cnt, item, plain, decayed), fill[0],
+                                                                 keep_held, rules)
     cnt, item, plain, decayed = cnt.cpu().numpy(), item.cpu().numpy(), plain.cpu().numpy(), decayed.cpu().numpy()
     iids = idt.iids
     out = [(uid, [(iids[item[q, t]], float(plain[q, t]), float(decayed[q, t])) for t in range(cnt[q])]) for q, uid in enumerate(uids)]
@@ -588,6 +639,9 @@ def _topn_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, decay, keep_
     res.stats = stats
     if diverse:
         res.ils, res.div_stats = [float(x) for x in ils.cpu().numpy()], div_stats
+    if fill:
+        src = src.cpu().numpy()
+        res.sources, res.fill_stats = [[int(x) for x in src[q, :cnt[q]]] for q in range(len(uids))], fill_stats
     return res
 
 
@@ -713,7 +767,7 @@ def _fold_in(st, G, profiles):
 
 
 def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=False, keep_held=False, neighbors=None, explain=None,
-                            allow_items=None, exclude=None, min_score=None, diversify=None, pool=None):
+                            allow_items=None, exclude=None, min_score=None, diversify=None, pool=None, fill=None):
     """recommend_topn for users that are not rows of the train set -- a user who arrived after training, a trained user whose
     profile changed: `profiles` is an RDD or list of (uid, [(iid, rating, time)*]) raw profiles, source and target items mixed.
     Each gets its AlterEgo profile with the replacement map behind alterEgoRDD (fold-in: Engine.foldin_profiles) and then the
@@ -723,15 +777,18 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     recommend_topn in the order of `profiles`, with .stats, .sim_pairs, .item_info, .unknown_items and .counts = (AlterEgo rows,
     pass-through rows, profiles with a row).  explain as recommend_topn takes it: the sources are then entries of the profile
     passed in (its iid, rating and time objects).  allow_items, exclude = {uid of a profile: iids}, min_score: the eligibility
-    rules of recommend_topn.  diversify, pool: the diversified lists of recommend_topn, with .ils and .div_stats."""
+    rules of recommend_topn.  diversify, pool: the diversified lists of recommend_topn, with .ils and .div_stats.  fill: the
+    popularity fill of recommend_topn, with .sources and .fill_stats: what a profile holds is its own (folded-in) rows, what is
+    popular is taken over the resident users."""
     _no_fold_in(alterEgoRDD, "recommend_topn_profiles")
     _diverse(n, diversify, pool)
-    st, eng2, _, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn_profiles")
+    spec = _fill_spec(fill)
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_topn_profiles")
     F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
     uids = sorted(index, key=index.get)
     res = _topn_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, n, decay, keep_held, getattr(profiles, "ctx", None),
                         _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score),
-                        _diverse(n, diversify, pool, eng2, S))
+                        _diverse(n, diversify, pool, eng2, S), (spec, P) if spec else None)
     res.unknown_items, res.counts = unknown, F.counts
     _tail_dicts(res, st, S, nb)
     if explain is not None:
@@ -1232,6 +1289,24 @@ def related_items(alterEgoRDD, baskets, cap, n, how="sum", keep_members=False, m
     return res
 
 
+def popular_items(alterEgoRDD, cap, n, how="count", damping=0.0, min_count=1):
+    """The most popular / best rated items of the resident profiles, on the device: the shelf an anonymous visitor sees, with no
+    user, no evidence and no model.  The profiles of the AlterEgo rows, their item-major transposition (Engine.peer_index) and the
+    ranking over it (Engine.pop_index): how="count" ranks by the profiles that hold an item, "mean" by (sum of its ratings +
+    damping * the mean of all ratings) / (holders + damping); an item with fewer than min_count holders is not ranked; score
+    descending, item index ascending on equal scores.  Returns [(iid, score)*], the first n of the ranking (fewer when it is
+    shorter).  cap is taken for the symmetry of the tail calls; the ranking needs no RecommenderSim and does not depend on it.
+    Takes an AlterEgoRDD or an AlterEgoUnion."""
+    spec = _fill_spec(dict(how=how, damping=damping, min_count=min_count))
+    if int(n) < 0:
+        raise ValueError("n = %d: at least 0" % int(n))
+    st, eng2, P = _tail_profiles(alterEgoRDD, "popular_items")
+    pop = eng2.pop_index(eng2.peer_index(P), *spec)
+    m = min(int(n), pop.n_ranked)
+    item, score = pop.item[:m].cpu().numpy(), pop.score[:m].cpu().numpy()
+    return [(st.idt.iids[int(i)], float(v)) for i, v in zip(item, score)]
+
+
 def _item_fold_in(st, eng2, P, S, nb, item_avg, new_items):
     """new items [(iid, [(uid, rating)*])*] (an RDD or a list) -> (their RecommenderSim rows: Engine.item_foldin against the
     profiles P with the norms and the cap of S, the extended tables of Engine.item_foldin_tables, {iid: index in the batch},
@@ -1338,7 +1413,7 @@ class TopnEvaluation(object):
 
 
 def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20), rel_min=4.0, decay=False, keep_held=False,
-                  neighbors=None, diversify=None, pool=None):
+                  neighbors=None, diversify=None, pool=None, fill=None):
     """Hold-out evaluation of the top-N recommendation on the device: the set-up of recommend, then the held-out pairs of
     testRDD ((uid, [(iid, rating, ...)*]) records as recommend takes them, every (uid, iid) once) pick the users with a rating
     >= rel_min (Engine.eval_users), those users get their n best items (Engine.topn: recommend_topn's lists), and the lists
@@ -1351,12 +1426,16 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     repeated (uid, iid) or a rating that is not a number.
     diversify, pool as recommend_topn takes them: the lists that are scored are the re-ranked ones, and .ils is the mean intra-list
     similarity over the evaluated users (summed on the host from the per-user values; 0.0 without users), so one call per weight
-    gives the accuracy / redundancy curve -- diversify = 0 the redundancy of the plain lists."""
+    gives the accuracy / redundancy curve -- diversify = 0 the redundancy of the plain lists.
+    fill as recommend_topn takes it: the lists that are scored are the completed ones (the same lists, filled in place on the
+    device, go to Engine.topn_eval), and the result carries .fill_stats -- one call with and one without shows what the fill buys
+    in recall and coverage."""
     import torch
     if not isinstance(alterEgoRDD, (AlterEgoRDD, AlterEgoUnion)):
         raise TypeError("evaluate_topn() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device) or the "
                         "AlterEgoUnion of union_alterego")
     _diverse(n, diversify, pool)
+    spec = _fill_spec(fill)
     recs = records_of(testRDD)
     seen = set()
     for uid, pairs in recs:
@@ -1379,8 +1458,11 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     d_tu, d_ti, d_tr = torch.from_numpy(tu).to(dev), torch.from_numpy(ti).to(dev), torch.from_numpy(real).to(dev)
     U, I = len(idt.uids), len(idt.iids)
     n_rel, users, counts = eng2.eval_users(d_tu, d_ti, d_tr, float(rel_min), U, I)
-    cnt, item, _, _, stats, ils, _ = _topn_lists(eng2, P, nb, users, item_avg, alpha, n, decay, keep_held, dev, None,
-                                                 _diverse(n, diversify, pool, eng2, S))
+    cnt, item, plain, decayed, stats, ils, _ = _topn_lists(eng2, P, nb, users, item_avg, alpha, n, decay, keep_held, dev, None,
+                                                           _diverse(n, diversify, pool, eng2, S))
+    fill_stats = None
+    if spec:
+        cnt, item, _, _, _, fill_stats = _fill_lists(eng2, P, P, users, item_avg, (cnt, item, plain, decayed), spec, keep_held, None)
     mask, _, agg, cover = eng2.topn_eval(d_tu, d_ti, d_tr, float(rel_min), n_rel, users, cnt, item, cuts, I)
     res = TopnEvaluation()
     agg, cover = agg.cpu().numpy(), cover.cpu().numpy()
@@ -1391,6 +1473,8 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
                          recall=mean(float(agg[k, 4])), ndcg=mean(float(agg[k, 5])), map=mean(float(agg[k, 6])),
                          mrr=mean(float(agg[k, 7])), coverage=int(cover[k]))
     res.stats = tuple(counts) + tuple(stats)
+    if spec:
+        res.fill_stats = fill_stats
     if ils is not None:
         v = ils.cpu().numpy()
         res.ils = math.fsum(v.tolist()) / len(v) if len(v) else 0.0
