@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW] [--hybrid W]]
 
 --user-based: the recommender stages with the user method of the reference's egg (calculate_xmap_sim_method = cosine_user): the
 similarity between the users' AlterEgo profiles with its local sensitivity on the device (xmap.engine.session.UserSimRDD), the
@@ -57,6 +57,12 @@ test user with few AlterEgo rows gets a short list and one without any an empty 
 (xmap.engine.session.recommend_topn / evaluate_topn with fill=HOW: short lists completed with the most held / best rated items
 the user does not hold), the share of short lists, the share of empty lists, recall@10 and the items covered, and the head of the
 ranking itself (popular_items).
+
+--hybrid W (with --device-tail): the item-based and the user-based recommender voting together -- every test user's 64 best items
+by their own rows and the 64 best items their 50 nearest users rate highest are fused on the device by reciprocal rank, the
+user-based half weighted W (xmap.engine.session.recommend_hybrid: neither list leaves the device).  The run prints the ranking
+metrics of the plain and of the hybrid top-10 lists side by side (evaluate_topn with hybrid=...), and for three test users the five
+fused items with the half that named each.
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -151,6 +157,7 @@ def main(argv=None):
     ap.add_argument("--user-knn", type=int, default=None, metavar="K")
     ap.add_argument("--related", type=int, default=None, metavar="N")
     ap.add_argument("--fill", default=None, choices=["count", "mean"], metavar="HOW")
+    ap.add_argument("--hybrid", type=float, default=None, metavar="W")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -194,6 +201,8 @@ def main(argv=None):
         ap.error("--related N needs --device-tail and 1 <= N <= 1024")
     if args.fill is not None and (not args.device_tail or para["recommender"]["private_flag"]):
         ap.error("--fill HOW needs --device-tail and the non-private recommender")
+    if args.hybrid is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 0.0 <= args.hybrid < float("inf")):
+        ap.error("--hybrid W needs --device-tail, the non-private recommender and a finite W >= 0")
     if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
         ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
@@ -373,6 +382,23 @@ def main(argv=None):
                 100.0 * sum(not l for _, l in lists) / max(len(lists), 1), ev.at[10]["recall"], ev.at[10]["coverage"]))
         shelf = session.popular_items(alterEgo_profile, w, 5, **(dict(how="count") if args.fill == "count" else spec))
         print("  the shelf of an anonymous visitor:", ", ".join("%s (%.3f)" % e for e in shelf))
+    if args.hybrid is not None:
+        # the item-based and the user-based lists fused on the device: what the vote of the two buys, and who named what
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        hyb = dict(n_nb=50, peer_cap=5, min_common=2, own_mean=True, how="rrf", weights=(1.0, args.hybrid))
+        print("hybrid (RRF, user-based half weighted %g): lists of 10" % args.hybrid)
+        print("  %-8s %10s %10s %10s %10s %10s" % ("", "hit rate", "recall@10", "NDCG@10", "MAP", "coverage"))
+        for name, spec in (("plain", None), ("hybrid", hyb)):
+            ev = timed("hybrid_eval_" + name, session.evaluate_topn, alterEgo_profile, testRDD, w, k, alpha, 10, cutoffs=(10,), rel_min=4.0,
+                       hybrid=spec)
+            m = ev.at[10]
+            print("  %-8s %10.4f %10.4f %10.4f %10.4f %10d" % (name, m["hit_rate"], m["recall"], m["ndcg"], m["map"], m["coverage"]))
+        fused = timed("hybrid_topn", session.recommend_hybrid, alterEgo_profile, [uid for uid, _ in testRDD.take(3)], w, k, alpha, 5,
+                      hyb["n_nb"], **{key: v for key, v in hyb.items() if key != "n_nb"})
+        print("  %d candidates of %d records; %d item-based and %d user-based candidates went in" % (
+            fused.stats[2][0], fused.stats[2][4], fused.stats[0][0], fused.stats[1][0]))
+        for uid, lst in fused.collect():
+            print("hybrid top 5 for %s:" % uid, ", ".join("%s (%.4f, %s)" % (iid, s, "+".join(which)) for iid, s, which in lst) or "no evidence")
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

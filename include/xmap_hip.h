@@ -1145,6 +1145,53 @@ int xmap_related_rows(void *stream, int64_t n_query, const int64_t *b_ptr /*[n_q
                       int32_t *out_cnt, int32_t *out_item, double *out_score, int32_t *out_support,
                       const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [6] or NULL */);
 
+/* ---- fused lists (csrc/stage_e_fuse.hip; DESIGN.md 4 "Fused lists"): several lists of the same queries -- item-kNN, user-kNN,
+ * related items, one list per source domain -- become one list per query, by rank (reciprocal rank fusion) or by score (weighted
+ * sum, weighted mean).  All arithmetic is fp64, one rounded operation per step, no fused multiply-add; the divisions are IEEE.
+ * The lists: n_lists (1 .. XMAP_FUSE_MAX_LISTS) of xmap_fuse_list, a host array with device pointers inside: cnt [n_query], item
+ *   [n_query][width], score beside it (may be NULL with XMAP_FUSE_RRF), width in 1 .. 1024 (the row stride), weight finite, any
+ *   sign.  Row q of every list belongs to the same query.  The ids are just ids in [0, n_ids): items for top-N lists, users for
+ *   audiences or peers.  Lists may alias each other; outputs may not alias inputs.
+ * Records of query q: for l = 0 .. n_lists - 1, for r = 0 .. m - 1 with m = min(max(cnt_l[q], 0), width_l): if id = item_l[q][r]
+ *   lies in [0, n_ids), the record (id, l, r).  An id a list holds twice gives two records.
+ * Term of a record: XMAP_FUSE_RRF: t = w_l / (rrf_c + (double)(r + 1)); XMAP_FUSE_SUM and XMAP_FUSE_MEAN: t = fl(w_l * score_l[q][r]).
+ * Score of an id, over its records in record order (l ascending, then r ascending): num from 0.0 left to right over t, den from
+ *   0.0 left to right over w_l, mask |= 1 << l.  RRF and SUM give num, MEAN gives num / den.
+ * Rules, in this order: (1) the candidates are the ids with a record; (2) popcount(mask) < min_lists (1 .. n_lists): dropped,
+ *   counted; (3) a score that is not finite (an inf or NaN input score, den == 0.0): dropped, counted; (4) selection by score
+ *   descending as numbers (-0.0 equals 0.0), id ascending on equal scores.
+ * Outputs (device): out_cnt [n_query]; out_id / out_score / out_lists [n_query][n_top] hold the id, the score's own bits and the
+ *   mask, with -1 / 0.0 / 0 behind the count; 1 <= n_top <= 1024.  h_stats (host, [5] or NULL): [0] candidates, [1] dropped by
+ *   min_lists, [2] dropped as non-finite, [3] the largest candidate count of one query, [4] records.  A pure function of the
+ *   inputs: it depends on neither the grid, nor the chunking, nor which of the two routes below ran.
+ * Two routes, chosen from W = the sum of the widths alone:
+ *   W <= XMAP_FUSE_BLOCK_RECORDS: one workgroup per query, launched in ranges below 2^32 threads, keeps the query's records in
+ *     LDS from the first load to the selected list: keys id << 14 | l << 10 | r (distinct, so the bitonic network sorts them
+ *     stably), run heads by comparing neighbours, the head lane walks its run, a second network on (score key, position).  The
+ *     networks span the power of two at or above the entries the query offers (at least 128), whatever the widths.  No global
+ *     temporaries, no host decision between load and store.
+ *   otherwise: record counts per (query, list) -> scan -> chunks of consecutive queries of at most max_records records (0: the
+ *     library's default, 2^22; a single query above that is a chunk of its own) -> expansion in (l, r) order -> stable radix sort
+ *     on (q - q0) << id_bits | id -> run heads -> scan -> one lane per run -> segmented selection.  Temporaries from the stream's
+ *     arena: 56 B per record of the largest chunk, 12 B per (query, list) and 8 B per query.
+ * n_lists, every width, weight and pointer, how, rrf_c (finite, >= 0), min_lists, n_top, n_ids, max_records and n_query (<= 2^28)
+ *   are checked on the host before any device work, each check naming its argument: on XMAP_ERR_ARG nothing is written.  Syncs. */
+#define XMAP_FUSE_RRF 0
+#define XMAP_FUSE_SUM 1
+#define XMAP_FUSE_MEAN 2
+#define XMAP_FUSE_MAX_LISTS 16
+#define XMAP_FUSE_BLOCK_RECORDS 2048
+typedef struct {
+    const int32_t *cnt;       /* [n_query] */
+    const int32_t *item;      /* [n_query][width] */
+    const double *score;      /* [n_query][width]; may be NULL with XMAP_FUSE_RRF */
+    int32_t width;            /* 1 .. 1024: the row stride */
+    double weight;            /* finite, any sign */
+} xmap_fuse_list;
+int xmap_fuse_rows(void *stream, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists /* host array, device pointers inside */,
+                   int32_t n_ids, int32_t how, double rrf_c, int32_t min_lists, int32_t n_top, int64_t max_records /*0: library default*/,
+                   int32_t *out_cnt, int32_t *out_id, double *out_score, int32_t *out_lists, int64_t *h_stats /* host, [5] or NULL */);
+
 /* ---- popularity fill (csrc/stage_e_fill.hip; DESIGN.md 4 "Popularity fill"): a ranking of the items by popularity, and the
  * completion of short top-N lists with its head.  Every other list of the tail is cut from candidates with evidence; these two
  * calls answer when there is none (a user without rows, a one-rating fold-in, a 1 % mask, the anonymous visitor).
@@ -1574,6 +1621,33 @@ int xmap_ctx_recommend_filled(xmap_ctx *ctx, int32_t source, int64_t n_query, co
                               int32_t min_count, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
                               int32_t *out_src, const xmap_rec_filter *F /* host pointers inside, or NULL */,
                               int64_t *stats /* [10] or NULL */);
+/* Fused lists: xmap_fuse_rows with host arrays in and out.
+ *   xmap_ctx_fuse : lists holds HOST pointers (cnt [n_query], item / score [n_query][width]); they are uploaded, fused with the
+ *                   library's default max_records, and out_cnt [n_query], out_id / out_score / out_lists [n_query][n_top] and
+ *                   stats ([5] or NULL, the h_stats of xmap_fuse_rows) come back.  The context is used for its device and stream
+ *                   only: no stage needs to have run.  The host checks of xmap_fuse_rows are made before the context is read: a
+ *                   NULL context with good arguments fails on the context check alone.
+ *   xmap_ctx_recommend_hybrid : the item-based and the user-based lists of the same query users, fused.  List 0 is what
+ *                   xmap_ctx_recommend_filtered returns with n_top = n_pool_items (1 .. 64): the score of rank_by (0 plain, 1
+ *                   decayed), with wtab / n_w and topn_flags.  List 1 is what xmap_ctx_uknn_recommend returns with n_top =
+ *                   n_pool_users (1 .. 1024), given n_nb, peer_flags, cap, min_common, uknn_flags and min_support.  The one F
+ *                   acts on both halves (the mask and the exclusion ids are ITEMS).  Both lists stay in device temporaries and
+ *                   are fused with w_items, w_users, how, rrf_c, min_lists (1 .. 2) over n_ids = the context's items.  Sources:
+ *                   XMAP_SRC_RESIDENT (also on a union context) and XMAP_SRC_FOLDIN; XMAP_SRC_ITEM_FOLDIN is XMAP_ERR_ARG, as in
+ *                   the user-kNN calls.  Needs what both calls need.  stats ([17] or NULL): the six of
+ *                   xmap_ctx_recommend_filtered, the six of xmap_ctx_uknn_recommend, the five of xmap_fuse_rows.  Defined as
+ *                   equal, byte for byte, to calling the three public coarse calls one after the other.
+ * Every argument is checked on the host before the context is read, each check naming its argument: on XMAP_ERR_ARG the outputs
+ * keep every byte. */
+int xmap_ctx_fuse(xmap_ctx *ctx, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists /* host pointers inside */,
+                  int32_t n_ids, int32_t how, double rrf_c, int32_t min_lists, int32_t n_top, int32_t *out_cnt, int32_t *out_id,
+                  double *out_score, int32_t *out_lists, int64_t *stats /* [5] or NULL */);
+int xmap_ctx_recommend_hybrid(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top,
+                              int32_t n_pool_items, int32_t rank_by, int32_t topn_flags, const double *wtab, int32_t n_w,
+                              int32_t n_pool_users, int32_t n_nb, int32_t peer_flags, int32_t cap, int32_t min_common,
+                              int32_t uknn_flags, int32_t min_support, double w_items, double w_users, int32_t how, double rrf_c,
+                              int32_t min_lists, const xmap_rec_filter *F /* host pointers inside, or NULL */, int32_t *out_cnt,
+                              int32_t *out_item, double *out_score, int32_t *out_lists, int64_t *stats /* [17] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

@@ -1820,6 +1820,120 @@ int xmap_ctx_recommend_filled(xmap_ctx *c, int32_t source, int64_t n_query, cons
     return XMAP_OK;
 }
 
+// ---- fused lists: xmap_fuse_rows over uploaded lists, and the item-based and user-based lists of the same users fused -------------
+
+int xmap_ctx_fuse(xmap_ctx *c, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists, int32_t n_ids, int32_t how, double rrf_c,
+                  int32_t min_lists, int32_t n_top, int32_t *out_cnt, int32_t *out_id, double *out_score, int32_t *out_lists,
+                  int64_t *stats) {
+    // the host checks: before the context is read, the outputs untouched
+    XM_TRY(fuse_check("xmap_ctx_fuse", n_query, n_lists, lists, n_ids, how, rrf_c, min_lists, n_top, 0, out_cnt, out_id, out_score, out_lists));
+    XM_ARG(c);
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 5; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    ScratchPool tmp;
+    xmap_fuse_list D[XMAP_FUSE_MAX_LISTS];
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top;
+    for (int l = 0; l < n_lists; l++) {
+        const size_t ml = n * (size_t)lists[l].width;
+        int32_t *d_c, *d_i;
+        double *d_s = nullptr;
+        XM_TRY(h2d(tmp, &d_c, lists[l].cnt, n, c->st));
+        XM_TRY(h2d(tmp, &d_i, lists[l].item, ml, c->st));
+        if (lists[l].score) XM_TRY(h2d(tmp, &d_s, lists[l].score, ml, c->st));
+        D[l].cnt = d_c; D[l].item = d_i; D[l].score = d_s; D[l].width = lists[l].width; D[l].weight = lists[l].weight;
+    }
+    int32_t *d_cnt, *d_id, *d_lists;
+    double *d_score;
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_id, m, c->st));
+    XM_TRY(dalloc(tmp, &d_score, m, c->st)); XM_TRY(dalloc(tmp, &d_lists, m, c->st));
+    XM_TRY(xmap_fuse_rows(c->st, n_query, n_lists, D, n_ids, how, rrf_c, min_lists, n_top, 0, d_cnt, d_id, d_score, d_lists, stats));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_id, (const int32_t *)d_id, m, c->st));
+    XM_TRY(d2h(out_score, (const double *)d_score, m, c->st));
+    XM_TRY(d2h(out_lists, (const int32_t *)d_lists, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
+int xmap_ctx_recommend_hybrid(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t n_pool_items,
+                              int32_t rank_by, int32_t topn_flags, const double *wtab, int32_t n_w, int32_t n_pool_users, int32_t n_nb,
+                              int32_t peer_flags, int32_t cap, int32_t min_common, int32_t uknn_flags, int32_t min_support, double w_items,
+                              double w_users, int32_t how, double rrf_c, int32_t min_lists, const xmap_rec_filter *F, int32_t *out_cnt,
+                              int32_t *out_item, double *out_score, int32_t *out_lists, int64_t *stats) {
+    // the host checks: before the context is read or any device work is done, the outputs untouched
+    XM_ARG(n_top >= 1 && n_top <= 1024);
+    XM_ARG(n_pool_items >= 1 && n_pool_items <= 64);
+    XM_ARG(rank_by == 0 || rank_by == 1);
+    XM_ARG((topn_flags & ~XMAP_TOPN_KEEP_HELD) == 0);
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_pool_users >= 1 && n_pool_users <= 1024);
+    XM_ARG(n_nb >= 1 && n_nb <= 1024);
+    XM_ARG((peer_flags & ~(XMAP_PEERS_KEEP_SELF | XMAP_PEERS_CENTRED)) == 0);
+    XM_ARG(cap >= 1);
+    XM_ARG(min_common >= 1);
+    XM_ARG((uknn_flags & ~(XMAP_UKNN_OWN_MEAN | XMAP_UKNN_KEEP_HELD)) == 0);
+    XM_ARG(min_support >= 1);
+    XM_ARG(w_items >= -1.7976931348623157e308 && w_items <= 1.7976931348623157e308);       // finite (a NaN fails both)
+    XM_ARG(w_users >= -1.7976931348623157e308 && w_users <= 1.7976931348623157e308);
+    XM_ARG(how == XMAP_FUSE_RRF || how == XMAP_FUSE_SUM || how == XMAP_FUSE_MEAN);
+    XM_ARG(rrf_c >= 0.0 && rrf_c <= 1.7976931348623157e308);        // finite and >= 0
+    XM_ARG(min_lists >= 1 && min_lists <= 2);
+    XM_ARG(source == XMAP_SRC_RESIDENT || source == XMAP_SRC_FOLDIN);       // an item fold-in adds items, not users
+    XM_ARG(n_query >= 0 && n_query <= (1ll << 28) && (n_query == 0 || (query_user && out_cnt && out_item && out_score && out_lists)));
+    XM_ARG(n_query * (int64_t)n_nb < 2147483647ll);
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 17; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    const Profiles P = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const Tables T = resident_tables(c);
+    ScratchPool tmp;
+    const size_t n = (size_t)n_query, mi = n * (size_t)n_pool_items, mu = n * (size_t)n_pool_users, m = n * (size_t)n_top;
+    // ---- list 0: the filtered item-kNN top-N, as xmap_ctx_recommend_filtered runs it
+    int32_t *d_user, *i_cnt, *i_item;
+    double *d_w, *i_plain, *i_decay;
+    XM_TRY(h2d(tmp, &d_user, query_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &i_cnt, n, c->st)); XM_TRY(dalloc(tmp, &i_item, mi, c->st));
+    XM_TRY(dalloc(tmp, &i_plain, mi, c->st)); XM_TRY(dalloc(tmp, &i_decay, mi, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+    int64_t h6[6] = {0, 0, 0, 0, 0, 0}, u6[6] = {0, 0, 0, 0, 0, 0}, f5[5] = {0, 0, 0, 0, 0};
+    XM_TRY(topn_rows(c->st, n_query, d_user, n_pool_items, rank_by, topn_flags, rec_model(P, T, d_w, n_w), i_cnt, i_item, i_plain, i_decay, &D,
+                     h6, 6));
+    // ---- list 1: the user-kNN top-N, as xmap_ctx_uknn_recommend runs it
+    UknnLists L;
+    XM_TRY(uknn_lists(c, tmp, source, n_query, query_user, n_nb, peer_flags, cap, min_common, &L));
+    int32_t *u_cnt, *u_item, *u_support;
+    double *u_score;
+    XM_TRY(dalloc(tmp, &u_cnt, n, c->st)); XM_TRY(dalloc(tmp, &u_item, mu, c->st));
+    XM_TRY(dalloc(tmp, &u_score, mu, c->st)); XM_TRY(dalloc(tmp, &u_support, mu, c->st));
+    XM_TRY(xmap_uknn_topn_rows(c->st, n_query, L.query, L.Q.n_users, L.Q.ptr, L.Q.item, L.query_avg, n_nb, L.cnt, L.user, L.sim, c->R.n_users,
+                               c->R.n_items, c->pf_ptr, c->pf_item, c->pf_rating, L.user_avg, uknn_flags, n_pool_users, min_support, 0, u_cnt,
+                               u_item, u_score, u_support, &D, u6));
+    // ---- the fuse
+    const xmap_fuse_list lists[2] = {{i_cnt, i_item, rank_by ? i_decay : i_plain, n_pool_items, w_items},
+                                     {u_cnt, u_item, u_score, n_pool_users, w_users}};
+    int32_t *d_cnt, *d_id, *d_lists;
+    double *d_score;
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_id, m, c->st));
+    XM_TRY(dalloc(tmp, &d_score, m, c->st)); XM_TRY(dalloc(tmp, &d_lists, m, c->st));
+    XM_TRY(xmap_fuse_rows(c->st, n_query, 2, lists, c->R.n_items, how, rrf_c, min_lists, n_top, 0, d_cnt, d_id, d_score, d_lists, f5));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_id, m, c->st));
+    XM_TRY(d2h(out_score, (const double *)d_score, m, c->st));
+    XM_TRY(d2h(out_lists, (const int32_t *)d_lists, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    if (stats) {
+        for (int k = 0; k < 6; k++) { stats[k] = h6[k]; stats[6 + k] = u6[k]; }
+        for (int k = 0; k < 5; k++) stats[12 + k] = f5[k];
+    }
+    return XMAP_OK;
+}
+
 // ---- explanations -------------------------------------------------------------------------------------------------------
 
 // the raw profiles a set of AlterEgo profiles was made from, with the count (or the scan) of each profile's pass-through rows

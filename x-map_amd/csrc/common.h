@@ -74,6 +74,11 @@ int radix_sort_pairs(hipStream_t st, unsigned long long *keys, int *vals, unsign
 // stage_e_uknn.hip: out[k] = src[sel[k]], 0.0 for an index outside [0, n_src) -- the query means of the coarse user-kNN calls
 int uknn_gather(hipStream_t st, long long n, const int *sel, long long n_src, const double *src, double *out);
 
+// stage_e_fuse.hip: the host checks of xmap_fuse_rows, shared with xmap_ctx_fuse: each names its argument; nothing is written
+int fuse_check(const char *who, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists, int32_t n_ids, int32_t how, double rrf_c,
+               int32_t min_lists, int32_t n_top, int64_t max_records, const void *out_cnt, const void *out_id, const void *out_score,
+               const void *out_lists);
+
 constexpr int WAVE = 64;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -5,6 +5,7 @@ computation on the path is a kernel of libxmap_hip.so.  All results stay residen
 torch tensors until a caller asks for host copies.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -2241,7 +2242,73 @@ class Engine(object):
         del alive
         return out_cnt[:n_q], out_item[:n_q], out_score[:n_q], out_support[:n_q], tuple(int(x) for x in h)
 
-    def explain(self, P, neighbors, pair_user, pair_item, item_avg, wtab, n_ev, rank_by=0):
+    @staticmethod
+    def _fuse_args(n_lists, n_top, how, weights, rrf_c, min_lists):
+        """the argument checks fuse() and session.fuse_lists share; returns the weights as floats"""
+        n_top = int(n_top)
+        if not 1 <= n_lists <= abi.FUSE_MAX_LISTS:
+            raise ValueError("lists: %d of them, 1 .. %d are fused" % (n_lists, abi.FUSE_MAX_LISTS))
+        if how not in abi.FUSE_HOW:
+            raise ValueError("how = %r: one of %s" % (how, sorted(abi.FUSE_HOW)))
+        if not 1 <= n_top <= 1024:
+            raise ValueError("n_top = %d: the device selection takes 1 .. 1024" % n_top)
+        w = [1.0] * n_lists if weights is None else [float(x) for x in weights]
+        if len(w) != n_lists:
+            raise ValueError("weights: one per list (%d)" % n_lists)
+        if not all(math.isfinite(x) for x in w):
+            raise ValueError("weights = %r: finite" % (w,))
+        if not (math.isfinite(float(rrf_c)) and float(rrf_c) >= 0.0):
+            raise ValueError("rrf_c = %r: finite and >= 0" % (rrf_c,))
+        if not 1 <= int(min_lists) <= n_lists:
+            raise ValueError("min_lists = %r: 1 .. %d" % (min_lists, n_lists))
+        return w
+
+    def fuse(self, lists, n_top, how="rrf", weights=None, rrf_c=60.0, min_lists=1, n_ids=None, max_records=0):
+        """Fused lists on the device (xmap_fuse_rows): lists is a sequence of (cnt int32 [Q], item int32 [Q][width], score float64
+        [Q][width] or None, ...) device tensors -- the leading members of what topn(), uknn_topn(), related(), diversify() and
+        group_topn() return; row q of every list belongs to the same query.  An id's records are its entries in the lists, list
+        after list, rank after rank.  how = "rrf": the sum of weight / (rrf_c + rank) over them (ranks from 1; the scores may be
+        None); "sum": the sum of weight * score; "mean": that sum / the sum of the weights.  An id in fewer than min_lists lists
+        or with a score that is not finite is dropped; score descending, id ascending.  weights: one per list (None: 1.0 each),
+        finite, any sign.  n_ids: the ids are those in [0, n_ids) (None: the items of the engine's ratings).  Returns (cnt [Q],
+        id [Q][n_top] (-1 behind the count), score, lists [Q][n_top] (bit l: list l holds the id), stats) with stats =
+        (candidates, dropped by min_lists, dropped as non-finite, largest candidate count of a query, records).  (cnt, id) go
+        straight into topn_eval() when n_top <= 64.  max_records: the chunk bound of the long-list route (0: the library's)."""
+        lists = [tuple(x[:3]) if len(x) >= 3 else (x[0], x[1], None) for x in lists]
+        w = self._fuse_args(len(lists), n_top, how, weights, rrf_c, min_lists)
+        n_top = int(n_top)
+        n_q = int(lists[0][0].numel())
+        n_ids = int(self.R.n_items if n_ids is None else n_ids)
+        if n_ids < 0 or int(max_records) < 0:
+            raise ValueError("n_ids = %r, max_records = %r: >= 0" % (n_ids, max_records))
+        arr = (abi.FuseList * len(lists))()
+        alive = []
+        for l, (cnt, item, score) in enumerate(lists):
+            if cnt.dtype != torch.int32 or item.dtype != torch.int32 or int(cnt.numel()) != n_q:
+                raise ValueError("lists[%d] = (cnt int32 [%d], item int32 [%d][width], score float64 or None)" % (l, n_q, n_q))
+            width = int(item.shape[1]) if item.dim() == 2 else (int(item.numel()) // max(n_q, 1))
+            if not 1 <= width <= 1024 or int(item.numel()) != n_q * width:
+                raise ValueError("lists[%d]: item is [%d][width] with width 1 .. 1024" % (l, n_q))
+            if score is None and how != "rrf":
+                raise ValueError("lists[%d]: how = %r needs the scores" % (l, how))
+            if score is not None and (score.dtype != torch.float64 or int(score.numel()) != n_q * width):
+                raise ValueError("lists[%d]: score is float64 [%d][%d]" % (l, n_q, width))
+            cnt, item = cnt.contiguous(), item.contiguous()
+            score = None if score is None else score.contiguous()
+            alive.append((cnt, item, score))
+            arr[l] = abi.FuseList(cnt.data_ptr(), item.data_ptr(), None if score is None else score.data_ptr(), width, w[l])
+        out_cnt = self._empty(max(n_q, 1), torch.int32)
+        out_id, out_lists = self._empty((max(n_q, 1), n_top), torch.int32), self._empty((max(n_q, 1), n_top), torch.int32)
+        out_score = self._empty((max(n_q, 1), n_top), torch.float64)
+        h = (C.c_int64 * 5)()
+        with self.timed("fuse"):
+            check(lib.xmap_fuse_rows(_stream(self.dev), i64(n_q), i32(len(lists)), C.cast(arr, C.c_void_p), i32(n_ids),
+                                     i32(abi.FUSE_HOW[how]), C.c_double(float(rrf_c)), i32(min_lists), i32(n_top), i64(max_records),
+                                     vp(out_cnt), vp(out_id), vp(out_score), vp(out_lists), h))
+        del alive
+        return out_cnt[:n_q], out_id[:n_q], out_score[:n_q], out_lists[:n_q], tuple(int(x) for x in h)
+
+    def explain(self,P, neighbors, pair_user, pair_item, item_avg, wtab, n_ev, rank_by=0):
         """Why a pair scores what it scores (xmap_explain_rows, the pair body of predict() in its explain mode): for the (user,
         item) pairs -- int32 tensors, typically the lists of topn() -- the n_ev (1..16) strongest evidence entries of the
         unrounded score of rank_by (0 plain, 1 decayed), ranked by |share| descending, evidence order on ties.  P, neighbors,

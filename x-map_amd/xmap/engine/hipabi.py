@@ -31,6 +31,10 @@ RELATED_HOW = {"sum": RELATED_SUM, "mean": RELATED_MEAN, "max": RELATED_MAX}
 POP_COUNT, POP_MEAN = 0, 1      # XMAP_POP_*: `how` of xmap_pop_index / xmap_ctx_popular / xmap_ctx_recommend_filled
 FILL_WINDOW = 4096        # XMAP_FILL_WINDOW: rank positions one wave of xmap_topn_fill_rows marks at a time
 POP_HOW = {"count": POP_COUNT, "mean": POP_MEAN}
+FUSE_RRF, FUSE_SUM, FUSE_MEAN = 0, 1, 2      # XMAP_FUSE_*: `how` of xmap_fuse_rows / xmap_ctx_fuse / xmap_ctx_recommend_hybrid
+FUSE_MAX_LISTS = 16       # XMAP_FUSE_MAX_LISTS: lists of one fuse
+FUSE_BLOCK_RECORDS = 2048 # XMAP_FUSE_BLOCK_RECORDS: the sum of the widths up to which one workgroup fuses a query in LDS
+FUSE_HOW = {"rrf": FUSE_RRF, "sum": FUSE_SUM, "mean": FUSE_MEAN}
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -105,6 +109,11 @@ class RecFilter(C.Structure):
     _fields_ = [("allow", C.c_void_p), ("ex_ptr", C.c_void_p), ("ex_id", C.c_void_p), ("min_score", C.c_double)]
 
 
+class FuseList(C.Structure):
+    """xmap_fuse_list: one list of a fuse (device pointers for xmap_fuse_rows, host pointers for xmap_ctx_fuse)"""
+    _fields_ = [("cnt", C.c_void_p), ("item", C.c_void_p), ("score", C.c_void_p), ("width", C.c_int32), ("weight", C.c_double)]
+
+
 EXPORTS = [
     "xmap_last_error", "xmap_version", "xmap_trim", "xmap_debug_arena", "xmap_debug_arena_call", "xmap_debug_sort_pairs", "xmap_exclusive_scan_i64", "xmap_exclusive_scan_i32_to_i64",
     "xmap_exclusive_scan2_i32_to_i64", "xmap_scan_self_tiles", "xmap_sim3_plan_begin", "xmap_sim3_plan_wait", "xmap_sim3_counters_begin", "xmap_sim3_counters_wait",
@@ -130,6 +139,7 @@ EXPORTS = [
     "xmap_uknn_means", "xmap_uknn_predict_rows", "xmap_uknn_topn_rows", "xmap_ctx_uknn_predict", "xmap_ctx_uknn_recommend",
     "xmap_related_rows", "xmap_ctx_related",
     "xmap_pop_index", "xmap_topn_fill_rows", "xmap_ctx_popular", "xmap_ctx_recommend_filled",
+    "xmap_fuse_rows", "xmap_ctx_fuse", "xmap_ctx_recommend_hybrid",
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -1227,6 +1227,141 @@ def recommend_user_knn_profiles(alterEgoRDD, profiles, n_nb, n, cap=1, centred=T
     return res
 
 
+HYBRID_KEYS = ("n_nb", "peer_cap", "centred", "min_common", "own_mean", "min_support", "how", "weights", "rrf_c", "pool_items", "pool_users",
+               "min_lists")
+
+
+def _hybrid_spec(n, n_nb, peer_cap=1, centred=True, min_common=1, own_mean=False, min_support=1, how="rrf", weights=(1.0, 1.0), rrf_c=60.0,
+                 pool_items=64, pool_users=64, min_lists=1):
+    """the hybrid arguments of recommend_hybrid / evaluate_topn(hybrid=...), checked before any device work -> a dict of them"""
+    from . import device
+    device.Engine._fuse_args(2, n, how, weights, rrf_c, min_lists)
+    if not 1 <= int(pool_items) <= 64:
+        raise ValueError("pool_items = %r: the item-based list holds 1 .. 64" % (pool_items,))
+    if not 1 <= int(pool_users) <= 1024:
+        raise ValueError("pool_users = %r: the user-based list holds 1 .. 1024" % (pool_users,))
+    if not 1 <= int(n_nb) <= 1024:
+        raise ValueError("n_nb = %r: 1 .. 1024 neighbours" % (n_nb,))
+    if int(peer_cap) < 1 or int(min_common) < 1 or int(min_support) < 1:
+        raise ValueError("peer_cap = %r, min_common = %r, min_support = %r: >= 1" % (peer_cap, min_common, min_support))
+    return dict(n_nb=int(n_nb), peer_cap=int(peer_cap), centred=bool(centred), min_common=int(min_common), own_mean=bool(own_mean),
+                min_support=int(min_support), how=how, weights=tuple(float(w) for w in weights), rrf_c=float(rrf_c),
+                pool_items=int(pool_items), pool_users=int(pool_users), min_lists=int(min_lists))
+
+
+def _hybrid_lists(alterEgoRDD, who, st, eng2, Q, nb, item_avg, query, fold, alpha, n, decay, keep_held, rules, h):
+    """The item-based and the user-based list of the same queries, fused on the device: Engine.topn (pool_items) over the profiles Q
+    (the resident ones, or a folded-in batch with fold=True), Engine.uknn_topn (pool_users) over the peers of the same users,
+    Engine.fuse of (count, item, ranking score) of both.  query: a device tensor of indices into Q.  Returns (cnt, item, score,
+    mask, (top-N stats, user-kNN stats, fuse stats)); nothing is copied to the host."""
+    dev = st.engine.dev
+    it = _topn_lists(eng2, Q, nb, query, item_avg, alpha, h["pool_items"], decay, keep_held, dev, rules, None)
+    _, eng_u, Pu, X, means = _uknn_setup(alterEgoRDD, h["centred"], who)
+    q_host = query.cpu().tolist()
+    if fold:
+        d_q, peers, q_avg = _uknn_lists(st, eng_u, X, Q, eng_u.user_means(Q)[0], q_host, h["n_nb"], h["peer_cap"], h["min_common"], False)
+    else:
+        d_q, peers, q_avg = _uknn_lists(st, eng_u, X, Pu, means, q_host, h["n_nb"], h["peer_cap"], h["min_common"], True)
+    us = eng_u.uknn_topn(Pu, Q if fold else Pu, d_q, peers, q_avg, h["pool_users"], means, h["own_mean"], keep_held, h["min_support"],
+                         **(rules or {}))
+    cnt, item, score, mask, stats = eng2.fuse([(it[0], it[1], it[3] if decay else it[2]), us[:3]], int(n), h["how"], h["weights"], h["rrf_c"],
+                                              h["min_lists"], n_ids=len(st.idt.iids))
+    return cnt, item, score, mask, (tuple(it[4]), tuple(us[4]), stats)
+
+
+_WHICH = ((), ("item",), ("user",), ("item", "user"))
+
+
+def _hybrid_records(st, fused, labels, ctx):
+    cnt, item, score, mask = [x.cpu().numpy() for x in fused[:4]]
+    iids = st.idt.iids
+    res = LocalRDD([(lab, [(iids[item[q, t]], float(score[q, t]), _WHICH[mask[q, t] & 3]) for t in range(cnt[q])])
+                    for q, lab in enumerate(labels)], ctx)
+    res.stats = fused[4]
+    return res
+
+
+def recommend_hybrid(alterEgoRDD, users, cap, keep, alpha, n, n_nb, decay=False, keep_held=False, neighbors=None, allow_items=None,
+                     exclude=None, min_score=None, peer_cap=1, centred=True, min_common=1, own_mean=False, min_support=1, how="rrf",
+                     weights=(1.0, 1.0), rrf_c=60.0, pool_items=64, pool_users=64, min_lists=1):
+    """The usual hybrid on the device ("items my own ratings point to AND people like me rated highly"): for every uid of `users`
+    the pool_items (1..64) best items of recommend_topn (cap, keep, alpha, decay, keep_held, neighbors) and the pool_users (1..1024)
+    best items of recommend_user_knn (n_nb, peer_cap as its cap, centred, min_common, own_mean, min_support), fused into one list
+    of n (1..1024) by Engine.fuse: how = "rrf" (by rank: weight / (rrf_c + rank) summed), "sum" or "mean" (by score: the item-based
+    score is the plain prediction, or the decayed one with decay=True; the user-based score is its prediction), weights = (item
+    weight, user weight), min_lists = 2 keeps only the items both halves name.  allow_items, exclude, min_score act on both
+    halves.  Neither list leaves the device.  Returns a LocalRDD of (uid, [(iid, score, which)*]) in the order of `users`, which
+    = the halves that named the item, a subset of ("item", "user"); .stats = (the stats of recommend_topn, of recommend_user_knn,
+    of Engine.fuse)."""
+    import torch
+    h = _hybrid_spec(n, n_nb, peer_cap, centred, min_common, own_mean, min_support, how, weights, rrf_c, pool_items, pool_users, min_lists)
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_hybrid")
+    uids = list(users.collect()) if hasattr(users, "collect") else list(users)
+    uidx = _user_index(st.idt)
+    d_q = torch.from_numpy(np.fromiter((uidx.get(u, -1) for u in uids), np.int32, len(uids))).to(st.engine.dev)
+    rules = _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score)
+    fused = _hybrid_lists(alterEgoRDD, "recommend_hybrid", st, eng2, P, nb, item_avg, d_q, False, alpha, n, decay, keep_held, rules, h)
+    return _hybrid_records(st, fused, uids, getattr(users, "ctx", None))
+
+
+def recommend_hybrid_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, n_nb, decay=False, keep_held=False, neighbors=None,
+                              allow_items=None, exclude=None, min_score=None, peer_cap=1, centred=True, min_common=1, own_mean=False,
+                              min_support=1, how="rrf", weights=(1.0, 1.0), rrf_c=60.0, pool_items=64, pool_users=64, min_lists=1):
+    """recommend_hybrid for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them and folds them
+    in; both halves run over the folded-in profiles (recommend_topn_profiles and recommend_user_knn_profiles).  Returns the LocalRDD
+    of recommend_hybrid in the order of `profiles`, with .unknown_items and .counts.  exclude = {uid of a profile: iids}."""
+    import torch
+    _no_fold_in(alterEgoRDD, "recommend_hybrid_profiles")
+    h = _hybrid_spec(n, n_nb, peer_cap, centred, min_common, own_mean, min_support, how, weights, rrf_c, pool_items, pool_users, min_lists)
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_hybrid_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    labels = sorted(index, key=index.get)
+    d_q = torch.arange(len(labels), dtype=torch.int32, device=st.engine.dev)
+    rules = _eligibility(st.engine.dev, labels, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score)
+    fused = _hybrid_lists(alterEgoRDD, "recommend_hybrid_profiles", st, eng2, F, nb, item_avg, d_q, True, alpha, n, decay, keep_held, rules, h)
+    res = _hybrid_records(st, fused, labels, getattr(profiles, "ctx", None))
+    res.unknown_items, res.counts = unknown, F.counts
+    return res
+
+
+def fuse_lists(results, n, how="rrf", weights=None, rrf_c=60.0, min_lists=1, score_index=1, dev="cuda:0"):
+    """Late fusion of the lists of different calls -- recommend_topn, recommend_user_knn, related_items -- or of different AlterEgoRDD
+    handles over the same target items: one list per source domain, one weight each (the late counterpart of union_alterego, which
+    merges the rows before the model is built).  results: 1 .. 16 collected results [(label, [(iid, score, ...)*])*] (LocalRDDs or
+    lists) with the same labels in the same order; a list longer than 1 024 entries is cut there.  score_index: where an entry
+    holds its score (an int, or one per result; recommend_topn's decayed score is 2).  The iids of all results are numbered in
+    sorted order for the call, so equal scores come out in that order.  Engine.fuse does the rest on the device.  Returns a
+    LocalRDD of (label, [(iid, score, which)*]) with which = the indices of the results that named the iid, and .stats."""
+    import torch
+    from types import SimpleNamespace
+    from . import device
+    recs = [records_of(r) for r in results]
+    w = device.Engine._fuse_args(len(recs), n, how, weights, rrf_c, min_lists)
+    sidx = [int(score_index)] * len(recs) if isinstance(score_index, int) else [int(k) for k in score_index]
+    labels = [rec[0] for rec in recs[0]]
+    if len(sidx) != len(recs) or any([rec[0] for rec in r] != labels for r in recs):
+        raise ValueError("fuse_lists: one score_index per result, and every result lists the same labels in the same order")
+    ids = sorted({e[0] for r in recs for _, lst in r for e in lst})
+    index = {x: k for k, x in enumerate(ids)}
+    Q = len(labels)
+    lists = []
+    for r, k in zip(recs, sidx):
+        width = min(max([len(lst) for _, lst in r] + [1]), 1024)
+        cnt, item, score = np.zeros(max(Q, 1), np.int32), np.full((max(Q, 1), width), -1, np.int32), np.zeros((max(Q, 1), width), np.float64)
+        for q, (_, lst) in enumerate(r):
+            cnt[q] = min(len(lst), width)
+            for t, e in enumerate(lst[:width]):
+                item[q, t], score[q, t] = index[e[0]], e[k]
+        lists.append(tuple(torch.from_numpy(a).to(dev)[:Q] for a in (cnt, item, score)))
+    eng = device.Engine(SimpleNamespace(device=torch.device(dev), n_items=len(ids)))
+    cnt, item, score, mask, stats = eng.fuse(lists, int(n), how, w, rrf_c, min_lists, n_ids=len(ids))
+    cnt, item, score, mask = cnt.cpu().numpy(), item.cpu().numpy(), score.cpu().numpy(), mask.cpu().numpy()
+    res = LocalRDD([(lab, [(ids[item[q, t]], float(score[q, t]), tuple(l for l in range(len(recs)) if (mask[q, t] >> l) & 1))
+                           for t in range(cnt[q])]) for q, lab in enumerate(labels)], getattr(results[0], "ctx", None))
+    res.stats = stats
+    return res
+
+
 def related_items(alterEgoRDD, baskets, cap, n, how="sum", keep_members=False, min_support=1, allow_items=None, exclude=None,
                   min_score=None, map_sources=False):
     """Related items for a basket, on the device: "what goes with these items" -- the product page, the cart, an anonymous
@@ -1413,7 +1548,7 @@ class TopnEvaluation(object):
 
 
 def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20), rel_min=4.0, decay=False, keep_held=False,
-                  neighbors=None, diversify=None, pool=None, fill=None):
+                  neighbors=None, diversify=None, pool=None, fill=None, hybrid=None):
     """Hold-out evaluation of the top-N recommendation on the device: the set-up of recommend, then the held-out pairs of
     testRDD ((uid, [(iid, rating, ...)*]) records as recommend takes them, every (uid, iid) once) pick the users with a rating
     >= rel_min (Engine.eval_users), those users get their n best items (Engine.topn: recommend_topn's lists), and the lists
@@ -1429,8 +1564,20 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     gives the accuracy / redundancy curve -- diversify = 0 the redundancy of the plain lists.
     fill as recommend_topn takes it: the lists that are scored are the completed ones (the same lists, filled in place on the
     device, go to Engine.topn_eval), and the result carries .fill_stats -- one call with and one without shows what the fill buys
-    in recall and coverage."""
+    in recall and coverage.
+    hybrid = a dict of recommend_hybrid's extra arguments (n_nb, and any of peer_cap, centred, min_common, own_mean, min_support,
+    how, weights, rrf_c, pool_items, pool_users, min_lists): the lists that are scored are the fused ones of recommend_hybrid (n <=
+    64), and .stats carries the item-based half's counters; .hybrid_stats = (top-N, user-kNN, fuse).  Together with diversify or
+    fill it raises ValueError; None takes the path as it is without it."""
     import torch
+    if hybrid is not None:
+        if diversify is not None or pool is not None or fill is not None:
+            raise ValueError("evaluate_topn: hybrid together with diversify or fill")
+        if set(hybrid) - set(HYBRID_KEYS) or "n_nb" not in hybrid:
+            raise ValueError("hybrid = %r: a dict of n_nb and any of %s" % (hybrid, ", ".join(HYBRID_KEYS[1:])))
+        if not 1 <= int(n) <= 64:
+            raise ValueError("n = %d: the evaluation takes lists of 1 .. 64" % int(n))
+        hybrid = _hybrid_spec(n, **hybrid)
     if not isinstance(alterEgoRDD, (AlterEgoRDD, AlterEgoUnion)):
         raise TypeError("evaluate_topn() takes the AlterEgoRDD handle of generator_pipeline (rows resident on the device) or the "
                         "AlterEgoUnion of union_alterego")
@@ -1458,8 +1605,14 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     d_tu, d_ti, d_tr = torch.from_numpy(tu).to(dev), torch.from_numpy(ti).to(dev), torch.from_numpy(real).to(dev)
     U, I = len(idt.uids), len(idt.iids)
     n_rel, users, counts = eng2.eval_users(d_tu, d_ti, d_tr, float(rel_min), U, I)
-    cnt, item, plain, decayed, stats, ils, _ = _topn_lists(eng2, P, nb, users, item_avg, alpha, n, decay, keep_held, dev, None,
-                                                           _diverse(n, diversify, pool, eng2, S))
+    hybrid_stats = None
+    if hybrid is not None:
+        cnt, item, _, _, hybrid_stats = _hybrid_lists(alterEgoRDD, "evaluate_topn", st, eng2, P, nb, item_avg, users, False, alpha, n, decay,
+                                                      keep_held, None, hybrid)
+        stats, ils = hybrid_stats[0], None
+    else:
+        cnt, item, plain, decayed, stats, ils, _ = _topn_lists(eng2, P, nb, users, item_avg, alpha, n, decay, keep_held, dev, None,
+                                                               _diverse(n, diversify, pool, eng2, S))
     fill_stats = None
     if spec:
         cnt, item, _, _, _, fill_stats = _fill_lists(eng2, P, P, users, item_avg, (cnt, item, plain, decayed), spec, keep_held, None)
@@ -1475,6 +1628,8 @@ def evaluate_topn(alterEgoRDD, testRDD, cap, keep, alpha, n, cutoffs=(5, 10, 20)
     res.stats = tuple(counts) + tuple(stats)
     if spec:
         res.fill_stats = fill_stats
+    if hybrid_stats is not None:
+        res.hybrid_stats = hybrid_stats
     if ils is not None:
         v = ils.cpu().numpy()
         res.ils = math.fsum(v.tolist()) / len(v) if len(v) else 0.0
