@@ -83,7 +83,9 @@ def _alterego_rows(seed, users, items):
 # Rows of at least 2 048 entries (class 4 of the pair tables, here in its local-sensitivity form with 32-bit count halves): the
 # census of the two inputs below with the plan's statement (test_cpu_stage_a_layout.plan_statement; duplicates allowed, no heavy
 # set: ch_min = users + 2) finds none in the smaller one (600 items, 16 278 rows, the longest 940) and three in the larger one
-# (3 000 items, 114 749 rows, the longest 4 590), at both slot targets: the class runs below full size, so no input is added.
+# (3 000 items, 114 749 rows, the longest 4 590), at both slot targets.  The inputs that run the class at full size -- hubs of
+# 2 048 entries and more, 198 000 co-ratings in one slot, every rater of a hub holding it twice, every table class at its
+# design fill, the overflow ladder -- are the designed rows of tests/rec_sim_rows.py (test_gpu_rec_sim_rows.py).
 WIDE_ROWS = {(3000, 600): 0, (20000, 3000): 3}
 
 
