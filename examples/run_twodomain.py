@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW] [--hybrid W]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW] [--hybrid W] [--shelves K]]
 
 --user-based: the recommender stages with the user method of the reference's egg (calculate_xmap_sim_method = cosine_user): the
 similarity between the users' AlterEgo profiles with its local sensitivity on the device (xmap.engine.session.UserSimRDD), the
@@ -63,6 +63,12 @@ by their own rows and the 64 best items their 50 nearest users rate highest are 
 user-based half weighted W (xmap.engine.session.recommend_hybrid: neither list leaves the device).  The run prints the ranking
 metrics of the plain and of the hybrid top-10 lists side by side (evaluate_topn with hybrid=...), and for three test users the five
 fused items with the half that named each.
+
+--shelves K (with --device-tail): the front page -- not one ranking but a page of shelves, "Top picks in <category>", and the
+shelves this user sees (xmap.engine.session.recommend_shelves: one device call per batch of users, no list is downloaded to be
+cut).  The data carry no categories, so the items get K pseudo-categories by a hash of their id, every third item a second one.
+The run prints the page of the first three test users: the four best shelves by their best item, five items each, with the size
+of the whole shelf.
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -158,6 +164,7 @@ def main(argv=None):
     ap.add_argument("--related", type=int, default=None, metavar="N")
     ap.add_argument("--fill", default=None, choices=["count", "mean"], metavar="HOW")
     ap.add_argument("--hybrid", type=float, default=None, metavar="W")
+    ap.add_argument("--shelves", type=int, default=None, metavar="K")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -203,6 +210,8 @@ def main(argv=None):
         ap.error("--fill HOW needs --device-tail and the non-private recommender")
     if args.hybrid is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 0.0 <= args.hybrid < float("inf")):
         ap.error("--hybrid W needs --device-tail, the non-private recommender and a finite W >= 0")
+    if args.shelves is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.shelves <= 1000):
+        ap.error("--shelves K needs --device-tail, the non-private recommender and 1 <= K <= 1000")
     if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
         ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
@@ -399,6 +408,23 @@ def main(argv=None):
             fused.stats[2][0], fused.stats[2][4], fused.stats[0][0], fused.stats[1][0]))
         for uid, lst in fused.collect():
             print("hybrid top 5 for %s:" % uid, ", ".join("%s (%.4f, %s)" % (iid, s, "+".join(which)) for iid, s, which in lst) or "no evidence")
+    if args.shelves is not None:
+        # a page of shelves per user: pseudo-categories by a hash of the iid, every third item carries a second one
+        import zlib
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        K = args.shelves
+        iids = trainRDD.flatMap(lambda rec: [e[0] for e in rec[1]]).distinct().collect()
+        cats = {}
+        for iid in iids:
+            h = zlib.crc32(iid.encode())
+            cats[iid] = ["category %03d" % (h % K)] + (["category %03d" % ((h // 7) % K)] if h % 3 == 0 else [])
+        page = timed("shelves", session.recommend_shelves, alterEgo_profile, [uid for uid, _ in testRDD.take(3)], w, k, alpha, cats, 4, 5)
+        print("shelves: %d labels, %d (candidate, label) records, %d shelves with a member, at most %d for one user" % (
+            len(page.label_names), page.stats[6], page.stats[7], page.stats[9]))
+        for uid, shelves in page.collect():
+            print("the page of %s:" % uid if shelves else "the page of %s: no evidence" % uid)
+            for name, score, size, lst in shelves:
+                print("  top picks in %s (%d of %d):" % (name, len(lst), size), ", ".join("%s (%.3f)" % e for e in lst))
     if new_items:
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
         aud = timed("item_fold_in_audience", session.recommend_audience_items, alterEgo_profile, new_items, w, k, alpha, 10)

@@ -1192,6 +1192,67 @@ int xmap_fuse_rows(void *stream, int64_t n_query, int32_t n_lists, const xmap_fu
                    int32_t n_ids, int32_t how, double rrf_c, int32_t min_lists, int32_t n_top, int64_t max_records /*0: library default*/,
                    int32_t *out_cnt, int32_t *out_id, double *out_score, int32_t *out_lists, int64_t *h_stats /* host, [5] or NULL */);
 
+/* ---- shelves (csrc/stage_e_shelf.hip; DESIGN.md 4 "Shelves"): a page of shelves -- a top-N per LABEL of the items ("Top picks in
+ * Cookery") and the best shelves of this user -- in one call.  No returned list can be cut into shelves: the cut of every other call
+ * is inside the kernel, a user's fifth-best cookery book may be candidate number 300.
+ * Labels: a CSR over the item space, lab_ptr int64 [n_items + 1], lab_id int32 [lab_ptr[n_items]], ids in [0, n_labels), 1 <=
+ *   n_labels <= XMAP_SHELF_MAX_LABELS.  Checked on the device before any other work: lab_ptr[0] == 0; lab_ptr non-decreasing; every
+ *   id in range; the labels of ONE item strictly ascending (so a label stands once per item).  A table that fails: XMAP_ERR_ARG, the
+ *   message names the rule and the first offending index, nothing is read through the table, the outputs keep every byte.  An item
+ *   with no label is on no shelf.  lab_allow: a bitmap over the LABELS in the bit order of xmap_rec_filter.allow ((n_labels + 31) /
+ *   32 words; NULL: every label): which labels may form a shelf ("genre" labels may, "format" labels of the same table may not).
+ * Candidates and scores: for query q the kept candidates C_q are exactly steps (1)-(7) of xmap_topn_rows_filtered (candidates, held
+ *   items unless XMAP_TOPN_KEEP_HELD, the query's exclusion list, F->allow, scoring, status-2 drops, the floor on the rank_by score);
+ *   the scores are the same bits.
+ * A shelf (q, l), l an allowed label: the members of C_q whose item carries l, ranked by the rank_by score descending as numbers
+ *   (-0.0 equals 0.0), item index ascending on equal scores.  size = the members, cnt = min(size, n_top), the content = the first cnt
+ *   entries.  A shelf with size < min_fill (min_fill >= 1) is not formed; it is counted.
+ * The shelf's score and the order of the shelves, by shelf_by:
+ *   XMAP_SHELF_BY_BEST  : the rank_by score of entry 0, its bits; score descending as numbers, label ascending on equal scores
+ *   XMAP_SHELF_BY_MEAN  : (((s_0 + s_1) + ...) + s_{cnt-1}) / (double)cnt over the RETURNED entries in rank order, fp64, starting
+ *                         from s_0, one division, no fused multiply-add; order as BEST
+ *   XMAP_SHELF_BY_LABEL : the score of BEST; label ascending (a page with a fixed layout)
+ *   The first n_shelf shelves in that order are returned.
+ * Limits: 1 <= n_shelf <= 64, 1 <= n_top <= 64, rank_by 0 or 1, flags: XMAP_TOPN_KEEP_HELD only.  The status-0 scores are finite
+ *   (the scoring pass guarantees it; for xmap_shelf_segments a precondition: no order is promised for a NaN).
+ * Outputs (device): out_nshelf [Q]; out_label [Q][n_shelf] (-1 behind the count); out_sscore [Q][n_shelf] (0.0 behind); out_size
+ *   [Q][n_shelf]: the WHOLE shelf's size, the "see all 212" number (0 behind); out_cnt [Q][n_shelf] (0 behind); out_item / out_plain
+ *   / out_decay [Q][n_shelf][n_top]: -1 / 0.0 / 0.0 behind a shelf's count and for the shelves behind out_nshelf.  The slice [q][s]
+ *   has the layout of a row of xmap_topn_rows: out_cnt, out_item, out_plain, out_decay viewed as [Q * n_shelf] and [Q * n_shelf]
+ *   [n_top] are a pool for xmap_diversify_rows and a list for xmap_fuse_rows, unchanged.
+ * A query user outside the users, or one without rows, has 0 shelves.  Queries may repeat.  The result is a pure function of the
+ *   inputs: it depends on no grid, no atomic order and no chunking (no floating-point atomic, no lock).
+ * xmap_shelf_segments: the back half on its own, over scored segments in the layout the candidate-and-scoring half of a top-N
+ *   call leaves: cand_ptr [Q + 1] (checked on the device like the other pointer tables), and per candidate cand_item (ascending
+ *   within a segment, each once; an item outside [0, n_items) carries no label), plain, decay, status.  A candidate is kept iff
+ *   status == 0 and its rank_by score is >= min_score (-INFINITY: no floor; NaN: XMAP_ERR_ARG).  For callers with other scored
+ *   segments (user-kNN candidates, say).  h_stats (host, [4] or NULL) = [6..9] below.
+ * xmap_shelf_rows: the arguments of xmap_topn_rows_filtered up to n_w, then the labels, n_shelf, shelf_by, min_fill, max_records,
+ *   the outputs, F and h_stats (host, [10] or NULL): [0..5] as xmap_topn_rows_filtered; [6] (candidate, allowed label) records; [7]
+ *   shelves with size >= 1; [8] of those, the shelves below min_fill; [9] the largest number of formed shelves of one query.
+ * max_records: the records sorted at a time, in chunks of consecutive queries (a single query above it is a chunk of its own); 0:
+ *   the library's default 2^22; the result does not depend on it.  Temporaries: 12 B per candidate, 48 B per record of a chunk, 8
+ *   + 4 n_shelf B per query -- never records x n_top: the chosen shelves are selected twice instead. */
+#define XMAP_SHELF_BY_BEST 0
+#define XMAP_SHELF_BY_MEAN 1
+#define XMAP_SHELF_BY_LABEL 2
+#define XMAP_SHELF_MAX_LABELS 16777216
+int xmap_shelf_segments(void *stream, int64_t n_query, const int64_t *cand_ptr /*[n_query+1]*/, const int32_t *cand_item,
+                        const double *plain, const double *decay, const int32_t *status, double min_score, int32_t n_items,
+                        int32_t n_labels, const int64_t *lab_ptr /*[n_items+1]*/, const int32_t *lab_id,
+                        const uint32_t *lab_allow /* or NULL */, int32_t n_shelf, int32_t n_top, int32_t rank_by, int32_t shelf_by,
+                        int32_t min_fill, int64_t max_records /*0: library default*/, int32_t *out_nshelf, int32_t *out_label,
+                        double *out_sscore, int32_t *out_size, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                        double *out_decay, int64_t *h_stats /* host, [4] or NULL */);
+int xmap_shelf_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                    int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col, const double *nb_sim,
+                    const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time,
+                    const double *item_avg, const double *wtab, int32_t n_w, int32_t n_labels, const int64_t *lab_ptr /*[n_items+1]*/,
+                    const int32_t *lab_id, const uint32_t *lab_allow /* or NULL */, int32_t n_shelf, int32_t shelf_by,
+                    int32_t min_fill, int64_t max_records /*0: library default*/, int32_t *out_nshelf, int32_t *out_label,
+                    double *out_sscore, int32_t *out_size, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
+                    const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [10] or NULL */);
+
 /* ---- popularity fill (csrc/stage_e_fill.hip; DESIGN.md 4 "Popularity fill"): a ranking of the items by popularity, and the
  * completion of short top-N lists with its head.  Every other list of the tail is cut from candidates with evidence; these two
  * calls answer when there is none (a user without rows, a one-rating fold-in, a 1 % mask, the anonymous visitor).
@@ -1648,6 +1709,25 @@ int xmap_ctx_recommend_hybrid(xmap_ctx *ctx, int32_t source, int64_t n_query, co
                               int32_t uknn_flags, int32_t min_support, double w_items, double w_users, int32_t how, double rrf_c,
                               int32_t min_lists, const xmap_rec_filter *F /* host pointers inside, or NULL */, int32_t *out_cnt,
                               int32_t *out_item, double *out_score, int32_t *out_lists, int64_t *stats /* [17] or NULL */);
+/* Shelves: xmap_shelf_rows over the resident tables, host arrays in and out.
+ *   xmap_ctx_set_labels : the label table of the context's item space (host arrays: lab_ptr [n_items + 1], lab_id), checked as
+ *                   xmap_shelf_rows checks it and kept on the device beside the tail.  A second call replaces the table (a table
+ *                   that fails leaves the earlier one in place); n_labels == 0 drops it (lab_ptr / lab_id are not read).  The labels
+ *                   survive a retraining of the tail (xmap_ctx_rec_sim, xmap_ctx_rec_select); they go with the item space (an
+ *                   upload, a union) and with the context.  Needs the item space (have_gen; also on a union context).
+ *   xmap_ctx_recommend_shelves : sources as xmap_ctx_recommend_filtered (XMAP_SRC_RESIDENT also on a union context; XMAP_SRC_FOLDIN;
+ *                   XMAP_SRC_ITEM_FOLDIN: the batch items carry no label, lab_ptr is extended by its last value).  lab_allow: host
+ *                   words over the labels, or NULL.  The outputs are those of xmap_shelf_rows in host memory; max_records is the
+ *                   library's default.  Without labels set: XMAP_ERR_ARG, the message says so.
+ * Every argument is checked on the host before the context is read, each check naming its argument: on XMAP_ERR_ARG the outputs
+ * keep every byte. */
+int xmap_ctx_set_labels(xmap_ctx *ctx, int32_t n_labels, const int64_t *lab_ptr /*[n_items+1]*/, const int32_t *lab_id);
+int xmap_ctx_recommend_shelves(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_shelf, int32_t n_top,
+                               int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t shelf_by, int32_t min_fill,
+                               const uint32_t *lab_allow /* host words, or NULL */, int32_t *out_nshelf, int32_t *out_label,
+                               double *out_sscore, int32_t *out_size, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                               double *out_decay, const xmap_rec_filter *F /* host pointers inside, or NULL */,
+                               int64_t *stats /* [10] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

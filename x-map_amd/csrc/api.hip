@@ -136,6 +136,15 @@ struct xmap_ctx {
     // the batch's raw CSR and pass-through counts, for the sources of an explanation (xmap_ctx_foldin_explain)
     int64_t *f_raw_ptr = nullptr;
     int32_t *f_raw_item = nullptr, *f_cnt_t = nullptr;
+    // the label table of the item space (xmap_ctx_set_labels): lab_ptr [n_items + 1] and lab_id on the device, lab_ptr also on the
+    // host (an item fold-in extends it); survives the tail, dropped with the item space (an upload, a union) and the context
+    Pool p_lab;
+    bool have_lab = false;
+    int32_t n_labels = 0;
+    int64_t n_lab = 0;
+    int64_t *lb_ptr = nullptr;
+    int32_t *lb_id = nullptr;
+    std::vector<int64_t> h_lab_ptr;
     // multi-domain: this context holds the union of other contexts' AlterEgo rows as user-major profiles (xmap_ctx_union) and
     // nothing of the stages; have_gen is set, n_rows = the union's rows, R carries the union's sizes and all-target flags
     Pool p_union;
@@ -194,6 +203,13 @@ static void drop_union(xmap_ctx *c) {
     c->p_union.release();
     if (c->is_union) c->have_gen = false;
     c->is_union = false;
+}
+
+static void drop_labels(xmap_ctx *c) {
+    c->p_lab.release();
+    c->have_lab = false;
+    c->n_labels = 0; c->n_lab = 0;
+    c->h_lab_ptr.clear();
 }
 
 static void drop_fold(xmap_ctx *c) {
@@ -422,6 +438,7 @@ void xmap_ctx_destroy(xmap_ctx *c) {
     drop_tail(c);
     drop_fold(c);
     drop_union(c);
+    drop_labels(c);
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_rows.release(); c->p_ratings.release();
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
@@ -507,6 +524,7 @@ int xmap_ctx_upload_ratings(xmap_ctx *c, int64_t n_users, int32_t n_items, const
     drop_tail(c);
     drop_fold(c);
     drop_union(c);
+    drop_labels(c);             // the labels go with the item space
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_ratings.release();
     c->have_sim = c->have_ext = c->have_gen = false;
     const int64_t nnz = user_ptr[n_users];
@@ -1820,6 +1838,102 @@ int xmap_ctx_recommend_filled(xmap_ctx *c, int32_t source, int64_t n_query, cons
     return XMAP_OK;
 }
 
+// ---- shelves: the label table of the item space, and xmap_shelf_rows over the three sources ------------------------------------------
+
+int xmap_ctx_set_labels(xmap_ctx *c, int32_t n_labels, const int64_t *lab_ptr, const int32_t *lab_id) {
+    // the host checks: before the context is read
+    if (n_labels < 0 || n_labels > XMAP_SHELF_MAX_LABELS) {
+        set_error("xmap_ctx_set_labels: n_labels = %d, not in 0 .. 2^24", n_labels);
+        return XMAP_ERR_ARG;
+    }
+    if (n_labels > 0 && !lab_ptr) { set_error("xmap_ctx_set_labels: lab_ptr is NULL"); return XMAP_ERR_ARG; }
+    XM_ARG(c && (c->have_ratings || c->is_union));
+    XM_HIP(hipSetDevice(c->device));
+    if (n_labels == 0) { drop_labels(c); return XMAP_OK; }
+    const size_t I1 = (size_t)c->R.n_items + 1;
+    // the table's own check first needs lab_ptr[n_items] entries of lab_id: read on the host only where lab_ptr is sane so far
+    int64_t n_ids = 0;
+    bool sane = lab_ptr[0] == 0;
+    for (size_t i = 1; i < I1 && sane; i++) sane = lab_ptr[i] >= lab_ptr[i - 1];
+    if (sane) n_ids = lab_ptr[I1 - 1];
+    if (n_ids > 0 && !lab_id) { set_error("xmap_ctx_set_labels: lab_ptr lists %lld labels, lab_id is NULL", (long long)n_ids); return XMAP_ERR_ARG; }
+    ScratchPool fresh;          // (a table that fails leaves the earlier one in place)
+    int64_t *d_ptr;
+    int32_t *d_id;
+    XM_TRY(h2d(fresh, &d_ptr, lab_ptr, I1, c->st));
+    XM_TRY(h2d(fresh, &d_id, lab_id, (size_t)n_ids, c->st));
+    int64_t n_lab = 0;
+    XM_TRY(shelf_check_labels(c->st, "xmap_ctx_set_labels", c->R.n_items, n_labels, d_ptr, d_id, &n_lab));
+    drop_labels(c);
+    c->p_lab.ptrs.swap(fresh.ptrs);
+    c->have_lab = true;
+    c->n_labels = n_labels; c->n_lab = n_lab;
+    c->lb_ptr = d_ptr; c->lb_id = d_id;
+    c->h_lab_ptr.assign(lab_ptr, lab_ptr + I1);
+    return XMAP_OK;
+}
+
+int xmap_ctx_recommend_shelves(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_shelf, int32_t n_top,
+                               int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t shelf_by, int32_t min_fill,
+                               const uint32_t *lab_allow, int32_t *out_nshelf, int32_t *out_label, double *out_sscore, int32_t *out_size,
+                               int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, const xmap_rec_filter *F,
+                               int64_t *stats) {
+    // the host checks: before the context is read, the outputs untouched, the context as it was
+    const char *who = "xmap_ctx_recommend_shelves";
+    XM_TRY(shelf_check_args(who, n_query, n_shelf, n_top, rank_by, flags, shelf_by, min_fill, 1, 0));
+    if (source != XMAP_SRC_RESIDENT && source != XMAP_SRC_FOLDIN && source != XMAP_SRC_ITEM_FOLDIN) {
+        set_error("%s: source = %d, not XMAP_SRC_RESIDENT, _FOLDIN or _ITEM_FOLDIN", who, source);
+        return XMAP_ERR_ARG;
+    }
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query == 0 || (query_user && out_nshelf && out_label && out_sscore && out_size && out_cnt && out_item && out_plain && out_decay));
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(source != XMAP_SRC_ITEM_FOLDIN || c->have_ifold);
+    if (!c->have_lab) { set_error("%s: the context has no labels (xmap_ctx_set_labels)", who); return XMAP_ERR_ARG; }
+    XM_HIP(hipSetDevice(c->device));
+    if (stats) for (int k = 0; k < 10; k++) stats[k] = 0;
+    if (n_query == 0) return XMAP_OK;
+    const Profiles P = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const Tables T = source == XMAP_SRC_ITEM_FOLDIN ? itemfold_tables(c) : resident_tables(c);
+    ScratchPool tmp;
+    const int64_t *d_lab_ptr = c->lb_ptr;
+    if (T.n_items > c->R.n_items) {             // the batch items carry no label: lab_ptr extended by its last value
+        std::vector<int64_t> ext(c->h_lab_ptr);
+        ext.resize((size_t)T.n_items + 1, c->h_lab_ptr.back());
+        int64_t *d_ext;
+        XM_TRY(h2d(tmp, &d_ext, (const int64_t *)ext.data(), ext.size(), c->st));
+        XM_HIP(hipStreamSynchronize(c->st));    // (ext leaves with this block)
+        d_lab_ptr = d_ext;
+    }
+    uint32_t *d_allow = nullptr;
+    if (lab_allow) XM_TRY(h2d(tmp, &d_allow, lab_allow, (size_t)((c->n_labels + 31) / 32), c->st));
+    int32_t *d_user, *d_nshelf, *d_label, *d_size, *d_cnt, *d_item;
+    double *d_w, *d_sscore, *d_plain, *d_decay;
+    const size_t n = (size_t)n_query, ns = n * (size_t)n_shelf, m = ns * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_user, query_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_nshelf, n, c->st)); XM_TRY(dalloc(tmp, &d_label, ns, c->st)); XM_TRY(dalloc(tmp, &d_sscore, ns, c->st));
+    XM_TRY(dalloc(tmp, &d_size, ns, c->st)); XM_TRY(dalloc(tmp, &d_cnt, ns, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st));
+    XM_TRY(dalloc(tmp, &d_plain, m, c->st)); XM_TRY(dalloc(tmp, &d_decay, m, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+    XM_TRY(shelf_rows(c->st, n_query, d_user, n_top, rank_by, flags, rec_model(P, T, d_w, n_w),
+                      ShelfLabels{c->n_labels, d_lab_ptr, c->lb_id, d_allow}, n_shelf, shelf_by, min_fill, 0,
+                      ShelfOut{d_nshelf, d_label, d_sscore, d_size, d_cnt, d_item, d_plain, d_decay}, &D, stats));
+    XM_TRY(d2h(out_nshelf, (const int32_t *)d_nshelf, n, c->st));
+    XM_TRY(d2h(out_label, (const int32_t *)d_label, ns, c->st));
+    XM_TRY(d2h(out_sscore, (const double *)d_sscore, ns, c->st));
+    XM_TRY(d2h(out_size, (const int32_t *)d_size, ns, c->st));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, ns, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    return XMAP_OK;
+}
+
 // ---- fused lists: xmap_fuse_rows over uploaded lists, and the item-based and user-based lists of the same users fused -------------
 
 int xmap_ctx_fuse(xmap_ctx *c, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists, int32_t n_ids, int32_t how, double rrf_c,
@@ -2062,6 +2176,7 @@ int xmap_ctx_union(xmap_ctx *c, int n_parts, xmap_ctx *const *src, const int32_t
     drop_tail(c);
     drop_fold(c);
     drop_union(c);
+    drop_labels(c);             // the labels go with the item space
     c->p_gen.release(); c->p_ext.release(); c->p_sim.release(); c->p_ratings.release();
     c->have_ratings = c->have_sim = c->have_ext = false;
     c->p_union.ptrs.swap(fresh.ptrs);

@@ -56,5 +56,29 @@ int explain_rows(void *stream, int64_t n_pairs, const int32_t *pair_user, const 
                  const RecModel &M, int32_t *ex_status, int32_t *ex_total, int32_t *ex_cnt, double *ex_score, int64_t *ex_row,
                  int32_t *ex_slot, double *ex_share, int32_t *h_max_now);
 
+// stage_e_shelf.hip: xmap_shelf_rows; the label table and the outputs of a shelf call travel as two values (device pointers)
+struct ShelfLabels {
+    int32_t n_labels;
+    const int64_t *lab_ptr;             // [n_items + 1]
+    const int32_t *lab_id;
+    const uint32_t *lab_allow;          // (n_labels + 31) / 32 words, or NULL
+};
+struct ShelfOut {
+    int32_t *nshelf, *label;            // [Q], [Q][n_shelf]
+    double *sscore;                     // [Q][n_shelf]
+    int32_t *size, *cnt, *item;         // [Q][n_shelf] twice, [Q][n_shelf][n_top]
+    double *plain, *decay;              // [Q][n_shelf][n_top]
+};
+int shelf_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags, const RecModel &M,
+               const ShelfLabels &L, int32_t n_shelf, int32_t shelf_by, int32_t min_fill, int64_t max_records, const ShelfOut &O,
+               const xmap_rec_filter *F, int64_t *h_stats);
+// the host checks of the shelf calls, shared with xmap_ctx_recommend_shelves: each names its argument; nothing is written
+int shelf_check_args(const char *who, int64_t n_query, int32_t n_shelf, int32_t n_top, int32_t rank_by, int32_t flags, int32_t shelf_by,
+                     int32_t min_fill, int32_t n_labels, int64_t max_records);
+// the device check of a label table over n_items items (lab_ptr[0] == 0, non-decreasing; ids in range, strictly ascending inside an
+// item), shared with xmap_ctx_set_labels; *n_lab = lab_ptr[n_items].  Synchronises.
+int shelf_check_labels(hipStream_t st, const char *who, int32_t n_items, int32_t n_labels, const int64_t *lab_ptr, const int32_t *lab_id,
+                       int64_t *n_lab);
+
 }  // namespace xmap
 #endif

@@ -118,6 +118,11 @@ class PopIndex(object):
     pass
 
 
+class LabelTable(object):
+    """what Engine.set_labels returns: the label table of an item space on the device (lab_ptr, lab_id) and the labels' names"""
+    pass
+
+
 class GenResult(object):
     pass
 
@@ -2052,6 +2057,116 @@ class Engine(object):
                                           None if F is None else C.byref(F), h))
         del alive
         return cnt, item, plain, decay, src[:Q], tuple(int(x) for x in h)
+
+    def set_labels(self, n_items, n_labels, lab_ptr, lab_id, names=None):
+        """The label table of an item space of n_items items on the device, for shelves(): lab_ptr int64 [n_items + 1], lab_id
+        int32 (NumPy arrays or tensors; labels.label_csr makes them), ids in [0, n_labels), the labels of one item strictly
+        ascending -- the device call checks the table.  names: the labels' names in id order (kept on the handle for the caller).
+        Returns a LabelTable handle."""
+        n_items, n_labels = int(n_items), int(n_labels)
+        if not 1 <= n_labels <= abi.SHELF_MAX_LABELS:
+            raise ValueError("set_labels: n_labels = %d, not in 1 .. 2^24" % n_labels)
+        T = LabelTable()
+        T.n_items, T.n_labels, T.names = n_items, n_labels, None if names is None else list(names)
+        T.ptr = torch.as_tensor(np.asarray(lab_ptr) if not torch.is_tensor(lab_ptr) else lab_ptr, dtype=torch.int64).to(self.dev).contiguous()
+        ids = torch.as_tensor(np.asarray(lab_id) if not torch.is_tensor(lab_id) else lab_id, dtype=torch.int32).to(self.dev).contiguous()
+        if int(T.ptr.numel()) != n_items + 1:
+            raise ValueError("set_labels: lab_ptr has %d entries for %d items" % (int(T.ptr.numel()), n_items))
+        T.id = ids if ids.numel() else torch.zeros(1, dtype=torch.int32, device=self.dev)
+        return T
+
+    def _lab_allow(self, labels, lab_allow):
+        """the lab_allow words of a shelf call on the device: None, a bool tensor / array [n_labels], or the packed words of
+        labels.label_mask"""
+        if lab_allow is None:
+            return None
+        n_words = (labels.n_labels + 31) // 32
+        a = lab_allow if torch.is_tensor(lab_allow) else torch.from_numpy(np.ascontiguousarray(
+            np.asarray(lab_allow).view(np.int32) if np.asarray(lab_allow).dtype == np.uint32 else np.asarray(lab_allow)))
+        if a.dtype == torch.bool:
+            from .filters import pack_mask
+            a = torch.from_numpy(pack_mask(a.cpu().numpy(), labels.n_labels).view(np.int32))
+        if a.element_size() != 4 or a.dtype.is_floating_point or int(a.numel()) != n_words:
+            raise ValueError("lab_allow: %d packed 32-bit words for %d labels, not %s %s" % (n_words, labels.n_labels, a.dtype, tuple(a.shape)))
+        return a.to(self.dev).contiguous()
+
+    def _shelf_outs(self, Q, n_shelf, n_top):
+        Q1 = max(Q, 1)
+        return [self._empty(Q1, torch.int32), self._empty((Q1, n_shelf), torch.int32), self._empty((Q1, n_shelf), torch.float64),
+                self._empty((Q1, n_shelf), torch.int32), self._empty((Q1, n_shelf), torch.int32), self._empty((Q1, n_shelf, n_top), torch.int32),
+                self._empty((Q1, n_shelf, n_top), torch.float64), self._empty((Q1, n_shelf, n_top), torch.float64)]
+
+    @staticmethod
+    def _shelf_args(n_shelf, n_top, shelf_by, min_fill):
+        n_shelf, n_top, min_fill = int(n_shelf), int(n_top), int(min_fill)
+        if not 1 <= n_shelf <= 64:
+            raise ValueError("n_shelf = %d: a page takes 1 .. 64 shelves" % n_shelf)
+        if not 1 <= n_top <= 64:
+            raise ValueError("n_top = %d: a shelf takes 1 .. 64 entries" % n_top)
+        if min_fill < 1:
+            raise ValueError("min_fill = %d, not >= 1" % min_fill)
+        by = abi.SHELF_BY.get(shelf_by, -1) if isinstance(shelf_by, str) else int(shelf_by)
+        if by not in abi.SHELF_BY.values():
+            raise ValueError("shelf_by = %r: one of %s" % (shelf_by, sorted(abi.SHELF_BY)))
+        return n_shelf, n_top, by, min_fill
+
+    def shelves(self, P, neighbors, query_user, item_avg, wtab, labels, n_shelf, n_top, shelf_by="best", min_fill=1, rank_by=0,
+                keep_held=False, lab_allow=None, allow=None, exclude=None, min_score=None, n_items=None, max_records=0):
+        """A page of shelves per query user (xmap_shelf_rows): a top-n_top per label of the items over the kept candidates of
+        topn() under the same eligibility rules (allow, exclude, min_score as topn() takes them), and the n_shelf best shelves of
+        the page by shelf_by: "best" (the score of a shelf's first entry), "mean" (the mean of its returned entries) or "label" (a
+        fixed layout, label ascending).  labels: a set_labels() handle over the item space of the tables (n_items: as predict()
+        takes it); lab_allow: the labels that may form a shelf (bool [n_labels] or labels.label_mask words; None: all); a shelf of
+        fewer than min_fill members is not formed.  Returns (nshelf [Q], label [Q][n_shelf] (-1 behind the count), sscore, size
+        (the whole shelf's members), cnt [Q][n_shelf], item (-1 behind a shelf's count), plain, decayed [Q][n_shelf][n_top], stats
+        [10]: the six of the filtered topn(), then records, shelves with a member, of those the shelves below min_fill, the most
+        formed shelves of one query).  item / plain / decayed viewed as [Q * n_shelf][n_top] with cnt as [Q * n_shelf] are lists
+        for diversify() and fuse()."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        Q = int(query_user.numel())
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        n_shelf, n_top, by, min_fill = self._shelf_args(n_shelf, n_top, shelf_by, min_fill)
+        I = int(P.n_items if n_items is None else n_items)
+        if labels.n_items != I:
+            raise ValueError("shelves: the label table covers %d items, the tables %d" % (labels.n_items, I))
+        outs = self._shelf_outs(Q, n_shelf, n_top)
+        words = self._lab_allow(labels, lab_allow)
+        F = alive = None
+        if allow is not None or exclude is not None or min_score is not None:
+            F, alive = self._rec_filter(I, Q, allow, exclude, min_score)
+        h = (C.c_int64 * 10)()
+        with self.timed("shelves"):
+            check(lib.xmap_shelf_rows(st, i64(Q), vp(query_user.contiguous()), i32(n_top), i32(rank_by),
+                                      i32(abi.TOPN_KEEP_HELD if keep_held else 0), i64(P.n_users), i32(I), i32(keep), vp(cnt), vp(col), vp(sim),
+                                      vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()),
+                                      vp(wtab), i32(wtab.numel()), i32(labels.n_labels), vp(labels.ptr), vp(labels.id), vp(words),
+                                      i32(n_shelf), i32(by), i32(min_fill), i64(max_records), *([vp(t) for t in outs] +
+                                                                                                 [None if F is None else C.byref(F), h])))
+        del alive
+        return tuple(t[:Q] for t in outs) + (tuple(int(x) for x in h),)
+
+    def shelf_segments(self, scored, labels, n_shelf, n_top, shelf_by="best", min_fill=1, rank_by=0, lab_allow=None, min_score=None,
+                       max_records=0):
+        """The back half of shelves() over scored segments (xmap_shelf_segments): scored = (cand_ptr int64 [Q + 1], cand_item int32
+        (ascending within a segment, each once), plain, decayed fp64, status int32) on the device; a candidate is kept iff its status
+        is 0 and its rank_by score is >= min_score.  The other arguments and the first eight returns as shelves(); stats [4] =
+        (records, shelves with a member, of those the shelves below min_fill, the most formed shelves of one query)."""
+        st = _stream(self.dev)
+        ptr, item, plain, decay, status = [x.contiguous() for x in scored[:5]]
+        Q = int(ptr.numel()) - 1
+        n_shelf, n_top, by, min_fill = self._shelf_args(n_shelf, n_top, shelf_by, min_fill)
+        if min_score is not None and min_score != min_score:
+            raise ValueError("min_score is NaN")
+        outs = self._shelf_outs(Q, n_shelf, n_top)
+        words = self._lab_allow(labels, lab_allow)
+        h = (C.c_int64 * 4)()
+        with self.timed("shelf_segments"):
+            check(lib.xmap_shelf_segments(st, i64(Q), vp(ptr), vp(item), vp(plain), vp(decay), vp(status),
+                                          C.c_double(float("-inf") if min_score is None else float(min_score)), i32(labels.n_items),
+                                          i32(labels.n_labels), vp(labels.ptr), vp(labels.id), vp(words), i32(n_shelf), i32(n_top), i32(rank_by),
+                                          i32(by), i32(min_fill), i64(max_records), *([vp(t) for t in outs] + [h])))
+        return tuple(t[:Q] for t in outs) + (tuple(int(x) for x in h),)
 
     def peers(self, index, Q, query_user, n_top, cap=1, min_common=1, same=False, keep_self=False, allow=None, exclude=None,
               min_sim=None, max_records=0):

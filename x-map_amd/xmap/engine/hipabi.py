@@ -35,6 +35,8 @@ FUSE_RRF, FUSE_SUM, FUSE_MEAN = 0, 1, 2      # XMAP_FUSE_*: `how` of xmap_fuse_r
 FUSE_MAX_LISTS = 16       # XMAP_FUSE_MAX_LISTS: lists of one fuse
 FUSE_BLOCK_RECORDS = 2048 # XMAP_FUSE_BLOCK_RECORDS: the sum of the widths up to which one workgroup fuses a query in LDS
 FUSE_HOW = {"rrf": FUSE_RRF, "sum": FUSE_SUM, "mean": FUSE_MEAN}
+SHELF_BY_BEST, SHELF_BY_MEAN, SHELF_BY_LABEL = 0, 1, 2      # XMAP_SHELF_BY_*: `shelf_by` of xmap_shelf_rows / xmap_shelf_segments / xmap_ctx_recommend_shelves
+SHELF_MAX_LABELS = 1 << 24  # XMAP_SHELF_MAX_LABELS: labels of one table
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -140,6 +142,7 @@ EXPORTS = [
     "xmap_related_rows", "xmap_ctx_related",
     "xmap_pop_index", "xmap_topn_fill_rows", "xmap_ctx_popular", "xmap_ctx_recommend_filled",
     "xmap_fuse_rows", "xmap_ctx_fuse", "xmap_ctx_recommend_hybrid",
+    "xmap_shelf_segments", "xmap_shelf_rows", "xmap_ctx_set_labels", "xmap_ctx_recommend_shelves",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -208,6 +211,10 @@ def header_structs(path=HEADER_PATH):
                 fields.append((re.search(r"(\w+)\s*$", m).group(1), C.c_void_p if "*" in m else kind))
     return out
 
+
+# `shelf_by` by name, from the header's constants (XMAP_SHELF_BY_*)
+SHELF_BY = {k[len("SHELF_BY_"):].lower(): v for k, v in header_constants(("XMAP_SHELF_BY_",)).items()}
+assert SHELF_BY == {"best": SHELF_BY_BEST, "mean": SHELF_BY_MEAN, "label": SHELF_BY_LABEL}
 
 # argtypes of every export: a mis-ordered or mis-typed argument raises in ctypes instead of corrupting device memory
 PROTOTYPES = header_prototypes()

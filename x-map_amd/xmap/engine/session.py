@@ -796,6 +796,92 @@ def recommend_topn_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, decay=Fa
     return res
 
 
+def _shelf_labels(st, eng2, labels):
+    """the labels= keyword of a shelf call: {iid: [label names]} or an RDD / list of (iid, [names]) -> an Engine.set_labels handle
+    over the train set's items; an iid the model does not know is ignored"""
+    from .labels import label_csr
+    idt = st.idt
+    pairs = labels.items() if isinstance(labels, dict) else (labels.collect() if hasattr(labels, "collect") else labels)
+    per = {}
+    for iid, names in pairs:
+        i = idt.iidx.get(iid)
+        if i is not None:
+            per[i] = list(per.get(i, ())) + list(names)
+    n_labels, lab_ptr, lab_id, names = label_csr(per, len(idt.iids))
+    if n_labels == 0:
+        raise ValueError("shelves: no item of the model carries a label")
+    return eng2.set_labels(len(idt.iids), n_labels, lab_ptr, lab_id, names)
+
+
+def _shelf_records(st, eng2, P, nb, item_avg, query, uids, alpha, labels, n_shelf, n, shelf_by, min_fill, allow_labels, decay, keep_held, ctx,
+                   rules):
+    """what recommend_shelves and recommend_shelves_profiles share: the pages of the user indices `query` of P, labelled `uids` ->
+    the LocalRDD of (uid, [(label name, shelf score, size, [(iid, score)*])*]) with .stats"""
+    import torch
+    from .labels import label_mask
+    idt, dev = st.idt, st.engine.dev
+    T = _shelf_labels(st, eng2, labels)
+    words = None
+    if allow_labels is not None:
+        chosen = allow_labels.collect() if hasattr(allow_labels, "collect") else allow_labels
+        words = label_mask(T.names, [x for x in chosen if x in set(T.names)])
+    d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
+    rank_by = 1 if decay else 0
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        out = eng2.shelves(P, nb, d_q, item_avg, wtab, T, n_shelf, n, shelf_by, min_fill, rank_by, keep_held, lab_allow=words, **(rules or {}))
+        if out[8][2] <= n_w:
+            break
+        n_w = out[8][2]
+    nshelf, label, sscore, size, cnt, item, plain, decayed = [x.cpu().numpy() for x in out[:8]]
+    score = decayed if decay else plain
+    iids = idt.iids
+    recs = [(uid, [(T.names[label[q, s]], float(sscore[q, s]), int(size[q, s]),
+                    [(iids[item[q, s, t]], float(score[q, s, t])) for t in range(cnt[q, s])]) for s in range(nshelf[q])])
+            for q, uid in enumerate(uids)]
+    res = LocalRDD(recs, ctx)
+    res.stats, res.label_names = out[8], list(T.names)
+    return res
+
+
+def recommend_shelves(alterEgoRDD, users, cap, keep, alpha, labels, n_shelf, n, shelf_by="best", min_fill=1, decay=False, keep_held=False,
+                      neighbors=None, allow_labels=None, allow_items=None, exclude=None, min_score=None):
+    """A page of shelves per user on the device from an AlterEgoRDD handle: the set-up of recommend_topn, then for every uid of
+    `users` a top-n (1..64) per label of the items -- "Top picks in Cookery" -- over the eligible candidates of recommend_topn
+    (allow_items, exclude, min_score as it takes them), and the n_shelf (1..64) best shelves of the page (Engine.shelves).  labels =
+    {iid: [label names]} or an RDD / list of (iid, [names]): an item may carry several labels, a repeated name counts once, an iid
+    the model does not know is ignored, an item without labels is on no shelf.  shelf_by: "best" (a shelf's first score), "mean"
+    (the mean of its returned scores) or "label" (label name ascending, a fixed layout); a shelf with fewer than min_fill members is
+    not shown; allow_labels = the label names that may form a shelf (None: all; a name no item carries is ignored).  Returns a
+    LocalRDD of (uid, [(label name, shelf score, size, [(iid, score)*])*]) in the order of `users` -- size is the whole shelf's
+    ("see all 212"), score the plain prediction, or the decayed one with decay=True -- with .stats (the ten of Engine.shelves) and
+    .label_names.  A uid the train set does not know gives (uid, [])."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_shelves")
+    idt = st.idt
+    uids = list(users.collect()) if hasattr(users, "collect") else list(users)
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    query = [uidx.get(uid, -1) for uid in uids]
+    return _shelf_records(st, eng2, P, nb, item_avg, query, uids, alpha, labels, n_shelf, n, shelf_by, min_fill, allow_labels, decay, keep_held,
+                          getattr(users, "ctx", None),
+                          _eligibility(st.engine.dev, uids, idt.iidx, len(idt.iids), allow_items, exclude, min_score))
+
+
+def recommend_shelves_profiles(alterEgoRDD, profiles, cap, keep, alpha, labels, n_shelf, n, shelf_by="best", min_fill=1, decay=False,
+                               keep_held=False, neighbors=None, allow_labels=None, allow_items=None, exclude=None, min_score=None):
+    """recommend_shelves for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them (fold-in).
+    Returns the LocalRDD of recommend_shelves in the order of `profiles`, with .stats, .label_names, .unknown_items and .counts."""
+    _no_fold_in(alterEgoRDD, "recommend_shelves_profiles")
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_shelves_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    uids = sorted(index, key=index.get)
+    res = _shelf_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, labels, n_shelf, n, shelf_by, min_fill, allow_labels, decay,
+                         keep_held, getattr(profiles, "ctx", None),
+                         _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
+    res.unknown_items, res.counts = unknown, F.counts
+    return res
+
+
 def _group_records(st, eng2, P, nb, item_avg, uidx, groups, alpha, n, how, veto, decay, keep_held, ctx, allow_items, exclude, min_score):
     """what recommend_group and recommend_group_profiles share: groups = [(gid, [uid*])*] over the users of P (uidx: uid -> user
     index of P; an unknown uid stays a member without rows) -> the LocalRDD of (gid, [(iid, plain, decayed, low_uid)*]) with .stats;
