@@ -74,6 +74,12 @@ int xmap_debug_arena_call(void *stream, int64_t bytes, int fail);
 /* Measurement hook: the library's stable LSD radix sort of n (key, value) pairs by the low `bits` bits of the key, in place, alone
  * -- the yardstick of the calls built around it (item fold-in, peers; profiles/tools/peers_timing.py).  1 <= bits <= 64, n < 2^31. */
 int xmap_debug_sort_pairs(void *stream, uint64_t *keys, int32_t *vals, int64_t n, int32_t bits);
+/* Test hook, host only (no stream, no device work): the chunk plan of the calls that take max_records (peers, user-kNN top-N, item
+ * fold-in, related items, fused lists, shelves).  h_rec [n_query + 1] = the records in front of each query, non-decreasing.  A chunk
+ * is a run of consecutive queries with at most max_records records (<= 0: the default 2^22; never more than 2^31 - 2), or one query.
+ * cut [n_query + 1] receives the chunk borders cut[0 .. chunks], h_out [3] = {chunks, the most records of a chunk, the most queries
+ * of one}.  A query with 2^31 - 1 records or more: XMAP_ERR_CAPACITY, the error names it. */
+int xmap_debug_record_chunks(int64_t n_query, const int64_t *h_rec, int64_t max_records, int64_t *cut, int64_t *h_out);
 
 /* exclusive prefix sum of n int64 values; out[n] receives the total; *h_total (may be NULL) too (syncs). */
 int xmap_exclusive_scan_i64(void *stream, const int64_t *in, int64_t *out, int64_t n, int64_t *h_total);

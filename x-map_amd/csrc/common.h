@@ -81,6 +81,17 @@ int fuse_check(const char *who, int64_t n_query, int32_t n_lists, const xmap_fus
 
 constexpr int WAVE = 64;
 
+// ---- one-liners every stage uses
+__host__ __device__ __forceinline__ bool finite_f64(double x) { return fabs(x) <= 1.7976931348623157e308; }    // false for a NaN
+// bit i of an `allow` mask (one bit per id, 32 ids per word)
+__device__ __forceinline__ bool bit_allowed(const unsigned int *allow, int i) { return (allow[i >> 5] >> (i & 31)) & 1u; }
+inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+inline int bits_for(long long v) {              // bits that hold 0 .. v - 1, at least one
+    int b = 1;
+    while (b < 62 && (1ll << b) < v) b++;
+    return b;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 // readlane with a wave-uniform lane index (SGPR)

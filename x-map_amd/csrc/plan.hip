@@ -3,6 +3,7 @@
 // records, the work units of the path enumeration (heaviest first, heavy starts cut into chunks) and the order of the end
 // universe (the ends of a column side by side).
 #include "common.h"
+#include "sorted_runs.h"
 
 namespace xmap {
 
@@ -192,6 +193,17 @@ int xmap_debug_sort_pairs(void *stream, uint64_t *keys, int32_t *vals, int64_t n
     XM_HIP(xm_malloc_async((void **)&kt, sizeof(unsigned long long) * (size_t)n, st));
     XM_HIP(xm_malloc_async((void **)&vt, sizeof(int) * (size_t)n, st));
     return radix_sort_pairs(st, (unsigned long long *)keys, vals, kt, vt, n, bits);
+}
+
+int xmap_debug_record_chunks(int64_t n_query, const int64_t *h_rec, int64_t max_records, int64_t *cut, int64_t *h_out) {
+    XM_ARG(n_query >= 0 && h_rec && cut && h_out);
+    RecordChunks C;
+    C.rec.assign(h_rec, h_rec + n_query + 1);
+    const int rc = pr_plan_chunks("record chunks", n_query, max_records, PR_MAX_RECORDS, &C);
+    if (rc) return rc;
+    for (size_t k = 0; k < C.cut.size(); k++) cut[k] = C.cut[k];
+    h_out[0] = (int64_t)C.cut.size() - 1; h_out[1] = C.n_max; h_out[2] = C.nq_max;
+    return XMAP_OK;
 }
 
 int xmap_nb_index(void *stream, int32_t n_items, const uint8_t *cls, int32_t *nb_list, int32_t *nb_id, int64_t *h_n_nb) {

@@ -24,12 +24,6 @@ namespace xmap {
 
 constexpr int DV_MAX_POOL = 64;
 
-static int dv_bits(long long n) {           // bits that hold 0 .. n - 1 (at least 1)
-    int b = 1;
-    while (b < 62 && (1ll << b) < n) b++;
-    return b;
-}
-
 __global__ __launch_bounds__(256) void k_dv_keys(int I, long long nnz, int col_bits, const long long *row_ptr, const int *col,
                                                  unsigned long long *keys, int *vals, unsigned long long *bad) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -147,7 +141,7 @@ int xmap_div_index(void *stream, int32_t n_items, int64_t nnz, const int64_t *ro
     XM_ARG(nnz == 0 || (n_items > 0 && row_ptr && col && sim && dv_col && dv_abs));
     if (h_dups) *h_dups = 0;
     if (nnz == 0) return XMAP_OK;
-    const int col_bits = dv_bits(n_items), row_bits = dv_bits(n_items);
+    const int col_bits = bits_for(n_items), row_bits = bits_for(n_items);
     const size_t n = (size_t)nnz;
     unsigned long long *keys = nullptr, *cnt = nullptr;
     int *vals = nullptr;

@@ -30,8 +30,6 @@ constexpr int FL_WAVES = 4;
 constexpr int FL_TOTAL_THREADS = 1024;
 static_assert(XMAP_FILL_WINDOW % (2 * WAVE) == 0, "a lane zeroes whole words, a walk step covers 64 positions");
 
-static unsigned fl_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 __global__ __launch_bounds__(256) void k_fl_sums(long long base, long long I, const long long *hd_ptr, const double *hd_x, double *s_hi,
                                                  double *s_lo) {
     const long long i = base + (long long)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
@@ -69,8 +67,6 @@ __global__ __launch_bounds__(FL_TOTAL_THREADS) void k_fl_total(long long I, cons
     }
 }
 
-__device__ __forceinline__ bool fl_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // false for a NaN
-
 // cnt: [0] ranked, [1] below min_count, [2] a non-finite score (of those at or above min_count)
 __global__ __launch_bounds__(256) void k_fl_keys(int I, const long long *hd_ptr, const double *s_hi, const double *tot, int how,
                                                  double damping, int min_count, unsigned long long *keys, int *vals, double *score,
@@ -88,7 +84,7 @@ __global__ __launch_bounds__(256) void k_fl_keys(int I, const long long *hd_ptr,
     }
     unsigned long long key = ~0ull;
     if (n < (long long)min_count) atomicAdd(&cnt[1], 1ull);
-    else if (!fl_finite(sc)) atomicAdd(&cnt[2], 1ull);
+    else if (!finite_f64(sc)) atomicAdd(&cnt[2], 1ull);
     else {
         atomicAdd(&cnt[0], 1ull);
         unsigned long long u = (unsigned long long)__double_as_longlong(sc + 0.0);      // (-0.0 + 0.0 = +0.0)
@@ -120,13 +116,11 @@ __global__ __launch_bounds__(256) void k_fl_rank(int I, const unsigned long long
 
 // ---- the mask: the ranking compacted to its allowed positions ---------------------------------------------------------------
 
-__device__ __forceinline__ bool fl_allowed(const unsigned int *allow, int i) { return (allow[i >> 5] >> (i & 31)) & 1u; }
-
 __global__ __launch_bounds__(256) void k_fl_flag(int n_ranked, int n_pop, const int *pop_item, const unsigned int *allow, int *flag) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_ranked) return;
     const int i = pop_item[r];
-    flag[r] = (i >= 0 && i < n_pop && fl_allowed(allow, i)) ? 1 : 0;
+    flag[r] = (i >= 0 && i < n_pop && bit_allowed(allow, i)) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void k_fl_compact_item(int n_ranked, const int *pop_item, const int *flag, const long long *off, int *c_item) {
@@ -246,7 +240,7 @@ int xmap_pop_index(void *stream, int32_t n_items, const int64_t *hd_ptr, const d
     if (rc) return rc;
     k_fl_total<<<dim3(1), dim3(FL_TOTAL_THREADS), 0, st>>>(I, (const long long *)hd_ptr, s_hi, s_lo, tot);
     XM_LAUNCH_CHECK();
-    const unsigned nb = fl_blocks(I, 256);
+    const unsigned nb = blocks_for(I, 256);
     k_fl_keys<<<dim3(nb), dim3(256), 0, st>>>(I, (const long long *)hd_ptr, s_hi, tot, how, damping, min_count, keys, vals, score, pop_pos,
                                          cnt);
     XM_LAUNCH_CHECK();
@@ -293,13 +287,13 @@ int xmap_topn_fill_rows(void *stream, int64_t n_query, const int32_t *query_user
         XM_HIP(xm_malloc_async((void **)&off, sizeof(long long) * ((size_t)n_ranked + 1), st));
         XM_HIP(xm_malloc_async((void **)&c_item, sizeof(int) * (size_t)n_ranked, st));
         XM_HIP(xm_malloc_async((void **)&c_pos, sizeof(int) * (size_t)n_pop_items, st));
-        k_fl_flag<<<dim3(fl_blocks(n_ranked, 256)), dim3(256), 0, st>>>(n_ranked, n_pop_items, pop_item, allow, flag);
+        k_fl_flag<<<dim3(blocks_for(n_ranked, 256)), dim3(256), 0, st>>>(n_ranked, n_pop_items, pop_item, allow, flag);
         XM_LAUNCH_CHECK();
         int64_t total = 0;
         if ((rc = xmap_exclusive_scan_i32_to_i64(st, flag, (int64_t *)off, n_ranked, &total))) return rc;
-        k_fl_compact_item<<<dim3(fl_blocks(n_ranked, 256)), dim3(256), 0, st>>>(n_ranked, pop_item, flag, off, c_item);
+        k_fl_compact_item<<<dim3(blocks_for(n_ranked, 256)), dim3(256), 0, st>>>(n_ranked, pop_item, flag, off, c_item);
         XM_LAUNCH_CHECK();
-        k_fl_compact_pos<<<dim3(fl_blocks(n_pop_items, 256)), dim3(256), 0, st>>>(n_pop_items, n_ranked, pop_pos, flag, off, c_pos);
+        k_fl_compact_pos<<<dim3(blocks_for(n_pop_items, 256)), dim3(256), 0, st>>>(n_pop_items, n_ranked, pop_pos, flag, off, c_pos);
         XM_LAUNCH_CHECK();
         rk_item = c_item; rk_pos = c_pos; n_rk = (int)total;
     }

@@ -7,14 +7,13 @@
 //   W <= XMAP_FUSE_BLOCK_RECORDS : k_fu_block, one workgroup per query, the query's records in LDS from the first load to the
 //                  selected list: keys id << 14 | l << 10 | r (distinct, so the bitonic network sorts them stably), run heads by
 //                  comparing neighbours, the head lane walks its run, au_sort on (au_key(score), position).  No global temporary.
-//   otherwise    : "sort, don't hash" as stage_e_related.hip spells it out, one slot = one (query, list):
+//   otherwise    : "sort, don't hash" with the host half of sorted_runs.h (pr_plan_chunks, pr_each_chunk), one slot = one (query, list):
 //     k_fu_count  : records per slot, one wave per slot -> scan
 //     k_fu_expand : one wave per slot of the chunk compacts the valid ids in r order: key = (q - q0) << id_bits | id,
 //                   value = l << 10 | r
-//     radix_sort_pairs : stable, so the records of one (q, id) stay in (l, r) order
-//     k_pr_heads -> scan -> k_pr_starts, k_pr_first : runs, and per query of the chunk its first run
+//     pr_run_tables : the stable sort -- the records of one (q, id) stay in (l, r) order --, the runs, per query its first run
 //     k_fu_reduce : one lane per run: the same walk (fu_walk) as the block route's head lane
-//     k_pr_select : au_select_segment over the runs of a query; its int slot carries the mask
+//     pr_select   : au_select_segment over the runs of a query; its int slot carries the mask
 // Both routes compute a run's score with the one fu_walk and select on (au_key, position ascending with id): the same bytes.
 #include <vector>
 
@@ -25,7 +24,6 @@
 
 namespace xmap {
 
-constexpr long long FU_MAX_RECORDS = 1ll << 22;         // the library's default chunk of the sorted-runs route
 constexpr unsigned long long FU_PAD = ~0ull;            // behind every record key (an id stays below 2^31)
 
 // the lists of a call, by value in the kernel arguments
@@ -50,8 +48,6 @@ __device__ __forceinline__ void fu_stage(const FuseLists &A, FuseLists *s) {
     }
     __syncthreads();
 }
-
-__device__ __forceinline__ bool fu_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // false for a NaN
 
 // entries of list l that query q offers: min(max(cnt, 0), width)
 __device__ __forceinline__ int fu_len(const FuseLists *L, int l, long long q) {
@@ -78,7 +74,7 @@ __device__ __forceinline__ int fu_walk(const FuseLists *L, long long q, int how,
     *score = 0.0;
     if (__popc(m) < min_lists) { *why = 0; return PR_DROPPED; }
     const double x = how == XMAP_FUSE_MEAN ? num / den : num;
-    if (!fu_finite(x)) { *why = 1; return PR_DROPPED; }
+    if (!finite_f64(x)) { *why = 1; return PR_DROPPED; }
     *score = x;
     return 0;
 }
@@ -230,12 +226,6 @@ __global__ __launch_bounds__(256) void k_fu_count(long long base, long long n_sl
     }
 }
 
-// qrec[q] = records in front of query q = rec_off[q * n_lists], q <= n_query
-__global__ __launch_bounds__(256) void k_fu_qrec(long long n_query, int n_lists, const long long *rec_off, long long *qrec) {
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q <= n_query) qrec[q] = rec_off[q * n_lists];
-}
-
 // one wave per slot e in [e0, e1) of the chunk: its records at rec_off[e] - rec0, the valid ids compacted in r order
 __global__ __launch_bounds__(256) void k_fu_expand(long long e0, long long e1, long long rec0, long long q0, FuseLists A, int n_ids,
                                                    const long long *rec_off, int id_bits, unsigned long long *keys, int *vals) {
@@ -291,17 +281,16 @@ __global__ __launch_bounds__(256) void k_fu_reduce(long long n, long long q0, Fu
 int fuse_check(const char *who, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists, int32_t n_ids, int32_t how, double rrf_c,
                int32_t min_lists, int32_t n_top, int64_t max_records, const void *out_cnt, const void *out_id, const void *out_score,
                const void *out_lists) {
-    const auto finite = [](double x) { return x >= -1.7976931348623157e308 && x <= 1.7976931348623157e308; };
 #define FU_CHECK(cond, ...) do { if (!(cond)) { set_error(__VA_ARGS__); return XMAP_ERR_ARG; } } while (0)
     FU_CHECK(n_lists >= 1 && n_lists <= XMAP_FUSE_MAX_LISTS, "%s: n_lists = %d, not in 1 .. %d", who, n_lists, XMAP_FUSE_MAX_LISTS);
     FU_CHECK(lists, "%s: lists is NULL", who);
     FU_CHECK(how == XMAP_FUSE_RRF || how == XMAP_FUSE_SUM || how == XMAP_FUSE_MEAN, "%s: how = %d", who, how);
     for (int l = 0; l < n_lists; l++) {
         FU_CHECK(lists[l].width >= 1 && lists[l].width <= AU_MAX_TOP, "%s: lists[%d].width = %d, not in 1 .. 1024", who, l, lists[l].width);
-        FU_CHECK(finite(lists[l].weight), "%s: lists[%d].weight is not finite", who, l);
+        FU_CHECK(finite_f64(lists[l].weight), "%s: lists[%d].weight is not finite", who, l);
         FU_CHECK(lists[l].score || how == XMAP_FUSE_RRF, "%s: lists[%d].score is NULL, how is not XMAP_FUSE_RRF", who, l);
     }
-    FU_CHECK(finite(rrf_c) && rrf_c >= 0.0, "%s: rrf_c is not finite and >= 0", who);
+    FU_CHECK(finite_f64(rrf_c) && rrf_c >= 0.0, "%s: rrf_c is not finite and >= 0", who);
     FU_CHECK(min_lists >= 1 && min_lists <= n_lists, "%s: min_lists = %d, not in 1 .. n_lists = %d", who, min_lists, n_lists);
     FU_CHECK(n_top >= 1 && n_top <= AU_MAX_TOP, "%s: n_top = %d, not in 1 .. 1024", who, n_top);
     FU_CHECK(n_ids >= 0, "%s: n_ids = %d is negative", who, n_ids);
@@ -381,73 +370,38 @@ int xmap_fuse_rows(void *stream, int64_t n_query, int32_t n_lists, const xmap_fu
     });
     if (rc) return rc;
     if ((rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rec_off, n_slots, nullptr))) return rc;
-    k_fu_qrec<<<dim3(pr_blocks(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, n_lists, rec_off, qrec);
+    k_pr_qrec<<<dim3(blocks_for(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, nullptr, n_lists, rec_off, qrec);
     XM_LAUNCH_CHECK();
-    std::vector<long long> h_rec(nq1);
-    XM_HIP(hipMemcpyAsync(h_rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    RecordChunks C;
+    C.rec.resize(nq1);
+    XM_HIP(hipMemcpyAsync(C.rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    // ---- chunks of consecutive queries: [q0, q1) with at most max_records records, or one query (at most 16 * 1024 records)
-    if (max_records <= 0) max_records = FU_MAX_RECORDS;
-    if (max_records > 2147483646ll) max_records = 2147483646ll;
-    std::vector<long long> cut;
-    cut.push_back(0);
-    long long n_max = 0, nq_max = 0;
-    for (long long q0 = 0; q0 < n_query;) {
-        long long q1 = q0 + 1;
-        while (q1 < n_query && h_rec[q1 + 1] - h_rec[q0] <= max_records) q1++;
-        const long long n = h_rec[q1] - h_rec[q0];
-        n_max = n > n_max ? n : n_max;
-        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
-        cut.push_back(q1);
-        q0 = q1;
-    }
-    const unsigned bb = pr_blocks((long long)n_query * n_top, 256);
-    k_pr_blank<<<dim3(bb < PR_BLANK_BLOCKS ? bb : PR_BLANK_BLOCKS), dim3(256), 0, st>>>(n_query, n_top, out_cnt, out_id, out_score, out_lists);
-    XM_LAUNCH_CHECK();
-    if (n_max > 0) {
-        const int id_bits = pr_bits_for(n_ids);
-        XM_ARG(id_bits + pr_bits_for(nq_max) <= 62);
-        const size_t nm = (size_t)n_max;
-        unsigned long long *keys = nullptr;
-        int *vals = nullptr, *head = nullptr, *run_start = nullptr, *r_status = nullptr, *r_mask = nullptr;
-        long long *run_idx = nullptr, *first = nullptr;
+    // ---- the chunks (a query has at most 16 * 1024 records: the capacity error of the plan is out of reach), then the outputs
+    if ((rc = pr_plan_chunks("fuse", n_query, max_records, PR_MAX_RECORDS, &C))) return rc;
+    if ((rc = pr_blank(st, n_query, n_top, out_cnt, out_id, out_score, out_lists))) return rc;
+    if (C.n_max > 0) {
+        const int id_bits = bits_for(n_ids);
+        const size_t nm = (size_t)C.n_max;
+        RunTables T;
+        int *r_status = nullptr, *r_mask = nullptr;
         double *r_score = nullptr;
-        XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
-        XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
-        XM_HIP(xm_malloc_async((void **)&head, sizeof(int) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&run_idx, sizeof(long long) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&run_start, sizeof(int) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&first, sizeof(long long) * ((size_t)nq_max + 1), st));
+        if ((rc = pr_alloc_runs(st, C.n_max, C.nq_max, id_bits, true, &T))) return rc;
         XM_HIP(xm_malloc_async((void **)&r_status, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_mask, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_score, sizeof(double) * nm, st));
-        for (size_t k = 0; k + 1 < cut.size(); k++) {
-            const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
-            const long long n = h_rec[q1] - h_rec[q0];
-            if (n == 0) continue;               // (the blank outputs stand)
-            const unsigned nb = pr_blocks(n, 256);
+        rc = pr_each_chunk(C, [&](long long q0, long long q1, long long n) {
+            const unsigned nb = blocks_for(n, 256);
             const long long e0 = q0 * n_lists;
-            rc = for_pair_ranges(nq * n_lists, 4, [&](long long base, long long end, dim3 grid) {          // slots [base, end) of the chunk
-                k_fu_expand<<<grid, dim3(256), 0, st>>>(e0 + base, e0 + end, h_rec[q0], q0, A, n_ids, rec_off, id_bits, keys, vals);
+            int rc = for_pair_ranges((q1 - q0) * n_lists, 4, [&](long long base, long long end, dim3 grid) {       // slots [base, end) of the chunk
+                k_fu_expand<<<grid, dim3(256), 0, st>>>(e0 + base, e0 + end, C.rec[q0], q0, A, n_ids, rec_off, id_bits, T.keys, T.vals);
             });
-            if (rc) return rc;
-            if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, id_bits + pr_bits_for(nq)))) return rc;
-            k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
-            XM_LAUNCH_CHECK();
-            if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
-            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
-            XM_LAUNCH_CHECK();
-            k_pr_first<<<dim3(pr_blocks(nq + 1, 256)), dim3(256), 0, st>>>(nq, n, keys, id_bits, run_idx, first);
-            XM_LAUNCH_CHECK();
-            k_fu_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, q0, A, keys, vals, id_bits, run_idx, run_start, how, rrf_c,
+            if (rc || (rc = pr_run_tables(st, T, n, q1 - q0, id_bits))) return rc;
+            k_fu_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, q0, A, T.keys, T.vals, id_bits, T.run_idx, T.run_start, how, rrf_c,
                                                                             min_lists, r_status, r_score, r_mask, cnt);
             XM_LAUNCH_CHECK();
-            rc = n_top <= 256 ? pr_select_ranges<256>(st, nq, q0, n_top, first, keys, run_start, id_bits, r_status, r_score, r_mask, out_cnt,
-                                                      out_id, out_score, out_lists, cnt)
-                              : pr_select_ranges<1024>(st, nq, q0, n_top, first, keys, run_start, id_bits, r_status, r_score, r_mask, out_cnt,
-                                                       out_id, out_score, out_lists, cnt);
-            if (rc) return rc;
-        }
+            return pr_select(st, T, q1 - q0, q0, n_top, id_bits, r_status, r_score, r_mask, out_cnt, out_id, out_score, out_lists, cnt);
+        });
+        if (rc) return rc;
     }
     return finish();
 }

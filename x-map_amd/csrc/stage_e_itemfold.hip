@@ -11,16 +11,16 @@
 // pair kernels' LS variant, tri_pairs.hip).
 //
 // Sort, don't hash: no lock, no floating-point atomic, every output position from counts and scans.  The batch is cut into
-// chunks of consecutive items whose records number at most max_records (a single item above that is a chunk of its own).
+// chunks of consecutive items whose records number at most max_records (a single item above that is a chunk of its own):
+// the plan and the walk are sorted_runs.h's (pr_plan_chunks, pr_each_chunk; a "query" there is an item of the batch here).
 //   k_if_check   : the batch comes from outside: ptr[0] == 0, ptr non-decreasing, ptr[n_new] == nnz, 0 <= user < n_users
 //   k_if_len     : records per entry = the rater's profile length -> xmap_exclusive_scan -> rec_off
 //   k_if_expand  : one thread per record of the chunk (its entry and item by bisection): key = (q - q0) << item_bits | j,
 //                  value = the record's index in the chunk; the fill pass also keeps (r0, r1) per record
-//   radix_sort_pairs (plan.hip): stable, so the records of one (q, j) stay in expansion order
-//   k_pr_heads   : (sorted_runs.h, shared with the peers and the user-kNN top-N, as are k_pr_starts and the two bisections)
-//                  1 where a run of equal keys starts -> scan = the run's index
+//   pr_sort_runs : (sorted_runs.h) the stable sort -- the records of one (q, j) stay in expansion order --, then 1 where a run of
+//                  equal keys starts -> scan = the run's index
 //   k_if_rows    : per item of the chunk the index of its first run (pr_first_run: bisection of the sorted keys) -> its row count
-//   k_pr_starts / k_if_reduce (fill only): one lane per run walks its records twice -- the double-double sum and sim, then the
+//   pr_run_starts / k_if_reduce (fill only): one lane per run walks its records twice -- the double-double sum and sim, then the
 //                  leave-one-out maximum -- and writes the entry at row_ptr[q] + (run - first run of q)
 //   k_if_stats   : avg and norm of a new item, one wave per item: the lane-strided double-double sums and dd_reduce of
 //                  item_stats.h
@@ -34,7 +34,7 @@
 
 namespace xmap {
 
-constexpr long long IF_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (about 200 MB of temporaries)
+// The default chunk (PR_MAX_RECORDS) takes about 200 MB of temporaries.
 
 __global__ __launch_bounds__(256) void k_if_check(long long n_new, long long nnz, const long long *ptr, const int *user,
                                                   long long n_users, unsigned long long *bad) {
@@ -62,12 +62,6 @@ __global__ __launch_bounds__(256) void k_if_len(long long nnz, const int *user, 
     if (e >= nnz) return;
     const int u = user[e];
     len[e] = (int)(pptr[u + 1] - pptr[u]);
-}
-
-// item_rec[q] = records in front of item q = rec_off[ptr[q]], q <= n_new
-__global__ __launch_bounds__(256) void k_if_item_rec(long long n_new, const long long *ptr, const long long *rec_off, long long *item_rec) {
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q <= n_new) item_rec[q] = rec_off[ptr[q]];
 }
 
 __global__ __launch_bounds__(256) void k_if_expand(long long n, long long rec0, long long e0, long long e1, long long q0, long long q1,
@@ -178,7 +172,6 @@ static int itemfold_pass(hipStream_t st, const IfBatch &B, long long max_records
     if (h_records) *h_records = 0;
     if (!fill && B.n_new > 0) XM_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)B.n_new, st));
     if (B.n_new == 0 || B.nnz == 0) return XMAP_OK;
-    if (max_records <= 0) max_records = IF_MAX_RECORDS;
     const size_t nz = (size_t)B.nnz, nq1 = (size_t)B.n_new + 1;
     int *len = nullptr;
     long long *rec_off = nullptr, *item_rec = nullptr;
@@ -189,71 +182,43 @@ static int itemfold_pass(hipStream_t st, const IfBatch &B, long long max_records
     XM_LAUNCH_CHECK();
     int rc = xmap_exclusive_scan_i32_to_i64(st, len, (int64_t *)rec_off, B.nnz, nullptr);
     if (rc) return rc;
-    k_if_item_rec<<<dim3((unsigned)((B.n_new + 1 + 255) / 256)), dim3(256), 0, st>>>(B.n_new, B.ptr, rec_off, item_rec);
+    k_pr_qrec<<<dim3(blocks_for(B.n_new + 1, 256)), dim3(256), 0, st>>>(B.n_new, B.ptr, 0, rec_off, item_rec);
     XM_LAUNCH_CHECK();
-    std::vector<long long> h_ptr(nq1), h_rec(nq1);
+    RecordChunks C;
+    C.rec.resize(nq1);
+    std::vector<long long> h_ptr(nq1);
     XM_HIP(hipMemcpyAsync(h_ptr.data(), B.ptr, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
-    XM_HIP(hipMemcpyAsync(h_rec.data(), item_rec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    XM_HIP(hipMemcpyAsync(C.rec.data(), item_rec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    if (h_records) *h_records = h_rec[B.n_new];
-    // ---- chunks of consecutive items: [q0, q1) with at most max_records records, or one item
-    std::vector<long long> cut;
-    cut.push_back(0);
-    long long n_max = 0, nq_max = 0;
-    for (long long q0 = 0; q0 < B.n_new;) {
-        long long q1 = q0 + 1;
-        while (q1 < B.n_new && h_rec[q1 + 1] - h_rec[q0] <= max_records) q1++;
-        const long long n = h_rec[q1] - h_rec[q0];
-        if (n >= 2147483647ll) {
-            set_error("item fold-in: item %lld of the batch expands to %lld records, a chunk holds fewer than 2^31", q0, n);
-            return XMAP_ERR_CAPACITY;
-        }
-        n_max = n > n_max ? n : n_max;
-        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
-        cut.push_back(q1);
-        q0 = q1;
-    }
-    if (n_max == 0) return XMAP_OK;             // no rater has a row: every count is 0
-    const int item_bits = pr_bits_for(B.n_items);
-    XM_ARG(item_bits + pr_bits_for(nq_max) <= 62);
-    const size_t nm = (size_t)n_max;
-    unsigned long long *keys = nullptr;
-    int *vals = nullptr, *head = nullptr, *run_start = nullptr;
-    long long *run_idx = nullptr, *first = nullptr;
+    if (h_records) *h_records = C.rec[B.n_new];
+    if ((rc = pr_plan_chunks("item fold-in", B.n_new, max_records, PR_MAX_RECORDS, &C))) return rc;    // a query = an item of the batch
+    if (C.n_max == 0) return XMAP_OK;           // no rater has a row: every count is 0
+    const int item_bits = bits_for(B.n_items);
+    RunTables T;
     double *r0 = nullptr, *r1 = nullptr;
-    XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
-    XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
-    XM_HIP(xm_malloc_async((void **)&head, sizeof(int) * nm, st));
-    XM_HIP(xm_malloc_async((void **)&run_idx, sizeof(long long) * (nm + 1), st));
-    XM_HIP(xm_malloc_async((void **)&first, sizeof(long long) * (size_t)nq_max, st));
+    if ((rc = pr_alloc_runs(st, C.n_max, C.nq_max, item_bits, fill, &T))) return rc;
     if (fill) {
-        XM_HIP(xm_malloc_async((void **)&run_start, sizeof(int) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&r0, sizeof(double) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&r1, sizeof(double) * nm, st));
+        XM_HIP(xm_malloc_async((void **)&r0, sizeof(double) * T.nm, st));
+        XM_HIP(xm_malloc_async((void **)&r1, sizeof(double) * T.nm, st));
     }
-    for (size_t k = 0; k + 1 < cut.size(); k++) {
-        const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
-        const long long n = h_rec[q1] - h_rec[q0];
-        if (n == 0) continue;
-        const unsigned nb = (unsigned)((n + 255) / 256);
-        k_if_expand<<<dim3(nb), dim3(256), 0, st>>>(n, h_rec[q0], h_ptr[q0], h_ptr[q1], q0, q1, B.ptr, B.user, B.rating, B.pptr, B.pitem,
-                                                    B.prating, rec_off, item_bits, keys, vals, r0, r1);
+    return pr_each_chunk(C, [&](long long q0, long long q1, long long n) {
+        const long long nq = q1 - q0;
+        const unsigned nb = blocks_for(n, 256);
+        k_if_expand<<<dim3(nb), dim3(256), 0, st>>>(n, C.rec[q0], h_ptr[q0], h_ptr[q1], q0, q1, B.ptr, B.user, B.rating, B.pptr, B.pitem,
+                                                    B.prating, rec_off, item_bits, T.keys, T.vals, r0, r1);
         XM_LAUNCH_CHECK();
-        if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, item_bits + pr_bits_for(nq)))) return rc;
-        k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
+        int rc = pr_sort_runs(st, T, n, nq, item_bits);
+        if (rc) return rc;
+        k_if_rows<<<dim3(blocks_for(nq, 256)), dim3(256), 0, st>>>(nq, n, T.keys, item_bits, T.run_idx, T.first, fill ? nullptr : cnt + q0);
         XM_LAUNCH_CHECK();
-        if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
-        k_if_rows<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(nq, n, keys, item_bits, run_idx, first, fill ? nullptr : cnt + q0);
-        XM_LAUNCH_CHECK();
-        if (fill) {
-            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
-            XM_LAUNCH_CHECK();
-            k_if_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, keys, vals, r0, r1, run_idx, run_start, first, item_bits, q0,
-                                                                            B.n_items, item_norm, new_norm, cap, row_ptr, col, sim, ls, nij);
+        if (fill) {                             // (the count pass needs neither the run starts nor a reduce)
+            if ((rc = pr_run_starts(st, T, n))) return rc;
+            k_if_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, T.keys, T.vals, r0, r1, T.run_idx, T.run_start, T.first, item_bits,
+                                                                            q0, B.n_items, item_norm, new_norm, cap, row_ptr, col, sim, ls, nij);
             XM_LAUNCH_CHECK();
         }
-    }
-    return XMAP_OK;
+        return XMAP_OK;
+    });
 }
 
 }  // namespace xmap

@@ -12,16 +12,17 @@
 //   k_pr_hd_fill   : hd_user (bisection of prof_ptr) and hd_x per sorted position
 //   k_pr_norm      : one wave per user; the wave finds the rows r with the item of row p by ballot, every lane runs the same
 //                    double-double chain in record order (p in profile order, r in profile order)
-// The rows (xmap_peer_rows): the queries are cut into chunks of consecutive queries whose records number at most max_records.
+// The rows (xmap_peer_rows): the queries are cut into chunks of consecutive queries whose records number at most max_records
+// (sorted_runs.h: the plan pr_plan_chunks, the walk pr_each_chunk).
 //   k_pr_qlen / k_pr_count : rows per query -> scan; records per query row = holders of its item (under a mask: the ELIGIBLE
 //                    holders, one wave per row counting ballots) -> scan = rec_off
 //   k_pr_expand    : one thread per record (its row and query by bisection): key = (q - q0) << user_bits | v, value = the record's
 //                    index, t = fl(x(p) x(h)).  k_pr_expand_masked: one wave per query row walks the holders and compacts the
 //                    eligible ones in holder order -- no record of an ineligible user is written
-//   radix_sort_pairs : stable, so the records of one (q, v) stay in expansion order
-//   k_pr_heads -> scan -> k_pr_starts, k_pr_first : runs, and per query of the chunk its first run
+//   pr_run_tables  : (sorted_runs.h) the stable sort -- the records of one (q, v) stay in expansion order --, the runs, per query
+//                    of the chunk its first run
 //   k_pr_reduce    : one lane per run: self rule, exclusion list, min_common, dot = the double-double chain, sim, the floor
-//   k_pr_select    : au_select_segment (au_select.h) over the runs of a query; position in the segment ascends with the user
+//   pr_select      : au_select_segment (au_select.h) over the runs of a query; position in the segment ascends with the user
 // With the local sensitivity (xmap_peer_rows_ls; LS = true of the templates below -- xmap_peer_rows is the LS = false code): the
 // expansion writes the two factors of a record instead of their product, the reduce multiplies them (the same bits) and keeps the
 // dot of every run, and after the selection
@@ -39,7 +40,7 @@
 
 namespace xmap {
 
-constexpr long long PR_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (64 B each: 270 MB of temporaries; 80 B with the local sensitivity)
+// A record takes 64 B of temporaries (80 B with the local sensitivity): the default chunk (PR_MAX_RECORDS) 270 MB.
 
 __device__ __forceinline__ double pr_x(const int *item, const double *rating, const double *centre, long long p) {
     return centre ? rating[p] - centre[item[p]] : rating[p];
@@ -113,8 +114,6 @@ __global__ __launch_bounds__(256) void k_pr_qlen(long long n_query, const int *q
     qlen[q] = (a >= 0 && a < n_q_users) ? (int)(qptr[a + 1] - qptr[a]) : 0;
 }
 
-__device__ __forceinline__ bool pr_allowed(const unsigned int *allow, int v) { return (allow[v >> 5] >> (v & 31)) & 1u; }
-
 // records of flattened query row e (one wave per row): the holders of its item, under a mask the eligible ones
 __global__ __launch_bounds__(256) void k_pr_count(long long base, long long n_qrows, long long n_query, const long long *qrow_off, const int *query_user,
                                                   const long long *qptr, const int *qitem, int I, const long long *hd_ptr, const int *hd_user,
@@ -132,16 +131,10 @@ __global__ __launch_bounds__(256) void k_pr_count(long long base, long long n_qr
         else
             for (long long base = h0; base < h1; base += WAVE) {
                 const long long h = base + lane;
-                c += __popcll(__ballot(h < h1 && pr_allowed(allow, hd_user[h])));
+                c += __popcll(__ballot(h < h1 && bit_allowed(allow, hd_user[h])));
             }
     }
     if (lane == 0) cnt[e] = c;
-}
-
-// qrec[q] = records in front of query q = rec_off[qrow_off[q]], q <= n_query
-__global__ __launch_bounds__(256) void k_pr_qrec(long long n_query, const long long *qrow_off, const long long *rec_off, long long *qrec) {
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q <= n_query) qrec[q] = rec_off[qrow_off[q]];
 }
 
 template <bool LS>
@@ -186,7 +179,7 @@ __global__ __launch_bounds__(256) void k_pr_expand_masked(long long rec0, long l
     for (long long base = hd_ptr[it]; base < h1; base += WAVE) {
         const long long h = base + lane;
         const int v = h < h1 ? hd_user[h] : 0;
-        const bool m = h < h1 && pr_allowed(allow, v);
+        const bool m = h < h1 && bit_allowed(allow, v);
         const unsigned long long mask = __ballot(m);
         const long long at = o + __popcll(mask & lanemask_lt());
         if (m && at < end) {                    // (at < end: the count pass saw the same mask)
@@ -198,8 +191,6 @@ __global__ __launch_bounds__(256) void k_pr_expand_masked(long long rec0, long l
         o += __popcll(mask);
     }
 }
-
-// k_pr_heads, k_pr_starts, k_pr_first: sorted_runs.h
 
 // one lane per run, records in sorted (= expansion) order.  cnt: [0] dropped by min_common, [1] non-finite, [2] below the floor
 // LS: tv / tb are the factors, r_dot[r] = the dot of a kept run
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(256) void k_pr_reduce(long long n, const unsigned l
             for (int t = s; t < e; t++) dd_add(dot, lo, tv[vals[t]]);
         const double np = qnrm[q] * nrm[v];
         const double sim = weighted((np != 0.0) ? dot / np : 0.0, nc, cap);     // NaN != 0: divides
-        if (!(fabs(sim) <= 1.7976931348623157e308)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
+        if (!finite_f64(sim)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
         if (sim < min_score) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[2], 1ull); continue; }
         r_sim[r] = sim;
         r_status[r] = 0;
@@ -351,12 +342,12 @@ int xmap_peer_index(void *stream, int64_t n_users, int32_t n_items, const int64_
         int *vals = nullptr;
         XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nr, st));
         XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nr, st));
-        const unsigned nb = pr_blocks(n_rows, 256);
+        const unsigned nb = blocks_for(n_rows, 256);
         k_pr_item_keys<<<dim3(nb), dim3(256), 0, st>>>(n_rows, I, prof_item, keys, vals);
         XM_LAUNCH_CHECK();
-        int rc = radix_sort_pairs(st, keys, vals, keys + nr, vals + nr, n_rows, pr_bits_for((long long)I + 1));
+        int rc = radix_sort_pairs(st, keys, vals, keys + nr, vals + nr, n_rows, bits_for((long long)I + 1));
         if (rc) return rc;
-        k_pr_hd_ptr<<<dim3(pr_blocks((long long)I + 1, 256)), dim3(256), 0, st>>>(I, n_rows, keys, (long long *)hd_ptr);
+        k_pr_hd_ptr<<<dim3(blocks_for((long long)I + 1, 256)), dim3(256), 0, st>>>(I, n_rows, keys, (long long *)hd_ptr);
         XM_LAUNCH_CHECK();
         k_pr_hd_fill<<<dim3(nb), dim3(256), 0, st>>>(n_rows, n_users, I, keys, vals, (const long long *)prof_ptr, prof_item, prof_rating,
                                                      centre, hd_user, hd_x);
@@ -437,17 +428,12 @@ static int peer_rows_run(void *stream, int64_t n_query, const int32_t *query_use
     int64_t n_qrows = 0;
     XM_HIP(xm_malloc_async((void **)&qlen, sizeof(int) * (size_t)n_query, st));
     XM_HIP(xm_malloc_async((void **)&qrow_off, sizeof(long long) * nq1, st));
-    k_pr_qlen<<<dim3(pr_blocks(n_query, 256)), dim3(256), 0, st>>>(n_query, query_user, n_q_users, (const long long *)q_ptr, qlen);
+    k_pr_qlen<<<dim3(blocks_for(n_query, 256)), dim3(256), 0, st>>>(n_query, query_user, n_q_users, (const long long *)q_ptr, qlen);
     XM_LAUNCH_CHECK();
     if ((rc = xmap_exclusive_scan_i32_to_i64(st, qlen, (int64_t *)qrow_off, n_query, &n_qrows))) return rc;
     XM_ARG(n_qrows < 2147483647ll);
-    {
-        const long long cells = (long long)n_query * n_top;
-        const unsigned bb = pr_blocks(cells, 256);
-        k_pr_blank<<<dim3(bb < PR_BLANK_BLOCKS ? bb : PR_BLANK_BLOCKS), dim3(256), 0, st>>>(n_query, n_top, out_cnt, out_user, out_sim, out_common);
-        XM_LAUNCH_CHECK();
-        if constexpr (LS) XM_HIP(hipMemsetAsync(out_ls, 0, sizeof(double) * (size_t)cells, st));        // 0.0 behind the count
-    }
+    if ((rc = pr_blank(st, n_query, n_top, out_cnt, out_user, out_sim, out_common))) return rc;
+    if constexpr (LS) XM_HIP(hipMemsetAsync(out_ls, 0, sizeof(double) * (size_t)n_query * n_top, st));  // 0.0 behind the count
     if (n_qrows == 0 || n_users == 0 || I == 0) { XM_HIP(hipStreamSynchronize(st)); return XMAP_OK; }
     const size_t ne = (size_t)n_qrows;
     int *rcnt = nullptr;
@@ -463,51 +449,27 @@ static int peer_rows_run(void *stream, int64_t n_query, const int32_t *query_use
     });
     if (rc) return rc;
     if ((rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rec_off, n_qrows, nullptr))) return rc;
-    k_pr_qrec<<<dim3(pr_blocks(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, qrow_off, rec_off, qrec);
+    k_pr_qrec<<<dim3(blocks_for(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, qrow_off, 0, rec_off, qrec);
     XM_LAUNCH_CHECK();
     if ((rc = pr_norms(st, n_query, query_user, n_q_users, I, (const long long *)q_ptr, q_item, q_rating, centre, qnrm))) return rc;
-    std::vector<long long> h_row(nq1), h_rec(nq1);
+    RecordChunks C;
+    C.rec.resize(nq1);
+    std::vector<long long> h_row(nq1);
     XM_HIP(hipMemcpyAsync(h_row.data(), qrow_off, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
-    XM_HIP(hipMemcpyAsync(h_rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    XM_HIP(hipMemcpyAsync(C.rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    // ---- chunks of consecutive queries: [q0, q1) with at most max_records records, or one query
-    if (max_records <= 0) max_records = PR_MAX_RECORDS;
-    if (max_records > 2147483646ll) max_records = 2147483646ll;    // a chunk of several queries stays below 2^31 - 1 records: only a
-                                                                   // single query can reach the capacity error below
-    std::vector<long long> cut;
-    cut.push_back(0);
-    long long n_max = 0, nq_max = 0;
-    for (long long q0 = 0; q0 < n_query;) {
-        long long q1 = q0 + 1;
-        while (q1 < n_query && h_rec[q1 + 1] - h_rec[q0] <= max_records) q1++;
-        const long long n = h_rec[q1] - h_rec[q0];
-        if (n >= 2147483647ll) {
-            set_error("peers: query %lld expands to %lld records, a chunk holds fewer than 2^31", q0, n);
-            return XMAP_ERR_CAPACITY;
-        }
-        n_max = n > n_max ? n : n_max;
-        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
-        cut.push_back(q1);
-        q0 = q1;
-    }
+    if ((rc = pr_plan_chunks("peers", n_query, max_records, PR_MAX_RECORDS, &C))) return rc;
     unsigned long long *cnt = nullptr, h[5] = {0, 0, 0, 0, 0};
     XM_HIP(xm_malloc_async((void **)&cnt, sizeof(h), st));
     XM_HIP(hipMemsetAsync(cnt, 0, sizeof(h), st));
-    if (n_max > 0) {
-        const int user_bits = pr_bits_for(n_users);
-        XM_ARG(user_bits + pr_bits_for(nq_max) <= 62);
-        const size_t nm = (size_t)n_max;
-        unsigned long long *keys = nullptr;
-        int *vals = nullptr, *head = nullptr, *run_start = nullptr, *r_status = nullptr, *r_common = nullptr;
-        long long *run_idx = nullptr, *first = nullptr;
+    if (C.n_max > 0) {
+        const int user_bits = bits_for(n_users);
+        const size_t nm = (size_t)C.n_max;
+        RunTables T;
+        int *r_status = nullptr, *r_common = nullptr;
         double *tv = nullptr, *r_sim = nullptr, *tb = nullptr, *r_dot = nullptr;
-        XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
-        XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
+        if ((rc = pr_alloc_runs(st, C.n_max, C.nq_max, user_bits, true, &T))) return rc;
         XM_HIP(xm_malloc_async((void **)&tv, sizeof(double) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&head, sizeof(int) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&run_idx, sizeof(long long) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&run_start, sizeof(int) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&first, sizeof(long long) * ((size_t)nq_max + 1), st));
         XM_HIP(xm_malloc_async((void **)&r_status, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_common, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_sim, sizeof(double) * nm, st));
@@ -516,54 +478,44 @@ static int peer_rows_run(void *stream, int64_t n_query, const int32_t *query_use
             XM_HIP(xm_malloc_async((void **)&r_dot, sizeof(double) * nm, st));
         }
         const int same = (flags & XMAP_PEERS_SAME) ? 1 : 0, keep_self = (flags & XMAP_PEERS_KEEP_SELF) ? 1 : 0;
-        for (size_t k = 0; k + 1 < cut.size(); k++) {
-            const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
-            const long long n = h_rec[q1] - h_rec[q0];
-            if (n == 0) continue;               // (the blank outputs stand)
-            const unsigned nb = pr_blocks(n, 256);
+        rc = pr_each_chunk(C, [&](long long q0, long long q1, long long n) {
+            const long long nq = q1 - q0;
+            const unsigned nb = blocks_for(n, 256);
+            int rc = XMAP_OK;
             if (allow) {
                 rc = for_pair_ranges(h_row[q1] - h_row[q0], 4, [&](long long base, long long end, dim3 grid) {      // rows [base, end) of the chunk
-                    k_pr_expand_masked<LS><<<grid, dim3(256), 0, st>>>(h_rec[q0], h_row[q0] + base, h_row[q0] + end, q0, q1, qrow_off, rec_off,
+                    k_pr_expand_masked<LS><<<grid, dim3(256), 0, st>>>(C.rec[q0], h_row[q0] + base, h_row[q0] + end, q0, q1, qrow_off, rec_off,
                                                                    query_user, (const long long *)q_ptr, q_item, q_rating, centre, I,
-                                                                   (const long long *)hd_ptr, hd_user, hd_x, allow, user_bits, keys, vals, tv, tb);
+                                                                   (const long long *)hd_ptr, hd_user, hd_x, allow, user_bits, T.keys, T.vals, tv, tb);
                 });
                 if (rc) return rc;
             } else
-                k_pr_expand<LS><<<dim3(nb), dim3(256), 0, st>>>(n, h_rec[q0], h_row[q0], h_row[q1], q0, q1, qrow_off, rec_off, query_user,
+                k_pr_expand<LS><<<dim3(nb), dim3(256), 0, st>>>(n, C.rec[q0], h_row[q0], h_row[q1], q0, q1, qrow_off, rec_off, query_user,
                                                             (const long long *)q_ptr, q_item, q_rating, centre, (const long long *)hd_ptr,
-                                                            hd_user, hd_x, user_bits, keys, vals, tv, tb);
+                                                            hd_user, hd_x, user_bits, T.keys, T.vals, tv, tb);
             XM_LAUNCH_CHECK();
-            if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, user_bits + pr_bits_for(nq)))) return rc;
-            k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
+            if ((rc = pr_run_tables(st, T, n, nq, user_bits))) return rc;
+            k_pr_reduce<LS><<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, T.keys, T.vals, tv, tb, r_dot, T.run_idx, T.run_start, user_bits, q0,
+                                                                            query_user, same, keep_self, ex_ptr, ex_id, min_common, cap, min_score,
+                                                                            qnrm, nrm, r_status, r_sim, r_common, cnt);
             XM_LAUNCH_CHECK();
-            if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
-            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
-            XM_LAUNCH_CHECK();
-            k_pr_first<<<dim3(pr_blocks(nq + 1, 256)), dim3(256), 0, st>>>(nq, n, keys, user_bits, run_idx, first);
-            XM_LAUNCH_CHECK();
-            k_pr_reduce<LS><<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, keys, vals, tv, tb, r_dot, run_idx, run_start, user_bits, q0, query_user,
-                                                                            same, keep_self, ex_ptr, ex_id, min_common, cap, min_score, qnrm,
-                                                                            nrm, r_status, r_sim, r_common, cnt);
-            XM_LAUNCH_CHECK();
-            rc = n_top <= 256 ? pr_select_ranges<256>(st, nq, q0, n_top, first, keys, run_start, user_bits, r_status, r_sim, r_common, out_cnt,
-                                                      out_user, out_sim, out_common, cnt)
-                              : pr_select_ranges<1024>(st, nq, q0, n_top, first, keys, run_start, user_bits, r_status, r_sim, r_common, out_cnt,
-                                                       out_user, out_sim, out_common, cnt);
-            if (rc) return rc;
+            rc = pr_select(st, T, nq, q0, n_top, user_bits, r_status, r_sim, r_common, out_cnt, out_user, out_sim, out_common, cnt);
             if constexpr (LS) {
+                if (rc) return rc;
                 rc = for_pair_ranges(nq * n_top, 4, [&](long long base, long long end, dim3 grid) {
-                    k_pr_ls<<<grid, dim3(256), 0, st>>>(base, end, q0, n_top, first, keys, vals, tv, tb, run_start, user_bits, r_dot, cap,
+                    k_pr_ls<<<grid, dim3(256), 0, st>>>(base, end, q0, n_top, T.first, T.keys, T.vals, tv, tb, T.run_start, user_bits, r_dot, cap,
                                                         qnrm, nrm, out_cnt, out_user, out_sim, out_ls);
                 });
-                if (rc) return rc;
             }
-        }
+            return rc;
+        });
+        if (rc) return rc;
     }
     XM_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
     if (h_stats) {
         h_stats[0] = (int64_t)h[3]; h_stats[1] = (int64_t)h[0]; h_stats[2] = (int64_t)h[1]; h_stats[3] = (int64_t)h[2];
-        h_stats[4] = (int64_t)h[4]; h_stats[5] = h_rec[(size_t)n_query];
+        h_stats[4] = (int64_t)h[4]; h_stats[5] = C.rec[(size_t)n_query];
     }
     return XMAP_OK;
 }

@@ -11,13 +11,12 @@
 //                  list) + one MARKER for the member itself unless KEEP_MEMBERS, one wave per slot -> scan
 //   k_rl_expand  : one wave per slot of the chunk: the marker, then the row compacted in storage order by ballot / prefix:
 //                  key = (q - q0) << item_bits | item, value = the record's index (-1: the marker), v beside it
-//   radix_sort_pairs : stable, so the records of one (q, item) stay in position order, then storage order
-//   k_pr_heads -> scan -> k_pr_starts, k_pr_first : runs, and per query of the chunk its first run
+//   pr_run_tables : (sorted_runs.h, as are the chunk plan pr_plan_chunks and the walk pr_each_chunk) the stable sort -- the records
+//                  of one (q, item) stay in position order, then storage order --, the runs, per query of the chunk its first run
 //   k_rl_reduce  : one lane per run: a marker in the run = the item is a member: not a candidate (rule 2 without a second walk);
 //                  support (markers do not count), min_support, the score left to right, finite, the floor
-//   k_pr_select  : au_select_segment over the runs of a query; position in the segment ascends with the item
-// No floating-point atomic, no lock: the bits depend on neither the grid nor the chunking.  (two_pass.h's count_scan_fill fills in
-// one pass; here the fill runs chunk by chunk between host decisions, as in stage_e_uknn.hip, so the passes are spelled out.)
+//   pr_select    : au_select_segment over the runs of a query; position in the segment ascends with the item
+// No floating-point atomic, no lock: the bits depend on neither the grid nor the chunking.
 #include <vector>
 
 #include "common.h"
@@ -28,15 +27,13 @@
 
 namespace xmap {
 
-constexpr long long RL_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (64 B each: 268 MB of temporaries)
-
-__device__ __forceinline__ bool rl_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // false for a NaN
+// A record takes 64 B of temporaries: the default chunk (PR_MAX_RECORDS) 268 MB.
 
 // The ONE statement of "a record of item `it` is written for query q" that the count pass and the expansion both call: an item of
 // the matrix, allowed by the mask, not in the query's exclusion list ex_id[x0 .. x1).  Every lane of a wave runs the same list.
 __device__ __forceinline__ bool rl_eligible(int it, int I, const unsigned int *allow, const int *ex_id, long long x0, long long x1) {
     if (it < 0 || it >= I) return false;
-    if (allow && !((allow[it >> 5] >> (it & 31)) & 1u)) return false;
+    if (allow && !bit_allowed(allow, it)) return false;
     bool on = true;
     for (long long x = x0; x < x1 && on; x++) on = ex_id[x] != it;
     return on;
@@ -75,12 +72,6 @@ __global__ __launch_bounds__(256) void k_rl_count(long long base, long long n_sl
         cnt[e] = c + ((b >= 0 && !keep) ? 1 : 0);
         if (c) atomicAdd(n_real, (unsigned long long)c);
     }
-}
-
-// qrec[q] = records in front of query q = rec_off[b_ptr[q]], q <= n_query
-__global__ __launch_bounds__(256) void k_rl_qrec(long long n_query, const long long *b_ptr, const long long *rec_off, long long *qrec) {
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q <= n_query) qrec[q] = rec_off[b_ptr[q]];
 }
 
 // one wave per slot e of the chunk (slots [e0 + base .. e1)): its records at rec_off[e] - rec0: the marker, then the row compacted
@@ -146,7 +137,7 @@ __global__ __launch_bounds__(256) void k_rl_reduce(long long n, const int *vals,
         if (member) { r_status[r] = PR_NOT_CANDIDATE; continue; }
         if (sup < min_support) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[0], 1ull); continue; }
         const double score = how == XMAP_RELATED_SUM ? sum : how == XMAP_RELATED_MEAN ? sum / (double)sup : best;
-        if (nan || !rl_finite(score)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
+        if (nan || !finite_f64(score)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
         if (score < min_score) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[2], 1ull); continue; }
         r_score[r] = score;
         r_status[r] = 0;
@@ -196,14 +187,8 @@ int xmap_related_rows(void *stream, int64_t n_query, const int64_t *b_ptr, const
     const int I = n_items;
     const int keep = (flags & XMAP_RELATED_KEEP_MEMBERS) ? 1 : 0;
     const size_t nq1 = (size_t)n_query + 1;
-    const auto blank = [&]() {
-        const unsigned bb = pr_blocks((long long)n_query * n_top, 256);
-        k_pr_blank<<<dim3(bb < PR_BLANK_BLOCKS ? bb : PR_BLANK_BLOCKS), dim3(256), 0, st>>>(n_query, n_top, out_cnt, out_item, out_score,
-                                                                                            out_support);
-    };
     if (n_slots == 0 || I == 0) {               // no member has a row (the matrix arrays may be NULL)
-        blank();
-        XM_LAUNCH_CHECK();
+        if ((rc = pr_blank(st, n_query, n_top, out_cnt, out_item, out_score, out_support))) return rc;
         XM_HIP(hipStreamSynchronize(st));
         return XMAP_OK;
     }
@@ -222,81 +207,43 @@ int xmap_related_rows(void *stream, int64_t n_query, const int64_t *b_ptr, const
     });
     if (rc) return rc;
     if ((rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rec_off, n_slots, nullptr))) return rc;
-    k_rl_qrec<<<dim3(pr_blocks(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, (const long long *)b_ptr, rec_off, qrec);
+    k_pr_qrec<<<dim3(blocks_for(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, (const long long *)b_ptr, 0, rec_off, qrec);
     XM_LAUNCH_CHECK();
-    std::vector<long long> h_rec(nq1), h_bptr(nq1);
-    XM_HIP(hipMemcpyAsync(h_rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    RecordChunks C;
+    C.rec.resize(nq1);
+    std::vector<long long> h_bptr(nq1);
+    XM_HIP(hipMemcpyAsync(C.rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipMemcpyAsync(h_bptr.data(), b_ptr, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    // ---- chunks of consecutive queries: [q0, q1) with at most max_records records (markers included), or one query
-    if (max_records <= 0) max_records = RL_MAX_RECORDS;
-    if (max_records > 2147483646ll) max_records = 2147483646ll;    // a chunk of several queries stays below 2^31 - 1 records: only a
-                                                                   // single query can reach the capacity error below
-    std::vector<long long> cut;
-    cut.push_back(0);
-    long long n_max = 0, nq_max = 0;
-    for (long long q0 = 0; q0 < n_query;) {
-        long long q1 = q0 + 1;
-        while (q1 < n_query && h_rec[q1 + 1] - h_rec[q0] <= max_records) q1++;
-        const long long n = h_rec[q1] - h_rec[q0];
-        if (n >= 2147483647ll) {
-            set_error("related: query %lld expands to %lld records, a chunk holds fewer than 2^31", q0, n);
-            return XMAP_ERR_CAPACITY;
-        }
-        n_max = n > n_max ? n : n_max;
-        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
-        cut.push_back(q1);
-        q0 = q1;
-    }
-    blank();
-    XM_LAUNCH_CHECK();
-    if (n_max > 0) {
-        const int item_bits = pr_bits_for(I);
-        XM_ARG(item_bits + pr_bits_for(nq_max) <= 62);
-        const size_t nm = (size_t)n_max;
-        unsigned long long *keys = nullptr;
-        int *vals = nullptr, *head = nullptr, *run_start = nullptr, *r_status = nullptr, *r_support = nullptr;
-        long long *run_idx = nullptr, *first = nullptr;
+    // ---- the chunks (the markers count as records), then the first write of the outputs
+    if ((rc = pr_plan_chunks("related", n_query, max_records, PR_MAX_RECORDS, &C))) return rc;
+    if ((rc = pr_blank(st, n_query, n_top, out_cnt, out_item, out_score, out_support))) return rc;
+    if (C.n_max > 0) {
+        const int item_bits = bits_for(I);
+        const size_t nm = (size_t)C.n_max;
+        RunTables T;
+        int *r_status = nullptr, *r_support = nullptr;
         double *v = nullptr, *r_score = nullptr;
-        XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
-        XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
+        if ((rc = pr_alloc_runs(st, C.n_max, C.nq_max, item_bits, true, &T))) return rc;
         XM_HIP(xm_malloc_async((void **)&v, sizeof(double) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&head, sizeof(int) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&run_idx, sizeof(long long) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&run_start, sizeof(int) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&first, sizeof(long long) * ((size_t)nq_max + 1), st));
         XM_HIP(xm_malloc_async((void **)&r_status, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_support, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_score, sizeof(double) * nm, st));
-        for (size_t k = 0; k + 1 < cut.size(); k++) {
-            const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
-            const long long n = h_rec[q1] - h_rec[q0];
-            if (n == 0) continue;               // (the blank outputs stand)
-            const unsigned nb = pr_blocks(n, 256);
+        rc = pr_each_chunk(C, [&](long long q0, long long q1, long long n) {
+            const unsigned nb = blocks_for(n, 256);
             const long long e0 = h_bptr[q0];
-            rc = for_pair_ranges(h_bptr[q1] - e0, 4, [&](long long base, long long end, dim3 grid) {       // slots [base, end) of the chunk
-                k_rl_expand<<<grid, dim3(256), 0, st>>>(e0 + base, e0 + end, h_rec[q0], q0, n_query, (const long long *)b_ptr, b_item, b_weight,
+            int rc = for_pair_ranges(h_bptr[q1] - e0, 4, [&](long long base, long long end, dim3 grid) {   // slots [base, end) of the chunk
+                k_rl_expand<<<grid, dim3(256), 0, st>>>(e0 + base, e0 + end, C.rec[q0], q0, n_query, (const long long *)b_ptr, b_item, b_weight,
                                                         I, (const long long *)row_ptr, col, sim, keep, allow, ex_ptr, ex_id, rec_off,
-                                                        item_bits, keys, vals, v);
+                                                        item_bits, T.keys, T.vals, v);
             });
-            if (rc) return rc;
-            if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, item_bits + pr_bits_for(nq)))) return rc;
-            k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
-            XM_LAUNCH_CHECK();
-            if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
-            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
-            XM_LAUNCH_CHECK();
-            k_pr_first<<<dim3(pr_blocks(nq + 1, 256)), dim3(256), 0, st>>>(nq, n, keys, item_bits, run_idx, first);
-            XM_LAUNCH_CHECK();
-            k_rl_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, vals, v, run_idx, run_start, how, min_support, min_score,
+            if (rc || (rc = pr_run_tables(st, T, n, q1 - q0, item_bits))) return rc;
+            k_rl_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, T.vals, v, T.run_idx, T.run_start, how, min_support, min_score,
                                                                             r_status, r_score, r_support, cnt);
             XM_LAUNCH_CHECK();
-            rc = n_top <= 256 ? pr_select_ranges<256>(st, nq, q0, n_top, first, keys, run_start, item_bits, r_status, r_score, r_support, out_cnt,
-                                                      out_item, out_score, out_support, cnt)
-                              : pr_select_ranges<1024>(st, nq, q0, n_top, first, keys, run_start, item_bits, r_status, r_score, r_support,
-                                                       out_cnt, out_item, out_score, out_support, cnt);
-            if (rc) return rc;
-        }
+            return pr_select(st, T, q1 - q0, q0, n_top, item_bits, r_status, r_score, r_support, out_cnt, out_item, out_score, out_support, cnt);
+        });
+        if (rc) return rc;
     }
     XM_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));

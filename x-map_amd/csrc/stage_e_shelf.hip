@@ -9,8 +9,8 @@
 //                   "the records of candidate p" that the count and the expansion both call) -> scan
 //   k_sh_expand   : per chunk of consecutive queries: key = (q - q0) << label_bits | label, value = the candidate's position in its
 //                   segment; the records of a query come in candidate order = ascending item
-//   radix_sort_pairs : stable: a run (q, label) = a shelf, its records in ascending item
-//   k_pr_heads -> scan -> k_pr_starts, k_pr_first : (sorted_runs.h) runs, and per query of the chunk its first run
+//   pr_run_tables : (sorted_runs.h, as are the chunk plan pr_plan_chunks and the walk pr_each_chunk) the stable sort -- a run
+//                   (q, label) = a shelf, its records in ascending item --, the runs, per query of the chunk its first run
 //   k_sh_runs     : one wave per run: the shelf's score.  The run streams 64 records at a time through the register insertion of
 //                   k_tn_select (sh_select: lane j holds the j-th best); BEST and LABEL keep one entry (the arg-max), MEAN n_top,
 //                   then sums them in rank order in every lane alike
@@ -31,7 +31,7 @@
 
 namespace xmap {
 
-constexpr long long SH_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (48 B each: 201 MB of temporaries)
+// A record takes 48 B of temporaries: the default chunk (PR_MAX_RECORDS) 201 MB.
 constexpr int SH_MAX = 64;                              // n_top and n_shelf: one lane per entry
 constexpr unsigned SH_MAX_BLOCKS = 1u << 16;            // blocks of a grid-stride launch (4 waves each)
 static_assert(SH_MAX == TN_MAX_TOP && SH_MAX == WAVE, "a shelf has the layout of a row of xmap_topn_rows; lane j holds entry j");
@@ -66,7 +66,7 @@ __device__ __forceinline__ int sh_records(long long p, const int *cand_item, con
     const long long b = lab_ptr[it + 1];
     for (long long k = lab_ptr[it]; k < b; k++) {
         const int l = lab_id[k];
-        if (lab_allow && !((lab_allow[l >> 5] >> (l & 31)) & 1u)) continue;
+        if (lab_allow && !bit_allowed(lab_allow, l)) continue;
         emit(c, l);
         c++;
     }
@@ -307,7 +307,7 @@ int shelf_check_labels(hipStream_t st, const char *who, int32_t n_items, int32_t
     unsigned long long *bad = nullptr, h_bad[2] = {RF_NO_POS, RF_NO_POS};
     XM_HIP(xm_malloc_async((void **)&bad, sizeof(h_bad), st));
     XM_HIP(hipMemcpyAsync(bad, h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st));
-    const unsigned blocks = pr_blocks(n_items, 256) < 4096u ? pr_blocks(n_items, 256) : 4096u;
+    const unsigned blocks = blocks_for(n_items, 256) < 4096u ? blocks_for(n_items, 256) : 4096u;
     k_sh_check<<<dim3(blocks), dim3(256), 0, st>>>(n_items, n_labels, (const long long *)lab_ptr, lab_id, bad);
     XM_LAUNCH_CHECK();
     XM_HIP(hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
@@ -335,7 +335,7 @@ static int shelf_back(hipStream_t st, int64_t n_query, const long long *cand_ptr
     const unsigned int *lab_allow = (const unsigned int *)L.lab_allow;
     const size_t nq1 = (size_t)n_query + 1;
     const auto blank = [&]() {
-        const unsigned bb = pr_blocks((long long)n_query * n_shelf * n_top, 256);
+        const unsigned bb = blocks_for((long long)n_query * n_shelf * n_top, 256);
         k_sh_blank<<<dim3(bb < PR_BLANK_BLOCKS ? bb : PR_BLANK_BLOCKS), dim3(256), 0, st>>>(n_query, n_shelf, n_top, O.nshelf, O.label, O.sscore,
                                                                                             O.size, O.cnt, O.item, O.plain, O.decay);
     };
@@ -360,82 +360,58 @@ static int shelf_back(hipStream_t st, int64_t n_query, const long long *cand_ptr
     });
     if (rc) return rc;
     if ((rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rec_off, n_cand, nullptr))) return rc;
-    k_sh_qrec<<<dim3(pr_blocks(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, cand_ptr, rec_off, qrec, st4);
+    k_sh_qrec<<<dim3(blocks_for(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, cand_ptr, rec_off, qrec, st4);
     XM_LAUNCH_CHECK();
-    std::vector<long long> h_rec(nq1), h_cptr(nq1);
-    XM_HIP(hipMemcpyAsync(h_rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    RecordChunks C;
+    C.rec.resize(nq1);
+    std::vector<long long> h_cptr(nq1);
+    XM_HIP(hipMemcpyAsync(C.rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipMemcpyAsync(h_cptr.data(), cand_ptr, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    // ---- chunks of consecutive queries: [q0, q1) with at most max_records records, or one query
-    if (max_records <= 0) max_records = SH_MAX_RECORDS;
-    if (max_records > 2147483646ll) max_records = 2147483646ll;
-    std::vector<long long> cut;
-    cut.push_back(0);
-    long long n_max = 0, nq_max = 0;
-    for (long long q0 = 0; q0 < n_query;) {
-        long long q1 = q0 + 1;
-        while (q1 < n_query && h_rec[q1 + 1] - h_rec[q0] <= max_records) q1++;
-        const long long n = h_rec[q1] - h_rec[q0];
-        if (n >= 2147483647ll || h_cptr[q0 + 1] - h_cptr[q0] >= 2147483647ll) {
-            set_error("shelves: query %lld has %lld candidates and %lld records, a chunk holds fewer than 2^31", q0, h_cptr[q0 + 1] - h_cptr[q0], n);
+    // ---- the chunks; the shelves' own condition on the query that opens a chunk: its candidates too number fewer than 2^31
+    if ((rc = pr_plan_chunks("shelves", n_query, max_records, PR_MAX_RECORDS, &C))) return rc;
+    for (size_t k = 0; k + 1 < C.cut.size(); k++) {
+        const long long q0 = C.cut[k];
+        if (h_cptr[q0 + 1] - h_cptr[q0] >= 2147483647ll) {
+            set_error("shelves: query %lld has %lld candidates, a chunk holds fewer than 2^31", q0, h_cptr[q0 + 1] - h_cptr[q0]);
             return XMAP_ERR_CAPACITY;
         }
-        n_max = n > n_max ? n : n_max;
-        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
-        cut.push_back(q1);
-        q0 = q1;
     }
     blank();
     XM_LAUNCH_CHECK();
-    if (n_max > 0) {
-        const int label_bits = pr_bits_for(L.n_labels);
-        XM_ARG(label_bits + pr_bits_for(nq_max) <= 62);
-        const size_t nm = (size_t)n_max;
-        unsigned long long *keys = nullptr;
-        int *vals = nullptr, *head = nullptr, *run_start = nullptr, *sel_run = nullptr;
-        long long *run_idx = nullptr, *first = nullptr;
+    if (C.n_max > 0) {
+        const int label_bits = bits_for(L.n_labels);
+        RunTables T;
+        int *sel_run = nullptr;
         double *r_score = nullptr;
-        XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
-        XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
-        XM_HIP(xm_malloc_async((void **)&head, sizeof(int) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&run_idx, sizeof(long long) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&run_start, sizeof(int) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&r_score, sizeof(double) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&first, sizeof(long long) * ((size_t)nq_max + 1), st));
-        XM_HIP(xm_malloc_async((void **)&sel_run, sizeof(int) * (size_t)nq_max * n_shelf, st));
-        for (size_t k = 0; k + 1 < cut.size(); k++) {
-            const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
-            const long long n = h_rec[q1] - h_rec[q0];
-            if (n == 0) continue;               // (the blank outputs stand)
-            const unsigned nb = pr_blocks(n, 256);
-            const long long c0 = h_cptr[q0];
-            rc = for_pair_ranges(h_cptr[q1] - c0, 256, [&](long long base, long long end, dim3 grid) {       // candidates [base, end) of the chunk
-                k_sh_expand<<<grid, dim3(256), 0, st>>>(c0 + base, c0 + end, h_rec[q0], q0, n_query, cand_ptr, cand_item, plain, decay, status,
-                                                        rank_by, min_score, I, lab_ptr, L.lab_id, lab_allow, rec_off, label_bits, keys, vals);
+        if ((rc = pr_alloc_runs(st, C.n_max, C.nq_max, label_bits, true, &T))) return rc;
+        XM_HIP(xm_malloc_async((void **)&r_score, sizeof(double) * (size_t)C.n_max, st));
+        XM_HIP(xm_malloc_async((void **)&sel_run, sizeof(int) * (size_t)C.nq_max * n_shelf, st));
+        rc = pr_each_chunk(C, [&](long long q0, long long q1, long long n) {
+            const long long nq = q1 - q0, c0 = h_cptr[q0];
+            int rc = for_pair_ranges(h_cptr[q1] - c0, 256, [&](long long base, long long end, dim3 grid) {  // candidates [base, end) of the chunk
+                k_sh_expand<<<grid, dim3(256), 0, st>>>(c0 + base, c0 + end, C.rec[q0], q0, n_query, cand_ptr, cand_item, plain, decay, status,
+                                                        rank_by, min_score, I, lab_ptr, L.lab_id, lab_allow, rec_off, label_bits, T.keys, T.vals);
             });
-            if (rc) return rc;
-            if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, label_bits + pr_bits_for(nq)))) return rc;
-            k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
+            if (rc || (rc = pr_run_tables(st, T, n, nq, label_bits))) return rc;
+            k_sh_runs<<<dim3(sh_wave_blocks(n)), dim3(256), 0, st>>>(n, q0, T.keys, T.vals, T.run_idx, T.run_start, label_bits, cand_ptr, cand_item,
+                                                                     plain, decay, rank_by, n_top, shelf_by, min_fill, r_score, st4 + 4);
             XM_LAUNCH_CHECK();
-            if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
-            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
+            k_sh_pick<<<dim3(sh_wave_blocks(nq)), dim3(256), 0, st>>>(nq, q0, n_shelf, n_top, shelf_by, min_fill, T.first, T.keys, T.run_start,
+                                                                      label_bits, r_score, sel_run, O.nshelf, O.label, O.sscore, O.size, O.cnt,
+                                                                      st4 + 4);
             XM_LAUNCH_CHECK();
-            k_pr_first<<<dim3(pr_blocks(nq + 1, 256)), dim3(256), 0, st>>>(nq, n, keys, label_bits, run_idx, first);
+            k_sh_fill<<<dim3(sh_wave_blocks(nq * n_shelf)), dim3(256), 0, st>>>(nq * n_shelf, q0, n_shelf, n_top, rank_by, sel_run, T.vals,
+                                                                                T.run_start, cand_ptr, cand_item, plain, decay, O.item, O.plain,
+                                                                                O.decay);
             XM_LAUNCH_CHECK();
-            k_sh_runs<<<dim3(sh_wave_blocks(n)), dim3(256), 0, st>>>(n, q0, keys, vals, run_idx, run_start, label_bits, cand_ptr, cand_item, plain,
-                                                                     decay, rank_by, n_top, shelf_by, min_fill, r_score, st4 + 4);
-            XM_LAUNCH_CHECK();
-            k_sh_pick<<<dim3(sh_wave_blocks(nq)), dim3(256), 0, st>>>(nq, q0, n_shelf, n_top, shelf_by, min_fill, first, keys, run_start, label_bits,
-                                                                      r_score, sel_run, O.nshelf, O.label, O.sscore, O.size, O.cnt, st4 + 4);
-            XM_LAUNCH_CHECK();
-            k_sh_fill<<<dim3(sh_wave_blocks(nq * n_shelf)), dim3(256), 0, st>>>(nq * n_shelf, q0, n_shelf, n_top, rank_by, sel_run, vals, run_start,
-                                                                                cand_ptr, cand_item, plain, decay, O.item, O.plain, O.decay);
-            XM_LAUNCH_CHECK();
-        }
+            return XMAP_OK;
+        });
+        if (rc) return rc;
     }
     XM_HIP(hipMemcpyAsync(h8, st4, sizeof(unsigned long long) * 8, hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    h8[4] = (unsigned long long)h_rec[n_query];
+    h8[4] = (unsigned long long)C.rec[n_query];
     return XMAP_OK;
 }
 

@@ -11,10 +11,10 @@
 //   k_uk_count   : records per slot = the valid rows of the neighbour (under a mask: of eligible items), one wave per slot -> scan
 //   k_uk_expand  : one wave per slot of the chunk compacts its records in profile order: key = (q - q0) << item_bits | item, value =
 //                  the record's index, (s_j, d) beside it
-//   radix_sort_pairs : stable, so the records of one (q, item) stay in list order, then profile order
-//   k_pr_heads -> scan -> k_pr_starts, k_pr_first : runs, and per query of the chunk its first run
+//   pr_run_tables : (sorted_runs.h, as are the chunk plan pr_plan_chunks and the walk pr_each_chunk) the stable sort -- the records
+//                  of one (q, item) stay in list order, then profile order --, the runs, per query of the chunk its first run
 //   k_uk_reduce  : one lane per run: held items, exclusion list, min_support, the two sums left to right, the score, the floor
-//   k_pr_select  : au_select_segment over the runs of a query; position in the segment ascends with the item
+//   pr_select    : au_select_segment over the runs of a query; position in the segment ascends with the item
 // No floating-point atomic anywhere: the bits depend on neither the grid nor the chunking.
 #include <vector>
 
@@ -26,11 +26,8 @@
 
 namespace xmap {
 
-constexpr long long UK_MAX_RECORDS = 1ll << 22;         // the library's default chunk: 4 M records (72 B each: 302 MB of temporaries)
+// A record of the top-N takes 72 B of temporaries: the default chunk (PR_MAX_RECORDS) 302 MB.
 constexpr int UK_MAX_NB = 1024;
-
-__device__ __forceinline__ bool uk_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // false for a NaN
-__device__ __forceinline__ bool uk_allowed(const unsigned int *allow, int i) { return (allow[i >> 5] >> (i & 31)) & 1u; }
 
 __global__ __launch_bounds__(256) void k_uk_means(long long base, long long U, int I, const long long *pptr, const int *pitem,
                                                   const double *prating, double *avg, int *cnt) {
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(256) void k_uk_predict(long long base, long long n_
         bad = den == 0.0;                       // ZeroDivisionError
         pred = a + num / den;
     }
-    bad = bad || !uk_finite(pred);              // int() of a NaN or an infinity raises
+    bad = bad || !finite_f64(pred);              // int() of a NaN or an infinity raises
     status[t] = bad ? 2 : 0;
     o_score[t] = bad ? 0.0 : pred;
     o_bound[t] = bad ? 0.0 : bound_rating_rows(pred);
@@ -157,15 +154,9 @@ __global__ __launch_bounds__(256) void k_uk_count(long long base, long long n_sl
     for (long long b = p0; b < p1; b += WAVE) {
         const long long p = b + lane;
         const int it = p < p1 ? pitem[p] : -1;
-        c += __popcll(__ballot(it >= 0 && it < I && (!allow || uk_allowed(allow, it))));
+        c += __popcll(__ballot(it >= 0 && it < I && (!allow || bit_allowed(allow, it))));
     }
     if (lane == 0) cnt[e] = c;
-}
-
-// qrec[q] = records in front of query q = rec_off[q n_nb], q <= n_query
-__global__ __launch_bounds__(256) void k_uk_qrec(long long n_query, int n_nb, const long long *rec_off, long long *qrec) {
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q <= n_query) qrec[q] = rec_off[q * n_nb];
 }
 
 // one wave per slot e of the chunk (slots [e0 + base .. e1)): its records compacted in profile order at rec_off[e] - rec0
@@ -188,7 +179,7 @@ __global__ __launch_bounds__(256) void k_uk_expand(long long e0, long long e1, l
     for (long long b = p0; b < p1; b += WAVE) {
         const long long p = b + lane;
         const int it = p < p1 ? pitem[p] : -1;
-        const bool on = it >= 0 && it < I && (!allow || uk_allowed(allow, it));
+        const bool on = it >= 0 && it < I && (!allow || bit_allowed(allow, it));
         const unsigned long long mask = __ballot(on);
         const long long at = o + __popcll(mask & lanemask_lt());
         if (on && at < end) {                   // (at < end: the count pass saw the same rows)
@@ -240,7 +231,7 @@ __global__ __launch_bounds__(256) void k_uk_reduce(long long n, const unsigned l
             den += fabs(sl);
         }
         const double score = qavg[q] + num / den;       // a zero weight sum: an infinity or a NaN
-        if (!uk_finite(score)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
+        if (!finite_f64(score)) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[1], 1ull); continue; }
         if (score < min_score) { r_status[r] = PR_DROPPED; atomicAdd(&cnt[2], 1ull); continue; }
         r_score[r] = score;
         r_status[r] = 0;
@@ -249,7 +240,7 @@ __global__ __launch_bounds__(256) void k_uk_reduce(long long n, const unsigned l
 
 int uknn_gather(hipStream_t st, long long n, const int *sel, long long n_src, const double *src, double *out) {
     if (n <= 0) return XMAP_OK;
-    k_uk_gather<<<dim3(pr_blocks(n, 256)), dim3(256), 0, st>>>(n, sel, n_src, src, out);
+    k_uk_gather<<<dim3(blocks_for(n, 256)), dim3(256), 0, st>>>(n, sel, n_src, src, out);
     XM_LAUNCH_CHECK();
     return XMAP_OK;
 }
@@ -323,14 +314,8 @@ int xmap_uknn_topn_rows(void *stream, int64_t n_query, const int32_t *query_user
     const int own = (flags & XMAP_UKNN_OWN_MEAN) ? 1 : 0, keep_held = (flags & XMAP_UKNN_KEEP_HELD) ? 1 : 0;
     const size_t nq1 = (size_t)n_query + 1;
     const long long n_slots = n_query * (long long)n_nb;
-    const auto blank = [&]() {
-        const unsigned bb = pr_blocks((long long)n_query * n_top, 256);
-        k_pr_blank<<<dim3(bb < PR_BLANK_BLOCKS ? bb : PR_BLANK_BLOCKS), dim3(256), 0, st>>>(n_query, n_top, out_cnt, out_item, out_score,
-                                                                                            out_support);
-    };
     if (n_users == 0 || I == 0) {                 // no neighbour has a valid row (the profile arrays may be NULL)
-        blank();
-        XM_LAUNCH_CHECK();
+        if ((rc = pr_blank(st, n_query, n_top, out_cnt, out_item, out_score, out_support))) return rc;
         XM_HIP(hipStreamSynchronize(st));
         return XMAP_OK;
     }
@@ -346,92 +331,53 @@ int xmap_uknn_topn_rows(void *stream, int64_t n_query, const int32_t *query_user
     });
     if (rc) return rc;
     if ((rc = xmap_exclusive_scan_i32_to_i64(st, rcnt, (int64_t *)rec_off, n_slots, nullptr))) return rc;
-    k_uk_qrec<<<dim3(pr_blocks(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, n_nb, rec_off, qrec);
+    k_pr_qrec<<<dim3(blocks_for(n_query + 1, 256)), dim3(256), 0, st>>>(n_query, nullptr, n_nb, rec_off, qrec);
     XM_LAUNCH_CHECK();
-    std::vector<long long> h_rec(nq1);
-    XM_HIP(hipMemcpyAsync(h_rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
+    RecordChunks C;
+    C.rec.resize(nq1);
+    XM_HIP(hipMemcpyAsync(C.rec.data(), qrec, sizeof(long long) * nq1, hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
-    // ---- chunks of consecutive queries: [q0, q1) with at most max_records records, or one query
-    if (max_records <= 0) max_records = UK_MAX_RECORDS;
-    if (max_records > 2147483646ll) max_records = 2147483646ll;    // a chunk of several queries stays below 2^31 - 1 records: only a
-                                                                   // single query can reach the capacity error below
-    std::vector<long long> cut;
-    cut.push_back(0);
-    long long n_max = 0, nq_max = 0;
-    for (long long q0 = 0; q0 < n_query;) {
-        long long q1 = q0 + 1;
-        while (q1 < n_query && h_rec[q1 + 1] - h_rec[q0] <= max_records) q1++;
-        const long long n = h_rec[q1] - h_rec[q0];
-        if (n >= 2147483647ll) {
-            set_error("user-kNN: query %lld expands to %lld records, a chunk holds fewer than 2^31", q0, n);
-            return XMAP_ERR_CAPACITY;
-        }
-        n_max = n > n_max ? n : n_max;
-        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
-        cut.push_back(q1);
-        q0 = q1;
-    }
-    blank();
-    XM_LAUNCH_CHECK();
+    // ---- the chunks, then the first write of the outputs
+    if ((rc = pr_plan_chunks("user-kNN", n_query, max_records, PR_MAX_RECORDS, &C))) return rc;
+    if ((rc = pr_blank(st, n_query, n_top, out_cnt, out_item, out_score, out_support))) return rc;
     unsigned long long *cnt = nullptr, h[5] = {0, 0, 0, 0, 0};
     XM_HIP(xm_malloc_async((void **)&cnt, sizeof(h), st));
     XM_HIP(hipMemsetAsync(cnt, 0, sizeof(h), st));
-    if (n_max > 0) {
-        const int item_bits = pr_bits_for(I);
-        XM_ARG(item_bits + pr_bits_for(nq_max) <= 62);
-        const size_t nm = (size_t)n_max;
-        unsigned long long *keys = nullptr;
-        int *vals = nullptr, *head = nullptr, *run_start = nullptr, *r_status = nullptr, *r_support = nullptr;
-        long long *run_idx = nullptr, *first = nullptr;
+    if (C.n_max > 0) {
+        const int item_bits = bits_for(I);
+        const size_t nm = (size_t)C.n_max;
+        RunTables T;
+        int *r_status = nullptr, *r_support = nullptr;
         double *sv = nullptr, *dv = nullptr, *r_score = nullptr;
-        XM_HIP(xm_malloc_async((void **)&keys, sizeof(unsigned long long) * 2 * nm, st));
-        XM_HIP(xm_malloc_async((void **)&vals, sizeof(int) * 2 * nm, st));
+        if ((rc = pr_alloc_runs(st, C.n_max, C.nq_max, item_bits, true, &T))) return rc;
         XM_HIP(xm_malloc_async((void **)&sv, sizeof(double) * nm, st));
         XM_HIP(xm_malloc_async((void **)&dv, sizeof(double) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&head, sizeof(int) * nm, st));
-        XM_HIP(xm_malloc_async((void **)&run_idx, sizeof(long long) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&run_start, sizeof(int) * (nm + 1), st));
-        XM_HIP(xm_malloc_async((void **)&first, sizeof(long long) * ((size_t)nq_max + 1), st));
         XM_HIP(xm_malloc_async((void **)&r_status, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_support, sizeof(int) * nm, st));
         XM_HIP(xm_malloc_async((void **)&r_score, sizeof(double) * nm, st));
-        for (size_t k = 0; k + 1 < cut.size(); k++) {
-            const long long q0 = cut[k], q1 = cut[k + 1], nq = q1 - q0;
-            const long long n = h_rec[q1] - h_rec[q0];
-            if (n == 0) continue;               // (the blank outputs stand)
-            const unsigned nb = pr_blocks(n, 256);
+        rc = pr_each_chunk(C, [&](long long q0, long long q1, long long n) {
+            const unsigned nb = blocks_for(n, 256);
             const long long e0 = q0 * n_nb;
-            rc = for_pair_ranges(nq * n_nb, 4, [&](long long base, long long end, dim3 grid) {       // slots [base, end) of the chunk
-                k_uk_expand<<<grid, dim3(256), 0, st>>>(e0 + base, e0 + end, h_rec[q0], q0, n_nb, nb_cnt, nb_user, nb_sim, query_avg, n_users, I,
+            int rc = for_pair_ranges((q1 - q0) * n_nb, 4, [&](long long base, long long end, dim3 grid) {  // slots [base, end) of the chunk
+                k_uk_expand<<<grid, dim3(256), 0, st>>>(e0 + base, e0 + end, C.rec[q0], q0, n_nb, nb_cnt, nb_user, nb_sim, query_avg, n_users, I,
                                                         (const long long *)prof_ptr, prof_item, prof_rating, user_avg, own, allow, rec_off,
-                                                        item_bits, keys, vals, sv, dv);
+                                                        item_bits, T.keys, T.vals, sv, dv);
             });
-            if (rc) return rc;
-            if ((rc = radix_sort_pairs(st, keys, vals, keys + nm, vals + nm, n, item_bits + pr_bits_for(nq)))) return rc;
-            k_pr_heads<<<dim3(nb), dim3(256), 0, st>>>(n, keys, head);
-            XM_LAUNCH_CHECK();
-            if ((rc = xmap_exclusive_scan_i32_to_i64(st, head, (int64_t *)run_idx, n, nullptr))) return rc;
-            k_pr_starts<<<dim3(nb), dim3(256), 0, st>>>(n, head, run_idx, run_start);
-            XM_LAUNCH_CHECK();
-            k_pr_first<<<dim3(pr_blocks(nq + 1, 256)), dim3(256), 0, st>>>(nq, n, keys, item_bits, run_idx, first);
-            XM_LAUNCH_CHECK();
-            k_uk_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, keys, vals, sv, dv, run_idx, run_start, item_bits, q0, query_user,
-                                                                            n_q_users, (const long long *)q_ptr, q_item, keep_held, ex_ptr,
-                                                                            ex_id, min_support, min_score, query_avg, r_status, r_score,
+            if (rc || (rc = pr_run_tables(st, T, n, q1 - q0, item_bits))) return rc;
+            k_uk_reduce<<<dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, st>>>(n, T.keys, T.vals, sv, dv, T.run_idx, T.run_start, item_bits, q0,
+                                                                            query_user, n_q_users, (const long long *)q_ptr, q_item, keep_held,
+                                                                            ex_ptr, ex_id, min_support, min_score, query_avg, r_status, r_score,
                                                                             r_support, cnt);
             XM_LAUNCH_CHECK();
-            rc = n_top <= 256 ? pr_select_ranges<256>(st, nq, q0, n_top, first, keys, run_start, item_bits, r_status, r_score, r_support, out_cnt,
-                                                      out_item, out_score, out_support, cnt)
-                              : pr_select_ranges<1024>(st, nq, q0, n_top, first, keys, run_start, item_bits, r_status, r_score, r_support,
-                                                       out_cnt, out_item, out_score, out_support, cnt);
-            if (rc) return rc;
-        }
+            return pr_select(st, T, q1 - q0, q0, n_top, item_bits, r_status, r_score, r_support, out_cnt, out_item, out_score, out_support, cnt);
+        });
+        if (rc) return rc;
     }
     XM_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     XM_HIP(hipStreamSynchronize(st));
     if (h_stats) {
         h_stats[0] = (int64_t)h[3]; h_stats[1] = (int64_t)h[0]; h_stats[2] = (int64_t)h[1]; h_stats[3] = (int64_t)h[2];
-        h_stats[4] = (int64_t)h[4]; h_stats[5] = h_rec[(size_t)n_query];
+        h_stats[4] = (int64_t)h[4]; h_stats[5] = C.rec[(size_t)n_query];
     }
     return XMAP_OK;
 }

@@ -117,7 +117,7 @@ class FuseList(C.Structure):
 
 
 EXPORTS = [
-    "xmap_last_error", "xmap_version", "xmap_trim", "xmap_debug_arena", "xmap_debug_arena_call", "xmap_debug_sort_pairs", "xmap_exclusive_scan_i64", "xmap_exclusive_scan_i32_to_i64",
+    "xmap_last_error", "xmap_version", "xmap_trim", "xmap_debug_arena", "xmap_debug_arena_call", "xmap_debug_sort_pairs", "xmap_debug_record_chunks", "xmap_exclusive_scan_i64", "xmap_exclusive_scan_i32_to_i64",
     "xmap_exclusive_scan2_i32_to_i64", "xmap_scan_self_tiles", "xmap_sim3_plan_begin", "xmap_sim3_plan_wait", "xmap_sim3_counters_begin", "xmap_sim3_counters_wait",
     "xmap_build_csc", "xmap_user_stats", "xmap_item_stats", 
     "xmap_sim2_layout", "xmap_sim2_plan", "xmap_sim2_units",
