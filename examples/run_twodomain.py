@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW] [--hybrid W] [--shelves K]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW] [--hybrid W] [--shelves K] [--quota C] [--calibrated]]
 
 --user-based: the recommender stages with the user method of the reference's egg (calculate_xmap_sim_method = cosine_user): the
 similarity between the users' AlterEgo profiles with its local sensitivity on the device (xmap.engine.session.UserSimRDD), the
@@ -69,6 +69,13 @@ shelves this user sees (xmap.engine.session.recommend_shelves: one device call p
 cut).  The data carry no categories, so the items get K pseudo-categories by a hash of their id, every third item a second one.
 The run prints the page of the first three test users: the four best shelves by their best item, five items each, with the size
 of the whole shelf.
+
+--quota C / --calibrated (with --device-tail): ONE list with a guaranteed mix of categories, over the pseudo-categories of --shelves
+(K = 8 without it).  --quota C: at most C items of one category in a top ten, cut on the device from each test user's 256 best
+candidates (xmap.engine.session.recommend_quota).  --calibrated: the ten seats go to the categories in proportion to the user's own
+AlterEgo profile (mode="share": a user who only rated the other domain gets a list whose category mix follows the mapped taste).
+The run prints, for the test users, how many lists changed against the plain top ten and the largest share of one category in a
+list before and after.
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -165,6 +172,8 @@ def main(argv=None):
     ap.add_argument("--fill", default=None, choices=["count", "mean"], metavar="HOW")
     ap.add_argument("--hybrid", type=float, default=None, metavar="W")
     ap.add_argument("--shelves", type=int, default=None, metavar="K")
+    ap.add_argument("--quota", type=int, default=None, metavar="C")
+    ap.add_argument("--calibrated", action="store_true")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -212,6 +221,9 @@ def main(argv=None):
         ap.error("--hybrid W needs --device-tail, the non-private recommender and a finite W >= 0")
     if args.shelves is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.shelves <= 1000):
         ap.error("--shelves K needs --device-tail, the non-private recommender and 1 <= K <= 1000")
+    if (args.quota is not None or args.calibrated) and (not args.device_tail or para["recommender"]["private_flag"] or
+                                                        (args.quota is not None and args.quota < 1)):
+        ap.error("--quota C and --calibrated need --device-tail, the non-private recommender and C >= 1")
     if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
         ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
@@ -408,16 +420,42 @@ def main(argv=None):
             fused.stats[2][0], fused.stats[2][4], fused.stats[0][0], fused.stats[1][0]))
         for uid, lst in fused.collect():
             print("hybrid top 5 for %s:" % uid, ", ".join("%s (%.4f, %s)" % (iid, s, "+".join(which)) for iid, s, which in lst) or "no evidence")
-    if args.shelves is not None:
-        # a page of shelves per user: pseudo-categories by a hash of the iid, every third item carries a second one
+    if args.shelves is not None or args.quota is not None or args.calibrated:
+        # pseudo-categories by a hash of the iid, every third item carries a second one
         import zlib
         w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
-        K = args.shelves
+        K = args.shelves if args.shelves is not None else 8
         iids = trainRDD.flatMap(lambda rec: [e[0] for e in rec[1]]).distinct().collect()
         cats = {}
         for iid in iids:
             h = zlib.crc32(iid.encode())
             cats[iid] = ["category %03d" % (h % K)] + (["category %03d" % ((h // 7) % K)] if h % 3 == 0 else [])
+    if args.quota is not None or args.calibrated:
+        # one list with a guaranteed mix: caps per category, or seats in proportion to the user's own profile
+        test_uids = [uid for uid, _ in testRDD.collect()]
+        plain = timed("plain_top10", session.recommend_topn, alterEgo_profile, test_uids, w, k, alpha, 10).collect()
+
+        def largest_share(lists):
+            shares = []
+            for _, lst in lists:
+                seen = {}
+                for e in lst:
+                    for c in set(cats.get(e[0], ())):
+                        seen[c] = seen.get(c, 0) + 1
+                if lst:
+                    shares.append(max(seen.values()) / float(len(lst)) if seen else 0.0)
+            return (sum(shares) / len(shares), max(shares)) if shares else (0.0, 0.0)
+
+        runs = ([("quota %d" % args.quota, dict(at_most=args.quota))] if args.quota is not None else []) + \
+               ([("calibrated", dict(mode="share"))] if args.calibrated else [])
+        for name, kw in runs:
+            out = timed(name.split()[0], session.recommend_quota, alterEgo_profile, test_uids, w, k, alpha, cats, 10, 256, **kw)
+            before, after = largest_share(plain), largest_share(out.collect())
+            print("%s: %d of %d lists changed; the largest share of one category in a list: mean %.2f -> %.2f, worst %.2f -> %.2f%s" % (
+                name, out.stats[6], len(test_uids), before[0], after[0], before[1], after[1],
+                "; %d lists cut short by the pool of 256" % out.cut_short if out.cut_short else ""))
+    if args.shelves is not None:
+        # a page of shelves per user
         page = timed("shelves", session.recommend_shelves, alterEgo_profile, [uid for uid, _ in testRDD.take(3)], w, k, alpha, cats, 4, 5)
         print("shelves: %d labels, %d (candidate, label) records, %d shelves with a member, at most %d for one user" % (
             len(page.label_names), page.stats[6], page.stats[7], page.stats[9]))

@@ -1259,6 +1259,80 @@ int xmap_shelf_rows(void *stream, int64_t n_query, const int32_t *query_user, in
                     double *out_sscore, int32_t *out_size, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay,
                     const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [10] or NULL */);
 
+/* ---- label quotas and calibrated lists (csrc/stage_e_quota.hip; DESIGN.md 4 "Quotas and calibrated lists"): ONE list with a
+ * guaranteed mix of labels -- "at most two cookery books in my top ten" (caps), "a 70 % crime / 30 % history reader gets a 70 / 30
+ * list" (seat shares).  No returned list can be re-cut on the host: the cut of every other call is inside the kernel, the third
+ * admissible cookery book of a crime reader may be candidate number 300.
+ * Labels: the table of the shelves (lab_ptr, lab_id, n_labels), checked on the device by the same rules with the same messages; a
+ *   table that fails: XMAP_ERR_ARG, the outputs keep every byte.  GOVERNED labels: those lab_allow admits (a bitmap over the labels
+ *   in the bit order of xmap_rec_filter.allow; NULL: every label).  An ungoverned label is invisible to everything below.
+ * Pool of query q: the positions j = 0 .. m - 1 in the caller's order, m = clamp(in_cnt[q], 0, n_pool); position is rank, nothing is
+ *   sorted again.  L(j) = the governed labels of in_item[q][j]; an item outside [0, n_items) carries none; the same item at two
+ *   positions counts as two independent positions.
+ * Limits: 1 <= n_top <= n_pool <= XMAP_QUOTA_MAX_POOL; rank_by 0 or 1; 1 <= n_labels <= XMAP_SHELF_MAX_LABELS; n_pool * (the longest
+ *   label row of the WHOLE table, one integer max-reduction beside the table check) <= XMAP_QUOTA_MAX_RECORDS, else XMAP_ERR_ARG
+ *   naming n_pool, the longest label row and the limit -- a property of the table, not of a query: no call fails for some queries.
+ * mode XMAP_QUOTA_CAP: cap(l) = lab_cap[l] (device int32 [n_labels]; a negative entry: XMAP_ERR_ARG naming the first such label,
+ *   checked on the device before any other work; 0 bars the label; INT32_MAX is no cap), or the scalar cap >= 1 where lab_cap is NULL.
+ *     taken[*] = 0; r = 0
+ *     for j = 0 .. m-1 while r < n_top:
+ *         if every l in L(j) has taken[l] < cap(l):  out[r] = position j; taken[l] += 1 for every l in L(j); r += 1
+ *         else: refused += 1
+ *     out_cnt = r
+ *   A position without governed labels is always accepted; a position refused because label A is full consumes nothing of its label B.
+ * mode XMAP_QUOTA_SHARE: calibrated by Sainte-Lague seats.  Weights w[l], uint32 < 2^31 (a precondition): lab_weight (device
+ *   [n_labels], one editorial mix for all queries), or, where it is NULL, the query user's own history: w[l] = the rows of the
+ *   user's profile (prof_ptr / prof_item; nothing else of the profile is read) whose item carries governed label l -- a row held
+ *   twice counts twice, an item outside the table nothing, a query user outside [0, n_users) or without rows has all-zero weights.
+ *     s[*] = 0; left = {0 .. m-1}; n = min(m, n_top)
+ *     for r = 0 .. n-1:
+ *         E = { governed l : w[l] > 0 and some j in left has l in L(j) }
+ *         if E is empty:  j* = min(left); claim = -1                         (off-profile fill, in pool order)
+ *         else:  l* = the l of E with the largest w[l] / (2 s[l] + 1), compared exactly: a beats b iff w[a] * (2 s[b] + 1) > w[b] *
+ *                (2 s[a] + 1) in 64-bit unsigned products; on equality the smaller label id wins
+ *                j* = the smallest j in left with l* in L(j); claim = l*
+ *         out[r] = position j*; out_label[r] = claim; left -= {j*}; s[l] += 1 for every l in L(j*)
+ *     out_cnt = n
+ *   No floating point takes part in either mode; the returned scores are the pool's own bits.
+ * Outputs (device, the top-N layout: xmap_diversify_rows up to its 64, xmap_topn_fill_rows and xmap_fuse_rows take them unchanged):
+ *   out_cnt [Q]; out_item / out_plain / out_decay [Q][n_top] (-1 / 0.0 / 0.0 behind the count); out_pos [Q][n_top]: the pool position
+ *   of each entry (-1 behind); out_label [Q][n_top]: SHARE: the claiming label, -1 for a fill; CAP: the smallest governed label the
+ *   item carries, -1 for none; -1 behind the count.
+ *   h_stats (host, [4] or NULL; xmap_quota_pool synchronises only when it is given): [0] queries whose list is not the pool's
+ *   first min(m, n_top) positions; [1] the sum of out_cnt; [2] CAP: positions refused, SHARE: slots filled with E empty; [3] CAP:
+ *   queries with out_cnt < n_top and in_cnt >= n_pool -- the pool cut the list short, the caller should widen it; SHARE: 0.
+ * The result is a pure function of the inputs: no grid, no atomic order, no chunking (integer LDS atomics; no floating-point atomic,
+ *   no lock).  One workgroup per query; the labels of a pool live in LDS (hence XMAP_QUOTA_MAX_RECORDS).
+ * xmap_quota_pool: the back half over any pool in the top-N layout (item-based, user-kNN, group, related lists).  rank_by is kept
+ *   for symmetry (checked 0 / 1).  query_user / n_users / prof_ptr / prof_item: read in SHARE mode without lab_weight only.
+ * xmap_quota_rows: the whole call.  The arguments of xmap_topn_rows_filtered up to n_w (its n_top is this call's n_top), then
+ *   n_pool, the mode arguments, the labels, the outputs, F, h_stats.  The candidates are scored exactly by steps (1)-(7) of
+ *   xmap_topn_rows_filtered (the same score bits); the kept candidates of a query are ranked into a pool of n_pool by the rank_by score
+ *   descending as numbers (-0.0 equals 0.0), item ascending on equal scores -- for n_pool <= 64 by definition what
+ *   xmap_topn_rows_filtered returns with n_top = n_pool -- selected straight into LDS, never written to memory; the back half runs
+ *   over it (out_pos: the rank in that pool).  The history of SHARE mode: the profiles of the call.  h_stats (host, [10] or NULL):
+ *   [0..5] as xmap_topn_rows_filtered, [6..9] the four above ([9]: the pool was full). */
+#define XMAP_QUOTA_CAP 0
+#define XMAP_QUOTA_SHARE 1
+#define XMAP_QUOTA_MAX_POOL 1024
+#define XMAP_QUOTA_MAX_RECORDS 8192
+int xmap_quota_pool(void *stream, int64_t n_query, int32_t n_pool, const int32_t *in_cnt, const int32_t *in_item,
+                    const double *in_plain, const double *in_decay, int32_t rank_by, int32_t mode, int32_t cap,
+                    const int32_t *lab_cap /* device [n_labels], or NULL */, const uint32_t *lab_weight /* device [n_labels], or NULL */,
+                    const int32_t *query_user /* SHARE without lab_weight; else may be NULL */, int64_t n_users,
+                    const int64_t *prof_ptr, const int32_t *prof_item, int32_t n_items, int32_t n_labels,
+                    const int64_t *lab_ptr /*[n_items+1]*/, const int32_t *lab_id, const uint32_t *lab_allow /* or NULL */,
+                    int32_t n_top, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_pos,
+                    int32_t *out_label, int64_t *h_stats /* host, [4] or NULL */);
+int xmap_quota_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_top, int32_t rank_by, int32_t flags,
+                    int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col, const double *nb_sim,
+                    const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time,
+                    const double *item_avg, const double *wtab, int32_t n_w, int32_t n_pool, int32_t mode, int32_t cap,
+                    const int32_t *lab_cap /* or NULL */, const uint32_t *lab_weight /* or NULL */, int32_t n_labels,
+                    const int64_t *lab_ptr /*[n_items+1]*/, const int32_t *lab_id, const uint32_t *lab_allow /* or NULL */,
+                    int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_pos, int32_t *out_label,
+                    const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [10] or NULL */);
+
 /* ---- popularity fill (csrc/stage_e_fill.hip; DESIGN.md 4 "Popularity fill"): a ranking of the items by popularity, and the
  * completion of short top-N lists with its head.  Every other list of the tail is cut from candidates with evidence; these two
  * calls answer when there is none (a user without rows, a one-rating fold-in, a 1 % mask, the anonymous visitor).
@@ -1734,6 +1808,19 @@ int xmap_ctx_recommend_shelves(xmap_ctx *ctx, int32_t source, int64_t n_query, c
                                double *out_sscore, int32_t *out_size, int32_t *out_cnt, int32_t *out_item, double *out_plain,
                                double *out_decay, const xmap_rec_filter *F /* host pointers inside, or NULL */,
                                int64_t *stats /* [10] or NULL */);
+/* Quotas and calibrated lists: xmap_quota_rows over the resident tables and the labels of xmap_ctx_set_labels, host arrays in and
+ * out.  Sources as xmap_ctx_recommend_shelves (XMAP_SRC_FOLDIN: the history of SHARE mode is the fold-in batch's profiles;
+ * XMAP_SRC_ITEM_FOLDIN: the batch items carry no label).  lab_cap / lab_weight: host arrays [n_labels of the context], or NULL;
+ * lab_allow: host words over the labels, or NULL.  The outputs are those of xmap_quota_rows in host memory.  Without labels set:
+ * XMAP_ERR_ARG, the message says so.  Every scalar argument is checked on the host before the context is read, each check naming
+ * its argument (n_query >= 0, n_pool, n_top, rank_by, flags, mode, cap >= 1 where lab_cap is NULL in CAP mode, source, a NaN floor
+ * in F): on XMAP_ERR_ARG the outputs keep every byte. */
+int xmap_ctx_recommend_quota(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top,
+                             int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t mode, int32_t cap,
+                             const int32_t *lab_cap /* host, or NULL */, const uint32_t *lab_weight /* host, or NULL */,
+                             const uint32_t *lab_allow /* host words, or NULL */, int32_t *out_cnt, int32_t *out_item,
+                             double *out_plain, double *out_decay, int32_t *out_pos, int32_t *out_label,
+                             const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [10] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

@@ -1934,6 +1934,73 @@ int xmap_ctx_recommend_shelves(xmap_ctx *c, int32_t source, int64_t n_query, con
     return XMAP_OK;
 }
 
+// ---- quotas and calibrated lists: xmap_quota_rows over the three sources and the context's labels ------------------------------------
+
+int xmap_ctx_recommend_quota(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top,
+                             int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t mode, int32_t cap,
+                             const int32_t *lab_cap, const uint32_t *lab_weight, const uint32_t *lab_allow, int32_t *out_cnt,
+                             int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_pos, int32_t *out_label,
+                             const xmap_rec_filter *F, int64_t *stats) {
+    // the host checks: before the context is read, the outputs untouched, the context as it was
+    const char *who = "xmap_ctx_recommend_quota";
+    XM_TRY(quota_check_args(who, n_query, n_pool, n_top, rank_by, flags, mode, cap, lab_cap != nullptr, 1));
+    if (source != XMAP_SRC_RESIDENT && source != XMAP_SRC_FOLDIN && source != XMAP_SRC_ITEM_FOLDIN) {
+        set_error("%s: source = %d, not XMAP_SRC_RESIDENT, _FOLDIN or _ITEM_FOLDIN", who, source);
+        return XMAP_ERR_ARG;
+    }
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query == 0 || (query_user && out_cnt && out_item && out_plain && out_decay && out_pos && out_label));
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(source != XMAP_SRC_ITEM_FOLDIN || c->have_ifold);
+    if (!c->have_lab) { set_error("%s: the context has no labels (xmap_ctx_set_labels)", who); return XMAP_ERR_ARG; }
+    XM_HIP(hipSetDevice(c->device));
+    if (n_query == 0) {
+        if (stats) for (int k = 0; k < 10; k++) stats[k] = 0;
+        return XMAP_OK;
+    }
+    const Profiles P = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const Tables T = source == XMAP_SRC_ITEM_FOLDIN ? itemfold_tables(c) : resident_tables(c);
+    ScratchPool tmp;
+    const int64_t *d_lab_ptr = c->lb_ptr;
+    if (T.n_items > c->R.n_items) {             // the batch items carry no label: lab_ptr extended by its last value
+        std::vector<int64_t> ext(c->h_lab_ptr);
+        ext.resize((size_t)T.n_items + 1, c->h_lab_ptr.back());
+        int64_t *d_ext;
+        XM_TRY(h2d(tmp, &d_ext, (const int64_t *)ext.data(), ext.size(), c->st));
+        XM_HIP(hipStreamSynchronize(c->st));    // (ext leaves with this block)
+        d_lab_ptr = d_ext;
+    }
+    uint32_t *d_allow = nullptr, *d_weight = nullptr;
+    int32_t *d_cap = nullptr;
+    if (lab_allow) XM_TRY(h2d(tmp, &d_allow, lab_allow, (size_t)((c->n_labels + 31) / 32), c->st));
+    if (lab_cap) XM_TRY(h2d(tmp, &d_cap, lab_cap, (size_t)c->n_labels, c->st));
+    if (lab_weight) XM_TRY(h2d(tmp, &d_weight, lab_weight, (size_t)c->n_labels, c->st));
+    int32_t *d_user, *d_cnt, *d_item, *d_pos, *d_label;
+    double *d_w, *d_plain, *d_decay;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top;
+    XM_TRY(h2d(tmp, &d_user, query_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n, c->st)); XM_TRY(dalloc(tmp, &d_item, m, c->st)); XM_TRY(dalloc(tmp, &d_plain, m, c->st));
+    XM_TRY(dalloc(tmp, &d_decay, m, c->st)); XM_TRY(dalloc(tmp, &d_pos, m, c->st)); XM_TRY(dalloc(tmp, &d_label, m, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+    int64_t h10[10];
+    XM_TRY(quota_rows(c->st, n_query, d_user, n_pool, n_top, rank_by, flags, rec_model(P, T, d_w, n_w), QuotaRule{mode, cap, d_cap, d_weight},
+                      ShelfLabels{c->n_labels, d_lab_ptr, c->lb_id, d_allow}, QuotaOut{d_cnt, d_item, d_plain, d_decay, d_pos, d_label}, &D,
+                      h10));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_TRY(d2h(out_pos, (const int32_t *)d_pos, m, c->st));
+    XM_TRY(d2h(out_label, (const int32_t *)d_label, m, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    if (stats) for (int k = 0; k < 10; k++) stats[k] = h10[k];
+    return XMAP_OK;
+}
+
 // ---- fused lists: xmap_fuse_rows over uploaded lists, and the item-based and user-based lists of the same users fused -------------
 
 int xmap_ctx_fuse(xmap_ctx *c, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists, int32_t n_ids, int32_t how, double rrf_c,

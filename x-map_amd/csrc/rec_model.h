@@ -80,5 +80,22 @@ int shelf_check_args(const char *who, int64_t n_query, int32_t n_shelf, int32_t 
 int shelf_check_labels(hipStream_t st, const char *who, int32_t n_items, int32_t n_labels, const int64_t *lab_ptr, const int32_t *lab_id,
                        int64_t *n_lab);
 
+// stage_e_quota.hip: xmap_quota_rows; the mode arguments and the outputs of a quota call travel as two values (device pointers)
+struct QuotaRule {
+    int32_t mode, cap;
+    const int32_t *lab_cap;             // [n_labels], or NULL
+    const uint32_t *lab_weight;         // [n_labels], or NULL
+};
+struct QuotaOut {
+    int32_t *cnt, *item;                // [Q], [Q][n_top]
+    double *plain, *decay;              // [Q][n_top]
+    int32_t *pos, *label;               // [Q][n_top]
+};
+int quota_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top, int32_t rank_by, int32_t flags,
+               const RecModel &M, const QuotaRule &R, const ShelfLabels &L, const QuotaOut &O, const xmap_rec_filter *F, int64_t *h_stats);
+// the host checks of the quota calls, shared with xmap_ctx_recommend_quota: each names its argument; nothing is written
+int quota_check_args(const char *who, int64_t n_query, int32_t n_pool, int32_t n_top, int32_t rank_by, int32_t flags, int32_t mode,
+                     int32_t cap, bool has_lab_cap, int32_t n_labels);
+
 }  // namespace xmap
 #endif

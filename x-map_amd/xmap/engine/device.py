@@ -2168,6 +2168,94 @@ class Engine(object):
                                           i32(by), i32(min_fill), i64(max_records), *([vp(t) for t in outs] + [h])))
         return tuple(t[:Q] for t in outs) + (tuple(int(x) for x in h),)
 
+    def _quota_args(self, labels, n_pool, n_top, mode, cap, lab_cap, lab_weight):
+        """the checked scalars of a quota call and its per-label arrays on the device (None, a tensor or an array [n_labels])"""
+        n_pool, n_top = int(n_pool), int(n_top)
+        if not 1 <= n_pool <= abi.QUOTA_MAX_POOL:
+            raise ValueError("n_pool = %d: a pool takes 1 .. %d positions" % (n_pool, abi.QUOTA_MAX_POOL))
+        if not 1 <= n_top <= n_pool:
+            raise ValueError("n_top = %d, not in 1 .. n_pool = %d" % (n_top, n_pool))
+        m = abi.QUOTA_MODE.get(mode, -1) if isinstance(mode, str) else int(mode)
+        if m not in abi.QUOTA_MODE.values():
+            raise ValueError("mode = %r: one of %s" % (mode, sorted(abi.QUOTA_MODE)))
+        if m == abi.QUOTA_CAP and lab_cap is None and int(cap) < 1:
+            raise ValueError("cap = %d, not >= 1 (without lab_cap)" % int(cap))
+
+        def per_label(x, name, np_dtype):
+            if x is None:
+                return None
+            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x).astype(np_dtype)).view(np.int32))
+            if int(t.numel()) != labels.n_labels or t.element_size() != 4 or t.dtype.is_floating_point:
+                raise ValueError("%s: one 32-bit integer per label (%d), not %s %s" % (name, labels.n_labels, t.dtype, tuple(t.shape)))
+            return t.to(self.dev).contiguous()
+        return n_pool, n_top, m, int(cap), per_label(lab_cap, "lab_cap", np.int32), per_label(lab_weight, "lab_weight", np.uint32)
+
+    def _quota_outs(self, Q, n_top):
+        Q1 = max(Q, 1)
+        return [self._empty(Q1, torch.int32), self._empty((Q1, n_top), torch.int32), self._empty((Q1, n_top), torch.float64),
+                self._empty((Q1, n_top), torch.float64), self._empty((Q1, n_top), torch.int32), self._empty((Q1, n_top), torch.int32)]
+
+    def quota_pool(self, lists, labels, n_top, mode="cap", cap=1, lab_cap=None, lab_weight=None, lab_allow=None, P=None, query_user=None,
+                   n_items=None, rank_by=0):
+        """ONE list per query with a guaranteed mix of labels (xmap_quota_pool), cut from the pools `lists` = (cnt [Q], item, plain,
+        decayed [Q][n_pool], ...): what topn(), uknn_topn(), group_topn(), related(), fill() or quota_topn() returned, n_pool up to
+        1 024; position is rank.  labels: a set_labels() handle; lab_allow: the labels the quota governs (as shelves() takes it;
+        None: all).  mode "cap": at most cap entries of a label (lab_cap: one int32 cap per label instead; 0 bars a label), greedy
+        in pool order.  mode "share": the seats go to the labels by Sainte-Lague quotients of lab_weight (uint32 per label), or,
+        without it, of the history of query_user in the profiles P (rows per label).  Returns (cnt [Q], item (-1 behind the count),
+        plain, decayed, pos = the pool position of each entry, label = the claiming label ("share"; -1: a fill) or the item's
+        smallest governed label ("cap") [Q][n_top], stats = (lists that differ from the pool's prefix, entries, positions refused
+        / slots filled off-profile, "cap": lists cut short by a full pool -- widen it))."""
+        st = _stream(self.dev)
+        cnt, item, plain, decay = [x.contiguous() for x in lists[:4]]
+        Q = int(cnt.numel())
+        n_pool = int(item.shape[1]) if item.dim() == 2 else int(item.numel()) // max(Q, 1)
+        n_pool, n_top, m, cap, caps, weights = self._quota_args(labels, n_pool, n_top, mode, cap, lab_cap, lab_weight)
+        I = int(labels.n_items if n_items is None else n_items)
+        if labels.n_items != I:
+            raise ValueError("quota_pool: the label table covers %d items, the pools' id space %d" % (labels.n_items, I))
+        history = m == abi.QUOTA_SHARE and weights is None
+        if history and (P is None or query_user is None):
+            raise ValueError("quota_pool: mode \"share\" without lab_weight reads the history: P and query_user")
+        outs = self._quota_outs(Q, n_top)
+        words = self._lab_allow(labels, lab_allow)
+        h = (C.c_int64 * 4)()
+        with self.timed("quota_pool"):
+            check(lib.xmap_quota_pool(st, i64(Q), i32(n_pool), vp(cnt), vp(item), vp(plain), vp(decay), i32(rank_by), i32(m), i32(cap), vp(caps),
+                                      vp(weights), vp(query_user.contiguous() if history else None), i64(P.n_users if history else 0),
+                                      vp(P.user_ptr if history else None), vp(P.user_item if history else None), i32(I),
+                                      i32(labels.n_labels), vp(labels.ptr), vp(labels.id), vp(words), i32(n_top), *([vp(t) for t in outs] + [h])))
+        return tuple(t[:Q] for t in outs) + (tuple(int(x) for x in h),)
+
+    def quota_topn(self, P, neighbors, query_user, item_avg, wtab, labels, n_pool, n_top, mode="cap", cap=1, lab_cap=None, lab_weight=None,
+                   lab_allow=None, rank_by=0, keep_held=False, allow=None, exclude=None, min_score=None, n_items=None):
+        """The whole quota call (xmap_quota_rows): the candidates of topn() under the same eligibility rules (allow, exclude,
+        min_score), ranked into a pool of n_pool (up to 1 024) that never leaves the device, and quota_pool() over it -- the history
+        of mode "share" is the profiles P.  Returns (cnt, item, plain, decayed, pos, label, stats [10]: the six of the filtered
+        topn(), then the four of quota_pool())."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        Q = int(query_user.numel())
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        n_pool, n_top, m, cap, caps, weights = self._quota_args(labels, n_pool, n_top, mode, cap, lab_cap, lab_weight)
+        I = int(P.n_items if n_items is None else n_items)
+        if labels.n_items != I:
+            raise ValueError("quota_topn: the label table covers %d items, the tables %d" % (labels.n_items, I))
+        outs = self._quota_outs(Q, n_top)
+        words = self._lab_allow(labels, lab_allow)
+        F = alive = None
+        if allow is not None or exclude is not None or min_score is not None:
+            F, alive = self._rec_filter(I, Q, allow, exclude, min_score)
+        h = (C.c_int64 * 10)()
+        with self.timed("quota_topn"):
+            check(lib.xmap_quota_rows(st, i64(Q), vp(query_user.contiguous()), i32(n_top), i32(rank_by),
+                                      i32(abi.TOPN_KEEP_HELD if keep_held else 0), i64(P.n_users), i32(I), i32(keep), vp(cnt), vp(col), vp(sim),
+                                      vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()),
+                                      vp(wtab), i32(wtab.numel()), i32(n_pool), i32(m), i32(cap), vp(caps), vp(weights), i32(labels.n_labels),
+                                      vp(labels.ptr), vp(labels.id), vp(words), *([vp(t) for t in outs] + [None if F is None else C.byref(F), h])))
+        del alive
+        return tuple(t[:Q] for t in outs) + (tuple(int(x) for x in h),)
+
     def peers(self, index, Q, query_user, n_top, cap=1, min_common=1, same=False, keep_self=False, allow=None, exclude=None,
               min_sim=None, max_records=0):
         """Similar users on the device (xmap_peer_rows): per query user -- an index into the profiles Q, the resident ones (same

@@ -37,6 +37,9 @@ FUSE_BLOCK_RECORDS = 2048 # XMAP_FUSE_BLOCK_RECORDS: the sum of the widths up to
 FUSE_HOW = {"rrf": FUSE_RRF, "sum": FUSE_SUM, "mean": FUSE_MEAN}
 SHELF_BY_BEST, SHELF_BY_MEAN, SHELF_BY_LABEL = 0, 1, 2      # XMAP_SHELF_BY_*: `shelf_by` of xmap_shelf_rows / xmap_shelf_segments / xmap_ctx_recommend_shelves
 SHELF_MAX_LABELS = 1 << 24  # XMAP_SHELF_MAX_LABELS: labels of one table
+QUOTA_CAP, QUOTA_SHARE = 0, 1      # XMAP_QUOTA_*: `mode` of xmap_quota_pool / xmap_quota_rows / xmap_ctx_recommend_quota
+QUOTA_MAX_POOL = 1024     # XMAP_QUOTA_MAX_POOL: positions of one pool
+QUOTA_MAX_RECORDS = 8192  # XMAP_QUOTA_MAX_RECORDS: n_pool x the longest label row of the table
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -143,6 +146,7 @@ EXPORTS = [
     "xmap_pop_index", "xmap_topn_fill_rows", "xmap_ctx_popular", "xmap_ctx_recommend_filled",
     "xmap_fuse_rows", "xmap_ctx_fuse", "xmap_ctx_recommend_hybrid",
     "xmap_shelf_segments", "xmap_shelf_rows", "xmap_ctx_set_labels", "xmap_ctx_recommend_shelves",
+    "xmap_quota_pool", "xmap_quota_rows", "xmap_ctx_recommend_quota",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -215,6 +219,11 @@ def header_structs(path=HEADER_PATH):
 # `shelf_by` by name, from the header's constants (XMAP_SHELF_BY_*)
 SHELF_BY = {k[len("SHELF_BY_"):].lower(): v for k, v in header_constants(("XMAP_SHELF_BY_",)).items()}
 assert SHELF_BY == {"best": SHELF_BY_BEST, "mean": SHELF_BY_MEAN, "label": SHELF_BY_LABEL}
+# `mode` of the quota calls by name, and their limits, from the header's constants (XMAP_QUOTA_*)
+_QUOTA = header_constants(("XMAP_QUOTA_",))
+QUOTA_MODE = {k[len("QUOTA_"):].lower(): v for k, v in _QUOTA.items() if not k.startswith("QUOTA_MAX_")}
+assert QUOTA_MODE == {"cap": QUOTA_CAP, "share": QUOTA_SHARE}
+assert (_QUOTA["QUOTA_MAX_POOL"], _QUOTA["QUOTA_MAX_RECORDS"]) == (QUOTA_MAX_POOL, QUOTA_MAX_RECORDS)
 
 # argtypes of every export: a mis-ordered or mis-typed argument raises in ctypes instead of corrupting device memory
 PROTOTYPES = header_prototypes()

@@ -1,5 +1,6 @@
-"""Host helpers for the shelves (xmap_shelf_rows / xmap_ctx_set_labels of include/xmap_hip.h): the label table of an item space
-as the CSR the device calls read, and the bitmap of the labels that may form a shelf.  NumPy only."""
+"""Host helpers for the shelves and the quotas (xmap_shelf_rows / xmap_quota_rows / xmap_ctx_set_labels of include/xmap_hip.h): the
+label table of an item space as the CSR the device calls read, the bitmap of the labels that may form a shelf or that a quota
+governs, and the per-label caps / weights of a quota call.  NumPy only."""
 import numpy as np
 
 from .filters import pack_mask
@@ -45,3 +46,21 @@ def label_mask(names, chosen):
     if missing:
         raise ValueError("label_mask: %r is no label of the table" % (missing[0],))
     return pack_mask(np.asarray(sorted({at[x] for x in chosen}), np.int64), len(names))
+
+
+def label_values(names, mapping, default, dtype):
+    """The per-label array of a quota call (`lab_cap` int32, `lab_weight` uint32) over the labels `names` (label_csr's): the value
+    of `mapping` {label name: value} where it names the label, `default` elsewhere.  A name that is no label raises, as in
+    label_mask; a value the dtype does not hold raises too (a negative weight, a cap above INT32_MAX)."""
+    at = {x: k for k, x in enumerate(names)}
+    missing = [x for x in mapping if x not in at]
+    if missing:
+        raise ValueError("label_values: %r is no label of the table" % (missing[0],))
+    info = np.iinfo(dtype)
+    out = np.empty(len(names), dtype)
+    for k, x in enumerate(names):
+        v = int(mapping.get(x, default))
+        if not info.min <= v <= info.max:
+            raise ValueError("label_values: %r = %d does not fit %s" % (x, v, np.dtype(dtype).name))
+        out[k] = v
+    return out

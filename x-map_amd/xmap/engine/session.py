@@ -882,6 +882,80 @@ def recommend_shelves_profiles(alterEgoRDD, profiles, cap, keep, alpha, labels, 
     return res
 
 
+def _quota_records(st, eng2, P, nb, item_avg, query, uids, alpha, labels, n, pool, mode, at_most, per_label, weights, allow_labels, decay,
+                   keep_held, ctx, rules):
+    """what recommend_quota and recommend_quota_profiles share: the lists of the user indices `query` of P, labelled `uids` -> the
+    LocalRDD of (uid, [(iid, plain, decayed, label name or None)*]) with .stats, .cut_short and .label_names"""
+    import torch
+    from .labels import label_mask, label_values
+    idt, dev = st.idt, st.engine.dev
+    T = _shelf_labels(st, eng2, labels)
+    words = None
+    if allow_labels is not None:
+        words = label_mask(T.names, allow_labels.collect() if hasattr(allow_labels, "collect") else allow_labels)
+    caps = None if per_label is None else label_values(T.names, per_label, at_most, np.int32)
+    w = None if weights is None else label_values(T.names, weights, 0, np.uint32)
+    if w is not None and int(w.max(initial=0)) >= 1 << 31:
+        raise ValueError("recommend_quota: a weight is 2^31 or more")
+    d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
+    rank_by = 1 if decay else 0
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        out = eng2.quota_topn(P, nb, d_q, item_avg, wtab, T, pool, n, mode, at_most, caps, w, lab_allow=words, rank_by=rank_by,
+                              keep_held=keep_held, **(rules or {}))
+        if out[6][2] <= n_w:
+            break
+        n_w = out[6][2]
+    cnt, item, plain, decayed, pos, label = [x.cpu().numpy() for x in out[:6]]
+    iids = idt.iids
+    recs = [(uid, [(iids[item[q, t]], float(plain[q, t]), float(decayed[q, t]), T.names[label[q, t]] if label[q, t] >= 0 else None)
+                   for t in range(cnt[q])]) for q, uid in enumerate(uids)]
+    res = LocalRDD(recs, ctx)
+    res.stats, res.cut_short, res.label_names = out[6], out[6][9], list(T.names)
+    return res
+
+
+def recommend_quota(alterEgoRDD, users, cap, keep, alpha, labels, n, pool, mode="cap", per_label=None, weights=None, allow_labels=None,
+                    at_most=1, decay=False, keep_held=False, neighbors=None, allow_items=None, exclude=None, min_score=None):
+    """ONE list per user with a guaranteed mix of labels, on the device from an AlterEgoRDD handle: the set-up of recommend_topn,
+    then for every uid of `users` the eligible candidates of recommend_topn (allow_items, exclude, min_score as it takes them)
+    ranked into a pool of `pool` (n <= pool <= 1 024) that never leaves the device, and a list of n cut from it (Engine.quota_topn).
+    labels as recommend_shelves takes them.  mode "cap": at most at_most entries of one label, or per_label = {label name: cap}
+    (0 bars a label; a label it does not name: at_most), greedy in rank order.  mode "share": calibrated -- the seats of the list
+    go to the labels in proportion (Sainte-Lague) to weights = {label name: weight}, or, without it, to the user's own history:
+    the rows of the AlterEgo profile per label, so a user who only rated the other domain gets a list whose mix follows the mapped
+    taste.  allow_labels = the label names the quota governs (None: all).  A name that is no label raises.  Returns a LocalRDD of
+    (uid, [(iid, plain, decayed, label name or None)*]) in the order of `users` -- the name is the claiming label ("share"; None:
+    filled off-profile) or the item's first governed label ("cap") -- with .stats (the ten of Engine.quota_topn), .cut_short (the
+    "cap" lists a full pool cut short: widen `pool`) and .label_names.  A uid the train set does not know gives (uid, [])."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_quota")
+    idt = st.idt
+    uids = list(users.collect()) if hasattr(users, "collect") else list(users)
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    query = [uidx.get(uid, -1) for uid in uids]
+    return _quota_records(st, eng2, P, nb, item_avg, query, uids, alpha, labels, n, pool, mode, at_most, per_label, weights, allow_labels,
+                          decay, keep_held, getattr(users, "ctx", None),
+                          _eligibility(st.engine.dev, uids, idt.iidx, len(idt.iids), allow_items, exclude, min_score))
+
+
+def recommend_quota_profiles(alterEgoRDD, profiles, cap, keep, alpha, labels, n, pool, mode="cap", per_label=None, weights=None,
+                             allow_labels=None, at_most=1, decay=False, keep_held=False, neighbors=None, allow_items=None, exclude=None,
+                             min_score=None):
+    """recommend_quota for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them (fold-in);
+    the history of mode "share" is the folded-in profile.  Returns the LocalRDD of recommend_quota in the order of `profiles`, with
+    .stats, .cut_short, .label_names, .unknown_items and .counts."""
+    _no_fold_in(alterEgoRDD, "recommend_quota_profiles")
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_quota_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    uids = sorted(index, key=index.get)
+    res = _quota_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, labels, n, pool, mode, at_most, per_label, weights,
+                         allow_labels, decay, keep_held, getattr(profiles, "ctx", None),
+                         _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
+    res.unknown_items, res.counts = unknown, F.counts
+    return res
+
+
 def _group_records(st, eng2, P, nb, item_avg, uidx, groups, alpha, n, how, veto, decay, keep_held, ctx, allow_items, exclude, min_score):
     """what recommend_group and recommend_group_profiles share: groups = [(gid, [uid*])*] over the users of P (uidx: uid -> user
     index of P; an unknown uid stays a member without rows) -> the LocalRDD of (gid, [(iid, plain, decayed, low_uid)*]) with .stats;
