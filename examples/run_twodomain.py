@@ -6,7 +6,7 @@ code/twodomain_demo.py:31-140, which runs unmodified against x-map_amd/ when its
 /home/tlin/notebooks paths exist -- see INTEGRATION.md).  Data: synthetic Amazon-format text files written to a
 work directory (the reference ships none).
 
-    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW] [--hybrid W] [--shelves K] [--quota C] [--calibrated]]
+    python examples/run_twodomain.py [--users 3000] [--items 600] [--workdir /tmp/xmap_demo] [--private] [--user-based] [--device-tail [--fold-in] [--explain] [--audience] [--new-items] [--eligible] [--diverse W] [--groups K] [--peers N] [--user-knn K] [--related N] [--fill HOW] [--hybrid W] [--shelves K] [--quota C] [--calibrated] [--stock C]]
 
 --user-based: the recommender stages with the user method of the reference's egg (calculate_xmap_sim_method = cosine_user): the
 similarity between the users' AlterEgo profiles with its local sensitivity on the device (xmap.engine.session.UserSimRDD), the
@@ -76,6 +76,12 @@ candidates (xmap.engine.session.recommend_quota).  --calibrated: the ten seats g
 AlterEgo profile (mode="share": a user who only rated the other domain gets a list whose category mix follows the mapped taste).
 The run prints, for the test users, how many lists changed against the plain top ten and the largest share of one category in a
 list before and after.
+
+--stock C (with --device-tail): stock limits -- every item may go to at most C of the test users (C coupons per title), every user
+gets at most ten items.  The lists are cut on the device from each test user's 64 best candidates by deferred acceptance over all
+the test users at once (xmap.engine.session.recommend_allotted): an item keeps its C best offers by score, a user moves down its
+pool past the items that refused it.  The run prints how many lists changed against the plain top ten, the seats filled, the rounds
+and the share of users left short of ten.
 
 --new-items (with --device-tail): three target items are kept out of training altogether, as items that enter the catalogue
 afterwards would be.  The model is trained without them; the ratings they collected in the training period are then folded in
@@ -174,6 +180,7 @@ def main(argv=None):
     ap.add_argument("--shelves", type=int, default=None, metavar="K")
     ap.add_argument("--quota", type=int, default=None, metavar="C")
     ap.add_argument("--calibrated", action="store_true")
+    ap.add_argument("--stock", type=int, default=None, metavar="C")
     args = ap.parse_args(argv)
     para = assist.load_parameter(write_inputs(args.workdir, args.users, args.items, args.seed))
     if args.private:
@@ -224,6 +231,8 @@ def main(argv=None):
     if (args.quota is not None or args.calibrated) and (not args.device_tail or para["recommender"]["private_flag"] or
                                                         (args.quota is not None and args.quota < 1)):
         ap.error("--quota C and --calibrated need --device-tail, the non-private recommender and C >= 1")
+    if args.stock is not None and (not args.device_tail or para["recommender"]["private_flag"] or args.stock < 1):
+        ap.error("--stock C needs --device-tail, the non-private recommender and C >= 1")
     if args.peers is not None and (not args.device_tail or para["recommender"]["private_flag"] or not 1 <= args.peers <= 63):
         ap.error("--peers N needs --device-tail, the non-private recommender and 1 <= N <= 63")
     late = []                   # (uid, profile) of the users who arrive after training
@@ -454,6 +463,18 @@ def main(argv=None):
             print("%s: %d of %d lists changed; the largest share of one category in a list: mean %.2f -> %.2f, worst %.2f -> %.2f%s" % (
                 name, out.stats[6], len(test_uids), before[0], after[0], before[1], after[1],
                 "; %d lists cut short by the pool of 256" % out.cut_short if out.cut_short else ""))
+    if args.stock is not None:
+        # stock limits: every item goes to at most C of the test users -- one market over all of them
+        w, k, alpha = rc["calculate_xmap_weighting"], rc["mapping_range"], rc["decay_alpha"]
+        test_uids = [uid for uid, _ in testRDD.collect()]
+        out = timed("allotted", session.recommend_allotted, alterEgo_profile, test_uids, w, k, alpha, 10, 64, stock=args.stock)
+        lists = out.collect()
+        seats, short = sum(len(lst) for _, lst in lists), sum(1 for _, lst in lists if len(lst) < 10)
+        print("stock %d: %d of %d lists changed; %d seats filled over %d items (the fullest holds %d); %d rounds, %d offers refused; "
+              "%.1f %% of the users left short of ten%s" % (
+                  args.stock, out.changed, len(test_uids), seats, len(out.taken), max(out.taken.values()) if out.taken else 0, out.rounds,
+                  out.stats[8], 100.0 * short / max(len(test_uids), 1),
+                  "; %d lists cut short by the pool of 64" % out.cut_short if out.cut_short else ""))
     if args.shelves is not None:
         # a page of shelves per user
         page = timed("shelves", session.recommend_shelves, alterEgo_profile, [uid for uid, _ in testRDD.take(3)], w, k, alpha, cats, 4, 5)

@@ -1333,6 +1333,59 @@ int xmap_quota_rows(void *stream, int64_t n_query, const int32_t *query_user, in
                     int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_pos, int32_t *out_label,
                     const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [10] or NULL */);
 
+/* ---- allotment: top-N for many queries under item capacities (csrc/stage_e_allot.hip; DESIGN.md 4 "Allotment"): 500 coupons per
+ * title, 40 seats per event, 3 slots per newsletter -- "item i goes to at most cap(i) recipients, recipient q gets at most n_top
+ * items".  A constraint ACROSS queries, which no per-query call can honour: recipient-proposing deferred acceptance (Gale-Shapley,
+ * many-to-many) over pools that are already on the device.
+ * Inputs: Q pools in the top-N layout: in_cnt [Q], in_item / in_plain / in_decay [Q][n_pool]; rank_by 0 (plain) or 1 (decayed).
+ * Limits: 1 <= n_top <= n_pool <= XMAP_ALLOT_MAX_POOL and Q * n_pool < 2^31, else XMAP_ERR_ARG naming the argument, checked on the
+ *   host before any device work: the outputs keep every byte.
+ * Capacities: cap(i) = item_cap[i] (device int32 [n_items]), or the scalar cap >= 1 where item_cap is NULL.  A negative entry:
+ *   XMAP_ERR_ARG naming the first such item, found on the device before any other work, the outputs untouched.  0 bars the item;
+ *   INT32_MAX is no cap.
+ * Definitions: m(q) = clamp(in_cnt[q], 0, n_pool).  Position (q, j) is VOID if j >= m(q), the item is outside [0, n_items), or its
+ *   capacity is 0.  The same item at two positions of one pool is two independent positions, as in xmap_quota_pool (the scorers
+ *   never produce that).  Query users may repeat: a query is a recipient.
+ * Offer order: k(q, j) = (au_key(score), q, j), ascending lexicographically = better first; au_key (csrc/au_select.h) over the bits
+ *   of score + 0.0: b = those bits as uint64; au_key = b if its top bit is set, else ~(b | 2^63).  Defined for every bit pattern;
+ *   -0.0 equals 0.0; a larger score is better; ties go to the smaller query index, then the smaller position.
+ * Outcome: R is the SMALLEST set of refused positions such that the three statements hold together:
+ *     the proposals P(q) of each query are its first n_top positions that are neither void nor in R;
+ *     the offers of each item i are all proposals holding i;
+ *     every offer of i that is not among its cap(i) best by k is in R.
+ *   Equivalently: iterate "propose, refuse the excess, add to R" from R = {} until nothing is added; positions never leave R.  Every
+ *   query holds its best positions that no item refused, every item the cap best offers it was made: the recipient-optimal stable
+ *   assignment.  R is the least fixed point of a monotone operator, so every schedule of rounds reaches it: the outcome is a pure
+ *   function of the inputs.  No floating-point arithmetic takes part after au_key; the returned scores are the pool's own bits.
+ * Outputs (device, the top-N layout: xmap_topn_fill_rows, xmap_fuse_rows and xmap_quota_pool take them unchanged, xmap_diversify_rows
+ *   up to its 64): out_cnt[q] = |P(q)|; out_item / out_plain / out_decay / out_pos [Q][n_top] hold P(q) in ascending position (out_pos:
+ *   the pool position), -1 / 0.0 / 0.0 / -1 behind the count.  item_taken (device int32 [n_items], or NULL): the offers each item
+ *   holds.  A caller serving users in batches passes cap - taken to the next batch; BATCHING CHANGES THE OUTCOME: the batches are
+ *   not one market (an early batch keeps seats that better offers of a later batch would have won).
+ *   h_stats (host [6], or NULL; the call synchronises anyway, it reads a counter per round): [0] queries whose list is not the pool's
+ *   first min(m, n_top) positions; [1] the sum of out_cnt; [2] |R|; [3] void positions below m(q); [4] rounds run, the last empty one
+ *   included (a property of the schedule, not of the result); [5] queries with out_cnt < n_top and in_cnt >= n_pool (the pool cut
+ *   the list short: widen it).
+ * Temporaries (the stream's arena): 28 bytes per pool position, 4 per 32 positions of bitmap; every round sorts Q * n_top records of
+ *   12 bytes over all queries at once (an item's run crosses any chunking by queries).
+ * xmap_allot_pool: the back half over any pool (item-based, user-kNN up to 1 024 wide, group, related, fused lists).
+ * xmap_allot_rows: the arguments of xmap_topn_rows_filtered up to n_w -- its n_top is this call's n_pool, hence n_pool <= 64 here --
+ *   then n_top, cap, item_cap, the outputs, F, h_stats (host [12], or NULL): [0..5] the filtered call's, [6..11] the six above.  The
+ *   pool is by definition what xmap_topn_rows_filtered returns, so the eligibility rules act before the pool is cut. */
+#define XMAP_ALLOT_MAX_POOL 1024
+int xmap_allot_pool(void *stream, int64_t n_query, int32_t n_pool, const int32_t *in_cnt, const int32_t *in_item,
+                    const double *in_plain, const double *in_decay, int32_t rank_by, int32_t n_items, int32_t cap,
+                    const int32_t *item_cap /* device [n_items], or NULL */, int32_t n_top, int32_t *out_cnt, int32_t *out_item,
+                    double *out_plain, double *out_decay, int32_t *out_pos, int32_t *item_taken /* device [n_items], or NULL */,
+                    int64_t *h_stats /* host, [6] or NULL */);
+int xmap_allot_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t rank_by, int32_t flags,
+                    int64_t n_users, int32_t n_items, int32_t keep, const int32_t *nb_cnt, const int32_t *nb_col, const double *nb_sim,
+                    const int64_t *prof_ptr, const int32_t *prof_item, const double *prof_rating, const int64_t *prof_time,
+                    const double *item_avg, const double *wtab, int32_t n_w, int32_t n_top, int32_t cap,
+                    const int32_t *item_cap /* device [n_items], or NULL */, int32_t *out_cnt, int32_t *out_item, double *out_plain,
+                    double *out_decay, int32_t *out_pos, int32_t *item_taken /* device [n_items], or NULL */,
+                    const xmap_rec_filter *F /* device pointers inside, or NULL */, int64_t *h_stats /* host, [12] or NULL */);
+
 /* ---- popularity fill (csrc/stage_e_fill.hip; DESIGN.md 4 "Popularity fill"): a ranking of the items by popularity, and the
  * completion of short top-N lists with its head.  Every other list of the tail is cut from candidates with evidence; these two
  * calls answer when there is none (a user without rows, a one-rating fold-in, a 1 % mask, the anonymous visitor).
@@ -1821,6 +1874,17 @@ int xmap_ctx_recommend_quota(xmap_ctx *ctx, int32_t source, int64_t n_query, con
                              const uint32_t *lab_allow /* host words, or NULL */, int32_t *out_cnt, int32_t *out_item,
                              double *out_plain, double *out_decay, int32_t *out_pos, int32_t *out_label,
                              const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [10] or NULL */);
+/* Allotment: xmap_allot_rows over the three sources (as xmap_ctx_recommend_quota), host arrays in and out.  item_cap: host int32
+ * [n_cap], or NULL (then the scalar cap >= 1); n_cap must equal the item count of the source's tables (the resident items, plus the
+ * batch items for XMAP_SRC_ITEM_FOLDIN), which the context check holds it to.  item_taken: host int32 [n_cap items of the source], or
+ * NULL.  The outputs are those of xmap_allot_rows in host memory; stats [12].  Every argument that can be is checked on the host
+ * before the context is read, each check naming its argument (n_query, n_pool 1 .. 64, n_top, rank_by, flags, cap, a negative
+ * item_cap entry, source, a NaN floor in F): on XMAP_ERR_ARG the outputs keep every byte. */
+int xmap_ctx_recommend_allot(xmap_ctx *ctx, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top,
+                             int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t cap,
+                             const int32_t *item_cap /* host [n_cap], or NULL */, int32_t n_cap, int32_t *out_cnt, int32_t *out_item,
+                             double *out_plain, double *out_decay, int32_t *out_pos, int32_t *item_taken /* host, or NULL */,
+                             const xmap_rec_filter *F /* host pointers inside, or NULL */, int64_t *stats /* [12] or NULL */);
 int xmap_ctx_union(xmap_ctx *dst, int n_parts, xmap_ctx *const *src, const int32_t *const *user_map, const int32_t *const *item_map,
                    int64_t n_users, int32_t n_items, int flags, int64_t *counts /*[4] or NULL*/);
 int xmap_ctx_explain(xmap_ctx *ctx, int64_t n_pairs, const int32_t *pair_user, const int32_t *pair_item, int32_t rank_by,

@@ -2001,6 +2001,66 @@ int xmap_ctx_recommend_quota(xmap_ctx *c, int32_t source, int64_t n_query, const
     return XMAP_OK;
 }
 
+// ---- allotment: xmap_allot_rows over the three sources --------------------------------------------------------------------------------
+
+int xmap_ctx_recommend_allot(xmap_ctx *c, int32_t source, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top,
+                             int32_t rank_by, int32_t flags, const double *wtab, int32_t n_w, int32_t cap, const int32_t *item_cap,
+                             int32_t n_cap, int32_t *out_cnt, int32_t *out_item, double *out_plain, double *out_decay, int32_t *out_pos,
+                             int32_t *item_taken, const xmap_rec_filter *F, int64_t *stats) {
+    // the host checks: before the context is read, the outputs untouched, the context as it was
+    const char *who = "xmap_ctx_recommend_allot";
+    XM_TRY(allot_check_args(who, n_query, n_pool, 64, n_top, rank_by, flags, cap, item_cap != nullptr));
+    if (item_cap) {
+        if (n_cap < 0) { set_error("%s: n_cap = %d, not >= 0", who, n_cap); return XMAP_ERR_ARG; }
+        for (int32_t i = 0; i < n_cap; i++)
+            if (item_cap[i] < 0) {
+                set_error("%s: item_cap is negative: the first at item_cap[%d] (0 bars an item, INT32_MAX is no cap)", who, i);
+                return XMAP_ERR_ARG;
+            }
+    }
+    if (source != XMAP_SRC_RESIDENT && source != XMAP_SRC_FOLDIN && source != XMAP_SRC_ITEM_FOLDIN) {
+        set_error("%s: source = %d, not XMAP_SRC_RESIDENT, _FOLDIN or _ITEM_FOLDIN", who, source);
+        return XMAP_ERR_ARG;
+    }
+    XM_ARG(n_w >= 1 && wtab);
+    XM_ARG(n_query == 0 || (query_user && out_cnt && out_item && out_plain && out_decay && out_pos));
+    XM_TRY(check_filter(F, n_query));
+    XM_ARG(c && c->have_gen && c->have_rec && c->have_nb);
+    XM_ARG(source != XMAP_SRC_FOLDIN || c->have_fold);
+    XM_ARG(source != XMAP_SRC_ITEM_FOLDIN || c->have_ifold);
+    XM_HIP(hipSetDevice(c->device));
+    const Profiles P = source == XMAP_SRC_FOLDIN ? foldin_profiles(c) : resident_profiles(c);
+    const Tables T = source == XMAP_SRC_ITEM_FOLDIN ? itemfold_tables(c) : resident_tables(c);
+    if (item_cap && n_cap != T.n_items) {
+        set_error("%s: n_cap = %d, the tables of the source hold %d items", who, n_cap, T.n_items);
+        return XMAP_ERR_ARG;
+    }
+    ScratchPool tmp;
+    int32_t *d_cap = nullptr, *d_taken = nullptr, *d_user, *d_cnt, *d_item, *d_pos;
+    double *d_w, *d_plain, *d_decay;
+    const size_t n = (size_t)n_query, m = n * (size_t)n_top, I = (size_t)T.n_items;
+    if (item_cap) XM_TRY(h2d(tmp, &d_cap, item_cap, I, c->st));
+    if (item_taken) XM_TRY(dalloc(tmp, &d_taken, I ? I : 1, c->st));
+    XM_TRY(h2d(tmp, &d_user, query_user, n, c->st));
+    XM_TRY(h2d(tmp, &d_w, wtab, (size_t)n_w, c->st));
+    XM_TRY(dalloc(tmp, &d_cnt, n ? n : 1, c->st)); XM_TRY(dalloc(tmp, &d_item, m ? m : 1, c->st)); XM_TRY(dalloc(tmp, &d_plain, m ? m : 1, c->st));
+    XM_TRY(dalloc(tmp, &d_decay, m ? m : 1, c->st)); XM_TRY(dalloc(tmp, &d_pos, m ? m : 1, c->st));
+    xmap_rec_filter D;
+    XM_TRY(upload_filter(c, tmp, F, n_query, T.n_items, &D));
+    int64_t h12[12];
+    XM_TRY(allot_rows(c->st, n_query, d_user, n_pool, n_top, rank_by, flags, rec_model(P, T, d_w, n_w), cap, d_cap,
+                      AllotOut{d_cnt, d_item, d_plain, d_decay, d_pos, d_taken}, &D, h12));
+    XM_TRY(d2h(out_cnt, (const int32_t *)d_cnt, n, c->st));
+    XM_TRY(d2h(out_item, (const int32_t *)d_item, m, c->st));
+    XM_TRY(d2h(out_plain, (const double *)d_plain, m, c->st));
+    XM_TRY(d2h(out_decay, (const double *)d_decay, m, c->st));
+    XM_TRY(d2h(out_pos, (const int32_t *)d_pos, m, c->st));
+    if (item_taken) XM_TRY(d2h(item_taken, (const int32_t *)d_taken, I, c->st));
+    XM_HIP(hipStreamSynchronize(c->st));
+    if (stats) for (int k = 0; k < 12; k++) stats[k] = h12[k];
+    return XMAP_OK;
+}
+
 // ---- fused lists: xmap_fuse_rows over uploaded lists, and the item-based and user-based lists of the same users fused -------------
 
 int xmap_ctx_fuse(xmap_ctx *c, int64_t n_query, int32_t n_lists, const xmap_fuse_list *lists, int32_t n_ids, int32_t how, double rrf_c,

@@ -97,5 +97,17 @@ int quota_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t
 int quota_check_args(const char *who, int64_t n_query, int32_t n_pool, int32_t n_top, int32_t rank_by, int32_t flags, int32_t mode,
                      int32_t cap, bool has_lab_cap, int32_t n_labels);
 
+// stage_e_allot.hip: xmap_allot_rows; the outputs of an allot call travel as one value (device pointers)
+struct AllotOut {
+    int32_t *cnt, *item;                // [Q], [Q][n_top]
+    double *plain, *decay;              // [Q][n_top]
+    int32_t *pos, *taken;               // [Q][n_top], [n_items] or NULL
+};
+int allot_rows(void *stream, int64_t n_query, const int32_t *query_user, int32_t n_pool, int32_t n_top, int32_t rank_by, int32_t flags,
+               const RecModel &M, int32_t cap, const int32_t *item_cap, const AllotOut &O, const xmap_rec_filter *F, int64_t *h_stats);
+// the host checks of the allot calls, shared with xmap_ctx_recommend_allot: each names its argument; nothing is written
+int allot_check_args(const char *who, int64_t n_query, int32_t n_pool, int32_t max_pool, int32_t n_top, int32_t rank_by, int32_t flags,
+                     int32_t cap, bool has_item_cap);
+
 }  // namespace xmap
 #endif

@@ -320,7 +320,7 @@ static int exclusive_scan(hipStream_t st, int n_arrays, const TIn *in0, const TI
 
 extern "C" {
 const char *xmap_last_error(void) { return xmap::g_err; }
-int xmap_version(void) { return 124; }
+int xmap_version(void) { return 125; }
 
 /* The library's temporaries: give every idle arena's memory of the calling thread back to the driver (arenas with live
  * temporaries are left alone).  Synchronises the device. */

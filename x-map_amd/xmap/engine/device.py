@@ -123,6 +123,16 @@ class LabelTable(object):
     pass
 
 
+class AllotLists(tuple):
+    """what allot_pool() / allot_topn() return: the tuple (cnt, item, plain, decayed) of every list call, with .positions, .taken
+    and .stats"""
+
+    def __new__(cls, lists, positions, taken, stats):
+        self = tuple.__new__(cls, lists)
+        self.positions, self.taken, self.stats = positions, taken, stats
+        return self
+
+
 class GenResult(object):
     pass
 
@@ -2255,6 +2265,80 @@ class Engine(object):
                                       vp(labels.ptr), vp(labels.id), vp(words), *([vp(t) for t in outs] + [None if F is None else C.byref(F), h])))
         del alive
         return tuple(t[:Q] for t in outs) + (tuple(int(x) for x in h),)
+
+    def _allot_args(self, n_pool, max_pool, n_top, cap, item_cap, n_items, rank_by):
+        """the checked scalars of an allot call and its capacities on the device (None, a tensor or an array [n_items])"""
+        n_pool, n_top, cap = int(n_pool), int(n_top), int(cap)
+        if not 1 <= n_pool <= max_pool:
+            raise ValueError("n_pool = %d: a pool takes 1 .. %d positions" % (n_pool, max_pool))
+        if not 1 <= n_top <= n_pool:
+            raise ValueError("n_top = %d, not in 1 .. n_pool = %d" % (n_top, n_pool))
+        if rank_by not in (0, 1):
+            raise ValueError("rank_by = %r, not 0 or 1" % (rank_by,))
+        if item_cap is None:
+            if cap < 1:
+                raise ValueError("cap = %d, not >= 1 (without item_cap)" % cap)
+            return n_pool, n_top, cap, None
+        t = item_cap if torch.is_tensor(item_cap) else torch.from_numpy(np.ascontiguousarray(np.asarray(item_cap).astype(np.int32)))
+        if int(t.numel()) != n_items or t.dtype != torch.int32:
+            raise ValueError("item_cap: one int32 per item (%d), not %s %s" % (n_items, t.dtype, tuple(t.shape)))
+        return n_pool, n_top, cap, t.to(self.dev).contiguous()
+
+    def _allot_outs(self, Q, n_top, n_items):
+        Q1 = max(Q, 1)
+        return [self._empty(Q1, torch.int32), self._empty((Q1, n_top), torch.int32), self._empty((Q1, n_top), torch.float64),
+                self._empty((Q1, n_top), torch.float64), self._empty((Q1, n_top), torch.int32), self._empty(max(n_items, 1), torch.int32)]
+
+    def allot_pool(self, lists, n_top, cap=1, item_cap=None, rank_by=0, n_items=None):
+        """Top-N for many queries under item capacities (xmap_allot_pool): item i goes to at most cap(i) of the queries, every
+        query gets at most n_top items -- recipient-proposing deferred acceptance over the pools `lists` = (cnt [Q], item, plain,
+        decayed [Q][n_pool], ...): what topn(), uknn_topn(), group_topn(), related(), fill(), fuse-like lists returned, n_pool up
+        to 1 024; position is rank.  cap: one capacity for every item, or item_cap: an int32 per item (0 bars an item, 2^31 - 1 is
+        no cap).  An item keeps its best offers by the rank_by score (ties: the smaller query index, then the smaller position).
+        n_items: the size of the pools' id space (default: item_cap's length, else the largest id + 1).  Returns an AllotLists: the
+        tuple (cnt [Q], item (-1 behind the count), plain, decayed [Q][n_top]) that fill(), fuse() and quota_pool() take, with
+        .positions (the pool position of each entry), .taken (offers held per item [n_items]: a caller serving users in batches
+        passes cap - taken on -- the batches are not one market) and .stats = (lists that differ from the pool's prefix,
+        entries, positions refused, void positions, rounds, lists cut short by a full pool -- widen it)."""
+        st = _stream(self.dev)
+        cnt, item, plain, decay = [x.contiguous() for x in lists[:4]]
+        Q = int(cnt.numel())
+        n_pool = int(item.shape[1]) if item.dim() == 2 else int(item.numel()) // max(Q, 1)
+        if n_items is None:
+            n_items = len(item_cap) if item_cap is not None else (int(item.max()) + 1 if item.numel() else 0)
+        I = max(int(n_items), 0)
+        n_pool, n_top, cap, caps = self._allot_args(n_pool, abi.ALLOT_MAX_POOL, n_top, cap, item_cap, I, rank_by)
+        outs = self._allot_outs(Q, n_top, I)
+        h = (C.c_int64 * 6)()
+        with self.timed("allot_pool"):
+            check(lib.xmap_allot_pool(st, i64(Q), i32(n_pool), vp(cnt), vp(item), vp(plain), vp(decay), i32(rank_by), i32(I), i32(cap),
+                                      vp(caps), i32(n_top), *([vp(t) for t in outs] + [h])))
+        return AllotLists([t[:Q] for t in outs[:4]], outs[4][:Q], outs[5][:I], tuple(int(x) for x in h))
+
+    def allot_topn(self, P, neighbors, query_user, item_avg, wtab, n_pool, n_top, cap=1, item_cap=None, rank_by=0, keep_held=False,
+                   allow=None, exclude=None, min_score=None, n_items=None):
+        """The whole allot call (xmap_allot_rows): the pool of every query is what topn() returns with n_top = n_pool (1 .. 64)
+        under the same eligibility rules (allow, exclude, min_score), never leaving the device, and allot_pool() over the pools.
+        Returns the AllotLists of allot_pool() with .stats [12]: the six of the filtered topn(), then the six of allot_pool()."""
+        st = _stream(self.dev)
+        cnt, col, sim = [x.contiguous() for x in neighbors[:3]]
+        Q = int(query_user.numel())
+        keep = int(col.shape[1]) if col.dim() == 2 else 1
+        I = int(P.n_items if n_items is None else n_items)
+        n_pool, n_top, cap, caps = self._allot_args(n_pool, 64, n_top, cap, item_cap, I, rank_by)
+        outs = self._allot_outs(Q, n_top, I)
+        F = alive = None
+        if allow is not None or exclude is not None or min_score is not None:
+            F, alive = self._rec_filter(I, Q, allow, exclude, min_score)
+        h = (C.c_int64 * 12)()
+        with self.timed("allot_topn"):
+            check(lib.xmap_allot_rows(st, i64(Q), vp(query_user.contiguous()), i32(n_pool), i32(rank_by),
+                                      i32(abi.TOPN_KEEP_HELD if keep_held else 0), i64(P.n_users), i32(I), i32(keep), vp(cnt), vp(col), vp(sim),
+                                      vp(P.user_ptr), vp(P.user_item), vp(P.user_rating64), vp(P.user_time), vp(item_avg.contiguous()),
+                                      vp(wtab), i32(wtab.numel()), i32(n_top), i32(cap), vp(caps),
+                                      *([vp(t) for t in outs] + [None if F is None else C.byref(F), h])))
+        del alive
+        return AllotLists([t[:Q] for t in outs[:4]], outs[4][:Q], outs[5][:I], tuple(int(x) for x in h))
 
     def peers(self, index, Q, query_user, n_top, cap=1, min_common=1, same=False, keep_self=False, allow=None, exclude=None,
               min_sim=None, max_records=0):

@@ -40,6 +40,7 @@ SHELF_MAX_LABELS = 1 << 24  # XMAP_SHELF_MAX_LABELS: labels of one table
 QUOTA_CAP, QUOTA_SHARE = 0, 1      # XMAP_QUOTA_*: `mode` of xmap_quota_pool / xmap_quota_rows / xmap_ctx_recommend_quota
 QUOTA_MAX_POOL = 1024     # XMAP_QUOTA_MAX_POOL: positions of one pool
 QUOTA_MAX_RECORDS = 8192  # XMAP_QUOTA_MAX_RECORDS: n_pool x the longest label row of the table
+ALLOT_MAX_POOL = 1024     # XMAP_ALLOT_MAX_POOL: positions of one pool of xmap_allot_pool (xmap_allot_rows / xmap_ctx_recommend_allot: 64)
 GROUP_HOW = {"mean": GROUP_MEAN, "min": GROUP_MIN, "max": GROUP_MAX}
 UNION_DISTINCT = 1        # XMAP_UNION_DISTINCT: flag of xmap_union_count / xmap_union_fill / xmap_ctx_union
 UNION_MAX_PARTS = 16
@@ -147,6 +148,7 @@ EXPORTS = [
     "xmap_fuse_rows", "xmap_ctx_fuse", "xmap_ctx_recommend_hybrid",
     "xmap_shelf_segments", "xmap_shelf_rows", "xmap_ctx_set_labels", "xmap_ctx_recommend_shelves",
     "xmap_quota_pool", "xmap_quota_rows", "xmap_ctx_recommend_quota",
+    "xmap_allot_pool", "xmap_allot_rows", "xmap_ctx_recommend_allot",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -224,6 +226,8 @@ _QUOTA = header_constants(("XMAP_QUOTA_",))
 QUOTA_MODE = {k[len("QUOTA_"):].lower(): v for k, v in _QUOTA.items() if not k.startswith("QUOTA_MAX_")}
 assert QUOTA_MODE == {"cap": QUOTA_CAP, "share": QUOTA_SHARE}
 assert (_QUOTA["QUOTA_MAX_POOL"], _QUOTA["QUOTA_MAX_RECORDS"]) == (QUOTA_MAX_POOL, QUOTA_MAX_RECORDS)
+
+assert header_constants(("XMAP_ALLOT_",)) == {"ALLOT_MAX_POOL": ALLOT_MAX_POOL}
 
 # argtypes of every export: a mis-ordered or mis-typed argument raises in ctypes instead of corrupting device memory
 PROTOTYPES = header_prototypes()

@@ -956,6 +956,78 @@ def recommend_quota_profiles(alterEgoRDD, profiles, cap, keep, alpha, labels, n,
     return res
 
 
+def _allot_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, pool, stock, per_item, decay, keep_held, ctx, rules):
+    """what recommend_allotted and recommend_allotted_profiles share: the lists of the user indices `query` of P, labelled `uids` ->
+    the LocalRDD of (uid, [(iid, plain, decayed)*]) with .positions, .taken, .stats, .changed, .rounds and .cut_short"""
+    import torch
+    idt, dev = st.idt, st.engine.dev
+    caps = None
+    if per_item is not None:
+        per_item = dict(per_item.collect() if hasattr(per_item, "collect") else per_item)
+        unknown = [i for i in per_item if i not in idt.iidx]
+        if unknown:
+            raise ValueError("recommend_allotted: per_item names %d items the train set does not know, e.g. %r" % (len(unknown), unknown[0]))
+        caps = np.full(len(idt.iids), int(stock), np.int64)
+        for iid, c in per_item.items():
+            caps[idt.iidx[iid]] = int(c)
+        if caps.min(initial=0) < 0 or caps.max(initial=0) > 2 ** 31 - 1:
+            raise ValueError("recommend_allotted: a capacity is negative or above 2^31 - 1")
+        caps = caps.astype(np.int32)
+    d_q = torch.from_numpy(np.fromiter(query, np.int32, len(uids))).to(dev)
+    n_w = 66
+    while True:
+        wtab = _decay_table(alpha, n_w, dev)
+        out = eng2.allot_topn(P, nb, d_q, item_avg, wtab, pool, n, cap=stock, item_cap=caps, rank_by=1 if decay else 0, keep_held=keep_held,
+                              **(rules or {}))
+        if out.stats[2] <= n_w:
+            break
+        n_w = out.stats[2]
+    cnt, item, plain, decayed = [x.cpu().numpy() for x in out]
+    pos, taken = out.positions.cpu().numpy(), out.taken.cpu().numpy()
+    iids = idt.iids
+    res = LocalRDD([(uid, [(iids[item[q, t]], float(plain[q, t]), float(decayed[q, t])) for t in range(cnt[q])]) for q, uid in enumerate(uids)],
+                   ctx)
+    res.positions = [pos[q, :cnt[q]].tolist() for q in range(len(uids))]
+    res.taken = {iids[i]: int(taken[i]) for i in np.nonzero(taken)[0]}
+    res.stats, res.changed, res.rounds, res.cut_short = out.stats, out.stats[6], out.stats[10], out.stats[11]
+    return res
+
+
+def recommend_allotted(alterEgoRDD, users, cap, keep, alpha, n, pool, stock=1, per_item=None, decay=False, keep_held=False, neighbors=None,
+                       allow_items=None, exclude=None, min_score=None):
+    """Top-n under stock limits, on the device from an AlterEgoRDD handle: item i goes to at most stock (or per_item[iid]) of the
+    `users`, every user gets at most n items.  The set-up of recommend_topn; the pool of every uid is its recommend_topn list of
+    `pool` entries (n <= pool <= 64; allow_items, exclude, min_score as recommend_topn takes them), and the lists are the
+    recipient-optimal stable assignment over all the users at once (Engine.allot_topn): an item keeps its best offers by score, a
+    user moves down its pool past the items that refused it.  per_item = {iid: capacity} (0 bars an item; an item it does not name:
+    stock).  `users` are ONE market: serving them in batches with stock - taken handed on gives another, batch-order-dependent
+    outcome.  Returns a LocalRDD of (uid, [(iid, plain, decayed)*]) in the order of `users` with .positions (the pool position of
+    each entry), .taken ({iid: offers held}), .stats (the twelve of Engine.allot_topn), .changed (lists that differ from the plain
+    top-n), .rounds and .cut_short (lists a full pool cut short: widen `pool`).  A uid the train set does not know gives (uid, [])."""
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_allotted")
+    idt = st.idt
+    uids = list(users.collect()) if hasattr(users, "collect") else list(users)
+    uidx = getattr(idt, "uidx", None) or {u: k for k, u in enumerate(idt.uids)}
+    query = [uidx.get(uid, -1) for uid in uids]
+    return _allot_records(st, eng2, P, nb, item_avg, query, uids, alpha, n, pool, stock, per_item, decay, keep_held, getattr(users, "ctx", None),
+                          _eligibility(st.engine.dev, uids, idt.iidx, len(idt.iids), allow_items, exclude, min_score))
+
+
+def recommend_allotted_profiles(alterEgoRDD, profiles, cap, keep, alpha, n, pool, stock=1, per_item=None, decay=False, keep_held=False,
+                                neighbors=None, allow_items=None, exclude=None, min_score=None):
+    """recommend_allotted for users that are not rows of the train set: `profiles` as recommend_topn_profiles takes them (fold-in); the
+    batch is one market.  Returns the LocalRDD of recommend_allotted in the order of `profiles`, with .unknown_items and .counts."""
+    _no_fold_in(alterEgoRDD, "recommend_allotted_profiles")
+    st, eng2, P, S, nb, item_avg = _tail_setup(alterEgoRDD, cap, keep, neighbors, "recommend_allotted_profiles")
+    F, index, unknown = _fold_in(st, alterEgoRDD.G, profiles)
+    uids = sorted(index, key=index.get)
+    res = _allot_records(st, eng2, F, nb, item_avg, range(len(uids)), uids, alpha, n, pool, stock, per_item, decay, keep_held,
+                         getattr(profiles, "ctx", None),
+                         _eligibility(st.engine.dev, uids, st.idt.iidx, len(st.idt.iids), allow_items, exclude, min_score))
+    res.unknown_items, res.counts = unknown, F.counts
+    return res
+
+
 def _group_records(st, eng2, P, nb, item_avg, uidx, groups, alpha, n, how, veto, decay, keep_held, ctx, allow_items, exclude, min_score):
     """what recommend_group and recommend_group_profiles share: groups = [(gid, [uid*])*] over the users of P (uidx: uid -> user
     index of P; an unknown uid stays a member without rows) -> the LocalRDD of (gid, [(iid, plain, decayed, low_uid)*]) with .stats;
