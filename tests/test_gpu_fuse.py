@@ -358,6 +358,15 @@ def test_the_hybrid_call_equals_the_three_coarse_calls_composed():
                 assert got[0].sum() > 0
                 masks_seen |= set(np.unique(got[3]).tolist())
         assert masks_seen >= {0, 1, 2, 3}
+        # no queries, on both sources: the three calls return their stats zeroed and start nothing; the composition still holds
+        for source in (0, 1):
+            none = np.arange(0)
+            rc, got = _ctx_hybrid(ctx, source, none, 4, 8, 0, 0, w, 8, 5, 0, 1, 1, 0, 1, 1.0, 1.0, RRF, 60.0, 1, None)
+            assert rc == 0 and got[4] == [0] * 17, ctx.lib.xmap_last_error()
+            rc, a = _coarse(ctx, "xmap_ctx_recommend_filtered", source, none, 8, 0, 0, Filter(null=True), alpha=1.5)
+            assert rc == 0 and a[4] == [0] * 6, ctx.lib.xmap_last_error()
+            rc, b = _ctx_recommend(ctx, source, none, 5, 8, 0, 1, 1, 0, 1, None)
+            assert rc == 0 and b[4] == [0] * 6 and got[4] == a[4] + b[4] + [0] * 5, ctx.lib.xmap_last_error()
         # every host check: XMAP_ERR_ARG naming its argument, the outputs keep every byte
         good = dict(source=0, n_top=5, pool_i=10, rank_by=0, tflags=0, w=w, pool_u=10, n_nb=5, pf=0, cap=1, mc=1, uflags=0, ms=1, wi=1.0, wu=1.0,
                     how=RRF, rrf_c=60.0, min_lists=1, filt=None)

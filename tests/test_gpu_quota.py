@@ -576,6 +576,15 @@ def test_the_coarse_call_over_the_three_sources():
         assert small.any()
         assert got[0][small].tobytes() == ref[0][small].tobytes() and got[1][small].tobytes() == ref[1][small].tobytes()
         assert got[2][small].tobytes() == ref[2][small].tobytes() and (got[5] == -1).all()
+        # ---- the extended table beside a lab_allow: with every label allowed the same statement holds; no queries: the stats zeroed
+        few = qs_[np.flatnonzero(small)[:8]]
+        ref = _ctx_filtered(ctx, 2, few, 4, 0, 0, abi.RecFilter(words.ctypes.data, None, None, -np.inf))
+        rc, msg, got, stats = _ctx_quota(ctx, 2, few, 300, 4, 0, 0, CAP, lab_cap=np.zeros(7, np.int32), lab_allow=np.ones(7, bool))
+        assert rc == 0, msg
+        assert got[0].tobytes() == ref[0].tobytes() and got[1].tobytes() == ref[1].tobytes()
+        assert got[2].tobytes() == ref[2].tobytes() and (got[5] == -1).all()
+        rc, msg, got, stats = _ctx_quota(ctx, 2, few[:0], 300, 4, 0, 0, CAP, lab_allow=np.ones(7, bool))
+        assert rc == 0 and stats == [0] * 10, msg
     finally:
         ctx.close()
 

@@ -422,6 +422,15 @@ def test_the_coarse_calls_over_the_three_sources():
                     s = int(at[0])
                     assert s_cnt[q, s] == ref[0][q] and item[q, s].tobytes() == ref[1][q].tobytes()
                     assert s_plain[q, s].tobytes() == ref[2][q].tobytes() and s_decay[q, s].tobytes() == ref[3][q].tobytes()
+        # ---- the extended table beside a lab_allow: every label allowed is the bytes of lab_allow NULL, which the lists above are
+        # the first rows of; no queries: the stats zeroed, nothing else
+        few = _ctx_shelves(ctx, 2, qs[:8], 7, 4, 0, 0, LABEL, 1)
+        every = _ctx_shelves(ctx, 2, qs[:8], 7, 4, 0, 0, LABEL, 1, np.ones(7, bool))
+        assert few[0] == 0 and every[0] == 0, (few[1], every[1])
+        assert [a.tobytes() for a in every[2]] == [a.tobytes() for a in few[2]] and every[3] == few[3]
+        assert np.array_equal(few[2][1], label[:8]) and np.array_equal(few[2][5], item[:8, :, :4]) and few[2][0].max() > 1
+        rc, msg, none, stats = _ctx_shelves(ctx, 2, qs[:0], 7, 4, 0, 0, LABEL, 1, np.ones(7, bool))
+        assert rc == 0 and stats == [0] * 10, msg
         # ---- a table that fails leaves the earlier one in place; a second call replaces it; n_labels = 0 drops it
         before = _ctx_shelves(ctx, 0, qs, 3, 10, 0, 0, BEST, 1)
         bad = Labels(I, 7, labels.ptr, np.where(np.arange(len(labels.id)) == 4, 7, labels.id))

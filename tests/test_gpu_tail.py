@@ -1,6 +1,6 @@
 """The device-resident recommender tail: AlterEgo rows -> user-major profiles -> RecommenderSim -> neighbour selection ->
 prediction with temporal decay -> MAE, without a host conversion (csrc/stage_e_rows.hip, the xmap_ctx_rec_* / xmap_ctx_predict
-calls of csrc/api.hip, Engine.alterego_profiles / predict / mae, session.recommend).
+calls of csrc/api.hip and csrc/api_tail.hip, Engine.alterego_profiles / predict / mae, session.recommend).
 
 The coarse side is driven as a foreign host drives it (NumPy through ctypes, no torch).  RecommenderSim and the selection
 are compared bit for bit with the CPU oracle; the prediction with the Python statement of the reference

@@ -1,8 +1,8 @@
 // rec_model.h -- the model the recommender tail reads, as ONE value inside the library: user-major profiles, neighbour lists
 // [n_items][keep], item averages and the decay table.  The fine-grained extern "C" entries (include/xmap_hip.h) take these as
 // 13 separate arguments; each builds a RecModel from them on its first line -- the fields stand in the order of those
-// arguments -- and everything below an entry takes the struct, as do the coarse calls of api.hip, which build it once per call
-// from their profiles and tables.  Host code only: the kernels keep their parameter lists.
+// arguments -- and everything below an entry takes the struct, as do the coarse calls of api_tail.hip and api_lists.hip,
+// which build it once per call from their profiles and tables (ctx.h).  Host code only: the kernels keep their parameter lists.
 #ifndef XMAP_REC_MODEL_H
 #define XMAP_REC_MODEL_H
 #include "common.h"
@@ -32,8 +32,8 @@ static inline int rec_model_check(const RecModel &M) {
     return XMAP_OK;
 }
 
-// The bodies of the fine-grained entries, which the coarse calls of api.hip share.  Pointers are device pointers; the
-// arguments, outputs, h_stats and sync points are those of the entry of the same name in include/xmap_hip.h.
+// The bodies of the fine-grained entries, which the coarse calls of api_tail.hip and api_lists.hip share.  Pointers are device
+// pointers; the arguments, outputs, h_stats and sync points are those of the entry of the same name in include/xmap_hip.h.
 // stage_e_rows.hip: xmap_predict_rows
 int predict_rows(void *stream, int64_t n_test, const int32_t *test_user, const int32_t *test_item, const RecModel &M, double *out_plain,
                  double *out_decay, int32_t *status, int32_t *h_max_now);
